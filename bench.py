@@ -16,6 +16,13 @@ Workloads (weak scaling: per-GPU work is fixed as N grows):
              each, same samples; rank r renders prompts shard_prompts(8 N, r, N).
 Inputs are resident in HBM before the timed region.  Prints ONE JSON line on rank 0.  Every number of the line can be
 recomputed from profiles/ with the arithmetic in profiles/README.md.
+
+A plain run sets up, warms up, times the K steps and prints the headline (metric, value, unit, higher_is_better, dtype,
+ms_per_step).  --full adds everything else the line used to carry: per-kernel HIP-event timings and rooflines, the
+work-accounting step, the ray-march roofline, the rocprofv3 --pmc child passes, the sustained window, the other precision
+modes, the secondary workloads, the all-reduce timing (N > 1) and the CPU baseline (--no-pmc / --no-extras /
+--no-cpu-baseline drop parts of it).  --dump-outputs DIR writes what the timed path computed in its last step (loss,
+render outputs, gradients) as DIR/<name>.npy: same arguments, same inputs, so two builds can be compared output for output.
 """
 import argparse
 import csv
@@ -716,6 +723,7 @@ def run_config2(args, device, rank, world, dist):
             (("comp_rgb", 3), ("opacity", 1), ("depth", 1), ("comp_normal_cam_vis", 3))}
     te = torch.zeros(P, 77, 1024)
     params = list(geo.parameters())
+    last = {}  # --dump-outputs: the render outputs of the latest pass
 
     def step():
         for p_ in params:
@@ -728,6 +736,8 @@ def run_config2(args, device, rank, world, dist):
                 ops.eikonal_loss(out["sdf_grad"])
             (loss / PARTS).backward()
             total = total + loss.detach()
+            if args.dump_outputs:
+                last["out"] = out
         if world > 1:  # the renderer-side parameters' gradients: one flat all-reduce per step
             from triplaneturbo_amd.parallel import allreduce_mlp_grads
             allreduce_mlp_grads(params, dist)
@@ -741,7 +751,8 @@ def run_config2(args, device, rank, world, dist):
     for _ in range(args.warmup):
         loss = step()
     timer = ops.KernelTimer()
-    ops.set_kernel_timer(timer)
+    if args.full:  # per-launch HIP events in the timed steps: the per-kernel figures of --full
+        ops.set_kernel_timer(timer)
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -749,6 +760,10 @@ def run_config2(args, device, rank, world, dist):
     barrier()
     dt = time.perf_counter() - t0
     ops.set_kernel_timer(None)
+    if args.dump_outputs and rank == 0:
+        grads = {f"grad_planes{i}": c.grad for i, c in enumerate(caches)}
+        grads.update({"grad_" + n.replace(".", "_"): p_.grad for n, p_ in geo.named_parameters() if p_.grad is not None})
+        dump_outputs(args.dump_outputs, render_dump(loss, last["out"], grads))
     if world > 1:
         tmax = torch.tensor([dt], device=device, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -758,27 +773,6 @@ def run_config2(args, device, rank, world, dist):
     rays_render = P * NV * (42 * 42 + 40 * 40)           # rays marched per render (global + patch)
     rays_step = rays_render * PARTS
     S, S_PROP = 193, 128
-    torch.cuda.synchronize()
-    per_step = {}
-    for label, a, b in timer.events:
-        per_step[label] = per_step.get(label, 0.0) + a.elapsed_time(b) / args.steps
-    n_s = rays_step * S
-    kernels = {k: kernel_roofline(k, per_step[k], n_s, args.precision) for k in ALG if k in per_step}
-    if "tt_decode_rays" in per_step:
-        ALG["tt_decode_rays"] = ALG_PROPOSAL
-        kernels["tt_decode_rays"] = kernel_roofline("tt_decode_rays", per_step["tt_decode_rays"], rays_step * S_PROP, args.precision)
-    for k, v in kernels.items():
-        v["launches_per_step"] = sum(1 for lab, _, _ in timer.events if lab == k) // args.steps
-        v["note"] = "sum over the launches of one step (4 parts x 2 renders), samples = rays x 193 (proposal: x 128)"
-    dom = max((k for k in kernels), key=lambda k: kernels[k]["avg_ms"])
-    kd = kernels[dom]
-    roofline = {"kernel": dom, "bound": "mfma" if kd["bound_8d"] == "mfma" else "hbm",
-                "achieved": kd["alg_tflops"] if kd["bound_8d"] == "mfma" else kd["alg_GBs"],
-                "peak": PEAK_F32_TFLOPS if kd["bound_8d"] == "mfma" else PEAK_HBM_GBS,
-                "unit": "TFLOP/s" if kd["bound_8d"] == "mfma" else "GB/s", "frac": kd["frac_8d"],
-                "frac_pipe_mix": kd["frac_pipe_mix"], "avg_kernel_ms": kd["avg_ms"], "traffic": None,
-                "definition": "frac_8d over the summed launches of one step (see --config 1 for the per-launch form, the SQ / "
-                              "PMC counters and the executed-work fractions)"}
     ms = dt / args.steps * 1e3
     line = {"metric": "rendered rays/sec (fwd+bwd), BASELINE configs[2]: 8 prompts x 4 views, 128x128 rays, PatchRenderer, "
                       "193 importance samples, 4 render+backward passes per step",
@@ -792,14 +786,37 @@ def run_config2(args, device, rank, world, dist):
                        "rays_marched_per_render": rays_render, "rays_per_step": rays_step, "image_pixels_per_step": P * NV * H * W * PARTS,
                        "samples_per_ray": S, "proposal_samples_per_ray": S_PROP, "parallelism": f"dp{world}",
                        "ms_per_render_fwd_bwd": round(ms / PARTS, 3), "loss": float(loss)},
-            "roofline": roofline, "kernels": kernels,
-            "other_entry_points_ms_per_step": {k: round(v, 4) for k, v in per_step.items() if k not in kernels},
-            "glue_ms": round(ms - sum(per_step.values()), 3), "timed_region_s": round(dt, 3)}
+            "timed_region_s": round(dt, 3), "full": args.full}
     if world > 1:
         if dist.get_world_size() != args.gpus:
             raise SystemExit(f"bench.py: --gpus {args.gpus} but the process group has {dist.get_world_size()} ranks")
         line["multi_gpu"] = {"rccl": {"backend": dist.get_backend(), "world_size": dist.get_world_size()},
                              "note": "one flat all-reduce of the renderer-side MLP gradients per step (allreduce_mlp_grads)"}
+    if args.full:
+        torch.cuda.synchronize()
+        per_step = {}
+        for label, a, b in timer.events:
+            per_step[label] = per_step.get(label, 0.0) + a.elapsed_time(b) / args.steps
+        n_s = rays_step * S
+        kernels = {k: kernel_roofline(k, per_step[k], n_s, args.precision) for k in ALG if k in per_step}
+        if "tt_decode_rays" in per_step:
+            ALG["tt_decode_rays"] = ALG_PROPOSAL
+            kernels["tt_decode_rays"] = kernel_roofline("tt_decode_rays", per_step["tt_decode_rays"], rays_step * S_PROP, args.precision)
+        for k, v in kernels.items():
+            v["launches_per_step"] = sum(1 for lab, _, _ in timer.events if lab == k) // args.steps
+            v["note"] = "sum over the launches of one step (4 parts x 2 renders), samples = rays x 193 (proposal: x 128)"
+        dom = max((k for k in kernels), key=lambda k: kernels[k]["avg_ms"])
+        kd = kernels[dom]
+        roofline = {"kernel": dom, "bound": "mfma" if kd["bound_8d"] == "mfma" else "hbm",
+                    "achieved": kd["alg_tflops"] if kd["bound_8d"] == "mfma" else kd["alg_GBs"],
+                    "peak": PEAK_F32_TFLOPS if kd["bound_8d"] == "mfma" else PEAK_HBM_GBS,
+                    "unit": "TFLOP/s" if kd["bound_8d"] == "mfma" else "GB/s", "frac": kd["frac_8d"],
+                    "frac_pipe_mix": kd["frac_pipe_mix"], "avg_kernel_ms": kd["avg_ms"], "traffic": None,
+                    "definition": "frac_8d over the summed launches of one step (see --config 1 for the per-launch form, the SQ / "
+                                  "PMC counters and the executed-work fractions)"}
+        line.update(roofline=roofline, kernels=kernels,
+                    other_entry_points_ms_per_step={k: round(v, 4) for k, v in per_step.items() if k not in kernels},
+                    glue_ms=round(ms - sum(per_step.values()), 3))
     if world == 1 and not args.no_cpu_baseline:
         cb = cpu_baseline(S=193)
         cb["sample"] += "; stand-in for configs[2]: the same oracle pass with 193 (uniform) samples per ray -- the CPU cost per ray " \
@@ -884,7 +901,8 @@ def run_config4(args, device):
         torch.cuda.synchronize()
         return
     timer = ops.KernelTimer()
-    ops.set_kernel_timer(timer)
+    if args.full:  # per-launch HIP events in the timed steps: the per-kernel figures of --full
+        ops.set_kernel_timer(timer)
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -897,37 +915,8 @@ def run_config4(args, device):
     ops.set_kernel_timer(None)
     sdf, deform, col = out
     assert sdf.shape == (1, RES ** 3, 1) and deform.shape == (1, RES ** 3, 3) and col.shape == (1, N_V, 3)
-    n_pts = {"tt_query_field": RES ** 3, "tt_query_points": N_V}
-    ksum = timer.summary(median=True)
-    kernels = {k: dict(kernel_roofline(k, ms, n_pts[k], args.precision), launches=n, points_per_launch=n_pts[k],
-                       points_per_s=round(n_pts[k] / (ms * 1e-3), 1))
-               for k, (ms, n) in ksum.items() if k in n_pts}
-    traffic, traffic_err = (None, "skipped (--no-pmc)") if args.no_pmc else pmc_traffic(4, args.precision)
-    pipes, pipes_err = (None, "skipped (--no-pmc)") if args.no_pmc else pmc_pipes(4, args.precision)
-    cch, cch_err = (None, "skipped (--no-pmc)") if args.no_pmc else pmc_cache(4, args.precision)
-    for k, vv in kernels.items():
-        dk = ALG_POINTS[k]["device_kernel"]
-        if cch and dk in cch:
-            vv["cache"] = dict(cch[dk], kernel=dk,
-                               l2_request_GBs_at_128B=round(cch[dk]["l2_request_bytes_at_128B"] / (vv["avg_ms"] * 1e-3) / 1e9, 1))
-        if traffic and dk in traffic:
-            vv["pmc"] = dict(traffic[dk], kernel=dk)
-        if pipes and dk in pipes:
-            vv["sq"] = dict(pipes[dk], kernel=dk)
-    dom = max(kernels, key=lambda k: kernels[k]["avg_ms"])
-    kd = kernels[dom]
-    roofline = {"kernel": dom, "bound": "mfma", "achieved": kd["alg_tflops"], "peak": PEAK_F32_TFLOPS, "unit": "TFLOP/s",
-                "frac": kd["frac_8d"], "definition": "frac_8d (SURVEY 8(d)'s fp32-MFMA roofline, as in --config 1)",
-                "frac_pipe_mix": kd["frac_pipe_mix"], "frac_real": kd.get("frac_real"), "bound_real": kd.get("bound_real"),
-                "gather": kd.get("gather"), "cache": kd.get("cache"), "avg_kernel_ms": kd["avg_ms"],
-                "mfma_util": (kd.get("sq") or {}).get("mfma_util"), "valu_util": (kd.get("sq") or {}).get("valu_util"),
-                "waves_per_simd": (kd.get("sq") or {}).get("waves_per_simd"),
-                "traffic": (kd.get("pmc") or {}).get("bytes"),
-                "traffic_source": ("two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of this script in this run"
-                                   if traffic else f"not collected: {traffic_err}"),
-                "note": "a forward-only decode over cache-resident planes: frac prices its algorithmic FLOPs at the fp32-MFMA "
-                        "peak (SURVEY 8d); frac_real = max(six-term fp16-pipe time, texel-line requests / L2 peak) / duration "
-                        "is the bound it can physically reach; gather = the L1/L2 path of its texel reads"}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"sdf": sdf, "deformation": deform, "vertex_colours": col})
     step_ms = sorted(a.elapsed_time(b) for a, b in ev)
     ms = dt / args.steps * 1e3
     n_total = RES ** 3 + N_V
@@ -942,17 +931,84 @@ def run_config4(args, device):
                                    "(1,6,32,256,256), forward only (mesh_exporter.py:78-105,143-183); marching cubes, the SD "
                                    "generator and file output are not part of the path",
                        "grid_points": RES ** 3, "vertices": N_V, "parallelism": "dp1",
-                       "latency_ms": {"forward_field": round(sum(kernels[k]["avg_ms"] for k in kernels if k == "tt_query_field"), 4),
-                                      "export_colours": round(sum(kernels[k]["avg_ms"] for k in kernels if k == "tt_query_points"), 4),
-                                      "step_wall": round(ms, 4)},
                        "checksum": {"sdf_mean": float(sdf.mean()), "deform_abs_mean": float(deform.abs().mean()),
                                     "colour_mean": float(col.mean())}},
-            "roofline": roofline, "kernels": kernels,
-            "glue_ms": round(statistics.median(step_ms) - sum(v_["avg_ms"] * v_["launches"] / args.steps for v_ in kernels.values()), 4),
-            "timed_region_s": round(dt, 3)}
+            "timed_region_s": round(dt, 3), "full": args.full}
+    if args.full:
+        n_pts = {"tt_query_field": RES ** 3, "tt_query_points": N_V}
+        ksum = timer.summary(median=True)
+        kernels = {k: dict(kernel_roofline(k, ms_k, n_pts[k], args.precision), launches=n, points_per_launch=n_pts[k],
+                           points_per_s=round(n_pts[k] / (ms_k * 1e-3), 1))
+                   for k, (ms_k, n) in ksum.items() if k in n_pts}
+        traffic, traffic_err = (None, "skipped (--no-pmc)") if args.no_pmc else pmc_traffic(4, args.precision)
+        pipes, pipes_err = (None, "skipped (--no-pmc)") if args.no_pmc else pmc_pipes(4, args.precision)
+        cch, cch_err = (None, "skipped (--no-pmc)") if args.no_pmc else pmc_cache(4, args.precision)
+        for k, vv in kernels.items():
+            dk = ALG_POINTS[k]["device_kernel"]
+            if cch and dk in cch:
+                vv["cache"] = dict(cch[dk], kernel=dk,
+                                   l2_request_GBs_at_128B=round(cch[dk]["l2_request_bytes_at_128B"] / (vv["avg_ms"] * 1e-3) / 1e9, 1))
+            if traffic and dk in traffic:
+                vv["pmc"] = dict(traffic[dk], kernel=dk)
+            if pipes and dk in pipes:
+                vv["sq"] = dict(pipes[dk], kernel=dk)
+        dom = max(kernels, key=lambda k: kernels[k]["avg_ms"])
+        kd = kernels[dom]
+        roofline = {"kernel": dom, "bound": "mfma", "achieved": kd["alg_tflops"], "peak": PEAK_F32_TFLOPS, "unit": "TFLOP/s",
+                    "frac": kd["frac_8d"], "definition": "frac_8d (SURVEY 8(d)'s fp32-MFMA roofline, as in --config 1)",
+                    "frac_pipe_mix": kd["frac_pipe_mix"], "frac_real": kd.get("frac_real"), "bound_real": kd.get("bound_real"),
+                    "gather": kd.get("gather"), "cache": kd.get("cache"), "avg_kernel_ms": kd["avg_ms"],
+                    "mfma_util": (kd.get("sq") or {}).get("mfma_util"), "valu_util": (kd.get("sq") or {}).get("valu_util"),
+                    "waves_per_simd": (kd.get("sq") or {}).get("waves_per_simd"),
+                    "traffic": (kd.get("pmc") or {}).get("bytes"),
+                    "traffic_source": ("two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of this script in this run"
+                                       if traffic else f"not collected: {traffic_err}"),
+                    "note": "a forward-only decode over cache-resident planes: frac prices its algorithmic FLOPs at the fp32-MFMA "
+                            "peak (SURVEY 8d); frac_real = max(six-term fp16-pipe time, texel-line requests / L2 peak) / duration "
+                            "is the bound it can physically reach; gather = the L1/L2 path of its texel reads"}
+        line["config"]["latency_ms"] = {
+            "forward_field": round(sum(kernels[k]["avg_ms"] for k in kernels if k == "tt_query_field"), 4),
+            "export_colours": round(sum(kernels[k]["avg_ms"] for k in kernels if k == "tt_query_points"), 4),
+            "step_wall": round(ms, 4)}
+        line.update(roofline=roofline, kernels=kernels,
+                    glue_ms=round(statistics.median(step_ms) - sum(v_["avg_ms"] * v_["launches"] / args.steps
+                                                                   for v_ in kernels.values()), 4))
     if not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline_points()
     emit(line)
+
+
+DUMP_BYTES = 64 << 20   # --dump-outputs: at most this much in all
+DUMP_SAMPLE = 1 << 20   # elements kept of a larger array (fewer when many arrays share DUMP_BYTES)
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array of `arrays` (name -> tensor), float64 kept, everything else as float32.
+    An array with more elements than the per-array cap is written as a fixed sample of its flattened elements (indices
+    drawn with seed 0 and sorted): the same elements in every run with the same arguments."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    wide = {k: t.dtype == torch.float64 or not t.is_floating_point() for k, t in arrays.items()}
+    cap = min(DUMP_SAMPLE, DUMP_BYTES // max(sum(8 if w else 4 for w in wide.values()), 1))
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > cap:
+            idx = torch.randint(0, t.numel(), (cap,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.to(torch.float64 if wide[name] else torch.float32).cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        total += a.nbytes
+    assert total <= DUMP_BYTES, total
+
+
+def render_dump(loss, out, grads):
+    """The arrays a caller of the training step receives: the loss, the eager entries of the render output dict (the
+    lazy per-sample extras are not materialised) and the gradients, keyed by name."""
+    arrays = {"loss": loss}
+    arrays.update({"out_" + k: v for k, v in dict.items(out) if torch.is_tensor(v)})
+    arrays.update(grads)
+    return arrays
 
 
 _RESULT_FD = None
@@ -1018,9 +1074,16 @@ def main():
                     help="A/B: the eikonal term of the G6 loss with plain torch ops instead of ops.eikonal_loss")
     ap.add_argument("--graph", action="store_true",
                     help="A/B: capture the step in a hipGraph (torch.cuda.graph) and time replays instead of eager steps")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the two rocprofv3 --pmc passes (roofline.traffic = null)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the exact-f32 sub-result and the secondary workloads")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-kernel timings and rooflines, --pmc passes, sustained window, the other "
+                         "precision modes, secondary workloads, CPU baseline (a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-pmc", action="store_true",
+                    help="--full without the rocprofv3 --pmc passes (roofline.traffic = null)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="--full without the sustained window, the other precision modes and the secondary workloads")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)  # body of a rocprofv3 pass: steps only
     ap.add_argument("--lib-variant", default=None, help=argparse.SUPPRESS)  # dev A/B: an experiment build of the library
     ap.add_argument("--tile-sb", type=int, default=0, help=argparse.SUPPRESS)      # dev sweeps of the performance knobs
@@ -1031,6 +1094,8 @@ def main():
         args.steps = {2: 20, 4: 200}.get(args.config, 300)
     if args.warmup is None:
         args.warmup = 2 if args.config == 2 else 10
+    if not args.full:  # a plain run: the headline and nothing else
+        args.no_cpu_baseline = args.no_pmc = args.no_extras = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not args.pmc_child:
         sys.exit(spawn_ranks(args))
@@ -1091,6 +1156,7 @@ def main():
                           grad_copies=args.grad_copies)
     bucket = FlatGradBucket(inp["sw"] + inp["fw"])  # MLP grads = views of one buffer: one collective, no cat / copies
     fused = not args.torch_loss
+    last = {}  # --dump-outputs: the render outputs of the latest step
 
     def make_step(rcfg):
         def step():
@@ -1101,6 +1167,8 @@ def main():
             loss = loss_fn(out, inp["proj"], fused_eikonal=fused)
             loss.backward()
             bucket.all_reduce(dist)  # DDP-equivalent: one flat RCCL all-reduce on the compute stream
+            if args.dump_outputs:
+                last["out"] = out
             return loss
         return step
 
@@ -1132,6 +1200,7 @@ def main():
             ls = loss_fn(out, inp["proj"], fused_eikonal=fused)
             for dst, gr in zip(static_g, torch.autograd.grad(ls, params)):
                 dst.copy_(gr)
+            last["out"] = out  # (the captured call's outputs are the replays' static outputs)
             return ls
 
         side = torch.cuda.Stream()
@@ -1149,7 +1218,7 @@ def main():
         run = step
 
     timer = ops.KernelTimer()
-    if graph is None:
+    if graph is None and args.full:  # per-launch HIP events in the timed steps: the per-kernel figures of --full
         ops.set_kernel_timer(timer)
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
     barrier()
@@ -1163,6 +1232,12 @@ def main():
     barrier()
     dt_local = time.perf_counter() - t0
     ops.set_kernel_timer(None)
+    if args.dump_outputs and rank == 0:  # the last timed step's results, before anything else runs the step again
+        params = [inp["cache"]] + inp["sw"] + inp["fw"]
+        grads = static_g if graph is not None else [p.grad for p in params]
+        names = ["grad_planes"] + [f"grad_sdf_w{i}" for i in range(len(inp["sw"]))] + \
+                [f"grad_feat_w{i}" for i in range(len(inp["fw"]))]
+        dump_outputs(args.dump_outputs, render_dump(loss, last["out"], dict(zip(names, grads))))
     dt = dt_local
     per_rank_ms, allreduce_us, ranks_seen = None, None, None
     if world > 1:
@@ -1172,17 +1247,18 @@ def main():
         dist.all_gather(allt, tmax)
         per_rank_ms = [round(float(t) / args.steps * 1e3, 4) for t in allt]
         dt = max(float(t) for t in allt)
-        # the collective alone: the flat 66.6 KB MLP-gradient all-reduce, HIP events around 50 back-to-back calls
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        for _ in range(5):
-            bucket.all_reduce(dist)
-        barrier()
-        e0.record()
-        for _ in range(50):
-            bucket.all_reduce(dist)
-        e1.record()
-        torch.cuda.synchronize()
-        allreduce_us = round(e0.elapsed_time(e1) / 50 * 1e3, 2)
+        if args.full:
+            # the collective alone: the flat 66.6 KB MLP-gradient all-reduce, HIP events around 50 back-to-back calls
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            for _ in range(5):
+                bucket.all_reduce(dist)
+            barrier()
+            e0.record()
+            for _ in range(50):
+                bucket.all_reduce(dist)
+            e1.record()
+            torch.cuda.synchronize()
+            allreduce_us = round(e0.elapsed_time(e1) / 50 * 1e3, 2)
         info = [None] * world
         props = torch.cuda.get_device_properties(dev_index)
         dist.all_gather_object(info, {"rank": rank, "local_rank": local_rank, "device": dev_index, "name": props.name,
@@ -1197,6 +1273,36 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     n_rays = P * Hh * Ww
     value = n_rays * world * args.steps / dt
+    step_ms = sorted(a.elapsed_time(b) for a, b in ev)
+    cfg_name = {1: "BASELINE configs[1]: per GPU 1 triplane (1,6,32,256,256), 1 view 256x256 rays",
+                3: "BASELINE configs[3]: per GPU 8 prompts (8,6,32,256,256) of a batch sharded over the GPUs, one "
+                   "256x256 view each"}[args.config]
+    line = {
+        "metric": "rendered rays/sec (fwd+bwd) at 256x256 rays x 128 samples",
+        "value": value, "unit": "rays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "ms_per_step_median_hipevent": round(statistics.median(step_ms), 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": DTYPES[args.precision], "precision": args.precision, "dtype_note": DTYPE_NOTES[args.precision],
+        "data": "synthetic",
+        "config": {"workload": cfg_name + ", 128 uniform samples on [0.1,4.0], fwd + bwd of the G6 loss (d/d planes + "
+                                          "d/d 6 MLP matrices, second-order normal path included)",
+                   "rays_per_gpu": n_rays, "samples_per_ray": S, "prompts_per_gpu": P, "parallelism": f"dp{world}",
+                   "loss": float(loss.detach()), "eikonal": "torch ops" if args.torch_loss else "ops.eikonal_loss",
+                   "mode": "hipGraph replay" if graph is not None else "eager"},
+        "timed_region_s": round(dt, 3), "full": args.full,
+    }
+    if world > 1:
+        line["multi_gpu"] = {"per_rank_ms_per_step": per_rank_ms, "allreduce_us": allreduce_us,
+                             "allreduce_bytes": bucket.flat_grad.numel() * 4, "rccl": ranks_seen}
+    if not args.full:
+        if rank == 0:
+            emit(line)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # ---- --full: everything below is outside the headline ----
     # a window of >= 12 s of the same step (outside the K timed steps `value` comes from): several periods of a coarse
     # GPU-activity sampler (the driver's smi poll), and a check that the K-step number is sustained
     sustained = None
@@ -1217,7 +1323,6 @@ def main():
     torch.cuda.synchronize()
 
     if rank == 0:
-        step_ms = sorted(a.elapsed_time(b) for a, b in ev)
         n_samples = n_rays * S
         if graph is not None:  # per-kernel HIP events cannot be recorded inside a replay: time eager steps for them
             ops.set_kernel_timer(timer)
@@ -1287,27 +1392,7 @@ def main():
             ex_bytes = sum(v["alg_bytes_per_sample"] * v["inbounds_plane_frac"] for v in kernels.values())
             stage["sampling_stage"]["executed_frac_of_hbm_peak"] = round(ex_bytes * n_samples / t_all / 1e9 / PEAK_HBM_GBS, 4)
             stage["mlp_stage"]["executed_frac_of_f32_mfma_peak"] = round(ex_flop * n_samples / t_all / 1e12 / PEAK_F32_TFLOPS, 4)
-        cfg_name = {1: "BASELINE configs[1]: per GPU 1 triplane (1,6,32,256,256), 1 view 256x256 rays",
-                    3: "BASELINE configs[3]: per GPU 8 prompts (8,6,32,256,256) of a batch sharded over the GPUs, one "
-                       "256x256 view each"}[args.config]
-        line = {
-            "metric": "rendered rays/sec (fwd+bwd) at 256x256 rays x 128 samples",
-            "value": value, "unit": "rays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "ms_per_step_median_hipevent": round(statistics.median(step_ms), 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": DTYPES[args.precision], "precision": args.precision, "dtype_note": DTYPE_NOTES[args.precision],
-            "data": "synthetic",
-            "config": {"workload": cfg_name + ", 128 uniform samples on [0.1,4.0], fwd + bwd of the G6 loss (d/d planes + "
-                                              "d/d 6 MLP matrices, second-order normal path included)",
-                       "rays_per_gpu": n_rays, "samples_per_ray": S, "prompts_per_gpu": P, "parallelism": f"dp{world}",
-                       "loss": float(loss.detach()), "eikonal": "torch ops" if args.torch_loss else "ops.eikonal_loss",
-                       "mode": "hipGraph replay" if graph is not None else "eager"},
-            "roofline": roofline, "roofline_hbm": hbm, "kernels": kernels, "stages": stage,
-            "timed_region_s": round(dt, 3), "sustained": sustained,
-        }
-        if world > 1:
-            line["multi_gpu"] = {"per_rank_ms_per_step": per_rank_ms, "allreduce_us": allreduce_us,
-                                 "allreduce_bytes": bucket.flat_grad.numel() * 4, "rccl": ranks_seen}
+        line.update(roofline=roofline, roofline_hbm=hbm, kernels=kernels, stages=stage, sustained=sustained)
         if world == 1 and not args.no_extras:
             # the other two precision modes of the same build, over the SAME number of steps, with their own rooflines and
             # SQ counters (driver-visible): "f32" = the fp32-input MFMA (physical MFMA utilisation of an fp32 GEMM

@@ -113,13 +113,9 @@ def test_sampler_has_no_cpu_path():
 def test_reference_training_yaml_loads_into_the_plugins():
     """Drop-in check at the config level: the reference's own training config (configs/TriplaneTurbo_v1.yaml) must
     instantiate our geometry / material / background / patch renderer with every key it sets (unknown keys raise).
-    Reads /root/reference, so it only runs in the build container (skipped on the GPU box)."""
-    path = "/root/reference/configs/TriplaneTurbo_v1.yaml"
-    if not os.path.exists(path):
-        pytest.skip("reference checkout not present")
-    import yaml
-    txt = re.sub(r"\$\{[^}]*\}", "1", open(path).read())  # OmegaConf interpolations -> a plain scalar
-    s = yaml.safe_load(txt)["system"]
+    The config's plugin sections are stored in tests/golden/reference_training_config.json (make_golden_config.py)."""
+    import json
+    s = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_training_config.json")))
     g = tt.find(s["geometry_type"])(s["geometry"])
     m = tt.find(s["material_type"])(s["material"])
     b = tt.find(s["background_type"])(s["background"])
@@ -398,3 +394,25 @@ def test_bench_stdout_is_one_json_line():
     assert r.stdout.count("\n") == 1 and json.loads(r.stdout) == {"metric": "m", "value": 1.5}, r.stdout
     for s in ("[Gloo] Rank 0", "python-level chatter", "from a child process"):
         assert s in r.stderr
+
+
+def test_bench_dump_outputs_is_bounded_and_repeatable(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one <name>.npy per array, float32 (float64 and integer arrays as float64), small arrays
+    whole, large ones as the same seeded sample of their elements in every run, everything within DUMP_BYTES."""
+    import numpy as np
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 1 << 16)
+    big = torch.randn(100_000)
+    arrays = {"loss": torch.tensor(1.5), "small": torch.arange(12.0).reshape(3, 4), "big": big,
+              "wide": torch.arange(5, dtype=torch.float64), "count": torch.arange(3)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    got = {f: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert set(got) == {k + ".npy" for k in arrays}
+    assert got["loss.npy"].dtype == np.float32 and got["loss.npy"] == 1.5
+    assert np.array_equal(got["small.npy"], np.arange(12.0, dtype=np.float32).reshape(3, 4))
+    assert got["wide.npy"].dtype == np.float64 and got["count.npy"].dtype == np.float64
+    assert sum(a.nbytes for a in got.values()) <= bench.DUMP_BYTES
+    s = got["big.npy"]
+    assert s.ndim == 1 and 0 < s.size < big.numel() and np.isin(s, big.numpy()).all()
+    assert np.array_equal(s, np.load(tmp_path / "b" / "big.npy"))
