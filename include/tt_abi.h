@@ -55,6 +55,9 @@
  *                           threestudio/models/networks.py:17-26,54-64); tcnn is CUDA-only and un-vendored.
  *   tt_grid_sample_2d_grad2 gridsample_cuda.cpp:26-37 `grad2_2d` itself (operator-level drop-in; _typed: half / float /
  *   (_typed)                double, zeros / border padding, either align_corners, as gridsample_cuda.cu:560-594).
+ *   tt_mc_*                 marching cubes with a backward pass: the `diso.DiffMC` call of DiffMarchingCubeHelper
+ *                           (triplaneturbo_executable/utils/mesh_exporter.py:29-75, isosurface() :78-141;
+ *                           threestudio/models/isosurface.py:18-65); diso is a CUDA-only, un-vendored extension.
  */
 #ifndef TT_ABI_H
 #define TT_ABI_H
@@ -430,6 +433,44 @@ int tt_grid_sample_2d_grad2(const float* grad2_grad_input, const float* grad2_gr
                             const float* input, const float* grid, int32_t n, int32_t c, int32_t h, int32_t w,
                             int64_t n_points_per_batch, int32_t padding_mode, int32_t align_corners,
                             float* grad_grad_output, float* grad_input, float* grad_grid, void* stream);
+
+/* ---- marching cubes (tt_isosurface.hip): the drop-in for diso.DiffMC ----
+ * Replaces `DiffMC(dtype=torch.float32)(level, deformation, isovalue=...)` as DiffMarchingCubeHelper.forward calls it
+ * (triplaneturbo_executable/utils/mesh_exporter.py:65-75; grid query :78-105 = tt_query_field).  diso's own
+ * conventions are not available to pin, so this is the library's contract; what the reference itself fixes is marked (ref).
+ *   input       level (R,R,R) fp32, indexed [i][j][k] = level.view(R,R,R) of the helper's grid_vertices
+ *               (torch.meshgrid(..., indexing="ij"), k fastest) (ref); deformation (R,R,R,3) fp32 or NULL; isovalue.
+ *               2 <= R <= TT_MC_MAX_RES, anything else is TT_ERR_BAD_ARG.
+ *   inside      a grid point is inside iff level < isovalue (strict); an edge crosses iff exactly one end is inside.
+ *   vertex      on the crossing edge p0 -> p1 (p = integer grid index, d = deformation IN GRID-CELL UNITS -- an
+ *               assumption about diso, not verifiable here):  t = (iso - s0) / (s1 - s0),
+ *               v = ((p0 + d0) + t * ((p1 + d1) - (p0 + d0))) / (R - 1), i.e. [0,1] coordinates like the reference's
+ *               CPU helper (isosurface.py:122); the caller maps them to its points_range (mesh_exporter.py:73) (ref).
+ *   sharing     one vertex per crossing edge; grid point p owns its +x, +y, +z edges.
+ *   order       vertices by (owner point linear index, axis x < y < z); triangles by (cell linear index, table order),
+ *               the cell of origin (i,j,k) having linear index i*R*R + j*R + k.  Deterministic: no atomics, identical
+ *               launches give bit-identical outputs and gradients.
+ *   orientation cross(v1 - v0, v2 - v0) points toward increasing level (outward for an SDF), as Mesh.v_nrm
+ *               (mesh.py:114-140) expects.  The case tables (csrc/tt_mc_tables.h, generated by tools/gen_mc_tables.py)
+ *               cut every face from its own 4 bits (an ambiguous face cuts its two inside corners off separately), so
+ *               the mesh is watertight inside the box.
+ *   boundary    no padding: a surface that leaves the box is open there (like the reference's mcubes helper).
+ *   outputs     v_pos fp32 (V,3); t_pos_idx int32 (T,3) (the type nvdiffrast consumes).
+ *   gradients   tt_mc_bwd: from d loss / d v_pos to level and deformation (as DiffMC); t_pos_idx has none.
+ * Use: bytes = tt_mc_workspace_bytes(R); tt_mc_count(...) writes (V, T) to out_totals (2 int32 in DEVICE memory; read
+ * them back -- the only host round trip); allocate v_pos / t_pos_idx; tt_mc_emit(...) with the SAME level / isovalue /
+ * workspace; the backward reads the crossing masks and vertex offsets the count left in the workspace, so keep it.
+ * Every kernel write is bounded by the totals the count itself computed (whatever the level values); NaN levels are
+ * outside.  tt_mc_workspace_bytes returns TT_ERR_BAD_ARG for an unsupported R. */
+#define TT_MC_MAX_RES 512
+int64_t tt_mc_workspace_bytes(int32_t res);
+int tt_mc_count(const float* level, int32_t res, float isovalue, void* workspace, int32_t* out_totals, void* stream);
+int tt_mc_emit(const float* level, const float* deformation, int32_t res, float isovalue, void* workspace, float* v_pos,
+               int32_t* t_pos_idx, void* stream);
+/* grad_v (V,3) -> grad_level (R,R,R) and, iff deformation is given, grad_deformation (R,R,R,3): dense, every element
+ * written (zero off the surface); a gather over each point's 6 incident edges. */
+int tt_mc_bwd(const float* level, const float* deformation, int32_t res, float isovalue, void* workspace,
+              const float* grad_v, float* grad_level, float* grad_deformation, void* stream);
 
 #ifdef __cplusplus
 }

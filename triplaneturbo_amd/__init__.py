@@ -5,8 +5,10 @@ kernels in libtt_hip.so behind the C ABI of include/tt_abi.h.  No CPU fallback.
 
     from triplaneturbo_amd import find, register      # threestudio-style plugin registry
     Renderer = find("generative-space-sdf-volume-renderer")
+    from triplaneturbo_amd.isosurface import DiffMarchingCubeHelper, isosurface, colorize_mesh  # mesh extraction
 """
 from . import _lib  # noqa: F401
+from . import isosurface  # noqa: F401
 from .registry import C, find, register  # noqa: F401
 
 

@@ -22,7 +22,7 @@ LIB_PATH = os.path.join(_HERE, "libtt_hip.so")
 # environment variables (profiling ablations and tuning sweeps, tools/).  The product library above never calls getenv.
 _DEFAULT_LIB_PATH = LIB_PATH
 TUNING_LIB_PATH = os.path.join(_HERE, "libtt_hip_tuning.so")
-SOURCES = ["tt_forward.hip", "tt_march.hip", "tt_backward.hip", "tt_backward_tex.hip", "tt_points.hip", "tt_composite.hip", "tt_grad2.hip", "tt_sampler.hip", "tt_hashgrid.hip", "tt_host.cpp"]
+SOURCES = ["tt_forward.hip", "tt_march.hip", "tt_backward.hip", "tt_backward_tex.hip", "tt_points.hip", "tt_composite.hip", "tt_grad2.hip", "tt_sampler.hip", "tt_hashgrid.hip", "tt_isosurface.hip", "tt_host.cpp"]
 # per-translation-unit flags: the texture backward is faster under hipcc's max-ILP scheduling strategy (3.11 -> 3.02 ms;
 # the other kernels are not); the geometry backward is faster with its transient MFMA results in VGPRs rather than AGPRs
 # (-amdgpu-mfma-vgpr-form: 471 -> 248 v_accvgpr_read, 3.045 -> 2.995 ms; texture backward slower, forward neutral) and
@@ -44,6 +44,7 @@ SYMBOLS = [
     "tt_points_bwd_geo", "tt_points_bwd_tex", "tt_points_bwd_x", "tt_hashgrid_n_params", "tt_hashgrid_fwd", "tt_hashgrid_bwd",
     "tt_debug_poison_queue", "tt_patch_composite_fwd", "tt_patch_composite_bwd", "tt_render_eval",
     "tt_composite_fwd", "tt_composite_bwd", "tt_eikonal_fwd", "tt_eikonal_bwd", "tt_source_hash",
+    "tt_mc_workspace_bytes", "tt_mc_count", "tt_mc_emit", "tt_mc_bwd",
 ]
 
 
@@ -347,6 +348,10 @@ def load() -> ctypes.CDLL:
         "tt_eikonal_bwd": [_P, _P, _I64, _P, _P],
         "tt_patch_composite_fwd": [_P, _P, _P] + [_I32] * 9 + [_P],
         "tt_patch_composite_bwd": [_P, _P, _P] + [_I32] * 9 + [_P],
+        "tt_mc_workspace_bytes": [_I32],
+        "tt_mc_count": [_P, _I32, _F, _P, _P, _P],
+        "tt_mc_emit": [_P, _P, _I32, _F, _P, _P, _P, _P],
+        "tt_mc_bwd": [_P, _P, _I32, _F, _P, _P, _P, _P, _P],
     }
     for name, argtypes in optional.items():
         if name in SYMBOLS:
@@ -355,6 +360,7 @@ def load() -> ctypes.CDLL:
         if name != "tt_source_hash":
             getattr(lib, name).restype = ctypes.c_int
     lib.tt_hashgrid_n_params.restype = ctypes.c_int64
+    lib.tt_mc_workspace_bytes.restype = ctypes.c_int64
     _lib = lib
     return lib
 

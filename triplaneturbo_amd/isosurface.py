@@ -1,0 +1,155 @@
+"""Mesh extraction: the reference's DiffMarchingCubeHelper / isosurface / colorize_mesh
+(triplaneturbo_executable/utils/mesh_exporter.py:22-183) on the HIP marching cubes (ops.marching_cubes, tt_mc_* in
+include/tt_abi.h) instead of the CUDA-only `diso.DiffMC`.
+
+    from triplaneturbo_amd.isosurface import DiffMarchingCubeHelper, isosurface, colorize_mesh
+    helper = DiffMarchingCubeHelper(160).to("cuda")
+    meshes = isosurface(space_cache, geometry.forward_field, helper)
+    meshes = colorize_mesh(space_cache, geometry.export, meshes, torch.sigmoid)
+
+Same signatures and behaviour as the reference; Mesh keeps only what these functions and their users touch (no UV
+unwrap, no file output)."""
+from __future__ import annotations
+
+from typing import Any, Callable, Dict, List, Optional, Tuple
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import ops
+
+Tensor = torch.Tensor
+
+
+def scale_tensor(dat: Tensor, inp_scale, tgt_scale) -> Tensor:
+    """triplaneturbo_executable/utils/general_utils.py:12-25"""
+    if inp_scale is None:
+        inp_scale = (0, 1)
+    if tgt_scale is None:
+        tgt_scale = (0, 1)
+    if isinstance(tgt_scale, Tensor):
+        assert dat.shape[-1] == tgt_scale.shape[-1]
+    dat = (dat - inp_scale[0]) / (inp_scale[1] - inp_scale[0])
+    dat = dat * (tgt_scale[1] - tgt_scale[0]) + tgt_scale[0]
+    return dat
+
+
+class Mesh:
+    """The part of the reference's Mesh (triplaneturbo_executable/utils/mesh.py) that mesh extraction and colouring
+    use: positions, int32 triangles, vertex colours and area-weighted vertex normals (mesh.py:114-140)."""
+
+    def __init__(self, v_pos: Tensor, t_pos_idx: Tensor, **kwargs) -> None:
+        self.v_pos = v_pos
+        self.t_pos_idx = t_pos_idx
+        self._v_nrm: Optional[Tensor] = None
+        self._v_rgb: Optional[Tensor] = None
+        self.extras: Dict[str, Any] = {}
+        for k, v in kwargs.items():
+            self.add_extra(k, v)
+
+    def add_extra(self, k, v) -> None:
+        self.extras[k] = v
+
+    @property
+    def v_nrm(self) -> Tensor:
+        if self._v_nrm is None:
+            self._v_nrm = self._compute_vertex_normal()
+        return self._v_nrm
+
+    @property
+    def v_rgb(self) -> Optional[Tensor]:
+        return self._v_rgb
+
+    def _compute_vertex_normal(self) -> Tensor:
+        i0, i1, i2 = (self.t_pos_idx[:, c].long() for c in range(3))
+        v0, v1, v2 = self.v_pos[i0, :], self.v_pos[i1, :], self.v_pos[i2, :]
+        face_normals = torch.cross(v1 - v0, v2 - v0, dim=-1)
+        v_nrm = torch.zeros_like(self.v_pos)
+        v_nrm.scatter_add_(0, i0[:, None].repeat(1, 3), face_normals)
+        v_nrm.scatter_add_(0, i1[:, None].repeat(1, 3), face_normals)
+        v_nrm.scatter_add_(0, i2[:, None].repeat(1, 3), face_normals)
+        v_nrm = torch.where((v_nrm * v_nrm).sum(-1, keepdim=True) > 1e-20, v_nrm,
+                            torch.as_tensor([0.0, 0.0, 1.0]).to(v_nrm))
+        return F.normalize(v_nrm, dim=1)
+
+
+class IsosurfaceHelper(nn.Module):
+    points_range: Tuple[float, float] = (0, 1)
+
+    @property
+    def grid_vertices(self) -> Tensor:
+        raise NotImplementedError
+
+
+class DiffMarchingCubeHelper(IsosurfaceHelper):
+    """mesh_exporter.py:29-75 with the HIP marching cubes in place of diso.DiffMC."""
+
+    def __init__(self, resolution: int, point_range: Tuple[float, float] = (0, 1)) -> None:
+        super().__init__()
+        self.resolution = resolution
+        self.points_range = point_range
+        self.mc_func: Callable = ops.marching_cubes
+        self._grid_vertices: Optional[Tensor] = None
+        self.register_buffer("_dummy", torch.zeros(0, dtype=torch.float32), persistent=False)
+
+    @property
+    def grid_vertices(self) -> Tensor:
+        if self._grid_vertices is None:
+            # on the CPU, like the reference (very large resolutions); callers move them
+            x, y, z = (torch.linspace(*self.points_range, self.resolution) for _ in range(3))
+            x, y, z = torch.meshgrid(x, y, z, indexing="ij")
+            verts = torch.stack([x, y, z], dim=-1).reshape(-1, 3)
+            verts = verts * (self.points_range[1] - self.points_range[0]) + self.points_range[0]
+            self._grid_vertices = verts
+        return self._grid_vertices
+
+    def forward(self, level: Tensor, deformation: Optional[Tensor] = None, isovalue=0.0) -> Mesh:
+        R = self.resolution
+        level = level.view(R, R, R)
+        if deformation is not None:
+            deformation = deformation.view(R, R, R, 3)
+        v_pos, t_pos_idx = self.mc_func(level, deformation, isovalue=isovalue)
+        v_pos = v_pos * (self.points_range[1] - self.points_range[0]) + self.points_range[0]
+        return Mesh(v_pos=v_pos, t_pos_idx=t_pos_idx)
+
+
+def isosurface(space_cache: Any, forward_field: Callable, isosurface_helper: Callable) -> List[Mesh]:
+    """mesh_exporter.py:78-141: query the field on the helper's grid (mapped to the hard-coded [-1, 1] bbox), one
+    mesh per prompt, |p| - 1 in place of a field without a level set, vertices mapped back to [-1, 1]."""
+    if torch.is_tensor(space_cache):
+        batch_size = space_cache.shape[0]
+        device = space_cache.device
+    elif isinstance(space_cache, dict):
+        for key in space_cache.keys():
+            batch_size = space_cache[key][0].shape[0]
+            device = space_cache[key][0].device
+            break
+    points = scale_tensor(isosurface_helper.grid_vertices.to(device), isosurface_helper.points_range, [-1, 1])
+    sdf_batch, deformation_batch = forward_field(points[None, ...].expand(batch_size, -1, -1), space_cache)
+    mesh_list = []
+    for index in range(sdf_batch.shape[0]):
+        sdf = sdf_batch[index]
+        deformation = None if deformation_batch is None else deformation_batch[index]
+        if torch.all(sdf > 0) or torch.all(sdf < 0):
+            print("All sdf values are positive or negative, no isosurface")
+            sdf = torch.norm(points, dim=-1) - 1
+        mesh = isosurface_helper(sdf, deformation)
+        mesh.v_pos = scale_tensor(mesh.v_pos, isosurface_helper.points_range, [-1, 1])
+        mesh_list.append(mesh)
+    return mesh_list
+
+
+def colorize_mesh(space_cache: Any, export_fn: Callable, mesh_list: List[Mesh], activation: Callable) -> List[Mesh]:
+    """mesh_exporter.py:143-183: per mesh, the prompt's slice of the space cache, export_fn on the vertices, and
+    activation(features) as the vertex colours."""
+    for i, mesh in enumerate(mesh_list):
+        points = mesh.v_pos[None, ...]
+        if torch.is_tensor(space_cache):
+            space_cache_slice = space_cache[i:i + 1]
+        elif isinstance(space_cache, dict):
+            space_cache_slice = {key: [w[i:i + 1] for w in space_cache[key]] for key in space_cache.keys()}
+        out = export_fn(points, space_cache_slice)
+        if "features" in out:
+            mesh._v_rgb = activation(out["features"].squeeze(0))
+    return mesh_list

@@ -860,3 +860,62 @@ def eikonal_loss(sdf_grad: Tensor) -> Tensor:
     multiprompt_dual_renderer_multistep_generator.py:696-699) as one HIP kernel each way; sdf_grad (n,3) is the
     renderer's `out["sdf_grad"]`.  Equal to `((torch.linalg.norm(g, ord=2, dim=-1) - 1.0) ** 2).mean()`."""
     return _EikonalFn.apply(sdf_grad)
+
+
+class _MarchingCubesFn(torch.autograd.Function):
+    """Marching cubes with a backward pass (tt_mc_*, include/tt_abi.h "marching cubes"): the `diso.DiffMC` call of
+    DiffMarchingCubeHelper.forward (mesh_exporter.py:65-75).  Forward = count, one 8-byte read-back, allocate, emit;
+    the workspace (crossing masks + vertex offsets) stays in ctx for the backward gather tt_mc_bwd."""
+
+    @staticmethod
+    def forward(ctx, level, deformation, isovalue):
+        R = level.shape[0]
+        lib = _lib.load()
+        nbytes = lib.tt_mc_workspace_bytes(R)
+        _lib.check(int(nbytes) if nbytes < 0 else 0, "tt_mc_workspace_bytes")
+        ws = torch.empty(int(nbytes), device=level.device, dtype=torch.uint8)
+        totals = torch.empty(2, device=level.device, dtype=torch.int32)
+        _lib.check(lib.tt_mc_count(_ptr(level), R, isovalue, _ptr(ws), _ptr(totals), _stream()), "tt_mc_count")
+        n_vert, n_tri = (int(x) for x in totals.cpu())
+        v_pos = torch.empty((n_vert, 3), device=level.device, dtype=torch.float32)
+        t_pos_idx = torch.empty((n_tri, 3), device=level.device, dtype=torch.int32)
+        if n_vert > 0:
+            _lib.check(lib.tt_mc_emit(_ptr(level), _ptr(deformation), R, isovalue, _ptr(ws), _ptr(v_pos),
+                                      _ptr(t_pos_idx), _stream()), "tt_mc_emit")
+        ctx.save_for_backward(level, deformation, ws)
+        ctx.isovalue = isovalue
+        ctx.mark_non_differentiable(t_pos_idx)
+        return v_pos, t_pos_idx
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_v, g_t):
+        level, deformation, ws = ctx.saved_tensors
+        if g_v is None or not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return None, None, None
+        R = level.shape[0]
+        g_level = torch.empty_like(level)
+        g_def = torch.empty_like(deformation) if deformation is not None else None
+        if g_v.shape[0] == 0:
+            g_level.zero_()
+            if g_def is not None:
+                g_def.zero_()
+        else:
+            g_v = g_v.contiguous()
+            _lib.check(_lib.load().tt_mc_bwd(_ptr(level), _ptr(deformation), R, ctx.isovalue, _ptr(ws), _ptr(g_v),
+                                             _ptr(g_level), _ptr(g_def), _stream()), "tt_mc_bwd")
+        return (g_level if ctx.needs_input_grad[0] else None,
+                g_def if ctx.needs_input_grad[1] else None, None)
+
+
+def marching_cubes(level: Tensor, deformation: Optional[Tensor] = None, isovalue: float = 0.0) -> Tuple[Tensor, Tensor]:
+    """Isosurface of `level` (R,R,R) at `isovalue`, optionally on a grid deformed by `deformation` (R,R,R,3, grid-cell
+    units): v_pos (V,3) fp32 in [0,1]^3 (plus deformation / (R-1)), t_pos_idx (T,3) int32.  Differentiable w.r.t.
+    level and deformation (through v_pos).  Contract: include/tt_abi.h, "marching cubes"."""
+    if level.dim() != 3 or not (level.shape[0] == level.shape[1] == level.shape[2]):
+        raise ValueError(f"level must be (R,R,R), got {tuple(level.shape)}")
+    R = level.shape[0]
+    level = _chk(level, "level")
+    if deformation is not None:
+        deformation = _chk(deformation, "deformation", (R, R, R, 3))
+    return _MarchingCubesFn.apply(level, deformation, float(isovalue))
