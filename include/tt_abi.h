@@ -472,6 +472,78 @@ int tt_mc_emit(const float* level, const float* deformation, int32_t res, float 
 int tt_mc_bwd(const float* level, const float* deformation, int32_t res, float isovalue, void* workspace,
               const float* grad_v, float* grad_level, float* grad_deformation, void* stream);
 
+/* ---- rasterize / interpolate / antialias (tt_raster.hip): the drop-in for nvdiffrast ----
+ * Replaces dr.rasterize, dr.interpolate and dr.antialias as NVDiffRasterizerContext calls them
+ * (threestudio/utils/rasterize.py; generative_space_mesh_rasterize_renderer.py:137-295).  Instance mode only: one
+ * topology tri (T,3) int32 shared by B >= 1 views of clip-space positions pos (B,V,4); every tensor contiguous, fp32.
+ * T = 0 and V = 0 are legal (zero outputs, zero gradients).  T >= TT_RAST_MAX_TRIS is TT_ERR_BAD_ARG (tri + 1 is
+ * stored as a float).  A pointer may be NULL only where the count it is indexed by is 0 (pos: V, tri / topology: T).
+ * A triangle with an index outside [0, V) or a repeated index is never rasterized, and interpolate / antialias treat
+ * a pixel whose id is not in [1, T] as empty.  nvdiffrast's source is not available to pin, so this is the contract:
+ *   rasterize   rast (B,H,W,4) = (u, v, z/w, tri + 1); an empty pixel is all zeros.
+ *     pixel     (px, py) samples NDC x = (2 px + 1) / W - 1, y = (2 py + 1) / H - 1 (row 0 at y = -1).
+ *     bary      u, v perspective-correct barycentrics of vertices tri[t,0], tri[t,1] (tri[t,2] gets 1 - u - v).
+ *     coverage  the pixel centre is inside by the homogeneous 2-D edge functions (Olano-Greer) over (x, y, w), with
+ *               e_k = (v_i x v_j) . (x, y, 1), (i, j, k) cyclic, each multiplied by sign(det[v0, v1, v2]); the
+ *               interpolated w > 0; -1 <= z/w <= 1 (near / far clipping).  No face is culled; zero-area triangles
+ *               (det = 0) never produce fragments.  When all three w > 0 the same test runs on screen-space edge
+ *               functions (x/w, y/w differences, with their rounding residuals) for accuracy on pixel-sized triangles.
+ *     edges     every edge function is evaluated from its endpoints in canonical order (lower vertex index first), so
+ *               two triangles sharing an edge see exactly negated values.  Tie (value exactly 0): the triangle owns
+ *               the pixel iff its inward edge normal (sign * (n.x, n.y)) has n.x > 0, or n.x = 0 and n.y > 0 -- one
+ *               of the two triangles of a shared edge.
+ *     depth     the smallest z/w wins; on equal z/w the smaller triangle id.  64-bit atomicMin of
+ *               (order-preserving z/w bits << 32 | tri) per pixel: bit-identical across launches.
+ *     gradient  tt_rast_bwd: grad_rast (B,H,W,4) -> grad_pos (B,V,4) through u, v only (z/w and the id carry none;
+ *               pos[...,2] receives nothing: u, v do not depend on clip z).
+ *   interpolate out (B,H,W,C) = u a0 + v a1 + (1-u-v) a2, 0 on empty pixels; attr (attr_batch,V,C), attr_batch = B or
+ *               1 (broadcast over views).  Backward: grad_attr (attr_batch,V,C) (batch summed out when broadcast) and
+ *               grad_rast (B,H,W,4) in the u, v channels (z/w, id zero); either output may be NULL, not both.  No
+ *               rast_db / diff_attrs.
+ *   antialias   analytic silhouette antialiasing (Laine et al. 2020, "Modular Primitives for High-Performance
+ *               Differentiable Rendering", section 4.3):
+ *     pairs     every horizontally or vertically adjacent pixel pair (p, q) whose triangle ids differ.
+ *     occluder  t = the triangle of the covered pixel; both covered: the smaller z/w, on a tie the smaller id.  a =
+ *               t's pixel, b = the other.
+ *     silhouette an edge of t is a silhouette edge in this view if no other triangle shares it, or a triangle sharing
+ *               it has the opposite screen-space orientation (sign of det[[x,y,w]_0, [x,y,w]_1, [x,y,w]_2]).  Edges
+ *               with an endpoint at w <= 0 are skipped.
+ *     crossing  among the silhouette edges whose screen projection crosses the segment from a's centre to b's
+ *               centre, the crossing nearest a; half-open in the perpendicular axis (an edge crosses the scanline q
+ *               iff (q_0 > q) != (q_1 > q)); s in [0, 1) its distance from a's centre in pixels.  A vertex projects
+ *               to pixel coordinates ((x/w + 1) W - 1) / 2, ((y/w + 1) H - 1) / 2.
+ *     blend     out = color; per pair, if s < 0.5: out[a] += (0.5 - s)(color[b] - color[a]), else
+ *               out[b] += (s - 0.5)(color[a] - color[b]).  Each pair changes at most one pixel; coverage moves
+ *               one-for-one with the edge.
+ *     gradient  tt_aa_bwd: grad_color, and through s to the two edge vertices' clip x, y, w (grad_pos, may be NULL);
+ *               none to rast.
+ *     topology  edge_ofs (3T,2) int32 = (first, count) of the group of triangle edge 3t + k (vertices k, (k+1)%3)
+ *               in the list of the 3T edges sorted by (lower, higher) vertex index; edge_tri (3T) int32 = the
+ *               triangle of each sorted entry.  It depends on tri only: build it once per mesh (raster.py).
+ * Determinism: rast, interpolate's output, antialias's output and grad_color are gathers (or an order-independent
+ * min): bit-identical across launches.  grad_pos (tt_rast_bwd, tt_aa_bwd) and grad_attr use fp32 atomic adds and are
+ * NOT bit-reproducible.  Every gradient output is overwritten (zeroed inside).
+ * Use: bytes = tt_rast_workspace_bytes(B, T, H, W) (device workspace of tt_rast_fwd: bounding boxes, the int64
+ * candidate scan, per-pixel depth keys); no host round trip (the candidate total is read on the device), so the
+ * forward is capturable. */
+#define TT_RAST_MAX_TRIS (1 << 24)
+int64_t tt_rast_workspace_bytes(int32_t B, int32_t T, int32_t H, int32_t W);
+int tt_rast_fwd(const float* pos, const int32_t* tri, int32_t B, int32_t V, int32_t T, int32_t H, int32_t W,
+                void* workspace, float* rast, void* stream);
+int tt_rast_bwd(const float* pos, const int32_t* tri, const float* rast, const float* grad_rast, int32_t B, int32_t V,
+                int32_t T, int32_t H, int32_t W, float* grad_pos, void* stream);
+int tt_interp_fwd(const float* attr, int32_t attr_batch, const float* rast, const int32_t* tri, int32_t B, int32_t V,
+                  int32_t T, int32_t H, int32_t W, int32_t C, float* out, void* stream);
+int tt_interp_bwd(const float* attr, int32_t attr_batch, const float* rast, const int32_t* tri, const float* grad_out,
+                  int32_t B, int32_t V, int32_t T, int32_t H, int32_t W, int32_t C, float* grad_attr, float* grad_rast,
+                  void* stream);
+int tt_aa_fwd(const float* color, const float* rast, const float* pos, const int32_t* tri, const int32_t* edge_ofs,
+              const int32_t* edge_tri, int32_t B, int32_t V, int32_t T, int32_t H, int32_t W, int32_t C, float* out,
+              void* stream);
+int tt_aa_bwd(const float* color, const float* rast, const float* pos, const int32_t* tri, const int32_t* edge_ofs,
+              const int32_t* edge_tri, const float* grad_out, int32_t B, int32_t V, int32_t T, int32_t H, int32_t W,
+              int32_t C, float* grad_color, float* grad_pos, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,150 @@
+"""`generative-space-mesh-rasterize-renderer` end to end: an analytic sphere (zero MLP weights, so the field is
+|x| - 0.5) against its projected disc, depth and camera-space normal and against the volume renderer's opacity; the
+training shape (8 prompts x 4 views at 512^2, 128^3, deformable grid, hashgrid background) through backward(); and
+the empty-field fix-up."""
+import json
+import math
+import os
+import sys
+
+import pytest
+import torch
+
+import triplaneturbo_amd as tt
+from triplaneturbo_amd import synthetic
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from test_gpu_raster import perspective  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FOVY = 60.0
+
+
+@pytest.fixture(scope="module")
+def dev():
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    return torch.device("cuda", 0)
+
+
+def _configs():
+    s = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_mesh_renderer_config.json")))
+    t = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_training_config.json")))
+    return s, t
+
+
+def _cameras(n_view, H, W, dev):
+    rays_o, rays_d, c2w, dist = synthetic.make_cameras(n_view, H, W, fovy_deg=FOVY)
+    mvp = perspective(FOVY, W / H)[None] @ torch.inverse(c2w)
+    pos = c2w[:, :3, 3]
+    return {k: v.to(dev) for k, v in dict(mvp_mtx=mvp, camera_positions=pos, light_positions=pos, c2w=c2w,
+                                           camera_distances=dist, rays_d_rasterize=rays_d, rays_o=rays_o).items()}
+
+
+def _sphere_modules(dev, geo_over=None, **rend_over):
+    s, t = _configs()
+    geo = dict(t["geometry"], isosurface_deformable_grid=False, **(geo_over or {}))
+    g = tt.find(t["geometry_type"])(geo).to(dev)
+    with torch.no_grad():
+        for w in list(g.sdf_network.parameters()) + list(g.feature_network.parameters()):
+            w.zero_()
+    m = tt.find(t["material_type"])(t["material"]).to(dev)
+    b = tt.find("solid-color-background")({"color": (1.0, 1.0, 1.0)}).to(dev)
+    r = tt.find(s["renderer_type"])(dict(s["renderer"], enable_bg_rays=False, **rend_over), geometry=g, material=m,
+                                    background=b).to(dev)
+    return r, g, m, b
+
+
+def test_analytic_sphere(dev):
+    H = W = 128
+    n = 4
+    r, g, m, b = _sphere_modules(dev)
+    r.eval()
+    cam = _cameras(n, H, W, dev)
+    cache = torch.randn(1, 6, 32, 32, 32, device=dev)
+    text = torch.zeros(1, 1024, device=dev)  # its batch is the number of prompts (views per prompt = B / that)
+    with torch.no_grad():
+        out = r(cam["mvp_mtx"], cam["camera_positions"], cam["light_positions"], H, W, space_cache=cache,
+                text_embed=text, camera_distances=cam["camera_distances"], c2w=cam["c2w"])
+    for k in ("opacity", "depth", "disparity", "comp_normal", "comp_normal_cam_vis", "comp_normal_cam_vis_white",
+              "comp_rgb", "comp_rgb_bg"):
+        assert out[k].shape[:3] == (n, H, W) and torch.isfinite(out[k]).all(), k
+    for v in range(n):
+        d = float(cam["camera_distances"][v])
+        rad = math.tan(math.asin(0.5 / d)) / math.tan(math.radians(FOVY) / 2) * H / 2
+        area = float(out["opacity"][v].sum())
+        assert abs(area - math.pi * rad ** 2) <= 2 * math.pi * rad * 0.5 + 4, (area, math.pi * rad ** 2)
+        # centre pixel: the ray hits the sphere at about d - 0.5 (clip z of the reference projection)
+        c = out["disparity"][v, H // 2, W // 2, 0].item()
+        zc = d - 0.5  # eye-space distance of the nearest point
+        far, near = 1000.0, 0.1
+        clip_z = ((far + near) * zc - 2 * far * near) / (far - near)
+        want = min(max((d + math.sqrt(3) - clip_z) / (2 * math.sqrt(3)), 0.0), 1.0)
+        assert abs(c - want) < 1e-2, (c, want)
+        nv = out["comp_normal_cam_vis"][v, H // 2, W // 2]
+        assert torch.allclose(nv, torch.tensor([0.5, 0.5, 1.0], device=dev), atol=0.03), nv
+
+    # the volume renderer sees the same sphere in the same pixels (pins the image orientation between the two)
+    s, t = _configs()
+    vr = tt.find(t["renderer_2nd"]["base_renderer_type"])(t["renderer_2nd"]["base_renderer"], geometry=g,
+                                                         material=m, background=b).to(dev)
+    vr.eval()
+    with torch.no_grad():
+        vo = vr(cam["rays_o"], cam["rays_d_rasterize"], cam["light_positions"], space_cache=cache,
+                camera_distances=cam["camera_distances"], c2w=cam["c2w"])
+    a = out["opacity"][..., 0] > 0.5
+    bmask = vo["opacity"].reshape(n, H, W) > 0.5
+    iou = (a & bmask).sum().item() / (a | bmask).sum().item()
+    assert iou > 0.98, iou
+
+
+def test_training_shape_backward(dev):
+    P, n_view, H, W = 8, 4, 512, 512
+    s, t = _configs()
+    g = tt.find(t["geometry_type"])(t["geometry"]).to(dev)
+    m = tt.find(t["material_type"])(t["material"]).to(dev)
+    b = tt.find(t["background_type"])(t["background"]).to(dev)
+    r = tt.find(s["renderer_type"])(s["renderer"], geometry=g, material=m, background=b).to(dev)
+    r.train()
+    r.update_step(0, 100)
+    cam = _cameras(P * n_view, H, W, dev)
+    torch.manual_seed(0)
+    cache = (torch.randn(P, 6, 32, 64, 64, device=dev) * 0.3).requires_grad_(True)
+    text = torch.randn(P, 1024, device=dev)
+    out = r(cam["mvp_mtx"], cam["camera_positions"], cam["light_positions"], H, W, space_cache=cache,
+            text_embed=text, rays_d_rasterize=cam["rays_d_rasterize"], camera_distances=cam["camera_distances"],
+            c2w=cam["c2w"])
+    B = P * n_view
+    shapes = {"opacity": 1, "depth": 1, "disparity": 1, "comp_normal": 3, "comp_normal_cam_vis": 3,
+              "comp_normal_cam_vis_white": 3, "comp_rgb": 3, "comp_rgb_bg": 3}
+    for k, c in shapes.items():
+        assert out[k].shape == (B, H, W, c), (k, out[k].shape)
+        assert torch.isfinite(out[k]).all(), k
+    assert len(out["mesh"]) == P and len(out["sdf"]) == P and len(out["sdf_grad"]) == P
+    assert all(torch.isfinite(x).all() for x in out["sdf"] + out["sdf_grad"])
+    loss = sum(out[k].square().mean() for k in shapes) + sum(x.mean() for x in out["sdf"]) + \
+        sum((x.norm(dim=-1) - 1).square().mean() for x in out["sdf_grad"])
+    loss.backward()
+    params = {"space_cache": cache, "sdf_network": next(g.sdf_network.parameters()),
+              "feature_network": next(g.feature_network.parameters()),
+              "deformation_network": next(g.deformation_network.parameters()),
+              "background": next(b.parameters())}
+    for name, p in params.items():
+        assert p.grad is not None and torch.isfinite(p.grad).all() and p.grad.abs().sum() > 0, name
+
+
+def test_empty_field_takes_the_fix_up_path(dev):
+    H = W = 64
+    r, g, m, b = _sphere_modules(dev, geo_over={"sdf_bias_params": -0.1}, allow_empty_flag=True)  # |x| + 0.1 > 0
+    r.train()
+    cam = _cameras(2, H, W, dev)
+    cache = torch.randn(1, 6, 32, 32, 32, device=dev).requires_grad_(True)
+    out = r(cam["mvp_mtx"], cam["camera_positions"], cam["light_positions"], H, W, space_cache=cache,
+            text_embed=torch.zeros(1, 1024, device=dev), camera_distances=cam["camera_distances"], c2w=cam["c2w"])
+    assert out["opacity"].shape[0] == 2
+    mesh = out["mesh"][0]
+    assert mesh.t_pos_idx.shape[0] > 0  # the InstantMesh fix-up made a surface
+    assert not r.empty_flag  # consumed by the forward
+    for k in ("opacity", "disparity", "comp_rgb", "comp_normal_cam_vis"):
+        assert torch.isfinite(out[k]).all() and not out[k].requires_grad, k  # detached (allow_empty_flag)

@@ -13,7 +13,7 @@ from .registry import C, find, register  # noqa: F401
 
 
 def _register_plugins():
-    from . import background, geometry, renderer  # noqa: F401  (import = registration)
+    from . import background, geometry, mesh_renderer, renderer  # noqa: F401  (import = registration)
 
 
 _register_plugins()

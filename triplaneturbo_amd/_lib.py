@@ -22,7 +22,7 @@ LIB_PATH = os.path.join(_HERE, "libtt_hip.so")
 # environment variables (profiling ablations and tuning sweeps, tools/).  The product library above never calls getenv.
 _DEFAULT_LIB_PATH = LIB_PATH
 TUNING_LIB_PATH = os.path.join(_HERE, "libtt_hip_tuning.so")
-SOURCES = ["tt_forward.hip", "tt_march.hip", "tt_backward.hip", "tt_backward_tex.hip", "tt_points.hip", "tt_composite.hip", "tt_grad2.hip", "tt_sampler.hip", "tt_hashgrid.hip", "tt_isosurface.hip", "tt_host.cpp"]
+SOURCES = ["tt_forward.hip", "tt_march.hip", "tt_backward.hip", "tt_backward_tex.hip", "tt_points.hip", "tt_composite.hip", "tt_grad2.hip", "tt_sampler.hip", "tt_hashgrid.hip", "tt_isosurface.hip", "tt_raster.hip", "tt_host.cpp"]
 # per-translation-unit flags: the texture backward is faster under hipcc's max-ILP scheduling strategy (3.11 -> 3.02 ms;
 # the other kernels are not); the geometry backward is faster with its transient MFMA results in VGPRs rather than AGPRs
 # (-amdgpu-mfma-vgpr-form: 471 -> 248 v_accvgpr_read, 3.045 -> 2.995 ms; texture backward slower, forward neutral) and
@@ -45,6 +45,7 @@ SYMBOLS = [
     "tt_debug_poison_queue", "tt_patch_composite_fwd", "tt_patch_composite_bwd", "tt_render_eval",
     "tt_composite_fwd", "tt_composite_bwd", "tt_eikonal_fwd", "tt_eikonal_bwd", "tt_source_hash",
     "tt_mc_workspace_bytes", "tt_mc_count", "tt_mc_emit", "tt_mc_bwd",
+    "tt_rast_workspace_bytes", "tt_rast_fwd", "tt_rast_bwd", "tt_interp_fwd", "tt_interp_bwd", "tt_aa_fwd", "tt_aa_bwd",
 ]
 
 
@@ -352,6 +353,13 @@ def load() -> ctypes.CDLL:
         "tt_mc_count": [_P, _I32, _F, _P, _P, _P],
         "tt_mc_emit": [_P, _P, _I32, _F, _P, _P, _P, _P],
         "tt_mc_bwd": [_P, _P, _I32, _F, _P, _P, _P, _P, _P],
+        "tt_rast_workspace_bytes": [_I32] * 4,
+        "tt_rast_fwd": [_P, _P] + [_I32] * 5 + [_P, _P, _P],
+        "tt_rast_bwd": [_P] * 4 + [_I32] * 5 + [_P, _P],
+        "tt_interp_fwd": [_P, _I32, _P, _P] + [_I32] * 6 + [_P, _P],
+        "tt_interp_bwd": [_P, _I32, _P, _P, _P] + [_I32] * 6 + [_P, _P, _P],
+        "tt_aa_fwd": [_P] * 6 + [_I32] * 6 + [_P, _P],
+        "tt_aa_bwd": [_P] * 7 + [_I32] * 6 + [_P, _P, _P],
     }
     for name, argtypes in optional.items():
         if name in SYMBOLS:
@@ -361,6 +369,7 @@ def load() -> ctypes.CDLL:
             getattr(lib, name).restype = ctypes.c_int
     lib.tt_hashgrid_n_params.restype = ctypes.c_int64
     lib.tt_mc_workspace_bytes.restype = ctypes.c_int64
+    lib.tt_rast_workspace_bytes.restype = ctypes.c_int64
     _lib = lib
     return lib
 

@@ -1,0 +1,801 @@
+// tt_raster.hip -- differentiable triangle rasterization, attribute interpolation and silhouette antialiasing: the
+// drop-in for the three nvdiffrast primitives (CUDA-only) that the reference's mesh renderer calls through
+// NVDiffRasterizerContext (threestudio/utils/rasterize.py; generative_space_mesh_rasterize_renderer.py:137-295).
+// Instance mode only: one topology tri (T,3) shared by B views of clip-space positions pos (B,V,4).  The contract
+// (pixel centres, coverage, tie rule, depth test, antialias pairs) is written in include/tt_abi.h.
+//
+// Rasterize, five launches, no host round trip:
+//   k_rast_setup      per (view, triangle): clip culling and a clamped screen bounding box; its pixel count
+//   k_scan_reduce / k_scan_blocks / k_scan_apply     exclusive int64 scan of the counts -> candidate offsets
+//   k_rast_cover      grid-stride over the candidates (triangle, pixel), total read on the device: coverage by the
+//                     homogeneous edge functions, then a 64-bit atomicMin of (ordered z/w bits << 32 | tri) into the
+//                     pixel's key.  Min is order-independent, so the result is bit-reproducible.
+//   k_rast_resolve    per pixel: the winner's (u, v, z/w) recomputed by the same function as the coverage test
+// Interpolate and antialias are per-pixel gathers; their vertex gradients (grad_pos, grad_attr) use fp32 atomics.
+#include "tt_host.h"
+
+#pragma clang fp contract(off)  // edge functions exactly as written: shared edges must see exactly negated values
+
+#define RS_BLOCK 256
+#define RS_SCAN_ITEMS 4  // elements per thread of the scan kernels (1024 per block)
+#define RS_SCAN_BLOCK 1024
+
+// ---------------------------------------------------------------------------------------------------------------
+// triangle setup shared by every kernel (one function, so that coverage, resolve and backward agree bit for bit)
+
+struct TriSetup {
+    int idx[3];
+    float x[3], y[3], z[3], w[3];
+    bool homog;     // some w <= 0: homogeneous edge functions; else screen-space ones (all w > 0, the common case)
+    float X[3], Y[3], ZW[3];  // screen path: NDC x/w, y/w, z/w of the vertices
+    float n[3][3];  // homogeneous path: canonical edge k (opposite vertex k) v_lo x v_hi over (x, y, w)
+    float XL[3], YL[3];       // their rounding residuals (x/w = X + XL to about twice float precision)
+    float ex[3][4];  // screen path: canonical endpoints of edge k (X, Y of the lower vertex index, then the higher)
+    float el[3][4];  // and their residuals
+    float sg[3];    // +-1: sign of the true edge function (cyclic order) relative to the canonical one, times sign(D)
+    float sd;       // sign(D), D = det[v0, v1, v2] over (x, y, w) (= sign of the screen area when all w > 0)
+};
+
+__device__ __forceinline__ void cross3(float ax, float ay, float aw, float bx, float by, float bw, float* o) {
+    o[0] = ay * bw - aw * by;
+    o[1] = aw * bx - ax * bw;
+    o[2] = ax * by - ay * bx;
+}
+
+__device__ __forceinline__ bool tri_indices(const int* __restrict__ tri, long long t, int V, int* idx) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) idx[k] = tri[t * 3 + k];
+    return (unsigned)idx[0] < (unsigned)V && (unsigned)idx[1] < (unsigned)V && (unsigned)idx[2] < (unsigned)V;
+}
+
+__device__ __forceinline__ float4 vtx(const float* __restrict__ pos, int b, int V, int i) {
+    return reinterpret_cast<const float4*>(pos)[(long long)b * V + i];
+}
+
+// orientation sign of triangle t in view b (0: degenerate / invalid indices)
+__device__ __forceinline__ float tri_orient(const float* __restrict__ pos, const int* __restrict__ tri, int b, int t,
+                                            int V) {
+    int idx[3];
+    if (!tri_indices(tri, t, V, idx)) return 0.f;
+    const float4 a = vtx(pos, b, V, idx[0]), c = vtx(pos, b, V, idx[1]), e = vtx(pos, b, V, idx[2]);
+    float n[3];
+    cross3(a.x, a.y, a.w, c.x, c.y, c.w, n);
+    const float D = n[0] * e.x + n[1] * e.y + n[2] * e.w;
+    return D > 0.f ? 1.f : (D < 0.f ? -1.f : 0.f);
+}
+
+// false: the triangle never produces fragments (invalid or repeated indices, non-finite positions, zero area)
+__device__ __forceinline__ bool tri_setup(const float* __restrict__ pos, const int* __restrict__ tri, int b, int t, int V,
+                          TriSetup& s) {
+    if (!tri_indices(tri, t, V, s.idx)) return false;
+    if (s.idx[0] == s.idx[1] || s.idx[1] == s.idx[2] || s.idx[0] == s.idx[2]) return false;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float4 p = vtx(pos, b, V, s.idx[k]);
+        s.x[k] = p.x;
+        s.y[k] = p.y;
+        s.z[k] = p.z;
+        s.w[k] = p.w;
+        if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z) && isfinite(p.w))) return false;
+    }
+    s.homog = !(fminf(fminf(s.w[0], s.w[1]), s.w[2]) > 0.f);  // one compare (finite here): see pix_tri
+    // screen-space edge functions from coordinate differences when all w > 0: accurate for triangles of a few pixels,
+    // where the homogeneous cross products lose the small area to cancellation (unused on the homogeneous path)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        s.X[k] = s.x[k] / s.w[k];
+        s.Y[k] = s.y[k] / s.w[k];
+        s.ZW[k] = s.z[k] / s.w[k];
+        // the quotient's residual: the edge functions of sliver triangles subtract nearly equal coordinates
+        s.XL[k] = fmaf(-s.X[k], s.w[k], s.x[k]) / s.w[k];
+        s.YL[k] = fmaf(-s.Y[k], s.w[k], s.y[k]) / s.w[k];
+    }
+    float n01[3];
+    cross3(s.x[0], s.y[0], s.w[0], s.x[1], s.y[1], s.w[1], n01);
+    const float Dh = n01[0] * s.x[2] + n01[1] * s.y[2] + n01[2] * s.w[2];
+    const float Ds = (s.X[1] - s.X[0]) * (s.Y[2] - s.Y[0]) - (s.Y[1] - s.Y[0]) * (s.X[2] - s.X[0]);
+    const float D = s.homog ? Dh : Ds;
+    if (!(D != 0.f) || !isfinite(D)) return false;
+    s.sd = D > 0.f ? 1.f : -1.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int i = (k + 1) % 3, j = (k + 2) % 3;
+        const bool fwd = s.idx[i] < s.idx[j];
+        // (selects between the two compile-time vertex numbers: no dynamically indexed private arrays)
+        // (both forms, unconditionally: a store into one of two private arrays chosen at run time goes to scratch)
+        cross3(fwd ? s.x[i] : s.x[j], fwd ? s.y[i] : s.y[j], fwd ? s.w[i] : s.w[j], fwd ? s.x[j] : s.x[i],
+               fwd ? s.y[j] : s.y[i], fwd ? s.w[j] : s.w[i], s.n[k]);
+        s.ex[k][0] = fwd ? s.X[i] : s.X[j];
+        s.ex[k][1] = fwd ? s.Y[i] : s.Y[j];
+        s.ex[k][2] = fwd ? s.X[j] : s.X[i];
+        s.ex[k][3] = fwd ? s.Y[j] : s.Y[i];
+        s.el[k][0] = fwd ? s.XL[i] : s.XL[j];
+        s.el[k][1] = fwd ? s.YL[i] : s.YL[j];
+        s.el[k][2] = fwd ? s.XL[j] : s.XL[i];
+        s.el[k][3] = fwd ? s.YL[j] : s.YL[i];
+        s.sg[k] = fwd ? s.sd : -s.sd;
+    }
+    return true;
+}
+
+// NDC of pixel centre (px, py): x = (2 px + 1) / W - 1, y = (2 py + 1) / H - 1
+__device__ __forceinline__ float pix_ndc(int p, int N) { return (float)(2 * p + 1) / (float)N - 1.f; }
+// its rounding residual: the exact value is pix_ndc + pix_ndc_lo to about twice float precision
+__device__ __forceinline__ float pix_ndc_lo(int p, int N) {
+    const float n = (float)(2 * p + 1), q = n / (float)N;
+    const float rq = fmaf(-q, (float)N, n) / (float)N;  // q + rq = n / N
+    const float hi = q - 1.f;
+    const float err = q - (hi + 1.f);                      // Fast2Sum of q + (-1): |-1| >= |q| for q < 1
+    return err + rq;
+}
+
+// coverage test + perspective-correct (u, v, z/w) at NDC (X, Y).  S = the sum of the three homogeneous oriented edge
+// values sign(D) (v_i x v_j) . (X, Y, 1) (= |D| / interpolated w), which the backward divides by.
+__device__ __forceinline__ bool tri_cover(const TriSetup& s, float X, float XL, float Y, float YL, float& u, float& v,
+                                          float& zw, float& S) {
+    float te[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        float c, gx, gy;
+        if (s.homog) {
+            c = (s.n[k][0] * X + s.n[k][1] * Y) + s.n[k][2];
+            gx = s.n[k][0];
+            gy = s.n[k][1];
+        } else {
+            const float ax = (s.ex[k][0] - X) + (s.el[k][0] - XL), ay = (s.ex[k][1] - Y) + (s.el[k][1] - YL);
+            const float bx = (s.ex[k][2] - X) + (s.el[k][2] - XL), by = (s.ex[k][3] - Y) + (s.el[k][3] - YL);
+            c = ax * by - ay * bx;
+            gx = s.ex[k][1] - s.ex[k][3];
+            gy = s.ex[k][2] - s.ex[k][0];
+        }
+        const float t = s.sg[k] * c;
+        if (t < 0.f) return false;
+        if (t == 0.f) {  // on the edge: the triangle owns it iff its inward normal points to +x (or +y if vertical)
+            gx *= s.sg[k];
+            gy *= s.sg[k];
+            if (!(gx > 0.f || (gx == 0.f && gy > 0.f))) return false;
+        }
+        if (!(t >= 0.f)) return false;  // NaN
+        te[k] = t;
+    }
+    if (s.homog) {
+        const float sum = (te[0] + te[1]) + te[2];
+        if (!(sum > 0.f)) return false;
+        const float den = (te[0] * s.w[0] + te[1] * s.w[1]) + te[2] * s.w[2];
+        if (!(den > 0.f)) return false;
+        const float num = (te[0] * s.z[0] + te[1] * s.z[1]) + te[2] * s.z[2];
+        zw = num / den;
+        u = te[0] / sum;
+        v = te[1] / sum;
+        S = sum;
+    } else {
+        const float sum = (te[0] + te[1]) + te[2];  // screen area: z/w is affine in screen space
+        if (!(sum > 0.f)) return false;
+        zw = ((te[0] * s.ZW[0] + te[1] * s.ZW[1]) + te[2] * s.ZW[2]) / sum;
+        const float l0 = te[0] / s.w[0], l1 = te[1] / s.w[1], l2 = te[2] / s.w[2];
+        const float L = (l0 + l1) + l2;
+        u = l0 / L;
+        v = l1 / L;
+        S = ((s.w[0] * s.w[1]) * s.w[2]) * L;
+    }
+    if (!(zw >= -1.f && zw <= 1.f)) return false;
+    return true;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// rasterize forward
+
+struct RastLayout {
+    long long n, nblk, off_bbox, off_offs, off_bsum, off_keys, bytes;
+};
+
+static inline long long rs_align(long long x) { return (x + 255) & ~255ll; }
+
+static RastLayout rast_layout(int B, int T, int H, int W) {
+    RastLayout l;
+    l.n = (long long)B * T;
+    l.nblk = (l.n + RS_SCAN_BLOCK - 1) / RS_SCAN_BLOCK;
+    l.off_bbox = 0;
+    l.off_offs = rs_align(16 * l.n);
+    l.off_bsum = l.off_offs + rs_align(8 * (l.n + 1));
+    l.off_keys = l.off_bsum + rs_align(8 * (l.nblk + 1));
+    l.bytes = l.off_keys + rs_align(8ll * B * H * W);
+    return l;
+}
+
+__global__ __launch_bounds__(RS_BLOCK) void k_rast_setup(const float* __restrict__ pos, const int* __restrict__ tri,
+                                                         int B, int V, int T, int H, int W, int4* __restrict__ bbox,
+                                                         long long* __restrict__ cnt) {
+    const long long i = (long long)blockIdx.x * RS_BLOCK + threadIdx.x;
+    if (i >= (long long)B * T) return;
+    const int b = (int)(i / T), t = (int)(i % T);
+    TriSetup s;
+    long long area = 0;
+    int4 bb = make_int4(0, 0, -1, -1);
+    if (tri_setup(pos, tri, b, t, V, s)) {
+        // culled if all vertices lie beyond one clip plane, or all w <= 0
+        bool cull = (s.w[0] <= 0.f && s.w[1] <= 0.f && s.w[2] <= 0.f);
+        cull |= (s.x[0] > s.w[0] && s.x[1] > s.w[1] && s.x[2] > s.w[2]);
+        cull |= (s.x[0] < -s.w[0] && s.x[1] < -s.w[1] && s.x[2] < -s.w[2]);
+        cull |= (s.y[0] > s.w[0] && s.y[1] > s.w[1] && s.y[2] > s.w[2]);
+        cull |= (s.y[0] < -s.w[0] && s.y[1] < -s.w[1] && s.y[2] < -s.w[2]);
+        cull |= (s.z[0] > s.w[0] && s.z[1] > s.w[1] && s.z[2] > s.w[2]);
+        cull |= (s.z[0] < -s.w[0] && s.z[1] < -s.w[1] && s.z[2] < -s.w[2]);
+        if (!cull) {
+            if (s.w[0] > 0.f && s.w[1] > 0.f && s.w[2] > 0.f) {
+                float x0 = 3.4e38f, x1 = -3.4e38f, y0 = 3.4e38f, y1 = -3.4e38f;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    // pixel coordinate whose centre samples NDC X: ((X + 1) W - 1) / 2
+                    const float px = ((s.x[k] / s.w[k] + 1.f) * (float)W - 1.f) * 0.5f;
+                    const float py = ((s.y[k] / s.w[k] + 1.f) * (float)H - 1.f) * 0.5f;
+                    x0 = fminf(x0, px);
+                    x1 = fmaxf(x1, px);
+                    y0 = fminf(y0, py);
+                    y1 = fmaxf(y1, py);
+                }
+                // one pixel of margin against rounding (the coverage test is exact; the box only bounds it), clamped
+                // in float before the conversion
+                x0 = fminf(fmaxf(floorf(x0) - 1.f, 0.f), (float)W);
+                x1 = fminf(fmaxf(ceilf(x1) + 1.f, -1.f), (float)(W - 1));
+                y0 = fminf(fmaxf(floorf(y0) - 1.f, 0.f), (float)H);
+                y1 = fminf(fmaxf(ceilf(y1) + 1.f, -1.f), (float)(H - 1));
+                bb = make_int4((int)x0, (int)y0, (int)x1, (int)y1);
+            } else {  // straddles w = 0 (rare): the whole screen
+                bb = make_int4(0, 0, W - 1, H - 1);
+            }
+            if (bb.z >= bb.x && bb.w >= bb.y) area = (long long)(bb.z - bb.x + 1) * (bb.w - bb.y + 1);
+        }
+    }
+    bbox[i] = bb;
+    cnt[i] = area;
+}
+
+template <typename T>
+__device__ __forceinline__ T wave_incl_scan(T v, int lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const T x = __shfl_up(v, d, 64);
+        if (lane >= d) v += x;
+    }
+    return v;
+}
+
+// block-wide exclusive scan of one int64 per thread (RS_BLOCK threads); returns the exclusive prefix, *total the sum
+__device__ __forceinline__ long long block_excl_scan(long long v, long long* total) {
+    __shared__ long long wsum[RS_BLOCK / 64];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const long long inc = wave_incl_scan(v, lane);
+    if (lane == 63) wsum[wid] = inc;
+    __syncthreads();
+    long long before = 0, tot = 0;
+#pragma unroll
+    for (int k = 0; k < RS_BLOCK / 64; ++k) {
+        if (k < wid) before += wsum[k];
+        tot += wsum[k];
+    }
+    __syncthreads();
+    *total = tot;
+    return before + inc - v;
+}
+
+__global__ __launch_bounds__(RS_BLOCK) void k_scan_reduce(const long long* __restrict__ cnt, long long n,
+                                                          long long* __restrict__ bsum) {
+    const long long base = (long long)blockIdx.x * RS_SCAN_BLOCK + threadIdx.x * RS_SCAN_ITEMS;
+    long long v = 0;
+#pragma unroll
+    for (int k = 0; k < RS_SCAN_ITEMS; ++k)
+        if (base + k < n) v += cnt[base + k];
+    long long tot;
+    block_excl_scan(v, &tot);
+    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
+}
+
+// one block: exclusive scan of the block sums in place, in chunks of RS_BLOCK with a running carry; offs[n] = total
+__global__ __launch_bounds__(RS_BLOCK) void k_scan_blocks(long long* __restrict__ bsum, long long nblk,
+                                                          long long* __restrict__ offs, long long n) {
+    long long carry = 0;
+    for (long long base = 0; base < nblk; base += RS_BLOCK) {
+        const long long i = base + threadIdx.x;
+        const long long v = i < nblk ? bsum[i] : 0;
+        long long tot;
+        const long long ex = block_excl_scan(v, &tot);
+        if (i < nblk) bsum[i] = carry + ex;
+        carry += tot;
+    }
+    if (threadIdx.x == 0) offs[n] = carry;
+}
+
+__global__ __launch_bounds__(RS_BLOCK) void k_scan_apply(const long long* cnt, long long n,
+                                                         const long long* __restrict__ bsum, long long* offs) {
+    const long long base = (long long)blockIdx.x * RS_SCAN_BLOCK + threadIdx.x * RS_SCAN_ITEMS;
+    long long c[RS_SCAN_ITEMS], v = 0;
+#pragma unroll
+    for (int k = 0; k < RS_SCAN_ITEMS; ++k) {
+        c[k] = base + k < n ? cnt[base + k] : 0;
+        v += c[k];
+    }
+    long long tot;
+    long long run = bsum[blockIdx.x] + block_excl_scan(v, &tot);
+#pragma unroll
+    for (int k = 0; k < RS_SCAN_ITEMS; ++k) {
+        if (base + k < n) offs[base + k] = run;
+        run += c[k];
+    }
+}
+
+__device__ __forceinline__ unsigned ordered_bits(float f) {
+    const unsigned u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__global__ __launch_bounds__(RS_BLOCK) void k_rast_cover(const float* __restrict__ pos, const int* __restrict__ tri,
+                                                         int V, int T, int H, int W, const int4* __restrict__ bbox,
+                                                         const long long* __restrict__ offs, long long n,
+                                                         unsigned long long* __restrict__ keys) {
+    const long long total = offs[n];  // read on the device: no host round trip, capturable
+    const long long stride = (long long)gridDim.x * RS_BLOCK;
+    for (long long c = (long long)blockIdx.x * RS_BLOCK + threadIdx.x; c < total; c += stride) {
+        // the (view, triangle) slot i with offs[i] <= c < offs[i + 1] (the last of equal offsets: a non-empty box)
+        long long lo = 0, hi = n - 1;
+        while (lo < hi) {
+            const long long mid = (lo + hi + 1) >> 1;
+            if (offs[mid] <= c) lo = mid;
+            else hi = mid - 1;
+        }
+        const int4 bb = bbox[lo];
+        const long long local = c - offs[lo];
+        const int bw = bb.z - bb.x + 1;
+        const int px = bb.x + (int)(local % bw), py = bb.y + (int)(local / bw);
+        if (px > bb.z || py > bb.w) continue;  // cannot happen for a consistent scan; keeps every store in bounds
+        const int b = (int)(lo / T), t = (int)(lo % T);
+        TriSetup s;
+        if (!tri_setup(pos, tri, b, t, V, s)) continue;
+        float u, v, zw, S;
+        if (!tri_cover(s, pix_ndc(px, W), pix_ndc_lo(px, W), pix_ndc(py, H), pix_ndc_lo(py, H), u, v, zw, S)) continue;
+        const unsigned long long key = ((unsigned long long)ordered_bits(zw) << 32) | (unsigned)t;
+        atomicMin(keys + ((long long)b * H + py) * W + px, key);
+    }
+}
+
+__global__ __launch_bounds__(RS_BLOCK) void k_rast_resolve(const float* __restrict__ pos, const int* __restrict__ tri,
+                                                           int B, int V, int T, int H, int W,
+                                                           const unsigned long long* __restrict__ keys,
+                                                           float* __restrict__ rast) {
+    const long long p = (long long)blockIdx.x * RS_BLOCK + threadIdx.x;
+    if (p >= (long long)B * H * W) return;
+    const int b = (int)(p / ((long long)H * W));
+    const int rem = (int)(p % ((long long)H * W));
+    const int py = rem / W, px = rem % W;
+    float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
+    const unsigned long long key = keys[p];
+    if (key != ~0ull) {
+        const int t = (int)(unsigned)(key & 0xffffffffu);
+        TriSetup s;
+        float u, v, zw, S;
+        if (t < T && tri_setup(pos, tri, b, t, V, s) && tri_cover(s, pix_ndc(px, W), pix_ndc_lo(px, W), pix_ndc(py, H), pix_ndc_lo(py, H), u, v, zw, S))
+            out = make_float4(u, v, zw, (float)(t + 1));
+    }
+    reinterpret_cast<float4*>(rast)[p] = out;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// rasterize backward: d(u, v) / d(x, y, w) of the three vertices (z receives nothing)
+
+__device__ __forceinline__ int pix_tri(float id, int T) {
+    // id channel: tri + 1 (0 = empty); anything that is not a valid id is empty.  (Clamped in float, then ONE
+    // compare and select: a select on two combined compares is the lane-mask shape tools/mask_hazard_lint.py flags.)
+    const int t = (int)fminf(fmaxf(id, 0.f), 33554432.f) - 1;
+    return t >= T ? -1 : t;
+}
+
+__global__ __launch_bounds__(RS_BLOCK) void k_rast_bwd(const float* __restrict__ pos, const int* __restrict__ tri,
+                                                       const float* __restrict__ rast,
+                                                       const float* __restrict__ grad_rast, int B, int V, int T, int H,
+                                                       int W, float* __restrict__ grad_pos) {
+    const long long p = (long long)blockIdx.x * RS_BLOCK + threadIdx.x;
+    if (p >= (long long)B * H * W) return;
+    const float4 r = reinterpret_cast<const float4*>(rast)[p];
+    const int t = pix_tri(r.w, T);
+    if (t < 0) return;
+    const float4 g = reinterpret_cast<const float4*>(grad_rast)[p];
+    if (g.x == 0.f && g.y == 0.f) return;
+    const int b = (int)(p / ((long long)H * W));
+    const int rem = (int)(p % ((long long)H * W));
+    const int py = rem / W, px = rem % W;
+    TriSetup s;
+    float u, v, zw, sum;
+    if (!tri_setup(pos, tri, b, t, V, s)) return;
+    if (!tri_cover(s, pix_ndc(px, W), pix_ndc_lo(px, W), pix_ndc(py, H), pix_ndc_lo(py, H), u, v, zw, sum)) return;
+    const float base = g.x * u + g.y * v;
+    float ge[3];  // d loss / d e_k, e_k = (v_i x v_j) . p in cyclic order (u = sign(D) e_0 / sum, v likewise)
+    ge[0] = s.sd * (g.x - base) / sum;
+    ge[1] = s.sd * (g.y - base) / sum;
+    ge[2] = s.sd * (-base) / sum;
+    const float P[3] = {pix_ndc(px, W), pix_ndc(py, H), 1.f};
+    float acc[3][3] = {};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int i = (k + 1) % 3, j = (k + 2) % 3;
+        float c[3];
+        // d e_k / d v_i = v_j x p ; d e_k / d v_j = p x v_i
+        cross3(s.x[j], s.y[j], s.w[j], P[0], P[1], P[2], c);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) acc[i][q] += ge[k] * c[q];
+        cross3(P[0], P[1], P[2], s.x[i], s.y[i], s.w[i], c);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) acc[j][q] += ge[k] * c[q];
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        float* gp = grad_pos + ((long long)b * V + s.idx[k]) * 4;
+        atomicAdd(gp + 0, acc[k][0]);
+        atomicAdd(gp + 1, acc[k][1]);
+        atomicAdd(gp + 3, acc[k][2]);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// interpolate
+
+__global__ __launch_bounds__(RS_BLOCK) void k_interp_fwd(const float* __restrict__ attr, int attr_batch,
+                                                         const float* __restrict__ rast, const int* __restrict__ tri,
+                                                         int B, int V, int T, int H, int W, int C,
+                                                         float* __restrict__ out) {
+    const long long p = (long long)blockIdx.x * RS_BLOCK + threadIdx.x;
+    if (p >= (long long)B * H * W) return;
+    const float4 r = reinterpret_cast<const float4*>(rast)[p];
+    const int t = pix_tri(r.w, T);
+    int idx[3];
+    float* o = out + p * C;
+    if (t < 0 || !tri_indices(tri, t, V, idx)) {
+        for (int c = 0; c < C; ++c) o[c] = 0.f;
+        return;
+    }
+    const int b = (int)(p / ((long long)H * W));
+    const long long ab = attr_batch == 1 ? 0 : b;
+    const float w2 = 1.f - r.x - r.y;
+    const float* a0 = attr + (ab * V + idx[0]) * C;
+    const float* a1 = attr + (ab * V + idx[1]) * C;
+    const float* a2 = attr + (ab * V + idx[2]) * C;
+    for (int c = 0; c < C; ++c) o[c] = (r.x * a0[c] + r.y * a1[c]) + w2 * a2[c];
+}
+
+__global__ __launch_bounds__(RS_BLOCK) void k_interp_bwd(const float* __restrict__ attr, int attr_batch,
+                                                         const float* __restrict__ rast, const int* __restrict__ tri,
+                                                         const float* __restrict__ grad_out, int B, int V, int T,
+                                                         int H, int W, int C, float* __restrict__ grad_attr,
+                                                         float* __restrict__ grad_rast) {
+    const long long p = (long long)blockIdx.x * RS_BLOCK + threadIdx.x;
+    if (p >= (long long)B * H * W) return;
+    const float4 r = reinterpret_cast<const float4*>(rast)[p];
+    const int t = pix_tri(r.w, T);
+    int idx[3];
+    float gu = 0.f, gv = 0.f;
+    if (t >= 0 && tri_indices(tri, t, V, idx)) {
+        const int b = (int)(p / ((long long)H * W));
+        const long long ab = attr_batch == 1 ? 0 : b;
+        const float w2 = 1.f - r.x - r.y;
+        const float* a0 = attr + (ab * V + idx[0]) * C;
+        const float* a1 = attr + (ab * V + idx[1]) * C;
+        const float* a2 = attr + (ab * V + idx[2]) * C;
+        float* g0 = grad_attr ? grad_attr + (ab * V + idx[0]) * C : nullptr;
+        float* g1 = grad_attr ? grad_attr + (ab * V + idx[1]) * C : nullptr;
+        float* g2 = grad_attr ? grad_attr + (ab * V + idx[2]) * C : nullptr;
+        const float* go = grad_out + p * C;
+        for (int c = 0; c < C; ++c) {
+            const float g = go[c];
+            gu += g * (a0[c] - a2[c]);
+            gv += g * (a1[c] - a2[c]);
+            if (g0 && g != 0.f) {
+                atomicAdd(g0 + c, r.x * g);
+                atomicAdd(g1 + c, r.y * g);
+                atomicAdd(g2 + c, w2 * g);
+            }
+        }
+    }
+    if (grad_rast) reinterpret_cast<float4*>(grad_rast)[p] = make_float4(gu, gv, 0.f, 0.f);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// antialias (Laine et al. 2020, section 4.3; contract in tt_abi.h)
+
+struct AaCtx {
+    const float* rast;
+    const float* pos;
+    const int* tri;
+    const int* edge_ofs;  // (3T, 2): first sorted slot, count of the edge group of triangle edge 3t + k
+    const int* edge_tri;  // (3T): triangle of each sorted slot
+    int B, V, T, H, W;
+};
+
+struct AaPair {
+    int a_first;  // 1: the occluder's pixel a is the pair's first (left / top) pixel
+    float s;      // crossing distance from a's centre, in pixels, [0, 1)
+    int k;        // edge of the occluder: vertices k, (k + 1) % 3
+    int t;        // occluder
+};
+
+__device__ __forceinline__ float vtx_pix(float c, float w, int N) { return ((c / w + 1.f) * (float)N) * 0.5f - 0.5f; }
+
+__device__ bool aa_silhouette(const AaCtx& cx, int b, int t, int k, float ot) {
+    const int slot = 3 * t + k;
+    const int first = cx.edge_ofs[2 * slot], cnt = cx.edge_ofs[2 * slot + 1];
+    if (first < 0 || cnt < 1 || (long long)first + cnt > 3ll * cx.T) return false;  // malformed topology: no edge
+    bool other = false;
+    for (int j = first; j < first + cnt; ++j) {
+        const int u = cx.edge_tri[j];
+        if (u == t || (unsigned)u >= (unsigned)cx.T) continue;
+        other = true;
+        if (tri_orient(cx.pos, cx.tri, b, u, cx.V) * ot < 0.f) return true;
+    }
+    return !other;
+}
+
+// the pair (first, second) of view b, first = the left (horiz) or upper pixel; false: the pair changes nothing
+__device__ bool aa_pair(const AaCtx& cx, int b, int fx, int fy, bool horiz, AaPair& pr) {
+    const int sx = fx + (horiz ? 1 : 0), sy = fy + (horiz ? 0 : 1);
+    const long long pf = ((long long)b * cx.H + fy) * cx.W + fx, ps = ((long long)b * cx.H + sy) * cx.W + sx;
+    const float4 rf = reinterpret_cast<const float4*>(cx.rast)[pf];
+    const float4 rs = reinterpret_cast<const float4*>(cx.rast)[ps];
+    const int tf = pix_tri(rf.w, cx.T), ts = pix_tri(rs.w, cx.T);
+    if (tf == ts) return false;
+    // occluder: the smaller depth key (z/w, then id), an empty pixel's key is the largest (one 64-bit compare)
+    const unsigned long long kf = tf < 0 ? ~0ull : ((unsigned long long)ordered_bits(rf.z) << 32) | (unsigned)tf;
+    const unsigned long long ks = ts < 0 ? ~0ull : ((unsigned long long)ordered_bits(rs.z) << 32) | (unsigned)ts;
+    const bool a_first = kf < ks;
+    const int t = a_first ? tf : ts;
+    int idx[3];
+    if (!tri_indices(cx.tri, t, cx.V, idx)) return false;
+    float4 v[3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) v[q] = vtx(cx.pos, b, cx.V, idx[q]);
+    const float ot = tri_orient(cx.pos, cx.tri, b, t, cx.V);
+    // a's centre along the pair axis, the direction to b, and the perpendicular (scanline) coordinate
+    const float al = horiz ? (float)(a_first ? fx : sx) : (float)(a_first ? fy : sy);
+    const float dir = a_first ? 1.f : -1.f;
+    const float q0 = horiz ? (float)fy : (float)fx;
+    float best = 1.f;
+    int bk = -1;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float4 e0 = v[k], e1 = v[(k + 1) % 3];
+        if (!(e0.w > 0.f) || !(e1.w > 0.f)) continue;
+        const float l0 = horiz ? vtx_pix(e0.x, e0.w, cx.W) : vtx_pix(e0.y, e0.w, cx.H);
+        const float l1 = horiz ? vtx_pix(e1.x, e1.w, cx.W) : vtx_pix(e1.y, e1.w, cx.H);
+        const float p0 = horiz ? vtx_pix(e0.y, e0.w, cx.H) : vtx_pix(e0.x, e0.w, cx.W);
+        const float p1 = horiz ? vtx_pix(e1.y, e1.w, cx.H) : vtx_pix(e1.x, e1.w, cx.W);
+        if ((p0 > q0) == (p1 > q0)) continue;  // half-open in the perpendicular axis
+        const float r = (q0 - p0) / (p1 - p0);
+        const float lc = l0 + r * (l1 - l0);
+        const float s = (lc - al) * dir;
+        if (!(s >= 0.f && s < best)) continue;
+        if (!aa_silhouette(cx, b, t, k, ot)) continue;
+        best = s;
+        bk = k;
+    }
+    if (bk < 0) return false;
+    pr.a_first = a_first ? 1 : 0;
+    pr.s = best;
+    pr.k = bk;
+    pr.t = t;
+    return true;
+}
+
+// the pairs of pixel (x, y) in a fixed order: left, right, up, down.  Returns the pair's first pixel and axis.
+__device__ __forceinline__ bool aa_pair_of(int n, int x, int y, int W, int H, int& fx, int& fy, bool& horiz,
+                                           bool& self_first) {
+    switch (n) {
+        case 0: fx = x - 1; fy = y; horiz = true; self_first = false; return x > 0;
+        case 1: fx = x; fy = y; horiz = true; self_first = true; return x + 1 < W;
+        case 2: fx = x; fy = y - 1; horiz = false; self_first = false; return y > 0;
+        default: fx = x; fy = y; horiz = false; self_first = true; return y + 1 < H;
+    }
+}
+
+__global__ __launch_bounds__(RS_BLOCK) void k_aa_fwd(AaCtx cx, const float* __restrict__ color, int C,
+                                                     float* __restrict__ out) {
+    const long long p = (long long)blockIdx.x * RS_BLOCK + threadIdx.x;
+    if (p >= (long long)cx.B * cx.H * cx.W) return;
+    const int b = (int)(p / ((long long)cx.H * cx.W));
+    const int rem = (int)(p % ((long long)cx.H * cx.W));
+    const int y = rem / cx.W, x = rem % cx.W;
+    const float* cs = color + p * C;
+    float* o = out + p * C;
+    for (int c = 0; c < C; ++c) o[c] = cs[c];
+    for (int n = 0; n < 4; ++n) {
+        int fx, fy;
+        bool horiz, self_first;
+        if (!aa_pair_of(n, x, y, cx.W, cx.H, fx, fy, horiz, self_first)) continue;
+        AaPair pr;
+        if (!aa_pair(cx, b, fx, fy, horiz, pr)) continue;
+        const bool m_first = pr.a_first ? (pr.s < 0.5f) : !(pr.s < 0.5f);  // the pixel the pair changes
+        if (m_first != self_first) continue;
+        const float alpha = pr.s < 0.5f ? 0.5f - pr.s : pr.s - 0.5f;
+        const long long po = self_first ? p + (horiz ? 1 : cx.W) : p - (horiz ? 1 : cx.W);
+        const float* co = color + po * C;
+        for (int c = 0; c < C; ++c) o[c] += alpha * (co[c] - cs[c]);
+    }
+}
+
+__global__ __launch_bounds__(RS_BLOCK) void k_aa_bwd(AaCtx cx, const float* __restrict__ color, int C,
+                                                     const float* __restrict__ grad_out,
+                                                     float* __restrict__ grad_color, float* __restrict__ grad_pos) {
+    const long long p = (long long)blockIdx.x * RS_BLOCK + threadIdx.x;
+    if (p >= (long long)cx.B * cx.H * cx.W) return;
+    const int b = (int)(p / ((long long)cx.H * cx.W));
+    const int rem = (int)(p % ((long long)cx.H * cx.W));
+    const int y = rem / cx.W, x = rem % cx.W;
+    const float* gs = grad_out + p * C;
+    float* gc = grad_color + p * C;
+    for (int c = 0; c < C; ++c) gc[c] = gs[c];
+    for (int n = 0; n < 4; ++n) {
+        int fx, fy;
+        bool horiz, self_first;
+        if (!aa_pair_of(n, x, y, cx.W, cx.H, fx, fy, horiz, self_first)) continue;
+        AaPair pr;
+        if (!aa_pair(cx, b, fx, fy, horiz, pr)) continue;
+        const bool m_first = pr.a_first ? (pr.s < 0.5f) : !(pr.s < 0.5f);
+        const float alpha = pr.s < 0.5f ? 0.5f - pr.s : pr.s - 0.5f;
+        const long long po = self_first ? p + (horiz ? 1 : cx.W) : p - (horiz ? 1 : cx.W);
+        if (m_first != self_first) {  // the other pixel m is changed by alpha (c_self - c_m)
+            const float* gm = grad_out + po * C;
+            for (int c = 0; c < C; ++c) gc[c] += alpha * gm[c];
+            continue;
+        }
+        // this pixel is m: out[m] += alpha (c_o - c_m)
+        for (int c = 0; c < C; ++c) gc[c] -= alpha * gs[c];
+        if (!grad_pos) continue;
+        // d out[m] / d s = c_a - c_b
+        const bool self_is_a = pr.a_first ? self_first : !self_first;
+        const float* ca = color + (self_is_a ? p : po) * C;
+        const float* cb = color + (self_is_a ? po : p) * C;
+        float gsum = 0.f;
+        for (int c = 0; c < C; ++c) gsum += gs[c] * (ca[c] - cb[c]);
+        if (gsum == 0.f) continue;
+        // s = (l0 + r (l1 - l0) - al) dir, r = (q0 - p0) / (p1 - p0); l / p pixel coordinates of the edge ends
+        int idx[3];
+        tri_indices(cx.tri, pr.t, cx.V, idx);  // valid: aa_pair checked it
+        const int i0 = idx[pr.k], i1 = idx[(pr.k + 1) % 3];
+        const float4 e0 = vtx(cx.pos, b, cx.V, i0), e1 = vtx(cx.pos, b, cx.V, i1);
+        const int Nl = horiz ? cx.W : cx.H, Np = horiz ? cx.H : cx.W;
+        const float cl0 = horiz ? e0.x : e0.y, cl1 = horiz ? e1.x : e1.y;
+        const float cp0 = horiz ? e0.y : e0.x, cp1 = horiz ? e1.y : e1.x;
+        const float l0 = vtx_pix(cl0, e0.w, Nl), l1 = vtx_pix(cl1, e1.w, Nl);
+        const float p0 = vtx_pix(cp0, e0.w, Np), p1 = vtx_pix(cp1, e1.w, Np);
+        const float q0 = horiz ? (float)fy : (float)fx;
+        const float dp = p1 - p0, r = (q0 - p0) / dp, dl = l1 - l0;
+        const float dir = pr.a_first ? 1.f : -1.f;
+        const float g = gsum * dir;
+        const float g_l0 = g * (1.f - r), g_l1 = g * r;
+        const float g_p0 = g * dl * (r - 1.f) / dp, g_p1 = -g * dl * r / dp;
+        // pixel coordinate c -> ((c / w + 1) N) / 2 - 1/2:  d/dc = N / (2 w),  d/dw = -c N / (2 w^2)
+        const float hl = 0.5f * (float)Nl, hp = 0.5f * (float)Np;
+        const float gcl0 = g_l0 * hl / e0.w, gcl1 = g_l1 * hl / e1.w;
+        const float gcp0 = g_p0 * hp / e0.w, gcp1 = g_p1 * hp / e1.w;
+        const float gw0 = -(gcl0 * cl0 + gcp0 * cp0) / e0.w, gw1 = -(gcl1 * cl1 + gcp1 * cp1) / e1.w;
+        float* gp0 = grad_pos + ((long long)b * cx.V + i0) * 4;
+        float* gp1 = grad_pos + ((long long)b * cx.V + i1) * 4;
+        atomicAdd(gp0 + (horiz ? 0 : 1), gcl0);
+        atomicAdd(gp0 + (horiz ? 1 : 0), gcp0);
+        atomicAdd(gp0 + 3, gw0);
+        atomicAdd(gp1 + (horiz ? 0 : 1), gcl1);
+        atomicAdd(gp1 + (horiz ? 1 : 0), gcp1);
+        atomicAdd(gp1 + 3, gw1);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// C ABI
+
+static bool rs_dims_ok(int B, int V, int T, int H, int W) {
+    return B >= 1 && V >= 0 && T >= 0 && T < TT_RAST_MAX_TRIS && H >= 1 && W >= 1 &&
+           (long long)B * H * W < (1ll << 40);
+}
+
+static unsigned rs_blocks(long long n) { return (unsigned)((n + RS_BLOCK - 1) / RS_BLOCK); }
+
+extern "C" int64_t tt_rast_workspace_bytes(int32_t B, int32_t T, int32_t H, int32_t W) {
+    if (!rs_dims_ok(B, 0, T, H, W)) return TT_ERR_BAD_ARG;
+    return rast_layout(B, T, H, W).bytes;
+}
+
+extern "C" int tt_rast_fwd(const float* pos, const int32_t* tri, int32_t B, int32_t V, int32_t T, int32_t H,
+                           int32_t W, void* workspace, float* rast, void* stream) {
+    if (!rs_dims_ok(B, V, T, H, W) || !workspace || !rast || (V > 0 && !pos) || (T > 0 && !tri))
+        return TT_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const long long npix = (long long)B * H * W;
+    if (T == 0 || V == 0) {
+        if (hipMemsetAsync(rast, 0, (size_t)npix * 16, st) != hipSuccess) return TT_ERR_LAUNCH;
+        return tt_check_launch();
+    }
+    const RastLayout l = rast_layout(B, T, H, W);
+    char* ws = (char*)workspace;
+    int4* bbox = (int4*)(ws + l.off_bbox);
+    long long* offs = (long long*)(ws + l.off_offs);
+    long long* bsum = (long long*)(ws + l.off_bsum);
+    unsigned long long* keys = (unsigned long long*)(ws + l.off_keys);
+    // the counts are written into offs[] and scanned in place (k_scan_apply reads each count before it writes it)
+    if (hipMemsetAsync(keys, 0xff, (size_t)npix * 8, st) != hipSuccess) return TT_ERR_LAUNCH;
+    hipLaunchKernelGGL(k_rast_setup, dim3(rs_blocks(l.n)), dim3(RS_BLOCK), 0, st, pos, (const int*)tri, B, V, T, H, W,
+                       bbox, offs);
+    hipLaunchKernelGGL(k_scan_reduce, dim3((unsigned)l.nblk), dim3(RS_BLOCK), 0, st, offs, l.n, bsum);
+    hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(RS_BLOCK), 0, st, bsum, l.nblk, offs, l.n);
+    hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)l.nblk), dim3(RS_BLOCK), 0, st, offs, l.n, bsum, offs);
+    int cus = tt_num_cus();
+    if (cus <= 0) cus = 256;
+    hipLaunchKernelGGL(k_rast_cover, dim3((unsigned)cus * 8), dim3(RS_BLOCK), 0, st, pos, (const int*)tri, V, T, H, W,
+                       bbox, offs, l.n, keys);
+    hipLaunchKernelGGL(k_rast_resolve, dim3(rs_blocks(npix)), dim3(RS_BLOCK), 0, st, pos, (const int*)tri, B, V, T, H,
+                       W, keys, rast);
+    return tt_check_launch();
+}
+
+extern "C" int tt_rast_bwd(const float* pos, const int32_t* tri, const float* rast, const float* grad_rast, int32_t B,
+                           int32_t V, int32_t T, int32_t H, int32_t W, float* grad_pos, void* stream) {
+    if (!rs_dims_ok(B, V, T, H, W) || !rast || !grad_rast || (V > 0 && (!pos || !grad_pos)) || (T > 0 && !tri))
+        return TT_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (V == 0) return TT_OK;
+    if (hipMemsetAsync(grad_pos, 0, (size_t)B * V * 16, st) != hipSuccess) return TT_ERR_LAUNCH;
+    if (T == 0) return tt_check_launch();
+    hipLaunchKernelGGL(k_rast_bwd, dim3(rs_blocks((long long)B * H * W)), dim3(RS_BLOCK), 0, st, pos, (const int*)tri,
+                       rast, grad_rast, B, V, T, H, W, grad_pos);
+    return tt_check_launch();
+}
+
+extern "C" int tt_interp_fwd(const float* attr, int32_t attr_batch, const float* rast, const int32_t* tri, int32_t B,
+                             int32_t V, int32_t T, int32_t H, int32_t W, int32_t C, float* out, void* stream) {
+    if (!rs_dims_ok(B, V, T, H, W) || C < 1 || !rast || !out || (V > 0 && !attr) || (T > 0 && !tri) ||
+        (attr_batch != 1 && attr_batch != B))
+        return TT_ERR_BAD_ARG;
+    hipLaunchKernelGGL(k_interp_fwd, dim3(rs_blocks((long long)B * H * W)), dim3(RS_BLOCK), 0, (hipStream_t)stream,
+                       attr, attr_batch, rast, (const int*)tri, B, V, T, H, W, C, out);
+    return tt_check_launch();
+}
+
+extern "C" int tt_interp_bwd(const float* attr, int32_t attr_batch, const float* rast, const int32_t* tri,
+                             const float* grad_out, int32_t B, int32_t V, int32_t T, int32_t H, int32_t W, int32_t C,
+                             float* grad_attr, float* grad_rast, void* stream) {
+    if (!rs_dims_ok(B, V, T, H, W) || C < 1 || !rast || !grad_out || (V > 0 && !attr) || (T > 0 && !tri) ||
+        (attr_batch != 1 && attr_batch != B) || (!grad_attr && !grad_rast))
+        return TT_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (grad_attr && V > 0 &&
+        hipMemsetAsync(grad_attr, 0, (size_t)attr_batch * V * C * 4, st) != hipSuccess)
+        return TT_ERR_LAUNCH;
+    hipLaunchKernelGGL(k_interp_bwd, dim3(rs_blocks((long long)B * H * W)), dim3(RS_BLOCK), 0, st, attr, attr_batch,
+                       rast, (const int*)tri, grad_out, B, V, T, H, W, C, V > 0 ? grad_attr : nullptr, grad_rast);
+    return tt_check_launch();
+}
+
+static bool aa_args_ok(const float* color, const float* rast, const float* pos, const int32_t* tri,
+                       const int32_t* edge_ofs, const int32_t* edge_tri, int B, int V, int T, int H, int W, int C) {
+    return rs_dims_ok(B, V, T, H, W) && C >= 1 && color && rast && (V > 0 || T == 0) && (V == 0 || pos) &&
+           (T == 0 || (tri && edge_ofs && edge_tri));
+}
+
+extern "C" int tt_aa_fwd(const float* color, const float* rast, const float* pos, const int32_t* tri,
+                         const int32_t* edge_ofs, const int32_t* edge_tri, int32_t B, int32_t V, int32_t T, int32_t H,
+                         int32_t W, int32_t C, float* out, void* stream) {
+    if (!aa_args_ok(color, rast, pos, tri, edge_ofs, edge_tri, B, V, T, H, W, C) || !out) return TT_ERR_BAD_ARG;
+    const AaCtx cx{rast, pos, (const int*)tri, (const int*)edge_ofs, (const int*)edge_tri, B, V, T, H, W};
+    hipLaunchKernelGGL(k_aa_fwd, dim3(rs_blocks((long long)B * H * W)), dim3(RS_BLOCK), 0, (hipStream_t)stream, cx,
+                       color, C, out);
+    return tt_check_launch();
+}
+
+extern "C" int tt_aa_bwd(const float* color, const float* rast, const float* pos, const int32_t* tri,
+                         const int32_t* edge_ofs, const int32_t* edge_tri, const float* grad_out, int32_t B,
+                         int32_t V, int32_t T, int32_t H, int32_t W, int32_t C, float* grad_color, float* grad_pos,
+                         void* stream) {
+    if (!aa_args_ok(color, rast, pos, tri, edge_ofs, edge_tri, B, V, T, H, W, C) || !grad_out || !grad_color)
+        return TT_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (grad_pos && V > 0 && hipMemsetAsync(grad_pos, 0, (size_t)B * V * 16, st) != hipSuccess) return TT_ERR_LAUNCH;
+    const AaCtx cx{rast, pos, (const int*)tri, (const int*)edge_ofs, (const int*)edge_tri, B, V, T, H, W};
+    hipLaunchKernelGGL(k_aa_bwd, dim3(rs_blocks((long long)B * H * W)), dim3(RS_BLOCK), 0, st, cx, color, C, grad_out,
+                       grad_color, V > 0 ? grad_pos : nullptr);
+    return tt_check_launch();
+}

@@ -1,0 +1,240 @@
+"""Differentiable rasterization on the HIP kernels of tt_raster.hip (include/tt_abi.h, "rasterize / interpolate /
+antialias"): the drop-in for nvdiffrast's `rasterize`, `interpolate` and `antialias` in instance mode, and
+`RasterizerContext`, a drop-in for threestudio's `NVDiffRasterizerContext` (threestudio/utils/rasterize.py).
+
+    from triplaneturbo_amd.raster import RasterizerContext
+    ctx = RasterizerContext("cuda", device)
+    pos = ctx.vertex_transform(v_pos, mvp)                 # (B,V,4) clip space
+    rast, _ = ctx.rasterize(pos, tri, (H, W))              # (B,H,W,4) = (u, v, z/w, tri + 1)
+    feat, _ = ctx.interpolate(pos, rast, tri)              # (B,H,W,4)
+    img = ctx.antialias(color, rast, pos, tri)             # (B,H,W,C)
+
+No rast_db / diff_attrs (mip texturing), no range mode, no texture(); there is no CPU path."""
+from __future__ import annotations
+
+from typing import Optional, Tuple, Union
+
+import torch
+
+from . import _lib
+from .ops import _chk, _ptr, _stream
+
+Tensor = torch.Tensor
+MAX_TRIS = 1 << 24  # TT_RAST_MAX_TRIS: tri + 1 is stored as a float
+
+
+def _check_tri(tri: Tensor) -> Tensor:
+    tri = _chk(tri, "tri", dtype=torch.int32)
+    if tri.dim() != 2 or tri.shape[1] != 3:
+        raise ValueError(f"tri must be (T,3), got {tuple(tri.shape)}")
+    if tri.shape[0] >= MAX_TRIS:
+        raise ValueError(f"{tri.shape[0]} triangles: at most {MAX_TRIS - 1} (the id channel is a float)")
+    return tri
+
+
+def _check_rast(rast: Tensor) -> Tensor:
+    rast = _chk(rast, "rast")
+    if rast.dim() != 4 or rast.shape[-1] != 4:
+        raise ValueError(f"rast must be (B,H,W,4), got {tuple(rast.shape)}")
+    return rast
+
+
+def edge_topology(tri: Tensor, n_vertices: Optional[int] = None) -> Tuple[Tensor, Tensor]:
+    """The edge -> triangles table antialias() needs (tt_abi.h "topology"): edge_ofs (3T,2) int32 = (first, count)
+    of the group of triangle edge 3t + k (vertices k, (k+1) % 3) in the sorted edge list, edge_tri (3T) int32 = the
+    triangle of each sorted entry.  Depends on tri only (torch sort as plumbing): build it once per mesh."""
+    T = tri.shape[0]
+    dev = tri.device
+    if T == 0:
+        return torch.zeros((0, 2), dtype=torch.int32, device=dev), torch.zeros(0, dtype=torch.int32, device=dev)
+    a = tri.long()
+    b = a[:, [1, 2, 0]]
+    lo, hi = torch.minimum(a, b), torch.maximum(a, b)
+    n = int(n_vertices) if n_vertices is not None else int(a.max().item()) + 1
+    key = (lo * max(n, 1) + hi).reshape(-1)
+    skey, perm = torch.sort(key, stable=True)
+    _, inverse, counts = torch.unique_consecutive(skey, return_inverse=True, return_counts=True)
+    starts = torch.cumsum(counts, 0) - counts
+    ofs = torch.empty((3 * T, 2), dtype=torch.int32, device=dev)
+    ofs[perm, 0] = starts[inverse].int()
+    ofs[perm, 1] = counts[inverse].int()
+    return ofs.contiguous(), (perm // 3).int().contiguous()
+
+
+class _RasterizeFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pos, tri, H, W):
+        B, V, _ = pos.shape
+        T = tri.shape[0]
+        lib = _lib.load()
+        nbytes = lib.tt_rast_workspace_bytes(B, T, H, W)
+        _lib.check(int(nbytes) if nbytes < 0 else 0, "tt_rast_workspace_bytes")
+        ws = torch.empty(int(nbytes), device=pos.device, dtype=torch.uint8)
+        rast = torch.empty((B, H, W, 4), device=pos.device, dtype=torch.float32)
+        _lib.check(lib.tt_rast_fwd(_ptr(pos), _ptr(tri), B, V, T, H, W, _ptr(ws), _ptr(rast), _stream()),
+                   "tt_rast_fwd")
+        ctx.save_for_backward(pos, tri, rast)
+        return rast
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_rast):
+        pos, tri, rast = ctx.saved_tensors
+        if g_rast is None or not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        B, V, _ = pos.shape
+        H, W = rast.shape[1], rast.shape[2]
+        g_pos = torch.empty_like(pos)
+        _lib.check(_lib.load().tt_rast_bwd(_ptr(pos), _ptr(tri), _ptr(rast), _ptr(g_rast.contiguous()), B, V,
+                                           tri.shape[0], H, W, _ptr(g_pos), _stream()), "tt_rast_bwd")
+        return g_pos, None, None, None
+
+
+def rasterize(pos: Tensor, tri: Tensor, resolution: Union[int, Tuple[int, int]]) -> Tensor:
+    """rast (B,H,W,4) = (u, v, z/w, tri + 1), 0 where empty.  pos (B,V,4) clip space, tri (T,3) int32.
+    Differentiable w.r.t. pos through u, v (dr.rasterize without rast_db)."""
+    H, W = (resolution, resolution) if isinstance(resolution, int) else (int(resolution[0]), int(resolution[1]))
+    if H < 1 or W < 1:
+        raise ValueError(f"resolution must be positive, got {(H, W)}")
+    pos = _chk(pos, "pos")
+    if pos.dim() != 3 or pos.shape[-1] != 4 or pos.shape[0] < 1:
+        raise ValueError(f"pos must be (B,V,4) with B >= 1, got {tuple(pos.shape)}")
+    return _RasterizeFn.apply(pos, _check_tri(tri), H, W)
+
+
+class _InterpolateFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, attr, rast, tri):
+        A, V, C = attr.shape
+        B, H, W, _ = rast.shape
+        out = torch.empty((B, H, W, C), device=attr.device, dtype=torch.float32)
+        _lib.check(_lib.load().tt_interp_fwd(_ptr(attr), A, _ptr(rast), _ptr(tri), B, V, tri.shape[0], H, W, C,
+                                             _ptr(out), _stream()), "tt_interp_fwd")
+        ctx.save_for_backward(attr, rast, tri)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out):
+        attr, rast, tri = ctx.saved_tensors
+        A, V, C = attr.shape
+        B, H, W, _ = rast.shape
+        g_attr = torch.empty_like(attr) if ctx.needs_input_grad[0] else None
+        g_rast = torch.empty_like(rast) if ctx.needs_input_grad[1] else None
+        if g_attr is None and g_rast is None:
+            return None, None, None
+        _lib.check(_lib.load().tt_interp_bwd(_ptr(attr), A, _ptr(rast), _ptr(tri), _ptr(g_out.contiguous()), B, V,
+                                             tri.shape[0], H, W, C, _ptr(g_attr), _ptr(g_rast), _stream()),
+                   "tt_interp_bwd")
+        return g_attr, g_rast, None
+
+
+def interpolate(attr: Tensor, rast: Tensor, tri: Tensor, rast_db=None, diff_attrs=None) -> Tensor:
+    """out (B,H,W,C) = u a0 + v a1 + (1-u-v) a2 (0 where empty); attr (B,V,C) or (1,V,C) (broadcast over views).
+    Differentiable w.r.t. attr and rast (its u, v channels).  rast_db / diff_attrs are not supported."""
+    if rast_db is not None or diff_attrs is not None:
+        raise NotImplementedError("rast_db / diff_attrs (attribute derivatives for mip texturing) are not supported")
+    attr = _chk(attr, "attr")
+    rast = _check_rast(rast)
+    if attr.dim() != 3 or attr.shape[0] not in (1, rast.shape[0]) or attr.shape[2] < 1:
+        raise ValueError(f"attr must be (B,V,C) or (1,V,C) with C >= 1, got {tuple(attr.shape)} for B={rast.shape[0]}")
+    return _InterpolateFn.apply(attr, rast, _check_tri(tri))
+
+
+class _AntialiasFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, color, rast, pos, tri, edge_ofs, edge_tri):
+        B, H, W, C = color.shape
+        V = pos.shape[1]
+        out = torch.empty_like(color)
+        _lib.check(_lib.load().tt_aa_fwd(_ptr(color), _ptr(rast), _ptr(pos), _ptr(tri), _ptr(edge_ofs),
+                                         _ptr(edge_tri), B, V, tri.shape[0], H, W, C, _ptr(out), _stream()),
+                   "tt_aa_fwd")
+        ctx.save_for_backward(color, rast, pos, tri, edge_ofs, edge_tri)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out):
+        color, rast, pos, tri, edge_ofs, edge_tri = ctx.saved_tensors
+        if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[2]):
+            return (None,) * 6
+        B, H, W, C = color.shape
+        V = pos.shape[1]
+        g_color = torch.empty_like(color)
+        g_pos = torch.empty_like(pos) if ctx.needs_input_grad[2] else None
+        _lib.check(_lib.load().tt_aa_bwd(_ptr(color), _ptr(rast), _ptr(pos), _ptr(tri), _ptr(edge_ofs),
+                                         _ptr(edge_tri), _ptr(g_out.contiguous()), B, V, tri.shape[0], H, W, C,
+                                         _ptr(g_color), _ptr(g_pos), _stream()), "tt_aa_bwd")
+        return (g_color if ctx.needs_input_grad[0] else None), None, g_pos, None, None, None
+
+
+def antialias(color: Tensor, rast: Tensor, pos: Tensor, tri: Tensor,
+              topology: Optional[Tuple[Tensor, Tensor]] = None) -> Tensor:
+    """Analytic silhouette antialiasing (Laine et al. 2020, section 4.3; tt_abi.h "antialias"): color (B,H,W,C),
+    rast from rasterize(pos, tri), pos (B,V,4).  Differentiable w.r.t. color and pos (none to rast).  `topology`
+    = edge_topology(tri), computed here when not given."""
+    color = _chk(color, "color")
+    rast = _check_rast(rast)
+    pos = _chk(pos, "pos")
+    tri = _check_tri(tri)
+    if color.dim() != 4 or tuple(color.shape[:3]) != tuple(rast.shape[:3]):
+        raise ValueError(f"color must be (B,H,W,C) matching rast {tuple(rast.shape)}, got {tuple(color.shape)}")
+    if pos.dim() != 3 or pos.shape[0] != rast.shape[0] or pos.shape[2] != 4:
+        raise ValueError(f"pos must be (B,V,4) with B={rast.shape[0]}, got {tuple(pos.shape)}")
+    if topology is None:
+        topology = edge_topology(tri, pos.shape[1])
+    edge_ofs = _chk(topology[0], "edge_ofs", (tri.shape[0] * 3, 2), dtype=torch.int32)
+    edge_tri = _chk(topology[1], "edge_tri", (tri.shape[0] * 3,), dtype=torch.int32)
+    return _AntialiasFn.apply(color, rast, pos, tri, edge_ofs, edge_tri)
+
+
+def mesh_topology(mesh) -> Tuple[Tensor, Tensor]:
+    """edge_topology of a Mesh, cached on it (the mesh renderer antialiases about six images per mesh)."""
+    topo = getattr(mesh, "_aa_topology", None)
+    if topo is None:
+        topo = edge_topology(mesh.t_pos_idx.int(), mesh.v_pos.shape[0])
+        mesh._aa_topology = topo
+    return topo
+
+
+class RasterizerContext:
+    """threestudio's NVDiffRasterizerContext (threestudio/utils/rasterize.py) on the HIP kernels: same methods,
+    signatures and tuple returns.  `context_type` ("gl" / "cuda") is accepted and ignored."""
+
+    def __init__(self, context_type: str = "cuda", device: Optional[torch.device] = None) -> None:
+        self.device = device
+        self.context_type = context_type
+        self._topo_tri = None  # the tri tensor the cached table was built from (held, so it cannot be recycled)
+        self._topo_key = None
+        self._topo = None
+
+    def vertex_transform(self, verts: Tensor, mvp_mtx: Tensor) -> Tensor:
+        verts_homo = torch.cat([verts, torch.ones([verts.shape[0], 1]).to(verts)], dim=-1)
+        return torch.matmul(verts_homo, mvp_mtx.permute(0, 2, 1))
+
+    def rasterize(self, pos: Tensor, tri: Tensor, resolution: Union[int, Tuple[int, int]]):
+        """(rast, None): there is no rast_db."""
+        return rasterize(pos.float(), tri.int(), resolution), None
+
+    def rasterize_one(self, pos: Tensor, tri: Tensor, resolution: Union[int, Tuple[int, int]]):
+        rast, _ = self.rasterize(pos[None, ...], tri, resolution)
+        return rast[0], None
+
+    def antialias(self, color: Tensor, rast: Tensor, pos: Tensor, tri: Tensor,
+                  topology: Optional[Tuple[Tensor, Tensor]] = None) -> Tensor:
+        tri = tri.int()
+        if topology is None:  # one cached table: consecutive calls on the same mesh reuse it
+            key = (tri._version, pos.shape[1])
+            if tri is not self._topo_tri or key != self._topo_key:
+                self._topo_tri, self._topo_key, self._topo = tri, key, edge_topology(tri, pos.shape[1])
+            topology = self._topo
+        return antialias(color.float(), rast, pos.float(), tri, topology)
+
+    def interpolate(self, attr: Tensor, rast: Tensor, tri: Tensor, rast_db=None, diff_attrs=None):
+        """(out, empty tensor): there are no attribute derivatives."""
+        out = interpolate(attr.float(), rast, tri.int(), rast_db=rast_db, diff_attrs=diff_attrs)
+        return out, torch.empty(0, device=out.device)
+
+    def interpolate_one(self, attr: Tensor, rast: Tensor, tri: Tensor, rast_db=None, diff_attrs=None):
+        return self.interpolate(attr[None, ...], rast, tri, rast_db, diff_attrs)
