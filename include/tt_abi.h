@@ -58,6 +58,9 @@
  *   tt_mc_*                 marching cubes with a backward pass: the `diso.DiffMC` call of DiffMarchingCubeHelper
  *                           (triplaneturbo_executable/utils/mesh_exporter.py:29-75, isosurface() :78-141;
  *                           threestudio/models/isosurface.py:18-65); diso is a CUDA-only, un-vendored extension.
+ *   tt_mesh_*               Mesh.normal_consistency / laplacian and their backward, Mesh.remove_outlier's connected
+ *                           components and compaction (threestudio/models/mesh.py:31-95,255-308; trimesh on the host
+ *                           in the reference).
  */
 #ifndef TT_ABI_H
 #define TT_ABI_H
@@ -543,6 +546,62 @@ int tt_aa_fwd(const float* color, const float* rast, const float* pos, const int
 int tt_aa_bwd(const float* color, const float* rast, const float* pos, const int32_t* tri, const int32_t* edge_ofs,
               const int32_t* edge_tri, const float* grad_out, int32_t B, int32_t V, int32_t T, int32_t H, int32_t W,
               int32_t C, float* grad_color, float* grad_pos, void* stream);
+
+/* ---- mesh regularisers and outlier removal (tt_mesh.hip): threestudio Mesh.normal_consistency / laplacian /
+ * remove_outlier (threestudio/models/mesh.py:31-95,255-308) ----
+ * A mesh is v_pos (V,3) fp32 and t_pos_idx (T,3) int32 with every index in [0, V) (the host checks it when it builds
+ * the topology; a face with an index outside [0, V) is never kept and never read through).
+ *   topology    built once per mesh on the host side with torch sorts (ops.mesh_topology), from t_pos_idx alone:
+ *               edges (E,2) int32 = the unique rows of sort(each face's (0,1), (1,2), (2,0) pair), ascending
+ *               lexicographic, self pairs (a,a) of degenerate faces included (Mesh._compute_edges);
+ *               face_pairs (P,2) int32 = for every edge that EXACTLY TWO of the 3T face edges use, the two faces;
+ *               the vertex -> neighbour CSR nbr_ptr (V+1), nbr_col (2E) int32 = both directions of every edge, each
+ *               row in ascending column order (a self edge appears twice in its row); nbr_col (and edges) may be
+ *               NULL for a mesh without edges.
+ *   adjacency   two faces are joined iff they share an edge used by exactly two face edges (trimesh's
+ *               face_adjacency rule, group_rows(..., require_count=2)); an edge used once, or three or more times
+ *               (non-manifold), joins nothing.  On an edge-manifold mesh (every tt_mc_* mesh) any rule agrees.
+ *   components  tt_mesh_components: labels (T) int32, label[f] = the smallest face index of f's component
+ *               (independent of scheduling); the workspace keeps the face count per component and the largest count.
+ *   threshold   tt_mesh_compact_count after tt_mesh_components with the same workspace: frac_mode = 1 -> thr =
+ *               (int64)((double)max_faces * frac) (Python's int(max * t)); frac_mode = 0 -> thr = threshold.  A
+ *               face is kept iff its component has >= thr faces; a vertex is kept iff a kept face references it.
+ *   order       kept vertices and kept faces keep their original relative order; t_out holds the new vertex ids.
+ *               (V', T') go to out_totals (2 int32, DEVICE memory, read back: the only host round trip); allocate;
+ *               tt_mesh_compact_emit with the same workspace.  Every write is bounded by those totals.
+ *   empty       T = 0: tt_mesh_components does nothing; the compaction needs T >= 1 (the host returns an empty mesh
+ *               unchanged).
+ *   laplacian   r_i = sum over the neighbours j != i of (v_i - v_j); loss = (1/V) sum_i |r_i| (unreferenced vertices
+ *               count in V with r_i = 0; V = 0 gives NaN like torch's mean).  Backward: g_k = sum over the neighbours
+ *               j != k of (w_k - w_j), w_i = (grad_loss / V) r_i / |r_i| (0 where r_i = 0, torch's subgradient).
+ *   normal c.   loss = (1/E) sum over the edges (a,b) of (1 - cos(n_a, n_b)) with torch.cosine_similarity(dim=-1,
+ *               eps=1e-8): cos = sum_c (x_c / max(|x|, eps)) (y_c / max(|y|, eps)); E = 0 gives NaN.  Backward to
+ *               v_nrm per vertex over its CSR row: d cos / d x = y/(max(|y|,eps) max(|x|,eps)) - cos x/(max(|x|,eps)
+ *               |x|) (the last factor 0 for x = 0), times -grad_loss / E.  The gradient to v_pos is the caller's
+ *               (autograd through its vertex normals).
+ * Determinism: the labels, counts and the compaction use integer atomics only (order-independent); the losses are
+ * fixed-order block partials plus a one-block sum, the gradients CSR gathers: forward values and gradients are
+ * bit-identical from launch to launch.  The losses take no host round trip and allocate nothing (grad_loss is read
+ * on the device), so they are capturable given the topology and workspace.  Every gradient output is overwritten.
+ * Use: bytes = tt_mesh_workspace_bytes(V, T) (one workspace serves all entry points of one mesh); every entry point
+ * validates its arguments before any HIP call (TT_ERR_BAD_ARG). */
+#define TT_MESH_MAX_ITEMS (1 << 28)
+#define TT_MESH_COS_EPS 1e-8f
+int64_t tt_mesh_workspace_bytes(int32_t V, int32_t T);
+int tt_mesh_components(const int32_t* face_pairs, int32_t P, int32_t T, void* workspace, int32_t* labels,
+                       void* stream);
+int tt_mesh_compact_count(const int32_t* t_pos_idx, const int32_t* labels, int32_t V, int32_t T, int32_t frac_mode,
+                          double frac, int64_t threshold, void* workspace, int32_t* out_totals, void* stream);
+int tt_mesh_compact_emit(const float* v_pos, const int32_t* t_pos_idx, int32_t V, int32_t T, void* workspace,
+                         float* v_out, int32_t* t_out, void* stream);
+int tt_mesh_laplacian_fwd(const float* v_pos, const int32_t* nbr_ptr, const int32_t* nbr_col, int32_t V, int32_t T,
+                          void* workspace, float* loss, void* stream);
+int tt_mesh_laplacian_bwd(const float* v_pos, const int32_t* nbr_ptr, const int32_t* nbr_col, int32_t V, int32_t T,
+                          const float* grad_loss, void* workspace, float* grad_v, void* stream);
+int tt_mesh_nc_fwd(const float* v_nrm, const int32_t* edges, int32_t V, int32_t T, int32_t E, void* workspace,
+                   float* loss, void* stream);
+int tt_mesh_nc_bwd(const float* v_nrm, const int32_t* nbr_ptr, const int32_t* nbr_col, int32_t V, int32_t E,
+                   const float* grad_loss, float* grad_nrm, void* stream);
 
 #ifdef __cplusplus
 }

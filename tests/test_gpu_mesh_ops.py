@@ -1,0 +1,231 @@
+"""The tt_mesh_* kernels behind Mesh.edges / normal_consistency() / laplacian() / remove_outlier() against the
+reference's own Mesh (tests/golden/reference_mesh_ops.npz: edges, both losses and their gradients, computed in float64
+by make_golden_mesh_ops.py) and the numpy oracle tests/mesh_reference.py.
+
+remove_outlier has no golden: the reference runs it with trimesh, which is not available here.  Its oracle is the
+contract of include/tt_abi.h ("mesh regularisers and outlier removal") as tests/mesh_reference.py implements it:
+faces joined by an edge that exactly two face edges use, components with >= threshold faces kept, vertices and faces
+in their original order."""
+import json
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import triplaneturbo_amd as tt
+from triplaneturbo_amd import ops
+from triplaneturbo_amd.isosurface import DiffMarchingCubeHelper, Mesh, isosurface
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+import mc_reference as MC  # noqa: E402
+import mesh_reference as M  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+GOLDEN = np.load(os.path.join(HERE, "golden", "reference_mesh_ops.npz"))
+NAMES = sorted({k.rsplit("_v_pos", 1)[0] for k in GOLDEN.files if k.endswith("_v_pos")})
+LOSSES = ("laplacian", "normal_consistency")
+
+
+@pytest.fixture(scope="module")
+def dev():
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    return torch.device("cuda", 0)
+
+
+def _mesh(v, t, dev, grad=False, idx_dtype=torch.int32):
+    vp = torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(dev).requires_grad_(grad)
+    return Mesh(vp, torch.from_numpy(np.asarray(t, dtype=np.int64)).to(dev, idx_dtype).reshape(-1, 3))
+
+
+def _loss_and_grad(v, t, loss_name, dev):
+    m = _mesh(v, t, dev, grad=True)
+    loss = getattr(m, loss_name)()
+    loss.backward()
+    return loss.detach(), m.v_pos.grad
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_edges_match_the_reference(dev, name):
+    v, t = GOLDEN[f"{name}_v_pos"], GOLDEN[f"{name}_t_pos_idx"]
+    want = GOLDEN[f"{name}_edges"]
+    assert np.array_equal(want, M.edges(t))
+    for dt in (torch.int32, torch.int64):
+        e = _mesh(v, t, dev, idx_dtype=dt).edges
+        assert e.dtype == dt and np.array_equal(e.cpu().numpy(), want)
+
+
+@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("loss_name", LOSSES)
+def test_losses_and_gradients_match_the_reference(dev, name, loss_name):
+    v, t = GOLDEN[f"{name}_v_pos"], GOLDEN[f"{name}_t_pos_idx"]
+    loss, grad = _loss_and_grad(v, t, loss_name, dev)
+    want, want_g = float(GOLDEN[f"{name}_{loss_name}"]), GOLDEN[f"{name}_{loss_name}_grad"]
+    o_loss, o_grad = (M.laplacian if loss_name == "laplacian" else M.normal_consistency)(v, t)
+    for ref, ref_g in ((want, want_g), (o_loss, o_grad)):
+        assert abs(loss.item() - ref) <= 1e-5 * abs(ref), (loss.item(), ref)
+        err = np.abs(grad.cpu().numpy().astype(np.float64) - ref_g).max()
+        assert err <= 1e-4 * np.abs(ref_g).max(), (err, np.abs(ref_g).max())
+
+
+@pytest.mark.parametrize("loss_name", LOSSES)
+def test_loss_gradient_against_the_normals_oracle(dev, loss_name):
+    """the HIP backward w.r.t. v_nrm alone (normal consistency) / v_pos (Laplacian) against float64"""
+    v, t = GOLDEN["blobs33_v_pos"], GOLDEN["blobs33_t_pos_idx"]
+    m = _mesh(v, t, dev)
+    x = (m.v_nrm if loss_name == "normal_consistency" else m.v_pos).detach().clone().requires_grad_(True)
+    fn = ops.mesh_normal_consistency_loss if loss_name == "normal_consistency" else ops.mesh_laplacian_loss
+    (fn(x, m.topology) * 3.0).backward()
+    x64 = x.detach().cpu().numpy()
+    _, want = (M.normal_consistency_of_normals if loss_name == "normal_consistency" else M.laplacian)(x64, t)
+    assert np.abs(x.grad.cpu().numpy() - 3.0 * want).max() <= 1e-4 * np.abs(3.0 * want).max()
+
+
+@pytest.mark.parametrize("loss_name", LOSSES)
+def test_launches_are_bit_identical(dev, loss_name):
+    """the HIP forward and backward on a fixed input (v_pos for the Laplacian, v_nrm for normal consistency).  The
+    vertex normals themselves come from Mesh._compute_vertex_normal, whose torch scatter_add_ is not bit-reproducible
+    on the GPU, so the normal-consistency gradient w.r.t. v_pos is only as repeatable as that."""
+    v, t = GOLDEN["blobs33_v_pos"], GOLDEN["blobs33_t_pos_idx"]
+    m = _mesh(v, t, dev)
+    x0 = (m.v_nrm if loss_name == "normal_consistency" else m.v_pos).detach().clone()
+    fn = ops.mesh_normal_consistency_loss if loss_name == "normal_consistency" else ops.mesh_laplacian_loss
+    runs = []
+    for _ in range(2):
+        x = x0.clone().requires_grad_(True)
+        loss = fn(x, m.topology)
+        loss.backward()
+        runs.append((loss.detach(), x.grad))
+    assert torch.equal(runs[0][0], runs[1][0]) and torch.equal(runs[0][1], runs[1][1])
+
+
+def test_empty_and_faceless_losses_follow_torch_mean(dev):
+    m = _mesh(np.zeros((3, 3), np.float32), np.zeros((0, 3), np.int64), dev, grad=True)
+    assert m.edges.shape == (0, 2)
+    lap = m.laplacian()
+    assert lap.item() == 0.0  # every r_i = 0, V = 3
+    lap.backward()
+    assert torch.equal(m.v_pos.grad, torch.zeros_like(m.v_pos))
+    assert torch.isnan(ops.mesh_normal_consistency_loss(m.v_nrm.detach(), m.topology))  # mean over no edges
+
+
+def _check_remove(v, t, thr, dev, idx_dtype=torch.int32):
+    m = _mesh(v, t, dev, idx_dtype=idx_dtype)
+    m.add_extra("tag", 5)
+    out = m.remove_outlier(thr)
+    want_v, want_t = M.remove_small_components(v, t, thr)
+    assert out is not m and out.extras == {"tag": 5}
+    assert out.t_pos_idx.dtype == idx_dtype and out.v_pos.dtype == torch.float32
+    assert np.array_equal(out.v_pos.cpu().numpy(), want_v)
+    assert np.array_equal(out.t_pos_idx.cpu().numpy(), np.asarray(want_t).reshape(-1, 3))
+    return out
+
+
+@pytest.fixture(scope="module")
+def blobs():
+    mc = MC.marching_cubes(M.blobs_field(48))
+    return mc.v_pos, mc.t_pos_idx.astype(np.int64)
+
+
+def test_components_match_the_oracle(dev, blobs):
+    v, t = blobs
+    m = _mesh(v, t, dev)
+    labels = ops.mesh_face_components(m.topology).cpu().numpy()
+    want = M.face_components(t)
+    assert np.array_equal(labels, want)
+    assert len(np.unique(want)) == 5
+
+
+def test_remove_outlier_matches_the_oracle(dev, blobs):
+    v, t = blobs
+    sizes = np.sort(np.bincount(M.face_components(t)))[::-1]
+    sizes = sizes[sizes > 0]
+    n_all = len(t)
+    out = _check_remove(v, t, 0.1, dev)  # the two spheres stay, the blobs go
+    assert 0 < out.t_pos_idx.shape[0] < n_all
+    _check_remove(v, t, int(sizes[2]) + 1, dev, idx_dtype=torch.int64)  # int threshold
+    out = _check_remove(v, t, 0, dev)  # keeps everything
+    assert out.t_pos_idx.shape[0] == n_all and out.v_pos.shape[0] == len(v)
+    out = _check_remove(v, t, 1.0, dev)  # only the largest
+    assert out.t_pos_idx.shape[0] == sizes[0]
+    out = _check_remove(v, t, int(sizes[0]) + 1, dev)  # nothing
+    assert out.t_pos_idx.shape == (0, 3) and out.v_pos.shape == (0, 3)
+
+
+@pytest.mark.parametrize("thr", [1, 2, 3, 0.75, 0.5, 0.0])
+def test_remove_outlier_on_the_non_manifold_hand_mesh(dev, thr):
+    v, t = M.hand_mesh()
+    _check_remove(v, t, thr, dev)
+
+
+def test_remove_outlier_edge_cases(dev):
+    empty = _mesh(np.zeros((4, 3), np.float32), np.zeros((0, 3), np.int64), dev)
+    assert empty.remove_outlier(0.01) is empty
+    v, t = M.hand_mesh()
+    m = _mesh(v, t, dev, grad=True)
+    assert m.remove_outlier(0.5) is m
+
+
+def _mesh_renderer(dev):
+    s = json.load(open(os.path.join(HERE, "golden", "reference_mesh_renderer_config.json")))
+    tc = json.load(open(os.path.join(HERE, "golden", "reference_training_config.json")))
+    g = tt.find(tc["geometry_type"])(tc["geometry"]).to(dev)
+    m = tt.find(tc["material_type"])(tc["material"]).to(dev)
+    b = tt.find(tc["background_type"])(tc["background"]).to(dev)
+    r = tt.find(s["renderer_type"])(s["renderer"], geometry=g, material=m, background=b).to(dev)
+    return r
+
+
+def test_regularisers_through_the_mesh_renderer(dev):
+    from test_gpu_mesh_renderer import _cameras
+    P, n_view, H, W = 2, 2, 64, 64
+    torch.manual_seed(0)
+    r = _mesh_renderer(dev)
+    assert r.cfg.isosurface_resolution == 128
+    r.train()
+    r.update_step(0, 100)
+    cam = _cameras(P * n_view, H, W, dev)
+    cache = (torch.randn(P, 6, 32, 64, 64, device=dev) * 0.3).requires_grad_(True)
+    out = r(cam["mvp_mtx"], cam["camera_positions"], cam["light_positions"], H, W, space_cache=cache,
+            text_embed=torch.randn(P, 1024, device=dev), rays_d_rasterize=cam["rays_d_rasterize"],
+            camera_distances=cam["camera_distances"], c2w=cam["c2w"])
+    # the reference system's loop (multiprompt_dual_renderer_multistep_generator.py:716-757)
+    loss = 0.0
+    for mesh in out["mesh"]:
+        assert mesh.requires_grad and mesh.t_pos_idx.shape[0] > 0
+        loss += mesh.normal_consistency() + mesh.laplacian()
+    assert torch.isfinite(loss)
+    loss.backward()
+    assert cache.grad is not None and torch.isfinite(cache.grad).all() and cache.grad.abs().sum() > 0
+    with torch.no_grad():
+        meshes = r.isosurface(cache)
+    for mesh in meshes:
+        assert not mesh.requires_grad
+        clean = mesh.remove_outlier(0.01)
+        v, t = mesh.v_pos.cpu().numpy(), mesh.t_pos_idx.cpu().numpy()
+        want_v, want_t = M.remove_small_components(v, t, 0.01)
+        cv, ct = clean.v_pos.cpu().numpy(), clean.t_pos_idx.cpu().numpy()
+        assert np.array_equal(cv, want_v) and np.array_equal(ct, want_t)
+        assert ct.size == 0 or (ct.min() >= 0 and ct.max() < len(cv))
+        faces_in = {tuple(map(tuple, f)) for f in v[t].tolist()}
+        assert all(tuple(map(tuple, f)) in faces_in for f in cv[ct].tolist())  # a subset of the input's faces
+
+
+def test_remove_outlier_160_through_isosurface(dev):
+    torch.manual_seed(0)
+    g = tt.find("few-step-triplane-dual-stable-diffusion")({"isosurface_deformable_grid": True}).to(dev)
+    cache = (torch.randn(1, 6, 32, 256, 256, generator=torch.Generator().manual_seed(8)) * 0.5).to(dev)
+    helper = DiffMarchingCubeHelper(160).to(dev)
+    with torch.no_grad():
+        (mesh,) = isosurface(cache, g.forward_field, helper)
+    v, t = mesh.v_pos.cpu().numpy(), mesh.t_pos_idx.cpu().numpy()
+    labels = ops.mesh_face_components(mesh.topology).cpu().numpy()
+    assert np.array_equal(labels, M.face_components(t))
+    for thr in (0.01, 0.5):
+        clean = mesh.remove_outlier(thr)
+        want_v, want_t = M.remove_small_components(v, t, thr)
+        assert np.array_equal(clean.v_pos.cpu().numpy(), want_v)
+        assert np.array_equal(clean.t_pos_idx.cpu().numpy(), want_t)

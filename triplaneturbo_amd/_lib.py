@@ -22,7 +22,7 @@ LIB_PATH = os.path.join(_HERE, "libtt_hip.so")
 # environment variables (profiling ablations and tuning sweeps, tools/).  The product library above never calls getenv.
 _DEFAULT_LIB_PATH = LIB_PATH
 TUNING_LIB_PATH = os.path.join(_HERE, "libtt_hip_tuning.so")
-SOURCES = ["tt_forward.hip", "tt_march.hip", "tt_backward.hip", "tt_backward_tex.hip", "tt_points.hip", "tt_composite.hip", "tt_grad2.hip", "tt_sampler.hip", "tt_hashgrid.hip", "tt_isosurface.hip", "tt_raster.hip", "tt_host.cpp"]
+SOURCES = ["tt_forward.hip", "tt_march.hip", "tt_backward.hip", "tt_backward_tex.hip", "tt_points.hip", "tt_composite.hip", "tt_grad2.hip", "tt_sampler.hip", "tt_hashgrid.hip", "tt_isosurface.hip", "tt_raster.hip", "tt_mesh.hip", "tt_host.cpp"]
 # per-translation-unit flags: the texture backward is faster under hipcc's max-ILP scheduling strategy (3.11 -> 3.02 ms;
 # the other kernels are not); the geometry backward is faster with its transient MFMA results in VGPRs rather than AGPRs
 # (-amdgpu-mfma-vgpr-form: 471 -> 248 v_accvgpr_read, 3.045 -> 2.995 ms; texture backward slower, forward neutral) and
@@ -46,6 +46,8 @@ SYMBOLS = [
     "tt_composite_fwd", "tt_composite_bwd", "tt_eikonal_fwd", "tt_eikonal_bwd", "tt_source_hash",
     "tt_mc_workspace_bytes", "tt_mc_count", "tt_mc_emit", "tt_mc_bwd",
     "tt_rast_workspace_bytes", "tt_rast_fwd", "tt_rast_bwd", "tt_interp_fwd", "tt_interp_bwd", "tt_aa_fwd", "tt_aa_bwd",
+    "tt_mesh_workspace_bytes", "tt_mesh_components", "tt_mesh_compact_count", "tt_mesh_compact_emit",
+    "tt_mesh_laplacian_fwd", "tt_mesh_laplacian_bwd", "tt_mesh_nc_fwd", "tt_mesh_nc_bwd",
 ]
 
 
@@ -360,6 +362,14 @@ def load() -> ctypes.CDLL:
         "tt_interp_bwd": [_P, _I32, _P, _P, _P] + [_I32] * 6 + [_P, _P, _P],
         "tt_aa_fwd": [_P] * 6 + [_I32] * 6 + [_P, _P],
         "tt_aa_bwd": [_P] * 7 + [_I32] * 6 + [_P, _P, _P],
+        "tt_mesh_workspace_bytes": [_I32, _I32],
+        "tt_mesh_components": [_P, _I32, _I32, _P, _P, _P],
+        "tt_mesh_compact_count": [_P, _P, _I32, _I32, _I32, ctypes.c_double, _I64, _P, _P, _P],
+        "tt_mesh_compact_emit": [_P, _P, _I32, _I32, _P, _P, _P, _P],
+        "tt_mesh_laplacian_fwd": [_P, _P, _P, _I32, _I32, _P, _P, _P],
+        "tt_mesh_laplacian_bwd": [_P, _P, _P, _I32, _I32, _P, _P, _P, _P],
+        "tt_mesh_nc_fwd": [_P, _P, _I32, _I32, _I32, _P, _P, _P],
+        "tt_mesh_nc_bwd": [_P, _P, _P, _I32, _I32, _P, _P, _P],
     }
     for name, argtypes in optional.items():
         if name in SYMBOLS:
@@ -370,6 +380,7 @@ def load() -> ctypes.CDLL:
     lib.tt_hashgrid_n_params.restype = ctypes.c_int64
     lib.tt_mc_workspace_bytes.restype = ctypes.c_int64
     lib.tt_rast_workspace_bytes.restype = ctypes.c_int64
+    lib.tt_mesh_workspace_bytes.restype = ctypes.c_int64
     _lib = lib
     return lib
 

@@ -16,6 +16,7 @@
 //                     via table edge -> (owner point, axis) -> block offset + in-block offset + rank of the axis
 //   k_mc_bwd          gather per point over its 6 incident edges: dense grad_level and grad_deformation, no scatter
 #include "tt_host.h"
+#include "tt_scan.h"
 
 #pragma clang fp contract(off)  // the interpolation exactly as written in tt_abi.h (the numpy oracle replays it)
 
@@ -23,7 +24,7 @@
 #include "tt_mc_tables.h"
 
 #define MC_BLOCK 256
-#define MC_SCAN_BLOCK 1024
+#define MC_SCAN_BLOCK TT_SCAN_BLOCK
 
 // base-corner offset (di | dj << 1 | dk << 2) of each of the 12 cube edges (tools/gen_mc_tables.py)
 static __constant__ const unsigned char k_edge_base[12] = {0, 2, 4, 6, 0, 1, 4, 5, 0, 1, 2, 3};
@@ -65,16 +66,6 @@ static McWs mc_ws(void* base, const McLayout& l) {
             (unsigned*)(b + l.off_bsum), (unsigned long long*)(b + l.off_boff), (int*)(b + l.off_tot)};
 }
 
-template <typename T>
-__device__ __forceinline__ T wave_inclusive_scan(T v, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const T x = __shfl_up(v, d, 64);
-        if (lane >= d) v += x;
-    }
-    return v;
-}
-
 __global__ __launch_bounds__(MC_BLOCK) void k_mc_classify(const float* __restrict__ level, int R, float iso, McWs w) {
     __shared__ unsigned wave_tot[MC_BLOCK / 64];
     const int n = R * R * R;
@@ -111,33 +102,7 @@ __global__ __launch_bounds__(MC_BLOCK) void k_mc_classify(const float* __restric
 }
 
 __global__ __launch_bounds__(MC_SCAN_BLOCK) void k_mc_scan_blocks(McWs w, int nblk, int* __restrict__ out_totals) {
-    __shared__ unsigned long long wave_tot[MC_SCAN_BLOCK / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long carry = 0;
-    for (int base = 0; base < nblk; base += MC_SCAN_BLOCK) {
-        const int b = base + threadIdx.x;
-        const unsigned s = b < nblk ? w.bsum[b] : 0u;
-        const unsigned long long v = (unsigned long long)(s & 0xffffu) | ((unsigned long long)(s >> 16) << 32);
-        const unsigned long long incl = wave_inclusive_scan(v, lane);
-        if (lane == 63) wave_tot[wave] = incl;
-        __syncthreads();
-        unsigned long long before = 0, total = 0;
-#pragma unroll
-        for (int q = 0; q < MC_SCAN_BLOCK / 64; ++q) {
-            before += q < wave ? wave_tot[q] : 0ull;
-            total += wave_tot[q];
-        }
-        if (b < nblk) w.boff[b] = carry + before + incl - v;
-        carry += total;
-        __syncthreads();  // wave_tot is rewritten by the next chunk
-    }
-    if (threadIdx.x == 0) {
-        const int nv = (int)(carry & 0xffffffffull), nt = (int)(carry >> 32);
-        w.tot[0] = nv;
-        w.tot[1] = nt;
-        out_totals[0] = nv;
-        out_totals[1] = nt;
-    }
+    tt_scan_block_totals(w.bsum, nblk, w.boff, w.tot, out_totals);
 }
 
 // vertex id of the edge (owner point q, axis a): requires bit a of mask[q]

@@ -7,11 +7,11 @@ include/tt_abi.h) instead of the CUDA-only `diso.DiffMC`.
     meshes = isosurface(space_cache, geometry.forward_field, helper)
     meshes = colorize_mesh(space_cache, geometry.export, meshes, torch.sigmoid)
 
-Same signatures and behaviour as the reference; Mesh keeps only what these functions and their users touch (no UV
-unwrap, no file output)."""
+Same signatures and behaviour as the reference; Mesh keeps what these functions and their users touch plus the
+training system's regularisers and outlier removal (no UV unwrap, no tangents, no file output)."""
 from __future__ import annotations
 
-from typing import Any, Callable, Dict, List, Optional, Tuple
+from typing import Any, Callable, Dict, List, Optional, Tuple, Union
 
 import torch
 import torch.nn as nn
@@ -36,14 +36,17 @@ def scale_tensor(dat: Tensor, inp_scale, tgt_scale) -> Tensor:
 
 
 class Mesh:
-    """The part of the reference's Mesh (triplaneturbo_executable/utils/mesh.py) that mesh extraction and colouring
-    use: positions, int32 triangles, vertex colours and area-weighted vertex normals (mesh.py:114-140)."""
+    """The part of threestudio's Mesh (threestudio/models/mesh.py; triplaneturbo_executable/utils/mesh.py is its
+    subset) that mesh extraction, colouring, the mesh renderer and the training system use: positions, int32
+    triangles, vertex colours, area-weighted vertex normals (mesh.py:114-140), edges, the normal-consistency and
+    Laplacian regularisers and remove_outlier, the last three on the tt_mesh_* kernels (include/tt_abi.h)."""
 
     def __init__(self, v_pos: Tensor, t_pos_idx: Tensor, **kwargs) -> None:
         self.v_pos = v_pos
         self.t_pos_idx = t_pos_idx
         self._v_nrm: Optional[Tensor] = None
         self._v_rgb: Optional[Tensor] = None
+        self._topology: Optional[ops.MeshTopology] = None  # depends on t_pos_idx and V only: built once
         self.extras: Dict[str, Any] = {}
         for k, v in kwargs.items():
             self.add_extra(k, v)
@@ -60,6 +63,53 @@ class Mesh:
     @property
     def v_rgb(self) -> Optional[Tensor]:
         return self._v_rgb
+
+    @property
+    def requires_grad(self) -> bool:
+        return self.v_pos.requires_grad
+
+    @property
+    def topology(self) -> ops.MeshTopology:
+        if self._topology is None:
+            self._topology = ops.mesh_topology(self.t_pos_idx, self.v_pos.shape[0])
+        return self._topology
+
+    @property
+    def edges(self) -> Tensor:
+        """(E,2) unique sorted vertex pairs of the face edges in lexicographic order, self pairs of degenerate faces
+        included, dtype of t_pos_idx: the values and order of the reference's _compute_edges (mesh.py:255-267)."""
+        return self.topology.edges
+
+    def set_vertex_color(self, v_rgb: Tensor) -> None:
+        assert v_rgb.shape[0] == self.v_pos.shape[0]
+        self._v_rgb = v_rgb
+
+    def normal_consistency(self) -> Tensor:
+        """mean over the edges of 1 - cos(n_a, n_b) of the vertex normals (mesh.py:269-274); differentiable to v_pos
+        through v_nrm."""
+        return ops.mesh_normal_consistency_loss(self.v_nrm, self.topology)
+
+    def laplacian(self) -> Tensor:
+        """mean row norm of the uniform Laplacian applied to v_pos (mesh.py:276-308), without the sparse matrix."""
+        return ops.mesh_laplacian_loss(self.v_pos, self.topology)
+
+    def remove_outlier(self, outlier_n_faces_threshold: Union[int, float]) -> Mesh:
+        """mesh.py:31-95: drop the connected components with fewer faces than the threshold (a float t: int(faces of
+        the largest component * t); an int: as given) and the vertices they leave unreferenced; a differentiable
+        mesh comes back as it is (self).  A new Mesh that inherits extras.  Two deliberate differences from the
+        reference's trimesh path: vertices are identified by index (trimesh's process=True would also merge
+        bitwise-equal positions), and the output keeps the original relative order of vertices and faces (trimesh
+        concatenates component by component).  A mesh without faces comes back as it is (the reference raises)."""
+        if self.requires_grad:
+            return self
+        if self.t_pos_idx.shape[0] == 0:
+            return self
+        v_pos, t_pos_idx = ops.mesh_remove_small_components(self.v_pos, self.t_pos_idx, outlier_n_faces_threshold,
+                                                            self.topology)
+        clean_mesh = Mesh(v_pos, t_pos_idx)
+        if len(self.extras) > 0:
+            clean_mesh.extras = self.extras
+        return clean_mesh
 
     def _compute_vertex_normal(self) -> Tensor:
         i0, i1, i2 = (self.t_pos_idx[:, c].long() for c in range(3))

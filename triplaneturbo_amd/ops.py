@@ -919,3 +919,181 @@ def marching_cubes(level: Tensor, deformation: Optional[Tensor] = None, isovalue
     if deformation is not None:
         deformation = _chk(deformation, "deformation", (R, R, R, 3))
     return _MarchingCubesFn.apply(level, deformation, float(isovalue))
+
+
+class MeshTopology:
+    """What the tt_mesh_* kernels need of a mesh's connectivity (include/tt_abi.h, "mesh regularisers and outlier
+    removal"), built once per mesh from t_pos_idx with torch sorts (plumbing; this is the one place that syncs):
+      edges       (E,2), dtype of t_pos_idx: the unique sorted face edges in lexicographic order, self pairs included
+                  (threestudio Mesh._compute_edges)
+      face_pairs  (P,2) int32: the two faces of every edge that exactly two face edges use
+      nbr_ptr     (V+1) int32, nbr_col (2E) int32: vertex -> neighbour CSR, each row ascending
+      ws          the device workspace every entry point of this mesh shares"""
+
+    def __init__(self, t_pos_idx: Tensor, n_vertices: int):
+        if not isinstance(t_pos_idx, torch.Tensor) or not t_pos_idx.is_cuda:
+            raise RuntimeError("t_pos_idx must live on the GPU (triplaneturbo_amd has no CPU path)")
+        if t_pos_idx.dtype not in (torch.int32, torch.int64) or t_pos_idx.dim() != 2 or t_pos_idx.shape[1] != 3:
+            raise TypeError(f"t_pos_idx must be (T,3) int32 / int64, got {tuple(t_pos_idx.shape)} {t_pos_idx.dtype}")
+        V, T = int(n_vertices), int(t_pos_idx.shape[0])
+        lim = 1 << 28  # TT_MESH_MAX_ITEMS
+        if V > lim or T > lim:
+            raise ValueError(f"mesh too large for tt_mesh_*: V={V}, T={T} (limit {lim})")
+        dev = t_pos_idx.device
+        self.n_vertices, self.n_faces = V, T
+        tri = t_pos_idx.long()
+        if T > 0 and (int(tri.min()) < 0 or int(tri.max()) >= V):
+            raise ValueError(f"t_pos_idx holds an index outside [0, {V})")
+        self.tri = t_pos_idx.int().contiguous()
+        a, b = tri, tri[:, [1, 2, 0]]
+        key = (torch.minimum(a, b) * max(V, 1) + torch.maximum(a, b)).reshape(-1)  # face edge 3f + k
+        skey, perm = torch.sort(key, stable=True)
+        uniq, counts = torch.unique_consecutive(skey, return_counts=True)
+        e0, e1 = uniq // max(V, 1), uniq % max(V, 1)
+        self.edges = torch.stack([e0, e1], dim=1).to(t_pos_idx.dtype).contiguous()
+        self.edges_i32 = self.edges if self.edges.dtype == torch.int32 else self.edges.int().contiguous()
+        starts = torch.cumsum(counts, 0) - counts
+        two = starts[counts == 2]
+        self.face_pairs = torch.stack([perm[two] // 3, perm[two + 1] // 3], dim=1).int().contiguous()
+        # both directions of every unique edge, sorted by (row, column): a second stable sort
+        src, dst = torch.cat([e0, e1]), torch.cat([e1, e0])
+        order = torch.sort(src * max(V, 1) + dst, stable=True)[1]
+        self.nbr_col = dst[order].int().contiguous()
+        self.nbr_ptr = torch.zeros(V + 1, dtype=torch.int64, device=dev)
+        self.nbr_ptr[1:] = torch.cumsum(torch.bincount(src, minlength=V), 0)
+        self.nbr_ptr = self.nbr_ptr.int().contiguous()
+        lib = _lib.load()
+        nbytes = lib.tt_mesh_workspace_bytes(V, T)
+        _lib.check(int(nbytes) if nbytes < 0 else 0, "tt_mesh_workspace_bytes")
+        self.ws = torch.empty(int(nbytes), device=dev, dtype=torch.uint8)
+
+    @property
+    def n_edges(self) -> int:
+        return self.edges.shape[0]
+
+
+def mesh_topology(t_pos_idx: Tensor, n_vertices: int) -> MeshTopology:
+    return MeshTopology(t_pos_idx, n_vertices)
+
+
+def _chk_mesh_attr(x: Tensor, name: str, topo: MeshTopology) -> Tensor:
+    x = _chk(x, name)
+    if x.dim() != 2 or x.shape[1] != 3 or x.shape[0] != topo.n_vertices:
+        raise ValueError(f"{name} must be ({topo.n_vertices}, 3), got {tuple(x.shape)}")
+    return x
+
+
+class _MeshLaplacianFn(torch.autograd.Function):
+    """tt_mesh_laplacian_fwd / _bwd: threestudio Mesh.laplacian() (uniform Laplacian, mean row norm)."""
+
+    @staticmethod
+    def forward(ctx, v_pos, topo):
+        loss = torch.empty((), device=v_pos.device, dtype=torch.float32)
+        with _timed("mesh_laplacian_fwd"):
+            _lib.check(_lib.load().tt_mesh_laplacian_fwd(_ptr(v_pos), _ptr(topo.nbr_ptr), _ptr(topo.nbr_col),
+                                                         topo.n_vertices, topo.n_faces, _ptr(topo.ws), _ptr(loss),
+                                                         _stream()), "tt_mesh_laplacian_fwd")
+        ctx.save_for_backward(v_pos)
+        ctx.topo = topo
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss):
+        v_pos, = ctx.saved_tensors
+        topo = ctx.topo
+        g = torch.empty_like(v_pos)
+        g_loss = g_loss.contiguous().float()
+        with _timed("mesh_laplacian_bwd"):
+            _lib.check(_lib.load().tt_mesh_laplacian_bwd(_ptr(v_pos), _ptr(topo.nbr_ptr), _ptr(topo.nbr_col),
+                                                         topo.n_vertices, topo.n_faces, _ptr(g_loss), _ptr(topo.ws),
+                                                         _ptr(g), _stream()), "tt_mesh_laplacian_bwd")
+        return g, None
+
+
+def mesh_laplacian_loss(v_pos: Tensor, topo: MeshTopology) -> Tensor:
+    """(1/V) sum_i |sum_{j in N(i), j != i} (v_i - v_j)|: threestudio Mesh.laplacian() (mesh.py:282-288) as HIP
+    kernels, differentiable w.r.t. v_pos (V,3) fp32.  No host round trip, no allocation beyond the outputs."""
+    return _MeshLaplacianFn.apply(_chk_mesh_attr(v_pos, "v_pos", topo), topo)
+
+
+class _MeshNormalConsistencyFn(torch.autograd.Function):
+    """tt_mesh_nc_fwd / _bwd: threestudio Mesh.normal_consistency() w.r.t. the vertex normals."""
+
+    @staticmethod
+    def forward(ctx, v_nrm, topo):
+        loss = torch.empty((), device=v_nrm.device, dtype=torch.float32)
+        with _timed("mesh_nc_fwd"):
+            _lib.check(_lib.load().tt_mesh_nc_fwd(_ptr(v_nrm), _ptr(topo.edges_i32), topo.n_vertices, topo.n_faces,
+                                                  topo.n_edges, _ptr(topo.ws), _ptr(loss), _stream()),
+                       "tt_mesh_nc_fwd")
+        ctx.save_for_backward(v_nrm)
+        ctx.topo = topo
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss):
+        v_nrm, = ctx.saved_tensors
+        topo = ctx.topo
+        g = torch.empty_like(v_nrm)
+        g_loss = g_loss.contiguous().float()
+        with _timed("mesh_nc_bwd"):
+            _lib.check(_lib.load().tt_mesh_nc_bwd(_ptr(v_nrm), _ptr(topo.nbr_ptr), _ptr(topo.nbr_col),
+                                                  topo.n_vertices, topo.n_edges, _ptr(g_loss), _ptr(g), _stream()),
+                       "tt_mesh_nc_bwd")
+        return g, None
+
+
+def mesh_normal_consistency_loss(v_nrm: Tensor, topo: MeshTopology) -> Tensor:
+    """mean over the mesh edges (a,b) of 1 - cosine_similarity(n_a, n_b, eps=1e-8): threestudio
+    Mesh.normal_consistency() (mesh.py:269-274) as HIP kernels, differentiable w.r.t. v_nrm (V,3) fp32 (the caller's
+    autograd carries it on to v_pos)."""
+    return _MeshNormalConsistencyFn.apply(_chk_mesh_attr(v_nrm, "v_nrm", topo), topo)
+
+
+def mesh_face_components(topo: MeshTopology) -> Tensor:
+    """(T,) int32 connected-component label per face: the smallest face index of its component (faces joined by an
+    edge that exactly two face edges use).  Leaves the per-component face counts in topo.ws."""
+    labels = torch.empty(topo.n_faces, device=topo.tri.device, dtype=torch.int32)
+    with _timed("mesh_components"):
+        _lib.check(_lib.load().tt_mesh_components(_ptr(topo.face_pairs), topo.face_pairs.shape[0], topo.n_faces,
+                                                  _ptr(topo.ws), _ptr(labels), _stream()), "tt_mesh_components")
+    return labels
+
+
+@torch.no_grad()
+def mesh_remove_small_components(v_pos: Tensor, t_pos_idx: Tensor, threshold, topo: MeshTopology
+                                 ) -> Tuple[Tensor, Tensor]:
+    """Drop the connected components with fewer than `threshold` faces (threestudio Mesh.remove_outlier's rule: a
+    float threshold t means int(largest component's faces * t), an int is used as given; components with
+    faces >= threshold stay) and the vertices no kept face references.  Kept vertices and faces keep their original
+    order; faces are renumbered.  Returns (v_pos', t_pos_idx') with t_pos_idx's dtype; a mesh without faces comes
+    back as it is.  One 8-byte read-back."""
+    v_pos = _chk_mesh_attr(v_pos, "v_pos", topo)
+    if t_pos_idx.shape != topo.tri.shape:
+        raise ValueError(f"t_pos_idx {tuple(t_pos_idx.shape)} is not the topology's {tuple(topo.tri.shape)}")
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float)):
+        raise TypeError(f"threshold must be an int or a float, got {type(threshold).__name__}")
+    if topo.n_faces == 0:
+        return v_pos, t_pos_idx
+    frac_mode = isinstance(threshold, float)
+    if frac_mode and threshold != threshold:
+        raise ValueError("threshold is NaN")
+    thr_int = 0 if frac_mode else max(min(int(threshold), 1 << 62), -(1 << 62))
+    frac = max(min(float(threshold), 1e300), -1e300) if frac_mode else 0.0
+    lib = _lib.load()
+    V, T = topo.n_vertices, topo.n_faces
+    labels = mesh_face_components(topo)
+    totals = torch.empty(2, device=v_pos.device, dtype=torch.int32)
+    with _timed("mesh_compact_count"):
+        _lib.check(lib.tt_mesh_compact_count(_ptr(topo.tri), _ptr(labels), V, T, int(frac_mode), frac, thr_int,
+                                             _ptr(topo.ws), _ptr(totals), _stream()), "tt_mesh_compact_count")
+    n_vert, n_tri = (int(x) for x in totals.cpu())
+    v_out = torch.empty((n_vert, 3), device=v_pos.device, dtype=torch.float32)
+    t_out = torch.empty((n_tri, 3), device=v_pos.device, dtype=torch.int32)
+    if n_tri > 0:
+        with _timed("mesh_compact_emit"):
+            _lib.check(lib.tt_mesh_compact_emit(_ptr(v_pos), _ptr(topo.tri), V, T, _ptr(topo.ws), _ptr(v_out),
+                                                _ptr(t_out), _stream()), "tt_mesh_compact_emit")
+    return v_out, t_out.to(t_pos_idx.dtype)
