@@ -61,6 +61,9 @@
  *   tt_mesh_*               Mesh.normal_consistency / laplacian and their backward, Mesh.remove_outlier's connected
  *                           components and compaction (threestudio/models/mesh.py:31-95,255-308; trimesh on the host
  *                           in the reference).
+ *   tt_uv_* / tt_tex_fill   the mesh exporter's xatlas UV unwrap (threestudio/models/mesh.py:207-249) and cv2.inpaint
+ *                           texture padding (multiprompt_mesh_exporter.py:96-107): axis-projection charts, shelf
+ *                           packing, an overlap guard, nearest-texel fill.
  */
 #ifndef TT_ABI_H
 #define TT_ABI_H
@@ -602,6 +605,84 @@ int tt_mesh_nc_fwd(const float* v_nrm, const int32_t* edges, int32_t V, int32_t 
                    float* loss, void* stream);
 int tt_mesh_nc_bwd(const float* v_nrm, const int32_t* nbr_ptr, const int32_t* nbr_col, int32_t V, int32_t E,
                    const float* grad_loss, float* grad_nrm, void* stream);
+
+/* ---- UV atlas and texture fill (tt_uv.hip; tt_uv_pack in tt_host.cpp): the stand-ins for xatlas and cv2.inpaint
+ * in the mesh exporter (multiprompt_mesh_exporter.py:72-134, threestudio/models/mesh.py:207-249) ----
+ * An axis-projection atlas for marching-cubes meshes, NOT an xatlas clone.  A mesh is v_pos (V,3) fp32, t_pos_idx
+ * (T,3) int32 and its face_pairs (P,2) int32 (the topology of the mesh regularisers above, ops.mesh_topology).
+ *   labels      l in {0: +x, 1: -x, 2: +y, 3: -y, 4: +z, 5: -z}.  n = (p1 - p0) x (p2 - p0) in double from the fp32
+ *               positions (n_x = e1y e2z - e1z e2y, n_y = e1z e2x - e1x e2z, n_z = e1x e2y - e1y e2x, |n|^2 =
+ *               (n_x^2 + n_y^2) + n_z^2, in that order, no fused operations); the score of l is +-n_axis.  The
+ *               initial label is the first argmax of the six scores.  l is admissible iff copysign(s^2, s) >=
+ *               tau^2 |n|^2 (tau^2 = (double)tau * (double)tau), i.e. n_hat . a_l >= tau.  A face with |n|^2 = 0
+ *               (or an index outside [0, V)) is zero-area: no admissible label, initial label +x.
+ *   smoothing   `rounds` Jacobi rounds (TT_UV_DEFAULT_ROUNDS = 8, tau = TT_UV_DEFAULT_TAU = 0.3; 0 < tau <=
+ *               TT_UV_MAX_TAU < 1/sqrt(3), so the argmax is always admissible).  The neighbours of f are the other
+ *               faces of the face_pairs rows (a, b), a != b, that hold f (at most 3).  Votes: 1 for f's current label
+ *               and 1 per neighbour's.  The new label is the admissible label with the most votes; on a tie the
+ *               current label (always admissible) stays, else the smallest wins.  A zero-area face takes the smallest
+ *               neighbour label of the previous round, +x without neighbours.
+ *   charts      the connected components (tt_mesh_components) of the face_pairs rows whose faces have the same label
+ *               and are not marked in `singleton` (T uint8, may be NULL); dense ids 0..C-1 in order of each chart's
+ *               smallest face.  C goes to out_totals[0] (DEVICE memory).
+ *   projection  a chart of label l maps a position p to (u, v) = +x (y,z), -x (z,y), +y (z,x), -y (x,z), +z (x,y),
+ *               -z (y,x): u x v = +a_l, so a non-degenerate face has positive signed UV area, at least tau times its
+ *               3-D area.  chart_box (T,4) fp32, rows 0..C-1 = (umin, vmin, umax, vmax) of the chart's vertices.
+ *   packing     tt_uv_pack, HOST memory: w = (double)umax - (double)umin, h the same in v.  At density s (texels per
+ *               world unit) a chart's box is bw = ceil(w s) + 2 pad + 1 by bh = ceil(h s) + 2 pad + 1 texels.  Boxes
+ *               sorted by (bh desc, bw desc, chart asc) go left to right onto shelves of width N; a box that does not
+ *               fit on the current shelf opens a new one at y += the shelf's height (its first box's).  s fits iff
+ *               every box lands inside N x N.  s = the largest fitting value found by bisection on [0, (N - 2 pad) /
+ *               max(w, h)], every probe rounded to float, until hi - lo <= TT_UV_PACK_REL_PREC * hi (s = 1 when every
+ *               chart is a point); offsets (C,2) int32 = (x, y) of each box at s.  TT_ERR_UNSUPPORTED when no s > 0
+ *               fits (too many charts for N).
+ *   emit        one UV vertex per distinct (chart, vertex) pair of the face corners, numbered in order of the pair's
+ *               first corner 3f + k.  In fp32: U = ((float)(x + pad) + 0.5f) + (u - umin) * s, V' = the same with y,
+ *               v, vmin; v_tex = (U / N, V' / N), in [0, 1].  t_tex_idx (T,3) int32: row f is face f of t_pos_idx.
+ *               tt_uv_emit_count leaves Vt in out_totals[0] (DEVICE); tt_uv_emit, with the same workspace, writes
+ *               v_tex (Vt,2) and t_tex_idx.
+ *   overlap     tt_uv_overlap: per texel centre of the N x N texture, the UV triangles that cover it under the
+ *               rasterizer's rules above (clip (2u - 1, 2v - 1, 0, 1): coverage, canonical edges, tie rule), so a
+ *               shared edge counts once; flags (T) uint8 = 1 for the faces that cover a texel counted twice;
+ *               out_totals = (flagged faces, covered texels).  The caller (ops.uv_atlas) makes flagged faces singletons
+ *               and redoes charts .. overlap; after TT_UV_MAX_OVERLAP_ROUNDS such rounds every face of a chart that
+ *               still has a flagged face becomes a singleton.  A flagged face is never a singleton (singletons sit in
+ *               disjoint boxes), so every round adds singletons and the loop ends.  Result: no texel centre lies in
+ *               two UV triangles.
+ *   fill        tt_tex_fill: out (H,W,C) fp32 = img where mask (H,W) uint8 != 0, bit for bit; elsewhere img at the
+ *               nearest masked texel by jump flooding (steps 2^k .. 1, then 2, 1) of the keys (squared distance << 32
+ *               | texel id), the smaller key wins; 0 when nothing is masked.  Nearest up to JFA's rare misses.
+ * Determinism: labels, charts, UVs, flags and the fill use integer atomics and fixed-order gathers only: bit-identical
+ * from launch to launch.  Counts are read back through out_totals; every entry point validates its arguments before
+ * any HIP call (TT_ERR_BAD_ARG).  Use: bytes = tt_uv_workspace_bytes(V, T, N) (one workspace for every tt_uv_* call of
+ * one mesh and texture size), tt_tex_fill_workspace_bytes(H, W). */
+#define TT_UV_DEFAULT_ROUNDS 8
+#define TT_UV_DEFAULT_TAU 0.3f
+#define TT_UV_MAX_TAU 0.577f
+#define TT_UV_MAX_SMOOTH_ROUNDS 1024
+#define TT_UV_MAX_FACES ((1 << 24) - 1)
+#define TT_UV_MAX_TEX 16384
+#define TT_UV_MAX_PADDING 256
+#define TT_UV_MAX_CHANNELS 64
+#define TT_UV_MAX_OVERLAP_ROUNDS 4
+#define TT_UV_PACK_REL_PREC 1e-4
+int64_t tt_uv_workspace_bytes(int32_t V, int32_t T, int32_t N);
+int tt_uv_labels(const float* v_pos, const int32_t* t_pos_idx, const int32_t* face_pairs, int32_t V, int32_t T,
+                 int32_t P, int32_t rounds, float tau, int32_t N, void* workspace, int32_t* labels, void* stream);
+int tt_uv_charts(const float* v_pos, const int32_t* t_pos_idx, const int32_t* face_pairs, const int32_t* labels,
+                 const uint8_t* singleton, int32_t V, int32_t T, int32_t P, int32_t N, void* workspace, int32_t* chart,
+                 float* chart_box, int32_t* out_totals, void* stream);
+int tt_uv_pack(const float* chart_box, int32_t C, int32_t N, int32_t padding, int32_t* offsets, float* scale);
+int tt_uv_emit_count(const int32_t* t_pos_idx, const int32_t* chart, int32_t V, int32_t T, int32_t N, void* workspace,
+                     int32_t* out_totals, void* stream);
+int tt_uv_emit(const float* v_pos, const int32_t* t_pos_idx, const int32_t* labels, const int32_t* chart,
+               const float* chart_box, const int32_t* offsets, int32_t C, float scale, int32_t V, int32_t T, int32_t N,
+               int32_t padding, void* workspace, float* v_tex, int32_t* t_tex_idx, void* stream);
+int tt_uv_overlap(const float* v_tex, const int32_t* t_tex_idx, int32_t Vt, int32_t V, int32_t T, int32_t N,
+                  void* workspace, uint8_t* flags, int32_t* out_totals, void* stream);
+int64_t tt_tex_fill_workspace_bytes(int32_t H, int32_t W);
+int tt_tex_fill(const float* img, const uint8_t* mask, int32_t H, int32_t W, int32_t C, void* workspace, float* out,
+                void* stream);
 
 #ifdef __cplusplus
 }

@@ -22,7 +22,7 @@ LIB_PATH = os.path.join(_HERE, "libtt_hip.so")
 # environment variables (profiling ablations and tuning sweeps, tools/).  The product library above never calls getenv.
 _DEFAULT_LIB_PATH = LIB_PATH
 TUNING_LIB_PATH = os.path.join(_HERE, "libtt_hip_tuning.so")
-SOURCES = ["tt_forward.hip", "tt_march.hip", "tt_backward.hip", "tt_backward_tex.hip", "tt_points.hip", "tt_composite.hip", "tt_grad2.hip", "tt_sampler.hip", "tt_hashgrid.hip", "tt_isosurface.hip", "tt_raster.hip", "tt_mesh.hip", "tt_host.cpp"]
+SOURCES = ["tt_forward.hip", "tt_march.hip", "tt_backward.hip", "tt_backward_tex.hip", "tt_points.hip", "tt_composite.hip", "tt_grad2.hip", "tt_sampler.hip", "tt_hashgrid.hip", "tt_isosurface.hip", "tt_raster.hip", "tt_mesh.hip", "tt_uv.hip", "tt_host.cpp"]
 # per-translation-unit flags: the texture backward is faster under hipcc's max-ILP scheduling strategy (3.11 -> 3.02 ms;
 # the other kernels are not); the geometry backward is faster with its transient MFMA results in VGPRs rather than AGPRs
 # (-amdgpu-mfma-vgpr-form: 471 -> 248 v_accvgpr_read, 3.045 -> 2.995 ms; texture backward slower, forward neutral) and
@@ -48,6 +48,8 @@ SYMBOLS = [
     "tt_rast_workspace_bytes", "tt_rast_fwd", "tt_rast_bwd", "tt_interp_fwd", "tt_interp_bwd", "tt_aa_fwd", "tt_aa_bwd",
     "tt_mesh_workspace_bytes", "tt_mesh_components", "tt_mesh_compact_count", "tt_mesh_compact_emit",
     "tt_mesh_laplacian_fwd", "tt_mesh_laplacian_bwd", "tt_mesh_nc_fwd", "tt_mesh_nc_bwd",
+    "tt_uv_workspace_bytes", "tt_uv_labels", "tt_uv_charts", "tt_uv_pack", "tt_uv_emit_count", "tt_uv_emit",
+    "tt_uv_overlap", "tt_tex_fill_workspace_bytes", "tt_tex_fill",
 ]
 
 
@@ -370,6 +372,15 @@ def load() -> ctypes.CDLL:
         "tt_mesh_laplacian_bwd": [_P, _P, _P, _I32, _I32, _P, _P, _P, _P],
         "tt_mesh_nc_fwd": [_P, _P, _I32, _I32, _I32, _P, _P, _P],
         "tt_mesh_nc_bwd": [_P, _P, _P, _I32, _I32, _P, _P, _P],
+        "tt_uv_workspace_bytes": [_I32, _I32, _I32],
+        "tt_uv_labels": [_P, _P, _P, _I32, _I32, _I32, _I32, _F, _I32, _P, _P, _P],
+        "tt_uv_charts": [_P] * 5 + [_I32] * 4 + [_P] * 5,
+        "tt_uv_pack": [_P, _I32, _I32, _I32, _P, _P],
+        "tt_uv_emit_count": [_P, _P, _I32, _I32, _I32, _P, _P, _P],
+        "tt_uv_emit": [_P] * 6 + [_I32, _F, _I32, _I32, _I32, _I32] + [_P] * 4,
+        "tt_uv_overlap": [_P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P],
+        "tt_tex_fill_workspace_bytes": [_I32, _I32],
+        "tt_tex_fill": [_P, _P, _I32, _I32, _I32, _P, _P, _P],
     }
     for name, argtypes in optional.items():
         if name in SYMBOLS:
@@ -381,6 +392,8 @@ def load() -> ctypes.CDLL:
     lib.tt_mc_workspace_bytes.restype = ctypes.c_int64
     lib.tt_rast_workspace_bytes.restype = ctypes.c_int64
     lib.tt_mesh_workspace_bytes.restype = ctypes.c_int64
+    lib.tt_uv_workspace_bytes.restype = ctypes.c_int64
+    lib.tt_tex_fill_workspace_bytes.restype = ctypes.c_int64
     _lib = lib
     return lib
 

@@ -4,7 +4,10 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <algorithm>
+#include <cmath>
 #include <mutex>
+#include <vector>
 
 extern "C" const char* tt_strerror(int status) {
     switch (status) {
@@ -128,5 +131,88 @@ extern "C" int tt_debug_poison_queue(void* stream) {
         if (!slot) return TT_ERR_DEVICE;
         if (hipMemsetAsync(slot, 0x7f, kSlotInts * sizeof(int), (hipStream_t)stream) != hipSuccess) return TT_ERR_DEVICE;
     }
+    return TT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// UV atlas shelf packing (include/tt_abi.h, "UV atlas and texture fill", packing): O(charts) numbers on the host,
+// between tt_uv_charts and tt_uv_emit.  Deterministic: a stable order, double arithmetic, float-rounded probes.
+namespace {
+struct UvShelf {
+    std::vector<double> w, h;
+    std::vector<long long> bw, bh;
+    std::vector<int> order;
+    int N = 0, pad = 0;
+
+    // true iff every box fits at density s; writes (x, y) per chart when off != nullptr
+    bool pack(double s, int32_t* off) {
+        const int C = (int)w.size();
+        for (int c = 0; c < C; ++c) {
+            bw[c] = (long long)std::ceil(w[c] * s) + 2ll * pad + 1;
+            bh[c] = (long long)std::ceil(h[c] * s) + 2ll * pad + 1;
+            order[c] = c;
+        }
+        std::sort(order.begin(), order.end(), [&](int a, int b) {
+            if (bh[a] != bh[b]) return bh[a] > bh[b];
+            if (bw[a] != bw[b]) return bw[a] > bw[b];
+            return a < b;
+        });
+        long long x = 0, y = 0, shelf = 0;
+        for (int c : order) {
+            if (bw[c] > N || bh[c] > N) return false;
+            if (x + bw[c] > N) {  // a new shelf
+                y += shelf;
+                x = 0;
+                shelf = 0;
+            }
+            if (shelf == 0) shelf = bh[c];  // the first (tallest) box of the shelf sets its height
+            if (y + shelf > N) return false;
+            if (off) {
+                off[2 * c] = (int32_t)x;
+                off[2 * c + 1] = (int32_t)y;
+            }
+            x += bw[c];
+        }
+        return true;
+    }
+};
+}  // namespace
+
+extern "C" int tt_uv_pack(const float* chart_box, int32_t C, int32_t N, int32_t padding, int32_t* offsets,
+                          float* scale) {
+    if (C < 1 || C > TT_UV_MAX_FACES || N < 1 || N > TT_UV_MAX_TEX || padding < 0 || padding > TT_UV_MAX_PADDING)
+        return TT_ERR_BAD_ARG;
+    if (!chart_box || !offsets || !scale) return TT_ERR_BAD_ARG;
+    UvShelf p;
+    p.w.resize(C);
+    p.h.resize(C);
+    p.bw.resize(C);
+    p.bh.resize(C);
+    p.order.resize(C);
+    p.N = N;
+    p.pad = padding;
+    double m = 0.0;
+    for (int c = 0; c < C; ++c) {
+        p.w[c] = (double)chart_box[4 * c + 2] - (double)chart_box[4 * c];
+        p.h[c] = (double)chart_box[4 * c + 3] - (double)chart_box[4 * c + 1];
+        if (!(p.w[c] >= 0.0 && p.h[c] >= 0.0 && p.w[c] < 1e30 && p.h[c] < 1e30)) return TT_ERR_BAD_ARG;
+        m = std::max(m, std::max(p.w[c], p.h[c]));
+    }
+    if (m == 0.0) {  // every chart is a point: any density packs the same boxes
+        if (!p.pack(1.0, offsets)) return TT_ERR_UNSUPPORTED;
+        *scale = 1.0f;
+        return TT_OK;
+    }
+    // at hi the largest box is wider than N - 2 pad: it never fits; lo = 0 is the trivial lower end
+    double lo = 0.0, hi = (double)(float)(((double)N - 2.0 * padding) / m);
+    if (!(hi > 0.0)) return TT_ERR_UNSUPPORTED;
+    for (int it = 0; it < 200 && hi - lo > TT_UV_PACK_REL_PREC * hi; ++it) {
+        const double mid = (double)(float)(0.5 * (lo + hi));
+        if (!(mid > lo && mid < hi)) break;
+        if (p.pack(mid, nullptr)) lo = mid;
+        else hi = mid;
+    }
+    if (!(lo > 0.0) || !p.pack(lo, offsets)) return TT_ERR_UNSUPPORTED;
+    *scale = (float)lo;  // exact: every probe is a float
     return TT_OK;
 }

@@ -8,7 +8,9 @@ include/tt_abi.h) instead of the CUDA-only `diso.DiffMC`.
     meshes = colorize_mesh(space_cache, geometry.export, meshes, torch.sigmoid)
 
 Same signatures and behaviour as the reference; Mesh keeps what these functions and their users touch plus the
-training system's regularisers and outlier removal (no UV unwrap, no tangents, no file output)."""
+training system's regularisers and outlier removal, and threestudio's UV unwrap (`unwrap_uv`, lazy `v_tex` /
+`t_tex_idx`) on the HIP axis-projection atlas (ops.uv_atlas) instead of xatlas.  No tangents.  File output (OBJ + MTL +
+texture) is triplaneturbo_amd.export: `multiprompt-mesh-exporter` and `save_obj`."""
 from __future__ import annotations
 
 from typing import Any, Callable, Dict, List, Optional, Tuple, Union
@@ -46,6 +48,9 @@ class Mesh:
         self.t_pos_idx = t_pos_idx
         self._v_nrm: Optional[Tensor] = None
         self._v_rgb: Optional[Tensor] = None
+        self._v_tex: Optional[Tensor] = None
+        self._t_tex_idx: Optional[Tensor] = None
+        self.uv_info: Optional[Dict[str, Any]] = None  # ops.uv_atlas's info of the last unwrap
         self._topology: Optional[ops.MeshTopology] = None  # depends on t_pos_idx and V only: built once
         self.extras: Dict[str, Any] = {}
         for k, v in kwargs.items():
@@ -63,6 +68,43 @@ class Mesh:
     @property
     def v_rgb(self) -> Optional[Tensor]:
         return self._v_rgb
+
+    @property
+    def v_tex(self) -> Tensor:
+        """(Vt,2) fp32 UVs in [0,1], unwrapped on first use with the defaults (mesh.py:112-116)."""
+        if self._v_tex is None:
+            self._v_tex, self._t_tex_idx = self._unwrap_uv()
+        return self._v_tex
+
+    @property
+    def t_tex_idx(self) -> Tensor:
+        """(T,3) int32 UV-vertex ids, face f = face f of t_pos_idx (mesh.py:118-122; the reference's are int64)."""
+        if self._t_tex_idx is None:
+            self._v_tex, self._t_tex_idx = self._unwrap_uv()
+        return self._t_tex_idx
+
+    def _unwrap_uv(self, xatlas_chart_options: Optional[dict] = None, xatlas_pack_options: Optional[dict] = None,
+                   texture_size: Optional[int] = None) -> Tuple[Tensor, Tensor]:
+        """mesh.py:207-242 on the HIP axis-projection atlas (ops.uv_atlas, include/tt_abi.h "UV atlas and texture
+        fill").  Of xatlas's options only PackOptions.padding (texels around every chart, default 2 as the exporter's
+        inpaint radius) and PackOptions.resolution (the atlas size; else texture_size, else 1024) mean something here;
+        any other option raises NotImplementedError naming it."""
+        chart_opts, pack_opts = dict(xatlas_chart_options or {}), dict(xatlas_pack_options or {})
+        for k in chart_opts:
+            raise NotImplementedError(f"xatlas chart option {k!r}: the atlas is axis-projection charts, not xatlas")
+        for k in pack_opts:
+            if k not in ("padding", "resolution"):
+                raise NotImplementedError(f"xatlas pack option {k!r}: only 'padding' and 'resolution' are supported")
+        N = int(pack_opts.get("resolution") or texture_size or 1024)
+        v_tex, t_tex_idx, info = ops.uv_atlas(self.v_pos.detach(), self.t_pos_idx, self.topology, texture_size=N,
+                                              padding=int(pack_opts.get("padding", 2)))
+        self.uv_info = info
+        return v_tex, t_tex_idx
+
+    def unwrap_uv(self, xatlas_chart_options: Optional[dict] = None, xatlas_pack_options: Optional[dict] = None,
+                  texture_size: Optional[int] = None) -> None:
+        """mesh.py:244-249; `texture_size` (the exporter's) sizes the atlas unless the pack options name a resolution."""
+        self._v_tex, self._t_tex_idx = self._unwrap_uv(xatlas_chart_options, xatlas_pack_options, texture_size)
 
     @property
     def requires_grad(self) -> bool:

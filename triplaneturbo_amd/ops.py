@@ -1097,3 +1097,116 @@ def mesh_remove_small_components(v_pos: Tensor, t_pos_idx: Tensor, threshold, to
             _lib.check(lib.tt_mesh_compact_emit(_ptr(v_pos), _ptr(topo.tri), V, T, _ptr(topo.ws), _ptr(v_out),
                                                 _ptr(t_out), _stream()), "tt_mesh_compact_emit")
     return v_out, t_out.to(t_pos_idx.dtype)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# UV atlas and texture fill (include/tt_abi.h, "UV atlas and texture fill"): the exporter's xatlas / cv2.inpaint
+UV_DEFAULT_ROUNDS = 8  # TT_UV_DEFAULT_ROUNDS
+UV_DEFAULT_TAU = 0.3  # TT_UV_DEFAULT_TAU
+UV_MAX_OVERLAP_ROUNDS = 4  # TT_UV_MAX_OVERLAP_ROUNDS
+
+
+@torch.no_grad()
+def uv_atlas(v_pos: Tensor, t_pos_idx: Tensor, topology: Optional[MeshTopology] = None, texture_size: int = 1024,
+             padding: int = 2, rounds: int = UV_DEFAULT_ROUNDS, tau: float = UV_DEFAULT_TAU,
+             max_overlap_rounds: int = UV_MAX_OVERLAP_ROUNDS) -> Tuple[Tensor, Tensor, dict]:
+    """Axis-projection UV atlas of a mesh for a texture_size^2 texture with `padding` texels around every chart:
+    v_tex (Vt,2) fp32 in [0,1], t_tex_idx (T,3) int32 (face f of t_pos_idx), and info = {charts, scale (texels per
+    world unit), fill_ratio (covered texel centres / N^2), overlap_rounds, labels, chart, chart_box, offsets,
+    singleton}.  Labels and charts on the GPU (tt_uv_labels / tt_uv_charts), shelf packing on the host (tt_uv_pack,
+    one read-back of the chart boxes), UVs (tt_uv_emit_count / tt_uv_emit), then the overlap guard (tt_uv_overlap):
+    faces on a texel centre that two UV triangles cover become singleton charts and the atlas is redone; after
+    max_overlap_rounds such rounds every face of a chart that still overlaps becomes a singleton.  Bit-identical from
+    call to call."""
+    v_pos = _chk(v_pos.detach(), "v_pos")
+    if v_pos.dim() != 2 or v_pos.shape[1] != 3:
+        raise ValueError(f"v_pos must be (V,3), got {tuple(v_pos.shape)}")
+    V = v_pos.shape[0]
+    topo = topology if topology is not None else mesh_topology(t_pos_idx, V)
+    if topo.n_vertices != V or tuple(topo.tri.shape) != tuple(t_pos_idx.shape):
+        raise ValueError("topology was built for another mesh")
+    T, N, pad = topo.n_faces, int(texture_size), int(padding)
+    lib = _lib.load()
+    nbytes = lib.tt_uv_workspace_bytes(V, T, N)
+    _lib.check(int(nbytes) if nbytes < 0 else 0, "tt_uv_workspace_bytes")
+    dev = v_pos.device
+    i32 = dict(device=dev, dtype=torch.int32)
+    info = {"charts": 0, "scale": 0.0, "fill_ratio": 0.0, "overlap_rounds": 0, "texture_size": N, "padding": pad}
+    if T == 0:
+        return torch.zeros((0, 2), device=dev), torch.zeros((0, 3), **i32), info
+    ws = torch.empty(int(nbytes), device=dev, dtype=torch.uint8)
+    tri, pairs = topo.tri, topo.face_pairs
+    P = pairs.shape[0]
+    labels = torch.empty(T, **i32)
+    with _timed("uv_labels"):
+        _lib.check(lib.tt_uv_labels(_ptr(v_pos), _ptr(tri), _ptr(pairs), V, T, P, int(rounds), float(tau), N, _ptr(ws),
+                                    _ptr(labels), _stream()), "tt_uv_labels")
+    singleton = torch.zeros(T, device=dev, dtype=torch.uint8)
+    flags = torch.empty(T, device=dev, dtype=torch.uint8)
+    chart = torch.empty(T, **i32)
+    box = torch.empty((T, 4), device=dev, dtype=torch.float32)
+    totals = torch.empty(4, **i32)
+    r = 0
+    while True:
+        with _timed("uv_charts"):
+            _lib.check(lib.tt_uv_charts(_ptr(v_pos), _ptr(tri), _ptr(pairs), _ptr(labels), _ptr(singleton), V, T, P, N,
+                                        _ptr(ws), _ptr(chart), _ptr(box), _ptr(totals), _stream()), "tt_uv_charts")
+        C = int(totals[0].item())
+        box_h = box[:C].cpu()
+        off_h = torch.empty((C, 2), dtype=torch.int32)
+        scale_h = torch.zeros(1, dtype=torch.float32)
+        st = lib.tt_uv_pack(_ptr(box_h), C, N, pad, _ptr(off_h), _ptr(scale_h))
+        if st == -2:  # TT_ERR_UNSUPPORTED
+            raise RuntimeError(f"uv_atlas: {C} charts do not fit a {N}^2 atlas with padding {pad} (every chart box is at "
+                               f"least {2 * pad + 1}^2 texels): use a larger texture_size or a smaller padding")
+        _lib.check(st, "tt_uv_pack")
+        offsets = off_h.to(dev)
+        scale = float(scale_h[0])
+        with _timed("uv_emit"):
+            _lib.check(lib.tt_uv_emit_count(_ptr(tri), _ptr(chart), V, T, N, _ptr(ws), _ptr(totals), _stream()),
+                       "tt_uv_emit_count")
+            Vt = int(totals[0].item())
+            v_tex = torch.empty((Vt, 2), device=dev, dtype=torch.float32)
+            t_tex_idx = torch.empty((T, 3), **i32)
+            _lib.check(lib.tt_uv_emit(_ptr(v_pos), _ptr(tri), _ptr(labels), _ptr(chart), _ptr(box), _ptr(offsets), C,
+                                      scale, V, T, N, pad, _ptr(ws), _ptr(v_tex), _ptr(t_tex_idx), _stream()),
+                       "tt_uv_emit")
+        with _timed("uv_overlap"):
+            _lib.check(lib.tt_uv_overlap(_ptr(v_tex), _ptr(t_tex_idx), Vt, V, T, N, _ptr(ws), _ptr(flags),
+                                         _ptr(totals), _stream()), "tt_uv_overlap")
+        n_flagged, n_covered = (int(x) for x in totals[:2].cpu())
+        if n_flagged == 0:
+            break
+        if r < max_overlap_rounds:
+            singleton |= flags
+        else:  # every face of a chart that still overlaps: singleton charts sit in disjoint boxes and cannot overlap
+            hit = torch.zeros(C, device=dev, dtype=torch.bool)
+            hit[chart[flags.bool()].long()] = True
+            singleton |= hit[chart.long()].to(torch.uint8)
+        r += 1  # a flagged face is never a singleton: every round adds singletons, so the loop ends
+    info.update(charts=C, scale=scale, fill_ratio=n_covered / float(N * N), overlap_rounds=r, labels=labels,
+                chart=chart, chart_box=box_h, offsets=off_h, singleton=singleton)
+    return v_tex, t_tex_idx, info
+
+
+@torch.no_grad()
+def texture_fill(img: Tensor, mask: Tensor) -> Tensor:
+    """img (H,W,C) fp32 with every texel where mask (H,W) bool is False replaced by the texel value at the nearest
+    True texel (jump flooding, tt_tex_fill); True texels come back bit for bit.  The exporter's stand-in for
+    cv2.inpaint(TELEA) (multiprompt_mesh_exporter.py:96-107).  A (H,W) image is filled as one channel."""
+    squeeze = img.dim() == 2
+    x = _chk((img[..., None] if squeeze else img).detach(), "img")
+    if x.dim() != 3:
+        raise ValueError(f"img must be (H,W) or (H,W,C), got {tuple(img.shape)}")
+    H, W, C = x.shape
+    if not isinstance(mask, torch.Tensor) or not mask.is_cuda or tuple(mask.shape) != (H, W):
+        raise ValueError(f"mask must be a GPU tensor of shape {(H, W)}")
+    m = (mask != 0).to(torch.uint8).contiguous()
+    lib = _lib.load()
+    nbytes = lib.tt_tex_fill_workspace_bytes(H, W)
+    _lib.check(int(nbytes) if nbytes < 0 else 0, "tt_tex_fill_workspace_bytes")
+    ws = torch.empty(int(nbytes), device=x.device, dtype=torch.uint8)
+    out = torch.empty_like(x)
+    with _timed("tex_fill"):
+        _lib.check(lib.tt_tex_fill(_ptr(x), _ptr(m), H, W, C, _ptr(ws), _ptr(out), _stream()), "tt_tex_fill")
+    return out[..., 0] if squeeze else out

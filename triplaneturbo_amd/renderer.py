@@ -59,6 +59,15 @@ class NoMaterial(BaseModule):
     def forward(self, features: Tensor, **kwargs) -> Tensor:
         return torch.sigmoid(features) * (1 + 2 * 0.001) - 0.001
 
+    def export(self, features: Tensor, **kwargs) -> Dict[str, Any]:
+        """no_material.py:56-63: the colour clamped to [0, 1], its first three channels as the albedo (the mesh
+        exporter's texture bake)."""
+        color = self(features, **kwargs).clamp(0, 1)
+        assert color.shape[-1] >= 3, "Output color must have at least 3 channels"
+        if color.shape[-1] > 3:
+            print("Output color has >3 channels, treating the first 3 as RGB")
+        return {"albedo": color[..., :3]}
+
 
 @register("solid-color-background")
 class SolidColorBackground(BaseModule):
