@@ -23,6 +23,25 @@ static inline bool tt_qflags_ok(int flags) {
     return (pbits & (pbits - 1)) == 0;
 }
 
+// Carves the sections of one workspace allocation: every section starts 256-byte aligned, in the order of the take()
+// calls.  With a null base take() returns null and only bytes() means something (the tt_*_workspace_bytes queries run
+// the same function as the launches, so a section cannot be sized in one place and placed in another).
+struct TtCarver {
+    char* base;
+    long long off = 0;
+    template <typename T>
+    T* take(long long count) {
+        T* p = base ? (T*)(base + off) : nullptr;
+        off += ((long long)sizeof(T) * count + 255) & ~255ll;
+        return p;
+    }
+    long long bytes() const { return off; }
+};
+
+// the leading part of the tt_mesh_workspace_bytes layout that tt_mesh_components touches, for T faces (tt_mesh.hip);
+// tt_uv.hip nests such a workspace inside its own
+long long tt_mesh_components_bytes(long long T);
+
 struct TileGeom;
 // fills the tile geometry / chunking for a render config; returns the number of work items.
 // default_order: order of an XCD's item queue, 0 = chunk-major, 1 = block-major (measured slightly faster in all

@@ -29,48 +29,38 @@
 // base-corner offset (di | dj << 1 | dk << 2) of each of the 12 cube edges (tools/gen_mc_tables.py)
 static __constant__ const unsigned char k_edge_base[12] = {0, 2, 4, 6, 0, 1, 4, 5, 0, 1, 2, 3};
 
-// workspace sections (tt_mc_workspace_bytes): every section 256-byte aligned
-struct McLayout {
-    long long n, nblk;
-    long long off_mask, off_case, off_local, off_bsum, off_boff, off_tot, bytes;
+struct McWs {
+    unsigned char *mask, *cas;
+    int* local;
+    unsigned* bsum;
+    unsigned long long* boff;
+    int* tot;
 };
 
-static inline long long mc_align(long long x) { return (x + 255) & ~255ll; }
+struct McLayout {
+    McWs w;
+    long long n, nblk, bytes;  // grid points, blocks of MC_BLOCK of them, size of the workspace
+};
 
-static McLayout mc_layout(int res) {
+// the workspace sections (tt_mc_workspace_bytes); base may be null for the size alone
+static McLayout mc_layout(void* base, int res) {
+    TtCarver c{(char*)base};
     McLayout l;
     l.n = (long long)res * res * res;
     l.nblk = (l.n + MC_BLOCK - 1) / MC_BLOCK;
-    l.off_mask = 0;
-    l.off_case = mc_align(l.n);
-    l.off_local = l.off_case + mc_align(l.n);
-    l.off_bsum = l.off_local + mc_align(4 * l.n);
-    l.off_boff = l.off_bsum + mc_align(4 * l.nblk);
-    l.off_tot = l.off_boff + mc_align(8 * l.nblk);
-    l.bytes = l.off_tot + 256;
+    l.w.mask = c.take<unsigned char>(l.n);          // [n] bit a: the edge p -> p + e_a crosses
+    l.w.cas = c.take<unsigned char>(l.n);           // [n] case index of the cell with origin p (0: no cell origin)
+    l.w.local = c.take<int>(l.n);                   // [n] in-block exclusive prefix: n_vert | n_tri << 16
+    l.w.bsum = c.take<unsigned>(l.nblk);            // [nblk] block totals, same packing
+    l.w.boff = c.take<unsigned long long>(l.nblk);  // [nblk] block offsets: vertices | triangles << 32
+    l.w.tot = c.take<int>(64);                      // [2] grand totals: vertices, triangles
+    l.bytes = c.bytes();
     return l;
 }
 
-struct McWs {
-    unsigned char* mask;       // [n] bit a: the edge p -> p + e_a crosses
-    unsigned char* cas;        // [n] case index of the cell with origin p (0 for points that are no cell origin)
-    int* local;                // [n] in-block exclusive prefix: n_vert | n_tri << 16
-    unsigned* bsum;            // [nblk] block totals, same packing
-    unsigned long long* boff;  // [nblk] block offsets: vertices | triangles << 32
-    int* tot;                  // [2] grand totals: vertices, triangles
-};
-
-static McWs mc_ws(void* base, const McLayout& l) {
-    char* b = (char*)base;
-    return {(unsigned char*)(b + l.off_mask), (unsigned char*)(b + l.off_case), (int*)(b + l.off_local),
-            (unsigned*)(b + l.off_bsum), (unsigned long long*)(b + l.off_boff), (int*)(b + l.off_tot)};
-}
-
 __global__ __launch_bounds__(MC_BLOCK) void k_mc_classify(const float* __restrict__ level, int R, float iso, McWs w) {
-    __shared__ unsigned wave_tot[MC_BLOCK / 64];
     const int n = R * R * R;
     const int p = blockIdx.x * MC_BLOCK + threadIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     unsigned packed = 0;
     if (p < n) {
         const int k = p % R, j = (p / R) % R, i = p / (R * R);
@@ -88,16 +78,9 @@ __global__ __launch_bounds__(MC_BLOCK) void k_mc_classify(const float* __restric
         w.cas[p] = (unsigned char)origin;
         packed = (unsigned)__popc(mask) | ((unsigned)tt_mc_tri_count[origin] << 16);
     }
-    const unsigned incl = wave_inclusive_scan(packed, lane);
-    if (lane == 63) wave_tot[wave] = incl;
-    __syncthreads();
-    unsigned before = 0, total = 0;
-#pragma unroll
-    for (int q = 0; q < MC_BLOCK / 64; ++q) {
-        before += q < wave ? wave_tot[q] : 0u;
-        total += wave_tot[q];
-    }
-    if (p < n) w.local[p] = (int)(before + incl - packed);
+    unsigned total;
+    const unsigned before = tt_block_exclusive_scan<unsigned, MC_BLOCK>(packed, &total);
+    if (p < n) w.local[p] = (int)before;
     if (threadIdx.x == 0) w.bsum[blockIdx.x] = total;
 }
 
@@ -239,14 +222,14 @@ static bool mc_res_ok(int res) { return res >= 2 && res <= TT_MC_MAX_RES; }
 
 extern "C" int64_t tt_mc_workspace_bytes(int32_t res) {
     if (!mc_res_ok(res)) return TT_ERR_BAD_ARG;
-    return mc_layout(res).bytes;
+    return mc_layout(nullptr, res).bytes;
 }
 
 extern "C" int tt_mc_count(const float* level, int32_t res, float isovalue, void* workspace, int32_t* out_totals,
                            void* stream) {
     if (!mc_res_ok(res) || !level || !workspace || !out_totals) return TT_ERR_BAD_ARG;
-    const McLayout l = mc_layout(res);
-    const McWs w = mc_ws(workspace, l);
+    const McLayout l = mc_layout(workspace, res);
+    const McWs& w = l.w;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_mc_classify, dim3((unsigned)l.nblk), dim3(MC_BLOCK), 0, s, level, res, isovalue, w);
     hipLaunchKernelGGL(k_mc_scan_blocks, dim3(1), dim3(MC_SCAN_BLOCK), 0, s, w, (int)l.nblk, out_totals);
@@ -256,8 +239,8 @@ extern "C" int tt_mc_count(const float* level, int32_t res, float isovalue, void
 extern "C" int tt_mc_emit(const float* level, const float* deformation, int32_t res, float isovalue, void* workspace,
                           float* v_pos, int32_t* t_pos_idx, void* stream) {
     if (!mc_res_ok(res) || !level || !workspace || !v_pos || !t_pos_idx) return TT_ERR_BAD_ARG;
-    const McLayout l = mc_layout(res);
-    const McWs w = mc_ws(workspace, l);
+    const McLayout l = mc_layout(workspace, res);
+    const McWs& w = l.w;
     hipStream_t s = (hipStream_t)stream;
     if (deformation)
         hipLaunchKernelGGL(k_mc_emit<true>, dim3((unsigned)l.nblk), dim3(MC_BLOCK), 0, s, level, deformation, res,
@@ -272,8 +255,8 @@ extern "C" int tt_mc_bwd(const float* level, const float* deformation, int32_t r
                          const float* grad_v, float* grad_level, float* grad_deformation, void* stream) {
     if (!mc_res_ok(res) || !level || !workspace || !grad_v || !grad_level) return TT_ERR_BAD_ARG;
     if ((deformation == nullptr) != (grad_deformation == nullptr)) return TT_ERR_BAD_ARG;
-    const McLayout l = mc_layout(res);
-    const McWs w = mc_ws(workspace, l);
+    const McLayout l = mc_layout(workspace, res);
+    const McWs& w = l.w;
     hipStream_t s = (hipStream_t)stream;
     if (deformation)
         hipLaunchKernelGGL(k_mc_bwd<true>, dim3((unsigned)l.nblk), dim3(MC_BLOCK), 0, s, level, deformation, res,

@@ -28,53 +28,54 @@
 #define MESH_BLOCK 256
 #define MESH_FINAL_BLOCK 256
 
-struct MeshLayout {
-    long long n, nblk, nblk_loss;
-    long long off_parent, off_count, off_misc, off_fkeep, off_vmark, off_local, off_bsum, off_boff, off_part, off_w,
-        bytes;
+struct MeshWs {
+    int *parent, *count, *misc;
+    unsigned char *fkeep, *vmark;
+    int* local;
+    unsigned* bsum;
+    unsigned long long* boff;
+    float *part, *w;
 };
 
-static inline long long mesh_align(long long x) { return (x + 255) & ~255ll; }
+struct MeshLayout {
+    MeshWs w;
+    long long n, nblk, nblk_loss, bytes;  // compaction items and blocks, loss-reduction blocks, size of the workspace
+};
 
-static MeshLayout mesh_layout(long long V, long long T) {
+// the sections tt_mesh_components touches: they sit first and depend on T only, so a workspace of
+// tt_mesh_components_bytes(T) is enough for it (tt_uv.hip nests one)
+static MeshWs mesh_components_ws(TtCarver& c, long long T) {
+    MeshWs w{};
+    w.parent = c.take<int>(T);  // [T] union-find forest
+    w.count = c.take<int>(T);   // [T] faces per component, at its label
+    w.misc = c.take<int>(64);   // [0] max faces of a component, [2..3] (V', T')
+    return w;
+}
+
+long long tt_mesh_components_bytes(long long T) {
+    TtCarver c{nullptr};
+    mesh_components_ws(c, T);
+    return c.bytes();
+}
+
+// the workspace sections (tt_mesh_workspace_bytes); base may be null for the size alone
+static MeshLayout mesh_layout(void* base, long long V, long long T) {
+    TtCarver c{(char*)base};
     MeshLayout l;
     l.n = V > T ? V : T;
     l.nblk = (l.n + MESH_BLOCK - 1) / MESH_BLOCK;
     const long long nl = V > 3 * T ? V : 3 * T;  // items of a loss reduction: V vertices or E <= 3T edges
     l.nblk_loss = (nl + MESH_BLOCK - 1) / MESH_BLOCK;
-    l.off_parent = 0;
-    l.off_count = l.off_parent + mesh_align(4 * T);
-    l.off_misc = l.off_count + mesh_align(4 * T);
-    l.off_fkeep = l.off_misc + 256;
-    l.off_vmark = l.off_fkeep + mesh_align(T);
-    l.off_local = l.off_vmark + mesh_align(V);
-    l.off_bsum = l.off_local + mesh_align(4 * l.n);
-    l.off_boff = l.off_bsum + mesh_align(4 * l.nblk);
-    l.off_part = l.off_boff + mesh_align(8 * l.nblk);
-    l.off_w = l.off_part + mesh_align(4 * l.nblk_loss);
-    l.bytes = l.off_w + mesh_align(12 * V);
+    l.w = mesh_components_ws(c, T);
+    l.w.fkeep = c.take<unsigned char>(T);           // [T] face kept
+    l.w.vmark = c.take<unsigned char>(V);           // [V] vertex referenced by a kept face
+    l.w.local = c.take<int>(l.n);                   // [n] in-block exclusive prefix: vertex | face << 16
+    l.w.bsum = c.take<unsigned>(l.nblk);            // [nblk] block totals, same packing
+    l.w.boff = c.take<unsigned long long>(l.nblk);  // [nblk] block offsets: vertices | faces << 32
+    l.w.part = c.take<float>(l.nblk_loss);          // [nblk_loss] loss partials
+    l.w.w = c.take<float>(3 * V);                   // [3V] Laplacian backward: d loss / d r
+    l.bytes = c.bytes();
     return l;
-}
-
-struct MeshWs {
-    int* parent;               // [T] union-find forest
-    int* count;                // [T] faces per component, at its label
-    int* misc;                 // [0] max faces of a component, [2..3] (V', T')
-    unsigned char* fkeep;      // [T] face kept
-    unsigned char* vmark;      // [V] vertex referenced by a kept face
-    int* local;                // [n] in-block exclusive prefix: vertex | face << 16
-    unsigned* bsum;            // [nblk] block totals, same packing
-    unsigned long long* boff;  // [nblk] block offsets: vertices | faces << 32
-    float* part;               // [nblk_loss] loss partials
-    float* w;                  // [3V] Laplacian backward: d loss / d r
-};
-
-static MeshWs mesh_ws(void* base, const MeshLayout& l) {
-    char* b = (char*)base;
-    return {(int*)(b + l.off_parent), (int*)(b + l.off_count), (int*)(b + l.off_misc),
-            (unsigned char*)(b + l.off_fkeep), (unsigned char*)(b + l.off_vmark), (int*)(b + l.off_local),
-            (unsigned*)(b + l.off_bsum), (unsigned long long*)(b + l.off_boff), (float*)(b + l.off_part),
-            (float*)(b + l.off_w)};
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -172,21 +173,12 @@ __global__ __launch_bounds__(MESH_BLOCK) void k_cc_mark(const int* __restrict__ 
 }
 
 __global__ __launch_bounds__(MESH_BLOCK) void k_cc_scan(int V, int T, int n, MeshWs w) {
-    __shared__ unsigned wave_tot[MESH_BLOCK / 64];
     const int i = blockIdx.x * MESH_BLOCK + threadIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     unsigned packed = 0;
     if (i < n) packed = (i < V ? (unsigned)w.vmark[i] : 0u) | ((i < T ? (unsigned)w.fkeep[i] : 0u) << 16);
-    const unsigned incl = wave_inclusive_scan(packed, lane);
-    if (lane == 63) wave_tot[wave] = incl;
-    __syncthreads();
-    unsigned before = 0, total = 0;
-#pragma unroll
-    for (int q = 0; q < MESH_BLOCK / 64; ++q) {
-        before += q < wave ? wave_tot[q] : 0u;
-        total += wave_tot[q];
-    }
-    if (i < n) w.local[i] = (int)(before + incl - packed);
+    unsigned total;
+    const unsigned before = tt_block_exclusive_scan<unsigned, MESH_BLOCK>(packed, &total);
+    if (i < n) w.local[i] = (int)before;
     if (threadIdx.x == 0) w.bsum[blockIdx.x] = total;
 }
 
@@ -372,7 +364,7 @@ static inline unsigned mesh_grid(long long n) { return (unsigned)((n + MESH_BLOC
 
 extern "C" int64_t tt_mesh_workspace_bytes(int32_t V, int32_t T) {
     if (V < 0 || T < 0 || V > TT_MESH_MAX_ITEMS || T > TT_MESH_MAX_ITEMS) return TT_ERR_BAD_ARG;
-    return mesh_layout(V, T).bytes;
+    return mesh_layout(nullptr, V, T).bytes;
 }
 
 extern "C" int tt_mesh_components(const int32_t* face_pairs, int32_t P, int32_t T, void* workspace, int32_t* labels,
@@ -380,8 +372,8 @@ extern "C" int tt_mesh_components(const int32_t* face_pairs, int32_t P, int32_t 
     if (P < 0 || T < 0 || T > TT_MESH_MAX_ITEMS || !workspace) return TT_ERR_BAD_ARG;
     if ((P > 0 && !face_pairs) || (T > 0 && !labels)) return TT_ERR_BAD_ARG;
     if (T == 0) return 0;
-    const MeshLayout l = mesh_layout(0, T);  // the union-find sections sit first and depend on T only
-    const MeshWs w = mesh_ws(workspace, l);
+    TtCarver c{(char*)workspace};
+    const MeshWs w = mesh_components_ws(c, T);
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_uf_init, dim3(mesh_grid(T)), dim3(MESH_BLOCK), 0, s, (int)T, w);
     if (P > 0)
@@ -399,8 +391,8 @@ extern "C" int tt_mesh_compact_count(const int32_t* t_pos_idx, const int32_t* la
     if (!t_pos_idx || !labels || !workspace || !out_totals) return TT_ERR_BAD_ARG;
     if (frac_mode != 0 && frac_mode != 1) return TT_ERR_BAD_ARG;
     if (frac_mode == 1 && !(frac >= -1e300 && frac <= 1e300)) return TT_ERR_BAD_ARG;  // NaN / inf
-    const MeshLayout l = mesh_layout(V, T);
-    const MeshWs w = mesh_ws(workspace, l);
+    const MeshLayout l = mesh_layout(workspace, V, T);
+    const MeshWs& w = l.w;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_cc_keep, dim3(mesh_grid(l.n)), dim3(MESH_BLOCK), 0, s, (const int*)t_pos_idx,
                        (const int*)labels, (int)V, (int)T, (int)frac_mode, frac, (long long)threshold, w);
@@ -414,8 +406,8 @@ extern "C" int tt_mesh_compact_emit(const float* v_pos, const int32_t* t_pos_idx
                                     void* workspace, float* v_out, int32_t* t_out, void* stream) {
     if (V < 0 || T < 1 || V > TT_MESH_MAX_ITEMS || T > TT_MESH_MAX_ITEMS) return TT_ERR_BAD_ARG;
     if (!t_pos_idx || !workspace || !t_out || (V > 0 && (!v_pos || !v_out))) return TT_ERR_BAD_ARG;
-    const MeshLayout l = mesh_layout(V, T);
-    const MeshWs w = mesh_ws(workspace, l);
+    const MeshLayout l = mesh_layout(workspace, V, T);
+    const MeshWs& w = l.w;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_cc_emit, dim3((unsigned)l.nblk), dim3(MESH_BLOCK), 0, s, v_pos, (const int*)t_pos_idx,
                        (int)V, (int)T, w, v_out, (int*)t_out);
@@ -432,8 +424,8 @@ extern "C" int tt_mesh_laplacian_fwd(const float* v_pos, const int32_t* nbr_ptr,
     if (!mesh_csr_ok(nbr_ptr, V) || T < 0 || T > TT_MESH_MAX_ITEMS || !workspace || !loss)
         return TT_ERR_BAD_ARG;
     if (V > 0 && !v_pos) return TT_ERR_BAD_ARG;
-    const MeshLayout l = mesh_layout(V, T);
-    const MeshWs w = mesh_ws(workspace, l);
+    const MeshLayout l = mesh_layout(workspace, V, T);
+    const MeshWs& w = l.w;
     hipStream_t s = (hipStream_t)stream;
     const unsigned nb = mesh_grid(V);
     if (nb > 0)
@@ -450,8 +442,8 @@ extern "C" int tt_mesh_laplacian_bwd(const float* v_pos, const int32_t* nbr_ptr,
         return TT_ERR_BAD_ARG;
     if (V > 0 && (!v_pos || !grad_v)) return TT_ERR_BAD_ARG;
     if (V == 0) return 0;
-    const MeshLayout l = mesh_layout(V, T);
-    const MeshWs w = mesh_ws(workspace, l);
+    const MeshLayout l = mesh_layout(workspace, V, T);
+    const MeshWs& w = l.w;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_lap_bwd_w, dim3(mesh_grid(V)), dim3(MESH_BLOCK), 0, s, v_pos, (const int*)nbr_ptr,
                        (const int*)nbr_col, (int)V, grad_loss, w.w);
@@ -465,8 +457,8 @@ extern "C" int tt_mesh_nc_fwd(const float* v_nrm, const int32_t* edges, int32_t 
     if (V < 0 || T < 0 || E < 0 || V > TT_MESH_MAX_ITEMS || T > TT_MESH_MAX_ITEMS || (int64_t)E > 3 * (int64_t)T)
         return TT_ERR_BAD_ARG;
     if (!workspace || !loss || (E > 0 && (!edges || !v_nrm))) return TT_ERR_BAD_ARG;
-    const MeshLayout l = mesh_layout(V, T);
-    const MeshWs w = mesh_ws(workspace, l);
+    const MeshLayout l = mesh_layout(workspace, V, T);
+    const MeshWs& w = l.w;
     hipStream_t s = (hipStream_t)stream;
     const unsigned nb = mesh_grid(E);
     if (nb > 0)

@@ -6,19 +6,18 @@
 //
 // Rasterize, five launches, no host round trip:
 //   k_rast_setup      per (view, triangle): clip culling and a clamped screen bounding box; its pixel count
-//   k_scan_reduce / k_scan_blocks / k_scan_apply     exclusive int64 scan of the counts -> candidate offsets
+//   tt_exclusive_scan (tt_scan.h, three launches)    exclusive int64 scan of the counts -> candidate offsets
 //   k_rast_cover      grid-stride over the candidates (triangle, pixel), total read on the device: coverage by the
 //                     homogeneous edge functions, then a 64-bit atomicMin of (ordered z/w bits << 32 | tri) into the
 //                     pixel's key.  Min is order-independent, so the result is bit-reproducible.
 //   k_rast_resolve    per pixel: the winner's (u, v, z/w) recomputed by the same function as the coverage test
 // Interpolate and antialias are per-pixel gathers; their vertex gradients (grad_pos, grad_attr) use fp32 atomics.
 #include "tt_host.h"
+#include "tt_scan.h"
 
 #pragma clang fp contract(off)  // edge functions exactly as written: shared edges must see exactly negated values
 
 #define RS_BLOCK 256
-#define RS_SCAN_ITEMS 4  // elements per thread of the scan kernels (1024 per block)
-#define RS_SCAN_BLOCK 1024
 
 #include "tt_raster_cover.h"  // TriSetup, tri_setup, tri_cover, pix_ndc: shared with tt_uv.hip
 
@@ -26,20 +25,22 @@
 // rasterize forward
 
 struct RastLayout {
-    long long n, nblk, off_bbox, off_offs, off_bsum, off_keys, bytes;
+    int4* bbox;
+    long long *offs, *bsum;
+    unsigned long long* keys;
+    long long n, bytes;  // (view, triangle) slots, size of the workspace
 };
 
-static inline long long rs_align(long long x) { return (x + 255) & ~255ll; }
-
-static RastLayout rast_layout(int B, int T, int H, int W) {
+// the workspace sections (tt_rast_workspace_bytes); base may be null for the size alone
+static RastLayout rast_layout(void* base, int B, int T, int H, int W) {
+    TtCarver c{(char*)base};
     RastLayout l;
     l.n = (long long)B * T;
-    l.nblk = (l.n + RS_SCAN_BLOCK - 1) / RS_SCAN_BLOCK;
-    l.off_bbox = 0;
-    l.off_offs = rs_align(16 * l.n);
-    l.off_bsum = l.off_offs + rs_align(8 * (l.n + 1));
-    l.off_keys = l.off_bsum + rs_align(8 * (l.nblk + 1));
-    l.bytes = l.off_keys + rs_align(8ll * B * H * W);
+    l.bbox = c.take<int4>(l.n);                                 // [n] clamped screen box of the slot
+    l.offs = c.take<long long>(l.n + 1);                        // [n + 1] pixel counts, scanned in place; [n] = total
+    l.bsum = c.take<long long>(tt_xscan_blocks(l.n) + 1);       // scratch of the scan
+    l.keys = c.take<unsigned long long>((long long)B * H * W);  // per pixel: ordered z/w bits << 32 | tri, min wins
+    l.bytes = c.bytes();
     return l;
 }
 
@@ -89,79 +90,6 @@ __global__ __launch_bounds__(RS_BLOCK) void k_rast_setup(const float* __restrict
     }
     bbox[i] = bb;
     cnt[i] = area;
-}
-
-template <typename T>
-__device__ __forceinline__ T wave_incl_scan(T v, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const T x = __shfl_up(v, d, 64);
-        if (lane >= d) v += x;
-    }
-    return v;
-}
-
-// block-wide exclusive scan of one int64 per thread (RS_BLOCK threads); returns the exclusive prefix, *total the sum
-__device__ __forceinline__ long long block_excl_scan(long long v, long long* total) {
-    __shared__ long long wsum[RS_BLOCK / 64];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const long long inc = wave_incl_scan(v, lane);
-    if (lane == 63) wsum[wid] = inc;
-    __syncthreads();
-    long long before = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < RS_BLOCK / 64; ++k) {
-        if (k < wid) before += wsum[k];
-        tot += wsum[k];
-    }
-    __syncthreads();
-    *total = tot;
-    return before + inc - v;
-}
-
-__global__ __launch_bounds__(RS_BLOCK) void k_scan_reduce(const long long* __restrict__ cnt, long long n,
-                                                          long long* __restrict__ bsum) {
-    const long long base = (long long)blockIdx.x * RS_SCAN_BLOCK + threadIdx.x * RS_SCAN_ITEMS;
-    long long v = 0;
-#pragma unroll
-    for (int k = 0; k < RS_SCAN_ITEMS; ++k)
-        if (base + k < n) v += cnt[base + k];
-    long long tot;
-    block_excl_scan(v, &tot);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-
-// one block: exclusive scan of the block sums in place, in chunks of RS_BLOCK with a running carry; offs[n] = total
-__global__ __launch_bounds__(RS_BLOCK) void k_scan_blocks(long long* __restrict__ bsum, long long nblk,
-                                                          long long* __restrict__ offs, long long n) {
-    long long carry = 0;
-    for (long long base = 0; base < nblk; base += RS_BLOCK) {
-        const long long i = base + threadIdx.x;
-        const long long v = i < nblk ? bsum[i] : 0;
-        long long tot;
-        const long long ex = block_excl_scan(v, &tot);
-        if (i < nblk) bsum[i] = carry + ex;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) offs[n] = carry;
-}
-
-__global__ __launch_bounds__(RS_BLOCK) void k_scan_apply(const long long* cnt, long long n,
-                                                         const long long* __restrict__ bsum, long long* offs) {
-    const long long base = (long long)blockIdx.x * RS_SCAN_BLOCK + threadIdx.x * RS_SCAN_ITEMS;
-    long long c[RS_SCAN_ITEMS], v = 0;
-#pragma unroll
-    for (int k = 0; k < RS_SCAN_ITEMS; ++k) {
-        c[k] = base + k < n ? cnt[base + k] : 0;
-        v += c[k];
-    }
-    long long tot;
-    long long run = bsum[blockIdx.x] + block_excl_scan(v, &tot);
-#pragma unroll
-    for (int k = 0; k < RS_SCAN_ITEMS; ++k) {
-        if (base + k < n) offs[base + k] = run;
-        run += c[k];
-    }
 }
 
 __device__ __forceinline__ unsigned ordered_bits(float f) {
@@ -537,7 +465,7 @@ static unsigned rs_blocks(long long n) { return (unsigned)((n + RS_BLOCK - 1) / 
 
 extern "C" int64_t tt_rast_workspace_bytes(int32_t B, int32_t T, int32_t H, int32_t W) {
     if (!rs_dims_ok(B, 0, T, H, W)) return TT_ERR_BAD_ARG;
-    return rast_layout(B, T, H, W).bytes;
+    return rast_layout(nullptr, B, T, H, W).bytes;
 }
 
 extern "C" int tt_rast_fwd(const float* pos, const int32_t* tri, int32_t B, int32_t V, int32_t T, int32_t H,
@@ -550,25 +478,18 @@ extern "C" int tt_rast_fwd(const float* pos, const int32_t* tri, int32_t B, int3
         if (hipMemsetAsync(rast, 0, (size_t)npix * 16, st) != hipSuccess) return TT_ERR_LAUNCH;
         return tt_check_launch();
     }
-    const RastLayout l = rast_layout(B, T, H, W);
-    char* ws = (char*)workspace;
-    int4* bbox = (int4*)(ws + l.off_bbox);
-    long long* offs = (long long*)(ws + l.off_offs);
-    long long* bsum = (long long*)(ws + l.off_bsum);
-    unsigned long long* keys = (unsigned long long*)(ws + l.off_keys);
-    // the counts are written into offs[] and scanned in place (k_scan_apply reads each count before it writes it)
-    if (hipMemsetAsync(keys, 0xff, (size_t)npix * 8, st) != hipSuccess) return TT_ERR_LAUNCH;
+    const RastLayout l = rast_layout(workspace, B, T, H, W);
+    if (hipMemsetAsync(l.keys, 0xff, (size_t)npix * 8, st) != hipSuccess) return TT_ERR_LAUNCH;
     hipLaunchKernelGGL(k_rast_setup, dim3(rs_blocks(l.n)), dim3(RS_BLOCK), 0, st, pos, (const int*)tri, B, V, T, H, W,
-                       bbox, offs);
-    hipLaunchKernelGGL(k_scan_reduce, dim3((unsigned)l.nblk), dim3(RS_BLOCK), 0, st, offs, l.n, bsum);
-    hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(RS_BLOCK), 0, st, bsum, l.nblk, offs, l.n);
-    hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)l.nblk), dim3(RS_BLOCK), 0, st, offs, l.n, bsum, offs);
+                       l.bbox, l.offs);
+    // the counts were written into offs[]: scanned in place, the total behind them
+    tt_exclusive_scan<long long>(l.offs, l.n, l.offs, l.bsum, l.offs + l.n, st);
     int cus = tt_num_cus();
     if (cus <= 0) cus = 256;
     hipLaunchKernelGGL(k_rast_cover, dim3((unsigned)cus * 8), dim3(RS_BLOCK), 0, st, pos, (const int*)tri, V, T, H, W,
-                       bbox, offs, l.n, keys);
+                       l.bbox, l.offs, l.n, l.keys);
     hipLaunchKernelGGL(k_rast_resolve, dim3(rs_blocks(npix)), dim3(RS_BLOCK), 0, st, pos, (const int*)tri, B, V, T, H,
-                       W, keys, rast);
+                       W, l.keys, rast);
     return tt_check_launch();
 }
 

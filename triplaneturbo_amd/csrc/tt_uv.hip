@@ -10,7 +10,8 @@
 // Charts (tt_uv_charts):
 //   k_pair_filter  same-label pairs of non-singleton faces; the others become (-1, -1), which tt_mesh_components skips
 //   tt_mesh_components (tt_mesh.hip) -> comp = smallest face of the chart
-//   k_root_flag + int scan -> dense chart ids in order of the smallest face; k_chart_assign
+//   k_root_flag + int scan (tt_exclusive_scan of tt_scan.h) -> dense chart ids in order of the smallest face;
+//   k_chart_assign
 //   k_box_reduce   chart bounding box of the projected vertices, ordered-int atomicMin / atomicMax
 //   k_box_out      decoded to floats
 // Emit (tt_uv_emit_count, tt_uv_emit):
@@ -25,160 +26,55 @@
 // copy.  Every result is integer-atomic or a fixed-order gather: bit-identical from launch to launch.
 #include "tt_host.h"
 #include "tt_raster_cover.h"  // tri_setup / tri_cover / pix_ndc (and fp contract off for this file)
+#include "tt_scan.h"
 
 #define UV_BLOCK 256
-#define UV_SCAN_ITEMS 4
-#define UV_SCAN_SPAN (UV_BLOCK * UV_SCAN_ITEMS)
 
 // ---------------------------------------------------------------------------------------------------------------
 // workspace
-struct UvLayout {
-    long long nblk;
-    long long off_adm, off_lab2, off_deg, off_nbr, off_pairs, off_mesh, off_comp, off_flag, off_rootid, off_box,
-        off_vdeg, off_vptr, off_vfill, off_vcorner, off_rep, off_isrep, off_uvid, off_bsum, off_tot, off_clip, off_cnt,
-        bytes;
-};
-
-static inline long long uv_align(long long x) { return (x + 255) & ~255ll; }
-
-static UvLayout uv_layout(long long V, long long T, long long N) {
-    UvLayout l;
-    const long long n = 3 * T > V + 1 ? 3 * T : V + 1;  // longest scanned array
-    l.nblk = (n + UV_SCAN_SPAN - 1) / UV_SCAN_SPAN;
-    const long long mesh_bytes = tt_mesh_workspace_bytes(0, (int32_t)T);
-    l.off_adm = 0;
-    l.off_lab2 = l.off_adm + uv_align(T);
-    l.off_deg = l.off_lab2 + uv_align(4 * T);
-    l.off_nbr = l.off_deg + uv_align(4 * T);
-    l.off_pairs = l.off_nbr + uv_align(12 * T);
-    l.off_mesh = l.off_pairs + uv_align(12 * T);  // 2P <= 3T ints
-    l.off_comp = l.off_mesh + uv_align(mesh_bytes);
-    l.off_flag = l.off_comp + uv_align(4 * T);
-    l.off_rootid = l.off_flag + uv_align(4 * T);
-    l.off_box = l.off_rootid + uv_align(4 * T);
-    l.off_vdeg = l.off_box + uv_align(16 * T);
-    l.off_vptr = l.off_vdeg + uv_align(4 * (V + 1));
-    l.off_vfill = l.off_vptr + uv_align(4 * (V + 1));
-    l.off_vcorner = l.off_vfill + uv_align(4 * V);
-    l.off_rep = l.off_vcorner + uv_align(12 * T);
-    l.off_isrep = l.off_rep + uv_align(12 * T);
-    l.off_uvid = l.off_isrep + uv_align(12 * T);
-    l.off_bsum = l.off_uvid + uv_align(12 * T);
-    l.off_tot = l.off_bsum + uv_align(4 * (l.nblk + 1));
-    l.off_clip = l.off_tot + 256;
-    l.off_cnt = l.off_clip + uv_align(48 * T);  // one float4 per UV vertex, Vt <= 3T
-    l.bytes = l.off_cnt + uv_align(4 * N * N);
-    return l;
-}
-
 struct UvWs {
-    unsigned char* adm;  // [T] admissible-label bits (0: zero-area face)
-    int* lab2;           // [T] Jacobi ping-pong buffer
-    int* deg;            // [T] edge neighbours found per face
-    int* nbr;            // [3T] the neighbours (slots >= deg unused)
-    int* pairs;          // [3T] filtered face pairs
-    void* mesh;          // tt_mesh_components workspace
-    int* comp;           // [T] smallest face of the chart
-    int* flag;           // [T] chart roots
-    int* rootid;         // [T] exclusive scan of the roots: dense chart id at the root
-    int* box;            // [4T] ordered-int chart boxes: umin, vmin, umax, vmax
-    int* vdeg;           // [V+1] corners per vertex
-    int* vptr;           // [V+1] CSR offsets
-    int* vfill;          // [V] fill cursors
-    int* vcorner;        // [3T] corner ids by vertex
-    int* rep;            // [3T] representative corner of each corner's (vertex, chart) pair
-    int* isrep;          // [3T] 1 for representatives
-    int* uvid;           // [3T] exclusive scan of isrep
-    int* bsum;           // [nblk + 1] scan block sums
-    int* tot;            // [64] 0 charts, 1 UV vertices, 2 flagged faces, 3 covered texels, 8.. scan totals
-    float4* clip;        // [3T] clip positions of the UV vertices
-    int* cnt;            // [N*N] UV triangles per texel centre
+    unsigned char* adm;
+    int *lab2, *deg, *nbr, *pairs;
+    void* mesh;
+    int *comp, *flag, *rootid, *box, *vdeg, *vptr, *vfill, *vcorner, *rep, *isrep, *uvid, *bsum, *tot;
+    float4* clip;
+    int* cnt;
 };
 
-static UvWs uv_ws(void* base, const UvLayout& l) {
-    char* b = (char*)base;
-    return {(unsigned char*)(b + l.off_adm), (int*)(b + l.off_lab2), (int*)(b + l.off_deg), (int*)(b + l.off_nbr),
-            (int*)(b + l.off_pairs), (void*)(b + l.off_mesh), (int*)(b + l.off_comp), (int*)(b + l.off_flag),
-            (int*)(b + l.off_rootid), (int*)(b + l.off_box), (int*)(b + l.off_vdeg), (int*)(b + l.off_vptr),
-            (int*)(b + l.off_vfill), (int*)(b + l.off_vcorner), (int*)(b + l.off_rep), (int*)(b + l.off_isrep),
-            (int*)(b + l.off_uvid), (int*)(b + l.off_bsum), (int*)(b + l.off_tot), (float4*)(b + l.off_clip),
-            (int*)(b + l.off_cnt)};
+// the workspace sections (tt_uv_workspace_bytes); base may be null for the size alone
+static UvWs uv_ws(void* base, long long V, long long T, long long N, long long* bytes = nullptr) {
+    TtCarver c{(char*)base};
+    UvWs w;
+    const long long n = 3 * T > V + 1 ? 3 * T : V + 1;  // longest scanned array
+    // tt_mesh_components needs tt_mesh_components_bytes(T); the section keeps the larger size it has always had, a
+    // whole tt_mesh_workspace_bytes(0, T), so that tt_uv_workspace_bytes does not change
+    const long long mesh_used = tt_mesh_components_bytes(T), mesh_kept = tt_mesh_workspace_bytes(0, (int32_t)T);
+    w.adm = c.take<unsigned char>(T);      // [T] admissible-label bits (0: zero-area face)
+    w.lab2 = c.take<int>(T);               // [T] Jacobi ping-pong buffer
+    w.deg = c.take<int>(T);                // [T] edge neighbours found per face
+    w.nbr = c.take<int>(3 * T);            // [3T] the neighbours (slots >= deg unused)
+    w.pairs = c.take<int>(3 * T);          // [3T] filtered face pairs (2P <= 3T ints)
+    w.mesh = c.take<char>(mesh_kept > mesh_used ? mesh_kept : mesh_used);  // tt_mesh_components' workspace
+    w.comp = c.take<int>(T);               // [T] smallest face of the chart
+    w.flag = c.take<int>(T);               // [T] chart roots
+    w.rootid = c.take<int>(T);             // [T] exclusive scan of the roots: dense chart id at the root
+    w.box = c.take<int>(4 * T);            // [4T] ordered-int chart boxes: umin, vmin, umax, vmax
+    w.vdeg = c.take<int>(V + 1);           // [V+1] corners per vertex
+    w.vptr = c.take<int>(V + 1);           // [V+1] CSR offsets
+    w.vfill = c.take<int>(V);              // [V] fill cursors
+    w.vcorner = c.take<int>(3 * T);        // [3T] corner ids by vertex
+    w.rep = c.take<int>(3 * T);            // [3T] representative corner of each corner's (vertex, chart) pair
+    w.isrep = c.take<int>(3 * T);          // [3T] 1 for representatives
+    w.uvid = c.take<int>(3 * T);           // [3T] exclusive scan of isrep
+    w.bsum = c.take<int>(tt_xscan_blocks(n) + 1);  // scratch of the scans
+    w.tot = c.take<int>(64);               // 0 charts, 1 UV vertices, 2 flagged faces, 3 covered texels, 8.. scan totals
+    w.clip = c.take<float4>(3 * T);        // [3T] clip positions of the UV vertices (Vt <= 3T)
+    w.cnt = c.take<int>(N * N);            // [N*N] UV triangles per texel centre
+    if (bytes) *bytes = c.bytes();
+    return w;
 }
 
 static inline unsigned uv_grid(long long n) { return (unsigned)((n + UV_BLOCK - 1) / UV_BLOCK); }
-
-// ---------------------------------------------------------------------------------------------------------------
-// exclusive int32 scan: per-block sums, one block scans them, apply.  Fixed order, no atomics.
-__device__ __forceinline__ int uv_block_excl_scan(int v, int* total) {
-    __shared__ int wsum[UV_BLOCK / 64];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int x = __shfl_up(inc, d, 64);
-        inc += lane >= d ? x : 0;
-    }
-    if (lane == 63) wsum[wid] = inc;
-    __syncthreads();
-    int before = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < UV_BLOCK / 64; ++k) {
-        before += k < wid ? wsum[k] : 0;
-        tot += wsum[k];
-    }
-    __syncthreads();
-    *total = tot;
-    return before + inc - v;
-}
-
-__global__ __launch_bounds__(UV_BLOCK) void k_scan_reduce(const int* __restrict__ in, int n, int* __restrict__ bsum) {
-    const long long base = (long long)blockIdx.x * UV_SCAN_SPAN + threadIdx.x * UV_SCAN_ITEMS;
-    int v = 0;
-#pragma unroll
-    for (int k = 0; k < UV_SCAN_ITEMS; ++k) v += base + k < n ? in[base + k] : 0;
-    int tot;
-    uv_block_excl_scan(v, &tot);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-
-__global__ __launch_bounds__(UV_BLOCK) void k_scan_blocks(int* __restrict__ bsum, int nblk, int* __restrict__ total) {
-    int carry = 0;
-    for (int base = 0; base < nblk; base += UV_BLOCK) {
-        const int i = base + threadIdx.x;
-        const int v = i < nblk ? bsum[i] : 0;
-        int tot;
-        const int ex = uv_block_excl_scan(v, &tot);
-        if (i < nblk) bsum[i] = carry + ex;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) total[0] = carry;
-}
-
-__global__ __launch_bounds__(UV_BLOCK) void k_scan_apply(const int* __restrict__ in, int n,
-                                                         const int* __restrict__ bsum, int* __restrict__ out) {
-    const long long base = (long long)blockIdx.x * UV_SCAN_SPAN + threadIdx.x * UV_SCAN_ITEMS;
-    int c[UV_SCAN_ITEMS], v = 0;
-#pragma unroll
-    for (int k = 0; k < UV_SCAN_ITEMS; ++k) {
-        c[k] = base + k < n ? in[base + k] : 0;
-        v += c[k];
-    }
-    int tot;
-    int run = bsum[blockIdx.x] + uv_block_excl_scan(v, &tot);
-#pragma unroll
-    for (int k = 0; k < UV_SCAN_ITEMS; ++k) {
-        if (base + k < n) out[base + k] = run;
-        run += c[k];
-    }
-}
-
-// out[i] = sum of in[0..i); total[0] = the sum of all n (device)
-static void uv_scan(const int* in, int n, int* out, int* bsum, int* total, hipStream_t s) {
-    const unsigned nb = (unsigned)((n + UV_SCAN_SPAN - 1) / UV_SCAN_SPAN);
-    hipLaunchKernelGGL(k_scan_reduce, dim3(nb), dim3(UV_BLOCK), 0, s, in, n, bsum);
-    hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(UV_BLOCK), 0, s, bsum, (int)nb, total);
-    hipLaunchKernelGGL(k_scan_apply, dim3(nb), dim3(UV_BLOCK), 0, s, in, n, (const int*)bsum, out);
-}
 
 __global__ void k_copy_total(const int* __restrict__ src, int* __restrict__ dst, int* __restrict__ out) {
     if (threadIdx.x == 0) {
@@ -557,7 +453,9 @@ static bool uv_pairs_ok(const int32_t* face_pairs, int32_t P, int32_t T) {
 
 extern "C" int64_t tt_uv_workspace_bytes(int32_t V, int32_t T, int32_t N) {
     if (!uv_sizes_ok(V, T, N)) return TT_ERR_BAD_ARG;
-    return uv_layout(V, T, N).bytes;
+    long long bytes;
+    uv_ws(nullptr, V, T, N, &bytes);
+    return bytes;
 }
 
 extern "C" int tt_uv_labels(const float* v_pos, const int32_t* t_pos_idx, const int32_t* face_pairs, int32_t V,
@@ -567,8 +465,7 @@ extern "C" int tt_uv_labels(const float* v_pos, const int32_t* t_pos_idx, const 
     if (rounds < 0 || rounds > TT_UV_MAX_SMOOTH_ROUNDS || !(tau > 0.f && tau <= TT_UV_MAX_TAU)) return TT_ERR_BAD_ARG;
     if (T > 0 && (V < 1 || !v_pos || !t_pos_idx || !labels)) return TT_ERR_BAD_ARG;
     if (T == 0) return 0;
-    const UvLayout l = uv_layout(V, T, N);
-    const UvWs w = uv_ws(workspace, l);
+    const UvWs w = uv_ws(workspace, V, T, N);
     hipStream_t s = (hipStream_t)stream;
     const double tau2 = (double)tau * (double)tau;
     hipLaunchKernelGGL(k_lab_init, dim3(uv_grid(T)), dim3(UV_BLOCK), 0, s, v_pos, (const int*)t_pos_idx, (int)V,
@@ -596,15 +493,14 @@ extern "C" int tt_uv_charts(const float* v_pos, const int32_t* t_pos_idx, const 
         hipMemsetAsync(out_totals, 0, 4, s);
         return tt_check_launch();
     }
-    const UvLayout l = uv_layout(V, T, N);
-    const UvWs w = uv_ws(workspace, l);
+    const UvWs w = uv_ws(workspace, V, T, N);
     if (P > 0)
         hipLaunchKernelGGL(k_pair_filter, dim3(uv_grid(P)), dim3(UV_BLOCK), 0, s, (const int*)face_pairs, (int)P,
                            (int)T, (const int*)labels, (const unsigned char*)singleton, w);
     const int st = tt_mesh_components(w.pairs, P, T, w.mesh, w.comp, stream);
     if (st != 0) return st;
     hipLaunchKernelGGL(k_root_flag, dim3(uv_grid(T)), dim3(UV_BLOCK), 0, s, (int)T, w);
-    uv_scan(w.flag, T, w.rootid, w.bsum, w.tot + 8, s);
+    tt_exclusive_scan<int>(w.flag, T, w.rootid, w.bsum, w.tot + 8, s);
     hipLaunchKernelGGL(k_copy_total, dim3(1), dim3(64), 0, s, (const int*)(w.tot + 8), w.tot, (int*)out_totals);
     hipLaunchKernelGGL(k_chart_assign, dim3(uv_grid(T)), dim3(UV_BLOCK), 0, s, (int)T, w, (int*)chart);
     hipLaunchKernelGGL(k_box_reduce, dim3(uv_grid(T)), dim3(UV_BLOCK), 0, s, v_pos, (const int*)t_pos_idx, (int)V,
@@ -622,18 +518,17 @@ extern "C" int tt_uv_emit_count(const int32_t* t_pos_idx, const int32_t* chart, 
         hipMemsetAsync(out_totals, 0, 4, s);
         return tt_check_launch();
     }
-    const UvLayout l = uv_layout(V, T, N);
-    const UvWs w = uv_ws(workspace, l);
+    const UvWs w = uv_ws(workspace, V, T, N);
     hipMemsetAsync(w.vdeg, 0, 4 * ((size_t)V + 1), s);
     hipMemsetAsync(w.vfill, 0, 4 * (size_t)V, s);
     hipLaunchKernelGGL(k_vc_count, dim3(uv_grid(3ll * T)), dim3(UV_BLOCK), 0, s, (const int*)t_pos_idx, (int)V,
                        (int)T, w);
-    uv_scan(w.vdeg, V + 1, w.vptr, w.bsum, w.tot + 9, s);
+    tt_exclusive_scan<int>(w.vdeg, V + 1, w.vptr, w.bsum, w.tot + 9, s);
     hipLaunchKernelGGL(k_vc_fill, dim3(uv_grid(3ll * T)), dim3(UV_BLOCK), 0, s, (const int*)t_pos_idx, (int)V,
                        (int)T, w);
     hipLaunchKernelGGL(k_rep, dim3(uv_grid(3ll * T)), dim3(UV_BLOCK), 0, s, (const int*)t_pos_idx,
                        (const int*)chart, (int)V, (int)T, w);
-    uv_scan(w.isrep, 3 * T, w.uvid, w.bsum, w.tot + 10, s);
+    tt_exclusive_scan<int>(w.isrep, 3 * T, w.uvid, w.bsum, w.tot + 10, s);
     hipLaunchKernelGGL(k_copy_total, dim3(1), dim3(64), 0, s, (const int*)(w.tot + 10), w.tot + 1, (int*)out_totals);
     return tt_check_launch();
 }
@@ -648,8 +543,7 @@ extern "C" int tt_uv_emit(const float* v_pos, const int32_t* t_pos_idx, const in
     if (T == 0) return 0;
     if (C < 1 || V < 1 || !v_pos || !t_pos_idx || !labels || !chart || !chart_box || !offsets || !v_tex || !t_tex_idx)
         return TT_ERR_BAD_ARG;
-    const UvLayout l = uv_layout(V, T, N);
-    const UvWs w = uv_ws(workspace, l);
+    const UvWs w = uv_ws(workspace, V, T, N);
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_uv_emit, dim3(uv_grid(3ll * T)), dim3(UV_BLOCK), 0, s, v_pos, (const int*)t_pos_idx, (int)V,
                        (int)T, (const int*)labels, (const int*)chart, chart_box, (const int*)offsets, (int)C, scale,
@@ -663,8 +557,7 @@ extern "C" int tt_uv_overlap(const float* v_tex, const int32_t* t_tex_idx, int32
         return TT_ERR_BAD_ARG;
     if (T > 0 && (!t_tex_idx || !flags)) return TT_ERR_BAD_ARG;
     if (Vt > 0 && !v_tex) return TT_ERR_BAD_ARG;
-    const UvLayout l = uv_layout(V, T, N);
-    const UvWs w = uv_ws(workspace, l);
+    const UvWs w = uv_ws(workspace, V, T, N);
     hipStream_t s = (hipStream_t)stream;
     const long long n = (long long)N * N;
     hipMemsetAsync(w.cnt, 0, 4 * (size_t)n, s);
@@ -681,9 +574,23 @@ extern "C" int tt_uv_overlap(const float* v_tex, const int32_t* t_tex_idx, int32
     return tt_check_launch();
 }
 
+// the two ping-pong seed buffers of the jump flooding, [H*W] each; base may be null for the size alone
+struct TexFillWs {
+    int *a, *b;
+    long long bytes;
+};
+static TexFillWs tex_fill_ws(void* base, int H, int W) {
+    TtCarver c{(char*)base};
+    TexFillWs w;
+    w.a = c.take<int>((long long)H * W);
+    w.b = c.take<int>((long long)H * W);
+    w.bytes = c.bytes();
+    return w;
+}
+
 extern "C" int64_t tt_tex_fill_workspace_bytes(int32_t H, int32_t W) {
     if (H < 1 || W < 1 || H > TT_UV_MAX_TEX || W > TT_UV_MAX_TEX) return TT_ERR_BAD_ARG;
-    return 2 * uv_align(4ll * H * W);
+    return tex_fill_ws(nullptr, H, W).bytes;
 }
 
 extern "C" int tt_tex_fill(const float* img, const uint8_t* mask, int32_t H, int32_t W, int32_t C, void* workspace,
@@ -693,8 +600,8 @@ extern "C" int tt_tex_fill(const float* img, const uint8_t* mask, int32_t H, int
     if (!img || !mask || !workspace || !out) return TT_ERR_BAD_ARG;
     hipStream_t s = (hipStream_t)stream;
     const int n = H * W;
-    int* a = (int*)workspace;
-    int* b = (int*)((char*)workspace + uv_align(4ll * n));
+    const TexFillWs w = tex_fill_ws(workspace, H, W);
+    int *a = w.a, *b = w.b;
     hipLaunchKernelGGL(k_jfa_init, dim3(uv_grid(n)), dim3(UV_BLOCK), 0, s, (const unsigned char*)mask, n, a);
     // steps: the largest power of two below max(H, W) down to 1, then the JFA+2 refinement steps 2 and 1
     int step = 1;

@@ -70,6 +70,17 @@ def _stream() -> ctypes.c_void_p:
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _contig(t: Optional[Tensor]) -> Optional[Tensor]:
+    return None if t is None else t.contiguous()
+
+
+def _workspace(name: str, *dims: int, device) -> Tensor:
+    """The uint8 workspace of the size lib.<name>(*dims) asks for (a tt_*_workspace_bytes query; negative = error)."""
+    nbytes = int(getattr(_lib.load(), name)(*dims))
+    _lib.check(min(nbytes, 0), name)
+    return torch.empty(nbytes, device=device, dtype=torch.uint8)
+
+
 def _chk(t: Tensor, name: str, shape: Optional[Sequence[int]] = None, dtype=torch.float32) -> Tensor:
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name} must be a tensor")
@@ -255,8 +266,7 @@ class _QueryPointsFn(torch.autograd.Function):
         P, _, H, W, _ = packed.shape
         wst, keep = _weights_struct((w1, w2, w3), (v1, v2, v3))
         lib = _lib.load()
-        c = lambda t: None if t is None else t.contiguous()
-        g_sdf, g_grad, g_feat = c(g_sdf), c(g_grad), c(g_feat)
+        g_sdf, g_grad, g_feat = _contig(g_sdf), _contig(g_grad), _contig(g_feat)
         gw = [None] * 6
         g_cache = None
         if any(ctx.needs_input_grad[:7]):
@@ -563,8 +573,8 @@ def march_backward_raw(rays_d: Tensor, t_starts: Tensor, t_ends: Tensor, fwd: di
                          tile_sb=0, grad_copies=1, tile_chunk=0, inv_std_dev=inv_std_dev)
     if out is None:
         out = torch.empty((n_rays * S, 4), device=rays_d.device, dtype=torch.float32)
-    c = lambda t: None if t is None else t.contiguous()
-    gs = [c(t) for t in (g_opacity, g_depth, g_rgb_fg, g_z_variance, g_normal_acc, g_weights, g_sdf, g_sdf_grad)]
+    gs = [_contig(t)
+          for t in (g_opacity, g_depth, g_rgb_fg, g_z_variance, g_normal_acc, g_weights, g_sdf, g_sdf_grad)]
     with _timed("tt_march_bwd"):
         st = _lib.load().tt_march_bwd(_ptr(rays_d), _ptr(t_starts), _ptr(t_ends), ctypes.byref(cfg),
                                       _ptr(fwd["opacity"]), _ptr(fwd["depth"]), _ptr(fwd["trans"]), _ptr(sdf),
@@ -632,11 +642,8 @@ class _TriplaneRenderFn(torch.autograd.Function):
         gw = _zeros_like_flat((w1, w2, w3, v1, v2, v3))  # six views of ONE zero-filled buffer: one fill launch
         gst = _grads_struct(gw)
 
-        def c(t):
-            return None if t is None else t.contiguous()
-
-        g_op, g_depth, g_rgb, g_zvar, g_nacc = c(g_op), c(g_depth), c(g_rgb), c(g_zvar), c(g_nacc)
-        g_weights, g_sdf, g_sdf_grad, g_features = c(g_weights), c(g_sdf), c(g_sdf_grad), c(g_features)
+        g_op, g_depth, g_rgb, g_zvar, g_nacc, g_weights, g_sdf, g_sdf_grad, g_features = (
+            _contig(t) for t in (g_op, g_depth, g_rgb, g_zvar, g_nacc, g_weights, g_sdf, g_sdf_grad, g_features))
         lib = _lib.load()
         g_k_rays = None
         if ctx.needs_input_grad[14]:  # d loss / d inv_std, one partial per ray (summed below in a fixed order)
@@ -796,8 +803,8 @@ class _CompositeFn(torch.autograd.Function):
         opacity, depth, rgb_fg, normal_acc, bg, cam_dist, *rest = ctx.saved_tensors
         c2w = rest[0] if rest else None
         n, bg_stride, rays_per_view, mode, view_group = ctx.meta
-        c = lambda t: None if (t is None or t.numel() == 0) else t.contiguous()
-        g_rgb, g_disp, g_cn, g_vis, g_visw = c(g_rgb), c(g_disp), c(g_cn), c(g_vis), c(g_visw)
+        g_rgb, g_disp, g_cn, g_vis, g_visw = (  # an empty gradient counts as an absent one
+            _contig(t) if t is not None and t.numel() else None for t in (g_rgb, g_disp, g_cn, g_vis, g_visw))
         f32 = dict(device=opacity.device, dtype=torch.float32)
         g_op, g_dep = torch.empty((n, 1), **f32), torch.empty((n, 1), **f32)
         g_fg, g_na = torch.empty((n, 3), **f32), torch.empty((n, 3), **f32)
@@ -871,9 +878,7 @@ class _MarchingCubesFn(torch.autograd.Function):
     def forward(ctx, level, deformation, isovalue):
         R = level.shape[0]
         lib = _lib.load()
-        nbytes = lib.tt_mc_workspace_bytes(R)
-        _lib.check(int(nbytes) if nbytes < 0 else 0, "tt_mc_workspace_bytes")
-        ws = torch.empty(int(nbytes), device=level.device, dtype=torch.uint8)
+        ws = _workspace("tt_mc_workspace_bytes", R, device=level.device)
         totals = torch.empty(2, device=level.device, dtype=torch.int32)
         _lib.check(lib.tt_mc_count(_ptr(level), R, isovalue, _ptr(ws), _ptr(totals), _stream()), "tt_mc_count")
         n_vert, n_tri = (int(x) for x in totals.cpu())
@@ -962,10 +967,7 @@ class MeshTopology:
         self.nbr_ptr = torch.zeros(V + 1, dtype=torch.int64, device=dev)
         self.nbr_ptr[1:] = torch.cumsum(torch.bincount(src, minlength=V), 0)
         self.nbr_ptr = self.nbr_ptr.int().contiguous()
-        lib = _lib.load()
-        nbytes = lib.tt_mesh_workspace_bytes(V, T)
-        _lib.check(int(nbytes) if nbytes < 0 else 0, "tt_mesh_workspace_bytes")
-        self.ws = torch.empty(int(nbytes), device=dev, dtype=torch.uint8)
+        self.ws = _workspace("tt_mesh_workspace_bytes", V, T, device=dev)
 
     @property
     def n_edges(self) -> int:
@@ -1127,14 +1129,12 @@ def uv_atlas(v_pos: Tensor, t_pos_idx: Tensor, topology: Optional[MeshTopology] 
         raise ValueError("topology was built for another mesh")
     T, N, pad = topo.n_faces, int(texture_size), int(padding)
     lib = _lib.load()
-    nbytes = lib.tt_uv_workspace_bytes(V, T, N)
-    _lib.check(int(nbytes) if nbytes < 0 else 0, "tt_uv_workspace_bytes")
     dev = v_pos.device
+    ws = _workspace("tt_uv_workspace_bytes", V, T, N, device=dev)
     i32 = dict(device=dev, dtype=torch.int32)
     info = {"charts": 0, "scale": 0.0, "fill_ratio": 0.0, "overlap_rounds": 0, "texture_size": N, "padding": pad}
     if T == 0:
         return torch.zeros((0, 2), device=dev), torch.zeros((0, 3), **i32), info
-    ws = torch.empty(int(nbytes), device=dev, dtype=torch.uint8)
     tri, pairs = topo.tri, topo.face_pairs
     P = pairs.shape[0]
     labels = torch.empty(T, **i32)
@@ -1203,9 +1203,7 @@ def texture_fill(img: Tensor, mask: Tensor) -> Tensor:
         raise ValueError(f"mask must be a GPU tensor of shape {(H, W)}")
     m = (mask != 0).to(torch.uint8).contiguous()
     lib = _lib.load()
-    nbytes = lib.tt_tex_fill_workspace_bytes(H, W)
-    _lib.check(int(nbytes) if nbytes < 0 else 0, "tt_tex_fill_workspace_bytes")
-    ws = torch.empty(int(nbytes), device=x.device, dtype=torch.uint8)
+    ws = _workspace("tt_tex_fill_workspace_bytes", H, W, device=x.device)
     out = torch.empty_like(x)
     with _timed("tex_fill"):
         _lib.check(lib.tt_tex_fill(_ptr(x), _ptr(m), H, W, C, _ptr(ws), _ptr(out), _stream()), "tt_tex_fill")

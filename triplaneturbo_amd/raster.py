@@ -17,7 +17,7 @@ from typing import Optional, Tuple, Union
 import torch
 
 from . import _lib
-from .ops import _chk, _ptr, _stream
+from .ops import _chk, _ptr, _stream, _workspace
 
 Tensor = torch.Tensor
 MAX_TRIS = 1 << 24  # TT_RAST_MAX_TRIS: tri + 1 is stored as a float
@@ -67,9 +67,7 @@ class _RasterizeFn(torch.autograd.Function):
         B, V, _ = pos.shape
         T = tri.shape[0]
         lib = _lib.load()
-        nbytes = lib.tt_rast_workspace_bytes(B, T, H, W)
-        _lib.check(int(nbytes) if nbytes < 0 else 0, "tt_rast_workspace_bytes")
-        ws = torch.empty(int(nbytes), device=pos.device, dtype=torch.uint8)
+        ws = _workspace("tt_rast_workspace_bytes", B, T, H, W, device=pos.device)
         rast = torch.empty((B, H, W, 4), device=pos.device, dtype=torch.float32)
         _lib.check(lib.tt_rast_fwd(_ptr(pos), _ptr(tri), B, V, T, H, W, _ptr(ws), _ptr(rast), _stream()),
                    "tt_rast_fwd")
