@@ -181,3 +181,31 @@ def test_render_fwd_multi_prompt_ragged_tile(ops, precision):
     """2 prompts x 2 views, S=45 (last tile partially filled), small planes."""
     scene = _scene(seed=6, P=2, R=32, n_view=2, Hh=5, Ww=7, S=45, near=0.4, far=2.9)
     _compare_render(ops, scene, 2, precision=precision)
+
+
+def test_launch_helper_status_timer_labels_and_ray_checks(ops):
+    """ops._launch: a library status becomes a RuntimeError naming the entry point; wrappers that go through it work
+    under an installed KernelTimer and keep their labels; decode_rays checks ray / interval shapes like the renders."""
+    out = torch.empty(1, 6, 8, 8, 32, device="cuda")
+    with pytest.raises(RuntimeError, match="tt_planes_pack failed: bad argument"):
+        ops._launch("tt_planes_pack", None, out, 1, 8, 8)  # a null input is refused before any HIP call
+    cache, sw, fw, ro, rd, _, _, ts, te = _scene(3, 1, 8, 1, 4, 4, 8)
+    tet_v = torch.tensor([[0.0, 0, 0], [1, 0, 0], [0, 1, 0], [0, 0, 1]], device="cuda")
+    tet_f = torch.tensor([[0, 2, 1], [0, 1, 3], [1, 2, 3], [0, 3, 2]], device="cuda", dtype=torch.int32)
+    timer = ops.KernelTimer()
+    ops.set_kernel_timer(timer)
+    try:
+        packed = ops.planes_pack(cache.cuda())
+        loss = ops.mesh_laplacian_loss(tet_v, ops.mesh_topology(tet_f, 4))
+    finally:
+        ops.set_kernel_timer(None)
+    assert torch.equal(packed.cpu(), O.rotate_planes_v1(cache).permute(0, 1, 3, 4, 2).contiguous())
+    # every vertex of a tetrahedron has the other three as neighbours: r_i = 4 v_i - (1, 1, 1)
+    want = (4 * tet_v.cpu().double() - 1).norm(dim=1).mean().float()
+    torch.testing.assert_close(loss.cpu(), want, rtol=1e-6, atol=0)  # < 16 fp32 roundings (2^-24 each) on the way
+    assert "mesh_laplacian_fwd" in timer.summary()
+    sw, rays = [w.cuda() for w in sw], [x.cuda() for x in (ro.reshape(16, 3), rd.reshape(16, 3), ts, te)]
+    assert ops.decode_rays(packed, sw, None, *rays, rays_per_view=16, rc=ops.RenderConfig())[0].shape == (16, 8)
+    rays[0] = torch.zeros(17, 3, device="cuda")  # n_rays + 1 origins
+    with pytest.raises(ValueError, match="ray / interval shapes disagree"):
+        ops.decode_rays(packed, sw, None, *rays, rays_per_view=16, rc=ops.RenderConfig())

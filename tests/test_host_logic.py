@@ -183,6 +183,72 @@ def test_library_exports_every_declared_symbol():
     assert not _lib.needs_build(path)
 
 
+def test_load_binds_every_symbol_as_the_header_declares_it():
+    """load() takes restype / argtypes from include/tt_abi.h: every symbol is bound, with as many argtypes as its
+    prototype has parameters (counted here by a regex of the test's own) and its return type; one signature of each
+    shape is pinned literally."""
+    _lib.build()
+    lib = _lib.load()
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "tt_abi.h")).read(), flags=re.S)
+    protos = re.findall(r"^\s*(const char\s*\*|int64_t|int)\s+(tt_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", src, flags=re.M)
+    assert sorted(name for _, name, _ in protos) == _header_symbols()
+    ret_types = {"int": ctypes.c_int, "int64_t": ctypes.c_int64}
+    for ret, name, params in protos:
+        fn = getattr(lib, name)
+        n_params = 0 if params.strip() in ("", "void") else params.count(",") + 1
+        assert fn.argtypes is not None and len(fn.argtypes) == n_params, name
+        assert fn.restype is ret_types.get(ret, ctypes.c_char_p), name
+    P, I32, I64, F = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
+    W, CFG = ctypes.POINTER(_lib.MlpWeights), ctypes.POINTER(_lib.RenderCfg)
+
+    def sig(name):
+        fn = getattr(lib, name)
+        return fn.restype, list(fn.argtypes)
+
+    assert sig("tt_render_bwd_geo") == (I32, [P, W, P, P, P, P, CFG] + [P] * 17 + [W, P])
+    assert sig("tt_mesh_compact_count") == (I32, [P, P, I32, I32, I32, ctypes.c_double, I64, P, P, P])
+    assert sig("tt_sample_uniform") == (I32, [I64, I32, F, F, P, I32, P, P, P])
+    assert sig("tt_hashgrid_n_params") == (I64, [ctypes.POINTER(_lib.HashGridCfg)])
+    assert sig("tt_grid_sample_2d_grad2_typed") == (I32, [I32] + [P] * 5 + [I32] * 4 + [I64, I32, I32] + [P] * 4)
+    assert sig("tt_strerror") == (ctypes.c_char_p, [I32])
+
+
+def test_abi_parser_refuses_what_it_cannot_map():
+    protos, defines = _lib._parse_abi("""
+/* int tt_commented_out(int a); */
+#define TT_A 3 /* plain */
+#define TT_B 0x1F
+#define TT_C (1 << 4)
+#define TT_D 0.5f
+int tt_a(void);
+const char* tt_b(int status);
+int64_t tt_c(const float* x, int64_t n,
+             const tt_render_cfg* cfg, tt_mlp_grads* g,
+             double d, void* stream);
+""")
+    P = ctypes.c_void_p
+    assert protos == {
+        "tt_a": (ctypes.c_int32, []), "tt_b": (ctypes.c_char_p, [ctypes.c_int32]),
+        "tt_c": (ctypes.c_int64, [P, ctypes.c_int64, ctypes.POINTER(_lib.RenderCfg), ctypes.POINTER(_lib.MlpWeights),
+                                  ctypes.c_double, P])}
+    assert defines == {"TT_A": 3, "TT_B": 31}  # no expression evaluator: (1 << 4) and float macros are not constants
+    for bad in ("int tt_x(size_t n, void* stream);", "int tt_x(unsigned int n);", "size_t tt_x(int n);",
+                "int tt_x(float** p);"):
+        with pytest.raises(ValueError, match="tt_x"):  # never a silent c_void_p / c_int
+            _lib._parse_abi(bad)
+
+
+def test_flag_constants_come_from_the_header():
+    assert _lib.TT_R_PER_SAMPLE == 1 and _lib.TT_R_VOLSDF == 128 and _lib.TT_Q_SPLIT3 == 16
+    assert _lib.TT_PLACE_VOLSDF == 0x100 and _lib.TT_DTYPE_F64 == 2
+    assert (_lib.TT_R_EXACT_F32, _lib.TT_R_WGRAD_F32, _lib.TT_R_BWD_SOLO, _lib.TT_R_BWD_PAIR, _lib.TT_R_SPLIT2,
+            _lib.TT_R_SPLIT3) == (2, 4, 8, 16, 32, 64)
+    assert (_lib.TT_Q_NORMAL, _lib.TT_Q_TEX, _lib.TT_Q_EXACT_F32, _lib.TT_Q_SPLIT2) == (1, 2, 4, 8)
+    assert (_lib.r_flag("split3"), _lib.q_flag("split3"), _lib.r_flag("f32"), _lib.q_flag("split2")) == (64, 16, 2, 8)
+    from triplaneturbo_amd import grid_sample_gradfix
+    assert grid_sample_gradfix._DTYPES == {torch.float32: 0, torch.float16: 1, torch.float64: 2}
+
+
 def test_stale_library_is_rebuilt_whatever_its_mtime(tmp_path, monkeypatch):
     """needs_build compares the embedded source hash, not file times: a library whose sources changed is stale even when
     it is NEWER than every source (a pushed tree, a checkout), and a library without a hash is always stale."""

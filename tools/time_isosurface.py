@@ -55,11 +55,9 @@ def main():
         sdf, deform = g.forward_field(pts[None], cache)
     level = sdf.reshape(R, R, R).contiguous()
     deform = deform.reshape(R, R, R, 3).contiguous()
-    lib = _lib.load()
-    ws = torch.empty(lib.tt_mc_workspace_bytes(R), device=dev, dtype=torch.uint8)
+    ws = torch.empty(_lib.load().tt_mc_workspace_bytes(R), device=dev, dtype=torch.uint8)
     totals = torch.empty(2, device=dev, dtype=torch.int32)
-    P, S = ops._ptr, ops._stream
-    count = lambda: _lib.check(lib.tt_mc_count(P(level), R, 0.0, P(ws), P(totals), S()), "tt_mc_count")  # noqa: E731
+    count = lambda: ops._launch("tt_mc_count", level, R, 0.0, ws, totals)  # noqa: E731
     count()
     V, T = (int(x) for x in totals.cpu())
     v_pos = torch.empty(V, 3, device=dev)
@@ -67,10 +65,8 @@ def main():
     g_v = torch.randn(V, 3, device=dev)
     g_level = torch.empty_like(level)
     g_def = torch.empty_like(deform)
-    emit = lambda: _lib.check(lib.tt_mc_emit(P(level), P(deform), R, 0.0, P(ws), P(v_pos), P(t_pos), S()),  # noqa: E731
-                              "tt_mc_emit")
-    bwd = lambda: _lib.check(lib.tt_mc_bwd(P(level), P(deform), R, 0.0, P(ws), P(g_v), P(g_level), P(g_def), S()),  # noqa: E731
-                             "tt_mc_bwd")
+    emit = lambda: ops._launch("tt_mc_emit", level, deform, R, 0.0, ws, v_pos, t_pos)  # noqa: E731
+    bwd = lambda: ops._launch("tt_mc_bwd", level, deform, R, 0.0, ws, g_v, g_level, g_def)  # noqa: E731
     res = {"res": R, "n_points": R ** 3, "n_vert": V, "n_tri": T, "deformation": True,
            "workspace_bytes": int(ws.numel())}
     res["count_classify_scan"] = timed(count, a.reps)

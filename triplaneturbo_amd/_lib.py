@@ -36,32 +36,14 @@ SOURCE_FLAGS = {"tt_backward_tex.hip": ["-mllvm", "-amdgpu-disable-unclustered-h
                                     "-mllvm", "-amdgpu-disable-unclustered-high-rp-reschedule"]}
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-munsafe-fp-atomics", "-fPIC", "-shared", "-fno-gpu-rdc"]
 
-# every symbol include/tt_abi.h declares (tests check the header and this list agree)
-SYMBOLS = [
-    "tt_strerror", "tt_abi_version", "tt_planes_pack", "tt_planes_unpack_grad", "tt_query_points",
-    "tt_query_field", "tt_decode_rays", "tt_render_fwd", "tt_render_bwd_geo", "tt_render_bwd_tex", "tt_grid_sample_2d_grad2", "tt_grid_sample_2d_grad2_typed",
-    "tt_march_fwd", "tt_march_bwd", "tt_sample_uniform", "tt_sample_importance",
-    "tt_points_bwd_geo", "tt_points_bwd_tex", "tt_points_bwd_x", "tt_hashgrid_n_params", "tt_hashgrid_fwd", "tt_hashgrid_bwd",
-    "tt_debug_poison_queue", "tt_patch_composite_fwd", "tt_patch_composite_bwd", "tt_render_eval",
-    "tt_composite_fwd", "tt_composite_bwd", "tt_eikonal_fwd", "tt_eikonal_bwd", "tt_source_hash",
-    "tt_mc_workspace_bytes", "tt_mc_count", "tt_mc_emit", "tt_mc_bwd",
-    "tt_rast_workspace_bytes", "tt_rast_fwd", "tt_rast_bwd", "tt_interp_fwd", "tt_interp_bwd", "tt_aa_fwd", "tt_aa_bwd",
-    "tt_mesh_workspace_bytes", "tt_mesh_components", "tt_mesh_compact_count", "tt_mesh_compact_emit",
-    "tt_mesh_laplacian_fwd", "tt_mesh_laplacian_bwd", "tt_mesh_nc_fwd", "tt_mesh_nc_bwd",
-    "tt_uv_workspace_bytes", "tt_uv_labels", "tt_uv_charts", "tt_uv_pack", "tt_uv_emit_count", "tt_uv_emit",
-    "tt_uv_overlap", "tt_tex_fill_workspace_bytes", "tt_tex_fill",
-]
-
-
 def _sources() -> List[str]:
     return [os.path.join(CSRC, s) for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
 
 
 def _expected_abi() -> int:
-    m = re.search(r"#define\s+TT_ABI_VERSION\s+(\d+)", open(os.path.join(INCLUDE, "tt_abi.h")).read())
-    if not m:
+    if "TT_ABI_VERSION" not in _DEFINES:
         raise RuntimeError("include/tt_abi.h has no TT_ABI_VERSION")
-    return int(m.group(1))
+    return _DEFINES["TT_ABI_VERSION"]
 
 
 def _deps() -> List[str]:
@@ -246,27 +228,53 @@ class HashGridCfg(ctypes.Structure):  # tt_hashgrid_cfg
                 ("base_resolution", _I32), ("per_level_scale", _F)]
 
 
-TT_R_PER_SAMPLE = 1
-TT_R_EXACT_F32 = 2
-TT_R_WGRAD_F32 = 4
-TT_R_BWD_SOLO = 8
-TT_R_BWD_PAIR = 16
-TT_R_SPLIT2 = 32
-TT_R_SPLIT3 = 64
-TT_R_VOLSDF = 128
-TT_Q_NORMAL = 1
-TT_Q_TEX = 2
-TT_Q_EXACT_F32 = 4
-TT_Q_SPLIT2 = 8
-TT_Q_SPLIT3 = 16
+_SCALARS = {"int": _I32, "int32_t": _I32, "int64_t": _I64, "float": _F, "double": ctypes.c_double}
+_STRUCT_POINTERS = {"tt_mlp_weights": MlpWeights, "tt_mlp_grads": MlpWeights,  # same layout: six pointers
+                    "tt_render_cfg": RenderCfg, "tt_hashgrid_cfg": HashGridCfg}
+_PROTO_RE = re.compile(r"^[ \t]*((?:const\s+)?\w+\s*\*?)\s*(tt_\w+)\s*\(([^()]*)\)\s*;", re.M)
+_PARAM_RE = re.compile(r"(?:const\s+)?(\w+)\s*(\*?)\s*\w*")
+_DEFINE_RE = re.compile(r"^#define[ \t]+(TT_\w+)[ \t]+(0[xX][0-9a-fA-F]+|\d+)[ \t]*$", re.M)
+
+
+def _ctype(decl: str, proto: str):
+    """The ctypes type of one C return / parameter declaration (`proto` only names the prototype in the error)."""
+    m = _PARAM_RE.fullmatch(decl.strip())
+    base, star = m.groups() if m else (None, None)
+    if star:
+        if base == "char":
+            return ctypes.c_char_p
+        return ctypes.POINTER(_STRUCT_POINTERS[base]) if base in _STRUCT_POINTERS else _P
+    if base not in _SCALARS:  # never guess: a wrong width shifts every argument behind it
+        raise ValueError(f"include/tt_abi.h: {proto}: no ctypes type for {decl.strip()!r}")
+    return _SCALARS[base]
+
+
+def _parse_abi(text: Optional[str] = None):
+    """include/tt_abi.h (or `text`) as ({name: (restype, argtypes)} of every tt_* prototype, {name: value} of every
+    #define TT_* that is a plain integer literal).  The header is the one description of the C ABI: load() binds from
+    this, SYMBOLS and the TT_* flag constants below are read from it."""
+    if text is None:
+        text = open(os.path.join(INCLUDE, "tt_abi.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    protos = {}
+    for ret, name, params in _PROTO_RE.findall(text):
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        protos[name] = (_ctype(ret, name), [_ctype(p, name) for p in params])
+    return protos, {k: int(v, 0) for k, v in _DEFINE_RE.findall(text)}
+
+
+_PROTOS, _DEFINES = _parse_abi()
+SYMBOLS = list(_PROTOS)  # every symbol include/tt_abi.h declares
+globals().update(_DEFINES)  # TT_R_*, TT_Q_*, TT_PLACE_VOLSDF, TT_DTYPE_*, ... as module attributes
 
 # Precision of the per-point MLP products (include/tt_abi.h, "precision of the matrix products"):
 #   "split3" (default)  fp32-grade: three fp16 pieces per operand, six product terms on the fp16 matrix pipe
 #   "f32"               every product on the fp32-input MFMA (the A/B reference)
 #   "split2"            the FAST mode: two pieces, three terms, ~2^-21.5 per product (tolerance-bounded)
 DEFAULT_PRECISION = "split3"
-_PRECISION_FLAGS = {"split3": (TT_R_SPLIT3, TT_Q_SPLIT3), "split2": (TT_R_SPLIT2, TT_Q_SPLIT2),
-                    "f32": (TT_R_EXACT_F32, TT_Q_EXACT_F32)}
+_PRECISION_FLAGS = {"split3": (_DEFINES["TT_R_SPLIT3"], _DEFINES["TT_Q_SPLIT3"]),
+                    "split2": (_DEFINES["TT_R_SPLIT2"], _DEFINES["TT_Q_SPLIT2"]),
+                    "f32": (_DEFINES["TT_R_EXACT_F32"], _DEFINES["TT_Q_EXACT_F32"])}
 _PRECISION_ALIASES = {"fast": "split2", "exact_f32": "f32", "fp32_mfma": "f32"}
 
 
@@ -289,8 +297,9 @@ def r_flag(name: str) -> int:
 
 def q_flag(name: str) -> int:
     return _PRECISION_FLAGS[name][1]
+
+
 PLACEMENTS = {"tt": 0, "center": 1}  # enum tt_sample_placement
-TT_PLACE_VOLSDF = 0x100  # OR-ed into the placement of tt_sample_importance: VolSDF proposal density
 
 
 def load() -> ctypes.CDLL:
@@ -313,87 +322,13 @@ def load() -> ctypes.CDLL:
     missing = [s for s in SYMBOLS if not hasattr(lib, s)]
     if missing:
         raise RuntimeError(f"{LIB_PATH} lacks symbols {missing}; rebuild it")
-    lib.tt_strerror.restype = ctypes.c_char_p
-    lib.tt_strerror.argtypes = [ctypes.c_int]
-    lib.tt_abi_version.restype = ctypes.c_int
-    lib.tt_source_hash.restype = ctypes.c_char_p
-    lib.tt_source_hash.argtypes = []
-    if lib.tt_abi_version() != _expected_abi():
+    if lib.tt_abi_version() != _expected_abi():  # (int (void): callable before it is bound)
         # argument lists moved between ABI versions: calling a stale library would shift pointer arguments
         raise RuntimeError(f"{LIB_PATH} has ABI version {lib.tt_abi_version()}, include/tt_abi.h declares "
                            f"{_expected_abi()}: rebuild it (python -c 'import __graft_entry__ as g; g.build()')")
-    lib.tt_planes_pack.argtypes = [_P, _P, _I32, _I32, _I32, _P]
-    lib.tt_planes_unpack_grad.argtypes = [_P, _P, _I32, _I32, _I32, _I32, _P]
-    lib.tt_query_points.argtypes = [_P, ctypes.POINTER(MlpWeights), _P, _I32, _I64, _I32, _I32, _I32, _I32, _F, _F,
-                                    _I32, _P, _P, _P, _P]
-    lib.tt_render_fwd.argtypes = [_P, ctypes.POINTER(MlpWeights), _P, _P, _P, _P, ctypes.POINTER(RenderCfg)] + [_P] * 11
-    _cfgp, _wp = ctypes.POINTER(RenderCfg), ctypes.POINTER(MlpWeights)
-    lib.tt_query_field.argtypes = [_P, _wp, _P, _I32, _I64, _I32, _I32, _I32, _I32, _F, _F, _I32, _P, _P, _P]
-    lib.tt_decode_rays.argtypes = [_P, _wp, _P, _P, _P, _P, _cfgp, _I32, _P, _P, _P, _P]
-    optional = {
-        "tt_render_bwd_geo": [_P, _wp, _P, _P, _P, _P, _cfgp] + [_P] * 14 + [_P, _P, _P, _wp, _P],
-        "tt_render_bwd_tex": [_P, _wp, _P, _P, _P, _P, _cfgp] + [_P] * 4 + [_P, _wp, _P],
-        "tt_march_fwd": [_P, _P, _P, _cfgp] + [_P] * 11,
-        "tt_march_bwd": [_P, _P, _P, _cfgp] + [_P] * 17,
-        "tt_points_bwd_geo": [_P, _wp, _P, _I32, _I64, _I32, _I32, _I32, _I32, _F, _F, _I32, _P, _P, _P, _P, _wp, _P],
-        "tt_points_bwd_tex": [_P, _wp, _P, _I32, _I64, _I32, _I32, _I32, _I32, _F, _I32, _I32, _P, _P, _wp, _P],
-        "tt_points_bwd_x": [_P, _wp, _P, _I32, _I64, _I32, _I32, _I32, _I32, _F, _I32, _P, _P, _P, _P, _P],
-        "tt_hashgrid_n_params": [ctypes.POINTER(HashGridCfg)],
-        "tt_hashgrid_fwd": [_P, _I64, _P, ctypes.POINTER(HashGridCfg), _P, _P],
-        "tt_hashgrid_bwd": [_P, _I64, _P, ctypes.POINTER(HashGridCfg), _P, _P],
-        "tt_sample_uniform": [_I64, _I32, _F, _F, _P, _I32, _P, _P, _P],
-        "tt_sample_importance": [_P, _P, _P, _I64, _I32, _I32, _F, _P, _F, _P, _I32, _P, _P, _P],
-        "tt_grid_sample_2d_grad2": [_P] * 5 + [_I32] * 4 + [_I64, _I32, _I32] + [_P] * 3 + [_P],
-        "tt_grid_sample_2d_grad2_typed": [_I32] + [_P] * 5 + [_I32] * 4 + [_I64, _I32, _I32] + [_P] * 3 + [_P],
-        "tt_debug_poison_queue": [_P],
-        "tt_composite_fwd": [_P, _P, _P, _P, _P, _I32, _P, _P, _I64, _I32, _I32, _I32] + [_P] * 6,
-        "tt_composite_bwd": [_P, _P, _P, _P, _P, _I32, _P, _P, _I64, _I32, _I32, _I32] + [_P] * 11,
-        "tt_render_eval": [_P, _wp, _P, _P, _P, _P, _cfgp, _F, _F] + [_P] * 7,
-        "tt_eikonal_fwd": [_P, _I64, _P, _P],
-        "tt_eikonal_bwd": [_P, _P, _I64, _P, _P],
-        "tt_patch_composite_fwd": [_P, _P, _P] + [_I32] * 9 + [_P],
-        "tt_patch_composite_bwd": [_P, _P, _P] + [_I32] * 9 + [_P],
-        "tt_mc_workspace_bytes": [_I32],
-        "tt_mc_count": [_P, _I32, _F, _P, _P, _P],
-        "tt_mc_emit": [_P, _P, _I32, _F, _P, _P, _P, _P],
-        "tt_mc_bwd": [_P, _P, _I32, _F, _P, _P, _P, _P, _P],
-        "tt_rast_workspace_bytes": [_I32] * 4,
-        "tt_rast_fwd": [_P, _P] + [_I32] * 5 + [_P, _P, _P],
-        "tt_rast_bwd": [_P] * 4 + [_I32] * 5 + [_P, _P],
-        "tt_interp_fwd": [_P, _I32, _P, _P] + [_I32] * 6 + [_P, _P],
-        "tt_interp_bwd": [_P, _I32, _P, _P, _P] + [_I32] * 6 + [_P, _P, _P],
-        "tt_aa_fwd": [_P] * 6 + [_I32] * 6 + [_P, _P],
-        "tt_aa_bwd": [_P] * 7 + [_I32] * 6 + [_P, _P, _P],
-        "tt_mesh_workspace_bytes": [_I32, _I32],
-        "tt_mesh_components": [_P, _I32, _I32, _P, _P, _P],
-        "tt_mesh_compact_count": [_P, _P, _I32, _I32, _I32, ctypes.c_double, _I64, _P, _P, _P],
-        "tt_mesh_compact_emit": [_P, _P, _I32, _I32, _P, _P, _P, _P],
-        "tt_mesh_laplacian_fwd": [_P, _P, _P, _I32, _I32, _P, _P, _P],
-        "tt_mesh_laplacian_bwd": [_P, _P, _P, _I32, _I32, _P, _P, _P, _P],
-        "tt_mesh_nc_fwd": [_P, _P, _I32, _I32, _I32, _P, _P, _P],
-        "tt_mesh_nc_bwd": [_P, _P, _P, _I32, _I32, _P, _P, _P],
-        "tt_uv_workspace_bytes": [_I32, _I32, _I32],
-        "tt_uv_labels": [_P, _P, _P, _I32, _I32, _I32, _I32, _F, _I32, _P, _P, _P],
-        "tt_uv_charts": [_P] * 5 + [_I32] * 4 + [_P] * 5,
-        "tt_uv_pack": [_P, _I32, _I32, _I32, _P, _P],
-        "tt_uv_emit_count": [_P, _P, _I32, _I32, _I32, _P, _P, _P],
-        "tt_uv_emit": [_P] * 6 + [_I32, _F, _I32, _I32, _I32, _I32] + [_P] * 4,
-        "tt_uv_overlap": [_P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P],
-        "tt_tex_fill_workspace_bytes": [_I32, _I32],
-        "tt_tex_fill": [_P, _P, _I32, _I32, _I32, _P, _P, _P],
-    }
-    for name, argtypes in optional.items():
-        if name in SYMBOLS:
-            getattr(lib, name).argtypes = argtypes
-    for name in SYMBOLS[2:]:
-        if name != "tt_source_hash":
-            getattr(lib, name).restype = ctypes.c_int
-    lib.tt_hashgrid_n_params.restype = ctypes.c_int64
-    lib.tt_mc_workspace_bytes.restype = ctypes.c_int64
-    lib.tt_rast_workspace_bytes.restype = ctypes.c_int64
-    lib.tt_mesh_workspace_bytes.restype = ctypes.c_int64
-    lib.tt_uv_workspace_bytes.restype = ctypes.c_int64
-    lib.tt_tex_fill_workspace_bytes.restype = ctypes.c_int64
+    for name, (restype, argtypes) in _PROTOS.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 

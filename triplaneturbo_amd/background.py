@@ -18,7 +18,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .ops import _chk, _ptr, _stream
+from .ops import _chk, _launch
 from .registry import BaseModule, register
 
 Tensor = torch.Tensor
@@ -41,8 +41,7 @@ class _HashGridFn(torch.autograd.Function):
         params = _chk(params, "params")
         n = x.shape[0]
         out = torch.empty((n, cfg.n_levels * cfg.n_features_per_level), device=x.device, dtype=torch.float32)
-        st = _lib.load().tt_hashgrid_fwd(_ptr(x), n, _ptr(params), ctypes.byref(cfg), _ptr(out), _stream())
-        _lib.check(st, "tt_hashgrid_fwd")
+        _launch("tt_hashgrid_fwd", x, n, params, cfg, out)
         ctx.save_for_backward(x)
         ctx.cfg, ctx.n_params = cfg, params.numel()
         return out
@@ -52,9 +51,7 @@ class _HashGridFn(torch.autograd.Function):
     def backward(ctx, g_out):
         (x,) = ctx.saved_tensors
         grad = torch.zeros(ctx.n_params, device=x.device, dtype=torch.float32)
-        st = _lib.load().tt_hashgrid_bwd(_ptr(x), x.shape[0], _ptr(g_out.contiguous()), ctypes.byref(ctx.cfg),
-                                         _ptr(grad), _stream())
-        _lib.check(st, "tt_hashgrid_bwd")
+        _launch("tt_hashgrid_bwd", x, x.shape[0], g_out.contiguous(), ctx.cfg, grad)
         return None, grad, None
 
 

@@ -4,12 +4,10 @@ Forward and first backward are stock aten (they exist on ROCm); the second-order
 tt_grid_sample_2d_grad2 instead of the CUDA extension.  Same class structure as the reference (:31-79)."""
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from . import _lib
-from .ops import _chk, _ptr, _stream
+from .ops import _chk, _launch
 
 
 def grid_sample_2d(input, grid, padding_mode="zeros", align_corners=True):
@@ -19,7 +17,7 @@ def grid_sample_2d(input, grid, padding_mode="zeros", align_corners=True):
     return _GridSample2dForward.apply(input, grid, padding_mode, align_corners)
 
 
-_DTYPES = {torch.float32: 0, torch.float16: 1, torch.float64: 2}  # TT_DTYPE_* (include/tt_abi.h)
+_DTYPES = {torch.float32: _lib.TT_DTYPE_F32, torch.float16: _lib.TT_DTYPE_F16, torch.float64: _lib.TT_DTYPE_F64}
 
 
 def grad2_2d(grad2_grad_input, grad2_grad_grid, grad_output, input, grid, padding_mode, align_corners):
@@ -38,10 +36,8 @@ def grad2_2d(grad2_grad_input, grad2_grad_grid, grad_output, input, grid, paddin
     ggo = torch.empty_like(grad_output)
     gi = torch.empty_like(input)
     gg = torch.empty_like(grid)
-    st = _lib.load().tt_grid_sample_2d_grad2_typed(_DTYPES[dt], _ptr(g2i), _ptr(g2g), _ptr(grad_output), _ptr(input),
-                                                   _ptr(grid), N, C, H, W, M, int(padding_mode),
-                                                   int(bool(align_corners)), _ptr(ggo), _ptr(gi), _ptr(gg), _stream())
-    _lib.check(st, "tt_grid_sample_2d_grad2_typed")
+    _launch("tt_grid_sample_2d_grad2_typed", _DTYPES[dt], g2i, g2g, grad_output, input, grid, N, C, H, W, M,
+            int(padding_mode), int(bool(align_corners)), ggo, gi, gg)
     return [ggo, gi, gg]
 
 

@@ -74,6 +74,22 @@ def _contig(t: Optional[Tensor]) -> Optional[Tensor]:
     return None if t is None else t.contiguous()
 
 
+def _launch(name: str, *args, label: Optional[str] = None) -> None:
+    """One status-returning GPU entry point of the library on torch's current stream: lib.<name>(*args, stream), a
+    non-zero status raised as RuntimeError("<name> failed: ...").  A tensor goes in as its data pointer; the argtypes
+    load() bound from the header convert the rest (None -> null pointer, a ctypes.Structure -> its address, Python
+    numbers) and refuse anything else.  `args` holds every tensor (a `.contiguous()` temporary included) until the call
+    has returned.  `label`: the KernelTimer label the launch is timed under, when a timer is installed."""
+    fn = getattr(_lib.load(), name)
+    ptrs = [a.data_ptr() if isinstance(a, Tensor) else a for a in args]
+    if label is None:
+        status = fn(*ptrs, _stream())
+    else:
+        with _timed(label):
+            status = fn(*ptrs, _stream())
+    _lib.check(status, name)
+
+
 def _workspace(name: str, *dims: int, device) -> Tensor:
     """The uint8 workspace of the size lib.<name>(*dims) asks for (a tt_*_workspace_bytes query; negative = error)."""
     nbytes = int(getattr(_lib.load(), name)(*dims))
@@ -98,12 +114,15 @@ def _chk(t: Tensor, name: str, shape: Optional[Sequence[int]] = None, dtype=torc
     return t.contiguous()
 
 
-def _weights_struct(sdf_w: Sequence[Tensor], feat_w: Optional[Sequence[Tensor]]):
+def _weights_struct(sdf_w: Sequence[Tensor], net2_w: Optional[Sequence[Tensor]], net2: str = "feat v",
+                    net2_in: int = 96):
+    """tt_mlp_weights of the sdf net and a second net (net2_in -> 64 -> 64 -> 3) in v1..v3: the feature net, or
+    query_field's deformation net ("def d", 32 inputs)."""
     sw = [_chk(sdf_w[0], "sdf w1", (64, 32)), _chk(sdf_w[1], "sdf w2", (64, 64)), _chk(sdf_w[2], "sdf w3", (1, 64))]
     fw: List[Optional[Tensor]] = [None, None, None]
-    if feat_w is not None:
-        fw = [_chk(feat_w[0], "feat v1", (64, 96)), _chk(feat_w[1], "feat v2", (64, 64)),
-              _chk(feat_w[2], "feat v3", (3, 64))]
+    if net2_w is not None:
+        fw = [_chk(net2_w[0], net2 + "1", (64, net2_in)), _chk(net2_w[1], net2 + "2", (64, 64)),
+              _chk(net2_w[2], net2 + "3", (3, 64))]
     st = _lib.MlpWeights(*[_ptr(t) for t in sw + fw])
     return st, sw + fw  # keep tensors alive
 
@@ -153,7 +172,7 @@ def planes_pack(space_cache: Tensor) -> Tensor:
         raise ValueError(f"space_cache must be (P,6,32,H,W), got {tuple(space_cache.shape)}")
     P, _, _, H, W = space_cache.shape
     out = torch.empty((P, 6, H, W, 32), device=space_cache.device, dtype=torch.float32)
-    _lib.check(_lib.load().tt_planes_pack(_ptr(space_cache), _ptr(out), P, H, W, _stream()), "tt_planes_pack")
+    _launch("tt_planes_pack", space_cache, out, P, H, W)
     return out
 
 
@@ -163,8 +182,7 @@ def planes_unpack_grad(grad_packed: Tensor) -> Tensor:
     copies = grad_packed.shape[0] if grad_packed.ndim == 6 else 1
     P, _, H, W, _ = grad_packed.shape[-5:]
     out = torch.empty((P, 6, 32, H, W), device=grad_packed.device, dtype=torch.float32)
-    _lib.check(_lib.load().tt_planes_unpack_grad(_ptr(grad_packed), _ptr(out), P, H, W, copies, _stream()),
-               "tt_planes_unpack_grad")
+    _launch("tt_planes_unpack_grad", grad_packed, out, P, H, W, copies)
     return out
 
 
@@ -205,10 +223,8 @@ def query_points(packed: Tensor, sdf_w: Sequence[Tensor], feat_w: Optional[Seque
     feat = torch.empty((B * N, 3), device=dev, dtype=torch.float32) if need_features else None
     flags = (_lib.TT_Q_NORMAL if need_normal else 0) | (_lib.TT_Q_TEX if need_features else 0) | _lib.q_flag(
         _lib.resolve_precision(precision, exact_f32))
-    with _timed("tt_query_points"):
-        st = _lib.load().tt_query_points(_ptr(packed), ctypes.byref(wst), _ptr(points), B, N, P, views_per_prompt, H, W,
-                                         radius, sdf_bias_radius, flags, _ptr(sdf), _ptr(grad), _ptr(feat), _stream())
-    _lib.check(st, "tt_query_points")
+    _launch("tt_query_points", packed, wst, points, B, N, P, views_per_prompt, H, W, radius, sdf_bias_radius, flags,
+            sdf, grad, feat, label="tt_query_points")
     return sdf, grad, feat
 
 
@@ -220,17 +236,11 @@ def query_field(packed: Tensor, sdf_w: Sequence[Tensor], deform_w: Sequence[Tens
     points = _chk(points, "points")
     B, N, _ = points.shape
     P, _, H, W, _ = packed.shape
-    sw = [_chk(sdf_w[0], "sdf w1", (64, 32)), _chk(sdf_w[1], "sdf w2", (64, 64)), _chk(sdf_w[2], "sdf w3", (1, 64))]
-    dw = [_chk(deform_w[0], "def d1", (64, 32)), _chk(deform_w[1], "def d2", (64, 64)),
-          _chk(deform_w[2], "def d3", (3, 64))]
-    wst = _lib.MlpWeights(*[_ptr(t) for t in sw + dw])
+    wst, keep = _weights_struct(sdf_w, deform_w, "def d", 32)
     sdf = torch.empty((B * N, 1), device=points.device, dtype=torch.float32)
     deform = torch.empty((B * N, 3), device=points.device, dtype=torch.float32)
-    with _timed("tt_query_field"):
-        st = _lib.load().tt_query_field(_ptr(packed), ctypes.byref(wst), _ptr(points), B, N, P, views_per_prompt, H, W,
-                                        radius, sdf_bias_radius, _lib.q_flag(_lib.resolve_precision(precision, exact_f32)),
-                                        _ptr(sdf), _ptr(deform), _stream())
-    _lib.check(st, "tt_query_field")
+    _launch("tt_query_field", packed, wst, points, B, N, P, views_per_prompt, H, W, radius, sdf_bias_radius,
+            _lib.q_flag(_lib.resolve_precision(precision, exact_f32)), sdf, deform, label="tt_query_field")
     return sdf, deform
 
 
@@ -265,7 +275,6 @@ class _QueryPointsFn(torch.autograd.Function):
         B, N, _ = points.shape
         P, _, H, W, _ = packed.shape
         wst, keep = _weights_struct((w1, w2, w3), (v1, v2, v3))
-        lib = _lib.load()
         g_sdf, g_grad, g_feat = _contig(g_sdf), _contig(g_grad), _contig(g_feat)
         gw = [None] * 6
         g_cache = None
@@ -275,21 +284,17 @@ class _QueryPointsFn(torch.autograd.Function):
             gst = _grads_struct(gw)
             if g_sdf is not None or g_grad is not None:
                 ws = torch.empty((B * N, 4), device=packed.device, dtype=torch.float32)
-                st = lib.tt_points_bwd_geo(_ptr(packed), ctypes.byref(wst), _ptr(points), B, N, P, vpp, H, W, radius,
-                                           bias_r, qf, _ptr(g_sdf), _ptr(g_grad), _ptr(ws), _ptr(grad_packed),
-                                           ctypes.byref(gst), _stream())
-                _lib.check(st, "tt_points_bwd_geo")
+                _launch("tt_points_bwd_geo", packed, wst, points, B, N, P, vpp, H, W, radius, bias_r, qf, g_sdf, g_grad,
+                        ws, grad_packed, gst)
             if g_feat is not None:
-                st = lib.tt_points_bwd_tex(_ptr(packed), ctypes.byref(wst), _ptr(points), B, N, P, vpp, H, W, radius,
-                                           3, qf, _ptr(g_feat), _ptr(grad_packed), ctypes.byref(gst), _stream())
-                _lib.check(st, "tt_points_bwd_tex")
+                _launch("tt_points_bwd_tex", packed, wst, points, B, N, P, vpp, H, W, radius, 3, qf, g_feat,
+                        grad_packed, gst)
             g_cache = planes_unpack_grad(grad_packed) if ctx.needs_input_grad[0] else None
         g_points = None
         if ctx.needs_input_grad[7]:
             g_points = torch.empty_like(points)
-            st = lib.tt_points_bwd_x(_ptr(packed), ctypes.byref(wst), _ptr(points), B, N, P, vpp, H, W, radius, qf,
-                                     _ptr(g_sdf), _ptr(g_grad), _ptr(g_feat), _ptr(g_points), _stream())
-            _lib.check(st, "tt_points_bwd_x")
+            _launch("tt_points_bwd_x", packed, wst, points, B, N, P, vpp, H, W, radius, qf, g_sdf, g_grad, g_feat,
+                    g_points)
         return (g_cache, *gw, g_points, None, None, None, None, None)
 
 
@@ -334,19 +339,13 @@ class _QueryFieldFn(torch.autograd.Function):
         grad_packed = torch.zeros_like(packed)
         gw = [torch.zeros_like(t) for t in (w1, w2, w3, d1x3, d2, d3)]
         gst = _grads_struct(gw)
-        lib = _lib.load()
         if g_sdf is not None:
             ws = torch.empty((B * N, 4), device=packed.device, dtype=torch.float32)
-            g_sdf = g_sdf.contiguous()
-            st = lib.tt_points_bwd_geo(_ptr(packed), ctypes.byref(wst), _ptr(points), B, N, P, vpp, H, W, radius,
-                                       bias_r, qf, _ptr(g_sdf), None, _ptr(ws), _ptr(grad_packed),
-                                       ctypes.byref(gst), _stream())
-            _lib.check(st, "tt_points_bwd_geo")
+            _launch("tt_points_bwd_geo", packed, wst, points, B, N, P, vpp, H, W, radius, bias_r, qf,
+                    g_sdf.contiguous(), None, ws, grad_packed, gst)
         if g_def is not None:
-            g_def = g_def.contiguous()
-            st = lib.tt_points_bwd_tex(_ptr(packed), ctypes.byref(wst), _ptr(points), B, N, P, vpp, H, W, radius, 0,
-                                       qf, _ptr(g_def), _ptr(grad_packed), ctypes.byref(gst), _stream())
-            _lib.check(st, "tt_points_bwd_tex")
+            _launch("tt_points_bwd_tex", packed, wst, points, B, N, P, vpp, H, W, radius, 0, qf, g_def.contiguous(),
+                    grad_packed, gst)
         gw[3] = gw[3].view(64, 3, 32).sum(dim=1)
         g_cache = planes_unpack_grad(grad_packed) if ctx.needs_input_grad[0] else None
         return (g_cache, *gw, None, None, None, None, None)
@@ -399,37 +398,44 @@ def _make_cfg(packed: Tensor, n_rays: int, rays_per_view: int, n_samples: int, r
                           max(0.0, float(rc.skip_eps_geo)), inv_std_dev, stats)
 
 
-def render_forward_raw(packed: Tensor, sdf_w: Sequence[Tensor], feat_w: Sequence[Tensor], rays_o: Tensor,
-                       rays_d: Tensor, t_starts: Tensor, t_ends: Tensor, rays_per_view: int, rc: RenderConfig,
-                       per_sample: bool = True, image_w: int = 0):
-    """One tt_render_fwd call (decode kernel + march kernel).  rays_* (n_rays,3); t_* (n_rays,S); image_w = width
-    of each view's ray image (enables 8x4 pixel tiles).  Returns a dict of raw kernel outputs."""
+def _ray_args(packed: Tensor, rays_o: Tensor, rays_d: Tensor, t_starts: Tensor, t_ends: Tensor):
+    """The checked planes, rays (n_rays,3) and intervals (n_rays,S) of an entry point that walks rays."""
     packed = _chk(packed, "packed")
     rays_o, rays_d = _chk(rays_o, "rays_o"), _chk(rays_d, "rays_d")
     t_starts, t_ends = _chk(t_starts, "t_starts"), _chk(t_ends, "t_ends")
     n_rays, S = t_starts.shape
     if rays_o.shape != (n_rays, 3) or rays_d.shape != (n_rays, 3) or t_ends.shape != (n_rays, S):
         raise ValueError("ray / interval shapes disagree")
+    return packed, rays_o, rays_d, t_starts, t_ends
+
+
+def _ray_outputs(n_rays: int, device, S: Optional[int] = None) -> dict:
+    """Uninitialised per-ray outputs of the march and, given S, its per-sample weights / trans, in the order the
+    entry points take them."""
+    f32 = dict(device=device, dtype=torch.float32)
+    out = {"opacity": torch.empty((n_rays, 1), **f32), "depth": torch.empty((n_rays, 1), **f32),
+           "rgb_fg": torch.empty((n_rays, 3), **f32), "z_variance": torch.empty((n_rays, 1), **f32),
+           "normal_acc": torch.empty((n_rays, 3), **f32)}
+    if S is not None:
+        out.update(weights=torch.empty((n_rays * S, 1), **f32), trans=torch.empty((n_rays * S, 1), **f32))
+    return out
+
+
+def render_forward_raw(packed: Tensor, sdf_w: Sequence[Tensor], feat_w: Sequence[Tensor], rays_o: Tensor,
+                       rays_d: Tensor, t_starts: Tensor, t_ends: Tensor, rays_per_view: int, rc: RenderConfig,
+                       per_sample: bool = True, image_w: int = 0):
+    """One tt_render_fwd call (decode kernel + march kernel).  rays_* (n_rays,3); t_* (n_rays,S); image_w = width
+    of each view's ray image (enables 8x4 pixel tiles).  Returns a dict of raw kernel outputs."""
+    packed, rays_o, rays_d, t_starts, t_ends = _ray_args(packed, rays_o, rays_d, t_starts, t_ends)
+    n_rays, S = t_starts.shape
     cfg = _make_cfg(packed, n_rays, rays_per_view, S, rc, per_sample, image_w)
     wst, keep = _weights_struct(sdf_w, feat_w)
-    dev = packed.device
-    f32 = dict(device=dev, dtype=torch.float32)
-    out = {
-        "opacity": torch.empty((n_rays, 1), **f32), "depth": torch.empty((n_rays, 1), **f32),
-        "rgb_fg": torch.empty((n_rays, 3), **f32), "z_variance": torch.empty((n_rays, 1), **f32),
-        "normal_acc": torch.empty((n_rays, 3), **f32),
-        "weights": torch.empty((n_rays * S, 1), **f32), "trans": torch.empty((n_rays * S, 1), **f32),
-    }
+    f32 = dict(device=packed.device, dtype=torch.float32)
+    out = _ray_outputs(n_rays, packed.device, S)
     # per-sample decode results: outputs in training, inter-kernel workspace always
     out.update(sdf=torch.empty((n_rays * S, 1), **f32), sdf_grad=torch.empty((n_rays * S, 3), **f32),
                features=torch.empty((n_rays * S, 3), **f32))
-    with _timed("tt_render_fwd"):
-        st = _lib.load().tt_render_fwd(
-            _ptr(packed), ctypes.byref(wst), _ptr(rays_o), _ptr(rays_d), _ptr(t_starts), _ptr(t_ends),
-            ctypes.byref(cfg), _ptr(out["opacity"]), _ptr(out["depth"]), _ptr(out["rgb_fg"]),
-            _ptr(out["z_variance"]), _ptr(out["normal_acc"]), _ptr(out["weights"]), _ptr(out["trans"]),
-            _ptr(out.get("sdf")), _ptr(out.get("sdf_grad")), _ptr(out.get("features")), _stream())
-    _lib.check(st, "tt_render_fwd")
+    _launch("tt_render_fwd", packed, wst, rays_o, rays_d, t_starts, t_ends, cfg, *out.values(), label="tt_render_fwd")
     return out
 
 
@@ -441,27 +447,15 @@ def render_eval_raw(packed: Tensor, sdf_w: Sequence[Tensor], feat_w: Sequence[Te
     the fused decode + march kernel, no per-sample tensors, no autograd.  transmittance_eps / weight_eps > 0 switch
     on early termination / texture-decode skipping (error < transmittance_eps + S * weight_eps per ray); `stats` (2 x
     int64 on the device, zero-filled by the caller) receives the number of geometry / texture tile steps decoded."""
-    packed = _chk(packed, "packed")
-    rays_o, rays_d = _chk(rays_o, "rays_o"), _chk(rays_d, "rays_d")
-    t_starts, t_ends = _chk(t_starts, "t_starts"), _chk(t_ends, "t_ends")
+    packed, rays_o, rays_d, t_starts, t_ends = _ray_args(packed, rays_o, rays_d, t_starts, t_ends)
     n_rays, S = t_starts.shape
-    if rays_o.shape != (n_rays, 3) or rays_d.shape != (n_rays, 3) or t_ends.shape != (n_rays, S):
-        raise ValueError("ray / interval shapes disagree")
     cfg = _make_cfg(packed, n_rays, rays_per_view, S, rc, False, image_w)
     wst, keep = _weights_struct(sdf_w, feat_w)
-    f32 = dict(device=packed.device, dtype=torch.float32)
-    out = {"opacity": torch.empty((n_rays, 1), **f32), "depth": torch.empty((n_rays, 1), **f32),
-           "rgb_fg": torch.empty((n_rays, 3), **f32), "z_variance": torch.empty((n_rays, 1), **f32),
-           "normal_acc": torch.empty((n_rays, 3), **f32)}
+    out = _ray_outputs(n_rays, packed.device)
     if stats is not None and (stats.dtype != torch.int64 or stats.numel() < 2 or not stats.is_cuda):
         raise ValueError("stats must be a CUDA int64 tensor with 2 elements")
-    with _timed("tt_render_eval"):
-        st = _lib.load().tt_render_eval(
-            _ptr(packed), ctypes.byref(wst), _ptr(rays_o), _ptr(rays_d), _ptr(t_starts), _ptr(t_ends),
-            ctypes.byref(cfg), float(transmittance_eps), float(weight_eps), _ptr(out["opacity"]), _ptr(out["depth"]),
-            _ptr(out["rgb_fg"]), _ptr(out["z_variance"]), _ptr(out["normal_acc"]),
-            ctypes.c_void_p(stats.data_ptr()) if stats is not None else ctypes.c_void_p(0), _stream())
-    _lib.check(st, "tt_render_eval")
+    _launch("tt_render_eval", packed, wst, rays_o, rays_d, t_starts, t_ends, cfg, float(transmittance_eps),
+            float(weight_eps), *out.values(), stats, label="tt_render_eval")
     return out
 
 
@@ -486,10 +480,8 @@ def sample_uniform(n_rays: int, n_samples: int, near: float, far: float, device,
         jitter = _chk(jitter, "jitter")
         if jitter.shape != (n_rays, n_samples + 1):
             raise ValueError("jitter must be (n_rays, n_samples + 1)")
-    with torch.cuda.device(device):
-        st = _lib.load().tt_sample_uniform(n_rays, n_samples, float(near), float(far), _ptr(jitter), place,
-                                           _ptr(ts), _ptr(te), _stream())
-    _lib.check(st, "tt_sample_uniform")
+    with torch.cuda.device(device):  # (the launch takes `device`'s current stream)
+        _launch("tt_sample_uniform", n_rays, n_samples, float(near), float(far), jitter, place, ts, te)
     return ts, te
 
 
@@ -515,13 +507,19 @@ def sample_importance(t_starts: Tensor, t_ends: Tensor, sdf: Tensor, n_fine: int
     f32 = dict(device=t_starts.device, dtype=torch.float32)
     M = K + n_fine + 1
     ots, ote = torch.empty((n_rays, M), **f32), torch.empty((n_rays, M), **f32)
-    with _timed("tt_sample_importance"):
-        st = _lib.load().tt_sample_importance(_ptr(t_starts), _ptr(t_ends), _ptr(sdf), n_rays, K, int(n_fine),
-                                              float(inv_std), _ptr(inv_std_t), float(render_step_size),
-                                              _ptr(u_jitter), place,
-                                              _ptr(ots), _ptr(ote), _stream())
-    _lib.check(st, "tt_sample_importance")
+    _launch("tt_sample_importance", t_starts, t_ends, sdf, n_rays, K, int(n_fine), float(inv_std), inv_std_t,
+            float(render_step_size), u_jitter, place, ots, ote, label="tt_sample_importance")
     return ots, ote
+
+
+def _march_cfg(rc: RenderConfig, n_rays: int, S: int) -> "_lib.RenderCfg":
+    """tt_render_cfg of the march entry points: no planes, one view of n_rays rays."""
+    inv_std, inv_std_dev = _inv_std_args(rc)
+    return _lib.RenderCfg(n_prompts=1, views_per_prompt=1, plane_h=1, plane_w=1, rays_per_view=n_rays, n_samples=S,
+                          n_rays=n_rays, radius=rc.radius, sdf_bias_radius=rc.sdf_bias_radius, inv_std=inv_std,
+                          cos_anneal_ratio=rc.cos_anneal_ratio, rgb_grad_shrink=rc.rgb_grad_shrink,
+                          flags=_lib.TT_R_VOLSDF if rc.use_volsdf else 0, image_w=0,
+                          tile_sb=0, grad_copies=1, tile_chunk=0, inv_std_dev=inv_std_dev)
 
 
 @torch.no_grad()
@@ -535,24 +533,11 @@ def march_forward_raw(rays_d: Tensor, t_starts: Tensor, t_ends: Tensor, sdf: Ten
     n_rays, S = t_starts.shape
     if sdf.numel() != n_rays * S or sdf_grad.numel() != 3 * n_rays * S or features.numel() != 3 * n_rays * S:
         raise ValueError("per-sample tensors do not match (n_rays, S)")
-    inv_std, inv_std_dev = _inv_std_args(rc)
-    cfg = _lib.RenderCfg(n_prompts=1, views_per_prompt=1, plane_h=1, plane_w=1, rays_per_view=n_rays, n_samples=S,
-                         n_rays=n_rays, radius=rc.radius, sdf_bias_radius=rc.sdf_bias_radius, inv_std=inv_std,
-                         cos_anneal_ratio=rc.cos_anneal_ratio, rgb_grad_shrink=rc.rgb_grad_shrink,
-                         flags=_lib.TT_R_VOLSDF if rc.use_volsdf else 0, image_w=0,
-                         tile_sb=0, grad_copies=1, tile_chunk=0, inv_std_dev=inv_std_dev)
-    f32 = dict(device=rays_d.device, dtype=torch.float32)
+    cfg = _march_cfg(rc, n_rays, S)
     if out is None:
-        out = {"opacity": torch.empty((n_rays, 1), **f32), "depth": torch.empty((n_rays, 1), **f32),
-               "rgb_fg": torch.empty((n_rays, 3), **f32), "z_variance": torch.empty((n_rays, 1), **f32),
-               "normal_acc": torch.empty((n_rays, 3), **f32), "weights": torch.empty((n_rays * S, 1), **f32),
-               "trans": torch.empty((n_rays * S, 1), **f32)}
-    with _timed("tt_march_fwd"):
-        st = _lib.load().tt_march_fwd(_ptr(rays_d), _ptr(t_starts), _ptr(t_ends), ctypes.byref(cfg), _ptr(sdf),
-                                      _ptr(sdf_grad), _ptr(features), _ptr(out["opacity"]), _ptr(out["depth"]),
-                                      _ptr(out["rgb_fg"]), _ptr(out["z_variance"]), _ptr(out["normal_acc"]),
-                                      _ptr(out["weights"]), _ptr(out["trans"]), _stream())
-    _lib.check(st, "tt_march_fwd")
+        out = _ray_outputs(n_rays, rays_d.device, S)
+    _launch("tt_march_fwd", rays_d, t_starts, t_ends, cfg, sdf, sdf_grad, features, out["opacity"], out["depth"],
+            out["rgb_fg"], out["z_variance"], out["normal_acc"], out["weights"], out["trans"], label="tt_march_fwd")
     return out
 
 
@@ -565,22 +550,13 @@ def march_backward_raw(rays_d: Tensor, t_starts: Tensor, t_ends: Tensor, fwd: di
     the dict march_forward_raw / render_forward_raw returned (opacity, depth, trans).  g_inv_std_rays (n_rays), if
     given, receives d loss / d inv_std per ray."""
     n_rays, S = t_starts.shape
-    inv_std, inv_std_dev = _inv_std_args(rc)
-    cfg = _lib.RenderCfg(n_prompts=1, views_per_prompt=1, plane_h=1, plane_w=1, rays_per_view=n_rays, n_samples=S,
-                         n_rays=n_rays, radius=rc.radius, sdf_bias_radius=rc.sdf_bias_radius, inv_std=inv_std,
-                         cos_anneal_ratio=rc.cos_anneal_ratio, rgb_grad_shrink=rc.rgb_grad_shrink,
-                         flags=_lib.TT_R_VOLSDF if rc.use_volsdf else 0, image_w=0,
-                         tile_sb=0, grad_copies=1, tile_chunk=0, inv_std_dev=inv_std_dev)
+    cfg = _march_cfg(rc, n_rays, S)
     if out is None:
         out = torch.empty((n_rays * S, 4), device=rays_d.device, dtype=torch.float32)
     gs = [_contig(t)
           for t in (g_opacity, g_depth, g_rgb_fg, g_z_variance, g_normal_acc, g_weights, g_sdf, g_sdf_grad)]
-    with _timed("tt_march_bwd"):
-        st = _lib.load().tt_march_bwd(_ptr(rays_d), _ptr(t_starts), _ptr(t_ends), ctypes.byref(cfg),
-                                      _ptr(fwd["opacity"]), _ptr(fwd["depth"]), _ptr(fwd["trans"]), _ptr(sdf),
-                                      _ptr(sdf_grad), _ptr(features), *[_ptr(t) for t in gs], _ptr(g_inv_std_rays),
-                                      _ptr(out), _stream())
-    _lib.check(st, "tt_march_bwd")
+    _launch("tt_march_bwd", rays_d, t_starts, t_ends, cfg, fwd["opacity"], fwd["depth"], fwd["trans"], sdf, sdf_grad,
+            features, *gs, g_inv_std_rays, out, label="tt_march_bwd")
     return out
 
 
@@ -644,24 +620,14 @@ class _TriplaneRenderFn(torch.autograd.Function):
 
         g_op, g_depth, g_rgb, g_zvar, g_nacc, g_weights, g_sdf, g_sdf_grad, g_features = (
             _contig(t) for t in (g_op, g_depth, g_rgb, g_zvar, g_nacc, g_weights, g_sdf, g_sdf_grad, g_features))
-        lib = _lib.load()
         g_k_rays = None
         if ctx.needs_input_grad[14]:  # d loss / d inv_std, one partial per ray (summed below in a fixed order)
             g_k_rays = torch.empty((n_rays,), device=packed.device, dtype=torch.float32)
-        with _timed("tt_render_bwd_geo"):
-            st = lib.tt_render_bwd_geo(
-                _ptr(packed), ctypes.byref(wst), _ptr(rays_o), _ptr(rays_d), _ptr(t_starts), _ptr(t_ends),
-                ctypes.byref(cfg), _ptr(opacity), _ptr(depth), _ptr(trans), _ptr(sdf), _ptr(sdf_grad),
-                _ptr(features), _ptr(g_op), _ptr(g_depth), _ptr(g_rgb), _ptr(g_zvar), _ptr(g_nacc), _ptr(g_weights),
-                _ptr(g_sdf), _ptr(g_sdf_grad), _ptr(g_k_rays), _ptr(workspace), _ptr(grad_packed), ctypes.byref(gst),
-                _stream())
-        _lib.check(st, "tt_render_bwd_geo")
-        with _timed("tt_render_bwd_tex"):
-            st = lib.tt_render_bwd_tex(
-                _ptr(packed), ctypes.byref(wst), _ptr(rays_o), _ptr(rays_d), _ptr(t_starts), _ptr(t_ends),
-                ctypes.byref(cfg_tex), _ptr(weights), _ptr(features), _ptr(g_rgb), _ptr(g_features),
-                _ptr(grad_packed), ctypes.byref(gst), _stream())
-        _lib.check(st, "tt_render_bwd_tex")
+        _launch("tt_render_bwd_geo", packed, wst, rays_o, rays_d, t_starts, t_ends, cfg, opacity, depth, trans, sdf,
+                sdf_grad, features, g_op, g_depth, g_rgb, g_zvar, g_nacc, g_weights, g_sdf, g_sdf_grad, g_k_rays,
+                workspace, grad_packed, gst, label="tt_render_bwd_geo")
+        _launch("tt_render_bwd_tex", packed, wst, rays_o, rays_d, t_starts, t_ends, cfg_tex, weights, features, g_rgb,
+                g_features, grad_packed, gst, label="tt_render_bwd_tex")
         g_packed = None
         if ctx.needs_input_grad[0]:
             g_packed = grad_packed[0] if copies == 1 else grad_packed.sum(dim=0)
@@ -693,9 +659,7 @@ def decode_rays(packed: Tensor, sdf_w: Sequence[Tensor], feat_w: Optional[Sequen
                 need_normal: bool = False, need_features: bool = False, image_w: int = 0):
     """Per-sample decode along rays without the march (no grad): sdf (n_rays,S), optionally sdf_grad (n_rays,S,3)
     and features (n_rays,S,3).  The sampler's proposal pass uses the sdf-only form."""
-    packed = _chk(packed, "packed")
-    rays_o, rays_d = _chk(rays_o, "rays_o"), _chk(rays_d, "rays_d")
-    t_starts, t_ends = _chk(t_starts, "t_starts"), _chk(t_ends, "t_ends")
+    packed, rays_o, rays_d, t_starts, t_ends = _ray_args(packed, rays_o, rays_d, t_starts, t_ends)
     n_rays, S = t_starts.shape
     cfg = _make_cfg(packed, n_rays, rays_per_view, S, rc, False, image_w)
     wst, keep = _weights_struct(sdf_w, feat_w if need_features else None)
@@ -704,11 +668,8 @@ def decode_rays(packed: Tensor, sdf_w: Sequence[Tensor], feat_w: Optional[Sequen
     grad = torch.empty((n_rays, S, 3), **f32) if need_normal else None
     feat = torch.empty((n_rays, S, 3), **f32) if need_features else None
     flags = (_lib.TT_Q_NORMAL if need_normal else 0) | (_lib.TT_Q_TEX if need_features else 0)
-    with _timed("tt_decode_rays"):
-        st = _lib.load().tt_decode_rays(_ptr(packed), ctypes.byref(wst), _ptr(rays_o), _ptr(rays_d), _ptr(t_starts),
-                                        _ptr(t_ends), ctypes.byref(cfg), flags, _ptr(sdf), _ptr(grad), _ptr(feat),
-                                        _stream())
-    _lib.check(st, "tt_decode_rays")
+    _launch("tt_decode_rays", packed, wst, rays_o, rays_d, t_starts, t_ends, cfg, flags, sdf, grad, feat,
+            label="tt_decode_rays")
     return sdf, grad, feat
 
 
@@ -724,9 +685,7 @@ class _PatchCompositeFn(torch.autograd.Function):
         if patch.shape != (B, PS, PS, C):
             raise ValueError(f"patch {tuple(patch.shape)} does not match low {tuple(low.shape)}")
         out = torch.empty((B, H, W, C), device=low.device, dtype=torch.float32)
-        st = _lib.load().tt_patch_composite_fwd(_ptr(low), _ptr(patch), _ptr(out), B, h, w, H, W, C, PS, py, px,
-                                                _stream())
-        _lib.check(st, "tt_patch_composite_fwd")
+        _launch("tt_patch_composite_fwd", low, patch, out, B, h, w, H, W, C, PS, py, px)
         ctx.meta = (B, h, w, H, W, C, PS, py, px, detach_low)
         return out
 
@@ -734,13 +693,10 @@ class _PatchCompositeFn(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_out):
         B, h, w, H, W, C, PS, py, px, detach_low = ctx.meta
-        g_out = g_out.contiguous()
         want_low = ctx.needs_input_grad[0] and not detach_low
         g_low = torch.empty((B, h, w, C), device=g_out.device, dtype=torch.float32) if want_low else None
         g_patch = torch.empty((B, PS, PS, C), device=g_out.device, dtype=torch.float32)
-        st = _lib.load().tt_patch_composite_bwd(_ptr(g_out), _ptr(g_low), _ptr(g_patch), B, h, w, H, W, C, PS, py, px,
-                                                _stream())
-        _lib.check(st, "tt_patch_composite_bwd")
+        _launch("tt_patch_composite_bwd", g_out.contiguous(), g_low, g_patch, B, h, w, H, W, C, PS, py, px)
         return g_low, (g_patch if ctx.needs_input_grad[1] else None), None, None, None, None, None
 
 
@@ -784,11 +740,8 @@ class _CompositeFn(torch.autograd.Function):
         disparity = torch.empty((n, 1), **f32)
         vis = torch.empty((n, 3), **f32) if mode == 1 else None
         vis_white = torch.empty((n, 3), **f32) if mode != 0 else None
-        st = _lib.load().tt_composite_fwd(_ptr(opacity), _ptr(depth), _ptr(rgb_fg), _ptr(normal_acc), _ptr(bg),
-                                          bg_stride, _ptr(cam_dist), _ptr(c2w), n, rays_per_view, mode, view_group,
-                                          _ptr(comp_rgb), _ptr(disparity), _ptr(comp_normal), _ptr(vis),
-                                          _ptr(vis_white), _stream())
-        _lib.check(st, "tt_composite_fwd")
+        _launch("tt_composite_fwd", opacity, depth, rgb_fg, normal_acc, bg, bg_stride, cam_dist, c2w, n, rays_per_view,
+                mode, view_group, comp_rgb, disparity, comp_normal, vis, vis_white)
         ctx.save_for_backward(opacity, depth, rgb_fg, normal_acc, bg, cam_dist, *(() if c2w is None else (c2w,)))
         ctx.meta = (n, bg_stride, rays_per_view, mode, view_group)
         ctx.set_materialize_grads(False)
@@ -809,11 +762,8 @@ class _CompositeFn(torch.autograd.Function):
         g_op, g_dep = torch.empty((n, 1), **f32), torch.empty((n, 1), **f32)
         g_fg, g_na = torch.empty((n, 3), **f32), torch.empty((n, 3), **f32)
         g_bg = torch.empty((n, 3), **f32) if ctx.needs_input_grad[4] else None
-        st = _lib.load().tt_composite_bwd(_ptr(opacity), _ptr(depth), _ptr(rgb_fg), _ptr(normal_acc), _ptr(bg),
-                                          bg_stride, _ptr(cam_dist), _ptr(c2w), n, rays_per_view, mode, view_group,
-                                          _ptr(g_rgb), _ptr(g_disp), _ptr(g_cn), _ptr(g_vis), _ptr(g_visw), _ptr(g_op),
-                                          _ptr(g_dep), _ptr(g_fg), _ptr(g_na), _ptr(g_bg), _stream())
-        _lib.check(st, "tt_composite_bwd")
+        _launch("tt_composite_bwd", opacity, depth, rgb_fg, normal_acc, bg, bg_stride, cam_dist, c2w, n, rays_per_view,
+                mode, view_group, g_rgb, g_disp, g_cn, g_vis, g_visw, g_op, g_dep, g_fg, g_na, g_bg)
         if g_bg is not None:
             g_bg = g_bg.sum(dim=0).view_as(bg) if bg_stride == 0 else g_bg.view_as(bg)
         return g_op, g_dep, g_fg, g_na, g_bg, None, None, None, None, None
@@ -848,7 +798,7 @@ class _EikonalFn(torch.autograd.Function):
         if g.ndim != 2 or g.shape[1] != 3:
             raise ValueError(f"sdf_grad must be (n, 3), got {tuple(g.shape)}")
         loss = torch.empty((), device=g.device, dtype=torch.float32)
-        _lib.check(_lib.load().tt_eikonal_fwd(_ptr(g), g.shape[0], _ptr(loss), _stream()), "tt_eikonal_fwd")
+        _launch("tt_eikonal_fwd", g, g.shape[0], loss)
         ctx.save_for_backward(g)
         return loss
 
@@ -857,8 +807,7 @@ class _EikonalFn(torch.autograd.Function):
     def backward(ctx, g_loss):
         g, = ctx.saved_tensors
         out = torch.empty_like(g)
-        g_loss = g_loss.contiguous().float()
-        _lib.check(_lib.load().tt_eikonal_bwd(_ptr(g), _ptr(g_loss), g.shape[0], _ptr(out), _stream()), "tt_eikonal_bwd")
+        _launch("tt_eikonal_bwd", g, g_loss.contiguous().float(), g.shape[0], out)
         return out
 
 
@@ -877,16 +826,14 @@ class _MarchingCubesFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, level, deformation, isovalue):
         R = level.shape[0]
-        lib = _lib.load()
         ws = _workspace("tt_mc_workspace_bytes", R, device=level.device)
         totals = torch.empty(2, device=level.device, dtype=torch.int32)
-        _lib.check(lib.tt_mc_count(_ptr(level), R, isovalue, _ptr(ws), _ptr(totals), _stream()), "tt_mc_count")
+        _launch("tt_mc_count", level, R, isovalue, ws, totals)
         n_vert, n_tri = (int(x) for x in totals.cpu())
         v_pos = torch.empty((n_vert, 3), device=level.device, dtype=torch.float32)
         t_pos_idx = torch.empty((n_tri, 3), device=level.device, dtype=torch.int32)
         if n_vert > 0:
-            _lib.check(lib.tt_mc_emit(_ptr(level), _ptr(deformation), R, isovalue, _ptr(ws), _ptr(v_pos),
-                                      _ptr(t_pos_idx), _stream()), "tt_mc_emit")
+            _launch("tt_mc_emit", level, deformation, R, isovalue, ws, v_pos, t_pos_idx)
         ctx.save_for_backward(level, deformation, ws)
         ctx.isovalue = isovalue
         ctx.mark_non_differentiable(t_pos_idx)
@@ -906,9 +853,7 @@ class _MarchingCubesFn(torch.autograd.Function):
             if g_def is not None:
                 g_def.zero_()
         else:
-            g_v = g_v.contiguous()
-            _lib.check(_lib.load().tt_mc_bwd(_ptr(level), _ptr(deformation), R, ctx.isovalue, _ptr(ws), _ptr(g_v),
-                                             _ptr(g_level), _ptr(g_def), _stream()), "tt_mc_bwd")
+            _launch("tt_mc_bwd", level, deformation, R, ctx.isovalue, ws, g_v.contiguous(), g_level, g_def)
         return (g_level if ctx.needs_input_grad[0] else None,
                 g_def if ctx.needs_input_grad[1] else None, None)
 
@@ -991,10 +936,8 @@ class _MeshLaplacianFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, v_pos, topo):
         loss = torch.empty((), device=v_pos.device, dtype=torch.float32)
-        with _timed("mesh_laplacian_fwd"):
-            _lib.check(_lib.load().tt_mesh_laplacian_fwd(_ptr(v_pos), _ptr(topo.nbr_ptr), _ptr(topo.nbr_col),
-                                                         topo.n_vertices, topo.n_faces, _ptr(topo.ws), _ptr(loss),
-                                                         _stream()), "tt_mesh_laplacian_fwd")
+        _launch("tt_mesh_laplacian_fwd", v_pos, topo.nbr_ptr, topo.nbr_col, topo.n_vertices, topo.n_faces, topo.ws, loss,
+                label="mesh_laplacian_fwd")
         ctx.save_for_backward(v_pos)
         ctx.topo = topo
         return loss
@@ -1005,11 +948,8 @@ class _MeshLaplacianFn(torch.autograd.Function):
         v_pos, = ctx.saved_tensors
         topo = ctx.topo
         g = torch.empty_like(v_pos)
-        g_loss = g_loss.contiguous().float()
-        with _timed("mesh_laplacian_bwd"):
-            _lib.check(_lib.load().tt_mesh_laplacian_bwd(_ptr(v_pos), _ptr(topo.nbr_ptr), _ptr(topo.nbr_col),
-                                                         topo.n_vertices, topo.n_faces, _ptr(g_loss), _ptr(topo.ws),
-                                                         _ptr(g), _stream()), "tt_mesh_laplacian_bwd")
+        _launch("tt_mesh_laplacian_bwd", v_pos, topo.nbr_ptr, topo.nbr_col, topo.n_vertices, topo.n_faces,
+                g_loss.contiguous().float(), topo.ws, g, label="mesh_laplacian_bwd")
         return g, None
 
 
@@ -1025,10 +965,8 @@ class _MeshNormalConsistencyFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, v_nrm, topo):
         loss = torch.empty((), device=v_nrm.device, dtype=torch.float32)
-        with _timed("mesh_nc_fwd"):
-            _lib.check(_lib.load().tt_mesh_nc_fwd(_ptr(v_nrm), _ptr(topo.edges_i32), topo.n_vertices, topo.n_faces,
-                                                  topo.n_edges, _ptr(topo.ws), _ptr(loss), _stream()),
-                       "tt_mesh_nc_fwd")
+        _launch("tt_mesh_nc_fwd", v_nrm, topo.edges_i32, topo.n_vertices, topo.n_faces, topo.n_edges, topo.ws, loss,
+                label="mesh_nc_fwd")
         ctx.save_for_backward(v_nrm)
         ctx.topo = topo
         return loss
@@ -1039,11 +977,8 @@ class _MeshNormalConsistencyFn(torch.autograd.Function):
         v_nrm, = ctx.saved_tensors
         topo = ctx.topo
         g = torch.empty_like(v_nrm)
-        g_loss = g_loss.contiguous().float()
-        with _timed("mesh_nc_bwd"):
-            _lib.check(_lib.load().tt_mesh_nc_bwd(_ptr(v_nrm), _ptr(topo.nbr_ptr), _ptr(topo.nbr_col),
-                                                  topo.n_vertices, topo.n_edges, _ptr(g_loss), _ptr(g), _stream()),
-                       "tt_mesh_nc_bwd")
+        _launch("tt_mesh_nc_bwd", v_nrm, topo.nbr_ptr, topo.nbr_col, topo.n_vertices, topo.n_edges,
+                g_loss.contiguous().float(), g, label="mesh_nc_bwd")
         return g, None
 
 
@@ -1058,9 +993,8 @@ def mesh_face_components(topo: MeshTopology) -> Tensor:
     """(T,) int32 connected-component label per face: the smallest face index of its component (faces joined by an
     edge that exactly two face edges use).  Leaves the per-component face counts in topo.ws."""
     labels = torch.empty(topo.n_faces, device=topo.tri.device, dtype=torch.int32)
-    with _timed("mesh_components"):
-        _lib.check(_lib.load().tt_mesh_components(_ptr(topo.face_pairs), topo.face_pairs.shape[0], topo.n_faces,
-                                                  _ptr(topo.ws), _ptr(labels), _stream()), "tt_mesh_components")
+    _launch("tt_mesh_components", topo.face_pairs, topo.face_pairs.shape[0], topo.n_faces, topo.ws, labels,
+            label="mesh_components")
     return labels
 
 
@@ -1084,20 +1018,16 @@ def mesh_remove_small_components(v_pos: Tensor, t_pos_idx: Tensor, threshold, to
         raise ValueError("threshold is NaN")
     thr_int = 0 if frac_mode else max(min(int(threshold), 1 << 62), -(1 << 62))
     frac = max(min(float(threshold), 1e300), -1e300) if frac_mode else 0.0
-    lib = _lib.load()
     V, T = topo.n_vertices, topo.n_faces
     labels = mesh_face_components(topo)
     totals = torch.empty(2, device=v_pos.device, dtype=torch.int32)
-    with _timed("mesh_compact_count"):
-        _lib.check(lib.tt_mesh_compact_count(_ptr(topo.tri), _ptr(labels), V, T, int(frac_mode), frac, thr_int,
-                                             _ptr(topo.ws), _ptr(totals), _stream()), "tt_mesh_compact_count")
+    _launch("tt_mesh_compact_count", topo.tri, labels, V, T, int(frac_mode), frac, thr_int, topo.ws, totals,
+            label="mesh_compact_count")
     n_vert, n_tri = (int(x) for x in totals.cpu())
     v_out = torch.empty((n_vert, 3), device=v_pos.device, dtype=torch.float32)
     t_out = torch.empty((n_tri, 3), device=v_pos.device, dtype=torch.int32)
     if n_tri > 0:
-        with _timed("mesh_compact_emit"):
-            _lib.check(lib.tt_mesh_compact_emit(_ptr(v_pos), _ptr(topo.tri), V, T, _ptr(topo.ws), _ptr(v_out),
-                                                _ptr(t_out), _stream()), "tt_mesh_compact_emit")
+        _launch("tt_mesh_compact_emit", v_pos, topo.tri, V, T, topo.ws, v_out, t_out, label="mesh_compact_emit")
     return v_out, t_out.to(t_pos_idx.dtype)
 
 
@@ -1128,7 +1058,6 @@ def uv_atlas(v_pos: Tensor, t_pos_idx: Tensor, topology: Optional[MeshTopology] 
     if topo.n_vertices != V or tuple(topo.tri.shape) != tuple(t_pos_idx.shape):
         raise ValueError("topology was built for another mesh")
     T, N, pad = topo.n_faces, int(texture_size), int(padding)
-    lib = _lib.load()
     dev = v_pos.device
     ws = _workspace("tt_uv_workspace_bytes", V, T, N, device=dev)
     i32 = dict(device=dev, dtype=torch.int32)
@@ -1138,9 +1067,7 @@ def uv_atlas(v_pos: Tensor, t_pos_idx: Tensor, topology: Optional[MeshTopology] 
     tri, pairs = topo.tri, topo.face_pairs
     P = pairs.shape[0]
     labels = torch.empty(T, **i32)
-    with _timed("uv_labels"):
-        _lib.check(lib.tt_uv_labels(_ptr(v_pos), _ptr(tri), _ptr(pairs), V, T, P, int(rounds), float(tau), N, _ptr(ws),
-                                    _ptr(labels), _stream()), "tt_uv_labels")
+    _launch("tt_uv_labels", v_pos, tri, pairs, V, T, P, int(rounds), float(tau), N, ws, labels, label="uv_labels")
     singleton = torch.zeros(T, device=dev, dtype=torch.uint8)
     flags = torch.empty(T, device=dev, dtype=torch.uint8)
     chart = torch.empty(T, **i32)
@@ -1148,14 +1075,13 @@ def uv_atlas(v_pos: Tensor, t_pos_idx: Tensor, topology: Optional[MeshTopology] 
     totals = torch.empty(4, **i32)
     r = 0
     while True:
-        with _timed("uv_charts"):
-            _lib.check(lib.tt_uv_charts(_ptr(v_pos), _ptr(tri), _ptr(pairs), _ptr(labels), _ptr(singleton), V, T, P, N,
-                                        _ptr(ws), _ptr(chart), _ptr(box), _ptr(totals), _stream()), "tt_uv_charts")
+        _launch("tt_uv_charts", v_pos, tri, pairs, labels, singleton, V, T, P, N, ws, chart, box, totals,
+                label="uv_charts")
         C = int(totals[0].item())
         box_h = box[:C].cpu()
         off_h = torch.empty((C, 2), dtype=torch.int32)
         scale_h = torch.zeros(1, dtype=torch.float32)
-        st = lib.tt_uv_pack(_ptr(box_h), C, N, pad, _ptr(off_h), _ptr(scale_h))
+        st = _lib.load().tt_uv_pack(_ptr(box_h), C, N, pad, _ptr(off_h), _ptr(scale_h))  # on the host: no stream
         if st == -2:  # TT_ERR_UNSUPPORTED
             raise RuntimeError(f"uv_atlas: {C} charts do not fit a {N}^2 atlas with padding {pad} (every chart box is at "
                                f"least {2 * pad + 1}^2 texels): use a larger texture_size or a smaller padding")
@@ -1163,17 +1089,12 @@ def uv_atlas(v_pos: Tensor, t_pos_idx: Tensor, topology: Optional[MeshTopology] 
         offsets = off_h.to(dev)
         scale = float(scale_h[0])
         with _timed("uv_emit"):
-            _lib.check(lib.tt_uv_emit_count(_ptr(tri), _ptr(chart), V, T, N, _ptr(ws), _ptr(totals), _stream()),
-                       "tt_uv_emit_count")
+            _launch("tt_uv_emit_count", tri, chart, V, T, N, ws, totals)
             Vt = int(totals[0].item())
             v_tex = torch.empty((Vt, 2), device=dev, dtype=torch.float32)
             t_tex_idx = torch.empty((T, 3), **i32)
-            _lib.check(lib.tt_uv_emit(_ptr(v_pos), _ptr(tri), _ptr(labels), _ptr(chart), _ptr(box), _ptr(offsets), C,
-                                      scale, V, T, N, pad, _ptr(ws), _ptr(v_tex), _ptr(t_tex_idx), _stream()),
-                       "tt_uv_emit")
-        with _timed("uv_overlap"):
-            _lib.check(lib.tt_uv_overlap(_ptr(v_tex), _ptr(t_tex_idx), Vt, V, T, N, _ptr(ws), _ptr(flags),
-                                         _ptr(totals), _stream()), "tt_uv_overlap")
+            _launch("tt_uv_emit", v_pos, tri, labels, chart, box, offsets, C, scale, V, T, N, pad, ws, v_tex, t_tex_idx)
+        _launch("tt_uv_overlap", v_tex, t_tex_idx, Vt, V, T, N, ws, flags, totals, label="uv_overlap")
         n_flagged, n_covered = (int(x) for x in totals[:2].cpu())
         if n_flagged == 0:
             break
@@ -1202,9 +1123,7 @@ def texture_fill(img: Tensor, mask: Tensor) -> Tensor:
     if not isinstance(mask, torch.Tensor) or not mask.is_cuda or tuple(mask.shape) != (H, W):
         raise ValueError(f"mask must be a GPU tensor of shape {(H, W)}")
     m = (mask != 0).to(torch.uint8).contiguous()
-    lib = _lib.load()
     ws = _workspace("tt_tex_fill_workspace_bytes", H, W, device=x.device)
     out = torch.empty_like(x)
-    with _timed("tex_fill"):
-        _lib.check(lib.tt_tex_fill(_ptr(x), _ptr(m), H, W, C, _ptr(ws), _ptr(out), _stream()), "tt_tex_fill")
+    _launch("tt_tex_fill", x, m, H, W, C, ws, out, label="tex_fill")
     return out[..., 0] if squeeze else out

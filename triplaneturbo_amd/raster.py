@@ -16,8 +16,7 @@ from typing import Optional, Tuple, Union
 
 import torch
 
-from . import _lib
-from .ops import _chk, _ptr, _stream, _workspace
+from .ops import _chk, _launch, _workspace
 
 Tensor = torch.Tensor
 MAX_TRIS = 1 << 24  # TT_RAST_MAX_TRIS: tri + 1 is stored as a float
@@ -66,11 +65,9 @@ class _RasterizeFn(torch.autograd.Function):
     def forward(ctx, pos, tri, H, W):
         B, V, _ = pos.shape
         T = tri.shape[0]
-        lib = _lib.load()
         ws = _workspace("tt_rast_workspace_bytes", B, T, H, W, device=pos.device)
         rast = torch.empty((B, H, W, 4), device=pos.device, dtype=torch.float32)
-        _lib.check(lib.tt_rast_fwd(_ptr(pos), _ptr(tri), B, V, T, H, W, _ptr(ws), _ptr(rast), _stream()),
-                   "tt_rast_fwd")
+        _launch("tt_rast_fwd", pos, tri, B, V, T, H, W, ws, rast)
         ctx.save_for_backward(pos, tri, rast)
         return rast
 
@@ -83,8 +80,7 @@ class _RasterizeFn(torch.autograd.Function):
         B, V, _ = pos.shape
         H, W = rast.shape[1], rast.shape[2]
         g_pos = torch.empty_like(pos)
-        _lib.check(_lib.load().tt_rast_bwd(_ptr(pos), _ptr(tri), _ptr(rast), _ptr(g_rast.contiguous()), B, V,
-                                           tri.shape[0], H, W, _ptr(g_pos), _stream()), "tt_rast_bwd")
+        _launch("tt_rast_bwd", pos, tri, rast, g_rast.contiguous(), B, V, tri.shape[0], H, W, g_pos)
         return g_pos, None, None, None
 
 
@@ -106,8 +102,7 @@ class _InterpolateFn(torch.autograd.Function):
         A, V, C = attr.shape
         B, H, W, _ = rast.shape
         out = torch.empty((B, H, W, C), device=attr.device, dtype=torch.float32)
-        _lib.check(_lib.load().tt_interp_fwd(_ptr(attr), A, _ptr(rast), _ptr(tri), B, V, tri.shape[0], H, W, C,
-                                             _ptr(out), _stream()), "tt_interp_fwd")
+        _launch("tt_interp_fwd", attr, A, rast, tri, B, V, tri.shape[0], H, W, C, out)
         ctx.save_for_backward(attr, rast, tri)
         return out
 
@@ -121,9 +116,7 @@ class _InterpolateFn(torch.autograd.Function):
         g_rast = torch.empty_like(rast) if ctx.needs_input_grad[1] else None
         if g_attr is None and g_rast is None:
             return None, None, None
-        _lib.check(_lib.load().tt_interp_bwd(_ptr(attr), A, _ptr(rast), _ptr(tri), _ptr(g_out.contiguous()), B, V,
-                                             tri.shape[0], H, W, C, _ptr(g_attr), _ptr(g_rast), _stream()),
-                   "tt_interp_bwd")
+        _launch("tt_interp_bwd", attr, A, rast, tri, g_out.contiguous(), B, V, tri.shape[0], H, W, C, g_attr, g_rast)
         return g_attr, g_rast, None
 
 
@@ -145,9 +138,7 @@ class _AntialiasFn(torch.autograd.Function):
         B, H, W, C = color.shape
         V = pos.shape[1]
         out = torch.empty_like(color)
-        _lib.check(_lib.load().tt_aa_fwd(_ptr(color), _ptr(rast), _ptr(pos), _ptr(tri), _ptr(edge_ofs),
-                                         _ptr(edge_tri), B, V, tri.shape[0], H, W, C, _ptr(out), _stream()),
-                   "tt_aa_fwd")
+        _launch("tt_aa_fwd", color, rast, pos, tri, edge_ofs, edge_tri, B, V, tri.shape[0], H, W, C, out)
         ctx.save_for_backward(color, rast, pos, tri, edge_ofs, edge_tri)
         return out
 
@@ -161,9 +152,8 @@ class _AntialiasFn(torch.autograd.Function):
         V = pos.shape[1]
         g_color = torch.empty_like(color)
         g_pos = torch.empty_like(pos) if ctx.needs_input_grad[2] else None
-        _lib.check(_lib.load().tt_aa_bwd(_ptr(color), _ptr(rast), _ptr(pos), _ptr(tri), _ptr(edge_ofs),
-                                         _ptr(edge_tri), _ptr(g_out.contiguous()), B, V, tri.shape[0], H, W, C,
-                                         _ptr(g_color), _ptr(g_pos), _stream()), "tt_aa_bwd")
+        _launch("tt_aa_bwd", color, rast, pos, tri, edge_ofs, edge_tri, g_out.contiguous(), B, V, tri.shape[0], H, W, C,
+                g_color, g_pos)
         return (g_color if ctx.needs_input_grad[0] else None), None, g_pos, None, None, None
 
 
