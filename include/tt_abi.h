@@ -183,9 +183,8 @@ typedef struct {
  * cos_anneal_ratio.  Honoured by tt_render_forward / _backward, the march entry points and the fused eval render. */
 #define TT_R_VOLSDF 128
 
-#define TT_R_WGRAD_F32 4  /* TUNING BUILD ONLY (-DTT_TUNING; the product library returns TT_ERR_UNSUPPORTED): backward
-                             weight-gradient outer products on the fp32-input MFMA instead of split-fp16 products with
-                             per-launch operand scales; the round-2 A/B switch, TT_R_SPLIT2 only */
+#define TT_R_WGRAD_F32 4  /* RESERVED, always TT_ERR_UNSUPPORTED: selected the round-2 backward kernels with their weight-gradient
+                             outer products on the fp32-input MFMA (an A/B variant of TT_R_SPLIT2; removed from the tree) */
 #define TT_R_BWD_SOLO 8   /* backward: force the one-wave-per-tile decode kernels (the default) */
 #define TT_R_BWD_PAIR 16  /* RESERVED, always TT_ERR_UNSUPPORTED: selected the experimental wave-pair texture kernel of round 4
                              (two waves per SIMD; correct and 1.4x slower; removed from the tree in round 6) */

@@ -26,8 +26,8 @@ def _case(seed):
               cos_anneal_ratio=rnd.choice([0.0, 0.3, 1.0]))
     knobs = dict(tile_sb=rnd.choice([0, 1, 2, 4, 8, 16, 32]), tile_chunk=rnd.choice([0, 0, 1, 3, 8, 64]),
                  grad_copies=rnd.choice([1, 1, 2, 3]))
-    # (the same three draws as rounds 3-4 -- exact_f32, wgrad_f32, bwd_pair -- so every seed keeps its scene: the two A/B
-    # kernels of those rounds left the product library, their draws now select the fast mode)
+    # (the same three draws as rounds 3-4 -- the fp32 mode and the two A/B kernels of those rounds -- so every seed keeps its
+    # scene: the A/B kernels left the library, their draws now select the fast mode)
     r_f32, r_a = rnd.random(), rnd.random()
     near, far = rnd.choice([(0.1, 4.0), (0.3, 3.2), (1.0, 2.0)])
     jittered = rnd.random() < 0.5

@@ -1,6 +1,7 @@
 """CPU tests of the host side: plugin registry / configs / schedules, sampler contract, synthetic inputs,
 C-ABI surface (header <-> library <-> ctypes agreement).  No GPU, no compute calls into the library."""
 import ctypes
+import dataclasses
 import os
 import re
 import subprocess
@@ -337,6 +338,23 @@ def test_c_abi_rejects_bad_arguments_without_touching_the_gpu():
     assert lib.tt_sample_uniform(4, 8, 0.1, 4.0, null, 2, one, one, null) == -1
     assert lib.tt_sample_importance(one, one, one, 4, 8, 4, 100.0, null, 0.05, null, 7, one, one, null) == -1
     assert lib.tt_sample_importance(one, one, one, 4, 8, 4, 0.0, null, 0.05, null, 0, one, one, null) == -1  # no inv_std at all
+
+
+def test_reserved_render_flags_are_unsupported_before_any_hip_call():
+    """TT_R_BWD_PAIR and TT_R_WGRAD_F32 selected A/B kernels that left the tree: the constants keep their values, every
+    build answers TT_ERR_UNSUPPORTED (-2) from tt_validate_cfg, i.e. before a pointer is looked at or a HIP call is made."""
+    _lib.build()
+    lib = _lib.load()
+    null = ctypes.c_void_p(0)
+    w = _lib.MlpWeights()
+    for flag in (_lib.TT_R_BWD_PAIR, _lib.TT_R_WGRAD_F32, _lib.TT_R_WGRAD_F32 | _lib.TT_R_SPLIT2):
+        cfg = _lib.RenderCfg(1, 1, 8, 8, 16, 4, 16, 1.0, 0.5, 100.0, 1.0, 1.0, flag, 0, 0, 1)
+        assert lib.tt_render_bwd_geo(null, ctypes.byref(w), null, null, null, null, ctypes.byref(cfg), *([null] * 17),
+                                     ctypes.byref(w), null) == -2
+        assert lib.tt_render_bwd_tex(null, ctypes.byref(w), null, null, null, null, ctypes.byref(cfg), *([null] * 5),
+                                     ctypes.byref(w), null) == -2
+    from triplaneturbo_amd import ops
+    assert "wgrad_f32" not in {f.name for f in dataclasses.fields(ops.RenderConfig)}
 
 
 def test_product_library_never_reads_the_environment():

@@ -47,7 +47,9 @@ for seed in seeds:
     if os.environ.get("TT_FUZZ_KNOBS"):  # e.g. TT_FUZZ_KNOBS="tile_sb=0,tile_chunk=0"
         for kv in os.environ["TT_FUZZ_KNOBS"].split(","):
             k, v = kv.split("=")
-            kn[k] = type(kn[k])(int(v)) if k in kn else bool(int(v))  # (wgrad_f32=1 / bwd_pair=1: tuning build, TT_USE_TUNING=1)
+            if k not in kn:
+                sys.exit(f"TT_FUZZ_KNOBS: unknown knob {k!r} (known: {', '.join(sorted(kn))})")
+            kn[k] = type(kn[k])(v)
     if os.environ.get("TT_FUZZ_RC"):  # e.g. TT_FUZZ_RC="inv_std=10"
         for kv in os.environ["TT_FUZZ_RC"].split(","):
             k, v = kv.split("=")

@@ -4,7 +4,7 @@ Replays the tile decomposition of the kernels (csrc/tt_device.h: TileGeom -- bw 
 32 samples per tile) over PatchRenderer's two renders (42 x 42 global rays + a 40 x 40 patch of a 128 x 128 image, 193
 importance samples from the oracle's sampler) and counts, per (plane, tile): active corner references, DISTINCT texels
 (= the fewest 128-byte atomics any in-tile combine can issue), and the references that lose their slot under a slot
-window of a given shape (torus hash of the texel coordinates, first claim wins, as scatter_claim does).
+window of a given shape (torus hash of the texel coordinates, first claim wins, as the scatter's claims do).
 
     python tools/scatter_sim.py            # table over tile shapes and window shapes
 """

@@ -17,23 +17,16 @@ struct AlphaTerms {
 // the extra FMAs are free there.
 __device__ __forceinline__ float rcp_(float x) {
     const float r = __builtin_amdgcn_rcpf(x);
-#ifdef TT_FAST_RCP  // (dev A/B: rounds 1-4)
-    return r;
-#else
     // (x = 0, +-inf or a denormal: r is inf / 0 and the refinement would be inf * 0 = NaN -- keep the hardware's r, as the
     // reference's IEEE quotient gives inf / 0 there; one NaN test, no lane-mask combination)
     const float nr = fmaf(fmaf(-x, r, 1.f), r, r);
     return nr == nr ? nr : r;
-#endif
 }
 // logistic function 1 / (1 + exp(-x)) on the hardware exp2 + reciprocal, to ~2 ulp: the argument t = -x log2(e) is carried
 // as a pair (t_hi = rn(x c_hi), t_lo = the rounding error of that product + x c_lo: ~2^-48 |t|), exp2(t_hi) corrected by
 // (1 + ln2 t_lo) -- rounds 1-4 used exp2(rn(x c)) alone, whose relative error grows as |x| 2^-24 (1e-6 at |x| = 20).
 // t is clamped at 126 so that 1 + exp2(t) stays finite (x < -87: the result is ~1e-38 instead of the reference's 0 / denormal).
 __device__ __forceinline__ float sigmoid_(float x) {
-#ifdef TT_FAST_LOGISTIC  // (dev A/B: rounds 1-4)
-    return rcp_(1.f + __builtin_amdgcn_exp2f(x * -1.44269504f));
-#endif
     // |x| > 128 saturates like torch.sigmoid (an overflowing sdf * inv_std, +-inf: t_lo would be inf - inf); a NaN stays a NaN
     x = x < -128.f ? -128.f : x;
     x = x > 128.f ? 128.f : x;

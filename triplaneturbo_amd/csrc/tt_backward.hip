@@ -11,9 +11,6 @@
 //
 // Everything per-sample is RECOMPUTED from the planes; the forward saves only trans / weights / features.
 #include "tt_backward_common.h"
-#ifndef TT_GEO_REREAD_RAY
-#define TT_GEO_REREAD_RAY 0
-#endif
 
 // =====================================================================================================
 // geometry half
@@ -38,18 +35,16 @@ struct BwdGeoParams {
 
 #define GEO_SCRATCH_FLOATS (2 * 64 * XS)
 // split-fp16 weight images (tt_mfma16.h): W1, W2 at their fp32 offsets (same bytes); the transposed products use
-// transposed COPIES appended to them (TT_BWD_WT_COPIES, tt_backward_common.h: 26 KB of LDS nothing else wants at one wave
-// per SIMD) or, without, read the forward images through ds_read_b64_tr_b16 (mv16t)
+// transposed COPIES appended to them (tt_backward_common.h: 26 KB of LDS nothing else wants at one wave per SIMD)
 #define GOFF_W1T LDS_GEO_FLOATS
 #define GOFF_W2T (GOFF_W1T + IMG16_FLOATS(32, 64))
-#define LDS_GEO16_FLOATS (TT_BWD_WT_COPIES ? GOFF_W2T + IMG16_FLOATS(64, 64) : LDS_GEO_FLOATS)
-#define GEO_PAIR (TT_BWD_WT_COPIES ? PAIR_SEQ : PAIR_TR)
+#define LDS_GEO16_FLOATS (GOFF_W2T + IMG16_FLOATS(64, 64))
 // PREC_S3: the images of the third terms, appended (28 KB with the transposed copies: 157 KB per workgroup in all)
 #define GLO_W1 LDS_GEO16_FLOATS
 #define GLO_W2 (GLO_W1 + LO16_FLOATS(64, 32))
 #define GLO_W1T (GLO_W2 + LO16_FLOATS(64, 64))
-#define GLO_W2T (GLO_W1T + (TT_BWD_WT_COPIES ? LO16_FLOATS(32, 64) : 0))
-#define LDS_GEO3_FLOATS (GLO_W2T + (TT_BWD_WT_COPIES ? LO16_FLOATS(64, 64) : 0))
+#define GLO_W2T (GLO_W1T + LO16_FLOATS(32, 64))
+#define LDS_GEO3_FLOATS (GLO_W2T + LO16_FLOATS(64, 64))
 template <int PREC>
 struct GeoWFloats {
     static constexpr int value = PREC == PREC_S3 ? LDS_GEO3_FLOATS : LDS_GEO16_FLOATS;
@@ -68,10 +63,8 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
         stage_weights<PREC, 64, 32>(L + OFF_W1, L + GLO_W1, w.w1);
         stage_weights<PREC, 64, 64>(L + OFF_W2, L + GLO_W2, w.w2);
         lds_load_matrix(L + OFF_W3, w.w3, 1, 64, 64);
-        if (TT_BWD_WT_COPIES) {
-            stage_weights_t<PREC, 64, 32>(L + GOFF_W1T, L + GLO_W1T, w.w1);
-            stage_weights_t<PREC, 64, 64>(L + GOFF_W2T, L + GLO_W2T, w.w2);
-        }
+        stage_weights_t<PREC, 64, 32>(L + GOFF_W1T, L + GLO_W1T, w.w1);
+        stage_weights_t<PREC, 64, 64>(L + GOFF_W2T, L + GLO_W2T, w.w2);
     }
     const tt_render_cfg& cfg = p.cfg;
     // ---- per-launch operand scales of the fp16 outer products dW1 += a1 u^T, dW2 += a2 v^T (wgrad16 above) ----
@@ -145,12 +138,10 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
         const int ks = i % tg.sb;  // this lane's sample offset inside a tile step
         const int view = (int)(ray / cfg.rays_per_view);
         const size_t pofs = (size_t)(view / cfg.views_per_prompt) * plane_stride;
-#if !TT_GEO_REREAD_RAY
         const float ox = p.rays_o[ray * 3 + 0], oy = p.rays_o[ray * 3 + 1], oz = p.rays_o[ray * 3 + 2];
         // rays_d == null: explicit points (tt_points_bwd_*), x = rays_o exactly
         const float dx = p.rays_d ? p.rays_d[ray * 3 + 0] : 0.f, dy = p.rays_d ? p.rays_d[ray * 3 + 1] : 0.f,
                     dz = p.rays_d ? p.rays_d[ray * 3 + 2] : 0.f;
-#endif
         const int s_end = (ck + 1) * tg.chunk < S ? (ck + 1) * tg.chunk : S;
         // per-step inputs are prefetched one tile step ahead (see k_decode_bwd_tex); a step past the chunk reads a
         // clamped, valid address
@@ -185,14 +176,6 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
                          cfg.skip_eps_geo)))
                 continue;
             float tm, px, py, pz;
-#if TT_GEO_REREAD_RAY
-            // (per-ray constants re-read per tile step, as in k_decode_bwd_tex: dev A/B, off by default)
-            long long rr = ray;
-            asm volatile("" : "+v"(rr));
-            const float ox = p.rays_o[rr * 3 + 0], oy = p.rays_o[rr * 3 + 1], oz = p.rays_o[rr * 3 + 2];
-            const float dx = p.rays_d ? p.rays_d[rr * 3 + 0] : 0.f, dy = p.rays_d ? p.rays_d[rr * 3 + 1] : 0.f,
-                        dz = p.rays_d ? p.rays_d[rr * 3 + 2] : 0.f;
-#endif
             sample_position(ox, oy, oz, dx, dy, dz, in.ts, in.te, tm, px, py, pz);
             const float X = scale_coord(px, cfg.radius), Y = scale_coord(py, cfg.radius),
                         Z = scale_coord(pz, cfg.radius);
@@ -221,33 +204,21 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
                 for (int e2 = 0; e2 < 4; ++e2) a2[4 * g + e2] = h2[4 * g + e2] > 0.f ? w3[e2] : 0.f;
             }
             // a2 and a1 feed a product AND an outer product (dW2, dW1): split once under the per-launch scales
-            Split16<64, GEO_PAIR, NT> a2s, a1s;  // (consumed by the transposed products and the outer-product staging)
-            float ua1 = 1.f;                 // factor of a1 where it is RAW
+            Split16<64, PAIR_SEQ, NT> a2s, a1s;  // (consumed by the transposed products and the outer-product staging)
+            float ua1 = 1.f;                     // factor of a1 where it is RAW
             if (WG16) {
-                split16_vec<64, GEO_PAIR, NT>(a2, sA2, a2s);
-#if TT_BWD_WT_COPIES
+                split16_vec<64, PAIR_SEQ, NT>(a2, sA2, a2s);
                 mv16_pre<64, 64, true, NT>(L + GOFF_W2T, a2s, 1.f / sA2, a1, i, hi, &ua1, L + GLO_W2T);
-#else
-                mv16t_pre<64, 64, 64, NT>(L + OFF_W2, 0, a2s, 1.f / sA2, a1, lane, L + GLO_W2);
-#endif
-            } else if constexpr (TT_BWD_WT_COPIES) {
-                mvtx_copy<PREC, 64, 64, 64>(L + GOFF_W2T, L + GLO_W2T, L + OFF_W2, a2, a1, i, hi);
             } else {
-                mvtx<PREC, 64, 64, 64>(L + OFF_W2, L + GLO_W2, 0, a2, a1, i, hi);
+                mvtx_copy<PREC, 64, 64, 64>(L + GOFF_W2T, L + GLO_W2T, L + OFF_W2, a2, a1, i, hi);
             }
 #pragma unroll
             for (int r = 0; r < 32; ++r) a1[r] = h1[r] > 0.f ? a1[r] : 0.f;
             if (WG16) {
-                split16_vec<64, GEO_PAIR, NT>(a1, sA1 * ua1, a1s);
-#if TT_BWD_WT_COPIES
+                split16_vec<64, PAIR_SEQ, NT>(a1, sA1 * ua1, a1s);
                 mv16_pre<32, 64, false, NT>(L + GOFF_W1T, a1s, 1.f / sA1, q, i, hi, nullptr, L + GLO_W1T);
-#else
-                mv16t_pre<32, 64, 32, NT>(L + OFF_W1, 0, a1s, 1.f / sA1, q, lane, L + GLO_W1);
-#endif
-            } else if constexpr (TT_BWD_WT_COPIES) {
-                mvtx_copy<PREC, 32, 64, 32>(L + GOFF_W1T, L + GLO_W1T, L + OFF_W1, a1, q, i, hi);
             } else {
-                mvtx<PREC, 32, 64, 32>(L + OFF_W1, L + GLO_W1, 0, a1, q, i, hi);
+                mvtx_copy<PREC, 32, 64, 32>(L + GOFF_W1T, L + GLO_W1T, L + OFF_W1, a1, q, i, hi);
             }
             TT_PHASE(3);
             // ---- network + plane gradients ----
@@ -383,14 +354,9 @@ static void launch_bwd_geo(const BwdGeoParams& p0, long long blocks, hipStream_t
             LAUNCH_GEO(PREC_S3, true);
         else
             LAUNCH_GEO(PREC_S2, true);
-    } else if (prec == PREC_F32) {
+    } else {  // TT_R_EXACT_F32
         LAUNCH_GEO(PREC_F32, false);
     }
-#ifdef TT_TUNING
-    else {  // TT_R_WGRAD_F32: the round-2 A/B kernel (two-piece products, fp32 outer products)
-        LAUNCH_GEO(PREC_S2, false);
-    }
-#endif
 #undef LAUNCH_GEO
 }
 int tt_launch_march_bwd(const float* rays_d, const float* t_starts, const float* t_ends, const tt_render_cfg* cfg,

@@ -116,7 +116,6 @@ __device__ __forceinline__ float wg16_scale(float bound) {
     return __builtin_bit_cast(float, (unsigned)(268 - E) << 23);
 }
 __device__ __forceinline__ unsigned wg16_pack(float x) {  // (hi | lo << 16), both round-to-nearest-even: hi + lo ~ x
-#if TT_SPLIT_PAIR_ASM
     // three instructions in one block (see split_pair, tt_mfma16.h): hi = f16(x); r = x * 1.0 - hi (exact); pack(x, r)
     unsigned out;
     float r;
@@ -126,15 +125,6 @@ __device__ __forceinline__ unsigned wg16_pack(float x) {  // (hi | lo << 16), bo
         : "=&v"(out), "=&v"(r)
         : "v"(x));
     return out;
-#else
-    const float hf = (float)cvt_pk16(x, 0.f).x;
-#if TT_SPLIT_MODE != 2
-    return cvt_pk16u(x, x - hf);  // (both halves with the same rounding: one packed convert)
-#else
-    const unsigned h = cvt_pk16u(x, 0.f), l = cvt_pk16u_lo(x - hf, 0.f);
-    return (h & 0xffffu) | (l << 16);
-#endif
-#endif
 }
 template <int N>
 __device__ __forceinline__ void stage_rows16(float* S, const float (&v)[N / 2], int j, int hi, float sc) {
@@ -275,20 +265,21 @@ __device__ __forceinline__ void flush_wgrad_reduced(float* R, int& parity, const
     { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f }
 
 // ---- plane-gradient scatter, combined on the matrix cores --------------------------------------------------
-// (The text below describes the idea and its ROUNDS 2-5 form, kept as -DTT_SCATTER_V1 for A/B builds; the product build
-// uses the round-6 form further down -- 16 x 16 texel table, dense ranks, short flush -- under "#else  // !TT_SCATTER_V1".)
 // fp32 global atomics are THE bottleneck of the backward on MI355X (~325 G atomic float-adds/s chip-wide,
 // pattern-independent; LDS fp32 atomics are even slower: one ds_add_f32 wave-instruction per ~190 cycles per CU,
 // both measured with tools/atomic_bench.hip / tools/lds_atomic_bench.hip).  A tile is 32 adjacent rays at one
-// depth, so its 128 (sample, corner) references per plane touch only ~40-50 distinct texels.  Per plane the
+// depth, so its 128 (sample, corner) references per plane touch only ~25-70 distinct texels.  Per plane the
 // tile's gradient is
-//        G[slot][ch] = sum_j M[slot][j] * Q[j][ch]        (64 texel slots x 32 samples x 32 channels)
-// with M the sparse matrix of corner coefficients -- a GEMM, done exactly in fp32 with 32 MFMAs.  slot = 8x8
-// torus hash of the texel coordinates (the 4 corners of one sample never collide, so M is filled with plain
-// stores); slot ownership is claimed with one integer LDS CAS per reference, and a reference that loses its slot
-// to a different texel (footprint wider than 8 texels) falls back to direct global atomics.  The MFMA C/D layout
-// (lane <-> channel, register <-> slot) is exactly what a coalesced 128-byte global atomic needs, so every
-// occupied slot is flushed with ONE atomic instruction per half-wave straight from the accumulator registers.
+//        G[row][ch] = sum_j M[row][j] * Q[j][ch]        (64 texel rows x 32 samples x 32 channels)
+// with M the sparse matrix of corner coefficients -- a GEMM on the matrix cores.  Every distinct texel of the tile gets a
+// row of M (the 4 corners of one sample never share one, so M is filled with plain stores): a texel is claimed with one
+// integer LDS CAS per reference in a 16 x 16 torus hash table of the texel coordinates, and a reference that loses its
+// entry to a different texel (footprint wider than 16 texels) falls back to direct global atomics.  The MFMA C/D layout
+// (lane <-> channel, register <-> row) is exactly what a coalesced 128-byte global atomic needs, so every
+// occupied row is flushed with ONE atomic instruction per half-wave straight from the accumulator registers.
+// Everything except the rare lost-reference path is straight-line code (no per-reference branches: inactive references
+// CAS a per-lane dummy word and store to a dump row of M), so that plane p's MFMAs (one wave per SIMD: nothing else would
+// fill them) run over plane p+1's corner set-up, claims and M fill.
 #define MS XS  // row stride of M (floats): same conflict-free stride as the transposition scratch
 
 // M region: either the fp32 matrix (65 rows x MS floats, EXACT) or its split-fp16 image -- two planes (hi, lo) of
@@ -310,20 +301,14 @@ __device__ __forceinline__ void scatter_clear(float* M, int lane) {
     }
 }
 
-// (TT_SCATTER_V1, rounds 2-5; kept for A/B builds) The three planes of one tile step, software-pipelined.  Everything except the rare lost-reference path is
-// straight-line code (no per-reference branches: inactive references CAS a per-lane dummy tag and store to a dump
-// row of M; empty slots are dropped by the buffer range check), so that plane p's 32 MFMAs (2048 matrix-pipe cycles,
-// one wave per SIMD: nothing else would fill them) run over plane p+1's corner set-up, slot claims and M fill:
-//   operands of plane p -> registers (A = M rows, B = Q columns) ; M back to zero
-//   prep(p+1) ; GEMM(p) || claim(p+1) ; flush(p) from the accumulators ; tags(p) back to empty
-// Tags are double-buffered (the flush of plane p reads them after plane p+1 claimed its slots).
-// LDS per wave: M = 64 rows + 1 dump row (stride MS), tags = 2 x 64 slots + 32 dummies (SCATTER_TAG_INTS).
+// LDS per wave: M = 64 rows + 1 dump row (stride MS), and SCATTER_TAG_INTS ints of which the first 32 are the dummy words
+// (scatter_init_tags; the rest is unused since the texel table moved behind the lost-reference lists).
 #define SCATTER_TAG_INTS 160
 
 struct PlaneRefs {  // the two corners (2hi, 2hi+1) of this lane's sample in one plane
     float c0, c1;   // coefficient (0: no reference), normalised per sample unless EXACT
     int o0, o1;     // absolute texel index (prompt and plane included)
-    int h0, h1;     // entry of the texel table: 16x16 torus hash of the texel coordinates (V1: 8x8 slot)
+    int h0, h1;     // entry of the texel table: 16x16 torus hash of the texel coordinates
     float qs;       // factor the sample's row of Q must be staged with (inverse of the coefficient normalisation)
 };
 // NORM: the sample's four coefficients are scaled by the power of two that brings the largest into [2^14, 2^15) -- the
@@ -349,20 +334,10 @@ __device__ __forceinline__ PlaneRefs plane_refs(const float (&coef)[4], const in
     r.o1 = hi ? aoff[3] : aoff[1];
     r.h0 = hi ? hs[2] : hs[0];
     r.h1 = hi ? hs[3] : hs[1];
-#ifdef TT_SCATTER_V1  // the 8 x 8 window of rounds 2-5 out of the 16 x 16 hash
-    r.h0 = ((r.h0 >> 1) & 0x38) | (r.h0 & 7);
-    r.h1 = ((r.h1 >> 1) & 0x38) | (r.h1 & 7);
-#endif
     return r;
 }
 __device__ __forceinline__ void scatter_init_tags(int* tags, int lane) {
-#ifdef TT_SCATTER_V1
-    tags[lane] = -1;
-    tags[64 + lane] = -1;
-    if (lane < 32) tags[128 + lane] = -2;  // dummies: never empty, never equal to a texel index
-#else
     if (lane < 32) tags[lane] = -2;  // the dummy words inactive references CAS: never empty, never equal to a texel index
-#endif
 }
 
 // store / clear one coefficient of M (column i = this lane's sample; row 64 = dump row)
@@ -389,7 +364,7 @@ __device__ __forceinline__ void m_zero(float* M, int row, int i) {
     }
 }
 
-// references that lost their slot (tile footprint wider than the slot window / texel table: sparse rays) go straight to global
+// references that lost their table entry (tile footprint wider than the texel table: sparse rays) go straight to global
 // memory, one half-wave per reference (lanes <-> channels: a coalesced 128-byte atomic each)
 __device__ __forceinline__ void scatter_lost(const PlaneRefs& r, bool l0, bool l1, const float* Qs, float* Ls,
                                              __amdgpu_buffer_rsrc_t grsrc, int i, int hi) {
@@ -427,232 +402,25 @@ __device__ __forceinline__ void scatter_lost(const PlaneRefs& r, bool l0, bool l
     }
 }
 
-#ifdef TT_SCATTER_V1
-struct ClaimState {
-    bool w0, w1;  // wrote M (slot won or shared with the same texel)
-    bool m0, m1;  // won the slot: this lane resets the tag
-    bool l0, l1;  // lost the slot to a different texel: direct atomics
-};
-
-// st (tuning build): per-wave counters [0] active references, [1] lost references, [2] plane-tiles
-template <bool EXACT>
-__device__ __forceinline__ ClaimState scatter_claim(const PlaneRefs& r, float* M, int* tg, int* dummy, int i,
-                                                    unsigned long long* st = nullptr) {
-    ClaimState s;
-    const bool a0 = r.c0 != 0.f, a1 = r.c1 != 0.f;
-    const int old0 = atomicCAS(a0 ? tg + r.h0 : dummy, -1, r.o0);
-    const int old1 = atomicCAS(a1 ? tg + r.h1 : dummy, -1, r.o1);
-    s.m0 = old0 == -1;
-    s.m1 = old1 == -1;
-    s.w0 = tt_eq_either(old0, -1, r.o0);  // won the slot, or it already holds this texel (one compare: tt_device.h)
-    s.w1 = tt_eq_either(old1, -1, r.o1);
-    // not written to M.  (An inactive reference CASes the dummy tag -2, so it is "not written" too; what makes a
-    // reference LOST is a non-zero coefficient on top -- scatter_lost tests the coefficient it selects with this flag,
-    // instead of combining two lane masks here.)
-    s.l0 = !s.w0;
-    s.l1 = !s.w1;
-    m_store<EXACT>(M, s.w0 ? r.h0 : 64, i, r.c0);
-    m_store<EXACT>(M, s.w1 ? r.h1 : 64, i, r.c1);
-#ifdef TT_TUNING
-    if (st) {  // wave-uniform values, flushed once per wave with the phase timers
-        st[0] += __popcll(__ballot(a0)) + __popcll(__ballot(a1));
-        st[1] += __popcll(__ballot((s.l0 ? r.c0 : 0.f) != 0.f)) + __popcll(__ballot((s.l1 ? r.c1 : 0.f) != 0.f));
-        st[2] += 1;
-    }
-#endif
-    return s;
-}
-
-// prep(pl, refs): corner set-up of plane pl for this lane's sample (and, where Q differs per plane, its staging into
-// Qs[j*33 + ch] -- the previous plane's B operand is in registers by then).  M: all-zero on entry and on exit.
-// G = M Q for the two 32-slot tiles is either 32 fp32 MFMAs (EXACT, and the texture kernel -- see there; 2048
-// matrix-pipe cycles) or, in the geometry kernel (3.51 -> 3.33 ms), the split-fp16 scheme of tt_mfma16.h: M is already a
-// (hi, lo) fp16 image normalised per sample (plane_refs<true>, m_store), the B operand (16 samples of this lane's
-// channel per half-wave) is normalised per channel and split, and 12 fp16 MFMAs (384 cycles) do the work.
-// prep(pl, refs): corner set-up of plane pl for this lane's sample AND the staging of its row of Q, scaled by refs.qs,
-// into Qs[j*33 + ch] (the previous plane's B operand is in registers by then).  M: all-zero on entry and on exit.
-template <bool EXACT, class Prep>
-__device__ __forceinline__ void scatter_planes(float* __restrict__ grad, unsigned grad_bytes, const float* Qs, float* M,
-                                               int* tags, float* Ls, int i, int hi, Prep&& prep,
-                                               unsigned long long* st = nullptr) {
-    // BUFFER atomics with a 32-bit BYTE offset (texel << 7 | channel * 4) from the gradient copy: an empty slot's tag
-    // is -1, its offset 0xFFFFFF80 + 4 ch lies beyond num_records (the host refuses gradient buffers of 4 GB - 256 B
-    // and more) and the hardware range check drops the atomic -- no compare, no exec-mask branch per slot (the
-    // predicated global atomics this replaced cost ~100 cycles per slot pair, 12 % of the kernel).
-    const __amdgpu_buffer_rsrc_t grsrc = __builtin_amdgcn_make_buffer_rsrc(grad, 0, (int)grad_bytes, 0x00020000);
-    const unsigned lane_b = 4u * (unsigned)i;
-    int* const dummy = tags + 128 + i;
-    PlaneRefs rc, rn;
-    ClaimState sc, sn;
-#ifdef TT_TUNING  // sub-phase cycles of the epilogue (geometry kernel: st[3..5] = operands+prep / GEMM+claim / flush+reset+lost)
-    unsigned long long sp_t = __builtin_amdgcn_s_memtime();
-#define TT_SUBPHASE(k)                                                    \
-    do {                                                                  \
-        if (st) {                                                         \
-            __builtin_amdgcn_sched_barrier(0);                            \
-            const unsigned long long t_now = __builtin_amdgcn_s_memtime(); \
-            st[k] += t_now - sp_t;                                        \
-            sp_t = t_now;                                                 \
-            __builtin_amdgcn_sched_barrier(0);                            \
-        }                                                                 \
-    } while (0)
-#else
-#define TT_SUBPHASE(k) \
-    do {               \
-    } while (0)
-#endif
-#ifdef TT_SCATTER_DIRECT  // dev A/B (tools/build_variants.py): every reference straight to global memory, no slots
-    for (int pl = 0; pl < 3; ++pl) {
-        prep(pl, rc);
-        sc.w0 = sc.w1 = sc.m0 = sc.m1 = false;
-        sc.l0 = sc.l1 = true;
-        scatter_lost(rc, sc.l0, sc.l1, Qs, Ls, grsrc, i, hi);
-    }
-    return;
-#endif
-    prep(0, rc);
-    sc = scatter_claim<EXACT>(rc, M, tags, dummy, i, st);
-    scatter_lost(rc, sc.l0, sc.l1, Qs, Ls, grsrc, i, hi);
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) {
-        int* const tg = tags + 64 * (pl & 1);
-        // ---- G = M Q; once its operands are in registers: M back to all-zero, next plane's set-up and Q row; the
-        // next plane's claims fill the matrix-pipe time ----
-        f32x16 acc0 = ZERO16, acc1 = ZERO16;
-        if (EXACT) {
-            f32x4 a4[2][4];
-            float bq[16];
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int t4 = 0; t4 < 4; ++t4)
-                    a4[m][t4] = *reinterpret_cast<const f32x4*>(M + (32 * m + i) * MS + 16 * hi + 4 * t4);
-#pragma unroll
-            for (int t = 0; t < 16; ++t) bq[t] = Qs[(t + 16 * hi) * 33 + i];
-            M[(sc.w0 ? rc.h0 : 64) * MS + i] = 0.f;
-            M[(sc.w1 ? rc.h1 : 64) * MS + i] = 0.f;
-            if (pl < 2) prep(pl + 1, rn);
-#pragma unroll
-            for (int t = 0; t < 16; ++t) {
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[0][t >> 2][t & 3], bq[t], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[1][t >> 2][t & 3], bq[t], acc1, 0, 0, 0);
-            }
-        } else {
-            const half_t* Mh = reinterpret_cast<const half_t*>(M);
-            h8_t ah[2][2], al[2][2];  // [slot tile][k-step]: 8 samples 16 ks + 8 hi .. + 7 of slot row 32 m + i
-            float bs[2][8];           // the same samples of channel i
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) {
-                    const half_t* a = Mh + (32 * m + i) * M16_RS + 16 * ks + 8 * hi;
-                    ah[m][ks] = *reinterpret_cast<const h8_t*>(a);
-                    al[m][ks] = *reinterpret_cast<const h8_t*>(a + M16_PLANE);
-                }
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) bs[ks][j] = Qs[(16 * ks + 8 * hi + j) * 33 + i];
-            m_zero<false>(M, sc.w0 ? rc.h0 : 64, i);
-            m_zero<false>(M, sc.w1 ? rc.h1 : 64, i);
-            if (pl < 2) prep(pl + 1, rn);
-            // per-channel normalisation of the B operand to the top of the fp16 range (column = this lane and lane ^ 32)
-            float mx = 0.f;
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) mx = fmaxf(mx, __builtin_fabsf(bs[ks][j]));
-            mx = fmaxf(mx, __shfl_xor(mx, 32));
-            int E = (int)(__builtin_bit_cast(unsigned, mx) >> 23);
-            E = E < 16 ? 16 : (E > 240 ? 240 : E);
-            const float bsc = __builtin_bit_cast(float, (unsigned)(268 - E) << 23);
-            const float bun = __builtin_bit_cast(float, (unsigned)(E - 14) << 23);
-            h8_t bh[2], bl[2];
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float x0 = bs[ks][2 * j] * bsc, x1 = bs[ks][2 * j + 1] * bsc;
-                    h2_t ph, pq;
-                    split_pair(x0, x1, ph, pq);
-                    bh[ks][2 * j] = ph.x;
-                    bh[ks][2 * j + 1] = ph.y;
-                    bl[ks][2 * j] = pq.x;
-                    bl[ks][2 * j + 1] = pq.y;
-                }
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[0][ks], bh[ks], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[1][ks], bh[ks], acc1, 0, 0, 0);
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[0][ks], bl[ks], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[1][ks], bl[ks], acc1, 0, 0, 0);
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[0][ks], bh[ks], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[1][ks], bh[ks], acc1, 0, 0, 0);
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                acc0[r] *= bun;
-                acc1[r] *= bun;
-            }
-        }
-        TT_SUBPHASE(3);
-        if (pl < 2) sn = scatter_claim<EXACT>(rn, M, tags + 64 * ((pl + 1) & 1), dummy, i, st);
-        TT_SUBPHASE(4);
-        // ---- flush: one 128-byte atomic per slot pair, straight from the accumulators (slot of reg 4g+e = LIDX) ----
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const i32x4 k0 = *reinterpret_cast<const i32x4*>(tg + 8 * g + 4 * hi);
-            const i32x4 k1 = *reinterpret_cast<const i32x4*>(tg + 32 + 8 * g + 4 * hi);
-#pragma unroll
-            for (int e2 = 0; e2 < 4; ++e2) {
-                __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(acc0[4 * g + e2], grsrc,
-                                                                (int)(((unsigned)k0[e2] << 7) | lane_b), 0, 0);
-                __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(acc1[4 * g + e2], grsrc,
-                                                                (int)(((unsigned)k1[e2] << 7) | lane_b), 0, 0);
-            }
-        }
-        // ---- tags of this plane back to empty ----
-        *(sc.m0 ? tg + rc.h0 : dummy) = sc.m0 ? -1 : -2;
-        *(sc.m1 ? tg + rc.h1 : dummy) = sc.m1 ? -1 : -2;
-        if (pl < 2) {
-            scatter_lost(rn, sn.l0, sn.l1, Qs, Ls, grsrc, i, hi);
-            rc = rn;
-            sc = sn;
-        }
-        TT_SUBPHASE(5);
-    }
-}
-
-#else  // !TT_SCATTER_V1
-
 // =====================================================================================================================
-// Round 6: texel table -> DENSE ranks -> short flush, up to 128 distinct texels per plane-tile (two 64-row passes).
+// Texel table -> DENSE ranks -> short flush, up to 128 distinct texels per plane-tile (two 64-row passes).
 //
-// What rounds 2-5 did (TT_SCATTER_V1 above): slot = 8 x 8 torus hash of the texel, 64 slots, every plane flushes all 64
-// slots (32 atomic instructions, the empty ones dropped by the buffer range check), references that lose their slot go
-// out one by one.  Measured / simulated in round 6 (tools/scatter_sim.py, profiles/r06_scatter_*.txt): a plane-tile of the
-// headline scene holds 25-34 DISTINCT texels (half of the 32 flush instructions carry nothing), one of the reference's
-// sparse training renders 63-73 (up to 128) -- a hash window of 64 slots keeps ~44 of them and sends 28 % of the references
-// down the one-by-one path.  Now:
+// Measured / simulated (tools/scatter_sim.py, profiles/r06_scatter_*.txt): a plane-tile of the headline scene holds 25-34
+// DISTINCT texels, one of the reference's sparse training renders 63-73 (up to 128).  (Rounds 2-5 hashed straight into 64
+// rows and flushed all of them: profiles/experiments/README.md.)
 //   * claims go into a 16 x 16 torus table (256 entries; 4 % of the training shape's references collide there, 0.1 % of
-//     the headline's) -- one LDS CAS per reference as before;
+//     the headline's) -- one LDS CAS per reference;
 //   * the distinct texels are RANKED: the winner of an entry (exactly one reference per distinct texel) takes the next rank
 //     r < n (two ballots + mbcnt over the winner flags), copies the tag to ctag[r] and leaves r in the entry for the
 //     references that share the texel;
 //   * M row = rank.  Ranks 0..63 are combined and flushed by pass A, ranks 64..127 (n > 64: wave-uniform branch) by a
 //     second pass over the SAME 64-row M buffer and accumulators (32 samples x 4 corners = 128 references: n <= 128 always);
-//   * the flush issues 4 ceil(n / 8) atomic instructions instead of 32 (wave-uniform branches per group of 8 rows;
+//   * the flush issues 4 ceil(n / 8) atomic instructions, not 32 (wave-uniform branches per group of 8 rows;
 //     ctag[n .. n+7] = -1 keeps the tail of the last group out of range).
-// Tags need no double buffer any more: a plane's table entries go back to empty right after they were ranked (DS
+// The table needs no double buffer: a plane's entries go back to empty right after they were ranked (DS
 // operations of a wave execute in order), only the compacted tags (read by the flush after the next plane's claims) alternate.
 // LDS per wave (ints, behind the lost-reference lists at Ls + 256; all inside the kernels' existing scratch):
 //   htab[256] | ctag[2][136] | cdump[64]          dummies: tags[0..31] (scatter_init_tags)
-#ifndef TT_SC2_NO_PASSB
-#define TT_SC2_NO_PASSB 0
-#endif
-#ifndef TT_SC2_FLUSH_ALL
-#define TT_SC2_FLUSH_ALL 0
-#endif
 #define SC2_HT 256
 #define SC2_CT 136
 #define SC2_INTS (SC2_HT + 2 * SC2_CT + 64)
@@ -827,7 +595,7 @@ __device__ __forceinline__ void sc2_flush(const f32x16& acc0, const f32x16& acc1
                                           __amdgpu_buffer_rsrc_t grsrc, unsigned lane_b, int hi) {
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-        if (TT_SC2_FLUSH_ALL || n > 8 * g) {
+        if (n > 8 * g) {
             const i32x4 k0 = *reinterpret_cast<const i32x4*>(ct + 8 * g + 4 * hi);
 #pragma unroll
             for (int e2 = 0; e2 < 4; ++e2)
@@ -837,7 +605,7 @@ __device__ __forceinline__ void sc2_flush(const f32x16& acc0, const f32x16& acc1
     }
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-        if (TT_SC2_FLUSH_ALL || n > 32 + 8 * g) {
+        if (n > 32 + 8 * g) {
             const i32x4 k1 = *reinterpret_cast<const i32x4*>(ct + 32 + 8 * g + 4 * hi);
 #pragma unroll
             for (int e2 = 0; e2 < 4; ++e2)
@@ -881,8 +649,6 @@ __device__ __forceinline__ void scatter_planes(float* __restrict__ grad, unsigne
             __builtin_amdgcn_sched_barrier(0);                            \
         }                                                                 \
     } while (0)
-#elif defined(TT_SC2_FENCE)
-#define TT_SUBPHASE(k) __builtin_amdgcn_sched_barrier(0)
 #else
 #define TT_SUBPHASE(k) \
     do {               \
@@ -903,7 +669,7 @@ __device__ __forceinline__ void scatter_planes(float* __restrict__ grad, unsigne
     for (int pl = 0; pl < 3; ++pl) {
         const int* const ct = ctag + SC2_CT * (pl & 1);
         int* const ct_next = ctag + SC2_CT * ((pl + 1) & 1);
-        const bool pass_b = TT_SC2_NO_PASSB ? false : sc.n > 64;  // wave-uniform
+        const bool pass_b = sc.n > 64;  // wave-uniform
         f32x16 acc0, acc1;
         AOp A;
         BOp B;
@@ -943,7 +709,6 @@ __device__ __forceinline__ void scatter_planes(float* __restrict__ grad, unsigne
         TT_SUBPHASE(5);
     }
 }
-#endif  // TT_SCATTER_V1
 
 struct MlpGradPtrs {
     float* w1;
@@ -981,17 +746,13 @@ struct BwdTexParams {
 #define TV2 (OFF_V2 - OFF_V1)
 #define TV3 (OFF_V3 - OFF_V1)
 // V1, V2 as split-fp16 images (tt_mfma16.h): every mat-vec product of the kernel runs on the fp16 pipe.  The V2^T / V1^T
-// products either read the same images through ds_read_b64_tr_b16 (mv16t: the wave-pair kernel, where LDS is what limits
-// the pairs per CU) or use transposed COPIES (TT_BWD_WT_COPIES, the one-wave kernels' default: 43 KB more LDS that nothing
-// else wants at one wave per SIMD, and plain ds_read_b128 fragments: texture backward 2.94 -> 2.85 ms, bit-identical).
+// products use transposed COPIES of the images (43 KB more LDS that nothing else wants at one wave per SIMD) and plain
+// ds_read_b128 fragments instead of ds_read_b64_tr_b16 reads of the forward images.
 // The per-wave scratch is 128 rows: the parked e (96 rows) shares it with a 32-row window through which k2 (for dV3)
 // and k1bar (for dV1) are transposed in two halves.
-#ifndef TT_BWD_WT_COPIES
-#define TT_BWD_WT_COPIES 1
-#endif
 #define TV1T TEX_W_FLOATS
 #define TV2T (TV1T + IMG16_FLOATS(96, 64))
-#define TEX_W16_FLOATS (TT_BWD_WT_COPIES ? TV2T + IMG16_FLOATS(64, 64) : TEX_W_FLOATS)
+#define TEX_W16_FLOATS (TV2T + IMG16_FLOATS(64, 64))
 // PREC_S3 (three-piece products): the images of the third terms follow V3, and there are NO transposed copies -- with them
 // the kernel would need 204 KB of LDS -- so the V2^T / V1^T products read the forward images through ds_read_b64_tr_b16
 // (mv16t, as the forward kernels do): 66 KB of images + 76 KB of per-wave scratch = 143 KB.
@@ -1121,9 +882,8 @@ static inline void launch_planes_bound(const float* packed, const tt_render_cfg&
                        (unsigned*)nullptr);
 }
 
-// outer products on the fp16 pipe: both split modes (the fp32 MFMA mode and the tuning build's TT_R_WGRAD_F32 A/B kernel
-// use fp32 outer products)
-static inline bool use_wg16(const tt_render_cfg& cfg) { return !(cfg.flags & (TT_R_EXACT_F32 | TT_R_WGRAD_F32)); }
+// outer products on the fp16 pipe: both split modes (the fp32 MFMA mode uses fp32 outer products)
+static inline bool use_wg16(const tt_render_cfg& cfg) { return !(cfg.flags & TT_R_EXACT_F32); }
 
 static inline int points_cfg(tt_render_cfg* c, int32_t n_batch, int64_t n_points, int32_t n_prompts,
                       int32_t views_per_prompt, int32_t plane_h, int32_t plane_w, float radius, float sdf_bias_radius,

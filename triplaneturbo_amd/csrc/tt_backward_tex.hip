@@ -1,9 +1,6 @@
 // tt_backward_tex.hip -- texture half of the fused render backward: feature net backward, dV1 / dV2 / dV3, scatter of
 // d/d planes 3..5 (k_decode_bwd_tex), and the per-point variant tt_points_bwd_tex.  See tt_backward.hip for the overview.
 #include "tt_backward_common.h"
-#ifndef TT_TEX_REREAD_RAY
-#define TT_TEX_REREAD_RAY 1
-#endif
 
 // =====================================================================================================
 // texture half
@@ -14,7 +11,7 @@
 template <int PREC, bool WG16, bool STATS = false>
 __global__ __launch_bounds__(256, 1) void k_decode_bwd_tex(BwdTexParams p) {
     constexpr bool EXACT = PREC == PREC_F32;
-    constexpr bool COPIES = TT_BWD_WT_COPIES && PREC != PREC_S3;  // transposed weight copies (tt_backward_common.h)
+    constexpr bool COPIES = PREC != PREC_S3;  // transposed weight copies (tt_backward_common.h)
     constexpr int NT = PrecNT<PREC>::value, WF = TexWFloats<PREC>::value;
     __shared__ __attribute__((aligned(16))) float Lt[WF + 4 * (TEX_SCRATCH_FLOATS + SCATTER_TAG_INTS)];
     {
@@ -105,19 +102,6 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_tex(BwdTexParams p) {
       const int ks = i % tg.sb;  // this lane's sample offset inside a tile step
       const int view = (int)(ray / cfg.rays_per_view);
       const size_t pofs = (size_t)(view / cfg.views_per_prompt) * plane_stride;
-#if TT_TEX_REREAD_RAY
-      // Per-ray constants (origin, direction, d loss / d rgb) are RE-READ at the top of every tile step instead of living in
-      // nine registers across the item: the same addresses for every step of an item (L1 hits, ~0.5 % of a step), and the
-      // registers the allocator would otherwise spill to scratch memory (4 in the default mode, 68 in the fp32-MFMA mode).
-      // The ray index is laundered through an empty asm so that hipcc cannot hoist the loads back out of the loop.
-#else
-      const float ox = p.rays_o[ray * 3 + 0], oy = p.rays_o[ray * 3 + 1], oz = p.rays_o[ray * 3 + 2];
-      const float dx = p.rays_d ? p.rays_d[ray * 3 + 0] : 0.f, dy = p.rays_d ? p.rays_d[ray * 3 + 1] : 0.f,
-                  dz = p.rays_d ? p.rays_d[ray * 3 + 2] : 0.f;
-      float grgb[3];
-#pragma unroll
-      for (int o = 0; o < 3; ++o) grgb[o] = p.g_rgb ? p.g_rgb[ray * 3 + o] : 0.f;
-#endif
       const int s_end = (ck + 1) * tg.chunk < S ? (ck + 1) * tg.chunk : S;
       TT_PHASE(19);
       // Per-step inputs (weight, features, interval, upstream) are PREFETCHED one tile step ahead: their loads are
@@ -148,7 +132,10 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_tex(BwdTexParams p) {
         const int si = sb0 + ks;
         const bool valid = ray_ok && si < s_end;
         const float vf = ray_okf * (si < s_end ? 1.f : 0.f);
-#if TT_TEX_REREAD_RAY
+        // Per-ray constants (origin, direction, d loss / d rgb) are RE-READ at the top of every tile step instead of living in
+        // nine registers across the item: the same addresses for every step of an item (L1 hits, ~0.5 % of a step), and the
+        // registers the allocator would otherwise spill to scratch memory (4 in the default mode, 68 in the fp32-MFMA mode).
+        // The ray index is laundered through an empty asm so that hipcc cannot hoist the loads back out of the loop.
         long long rr = ray;
         asm volatile("" : "+v"(rr));
         const float ox = p.rays_o[rr * 3 + 0], oy = p.rays_o[rr * 3 + 1], oz = p.rays_o[rr * 3 + 2];
@@ -157,7 +144,6 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_tex(BwdTexParams p) {
         float grgb[3];
 #pragma unroll
         for (int o = 0; o < 3; ++o) grgb[o] = p.g_rgb ? p.g_rgb[rr * 3 + o] : 0.f;
-#endif
         // ---- upstream: cbar_o = shrink * w_i * g_rgb[ray,o] * 1.002 * s(1-s) + g_features ----
         float cb[3];
 #pragma unroll
@@ -312,10 +298,9 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_tex(BwdTexParams p) {
         if (region && !TT_DBG(cfg.flags, TT_DBG_NO_SCATTER)) {
             // the combine GEMM on the fp16 pipe as in the geometry kernel (round 2 measured +26 spilled registers and
             // 3.88 -> 4.16 ms for this; with the outer products on the fp16 pipe it fits: 3.65 -> 3.37 ms)
-            constexpr bool SC_EXACT = EXACT || !WG16;  // (the TT_R_WGRAD_F32 A/B variant = the round-2 kernel)
             float* M = Xs;              // rows 0..63: the slot x sample coefficient matrix (fp32), row 64: dump row
-            float* Es = Xs + (SC_EXACT ? 65 * XS : SCATTER_M_FLOATS);  // ebar rows [sample][32], stride 33; fallback lists
-            scatter_clear<SC_EXACT>(M, lane);
+            float* Es = Xs + (EXACT ? 65 * XS : SCATTER_M_FLOATS);  // ebar rows [sample][32], stride 33; fallback lists
+            scatter_clear<EXACT>(M, lane);
             // ebar = V1^T k1bar for the three planes in ONE product (96 rows: k1bar is split into fp16 terms once)
             float eb[48];
             if constexpr (COPIES)
@@ -324,14 +309,14 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_tex(BwdTexParams p) {
                 mvtx<PREC, 96, 64, 96>(Lt + TV1, Lt + TLO_V1, 0, kb1, eb, i, hi);
             TT_PHASE(9);
             const int tex0 = (int)(pofs / TT_C);
-            scatter_planes<SC_EXACT>(grad_out, grad_bytes, Es, M, tags, Es + 32 * 33, i, hi, [&](int pl, PlaneRefs& refs) {
+            scatter_planes<EXACT>(grad_out, grad_bytes, Es, M, tags, Es + 32 * 33, i, hi, [&](int pl, PlaneRefs& refs) {
                 Corners c;
                 corners_setup(PLANE_U(pl, X, Y, Z), PLANE_V(pl, X, Y, Z), H, W, valid, c);
                 int aoff[4];
 #pragma unroll
                 for (int q4 = 0; q4 < 4; ++q4)  // absolute texel index, prompt included
                     aoff[q4] = tex0 + (int)((3 + pl) * HW) + c.off[q4];
-                refs = plane_refs<!SC_EXACT>(c.w, aoff, c.hs, hi);
+                refs = plane_refs<!EXACT>(c.w, aoff, c.hs, hi);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) Es[i * 33 + LIDX(r, hi)] = eb[16 * pl + r] * refs.qs;
             }
@@ -407,14 +392,9 @@ static void launch_bwd_tex(const BwdTexParams& p0, long long blocks, hipStream_t
             LAUNCH_TEX(PREC_S3, true);
         else
             LAUNCH_TEX(PREC_S2, true);
-    } else if (prec == PREC_F32) {
+    } else {  // TT_R_EXACT_F32
         LAUNCH_TEX(PREC_F32, false);
     }
-#ifdef TT_TUNING
-    else {  // TT_R_WGRAD_F32: the round-2 A/B kernel
-        LAUNCH_TEX(PREC_S2, false);
-    }
-#endif
 #undef LAUNCH_TEX
 }
 

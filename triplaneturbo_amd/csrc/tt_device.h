@@ -382,14 +382,12 @@ struct TileStats {
 enum { TT_STAT_VISITED = 0, TT_STAT_EXECUTED = 1, TT_STAT_INBOUNDS = 2 };
 __device__ __forceinline__ TileStats tile_stats(uint64_t* stats64) {
     TileStats st = {nullptr, nullptr};
-#ifndef TT_NO_STATS  // (dev A/B only, tools/build_variants.py: what the counting costs)
     __shared__ unsigned tt_stat_slots[16 * 4];  // <= 16 waves per workgroup
     st.p = reinterpret_cast<unsigned long long*>(stats64);
     if (st.p) {
         st.w = tt_stat_slots + 4 * __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
         if ((threadIdx.x & 63) < 4) st.w[threadIdx.x & 63] = 0u;
     }
-#endif
     return st;
 }
 // wave-uniform `v`; one lane counts

@@ -1,7 +1,4 @@
 // tt_forward.hip -- plane pack/unpack, per-point decode (tt_query_points) and the fused forward render.
-#ifndef TT_FWD_PREFETCH
-#define TT_FWD_PREFETCH 1  // next tile step's interval loaded one step ahead: forward 1.676 -> 1.666 ms (A/B/A/B, one box)
-#endif
 #ifndef TT_MV16_FENCE
 #define TT_MV16_FENCE 1  // scheduling fence in front of every product's MFMA loop: see tt_mfma16.h
 #endif
@@ -272,40 +269,17 @@ __device__ __forceinline__ void stage_decode_images(float* L, const MlpPtrs& w) 
     }
 }
 
-#ifndef TT_DR_GEO_SAMPLES
-#define TT_DR_GEO_SAMPLES 64  // samples of a ray block per work item of the sdf-only decode (tt_decode_rays)
-#endif
-#ifndef TT_DR_GEO_MIN_ITEMS
+#define TT_DR_GEO_SAMPLES 64   // samples of a ray block per work item of the sdf-only decode (tt_decode_rays)
 #define TT_DR_GEO_MIN_ITEMS 0  // ... and no minimum number of items per wave slot
-#endif
 // 8 waves (2 per SIMD) share one set of split-fp16 weight images (93 KB: one workgroup per CU)
-#ifndef DECODE_THREADS
 #define DECODE_THREADS 512
-#endif
 
-// Staggered wave priority (dev A/B, TT_PRIO_MODE; 0 = off): the two waves of a SIMD run the same phases (gather -> products -> ...)
-// and, arbitrated evenly, tend to stay in step -- both in their matrix phase, then both in their VALU phase -- so the pipes
-// alternate instead of overlapping.  A STATIC higher priority for one wave of each pair lets it run as if alone while the other
-// fills the slots it leaves.  Mode 1: waves 4..7 of the 8-wave workgroup (wave w sits on SIMD w % 4); mode 2: odd waves.
-#ifndef TT_PRIO_MODE
-#define TT_PRIO_MODE 0
-#endif
-__device__ __forceinline__ void tt_stagger_priority() {
-#if TT_PRIO_MODE == 1
-    if (threadIdx.x >= 256) __builtin_amdgcn_s_setprio(3);
-#elif TT_PRIO_MODE == 2
-    if ((threadIdx.x >> 6) & 1) __builtin_amdgcn_s_setprio(3);
-#elif TT_PRIO_MODE == 3
-    if (threadIdx.x >= 256) __builtin_amdgcn_s_setprio(1);
-#endif
-}
 template <bool NEED_N, bool NEED_TEX, int PREC>
 __global__ __launch_bounds__(DECODE_THREADS) void k_query_points(QueryParams p) {
     __shared__ __attribute__((aligned(16))) float L[FwdWFloats<PREC>::value + (DECODE_THREADS / 64) * GC_SCRATCH_FLOATS];
     float* T = L + FwdWFloats<PREC>::value + (threadIdx.x >> 6) * GC_SCRATCH_FLOATS;
     stage_decode_images<NEED_N, NEED_TEX, PREC>(L, p.w);
     __syncthreads();
-    tt_stagger_priority();
     const int lane = threadIdx.x & 63, i = lane & 31, hi = lane >> 5;
     const long long tiles_per_batch = (p.n_points + TT_TILE - 1) / TT_TILE;
     const long long n_tiles = tiles_per_batch * p.n_batch;
@@ -385,11 +359,7 @@ struct QueryFieldParams {
 // one 4-wave workgroup per CU until the kernel-resource table showed its occupancy of 1.)
 template <int PREC>
 struct QueryFieldWaves {
-#ifdef TT_QF_WAVES4  // dev A/B: the one-workgroup-of-four form of PREC_S3
-    static constexpr int value = 4;
-#else
     static constexpr int value = PREC == PREC_S3 ? 8 : 4;
-#endif
 };
 template <int PREC>
 __global__ __launch_bounds__(64 * QueryFieldWaves<PREC>::value, PREC == PREC_S3 ? 1 : 2) void k_query_field(QueryFieldParams p) {
@@ -405,7 +375,6 @@ __global__ __launch_bounds__(64 * QueryFieldWaves<PREC>::value, PREC == PREC_S3 
         lds_load_matrix(L + OFF_D3, w.v3, 3, 64, 64);
     }
     __syncthreads();
-    tt_stagger_priority();
     const int lane = threadIdx.x & 63, i = lane & 31, hi = lane >> 5;
     const long long tiles_per_batch = (p.n_points + TT_TILE - 1) / TT_TILE;
     const long long n_tiles = tiles_per_batch * p.n_batch;
@@ -455,9 +424,6 @@ __global__ __launch_bounds__(64 * QueryFieldWaves<PREC>::value, PREC == PREC_S3 
 }
 
 // =====================================================================================================
-#ifndef TT_FWD_REREAD_RAY
-#define TT_FWD_REREAD_RAY 0
-#endif
 // K1: decode every sample of every ray (tiles of 32 adjacent rays x one sample index, chunks of CH indices)
 // =====================================================================================================
 struct DecodeRaysParams {
@@ -482,7 +448,6 @@ __global__ __launch_bounds__(DECODE_THREADS) void k_decode_rays(DecodeRaysParams
     float* T = L + FwdWFloats<PREC>::value + (threadIdx.x >> 6) * GC_SCRATCH_FLOATS;
     stage_decode_images<NEED_N, NEED_TEX, PREC>(L, p.w);
     __syncthreads();
-    tt_stagger_priority();
     const tt_render_cfg& cfg = p.cfg;
     const TileGeom& tg = p.geom;
     const int lane = threadIdx.x & 63, i = lane & 31, hi = lane >> 5;
@@ -513,12 +478,9 @@ __global__ __launch_bounds__(DECODE_THREADS) void k_decode_rays(DecodeRaysParams
         dc.ju = 0.5f * cfg.plane_w / cfg.radius;
         dc.jv = 0.5f * cfg.plane_h / cfg.radius;
         dc.dbg = cfg.flags;
-#if !TT_FWD_REREAD_RAY
         const float ox = p.rays_o[ray * 3 + 0], oy = p.rays_o[ray * 3 + 1], oz = p.rays_o[ray * 3 + 2];
         const float dx = p.rays_d[ray * 3 + 0], dy = p.rays_d[ray * 3 + 1], dz = p.rays_d[ray * 3 + 2];
-#endif
         const int s_end = (ck + 1) * tg.chunk < S ? (ck + 1) * tg.chunk : S;
-#if TT_FWD_PREFETCH
         // the sample interval of the NEXT tile step is loaded one step ahead (a step past the chunk reads a clamped, valid
         // address), as the backward kernels do
         auto load_t = [&](int sb0_, float& ts_, float& te_) {
@@ -529,7 +491,6 @@ __global__ __launch_bounds__(DECODE_THREADS) void k_decode_rays(DecodeRaysParams
         };
         float ts_n, te_n;
         load_t(ck * tg.chunk, ts_n, te_n);
-#endif
 #pragma nounroll
         for (int sb0 = ck * tg.chunk; sb0 < s_end; sb0 += tg.sb) {
             const int si = sb0 + ks;
@@ -538,24 +499,10 @@ __global__ __launch_bounds__(DECODE_THREADS) void k_decode_rays(DecodeRaysParams
             const bool rvalid = ray_okf * (si < s_end ? 1.f : 0.f) != 0.f;
             tile_stat(st, TT_STAT_VISITED);
             const long long sidx = ray * S + (si < S ? si : S - 1);
-#if TT_FWD_PREFETCH
             const float ts = ts_n, te = te_n;
             load_t(sb0 + tg.sb, ts_n, te_n);
-#else
-            const float ts = p.t_starts[sidx], te = p.t_ends[sidx];
-#endif
             float tm, px, py, pz;
-#if TT_FWD_REREAD_RAY
-            // (dev A/B, off by default: the ray re-read per tile step and the position rebuilt after the decode)
-            {
-                long long rr = ray;
-                asm volatile("" : "+v"(rr));
-                sample_position(p.rays_o[rr * 3 + 0], p.rays_o[rr * 3 + 1], p.rays_o[rr * 3 + 2], p.rays_d[rr * 3 + 0],
-                                p.rays_d[rr * 3 + 1], p.rays_d[rr * 3 + 2], ts, te, tm, px, py, pz);
-            }
-#else
             sample_position(ox, oy, oz, dx, dy, dz, ts, te, tm, px, py, pz);
-#endif
             float s0, gq[3], c[3];
             decode_fwd<NEED_N, NEED_TEX, PREC>(L, dc, px, py, pz, rvalid, i, hi, s0, gq, c);
             float nrm;
@@ -615,7 +562,6 @@ __global__ __launch_bounds__(DECODE_THREADS) void k_render_eval(RenderEvalParams
     float* T = L + FwdWFloats<PREC>::value + (threadIdx.x >> 6) * GC_SCRATCH_FLOATS;
     stage_decode_images<true, true, PREC>(L, p.w);
     __syncthreads();
-    tt_stagger_priority();
     const tt_render_cfg& cfg = p.cfg;
     const TileGeom& tg = p.geom;
     const int lane = threadIdx.x & 63, i = lane & 31, hi = lane >> 5;
@@ -877,10 +823,8 @@ int tt_validate_cfg(const tt_render_cfg* cfg) {
         const int pbits = cfg->flags & (TT_R_EXACT_F32 | TT_R_SPLIT2 | TT_R_SPLIT3);
         if (pbits & (pbits - 1)) return TT_ERR_BAD_ARG;
     }
-    if (cfg->flags & TT_R_BWD_PAIR) return TT_ERR_UNSUPPORTED;  // reserved (the wave-pair kernel left the tree in round 6)
-#ifndef TT_TUNING
-    if (cfg->flags & TT_R_WGRAD_F32) return TT_ERR_UNSUPPORTED;  // dev A/B kernel: tuning build only
-#endif
+    // reserved (the wave-pair kernel and the fp32-outer-product kernels of rounds 2-4 left the tree)
+    if (cfg->flags & (TT_R_BWD_PAIR | TT_R_WGRAD_F32)) return TT_ERR_UNSUPPORTED;
     if (!(cfg->skip_eps_tex >= 0.f) || !(cfg->skip_eps_geo >= 0.f)) return TT_ERR_BAD_ARG;
     return TT_OK;
 }

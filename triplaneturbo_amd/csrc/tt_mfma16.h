@@ -54,79 +54,26 @@ typedef float f2_t __attribute__((ext_vector_type(2)));
 // round-toward-zero v_cvt_pkrtz_f16_f32 it replaces since round 4).  With RNE |v - hi| <= 2^-11 |v| and lo = f16(v - hi)
 // is again correctly rounded, so hi + lo carries ~24 significand bits instead of the ~22 of the truncating split
 // (tools/mfma16_probe.hip measures both).  Nothing can overflow: operands are normalised below 2^15 < 65504.
-#ifndef TT_SPLIT_MODE
-// dev A/B (tools/build_variants.py), measured on one box, ms per bench step (forward / geometry / texture backward):
-//   1 RTZ (rounds 1-3) 7.77 (1.70 / 2.88 / 2.86)   0 RNE through __builtin_convertvector 8.01 (1.85 / 2.90 / 2.92): hipcc
-//   re-schedules around the fptrunc (+6 spilled registers in k_decode_rays)   4 RNE, the SAME instruction as inline asm
-//   7.81 (1.70 / 2.88 / 2.89), bit-identical results to 0   2 hi RNE / lo RTZ 7.89   3 bias + RTZ 8.23   5 lo only asm 7.85
-#define TT_SPLIT_MODE 4
-#endif
-__device__ __forceinline__ h2_t cvt_pk16_rne(float a, float b) {
-    const f2_t v = {a, b};
-    return __builtin_convertvector(v, h2_t);
-}
-__device__ __forceinline__ h2_t cvt_pk16_rtz(float a, float b) {
-    return __builtin_bit_cast(h2_t, __builtin_amdgcn_cvt_pkrtz(a, b));
-}
-// round to nearest (ties away from zero) on the truncating instruction: half an fp16 ulp (bit 12 of the fp32 pattern)
-// added to the magnitude first
-__device__ __forceinline__ h2_t cvt_pk16_bias(float a, float b) {
-    return cvt_pk16_rtz(__builtin_bit_cast(float, __builtin_bit_cast(unsigned, a) + 0x1000u),
-                        __builtin_bit_cast(float, __builtin_bit_cast(unsigned, b) + 0x1000u));
-}
-__device__ __forceinline__ h2_t cvt_pk16_asm(float a, float b) {  // the same instruction, opaque to the optimiser
+// Written as inline asm: through __builtin_convertvector hipcc re-schedules around the fptrunc and spills in k_decode_rays
+// (profiles/experiments/README.md, round 4).
+__device__ __forceinline__ h2_t cvt_pk16(float a, float b) {
     unsigned r;
     asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return __builtin_bit_cast(h2_t, r);
 }
-// hi term of a split
-__device__ __forceinline__ h2_t cvt_pk16(float a, float b) {
-#if TT_SPLIT_MODE == 4
-    return cvt_pk16_asm(a, b);
-#elif TT_SPLIT_MODE == 1
-    return cvt_pk16_rtz(a, b);
-#elif TT_SPLIT_MODE == 3
-    return cvt_pk16_bias(a, b);
-#else
-    return cvt_pk16_rne(a, b);
-#endif
-}
-// lo term (the residual) of a split
-__device__ __forceinline__ h2_t cvt_pk16_lo(float a, float b) {
-#if TT_SPLIT_MODE == 4 || TT_SPLIT_MODE == 5
-    return cvt_pk16_asm(a, b);
-#elif TT_SPLIT_MODE == 1 || TT_SPLIT_MODE == 2
-    return cvt_pk16_rtz(a, b);
-#elif TT_SPLIT_MODE == 3
-    return cvt_pk16_bias(a, b);
-#else
-    return cvt_pk16_rne(a, b);
-#endif
-}
-__device__ __forceinline__ unsigned cvt_pk16u(float a, float b) { return __builtin_bit_cast(unsigned, cvt_pk16(a, b)); }
-__device__ __forceinline__ unsigned cvt_pk16u_lo(float a, float b) { return __builtin_bit_cast(unsigned, cvt_pk16_lo(a, b)); }
 
 // The split of a PAIR of values: hi = pk_f16(a, b), lo = pk_f16(a - hi.x, b - hi.y) (both residuals exact).
-// TT_SPLIT_PAIR_ASM: one asm block of FOUR instructions -- convert, two v_fma_mix_f32 that subtract the f16 halves of hi
+// One asm block of FOUR instructions -- convert, two v_fma_mix_f32 that subtract the f16 halves of hi
 // straight from the fp32 inputs (a * 1.0 - hi: exact), convert -- where hipcc emits six (convert, v_cvt_f32_f16, subtract,
 // v_cvt_f32_f16_sdwa, subtract, convert).  It also removes the wait states hipcc puts around a lone inline-asm convert
 // (it assumes a dst_sel forwarding hazard for every asm result: +95 s_nop per tile step of the texture backward, which is
-// what the single-instruction asm form of round 4 cost against the truncating builtin).  Bit-identical to the generic form.
-#ifndef TT_SPLIT_PAIR_ASM
-#define TT_SPLIT_PAIR_ASM (TT_SPLIT_MODE == 4)
-#endif
+// what the single-instruction asm form of round 4 cost against the truncating builtin).
 __device__ __forceinline__ void split_pair(float a, float b, unsigned& hi, unsigned& lo) {
-#if TT_SPLIT_PAIR_ASM
     asm("v_cvt_pk_f16_f32 %0, %2, %3\n\t"
         "v_fma_mix_f32 %2, %2, 1.0, -%0 op_sel_hi:[0,0,1]\n\t"
         "v_fma_mix_f32 %3, %3, 1.0, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
         "v_cvt_pk_f16_f32 %1, %2, %3"
         : "=&v"(hi), "=v"(lo), "+v"(a), "+v"(b));
-#else
-    const h2_t p = cvt_pk16(a, b);
-    hi = __builtin_bit_cast(unsigned, p);
-    lo = cvt_pk16u_lo(a - (float)p.x, b - (float)p.y);
-#endif
 }
 __device__ __forceinline__ void split_pair(float a, float b, h2_t& hi, h2_t& lo) {
     unsigned h, l;
@@ -138,7 +85,6 @@ __device__ __forceinline__ void split_pair(float a, float b, h2_t& hi, h2_t& lo)
 // The EXACT three-piece split of a pair (NT = 3): hi, mid as above, lo = pk_f16(a - hi - mid) -- seven instructions in one
 // block (convert, two exact fma_mix residuals, convert, two more residuals, convert).
 __device__ __forceinline__ void split_pair3(float a, float b, unsigned& hi, unsigned& mid, unsigned& lo) {
-#if TT_SPLIT_PAIR_ASM
     asm("v_cvt_pk_f16_f32 %0, %3, %4\n\t"
         "v_fma_mix_f32 %3, %3, 1.0, -%0 op_sel_hi:[0,0,1]\n\t"
         "v_fma_mix_f32 %4, %4, 1.0, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
@@ -147,14 +93,6 @@ __device__ __forceinline__ void split_pair3(float a, float b, unsigned& hi, unsi
         "v_fma_mix_f32 %4, %4, 1.0, -%1 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
         "v_cvt_pk_f16_f32 %2, %3, %4"
         : "=&v"(hi), "=&v"(mid), "=&v"(lo), "+v"(a), "+v"(b));
-#else
-    const h2_t p = cvt_pk16(a, b);
-    hi = __builtin_bit_cast(unsigned, p);
-    const float ra = a - (float)p.x, rb = b - (float)p.y;
-    const h2_t q = cvt_pk16_lo(ra, rb);
-    mid = __builtin_bit_cast(unsigned, q);
-    lo = cvt_pk16u_lo(ra - (float)q.x, rb - (float)q.y);
-#endif
 }
 __device__ __forceinline__ void split_pair3(float a, float b, h2_t& hi, h2_t& mid, h2_t& lo) {
     unsigned h, m, l;
@@ -167,12 +105,12 @@ __device__ __forceinline__ void split_pair3(float a, float b, h2_t& hi, h2_t& mi
 __device__ __forceinline__ void split16(float v, half_t& hi, half_t& lo) {
     const h2_t p = cvt_pk16(v, 0.f);
     hi = p.x;
-    const h2_t q = cvt_pk16_lo(v - (float)hi, 0.f);  // may be subnormal
+    const h2_t q = cvt_pk16(v - (float)hi, 0.f);  // may be subnormal
     lo = q.x;
 }
 __device__ __forceinline__ void split16_3(float v, half_t& hi, half_t& mid, half_t& lo) {
     split16(v, hi, mid);
-    const h2_t q = cvt_pk16_lo((v - (float)hi) - (float)mid, 0.f);  // both residuals exact in fp32
+    const h2_t q = cvt_pk16((v - (float)hi) - (float)mid, 0.f);  // both residuals exact in fp32
     lo = q.x;
 }
 
@@ -534,44 +472,6 @@ __device__ __forceinline__ void mv16t(const float* img_f, int col0, const float 
     for (int m = 0; m < MT; ++m)
 #pragma unroll
         for (int k = 0; k < 16; ++k) y[16 * m + k] = RAW ? acc[m][k] : acc[m][k] * un;
-}
-// the same on an operand already split in PAIR_TR order (x = (hi + lo) * un_x)
-template <int NOUT, int NIN, int KM, int NT = 2>
-__device__ __forceinline__ void mv16t_pre(const float* img_f, int col0, const Split16<NIN, PAIR_TR, NT>& x, float un_x,
-                                          float (&y)[NOUT / 2], int lane, const float* lo_f = nullptr) {
-    constexpr int MT = NOUT / 32, KS = NIN / 16;
-    const lds_sv4_t* base = tr_lane_base<KM>(img_f, col0, lane);
-    const lds_sv4_t* base_lo[MT];
-    if constexpr (NT == 3) {
-#pragma unroll
-        for (int m = 0; m < MT; ++m) base_lo[m] = tr_lane_base_lo<KM>(lo_f, col0, m, lane);
-    }
-    const float un = img_f[KM] * un_x;
-    f32x16 acc[MT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-        acc[m] = f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    typedef unsigned u4_t __attribute__((ext_vector_type(4)));
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-        const h8_t bh = __builtin_bit_cast(h8_t, u4_t{x.h[4 * s], x.h[4 * s + 1], x.h[4 * s + 2], x.h[4 * s + 3]});
-        const h8_t bl = __builtin_bit_cast(h8_t, u4_t{x.l[4 * s], x.l[4 * s + 1], x.l[4 * s + 2], x.l[4 * s + 3]});
-        h8_t bt;
-        if constexpr (NT == 3)
-            bt = __builtin_bit_cast(h8_t, u4_t{x.t[4 * s], x.t[4 * s + 1], x.t[4 * s + 2], x.t[4 * s + 3]});
-        h8_t ah[MT], al[MT], at[MT];
-#pragma unroll
-        for (int m = 0; m < MT; ++m) {
-            ah[m] = tr_frag<KM>(base, s, m, 0);
-            al[m] = tr_frag<KM>(base, s, m, 1);
-            if constexpr (NT == 3) at[m] = tr_frag_lo<KM>(base_lo[m], s);
-        }
-        mfma_terms<MT, NT>(acc, ah, al, at, bh, bl, bt);
-    }
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int k = 0; k < 16; ++k) y[16 * m + k] = acc[m][k] * un;
 }
 
 // ---- precision switch ----------------------------------------------------------------------------------------------

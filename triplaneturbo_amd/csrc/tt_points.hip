@@ -59,11 +59,7 @@ __device__ __forceinline__ float dot16_pair(const f32x4 (&t)[4], const float* v)
 // registers each), four in the fp32-MFMA mode (282 registers).
 template <int PREC>
 struct PointsBwdXWaves {
-#ifdef TT_PX_WAVES4  // dev A/B: four waves in every mode (rounds 3-4)
-    static constexpr int value = 4;
-#else
     static constexpr int value = PREC == PREC_F32 ? 4 : 8;
-#endif
 };
 // The masked vectors a2 / k2 are built from f32x4 LDS loads, so hipcc carries them as <4 x float> values; the transposed
 // products then take the register PAIRS (0,2), (1,3) of each group (PAIR_TR, tt_mfma16.h) and the compiler lowers that
