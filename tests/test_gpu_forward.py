@@ -7,7 +7,7 @@ import torch
 
 from oracle import cpu_ref as O
 
-from parity import PRECISIONS  # noqa: E402
+from parity import PRECISIONS, check_grads, check_outputs  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -209,3 +209,124 @@ def test_launch_helper_status_timer_labels_and_ray_checks(ops):
     rays[0] = torch.zeros(17, 3, device="cuda")  # n_rays + 1 origins
     with pytest.raises(ValueError, match="ray / interval shapes disagree"):
         ops.decode_rays(packed, sw, None, *rays, rays_per_view=16, rc=ops.RenderConfig())
+
+
+# ---- the shapes at which the shared launch planning of the decode entry points can go wrong ---------------------------
+_PLANNER = {}
+
+
+def _planner_case():
+    """Inputs and fp32 / fp64 oracle results, computed once for the three precision modes.
+    Per-point entries: 2 prompts x 1 view, 8 x 8 planes, 33 points -- two tiles per batch, the second with ONE live lane,
+    four tiles in all: fewer than a workgroup has waves.  Ray entries: 1 prompt x 1 view, 40 rays with no image width,
+    3 samples -- two 16-ray blocks at the default sb = 2 and a ragged third, a half-empty second tile step, and so few
+    work items that the grid is one workgroup's worth of work padded to eight."""
+    if _PLANNER:
+        return _PLANNER
+    g = torch.Generator().manual_seed(40)
+    d = torch.float64
+    c = _PLANNER
+    c["cache"] = torch.randn(2, 6, 32, 8, 8, generator=g) * 0.5
+    c["sw"] = O.init_mlp_weights([32, 64, 64, 1], g)
+    c["fw"] = O.init_mlp_weights([96, 64, 64, 3], g)
+    c["dw"] = O.init_mlp_weights([32, 64, 64, 3], g)
+    c["pts"] = torch.rand(2, 33, 3, generator=g) * 2.4 - 1.2  # includes out-of-box points
+    c["proj"] = {k: torch.randn(66, n, generator=g) for k, n in (("sdf", 1), ("sdf_grad", 3), ("features", 3))}
+    for dt, tag in ((torch.float32, "32"), (d, "64")):
+        x = c["pts"].to(dt).requires_grad_(True)
+        o = O.geometry_forward(x, c["cache"].to(dt), [w.to(dt) for w in c["sw"]], [w.to(dt) for w in c["fw"]],
+                               output_normal=True, create_graph=True)
+        loss = sum((o[k] * c["proj"][k].to(dt)).sum() for k in c["proj"])
+        c["gx" + tag], = torch.autograd.grad(loss, [x])
+        c["pt" + tag] = {k: o[k].detach() for k in ("sdf", "sdf_grad", "features")}
+        c["pt" + tag]["deformation"] = O.vanilla_mlp(o["enc_geo"].detach(), [w.to(dt) for w in c["dw"]])
+    # rays
+    c["rcache"] = c["cache"][:1].contiguous()
+    ro, rd, c2w, cd = O.make_cameras(1, 5, 8)
+    ts, te = O.uniform_intervals(40, 3, 0.4, 2.9)
+    c["rays"] = (ro.reshape(-1, 3), rd.reshape(-1, 3), ts, te)
+    c["rproj"] = {k: torch.randn(n, generator=g) for k, n in (("opacity", 40), ("depth", 40), ("comp_rgb_fg", 120),
+                                                               ("z_variance", 40), ("normal_acc", 120), ("weights", 120),
+                                                               ("sdf", 120), ("sdf_grad", 360), ("features", 360))}
+    for dt, tag in ((torch.float32, "32"), (d, "64")):
+        params = [c["rcache"].to(dt).requires_grad_(True)] + [w.to(dt).requires_grad_(True) for w in c["sw"] + c["fw"]]
+        o = O.render(params[0], params[1:4], params[4:], ro.to(dt), rd.to(dt), ts.to(dt), te.to(dt),
+                     torch.ones(3, dtype=dt), cd.to(dt), c2w.to(dt), inv_std=100.0)
+        loss = sum((o[k].reshape(-1) * c["rproj"][k].to(dt)).sum() for k in c["rproj"])
+        c["rg" + tag] = list(torch.autograd.grad(loss, params))
+        c["ray" + tag] = {k: o[k].detach().reshape(-1) for k in c["rproj"]}
+    return c
+
+
+def _flat(out, keys):
+    return {k: out[k].reshape(-1) for k in keys}
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_launch_planning_at_its_edge_shapes_per_point(ops, precision):
+    """tt_query_points, tt_query_field and tt_points_bwd_x at the shapes of _planner_case, against the float64 oracle with
+    the bars of tests/parity.py (outputs: as close to exact as the fp32 oracle x 4, floor 2e-5; d/d points: 1e-4 against
+    the fp32 oracle and 3 x its own distance from fp64)."""
+    c = _planner_case()
+    dev = "cuda"
+    sw, fw, dw = ([w.to(dev) for w in c[k]] for k in ("sw", "fw", "dw"))
+    packed = ops.planes_pack(c["cache"].to(dev))
+    sdf, grad, feat = ops.query_points(packed, sw, fw, c["pts"].to(dev), precision=precision)
+    keys = ("sdf", "sdf_grad", "features")
+    check_outputs(f"planner shapes: query_points [{precision}]", _flat(dict(zip(keys, (sdf, grad, feat))), keys),
+                  _flat(c["pt32"], keys), _flat(c["pt64"], keys), keys)
+    sdf2, deform = ops.query_field(packed, sw, dw, c["pts"].to(dev), precision=precision)
+    keys = ("sdf", "deformation")
+    check_outputs(f"planner shapes: query_field [{precision}]", _flat({"sdf": sdf2, "deformation": deform}, keys),
+                  _flat(c["pt32"], keys), _flat(c["pt64"], keys), keys)
+    x = c["pts"].to(dev).requires_grad_(True)
+    out = ops.query_points_grad(c["cache"].to(dev), sw, fw, x, precision=precision)
+    loss = sum((o * c["proj"][k].to(dev)).sum() for k, o in zip(("sdf", "sdf_grad", "features"), out))
+    gx, = torch.autograd.grad(loss, [x])
+    check_grads(f"planner shapes: d/d points [{precision}]", [gx], [c["gx32"]], [c["gx64"]], names=["points"], elem=False)
+
+
+def test_the_three_precision_modes_run_three_different_kernels(ops):
+    """The modes differ at 2^-21 ... 2^-24 per product, below every tolerance: two of them collapsing onto one kernel
+    passes every parity test.  Their sdf outputs on the 66 points of _planner_case must differ pairwise as bit patterns."""
+    c = _planner_case()
+    packed = ops.planes_pack(c["cache"].cuda())
+    sw, fw = [w.cuda() for w in c["sw"]], [w.cuda() for w in c["fw"]]
+    bits = {p: ops.query_points(packed, sw, fw, c["pts"].cuda(), precision=p)[0].view(torch.int32).cpu() for p in PRECISIONS}
+    for a, b in (("split3", "f32"), ("split3", "split2"), ("f32", "split2")):
+        assert not torch.equal(bits[a], bits[b]), (a, b)
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_launch_planning_at_its_edge_shapes_rays(ops, precision):
+    """tt_decode_rays (the four normal / texture combinations), tt_render_fwd, tt_render_eval and one backward through
+    render_samples (tt_render_bwd_geo / _tex) at the ray shapes of _planner_case, against the float64 oracle with the bars
+    of tests/parity.py."""
+    c = _planner_case()
+    dev = "cuda"
+    sw, fw = [w.to(dev) for w in c["sw"]], [w.to(dev) for w in c["fw"]]
+    rays = [t.to(dev) for t in c["rays"]]
+    rc = ops.RenderConfig(inv_std=100.0, precision=precision)
+    packed = ops.planes_pack(c["rcache"].to(dev))
+    for need_n in (True, False):
+        for need_t in (True, False):
+            got = dict(zip(("sdf", "sdf_grad", "features"), ops.decode_rays(packed, sw, fw if need_t else None, *rays, 40, rc,
+                                                                            need_normal=need_n, need_features=need_t)))
+            keys = ("sdf",) + (("sdf_grad",) if need_n else ()) + (("features",) if need_t else ())
+            assert all((got[k] is None) == (k not in keys) for k in got)
+            check_outputs(f"planner shapes: decode_rays normal={need_n} tex={need_t} [{precision}]", _flat(got, keys),
+                          c["ray32"], c["ray64"], keys)
+    names = {"opacity": "opacity", "depth": "depth", "rgb_fg": "comp_rgb_fg", "z_variance": "z_variance",
+             "normal_acc": "normal_acc", "weights": "weights", "sdf": "sdf", "sdf_grad": "sdf_grad", "features": "features"}
+    raw = ops.render_forward_raw(packed, sw, fw, *rays, 40, rc)
+    check_outputs(f"planner shapes: render_forward_raw [{precision}]", {o: raw[k].reshape(-1) for k, o in names.items()},
+                  c["ray32"], c["ray64"], list(names.values()))
+    per_ray = list(names.values())[:5]
+    ev = ops.render_eval_raw(packed, sw, fw, *rays, 40, rc)
+    check_outputs(f"planner shapes: render_eval_raw [{precision}]", {o: ev[k].reshape(-1) for k, o in names.items() if o in per_ray},
+                  c["ray32"], c["ray64"], per_ray)
+    params = [c["rcache"].to(dev).requires_grad_(True)] + [w.clone().requires_grad_(True) for w in sw + fw]
+    out = ops.render_samples(params[0], params[1:4], params[4:], *rays, 40, rc)
+    loss = sum((out[k].reshape(-1) * c["rproj"][o].to(dev)).sum() for k, o in names.items())
+    g_hip = torch.autograd.grad(loss, params)
+    check_grads(f"planner shapes: render_samples backward [{precision}]", [t.cpu() for t in g_hip], c["rg32"], c["rg64"])

@@ -2,6 +2,7 @@
 C-ABI surface (header <-> library <-> ctypes agreement).  No GPU, no compute calls into the library."""
 import ctypes
 import dataclasses
+import math
 import os
 import re
 import subprocess
@@ -355,6 +356,196 @@ def test_reserved_render_flags_are_unsupported_before_any_hip_call():
                                      ctypes.byref(w), null) == -2
     from triplaneturbo_amd import ops
     assert "wgrad_f32" not in {f.name for f in dataclasses.fields(ops.RenderConfig)}
+
+
+# ---- status table of the ten decode-family entry points ---------------------------------------------------------------
+# Each entry point with one valid argument tuple (pointers are placeholders, counts are small) and a list of single
+# mutations of it.  _STATUS holds the status of every row as the library answered BEFORE the entry points shared their
+# validator, launch planner and precision dispatch (recorded from that build, not derived from the code under test).
+_PT = "n_batch=2 n_points=33 n_prompts=2 views_per_prompt=1 plane_h=8 plane_w=8 radius=1.0"
+_RAYS = "packed w rays_o rays_d t_starts t_ends cfg"
+_ENTRIES = {
+    "tt_query_points": f"packed w points {_PT} sdf_bias_radius=0.5 flags=3 out_sdf out_sdf_grad out_features",
+    "tt_query_field": f"packed w points {_PT} sdf_bias_radius=0.5 flags=0 out_sdf out_deformation",
+    "tt_points_bwd_x": f"packed w points {_PT} flags=0 g_sdf g_sdf_grad g_features grad_points",
+    "tt_render_fwd": f"{_RAYS} opacity depth rgb_fg z_variance normal_acc weights trans sdf sdf_grad features",
+    "tt_decode_rays": f"{_RAYS} flags=3 sdf sdf_grad features",
+    "tt_render_eval": f"{_RAYS} transmittance_eps=0.0 weight_eps=0.0 opacity depth rgb_fg z_variance normal_acc stats",
+    "tt_render_bwd_geo": f"{_RAYS} opacity depth trans sdf sdf_grad features g_opacity g_depth g_rgb_fg g_z_variance "
+                         "g_normal_acc g_weights g_sdf g_sdf_grad g_inv_std_rays workspace grad_packed grads",
+    "tt_points_bwd_geo": f"packed w points {_PT} sdf_bias_radius=0.5 flags=0 g_sdf g_sdf_grad workspace grad_packed grads",
+    "tt_render_bwd_tex": f"{_RAYS} weights features g_rgb_fg g_features grad_packed grads",
+    "tt_points_bwd_tex": f"packed w points {_PT} plane_base=3 flags=0 g_features grad_packed grads",
+}
+_CFG = dict(n_prompts=1, views_per_prompt=1, plane_h=8, plane_w=8, rays_per_view=16, n_samples=4, n_rays=16, radius=1.0,
+            sdf_bias_radius=0.5, inv_std=100.0, cos_anneal_ratio=1.0, rgb_grad_shrink=1.0, flags=0, grad_copies=1)
+_SIX = ("w1", "w2", "w3", "v1", "v2", "v3")
+
+
+def _status_rows(name):
+    """[(label, {argument or "struct.field": value})]: the valid tuple ("valid") and every single mutation of it."""
+    toks = [t.split("=")[0] for t in _ENTRIES[name].split()]
+    rays = "cfg" in toks
+    pre = "cfg." if rays else ""
+    rows = [("valid", {})]
+    rows += [(f"{t}=null", {t: None}) for t in toks if "=" not in _ENTRIES[name].split()[toks.index(t)]]
+    rows += [(f"{s}.{f}=null", {f"{s}.{f}": None}) for s in ("w", "grads") if s in toks for f in _SIX]
+    counts = ("n_prompts", "views_per_prompt", "rays_per_view", "n_samples", "n_rays") if rays else \
+        ("n_batch", "n_points", "n_prompts", "views_per_prompt")
+    rows += [(f"{c}={v}", {pre + c: v}) for c in counts for v in (0, -1)]
+    rows.append(("batch_inconsistent", {"cfg.n_rays": 17} if rays else {"n_batch": 3}))
+    rows += [(f"radius={v}", {pre + "radius": v}) for v in (0.0, math.nan)]
+    rows.append(("non_square", {pre + "plane_w": 16}))
+    big = {pre + "n_prompts": 86, pre + "plane_h": 256, pre + "plane_w": 256}
+    big.update({"cfg.n_rays": 86 * 16} if rays else {"n_batch": 86})
+    rows.append(("86_prompts_of_256x256", big))
+    if rays:
+        rows.append(("two_precision_bits_r", {"cfg.flags": _lib.TT_R_EXACT_F32 | _lib.TT_R_SPLIT2}))
+        rows += [(f"reserved_{f}", {"cfg.flags": getattr(_lib, f)}) for f in ("TT_R_BWD_PAIR", "TT_R_WGRAD_F32")]
+    if "flags" in toks:
+        rows.append(("two_precision_bits_q", {"flags": _lib.TT_Q_EXACT_F32 | _lib.TT_Q_SPLIT2}))
+    if name == "tt_points_bwd_tex":
+        rows.append(("plane_base=1", {"plane_base": 1}))
+    if name == "tt_points_bwd_geo":
+        rows.append(("g_sdf=g_sdf_grad=null", {"g_sdf": None, "g_sdf_grad": None}))
+    if name == "tt_render_eval":
+        rows += [(f"{e}=-1", {e: -1.0}) for e in ("transmittance_eps", "weight_eps")]
+    if name == "tt_decode_rays":
+        rows.append(("normal_without_sdf_grad", {"flags": _lib.TT_Q_NORMAL, "sdf_grad": None}))
+    return rows
+
+
+def _status_of(lib, name, mutation):
+    """Calls entry point `name` with its valid tuple changed by `mutation`.  Pointers are the address 8: never
+    dereferenced, because every row returns before the first launch (the caller sees to it that there is no device)."""
+    one = ctypes.c_void_p(8)
+    sub = lambda s: {k.split(".")[1]: v for k, v in mutation.items() if k.startswith(s + ".")}
+    keep = []
+    args = []
+    for tok in _ENTRIES[name].split():
+        t, _, default = tok.partition("=")
+        if t in mutation and mutation[t] is None:
+            args.append(None)
+        elif t in ("w", "grads"):
+            keep.append(_lib.MlpWeights(*[None if f in sub(t) else one for f in _SIX]))
+            args.append(ctypes.byref(keep[-1]))
+        elif t == "cfg":
+            keep.append(_lib.RenderCfg(**{**_CFG, **sub("cfg")}))
+            args.append(ctypes.byref(keep[-1]))
+        elif default:
+            args.append(mutation.get(t, float(default) if "." in default else int(default)))
+        else:
+            args.append(one)
+    return getattr(lib, name)(*args, None)
+
+_STATUS = {
+    'tt_query_points': {-4: 'valid out_sdf=null out_sdf_grad=null out_features=null 86_prompts_of_256x256',
+                        -2: 'non_square',
+                        -1: 'packed=null w=null points=null w.w1=null w.w2=null w.w3=null w.v1=null w.v2=null w.v3=null '
+                            'n_batch=0 n_batch=-1 n_points=0 n_points=-1 n_prompts=0 n_prompts=-1 views_per_prompt=0 '
+                            'views_per_prompt=-1 batch_inconsistent radius=0.0 radius=nan two_precision_bits_q'},
+    'tt_query_field': {-4: 'valid 86_prompts_of_256x256',
+                       -2: 'non_square',
+                       -1: 'packed=null w=null points=null out_sdf=null out_deformation=null w.w1=null w.w2=null '
+                           'w.w3=null w.v1=null w.v2=null w.v3=null n_batch=0 n_batch=-1 n_points=0 n_points=-1 '
+                           'n_prompts=0 n_prompts=-1 views_per_prompt=0 views_per_prompt=-1 batch_inconsistent '
+                           'radius=0.0 radius=nan two_precision_bits_q'},
+    'tt_points_bwd_x': {-4: 'valid g_sdf=null g_sdf_grad=null g_features=null 86_prompts_of_256x256',
+                        -2: 'non_square',
+                        # two_precision_bits_q: -4 until the entry points shared one validator -- tt_points_bwd_x alone looked
+                        # at its flag word after asking for the device; now it is TT_ERR_BAD_ARG before, as everywhere else
+                        -1: 'packed=null w=null points=null grad_points=null w.w1=null w.w2=null w.w3=null w.v1=null '
+                            'w.v2=null w.v3=null n_batch=0 n_batch=-1 n_points=0 n_points=-1 n_prompts=0 n_prompts=-1 '
+                            'views_per_prompt=0 views_per_prompt=-1 batch_inconsistent radius=0.0 radius=nan '
+                            'two_precision_bits_q'},
+    'tt_render_fwd': {-4: 'valid',
+                      -2: 'non_square 86_prompts_of_256x256 reserved_TT_R_BWD_PAIR reserved_TT_R_WGRAD_F32',
+                      -1: 'packed=null w=null rays_o=null rays_d=null t_starts=null t_ends=null cfg=null opacity=null '
+                          'depth=null rgb_fg=null z_variance=null normal_acc=null weights=null trans=null sdf=null '
+                          'sdf_grad=null features=null w.w1=null w.w2=null w.w3=null w.v1=null w.v2=null w.v3=null '
+                          'n_prompts=0 n_prompts=-1 views_per_prompt=0 views_per_prompt=-1 rays_per_view=0 '
+                          'rays_per_view=-1 n_samples=0 n_samples=-1 n_rays=0 n_rays=-1 batch_inconsistent radius=0.0 '
+                          'radius=nan two_precision_bits_r'},
+    'tt_decode_rays': {-4: 'valid',
+                       -2: 'non_square 86_prompts_of_256x256 reserved_TT_R_BWD_PAIR reserved_TT_R_WGRAD_F32',
+                       -1: 'packed=null w=null rays_o=null rays_d=null t_starts=null t_ends=null cfg=null sdf=null '
+                           'sdf_grad=null features=null w.w1=null w.w2=null w.w3=null w.v1=null w.v2=null w.v3=null '
+                           'n_prompts=0 n_prompts=-1 views_per_prompt=0 views_per_prompt=-1 rays_per_view=0 '
+                           'rays_per_view=-1 n_samples=0 n_samples=-1 n_rays=0 n_rays=-1 batch_inconsistent radius=0.0 '
+                           'radius=nan two_precision_bits_r two_precision_bits_q normal_without_sdf_grad'},
+    'tt_render_eval': {-4: 'valid stats=null',
+                       -2: 'non_square 86_prompts_of_256x256 reserved_TT_R_BWD_PAIR reserved_TT_R_WGRAD_F32',
+                       -1: 'packed=null w=null rays_o=null rays_d=null t_starts=null t_ends=null cfg=null opacity=null '
+                           'depth=null rgb_fg=null z_variance=null normal_acc=null w.w1=null w.w2=null w.w3=null '
+                           'w.v1=null w.v2=null w.v3=null n_prompts=0 n_prompts=-1 views_per_prompt=0 '
+                           'views_per_prompt=-1 rays_per_view=0 rays_per_view=-1 n_samples=0 n_samples=-1 n_rays=0 '
+                           'n_rays=-1 batch_inconsistent radius=0.0 radius=nan two_precision_bits_r '
+                           'transmittance_eps=-1 weight_eps=-1'},
+    'tt_render_bwd_geo': {-4: 'valid g_opacity=null g_depth=null g_rgb_fg=null g_z_variance=null g_normal_acc=null '
+                              'g_weights=null g_sdf=null g_sdf_grad=null g_inv_std_rays=null w.v1=null w.v2=null '
+                              'w.v3=null grads.v1=null grads.v2=null grads.v3=null',
+                          -2: 'non_square 86_prompts_of_256x256 reserved_TT_R_BWD_PAIR reserved_TT_R_WGRAD_F32',
+                          -1: 'packed=null w=null rays_o=null rays_d=null t_starts=null t_ends=null cfg=null '
+                              'opacity=null depth=null trans=null sdf=null sdf_grad=null features=null workspace=null '
+                              'grad_packed=null grads=null w.w1=null w.w2=null w.w3=null grads.w1=null grads.w2=null '
+                              'grads.w3=null n_prompts=0 n_prompts=-1 views_per_prompt=0 views_per_prompt=-1 '
+                              'rays_per_view=0 rays_per_view=-1 n_samples=0 n_samples=-1 n_rays=0 n_rays=-1 '
+                              'batch_inconsistent radius=0.0 radius=nan two_precision_bits_r'},
+    'tt_points_bwd_geo': {-4: 'valid g_sdf=null g_sdf_grad=null w.v1=null w.v2=null w.v3=null grads.v1=null '
+                              'grads.v2=null grads.v3=null',
+                          -2: 'non_square 86_prompts_of_256x256',
+                          -1: 'packed=null w=null points=null workspace=null grad_packed=null grads=null w.w1=null '
+                              'w.w2=null w.w3=null grads.w1=null grads.w2=null grads.w3=null n_batch=0 n_batch=-1 '
+                              'n_points=0 n_points=-1 n_prompts=0 n_prompts=-1 views_per_prompt=0 views_per_prompt=-1 '
+                              'batch_inconsistent radius=0.0 radius=nan two_precision_bits_q g_sdf=g_sdf_grad=null'},
+    'tt_render_bwd_tex': {-4: 'valid g_rgb_fg=null g_features=null w.w1=null w.w2=null w.w3=null grads.w1=null '
+                              'grads.w2=null grads.w3=null',
+                          -2: 'non_square 86_prompts_of_256x256 reserved_TT_R_BWD_PAIR reserved_TT_R_WGRAD_F32',
+                          -1: 'packed=null w=null rays_o=null rays_d=null t_starts=null t_ends=null cfg=null '
+                              'weights=null features=null grad_packed=null grads=null w.v1=null w.v2=null w.v3=null '
+                              'grads.v1=null grads.v2=null grads.v3=null n_prompts=0 n_prompts=-1 views_per_prompt=0 '
+                              'views_per_prompt=-1 rays_per_view=0 rays_per_view=-1 n_samples=0 n_samples=-1 n_rays=0 '
+                              'n_rays=-1 batch_inconsistent radius=0.0 radius=nan two_precision_bits_r'},
+    'tt_points_bwd_tex': {-4: 'valid w.w1=null w.w2=null w.w3=null grads.w1=null grads.w2=null grads.w3=null',
+                          -2: 'non_square 86_prompts_of_256x256',
+                          -1: 'packed=null w=null points=null g_features=null grad_packed=null grads=null w.v1=null '
+                              'w.v2=null w.v3=null grads.v1=null grads.v2=null grads.v3=null n_batch=0 n_batch=-1 '
+                              'n_points=0 n_points=-1 n_prompts=0 n_prompts=-1 views_per_prompt=0 views_per_prompt=-1 '
+                              'batch_inconsistent radius=0.0 radius=nan two_precision_bits_q plane_base=1'}
+}
+
+
+def test_status_table_of_the_decode_entry_points():
+    """Every row of _STATUS: the entry point answers the recorded status.  The TT_ERR_BAD_ARG / TT_ERR_UNSUPPORTED rows
+    return before any HIP call and are checked everywhere.  The TT_ERR_DEVICE rows -- the valid tuple and the mutations
+    that leave it valid -- get as far as asking for the device, so they are checked only where there is none: with a
+    device they would go on to launch kernels on the placeholder pointers."""
+    _lib.build()
+    lib = _lib.load()
+    no_device = not torch.cuda.is_available()
+    for name in _ENTRIES:
+        rows = dict(_status_rows(name))
+        want = {label: status for status, labels in _STATUS[name].items() for label in labels.split()}
+        assert set(want) == set(rows) and want["valid"] == -4, name
+        for label, mutation in rows.items():
+            if want[label] != -4 or no_device:
+                assert _status_of(lib, name, mutation) == want[label], (name, label)
+
+
+@pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan_ubsan"])
+def test_precision_dispatch_and_grid_size_as_a_stand_alone_host_program(tmp_path, sanitize):
+    """tests/host_launch_check.cpp drives the precision dispatcher of csrc/tt_host.h with every (precision, need_n, need_t),
+    checks the flag -> mode maps and sweeps tt_persistent_blocks against the formula the entry points used to spell out.
+    A tolerance test cannot see two modes swapped (they differ at 2^-21); this can.  The program makes no HIP call; the
+    second build runs it under the address and undefined-behaviour sanitizers (host code only)."""
+    exe = tmp_path / "host_launch_check"
+    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "--offload-arch=gfx950", "-std=c++17", "-g",
+           os.path.join(ROOT, "tests", "host_launch_check.cpp"), "-o", str(exe)]
+    if sanitize:
+        cmd += ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined"]
+    subprocess.run(cmd, check=True, cwd=str(tmp_path))
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.strip().endswith("0 failure(s)"), r.stdout[-2000:] + r.stderr[-2000:]
 
 
 def test_product_library_never_reads_the_environment():

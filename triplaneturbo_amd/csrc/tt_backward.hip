@@ -336,35 +336,22 @@ static void launch_bwd_geo(const BwdGeoParams& p0, long long blocks, hipStream_t
 #else
     p.phase_cycles = nullptr;
 #endif
-    const int prec = tt_prec_of_r(p.cfg.flags);
-#define LAUNCH_GEO(PREC_, WG_)                                                                                        \
-    do {                                                                                                              \
-        if (p.cfg.stats)                                                                                              \
-            hipLaunchKernelGGL((k_decode_bwd_geo<PREC_, WG_, true>), dim3((unsigned)blocks), dim3(256), 0, s, p);     \
-        else                                                                                                          \
-            hipLaunchKernelGGL((k_decode_bwd_geo<PREC_, WG_>), dim3((unsigned)blocks), dim3(256), 0, s, p);           \
-    } while (0)
-    if (use_wg16(p.cfg)) {
+    if (use_wg16(p.cfg)) {  // (every mode but PREC_F32)
         unsigned* bnd = reinterpret_cast<unsigned*>(p.queue) + TT_SLOT_BOUNDS;
         launch_planes_bound(p.packed, p.cfg, 0, bnd + TT_BOUND_PLANES, s);
         const long long n = p.cfg.n_rays * p.cfg.n_samples;  // upstream float4 (d sdf, d sdf_grad) per sample
         hipLaunchKernelGGL(k_absmax4, dim3(absmax_blocks(n), 1), dim3(256), 0, s, reinterpret_cast<const f32x4*>(p.ws), n, n,
                            bnd + TT_BOUND_UP0, bnd + TT_BOUND_UP1);
-        if (prec == PREC_S3)
-            LAUNCH_GEO(PREC_S3, true);
-        else
-            LAUNCH_GEO(PREC_S2, true);
-    } else {  // TT_R_EXACT_F32
-        LAUNCH_GEO(PREC_F32, false);
     }
-#undef LAUNCH_GEO
+    tt_dispatch_prec(tt_prec_of_r(p.cfg.flags), [&](auto P) {
+        constexpr int PREC = decltype(P)::value;
+        constexpr bool WG16 = PREC != PREC_F32;
+        if (p.cfg.stats)
+            hipLaunchKernelGGL((k_decode_bwd_geo<PREC, WG16, true>), dim3((unsigned)blocks), dim3(256), 0, s, p);
+        else
+            hipLaunchKernelGGL((k_decode_bwd_geo<PREC, WG16>), dim3((unsigned)blocks), dim3(256), 0, s, p);
+    });
 }
-int tt_launch_march_bwd(const float* rays_d, const float* t_starts, const float* t_ends, const tt_render_cfg* cfg,
-                        const float* sdf, const float* sdf_grad, const float* features, const float* trans,
-                        const float* opacity, const float* depth, const float* g_opacity, const float* g_depth,
-                        const float* g_rgb_fg, const float* g_z_variance, const float* g_normal_acc,
-                        const float* g_weights, const float* g_sdf, const float* g_sdf_grad, float* g_inv_std_rays,
-                        float* ws, hipStream_t stream);
 
 extern "C" int tt_render_bwd_geo(const float* packed, const tt_mlp_weights* w, const float* rays_o,
                                  const float* rays_d, const float* t_starts, const float* t_ends,
@@ -389,24 +376,15 @@ extern "C" int tt_render_bwd_geo(const float* packed, const tt_mlp_weights* w, c
                              workspace, s);
     if (st != TT_OK) return st;
     BwdGeoParams p;
-    p.packed = packed;
-    p.w = to_ptrs(w);
-    p.rays_o = rays_o;
-    p.rays_d = rays_d;
-    p.t_starts = t_starts;
-    p.t_ends = t_ends;
-    p.cfg = *cfg;
+    tt_fill_rays(p, packed, w, rays_o, rays_d, t_starts, t_ends, *cfg);
     p.cfg.flags |= debug_flags();
     p.ws = workspace;
     p.grad_packed = grad_packed;
     p.n_copies = cfg->grad_copies > 0 ? cfg->grad_copies : 1;
     p.grads = to_gptrs(grads);
-    p.n_items = tt_make_geom(cfg, 4LL * cus, &p.geom, 1);
-    long long blocks = persistent_blocks(p.n_items, cus);
-    if (p.n_items > (1LL << 30)) return TT_ERR_UNSUPPORTED;
-    p.queue = tt_queue_counters(s);
-    if (!p.queue) return TT_ERR_DEVICE;
-    launch_bwd_geo(p, blocks, s);
+    st = tt_plan_queue(cfg, 4LL * cus, s, &p.geom, &p.n_items, &p.queue);
+    if (st != TT_OK) return st;
+    launch_bwd_geo(p, tt_persistent_blocks(p.n_items, cus, 4), s);
     return tt_check_launch();
 }
 
@@ -443,23 +421,13 @@ extern "C" int tt_points_bwd_geo(const float* packed, const tt_mlp_weights* w, c
     st = tt_check_launch();
     if (st != TT_OK) return st;
     BwdGeoParams p;
-    p.packed = packed;
-    p.w = to_ptrs(w);
-    p.rays_o = points;
-    p.rays_d = nullptr;
-    p.t_starts = nullptr;
-    p.t_ends = nullptr;
-    p.cfg = cfg;
+    tt_fill_rays(p, packed, w, points, nullptr, nullptr, nullptr, cfg);
     p.ws = workspace;
     p.grad_packed = grad_packed;
     p.n_copies = 1;
     p.grads = to_gptrs(grads);
-    p.n_items = tt_make_geom(&cfg, 4LL * cus, &p.geom, 1);
-    if (p.n_items > (1LL << 30)) return TT_ERR_UNSUPPORTED;
-    long long blocks = persistent_blocks(p.n_items, cus);
-    p.queue = tt_queue_counters(s);
-    if (!p.queue) return TT_ERR_DEVICE;
-    launch_bwd_geo(p, blocks, s);
+    st = tt_plan_queue(&cfg, 4LL * cus, s, &p.geom, &p.n_items, &p.queue);
+    if (st != TT_OK) return st;
+    launch_bwd_geo(p, tt_persistent_blocks(p.n_items, cus, 4), s);
     return tt_check_launch();
 }
-

@@ -6,8 +6,7 @@
 #include "tt_device.h"
 #include "tt_mfma16.h"
 #include "tt_alpha.h"
-#include "tt_host.h"
-#include <stdlib.h>
+#include "tt_launch.h"
 #include <type_traits>
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -710,15 +709,6 @@ __device__ __forceinline__ void scatter_planes(float* __restrict__ grad, unsigne
     }
 }
 
-struct MlpGradPtrs {
-    float* w1;
-    float* w2;
-    float* w3;
-    float* v1;
-    float* v2;
-    float* v3;
-};
-
 // ---- texture half: parameters and weight-image map of tt_backward_tex.hip ----
 struct BwdTexParams {
     const float* packed;
@@ -767,47 +757,9 @@ struct TexWFloats {
 // =====================================================================================================
 // host side
 // =====================================================================================================
-static inline MlpPtrs to_ptrs(const tt_mlp_weights* w) {
-    MlpPtrs m;
-    m.w1 = w->w1;
-    m.w2 = w->w2;
-    m.w3 = w->w3;
-    m.v1 = w->v1;
-    m.v2 = w->v2;
-    m.v3 = w->v3;
-    return m;
-}
-static inline MlpGradPtrs to_gptrs(const tt_mlp_grads* g) {
-    MlpGradPtrs m;
-    m.w1 = g->w1;
-    m.w2 = g->w2;
-    m.w3 = g->w3;
-    m.v1 = g->v1;
-    m.v2 = g->v2;
-    m.v3 = g->v3;
-    return m;
-}
-
-static inline int debug_flags() {
-#ifdef TT_TUNING
-    const char* e = getenv("TT_DEBUG_FLAGS");  // profiling ablations, tuning build only
-    return e ? (int)strtol(e, nullptr, 0) : 0;
-#else
-    return 0;
-#endif
-}
-
 // the scatter addresses texels with 32-bit byte offsets from the (copy of the) gradient buffer
 static inline bool grad_buffer_too_large(const tt_render_cfg* cfg) {
     return (long long)cfg->n_prompts * 6 * cfg->plane_h * cfg->plane_w * TT_C * 4 >= (1LL << 32) - 256;
-}
-
-// one 4-wave workgroup per CU (register- and LDS-limited), grid a multiple of 8 (XCD chunking)
-static inline long long persistent_blocks(long long n_items, int cus) {
-    long long blocks = cus;
-    long long need = (n_items + 3) / 4;
-    if (blocks > need) blocks = need;
-    return (blocks + 7) / 8 * 8;
 }
 
 #ifdef TT_TUNING
@@ -888,8 +840,8 @@ static inline bool use_wg16(const tt_render_cfg& cfg) { return !(cfg.flags & TT_
 static inline int points_cfg(tt_render_cfg* c, int32_t n_batch, int64_t n_points, int32_t n_prompts,
                       int32_t views_per_prompt, int32_t plane_h, int32_t plane_w, float radius, float sdf_bias_radius,
                       int32_t grad_copies, int32_t q_flags) {
-    if (n_batch <= 0 || n_points <= 0 || n_prompts <= 0 || views_per_prompt <= 0) return TT_ERR_BAD_ARG;
-    if ((int64_t)n_prompts * views_per_prompt != n_batch || n_points > 0x7fffffffLL) return TT_ERR_BAD_ARG;
+    if (!tt_points_counts_ok(n_batch, n_points, n_prompts, views_per_prompt, q_flags) || n_points > 0x7fffffffLL)
+        return TT_ERR_BAD_ARG;
     c->n_prompts = n_prompts;
     c->views_per_prompt = views_per_prompt;
     c->plane_h = plane_h;
@@ -904,7 +856,6 @@ static inline int points_cfg(tt_render_cfg* c, int32_t n_batch, int64_t n_points
     c->stats = nullptr;
     c->cos_anneal_ratio = 1.f;
     c->rgb_grad_shrink = 1.f;
-    if (!tt_qflags_ok(q_flags)) return TT_ERR_BAD_ARG;
     c->flags = (q_flags & TT_Q_EXACT_F32) ? TT_R_EXACT_F32 : ((q_flags & TT_Q_SPLIT2) ? TT_R_SPLIT2 : 0);
     c->image_w = 0;
     c->tile_sb = 1;

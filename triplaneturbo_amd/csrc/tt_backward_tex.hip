@@ -370,15 +370,7 @@ static void launch_bwd_tex(const BwdTexParams& p0, long long blocks, hipStream_t
 #else
     p.phase_cycles = nullptr;
 #endif
-    const int prec = tt_prec_of_r(p.cfg.flags);
-#define LAUNCH_TEX(PREC_, WG_)                                                                                        \
-    do {                                                                                                              \
-        if (p.cfg.stats)                                                                                              \
-            hipLaunchKernelGGL((k_decode_bwd_tex<PREC_, WG_, true>), dim3((unsigned)blocks), dim3(256), 0, s, p);     \
-        else                                                                                                          \
-            hipLaunchKernelGGL((k_decode_bwd_tex<PREC_, WG_>), dim3((unsigned)blocks), dim3(256), 0, s, p);           \
-    } while (0)
-    if (use_wg16(p.cfg)) {
+    if (use_wg16(p.cfg)) {  // (every mode but PREC_F32)
         unsigned* bnd = reinterpret_cast<unsigned*>(p.queue) + TT_SLOT_BOUNDS;
         launch_planes_bound(p.packed, p.cfg, 3, bnd + TT_BOUND_PLANES, s);  // (p.packed may be slid by 3 planes: points)
         if (p.g_rgb)
@@ -388,14 +380,15 @@ static void launch_bwd_tex(const BwdTexParams& p0, long long blocks, hipStream_t
             const long long n = p.cfg.n_rays * p.cfg.n_samples * 3;
             hipLaunchKernelGGL(k_absmax1, dim3(absmax_blocks(n)), dim3(256), 0, s, p.g_features, n, bnd + TT_BOUND_UP1);
         }
-        if (prec == PREC_S3)
-            LAUNCH_TEX(PREC_S3, true);
-        else
-            LAUNCH_TEX(PREC_S2, true);
-    } else {  // TT_R_EXACT_F32
-        LAUNCH_TEX(PREC_F32, false);
     }
-#undef LAUNCH_TEX
+    tt_dispatch_prec(tt_prec_of_r(p.cfg.flags), [&](auto P) {
+        constexpr int PREC = decltype(P)::value;
+        constexpr bool WG16 = PREC != PREC_F32;
+        if (p.cfg.stats)
+            hipLaunchKernelGGL((k_decode_bwd_tex<PREC, WG16, true>), dim3((unsigned)blocks), dim3(256), 0, s, p);
+        else
+            hipLaunchKernelGGL((k_decode_bwd_tex<PREC, WG16>), dim3((unsigned)blocks), dim3(256), 0, s, p);
+    });
 }
 
 extern "C" int tt_render_bwd_tex(const float* packed, const tt_mlp_weights* w, const float* rays_o,
@@ -412,14 +405,9 @@ extern "C" int tt_render_bwd_tex(const float* packed, const tt_mlp_weights* w, c
     if (grad_buffer_too_large(cfg)) return TT_ERR_UNSUPPORTED;
     int cus = tt_num_cus();
     if (cus <= 0) return TT_ERR_DEVICE;
+    hipStream_t s = (hipStream_t)stream;
     BwdTexParams p;
-    p.packed = packed;
-    p.w = to_ptrs(w);
-    p.rays_o = rays_o;
-    p.rays_d = rays_d;
-    p.t_starts = t_starts;
-    p.t_ends = t_ends;
-    p.cfg = *cfg;
+    tt_fill_rays(p, packed, w, rays_o, rays_d, t_starts, t_ends, *cfg);
     p.cfg.flags |= debug_flags();
     p.weights = weights;
     p.features = features;
@@ -428,12 +416,9 @@ extern "C" int tt_render_bwd_tex(const float* packed, const tt_mlp_weights* w, c
     p.grad_packed = grad_packed;
     p.n_copies = cfg->grad_copies > 0 ? cfg->grad_copies : 1;
     p.grads = to_gptrs(grads);
-    p.n_items = tt_make_geom(cfg, 4LL * cus, &p.geom, 1, 12);
-    long long blocks = persistent_blocks(p.n_items, cus);
-    if (p.n_items > (1LL << 30)) return TT_ERR_UNSUPPORTED;
-    p.queue = tt_queue_counters((hipStream_t)stream);
-    if (!p.queue) return TT_ERR_DEVICE;
-    launch_bwd_tex(p, blocks, (hipStream_t)stream);
+    st = tt_plan_queue(cfg, 4LL * cus, s, &p.geom, &p.n_items, &p.queue, 12);
+    if (st != TT_OK) return st;
+    launch_bwd_tex(p, tt_persistent_blocks(p.n_items, cus, 4), s);
     return tt_check_launch();
 }
 
@@ -454,14 +439,9 @@ extern "C" int tt_points_bwd_tex(const float* packed, const tt_mlp_weights* w, c
     if (cus <= 0) return TT_ERR_DEVICE;
     // the kernel addresses planes 3..5 of each prompt; plane_base = 0 slides that window onto planes 0..2
     const ptrdiff_t shift = (ptrdiff_t)(plane_base - 3) * plane_h * plane_w * TT_C;
+    hipStream_t s = (hipStream_t)stream;
     BwdTexParams p;
-    p.packed = packed + shift;
-    p.w = to_ptrs(w);
-    p.rays_o = points;
-    p.rays_d = nullptr;
-    p.t_starts = nullptr;
-    p.t_ends = nullptr;
-    p.cfg = cfg;
+    tt_fill_rays(p, packed + shift, w, points, nullptr, nullptr, nullptr, cfg);
     p.weights = nullptr;
     p.features = nullptr;
     p.g_rgb = nullptr;
@@ -469,12 +449,8 @@ extern "C" int tt_points_bwd_tex(const float* packed, const tt_mlp_weights* w, c
     p.grad_packed = grad_packed + shift;
     p.n_copies = 1;
     p.grads = to_gptrs(grads);
-    p.n_items = tt_make_geom(&cfg, 4LL * cus, &p.geom, 1);
-    if (p.n_items > (1LL << 30)) return TT_ERR_UNSUPPORTED;
-    long long blocks = persistent_blocks(p.n_items, cus);
-    p.queue = tt_queue_counters((hipStream_t)stream);
-    if (!p.queue) return TT_ERR_DEVICE;
-    launch_bwd_tex(p, blocks, (hipStream_t)stream);
+    st = tt_plan_queue(&cfg, 4LL * cus, s, &p.geom, &p.n_items, &p.queue);
+    if (st != TT_OK) return st;
+    launch_bwd_tex(p, tt_persistent_blocks(p.n_items, cus, 4), s);
     return tt_check_launch();
 }
-

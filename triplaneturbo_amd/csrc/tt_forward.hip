@@ -5,9 +5,7 @@
 #include "tt_device.h"
 #include "tt_mfma16.h"
 #include "tt_alpha.h"
-#include "tt_host.h"
-
-#include <stdlib.h>
+#include "tt_launch.h"
 
 // =====================================================================================================
 // plane pack: (P,6,32,H,W) NCHW  ->  (P,6,H,W,32) channels-last with rotate_planes "v1" folded in
@@ -704,17 +702,6 @@ __global__ __launch_bounds__(DECODE_THREADS) void k_render_eval(RenderEvalParams
 // =====================================================================================================
 // host side (C ABI)
 // =====================================================================================================
-static MlpPtrs to_ptrs(const tt_mlp_weights* w) {
-    MlpPtrs m;
-    m.w1 = w->w1;
-    m.w2 = w->w2;
-    m.w3 = w->w3;
-    m.v1 = w->v1;
-    m.v2 = w->v2;
-    m.v3 = w->v3;
-    return m;
-}
-
 extern "C" int tt_planes_pack(const float* space_cache, float* packed, int32_t n_prompts, int32_t plane_h,
                               int32_t plane_w, void* stream) {
     if (!space_cache || !packed || n_prompts <= 0 || plane_h <= 0 || plane_w <= 0) return TT_ERR_BAD_ARG;
@@ -755,52 +742,24 @@ extern "C" int tt_query_points(const float* packed, const tt_mlp_weights* w, con
                                int64_t n_points, int32_t n_prompts, int32_t views_per_prompt, int32_t plane_h,
                                int32_t plane_w, float radius, float sdf_bias_radius, int32_t flags, float* out_sdf,
                                float* out_sdf_grad, float* out_features, void* stream) {
-    if (!packed || !w || !points || n_batch <= 0 || n_points <= 0 || n_prompts <= 0 || views_per_prompt <= 0)
-        return TT_ERR_BAD_ARG;
-    if (n_batch != n_prompts * views_per_prompt || !(radius > 0.f) || !tt_qflags_ok(flags)) return TT_ERR_BAD_ARG;
-    if (plane_h != plane_w || plane_h <= 0) return TT_ERR_UNSUPPORTED;
+    if (!packed || !w || !points) return TT_ERR_BAD_ARG;
+    const int st = tt_validate_points(n_batch, n_points, n_prompts, views_per_prompt, plane_h, plane_w, radius, flags);
+    if (st != TT_OK) return st;
     const bool need_n = (flags & TT_Q_NORMAL) != 0, need_t = (flags & TT_Q_TEX) != 0;
     if (!w->w1 || !w->w2 || !w->w3 || (need_t && (!w->v1 || !w->v2 || !w->v3))) return TT_ERR_BAD_ARG;
     QueryParams p;
-    p.packed = packed;
-    p.w = to_ptrs(w);
-    p.points = points;
-    p.n_batch = n_batch;
-    p.n_points = n_points;
-    p.views_per_prompt = views_per_prompt;
-    p.H = plane_h;
-    p.W = plane_w;
-    p.radius = radius;
+    tt_fill_points(p, packed, w, points, n_batch, n_points, views_per_prompt, plane_h, plane_w, radius);
     p.bias_radius = sdf_bias_radius;
     p.out_sdf = out_sdf;
     p.out_grad = out_sdf_grad;
     p.out_feat = out_features;
-    int cus = tt_num_cus();
+    const int cus = tt_num_cus();
     if (cus <= 0) return TT_ERR_DEVICE;
-    long long n_tiles = ((n_points + TT_TILE - 1) / TT_TILE) * n_batch;
-    long long blocks = (n_tiles + 7) / 8;
-    if (blocks > cus) blocks = cus;
-    dim3 grid((unsigned)blocks), block(DECODE_THREADS);
-    hipStream_t s = (hipStream_t)stream;
-    const int prec = tt_prec_of_q(flags);
-#define LAUNCH_QP(N, T)                                                                        \
-    do {                                                                                       \
-        if (prec == PREC_F32)                                                                  \
-            hipLaunchKernelGGL((k_query_points<N, T, PREC_F32>), grid, block, 0, s, p);        \
-        else if (prec == PREC_S3)                                                              \
-            hipLaunchKernelGGL((k_query_points<N, T, PREC_S3>), grid, block, 0, s, p);         \
-        else                                                                                   \
-            hipLaunchKernelGGL((k_query_points<N, T, PREC_S2>), grid, block, 0, s, p);         \
-    } while (0)
-    if (need_n && need_t)
-        LAUNCH_QP(true, true);
-    else if (need_n)
-        LAUNCH_QP(true, false);
-    else if (need_t)
-        LAUNCH_QP(false, true);
-    else
-        LAUNCH_QP(false, false);
-#undef LAUNCH_QP
+    const dim3 grid = tt_point_blocks(n_points, n_batch, DECODE_THREADS / 64, cus);
+    tt_dispatch(tt_prec_of_q(flags), need_n, need_t, [&](auto P, auto N, auto T) {
+        hipLaunchKernelGGL((k_query_points<decltype(N)::value, decltype(T)::value, decltype(P)::value>), grid,
+                           dim3(DECODE_THREADS), 0, (hipStream_t)stream, p);
+    });
     return tt_check_launch();
 }
 
@@ -903,11 +862,6 @@ long long tt_make_geom(const tt_render_cfg* cfg, long long wave_slots, TileGeom*
     return n_blocks * g->n_chunks;
 }
 
-int tt_launch_march_fwd(const float* rays_d, const float* t_starts, const float* t_ends, const tt_render_cfg* cfg,
-                        const float* sdf, const float* sdf_grad, const float* features, float* opacity, float* depth,
-                        float* rgb_fg, float* z_variance, float* normal_acc, float* weights, float* trans,
-                        hipStream_t stream);
-
 extern "C" int tt_render_fwd(const float* packed, const tt_mlp_weights* w, const float* rays_o, const float* rays_d,
                              const float* t_starts, const float* t_ends, const tt_render_cfg* cfg, float* opacity,
                              float* depth, float* rgb_fg, float* z_variance, float* normal_acc, float* weights,
@@ -918,39 +872,22 @@ extern "C" int tt_render_fwd(const float* packed, const tt_mlp_weights* w, const
         !normal_acc || !weights || !trans || !sdf || !sdf_grad || !features)
         return TT_ERR_BAD_ARG;
     if (!w->w1 || !w->w2 || !w->w3 || !w->v1 || !w->v2 || !w->v3) return TT_ERR_BAD_ARG;
-    int cus = tt_num_cus();
+    const int cus = tt_num_cus();
     if (cus <= 0) return TT_ERR_DEVICE;
     DecodeRaysParams p;
-    p.packed = packed;
-    p.w = to_ptrs(w);
-    p.rays_o = rays_o;
-    p.rays_d = rays_d;
-    p.t_starts = t_starts;
-    p.t_ends = t_ends;
-    p.cfg = *cfg;
-#ifdef TT_TUNING
-    if (const char* e = getenv("TT_DEBUG_FLAGS")) p.cfg.flags |= (int)strtol(e, nullptr, 0);
-#endif
+    tt_fill_rays(p, packed, w, rays_o, rays_d, t_starts, t_ends, *cfg);
+    p.cfg.flags |= debug_flags();
     p.sdf = sdf;
     p.sdf_grad = sdf_grad;
     p.features = features;
-    const long long slots = (long long)cus * (DECODE_THREADS / 64);  // one 8-wave workgroup per CU (LDS 93 KB)
-    p.n_items = tt_make_geom(cfg, slots, &p.geom, 1, 12);
-    long long blocks = cus;
-    long long need = (p.n_items + 7) / 8;
-    if (blocks > need) blocks = need;
-    blocks = (blocks + 7) / 8 * 8;
     hipStream_t s = (hipStream_t)stream;
-    if (p.n_items > (1LL << 30)) return TT_ERR_UNSUPPORTED;
-    p.queue = tt_queue_counters(s);
-    if (!p.queue) return TT_ERR_DEVICE;
-    const int prec = tt_prec_of_r(cfg->flags);
-    if (prec == PREC_F32)
-        hipLaunchKernelGGL((k_decode_rays<true, true, PREC_F32>), dim3((unsigned)blocks), dim3(DECODE_THREADS), 0, s, p);
-    else if (prec == PREC_S3)
-        hipLaunchKernelGGL((k_decode_rays<true, true, PREC_S3>), dim3((unsigned)blocks), dim3(DECODE_THREADS), 0, s, p);
-    else
-        hipLaunchKernelGGL((k_decode_rays<true, true, PREC_S2>), dim3((unsigned)blocks), dim3(DECODE_THREADS), 0, s, p);
+    // one 8-wave workgroup per CU (LDS 93 KB)
+    st = tt_plan_queue(cfg, (long long)cus * (DECODE_THREADS / 64), s, &p.geom, &p.n_items, &p.queue, 12);
+    if (st != TT_OK) return st;
+    const dim3 grid((unsigned)tt_persistent_blocks(p.n_items, cus, DECODE_THREADS / 64));
+    tt_dispatch_prec(tt_prec_of_r(cfg->flags), [&](auto P) {
+        hipLaunchKernelGGL((k_decode_rays<true, true, decltype(P)::value>), grid, dim3(DECODE_THREADS), 0, s, p);
+    });
     st = tt_check_launch();
     if (st != TT_OK) return st;
     return tt_launch_march_fwd(rays_d, t_starts, t_ends, cfg, sdf, sdf_grad, features, opacity, depth, rgb_fg,
@@ -970,61 +907,36 @@ extern "C" int tt_decode_rays(const float* packed, const tt_mlp_weights* w, cons
         (need_t && !features) || !tt_qflags_ok(flags))
         return TT_ERR_BAD_ARG;
     if (!w->w1 || !w->w2 || !w->w3 || (need_t && (!w->v1 || !w->v2 || !w->v3))) return TT_ERR_BAD_ARG;
-    int cus = tt_num_cus();
+    const int cus = tt_num_cus();
     if (cus <= 0) return TT_ERR_DEVICE;
     DecodeRaysParams p;
-    p.packed = packed;
-    p.w = to_ptrs(w);
-    p.rays_o = rays_o;
-    p.rays_d = rays_d;
-    p.t_starts = t_starts;
-    p.t_ends = t_ends;
-    p.cfg = *cfg;
+    tt_fill_rays(p, packed, w, rays_o, rays_d, t_starts, t_ends, *cfg);
     p.sdf = sdf;
     p.sdf_grad = sdf_grad;
     p.features = features;
+    hipStream_t s = (hipStream_t)stream;
     const long long slots = (long long)cus * (DECODE_THREADS / 64);
     // The sdf-only decode (the sampler's proposal pass) is so cheap per tile step that an item's ray set-up, its queue pop and
     // its first-touch texel misses show: items of TT_DR_GEO_SAMPLES (64) samples and no minimum number of items per wave slot
     // (round 5 sweep, tools/time_proposal.py / time_training_shapes.py: 256 x 256 x 128 0.837 -> 0.815 ms, the two launches of
     // a PatchRenderer step at the training shape 0.80 -> 0.63 ms; whole-ray items are better still for large launches and
     // worse for the 800-block patch render).
+    int steps_per_item = 12, min_items_per_slot = 8;
     if (!need_n && !need_t) {
         const int sb = cfg->tile_sb > 0 ? cfg->tile_sb : 2;
         const int spi = (TT_DR_GEO_SAMPLES + sb - 1) / sb;
-        p.n_items = tt_make_geom(cfg, slots, &p.geom, 1, spi > 1 ? spi : 1, TT_DR_GEO_MIN_ITEMS);
-    } else {
-        p.n_items = tt_make_geom(cfg, slots, &p.geom, 1, 12);
+        steps_per_item = spi > 1 ? spi : 1;
+        min_items_per_slot = TT_DR_GEO_MIN_ITEMS;
     }
-    long long blocks = cus;
-    long long need = (p.n_items + 7) / 8;
-    if (blocks > need) blocks = need;
-    blocks = (blocks + 7) / 8 * 8;
-    dim3 grid((unsigned)blocks), blk(DECODE_THREADS);
-    hipStream_t s = (hipStream_t)stream;
-    if (p.n_items > (1LL << 30)) return TT_ERR_UNSUPPORTED;
-    p.queue = tt_queue_counters(s);
-    if (!p.queue) return TT_ERR_DEVICE;
+    st = tt_plan_queue(cfg, slots, s, &p.geom, &p.n_items, &p.queue, steps_per_item, min_items_per_slot);
+    if (st != TT_OK) return st;
+    const dim3 grid((unsigned)tt_persistent_blocks(p.n_items, cus, DECODE_THREADS / 64));
     // precision: the query flags if they name one, else the render configuration's
     const int prec = (flags & (TT_Q_EXACT_F32 | TT_Q_SPLIT2 | TT_Q_SPLIT3)) ? tt_prec_of_q(flags) : tt_prec_of_r(cfg->flags);
-#define LAUNCH_DR(N, T)                                                                  \
-    do {                                                                                 \
-        if (prec == PREC_F32)                                                            \
-            hipLaunchKernelGGL((k_decode_rays<N, T, PREC_F32>), grid, blk, 0, s, p);     \
-        else if (prec == PREC_S3)                                                        \
-            hipLaunchKernelGGL((k_decode_rays<N, T, PREC_S3>), grid, blk, 0, s, p);      \
-        else                                                                             \
-            hipLaunchKernelGGL((k_decode_rays<N, T, PREC_S2>), grid, blk, 0, s, p);      \
-    } while (0)
-    if (need_n && need_t)
-        LAUNCH_DR(true, true);
-    else if (need_n)
-        LAUNCH_DR(true, false);
-    else if (need_t)
-        LAUNCH_DR(false, true);
-    else
-        LAUNCH_DR(false, false);
-#undef LAUNCH_DR
+    tt_dispatch(prec, need_n, need_t, [&](auto P, auto N, auto T) {
+        hipLaunchKernelGGL((k_decode_rays<decltype(N)::value, decltype(T)::value, decltype(P)::value>), grid,
+                           dim3(DECODE_THREADS), 0, s, p);
+    });
     return tt_check_launch();
 }
 
@@ -1034,41 +946,24 @@ extern "C" int tt_query_field(const float* packed, const tt_mlp_weights* w, cons
                               int64_t n_points, int32_t n_prompts, int32_t views_per_prompt, int32_t plane_h,
                               int32_t plane_w, float radius, float sdf_bias_radius, int32_t flags, float* out_sdf,
                               float* out_deformation, void* stream) {
-    if (!packed || !w || !points || !out_sdf || !out_deformation || n_batch <= 0 || n_points <= 0 || n_prompts <= 0 ||
-        views_per_prompt <= 0)
-        return TT_ERR_BAD_ARG;
-    if (n_batch != n_prompts * views_per_prompt || !(radius > 0.f) || !tt_qflags_ok(flags)) return TT_ERR_BAD_ARG;
-    if (plane_h != plane_w || plane_h <= 0) return TT_ERR_UNSUPPORTED;
+    if (!packed || !w || !points || !out_sdf || !out_deformation) return TT_ERR_BAD_ARG;
+    const int st = tt_validate_points(n_batch, n_points, n_prompts, views_per_prompt, plane_h, plane_w, radius, flags);
+    if (st != TT_OK) return st;
     if (!w->w1 || !w->w2 || !w->w3 || !w->v1 || !w->v2 || !w->v3) return TT_ERR_BAD_ARG;
     QueryFieldParams p;
-    p.packed = packed;
-    p.w = to_ptrs(w);
-    p.points = points;
-    p.n_batch = n_batch;
-    p.n_points = n_points;
-    p.views_per_prompt = views_per_prompt;
-    p.H = plane_h;
-    p.W = plane_w;
-    p.radius = radius;
+    tt_fill_points(p, packed, w, points, n_batch, n_points, views_per_prompt, plane_h, plane_w, radius);
     p.bias_radius = sdf_bias_radius;
     p.out_sdf = out_sdf;
     p.out_def = out_deformation;
-    int cus = tt_num_cus();
+    const int cus = tt_num_cus();
     if (cus <= 0) return TT_ERR_DEVICE;
-    long long n_tiles = ((n_points + TT_TILE - 1) / TT_TILE) * n_batch;
-    const int prec = tt_prec_of_q(flags);
-    const int waves = prec == PREC_S3 ? QueryFieldWaves<PREC_S3>::value : 4;  // per workgroup; 8 waves per CU either way
-    long long blocks = (n_tiles + waves - 1) / waves;
-    if (blocks > (8LL / waves) * cus) blocks = (8LL / waves) * cus;
-    if (prec == PREC_F32)
-        hipLaunchKernelGGL(k_query_field<PREC_F32>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
-    else if (prec == PREC_S3)
-        hipLaunchKernelGGL(k_query_field<PREC_S3>, dim3((unsigned)blocks), dim3(64 * waves), 0, (hipStream_t)stream, p);
-    else
-        hipLaunchKernelGGL(k_query_field<PREC_S2>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
+    tt_dispatch_prec(tt_prec_of_q(flags), [&](auto P) {
+        constexpr int PREC = decltype(P)::value, waves = QueryFieldWaves<PREC>::value;  // per workgroup; 8 waves per CU either way
+        hipLaunchKernelGGL(k_query_field<PREC>, tt_point_blocks(n_points, n_batch, waves, (8LL / waves) * cus),
+                           dim3(64 * waves), 0, (hipStream_t)stream, p);
+    });
     return tt_check_launch();
 }
-
 
 // Eval-mode render: per-ray outputs only, decode and march fused per ray tile, optional early termination.
 extern "C" int tt_render_eval(const float* packed, const tt_mlp_weights* w, const float* rays_o, const float* rays_d,
@@ -1082,16 +977,10 @@ extern "C" int tt_render_eval(const float* packed, const tt_mlp_weights* w, cons
         return TT_ERR_BAD_ARG;
     if (!w->w1 || !w->w2 || !w->w3 || !w->v1 || !w->v2 || !w->v3) return TT_ERR_BAD_ARG;
     if (!(transmittance_eps >= 0.f) || !(weight_eps >= 0.f)) return TT_ERR_BAD_ARG;
-    int cus = tt_num_cus();
+    const int cus = tt_num_cus();
     if (cus <= 0) return TT_ERR_DEVICE;
     RenderEvalParams p;
-    p.packed = packed;
-    p.w = to_ptrs(w);
-    p.rays_o = rays_o;
-    p.rays_d = rays_d;
-    p.t_starts = t_starts;
-    p.t_ends = t_ends;
-    p.cfg = *cfg;
+    tt_fill_rays(p, packed, w, rays_o, rays_d, t_starts, t_ends, *cfg);
     p.cfg.tile_sb = 1;                     // a lane is a ray: 8x4 pixel blocks, one sample index per step
     p.cfg.tile_chunk = cfg->n_samples;     // one work item per ray block (the march is sequential in depth)
     p.eps_T = transmittance_eps;
@@ -1102,22 +991,14 @@ extern "C" int tt_render_eval(const float* packed, const tt_mlp_weights* w, cons
     p.z_var = z_variance;
     p.nacc = normal_acc;
     p.stats = (unsigned long long*)stats;
-    const long long slots = (long long)cus * (DECODE_THREADS / 64);
-    const long long n_items = tt_make_geom(&p.cfg, slots, &p.geom, 1);
-    if (p.geom.n_chunks != 1 || n_items > (1LL << 30)) return TT_ERR_UNSUPPORTED;
-    long long blocks = cus;
-    const long long need = (n_items + 7) / 8;
-    if (blocks > need) blocks = need;
-    blocks = (blocks + 7) / 8 * 8;
     hipStream_t s = (hipStream_t)stream;
-    p.queue = tt_queue_counters(s);
-    if (!p.queue) return TT_ERR_DEVICE;
-    const int prec = tt_prec_of_r(cfg->flags);
-    if (prec == PREC_F32)
-        hipLaunchKernelGGL(k_render_eval<PREC_F32>, dim3((unsigned)blocks), dim3(DECODE_THREADS), 0, s, p);
-    else if (prec == PREC_S3)
-        hipLaunchKernelGGL(k_render_eval<PREC_S3>, dim3((unsigned)blocks), dim3(DECODE_THREADS), 0, s, p);
-    else
-        hipLaunchKernelGGL(k_render_eval<PREC_S2>, dim3((unsigned)blocks), dim3(DECODE_THREADS), 0, s, p);
+    long long n_items;
+    st = tt_plan_queue(&p.cfg, (long long)cus * (DECODE_THREADS / 64), s, &p.geom, &n_items, &p.queue);
+    if (st != TT_OK) return st;
+    if (p.geom.n_chunks != 1) return TT_ERR_UNSUPPORTED;
+    const dim3 grid((unsigned)tt_persistent_blocks(n_items, cus, DECODE_THREADS / 64));
+    tt_dispatch_prec(tt_prec_of_r(cfg->flags), [&](auto P) {
+        hipLaunchKernelGGL(k_render_eval<decltype(P)::value>, grid, dim3(DECODE_THREADS), 0, s, p);
+    });
     return tt_check_launch();
 }

@@ -25,6 +25,7 @@
 // floats).  `W^T x` products use a second image built from the transposed matrix.
 #pragma once
 #include "tt_device.h"
+#include "tt_host.h"  // enum PREC_*
 
 typedef _Float16 h8_t __attribute__((ext_vector_type(8)));
 typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
@@ -482,8 +483,7 @@ __device__ __forceinline__ void mv16t(const float* img_f, int col0, const float 
 //   chain, 1/16 of the fp16 pipe's rate) from plain fp32 weight images -- the A/B reference of both split modes.
 // The fp32 image of a matrix occupies the same LDS floats as its (hi, mid) split-fp16 image (row stride K + 4), so the
 // kernels' LDS maps do not depend on F32-vs-split; PREC_S3 appends the images of the third terms (`lo` pointers below,
-// ignored by the other two modes).
-enum { PREC_S2 = 0, PREC_F32 = 1, PREC_S3 = 2 };
+// ignored by the other two modes).  The PREC_* values themselves: tt_host.h.
 template <int PREC>
 struct PrecNT {
     static constexpr int value = PREC == PREC_S3 ? 3 : 2;

@@ -14,7 +14,7 @@
 // and reduces them against q / ebar, so no Jacobian is ever materialised.  No atomics: a point is owned by one lane pair.
 #include "tt_device.h"
 #include "tt_mfma16.h"
-#include "tt_host.h"
+#include "tt_launch.h"
 
 #define PX_W1 0
 #define PX_W2 (PX_W1 + IMG16_FLOATS(64, 32))
@@ -252,44 +252,22 @@ extern "C" int tt_points_bwd_x(const float* packed, const tt_mlp_weights* w, con
                                int64_t n_points, int32_t n_prompts, int32_t views_per_prompt, int32_t plane_h,
                                int32_t plane_w, float radius, int32_t flags, const float* g_sdf,
                                const float* g_sdf_grad, const float* g_features, float* grad_points, void* stream) {
-    if (!packed || !w || !points || !grad_points || n_batch <= 0 || n_points <= 0 || n_prompts <= 0 ||
-        views_per_prompt <= 0)
-        return TT_ERR_BAD_ARG;
-    if (n_batch != n_prompts * views_per_prompt || !(radius > 0.f)) return TT_ERR_BAD_ARG;
-    if (plane_h != plane_w || plane_h <= 0) return TT_ERR_UNSUPPORTED;
+    if (!packed || !w || !points || !grad_points) return TT_ERR_BAD_ARG;
+    const int st = tt_validate_points(n_batch, n_points, n_prompts, views_per_prompt, plane_h, plane_w, radius, flags);
+    if (st != TT_OK) return st;
     if (!w->w1 || !w->w2 || !w->w3 || (g_features && (!w->v1 || !w->v2 || !w->v3))) return TT_ERR_BAD_ARG;
-    PointsBwdXParams p;
-    p.packed = packed;
-    p.w.w1 = w->w1;
-    p.w.w2 = w->w2;
-    p.w.w3 = w->w3;
-    p.w.v1 = w->v1;  // read only when g_features is given
-    p.w.v2 = w->v2;
-    p.w.v3 = w->v3;
-    p.points = points;
-    p.n_batch = n_batch;
-    p.n_points = n_points;
-    p.views_per_prompt = views_per_prompt;
-    p.H = plane_h;
-    p.W = plane_w;
-    p.radius = radius;
+    PointsBwdXParams p;  // (w.v1..v3 are read only when g_features is given)
+    tt_fill_points(p, packed, w, points, n_batch, n_points, views_per_prompt, plane_h, plane_w, radius);
     p.g_sdf = g_sdf;
     p.g_sdf_grad = g_sdf_grad;
     p.g_feat = g_features;
     p.grad_points = grad_points;
     const int cus = tt_num_cus();
     if (cus <= 0) return TT_ERR_DEVICE;
-    const long long n_tiles = ((n_points + TT_TILE - 1) / TT_TILE) * n_batch;
-    if (!tt_qflags_ok(flags)) return TT_ERR_BAD_ARG;
-    const int prec = tt_prec_of_q(flags);
-    const int waves = prec == PREC_F32 ? PointsBwdXWaves<PREC_F32>::value : PointsBwdXWaves<PREC_S3>::value;
-    long long blocks = (n_tiles + waves - 1) / waves;
-    if (blocks > cus) blocks = cus;
-    if (prec == PREC_F32)
-        hipLaunchKernelGGL(k_points_bwd_x<PREC_F32>, dim3((unsigned)blocks), dim3(64 * waves), 0, (hipStream_t)stream, p);
-    else if (prec == PREC_S3)
-        hipLaunchKernelGGL(k_points_bwd_x<PREC_S3>, dim3((unsigned)blocks), dim3(64 * waves), 0, (hipStream_t)stream, p);
-    else
-        hipLaunchKernelGGL(k_points_bwd_x<PREC_S2>, dim3((unsigned)blocks), dim3(64 * waves), 0, (hipStream_t)stream, p);
+    tt_dispatch_prec(tt_prec_of_q(flags), [&](auto P) {
+        constexpr int PREC = decltype(P)::value, waves = PointsBwdXWaves<PREC>::value;
+        hipLaunchKernelGGL(k_points_bwd_x<PREC>, tt_point_blocks(n_points, n_batch, waves, cus), dim3(64 * waves), 0,
+                           (hipStream_t)stream, p);
+    });
     return tt_check_launch();
 }
