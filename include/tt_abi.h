@@ -479,8 +479,9 @@ int tt_mc_bwd(const float* level, const float* deformation, int32_t res, float i
 
 /* ---- rasterize / interpolate / antialias (tt_raster.hip): the drop-in for nvdiffrast ----
  * Replaces dr.rasterize, dr.interpolate and dr.antialias as NVDiffRasterizerContext calls them
- * (threestudio/utils/rasterize.py; generative_space_mesh_rasterize_renderer.py:137-295).  Instance mode only: one
+ * (threestudio/utils/rasterize.py; generative_space_mesh_rasterize_renderer.py:137-295).  Instance mode: one
  * topology tri (T,3) int32 shared by B >= 1 views of clip-space positions pos (B,V,4); every tensor contiguous, fp32.
+ * Range mode (the tt_*_range_* entries, below) renders different meshes in one call.
  * T = 0 and V = 0 are legal (zero outputs, zero gradients).  T >= TT_RAST_MAX_TRIS is TT_ERR_BAD_ARG (tri + 1 is
  * stored as a float).  A pointer may be NULL only where the count it is indexed by is 0 (pos: V, tri / topology: T).
  * A triangle with an index outside [0, V) or a repeated index is never rasterized, and interpolate / antialias treat
@@ -525,12 +526,27 @@ int tt_mc_bwd(const float* level, const float* deformation, int32_t res, float i
  *     topology  edge_ofs (3T,2) int32 = (first, count) of the group of triangle edge 3t + k (vertices k, (k+1)%3)
  *               in the list of the 3T edges sorted by (lower, higher) vertex index; edge_tri (3T) int32 = the
  *               triangle of each sorted entry.  It depends on tri only: build it once per mesh (raster.py).
+ *   range mode  nvdiffrast's second batching mode: one vertex buffer pos (V,4) shared by all images, tri (T,3), and
+ *               ranges (B,2) int32 = (first triangle, triangle count) per image.  Image b rasterizes exactly the
+ *               triangles first_b .. first_b + count_b - 1 by the rules above; the id channel holds the GLOBAL
+ *               triangle index + 1 (an index into the whole tri), so depth ties go to the smaller global index.
+ *               count = 0 is legal (an all-zero image, no gradient); ranges may overlap, repeat and come in any
+ *               order; first < 0, count < 0 or first + count > T is TT_ERR_BAD_ARG.  The caller passes the ranges
+ *               twice: ranges_dev (read by the kernels) and ranges_host, the same values in host memory, from which
+ *               the entry point validates them and sizes the work list (n_slots = the sum of the counts) without a
+ *               device round trip.  tt_rast_range_bwd, tt_aa_range_fwd / _bwd read pos (V,4) for every image and
+ *               write grad_pos (V,4), summed over the images.  Interpolation needs no entry of its own: tt_interp_fwd
+ *               / _bwd with attr_batch = 1 on a range-mode rast (global ids) is range-mode interpolation.  Antialias
+ *               takes the topology of the whole tri, and the silhouette test looks at every triangle sharing an edge,
+ *               whatever range it is in (nvdiffrast builds its topology on the whole tri too): meshes that share no
+ *               vertices never interact, meshes that share an edge see each other there.
  * Determinism: rast, interpolate's output, antialias's output and grad_color are gathers (or an order-independent
  * min): bit-identical across launches.  grad_pos (tt_rast_bwd, tt_aa_bwd) and grad_attr use fp32 atomic adds and are
  * NOT bit-reproducible.  Every gradient output is overwritten (zeroed inside).
  * Use: bytes = tt_rast_workspace_bytes(B, T, H, W) (device workspace of tt_rast_fwd: bounding boxes, the int64
  * candidate scan, per-pixel depth keys); no host round trip (the candidate total is read on the device), so the
- * forward is capturable. */
+ * forward is capturable.  Range mode: bytes = tt_rast_range_workspace_bytes(B, n_slots, H, W); tt_rast_range_fwd reads
+ * ranges_host during the call (it may be freed or changed afterwards) and makes no device round trip either. */
 #define TT_RAST_MAX_TRIS (1 << 24)
 int64_t tt_rast_workspace_bytes(int32_t B, int32_t T, int32_t H, int32_t W);
 int tt_rast_fwd(const float* pos, const int32_t* tri, int32_t B, int32_t V, int32_t T, int32_t H, int32_t W,
@@ -548,6 +564,18 @@ int tt_aa_fwd(const float* color, const float* rast, const float* pos, const int
 int tt_aa_bwd(const float* color, const float* rast, const float* pos, const int32_t* tri, const int32_t* edge_ofs,
               const int32_t* edge_tri, const float* grad_out, int32_t B, int32_t V, int32_t T, int32_t H, int32_t W,
               int32_t C, float* grad_color, float* grad_pos, void* stream);
+int64_t tt_rast_range_workspace_bytes(int32_t B, int64_t n_slots, int32_t H, int32_t W);
+int tt_rast_range_fwd(const float* pos, const int32_t* tri, const int32_t* ranges_dev, const int32_t* ranges_host,
+                      int32_t B, int32_t V, int32_t T, int32_t H, int32_t W, void* workspace, float* rast,
+                      void* stream);
+int tt_rast_range_bwd(const float* pos, const int32_t* tri, const float* rast, const float* grad_rast, int32_t B,
+                      int32_t V, int32_t T, int32_t H, int32_t W, float* grad_pos, void* stream);
+int tt_aa_range_fwd(const float* color, const float* rast, const float* pos, const int32_t* tri,
+                    const int32_t* edge_ofs, const int32_t* edge_tri, int32_t B, int32_t V, int32_t T, int32_t H,
+                    int32_t W, int32_t C, float* out, void* stream);
+int tt_aa_range_bwd(const float* color, const float* rast, const float* pos, const int32_t* tri,
+                    const int32_t* edge_ofs, const int32_t* edge_tri, const float* grad_out, int32_t B, int32_t V,
+                    int32_t T, int32_t H, int32_t W, int32_t C, float* grad_color, float* grad_pos, void* stream);
 
 /* ---- mesh regularisers and outlier removal (tt_mesh.hip): threestudio Mesh.normal_consistency / laplacian /
  * remove_outlier (threestudio/models/mesh.py:31-95,255-308) ----

@@ -5,7 +5,9 @@ HIP events, warm-up and repeats.  Each raster op forward and backward is timed o
 the renderer's forward and forward + backward on all 8 prompts.  Per-kernel durations: run it under
 `rocprofv3 --kernel-trace --stats` (profiles/mesh_render_512.json).
 
-usage: python tools/time_mesh_render.py [--reps 20] [--out profiles/mesh_render_512.json]"""
+--batch-prompts times the renderer with `batch_prompts = True` (all prompts through one set of range-mode launches).
+
+usage: python tools/time_mesh_render.py [--reps 20] [--batch-prompts] [--out profiles/mesh_render_512.json]"""
 import argparse
 import json
 import math
@@ -50,6 +52,7 @@ def main():
     ap.add_argument("--prompts", type=int, default=8)
     ap.add_argument("--views", type=int, default=4)
     ap.add_argument("--res", type=int, default=512)
+    ap.add_argument("--batch-prompts", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -61,6 +64,7 @@ def main():
     b = tt.find(cfg["background_type"])(cfg["background"]).to(dev)
     r = tt.find(rcfg["renderer_type"])(rcfg["renderer"], geometry=g, material=m, background=b).to(dev)
     r.train()
+    r.batch_prompts = a.batch_prompts
     P, NV, H = a.prompts, a.views, a.res
     rays_o, rays_d, c2w, dist = synthetic.make_cameras(P * NV, H, H, fovy_deg=60.0)
     mvp = (perspective(60.0, 1.0)[None] @ torch.inverse(c2w)).to(dev)
@@ -71,7 +75,8 @@ def main():
               c2w=c2w.to(dev))
 
     res = {"prompts": P, "views_per_prompt": NV, "height": H, "width": H,
-           "isosurface_resolution": r.cfg.isosurface_resolution, "deformable_grid": True}
+           "isosurface_resolution": r.cfg.isosurface_resolution, "deformable_grid": True,
+           "batch_prompts": bool(a.batch_prompts)}
     # the raster ops on prompt 0's mesh and views
     with torch.no_grad():
         mesh = r.isosurface(cache)[0]

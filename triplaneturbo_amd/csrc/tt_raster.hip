@@ -1,11 +1,13 @@
 // tt_raster.hip -- differentiable triangle rasterization, attribute interpolation and silhouette antialiasing: the
 // drop-in for the three nvdiffrast primitives (CUDA-only) that the reference's mesh renderer calls through
 // NVDiffRasterizerContext (threestudio/utils/rasterize.py; generative_space_mesh_rasterize_renderer.py:137-295).
-// Instance mode only: one topology tri (T,3) shared by B views of clip-space positions pos (B,V,4).  The contract
-// (pixel centres, coverage, tie rule, depth test, antialias pairs) is written in include/tt_abi.h.
+// Instance mode: one topology tri (T,3) shared by B views of clip-space positions pos (B,V,4).  Range mode: one
+// vertex buffer pos (V,4) and per image a range (first, count) of tri; the kernels are the same, the work list of the
+// forward is mapped to (image, triangle) by rast_slot and pos is read with a batch stride of 0.  The contract (pixel
+// centres, coverage, tie rule, depth test, antialias pairs) is written in include/tt_abi.h.
 //
-// Rasterize, five launches, no host round trip:
-//   k_rast_setup      per (view, triangle): clip culling and a clamped screen bounding box; its pixel count
+// Rasterize, five launches (range mode: four more for the images' slot prefix), no host round trip:
+//   k_rast_setup      per (image, triangle) slot: clip culling and a clamped screen bounding box; its pixel count
 //   tt_exclusive_scan (tt_scan.h, three launches)    exclusive int64 scan of the counts -> candidate offsets
 //   k_rast_cover      grid-stride over the candidates (triangle, pixel), total read on the device: coverage by the
 //                     homogeneous edge functions, then a 64-bit atomicMin of (ordered z/w bits << 32 | tri) into the
@@ -28,32 +30,77 @@ struct RastLayout {
     int4* bbox;
     long long *offs, *bsum;
     unsigned long long* keys;
-    long long n, bytes;  // (view, triangle) slots, size of the workspace
+    long long *prefix, *psum;  // range mode only
+    long long n, bytes;        // (image, triangle) slots, size of the workspace
 };
 
-// the workspace sections (tt_rast_workspace_bytes); base may be null for the size alone
-static RastLayout rast_layout(void* base, int B, int T, int H, int W) {
+// the workspace sections (tt_rast_workspace_bytes, tt_rast_range_workspace_bytes) for n slots (instance mode: B T,
+// range mode: the sum of the counts); base may be null for the size alone
+static RastLayout rast_layout(void* base, int B, long long n, int H, int W, bool range) {
     TtCarver c{(char*)base};
     RastLayout l;
-    l.n = (long long)B * T;
+    l.n = n;
     l.bbox = c.take<int4>(l.n);                                 // [n] clamped screen box of the slot
     l.offs = c.take<long long>(l.n + 1);                        // [n + 1] pixel counts, scanned in place; [n] = total
     l.bsum = c.take<long long>(tt_xscan_blocks(l.n) + 1);       // scratch of the scan
     l.keys = c.take<unsigned long long>((long long)B * H * W);  // per pixel: ordered z/w bits << 32 | tri, min wins
+    l.prefix = l.psum = nullptr;
+    if (range) {
+        l.prefix = c.take<long long>((long long)B + 1);         // [B + 1] the images' counts, scanned in place
+        l.psum = c.take<long long>(tt_xscan_blocks(B) + 1);     // scratch of that scan
+    }
     l.bytes = c.bytes();
     return l;
 }
 
+// The forward's work list: slot i -> image b, triangle t (an index into the whole tri) and the batch index pb of its
+// positions.  Instance mode (prefix null): the B T (view, triangle) pairs, b = i / T, t = i % T, pb = b.  Range mode:
+// image b owns the slots prefix[b] <= i < prefix[b + 1], t = first_b + (i - prefix[b]), pb = 0.
+struct RastSlots {
+    const long long* prefix;  // (B + 1) exclusive scan of the ranges' counts
+    const int* ranges;        // (B, 2) = (first, count)
+    int B, T;
+};
+
+// false: no such slot (only if the device ranges differ from the ones the host sized the work list by)
+__device__ __forceinline__ bool rast_slot(const RastSlots& m, long long i, int& b, int& t, int& pb) {
+    if (!m.prefix) {
+        b = (int)(i / m.T);
+        t = (int)(i % m.T);
+        pb = b;
+        return true;
+    }
+    // the image with prefix[b] <= i < prefix[b + 1] (the last of equal prefixes: a non-empty range)
+    int lo = 0, hi = m.B - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (m.prefix[mid] <= i) lo = mid;
+        else hi = mid - 1;
+    }
+    const long long local = i - m.prefix[lo];
+    b = lo;
+    pb = 0;
+    t = m.ranges[2 * lo] + (int)local;
+    return local < (long long)m.ranges[2 * lo + 1] && (unsigned)t < (unsigned)m.T;
+}
+
+// range mode: the images' counts as the input of the prefix scan
+__global__ __launch_bounds__(RS_BLOCK) void k_rast_range_counts(const int* __restrict__ ranges, int B,
+                                                                long long* __restrict__ cnt) {
+    const int b = blockIdx.x * RS_BLOCK + threadIdx.x;
+    if (b < B) cnt[b] = ranges[2 * b + 1] > 0 ? ranges[2 * b + 1] : 0;
+}
+
 __global__ __launch_bounds__(RS_BLOCK) void k_rast_setup(const float* __restrict__ pos, const int* __restrict__ tri,
-                                                         int B, int V, int T, int H, int W, int4* __restrict__ bbox,
-                                                         long long* __restrict__ cnt) {
+                                                         RastSlots m, long long n, int V, int H, int W,
+                                                         int4* __restrict__ bbox, long long* __restrict__ cnt) {
     const long long i = (long long)blockIdx.x * RS_BLOCK + threadIdx.x;
-    if (i >= (long long)B * T) return;
-    const int b = (int)(i / T), t = (int)(i % T);
+    if (i >= n) return;
+    int b, t, pb;
     TriSetup s;
     long long area = 0;
     int4 bb = make_int4(0, 0, -1, -1);
-    if (tri_setup(pos, tri, b, t, V, s)) {
+    if (rast_slot(m, i, b, t, pb) && tri_setup(pos, tri, pb, t, V, s)) {
         // culled if all vertices lie beyond one clip plane, or all w <= 0
         bool cull = (s.w[0] <= 0.f && s.w[1] <= 0.f && s.w[2] <= 0.f);
         cull |= (s.x[0] > s.w[0] && s.x[1] > s.w[1] && s.x[2] > s.w[2]);
@@ -98,13 +145,14 @@ __device__ __forceinline__ unsigned ordered_bits(float f) {
 }
 
 __global__ __launch_bounds__(RS_BLOCK) void k_rast_cover(const float* __restrict__ pos, const int* __restrict__ tri,
-                                                         int V, int T, int H, int W, const int4* __restrict__ bbox,
+                                                         RastSlots m, int V, int H, int W,
+                                                         const int4* __restrict__ bbox,
                                                          const long long* __restrict__ offs, long long n,
                                                          unsigned long long* __restrict__ keys) {
     const long long total = offs[n];  // read on the device: no host round trip, capturable
     const long long stride = (long long)gridDim.x * RS_BLOCK;
     for (long long c = (long long)blockIdx.x * RS_BLOCK + threadIdx.x; c < total; c += stride) {
-        // the (view, triangle) slot i with offs[i] <= c < offs[i + 1] (the last of equal offsets: a non-empty box)
+        // the (image, triangle) slot i with offs[i] <= c < offs[i + 1] (the last of equal offsets: a non-empty box)
         long long lo = 0, hi = n - 1;
         while (lo < hi) {
             const long long mid = (lo + hi + 1) >> 1;
@@ -116,9 +164,9 @@ __global__ __launch_bounds__(RS_BLOCK) void k_rast_cover(const float* __restrict
         const int bw = bb.z - bb.x + 1;
         const int px = bb.x + (int)(local % bw), py = bb.y + (int)(local / bw);
         if (px > bb.z || py > bb.w) continue;  // cannot happen for a consistent scan; keeps every store in bounds
-        const int b = (int)(lo / T), t = (int)(lo % T);
+        int b, t, pb;
         TriSetup s;
-        if (!tri_setup(pos, tri, b, t, V, s)) continue;
+        if (!rast_slot(m, lo, b, t, pb) || !tri_setup(pos, tri, pb, t, V, s)) continue;
         float u, v, zw, S;
         if (!tri_cover(s, pix_ndc(px, W), pix_ndc_lo(px, W), pix_ndc(py, H), pix_ndc_lo(py, H), u, v, zw, S)) continue;
         const unsigned long long key = ((unsigned long long)ordered_bits(zw) << 32) | (unsigned)t;
@@ -126,8 +174,8 @@ __global__ __launch_bounds__(RS_BLOCK) void k_rast_cover(const float* __restrict
     }
 }
 
-__global__ __launch_bounds__(RS_BLOCK) void k_rast_resolve(const float* __restrict__ pos, const int* __restrict__ tri,
-                                                           int B, int V, int T, int H, int W,
+__global__ __launch_bounds__(RS_BLOCK) void k_rast_resolve(const float* __restrict__ pos, int pos_batch,
+                                                           const int* __restrict__ tri, int B, int V, int T, int H, int W,
                                                            const unsigned long long* __restrict__ keys,
                                                            float* __restrict__ rast) {
     const long long p = (long long)blockIdx.x * RS_BLOCK + threadIdx.x;
@@ -141,7 +189,8 @@ __global__ __launch_bounds__(RS_BLOCK) void k_rast_resolve(const float* __restri
         const int t = (int)(unsigned)(key & 0xffffffffu);
         TriSetup s;
         float u, v, zw, S;
-        if (t < T && tri_setup(pos, tri, b, t, V, s) && tri_cover(s, pix_ndc(px, W), pix_ndc_lo(px, W), pix_ndc(py, H), pix_ndc_lo(py, H), u, v, zw, S))
+        if (t < T && tri_setup(pos, tri, pos_batch == 1 ? 0 : b, t, V, s) &&
+            tri_cover(s, pix_ndc(px, W), pix_ndc_lo(px, W), pix_ndc(py, H), pix_ndc_lo(py, H), u, v, zw, S))
             out = make_float4(u, v, zw, (float)(t + 1));
     }
     reinterpret_cast<float4*>(rast)[p] = out;
@@ -157,8 +206,8 @@ __device__ __forceinline__ int pix_tri(float id, int T) {
     return t >= T ? -1 : t;
 }
 
-__global__ __launch_bounds__(RS_BLOCK) void k_rast_bwd(const float* __restrict__ pos, const int* __restrict__ tri,
-                                                       const float* __restrict__ rast,
+__global__ __launch_bounds__(RS_BLOCK) void k_rast_bwd(const float* __restrict__ pos, int pos_batch,
+                                                       const int* __restrict__ tri, const float* __restrict__ rast,
                                                        const float* __restrict__ grad_rast, int B, int V, int T, int H,
                                                        int W, float* __restrict__ grad_pos) {
     const long long p = (long long)blockIdx.x * RS_BLOCK + threadIdx.x;
@@ -169,11 +218,12 @@ __global__ __launch_bounds__(RS_BLOCK) void k_rast_bwd(const float* __restrict__
     const float4 g = reinterpret_cast<const float4*>(grad_rast)[p];
     if (g.x == 0.f && g.y == 0.f) return;
     const int b = (int)(p / ((long long)H * W));
+    const int pb = pos_batch == 1 ? 0 : b;  // range mode: one vertex buffer, the images' gradients sum in it
     const int rem = (int)(p % ((long long)H * W));
     const int py = rem / W, px = rem % W;
     TriSetup s;
     float u, v, zw, sum;
-    if (!tri_setup(pos, tri, b, t, V, s)) return;
+    if (!tri_setup(pos, tri, pb, t, V, s)) return;
     if (!tri_cover(s, pix_ndc(px, W), pix_ndc_lo(px, W), pix_ndc(py, H), pix_ndc_lo(py, H), u, v, zw, sum)) return;
     const float base = g.x * u + g.y * v;
     float ge[3];  // d loss / d e_k, e_k = (v_i x v_j) . p in cyclic order (u = sign(D) e_0 / sum, v likewise)
@@ -196,7 +246,7 @@ __global__ __launch_bounds__(RS_BLOCK) void k_rast_bwd(const float* __restrict__
     }
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        float* gp = grad_pos + ((long long)b * V + s.idx[k]) * 4;
+        float* gp = grad_pos + ((long long)pb * V + s.idx[k]) * 4;
         atomicAdd(gp + 0, acc[k][0]);
         atomicAdd(gp + 1, acc[k][1]);
         atomicAdd(gp + 3, acc[k][2]);
@@ -275,7 +325,10 @@ struct AaCtx {
     const int* edge_ofs;  // (3T, 2): first sorted slot, count of the edge group of triangle edge 3t + k
     const int* edge_tri;  // (3T): triangle of each sorted slot
     int B, V, T, H, W;
+    int pos_batch;  // B (instance mode) or 1 (range mode: pos (V,4) shared by the images)
 };
+
+__device__ __forceinline__ int aa_pos_batch(const AaCtx& cx, int b) { return cx.pos_batch == 1 ? 0 : b; }
 
 struct AaPair {
     int a_first;  // 1: the occluder's pixel a is the pair's first (left / top) pixel
@@ -286,7 +339,7 @@ struct AaPair {
 
 __device__ __forceinline__ float vtx_pix(float c, float w, int N) { return ((c / w + 1.f) * (float)N) * 0.5f - 0.5f; }
 
-__device__ bool aa_silhouette(const AaCtx& cx, int b, int t, int k, float ot) {
+__device__ bool aa_silhouette(const AaCtx& cx, int pb, int t, int k, float ot) {
     const int slot = 3 * t + k;
     const int first = cx.edge_ofs[2 * slot], cnt = cx.edge_ofs[2 * slot + 1];
     if (first < 0 || cnt < 1 || (long long)first + cnt > 3ll * cx.T) return false;  // malformed topology: no edge
@@ -295,7 +348,7 @@ __device__ bool aa_silhouette(const AaCtx& cx, int b, int t, int k, float ot) {
         const int u = cx.edge_tri[j];
         if (u == t || (unsigned)u >= (unsigned)cx.T) continue;
         other = true;
-        if (tri_orient(cx.pos, cx.tri, b, u, cx.V) * ot < 0.f) return true;
+        if (tri_orient(cx.pos, cx.tri, pb, u, cx.V) * ot < 0.f) return true;
     }
     return !other;
 }
@@ -303,6 +356,7 @@ __device__ bool aa_silhouette(const AaCtx& cx, int b, int t, int k, float ot) {
 // the pair (first, second) of view b, first = the left (horiz) or upper pixel; false: the pair changes nothing
 __device__ bool aa_pair(const AaCtx& cx, int b, int fx, int fy, bool horiz, AaPair& pr) {
     const int sx = fx + (horiz ? 1 : 0), sy = fy + (horiz ? 0 : 1);
+    const int pb = aa_pos_batch(cx, b);
     const long long pf = ((long long)b * cx.H + fy) * cx.W + fx, ps = ((long long)b * cx.H + sy) * cx.W + sx;
     const float4 rf = reinterpret_cast<const float4*>(cx.rast)[pf];
     const float4 rs = reinterpret_cast<const float4*>(cx.rast)[ps];
@@ -317,8 +371,8 @@ __device__ bool aa_pair(const AaCtx& cx, int b, int fx, int fy, bool horiz, AaPa
     if (!tri_indices(cx.tri, t, cx.V, idx)) return false;
     float4 v[3];
 #pragma unroll
-    for (int q = 0; q < 3; ++q) v[q] = vtx(cx.pos, b, cx.V, idx[q]);
-    const float ot = tri_orient(cx.pos, cx.tri, b, t, cx.V);
+    for (int q = 0; q < 3; ++q) v[q] = vtx(cx.pos, pb, cx.V, idx[q]);
+    const float ot = tri_orient(cx.pos, cx.tri, pb, t, cx.V);
     // a's centre along the pair axis, the direction to b, and the perpendicular (scanline) coordinate
     const float al = horiz ? (float)(a_first ? fx : sx) : (float)(a_first ? fy : sy);
     const float dir = a_first ? 1.f : -1.f;
@@ -338,7 +392,7 @@ __device__ bool aa_pair(const AaCtx& cx, int b, int fx, int fy, bool horiz, AaPa
         const float lc = l0 + r * (l1 - l0);
         const float s = (lc - al) * dir;
         if (!(s >= 0.f && s < best)) continue;
-        if (!aa_silhouette(cx, b, t, k, ot)) continue;
+        if (!aa_silhouette(cx, pb, t, k, ot)) continue;
         best = s;
         bk = k;
     }
@@ -394,6 +448,7 @@ __global__ __launch_bounds__(RS_BLOCK) void k_aa_bwd(AaCtx cx, const float* __re
     const int b = (int)(p / ((long long)cx.H * cx.W));
     const int rem = (int)(p % ((long long)cx.H * cx.W));
     const int y = rem / cx.W, x = rem % cx.W;
+    const int pb = aa_pos_batch(cx, b);
     const float* gs = grad_out + p * C;
     float* gc = grad_color + p * C;
     for (int c = 0; c < C; ++c) gc[c] = gs[c];
@@ -425,7 +480,7 @@ __global__ __launch_bounds__(RS_BLOCK) void k_aa_bwd(AaCtx cx, const float* __re
         int idx[3];
         tri_indices(cx.tri, pr.t, cx.V, idx);  // valid: aa_pair checked it
         const int i0 = idx[pr.k], i1 = idx[(pr.k + 1) % 3];
-        const float4 e0 = vtx(cx.pos, b, cx.V, i0), e1 = vtx(cx.pos, b, cx.V, i1);
+        const float4 e0 = vtx(cx.pos, pb, cx.V, i0), e1 = vtx(cx.pos, pb, cx.V, i1);
         const int Nl = horiz ? cx.W : cx.H, Np = horiz ? cx.H : cx.W;
         const float cl0 = horiz ? e0.x : e0.y, cl1 = horiz ? e1.x : e1.y;
         const float cp0 = horiz ? e0.y : e0.x, cp1 = horiz ? e1.y : e1.x;
@@ -442,8 +497,8 @@ __global__ __launch_bounds__(RS_BLOCK) void k_aa_bwd(AaCtx cx, const float* __re
         const float gcl0 = g_l0 * hl / e0.w, gcl1 = g_l1 * hl / e1.w;
         const float gcp0 = g_p0 * hp / e0.w, gcp1 = g_p1 * hp / e1.w;
         const float gw0 = -(gcl0 * cl0 + gcp0 * cp0) / e0.w, gw1 = -(gcl1 * cl1 + gcp1 * cp1) / e1.w;
-        float* gp0 = grad_pos + ((long long)b * cx.V + i0) * 4;
-        float* gp1 = grad_pos + ((long long)b * cx.V + i1) * 4;
+        float* gp0 = grad_pos + ((long long)pb * cx.V + i0) * 4;
+        float* gp1 = grad_pos + ((long long)pb * cx.V + i1) * 4;
         atomicAdd(gp0 + (horiz ? 0 : 1), gcl0);
         atomicAdd(gp0 + (horiz ? 1 : 0), gcp0);
         atomicAdd(gp0 + 3, gw0);
@@ -465,45 +520,94 @@ static unsigned rs_blocks(long long n) { return (unsigned)((n + RS_BLOCK - 1) / 
 
 extern "C" int64_t tt_rast_workspace_bytes(int32_t B, int32_t T, int32_t H, int32_t W) {
     if (!rs_dims_ok(B, 0, T, H, W)) return TT_ERR_BAD_ARG;
-    return rast_layout(nullptr, B, T, H, W).bytes;
+    return rast_layout(nullptr, B, (long long)B * T, H, W, false).bytes;
+}
+
+// the launches of both modes behind the layout; range mode (l.prefix) first scans the images' counts
+static int rast_fwd_launch(const float* pos, const int* tri, const int* ranges, const RastLayout& l, int B, int V, int T,
+                           int H, int W, float* rast, hipStream_t st) {
+    const long long npix = (long long)B * H * W;
+    if (l.n == 0 || V == 0) {
+        if (hipMemsetAsync(rast, 0, (size_t)npix * 16, st) != hipSuccess) return TT_ERR_LAUNCH;
+        return tt_check_launch();
+    }
+    if (hipMemsetAsync(l.keys, 0xff, (size_t)npix * 8, st) != hipSuccess) return TT_ERR_LAUNCH;
+    if (l.prefix) {
+        hipLaunchKernelGGL(k_rast_range_counts, dim3(rs_blocks(B)), dim3(RS_BLOCK), 0, st, ranges, B, l.prefix);
+        tt_exclusive_scan<long long>(l.prefix, B, l.prefix, l.psum, l.prefix + B, st);
+    }
+    const RastSlots m{l.prefix, ranges, B, T};
+    hipLaunchKernelGGL(k_rast_setup, dim3(rs_blocks(l.n)), dim3(RS_BLOCK), 0, st, pos, tri, m, l.n, V, H, W, l.bbox,
+                       l.offs);
+    // the counts were written into offs[]: scanned in place, the total behind them
+    tt_exclusive_scan<long long>(l.offs, l.n, l.offs, l.bsum, l.offs + l.n, st);
+    int cus = tt_num_cus();
+    if (cus <= 0) cus = 256;
+    hipLaunchKernelGGL(k_rast_cover, dim3((unsigned)cus * 8), dim3(RS_BLOCK), 0, st, pos, tri, m, V, H, W, l.bbox,
+                       l.offs, l.n, l.keys);
+    hipLaunchKernelGGL(k_rast_resolve, dim3(rs_blocks(npix)), dim3(RS_BLOCK), 0, st, pos, l.prefix ? 1 : B, tri, B, V,
+                       T, H, W, l.keys, rast);
+    return tt_check_launch();
 }
 
 extern "C" int tt_rast_fwd(const float* pos, const int32_t* tri, int32_t B, int32_t V, int32_t T, int32_t H,
                            int32_t W, void* workspace, float* rast, void* stream) {
     if (!rs_dims_ok(B, V, T, H, W) || !workspace || !rast || (V > 0 && !pos) || (T > 0 && !tri))
         return TT_ERR_BAD_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    const long long npix = (long long)B * H * W;
-    if (T == 0 || V == 0) {
-        if (hipMemsetAsync(rast, 0, (size_t)npix * 16, st) != hipSuccess) return TT_ERR_LAUNCH;
-        return tt_check_launch();
+    return rast_fwd_launch(pos, (const int*)tri, nullptr, rast_layout(workspace, B, (long long)B * T, H, W, false), B,
+                           V, T, H, W, rast, (hipStream_t)stream);
+}
+
+// the slots of B ranges (first, count) over T triangles, read on the host; -1: a range leaves [0, T]
+static long long range_slots(const int32_t* ranges_host, int B, int T) {
+    long long n = 0;
+    for (int b = 0; b < B; ++b) {
+        const long long first = ranges_host[2 * b], count = ranges_host[2 * b + 1];
+        if (first < 0 || count < 0 || first + count > T) return -1;
+        n += count;
     }
-    const RastLayout l = rast_layout(workspace, B, T, H, W);
-    if (hipMemsetAsync(l.keys, 0xff, (size_t)npix * 8, st) != hipSuccess) return TT_ERR_LAUNCH;
-    hipLaunchKernelGGL(k_rast_setup, dim3(rs_blocks(l.n)), dim3(RS_BLOCK), 0, st, pos, (const int*)tri, B, V, T, H, W,
-                       l.bbox, l.offs);
-    // the counts were written into offs[]: scanned in place, the total behind them
-    tt_exclusive_scan<long long>(l.offs, l.n, l.offs, l.bsum, l.offs + l.n, st);
-    int cus = tt_num_cus();
-    if (cus <= 0) cus = 256;
-    hipLaunchKernelGGL(k_rast_cover, dim3((unsigned)cus * 8), dim3(RS_BLOCK), 0, st, pos, (const int*)tri, V, T, H, W,
-                       l.bbox, l.offs, l.n, l.keys);
-    hipLaunchKernelGGL(k_rast_resolve, dim3(rs_blocks(npix)), dim3(RS_BLOCK), 0, st, pos, (const int*)tri, B, V, T, H,
-                       W, l.keys, rast);
+    return n;
+}
+
+extern "C" int64_t tt_rast_range_workspace_bytes(int32_t B, int64_t n_slots, int32_t H, int32_t W) {
+    if (!rs_dims_ok(B, 0, 0, H, W) || n_slots < 0 || n_slots >= (1ll << 40)) return TT_ERR_BAD_ARG;
+    return rast_layout(nullptr, B, n_slots, H, W, true).bytes;
+}
+
+extern "C" int tt_rast_range_fwd(const float* pos, const int32_t* tri, const int32_t* ranges_dev,
+                                 const int32_t* ranges_host, int32_t B, int32_t V, int32_t T, int32_t H, int32_t W,
+                                 void* workspace, float* rast, void* stream) {
+    if (!rs_dims_ok(B, V, T, H, W) || !workspace || !rast || !ranges_dev || !ranges_host || (V > 0 && !pos) ||
+        (T > 0 && !tri))
+        return TT_ERR_BAD_ARG;
+    const long long n = range_slots(ranges_host, B, T);
+    if (n < 0 || n >= (1ll << 40)) return TT_ERR_BAD_ARG;
+    return rast_fwd_launch(pos, (const int*)tri, (const int*)ranges_dev, rast_layout(workspace, B, n, H, W, true), B,
+                           V, T, H, W, rast, (hipStream_t)stream);
+}
+
+static int rast_bwd_launch(const float* pos, int pos_batch, const int32_t* tri, const float* rast,
+                           const float* grad_rast, int B, int V, int T, int H, int W, float* grad_pos, void* stream) {
+    if (!rs_dims_ok(B, V, T, H, W) || !rast || !grad_rast || (V > 0 && (!pos || !grad_pos)) || (T > 0 && !tri))
+        return TT_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (V == 0) return TT_OK;
+    if (hipMemsetAsync(grad_pos, 0, (size_t)pos_batch * V * 16, st) != hipSuccess) return TT_ERR_LAUNCH;
+    if (T == 0) return tt_check_launch();
+    hipLaunchKernelGGL(k_rast_bwd, dim3(rs_blocks((long long)B * H * W)), dim3(RS_BLOCK), 0, st, pos, pos_batch,
+                       (const int*)tri, rast, grad_rast, B, V, T, H, W, grad_pos);
     return tt_check_launch();
 }
 
 extern "C" int tt_rast_bwd(const float* pos, const int32_t* tri, const float* rast, const float* grad_rast, int32_t B,
                            int32_t V, int32_t T, int32_t H, int32_t W, float* grad_pos, void* stream) {
-    if (!rs_dims_ok(B, V, T, H, W) || !rast || !grad_rast || (V > 0 && (!pos || !grad_pos)) || (T > 0 && !tri))
-        return TT_ERR_BAD_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (V == 0) return TT_OK;
-    if (hipMemsetAsync(grad_pos, 0, (size_t)B * V * 16, st) != hipSuccess) return TT_ERR_LAUNCH;
-    if (T == 0) return tt_check_launch();
-    hipLaunchKernelGGL(k_rast_bwd, dim3(rs_blocks((long long)B * H * W)), dim3(RS_BLOCK), 0, st, pos, (const int*)tri,
-                       rast, grad_rast, B, V, T, H, W, grad_pos);
-    return tt_check_launch();
+    return rast_bwd_launch(pos, B, tri, rast, grad_rast, B, V, T, H, W, grad_pos, stream);
+}
+
+extern "C" int tt_rast_range_bwd(const float* pos, const int32_t* tri, const float* rast, const float* grad_rast,
+                                 int32_t B, int32_t V, int32_t T, int32_t H, int32_t W, float* grad_pos,
+                                 void* stream) {
+    return rast_bwd_launch(pos, 1, tri, rast, grad_rast, B, V, T, H, W, grad_pos, stream);
 }
 
 extern "C" int tt_interp_fwd(const float* attr, int32_t attr_batch, const float* rast, const int32_t* tri, int32_t B,
@@ -537,26 +641,54 @@ static bool aa_args_ok(const float* color, const float* rast, const float* pos, 
            (T == 0 || (tri && edge_ofs && edge_tri));
 }
 
-extern "C" int tt_aa_fwd(const float* color, const float* rast, const float* pos, const int32_t* tri,
-                         const int32_t* edge_ofs, const int32_t* edge_tri, int32_t B, int32_t V, int32_t T, int32_t H,
-                         int32_t W, int32_t C, float* out, void* stream) {
+static int aa_fwd_launch(const float* color, const float* rast, const float* pos, int pos_batch, const int32_t* tri,
+                         const int32_t* edge_ofs, const int32_t* edge_tri, int B, int V, int T, int H, int W, int C,
+                         float* out, void* stream) {
     if (!aa_args_ok(color, rast, pos, tri, edge_ofs, edge_tri, B, V, T, H, W, C) || !out) return TT_ERR_BAD_ARG;
-    const AaCtx cx{rast, pos, (const int*)tri, (const int*)edge_ofs, (const int*)edge_tri, B, V, T, H, W};
+    const AaCtx cx{rast, pos, (const int*)tri, (const int*)edge_ofs, (const int*)edge_tri, B, V, T, H, W, pos_batch};
     hipLaunchKernelGGL(k_aa_fwd, dim3(rs_blocks((long long)B * H * W)), dim3(RS_BLOCK), 0, (hipStream_t)stream, cx,
                        color, C, out);
     return tt_check_launch();
+}
+
+static int aa_bwd_launch(const float* color, const float* rast, const float* pos, int pos_batch, const int32_t* tri,
+                         const int32_t* edge_ofs, const int32_t* edge_tri, const float* grad_out, int B, int V, int T,
+                         int H, int W, int C, float* grad_color, float* grad_pos, void* stream) {
+    if (!aa_args_ok(color, rast, pos, tri, edge_ofs, edge_tri, B, V, T, H, W, C) || !grad_out || !grad_color)
+        return TT_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (grad_pos && V > 0 && hipMemsetAsync(grad_pos, 0, (size_t)pos_batch * V * 16, st) != hipSuccess)
+        return TT_ERR_LAUNCH;
+    const AaCtx cx{rast, pos, (const int*)tri, (const int*)edge_ofs, (const int*)edge_tri, B, V, T, H, W, pos_batch};
+    hipLaunchKernelGGL(k_aa_bwd, dim3(rs_blocks((long long)B * H * W)), dim3(RS_BLOCK), 0, st, cx, color, C, grad_out,
+                       grad_color, V > 0 ? grad_pos : nullptr);
+    return tt_check_launch();
+}
+
+extern "C" int tt_aa_fwd(const float* color, const float* rast, const float* pos, const int32_t* tri,
+                         const int32_t* edge_ofs, const int32_t* edge_tri, int32_t B, int32_t V, int32_t T, int32_t H,
+                         int32_t W, int32_t C, float* out, void* stream) {
+    return aa_fwd_launch(color, rast, pos, B, tri, edge_ofs, edge_tri, B, V, T, H, W, C, out, stream);
+}
+
+extern "C" int tt_aa_range_fwd(const float* color, const float* rast, const float* pos, const int32_t* tri,
+                               const int32_t* edge_ofs, const int32_t* edge_tri, int32_t B, int32_t V, int32_t T,
+                               int32_t H, int32_t W, int32_t C, float* out, void* stream) {
+    return aa_fwd_launch(color, rast, pos, 1, tri, edge_ofs, edge_tri, B, V, T, H, W, C, out, stream);
 }
 
 extern "C" int tt_aa_bwd(const float* color, const float* rast, const float* pos, const int32_t* tri,
                          const int32_t* edge_ofs, const int32_t* edge_tri, const float* grad_out, int32_t B,
                          int32_t V, int32_t T, int32_t H, int32_t W, int32_t C, float* grad_color, float* grad_pos,
                          void* stream) {
-    if (!aa_args_ok(color, rast, pos, tri, edge_ofs, edge_tri, B, V, T, H, W, C) || !grad_out || !grad_color)
-        return TT_ERR_BAD_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (grad_pos && V > 0 && hipMemsetAsync(grad_pos, 0, (size_t)B * V * 16, st) != hipSuccess) return TT_ERR_LAUNCH;
-    const AaCtx cx{rast, pos, (const int*)tri, (const int*)edge_ofs, (const int*)edge_tri, B, V, T, H, W};
-    hipLaunchKernelGGL(k_aa_bwd, dim3(rs_blocks((long long)B * H * W)), dim3(RS_BLOCK), 0, st, cx, color, C, grad_out,
-                       grad_color, V > 0 ? grad_pos : nullptr);
-    return tt_check_launch();
+    return aa_bwd_launch(color, rast, pos, B, tri, edge_ofs, edge_tri, grad_out, B, V, T, H, W, C, grad_color,
+                         grad_pos, stream);
+}
+
+extern "C" int tt_aa_range_bwd(const float* color, const float* rast, const float* pos, const int32_t* tri,
+                               const int32_t* edge_ofs, const int32_t* edge_tri, const float* grad_out, int32_t B,
+                               int32_t V, int32_t T, int32_t H, int32_t W, int32_t C, float* grad_color,
+                               float* grad_pos, void* stream) {
+    return aa_bwd_launch(color, rast, pos, 1, tri, edge_ofs, edge_tri, grad_out, B, V, T, H, W, C, grad_color,
+                         grad_pos, stream);
 }

@@ -7,7 +7,7 @@ plumbing between the kernels (normal rotation, lerps, disparity) stays torch, as
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Any, Dict, List, Optional, Union
+from typing import Any, Callable, Dict, List, NamedTuple, Optional, Union
 
 import torch
 import torch.nn.functional as F
@@ -17,6 +17,24 @@ from .isosurface import DiffMarchingCubeHelper, Mesh, scale_tensor
 from .registry import BaseModule, C, register
 
 Tensor = torch.Tensor
+
+
+class _GBuffer(NamedTuple):
+    """What the raster stage hands one prompt's shading: (n_view,H,W,.) images of its views."""
+    rast: Tensor              # (u, v, z/w, id); only `id > 0` is used behind the raster stage
+    depth: Tensor             # clip w
+    normal: Tensor            # interpolated v_nrm, not normalized
+    pos: Optional[Tensor]     # interpolated v_pos (render_rgb)
+
+
+class _PreAA(NamedTuple):
+    """An output image that still has to go through antialias (per prompt, or all prompts' at once)."""
+    img: Tensor
+    detach: bool  # rendered from a fixed-up empty field
+
+    def resolve(self, aa: Callable[[Tensor], Tensor]) -> Tensor:
+        out = aa(self.img)
+        return out.detach() if self.detach else out
 
 
 @register("generative-space-mesh-rasterize-renderer")
@@ -53,6 +71,9 @@ class GenerativeSpaceMeshRasterizeRenderer(BaseModule):
         self.sdf_grad_shrink = C(c.sdf_grad_shrink, 0, 0)
         self.def_grad_shrink = C(c.def_grad_shrink, 0, 0)
         self.empty_flag = False
+        # an extra the reference does not have (so not a Config field): in training, rasterize, interpolate and
+        # antialias every prompt's views in one range-mode call each instead of once per prompt
+        self.batch_prompts = False
         # follow InstantMesh (reference :97-107): a positive shell and a negative centre for an empty field
         R = c.isosurface_resolution
         v = torch.zeros([R] * 3, dtype=torch.bool)
@@ -92,36 +113,17 @@ class GenerativeSpaceMeshRasterizeRenderer(BaseModule):
         def keep(t: Tensor) -> Tensor:
             return t.detach() if is_empty else t
 
-        out_list = []
-        for batch_idx, mesh in enumerate(mesh_list):
+        batched = self.batch_prompts and self.training
+        if batched:
+            gbuffers, aa_all = self._raster_batched(mesh_list, mvp_mtx, num_views_per_batch, height, width, render_rgb)
+
+        def shade(batch_idx: int, mesh: Mesh, g: _GBuffer) -> Dict[str, Any]:
+            """One prompt's images from its G-buffer; a _PreAA entry still wants its antialias."""
             sl = slice(batch_idx * num_views_per_batch, (batch_idx + 1) * num_views_per_batch)
-            v_pos_clip = self.ctx.vertex_transform(mesh.v_pos, mvp_mtx[sl])
-            tri = mesh.t_pos_idx
-            topo = raster.mesh_topology(mesh)
-
-            if self.training:
-                rast, _ = self.ctx.rasterize(v_pos_clip, tri, (height, width))
-                gb_feat, _ = self.ctx.interpolate(v_pos_clip, rast, tri)
-                depth = gb_feat[..., -2:-1]
-            else:  # about 40 views: rasterize 4 at a time (reference :145-156)
-                rast_list, depth_list = [], []
-                n_views_per_rasterize = 4
-                for i in range(0, v_pos_clip.shape[0], n_views_per_rasterize):
-                    r, _ = self.ctx.rasterize(v_pos_clip[i:i + n_views_per_rasterize], tri, (height, width))
-                    rast_list.append(r)
-                    gb_feat, _ = self.ctx.interpolate(v_pos_clip[i:i + n_views_per_rasterize], r, tri)
-                    depth_list.append(gb_feat[..., -2:-1])
-                rast = torch.cat(rast_list, dim=0)
-                depth = torch.cat(depth_list, dim=0)
-
-            def aa(img: Tensor) -> Tensor:
-                return self.ctx.antialias(img, rast, v_pos_clip, tri, topology=topo)
-
-            mask = rast[..., 3:] > 0
+            depth = g.depth
+            mask = g.rast[..., 3:] > 0
             if mask.sum() == 0:  # no visible points: the first view's pixels stand in (reference :160-163)
                 mask[:1] = True
-
-            mask_aa = aa(mask.float())
 
             # disparity, as required by RichDreamer
             sqrt3 = torch.sqrt(3 * torch.ones(1, device=camera_distances.device))
@@ -130,15 +132,13 @@ class GenerativeSpaceMeshRasterizeRenderer(BaseModule):
             disparity_tmp = depth.clamp_max(far)
             disparity_norm = ((far - disparity_tmp) / (far - near)).clamp(0, 1)
             disparity_norm = torch.lerp(torch.zeros_like(depth), disparity_norm, mask.float())
-            disparity_norm = aa(disparity_norm)
 
-            out = {"opacity": mask_aa if not is_empty else mask.detach(), "mesh": mesh, "depth": keep(depth),
-                   "disparity": keep(disparity_norm)}
+            out = {"opacity": _PreAA(mask.float(), False) if not is_empty else mask.detach(), "mesh": mesh,
+                   "depth": keep(depth), "disparity": _PreAA(disparity_norm, is_empty)}
 
-            gb_normal, _ = self.ctx.interpolate_one(mesh.v_nrm, rast, tri)
-            gb_normal = F.normalize(gb_normal, dim=-1)
+            gb_normal = F.normalize(g.normal, dim=-1)
             gb_normal_aa = torch.lerp(torch.zeros_like(gb_normal), (gb_normal + 1.0) / 2.0, mask.float())
-            out["comp_normal"] = aa(gb_normal_aa)  # in [0, 1]
+            out["comp_normal"] = _PreAA(gb_normal_aa, False)  # in [0, 1]
 
             if self.cfg.normal_direction == "camera":
                 bg_normal = 0.5 * torch.ones_like(gb_normal)
@@ -151,15 +151,17 @@ class GenerativeSpaceMeshRasterizeRenderer(BaseModule):
                 flip_x[0, 0] = -1
                 gb_normal_cam = (gb_normal_cam @ flip_x[None, None, None, ...]).squeeze(-2)
                 gb_normal_cam = (F.normalize(gb_normal_cam, dim=-1) + 1.0) / 2.0
-                out["comp_normal_cam_vis"] = keep(aa(torch.lerp(bg_normal, gb_normal_cam, mask.float())))
-                out["comp_normal_cam_vis_white"] = keep(aa(torch.lerp(bg_normal_white, gb_normal_cam, mask.float())))
+                out["comp_normal_cam_vis"] = _PreAA(torch.lerp(bg_normal, gb_normal_cam, mask.float()), is_empty)
+                out["comp_normal_cam_vis_white"] = _PreAA(torch.lerp(bg_normal_white, gb_normal_cam, mask.float()),
+                                                          is_empty)
             elif self.cfg.normal_direction == "front":
                 bg_normal_white = torch.ones_like(gb_normal)
                 c2w_front = c2w[batch_idx * num_views_per_batch][None, ...].repeat(num_views_per_batch, 1, 1)
                 rotate_front = torch.inverse(c2w_front)[:, :3, :3]
                 gb_normal_cam = (gb_normal[..., None, :] @ rotate_front.permute(0, 2, 1)[..., None, None, :, :])
                 gb_normal_cam = (F.normalize(gb_normal_cam.squeeze(-2), dim=-1) + 1.0) / 2.0
-                out["comp_normal_cam_vis_white"] = keep(aa(torch.lerp(bg_normal_white, gb_normal_cam, mask.float())))
+                out["comp_normal_cam_vis_white"] = _PreAA(torch.lerp(bg_normal_white, gb_normal_cam, mask.float()),
+                                                          is_empty)
 
             if render_rgb:
                 if torch.is_tensor(space_cache):
@@ -167,7 +169,7 @@ class GenerativeSpaceMeshRasterizeRenderer(BaseModule):
                 else:  # hyper net: Dict[str, List[Tensor]]
                     space_cache_slice = {k: [w[batch_idx:batch_idx + 1] for w in v] for k, v in space_cache.items()}
                 selector = mask[..., 0]
-                gb_pos, _ = self.ctx.interpolate_one(mesh.v_pos, rast, tri)
+                gb_pos = g.pos
                 gb_viewdirs = F.normalize(gb_pos - camera_positions[sl, None, None, :], dim=-1)
                 gb_light_positions = light_positions[sl, None, None, :].expand(-1, height, width, -1)
                 positions = gb_pos[selector]
@@ -202,19 +204,86 @@ class GenerativeSpaceMeshRasterizeRenderer(BaseModule):
                 else:
                     gb_rgb_bg = self.background(dirs=view_dirs)
 
-                gb_rgb = torch.lerp(gb_rgb_bg, gb_rgb_fg, mask.float())
-                out["comp_rgb"] = keep(aa(gb_rgb))
+                out["comp_rgb"] = _PreAA(torch.lerp(gb_rgb_bg, gb_rgb_fg, mask.float()), is_empty)
                 out["comp_rgb_bg"] = keep(gb_rgb_bg)
+            return out
 
-            out_list.append(out)
+        out_list = []
+        for batch_idx, mesh in enumerate(mesh_list):
+            if batched:
+                out_list.append(shade(batch_idx, mesh, gbuffers[batch_idx]))
+                continue
+            sl = slice(batch_idx * num_views_per_batch, (batch_idx + 1) * num_views_per_batch)
+            g, aa = self._raster_prompt(mesh, mvp_mtx[sl], height, width, render_rgb)
+            out = shade(batch_idx, mesh, g)
+            out_list.append({k: v.resolve(aa) if isinstance(v, _PreAA) else v for k, v in out.items()})
 
         out = {}
         for key in out_list[0].keys():
-            if key not in ["mesh", "sdf_grad", "sdf"]:
-                out[key] = torch.concat([o[key] for o in out_list], dim=0)
+            vals = [o[key] for o in out_list]
+            if key in ["mesh", "sdf_grad", "sdf"]:
+                out[key] = vals
+            elif isinstance(vals[0], _PreAA):  # batched: every prompt's image through one antialias
+                out[key] = _PreAA(torch.concat([v.img for v in vals], dim=0), vals[0].detach).resolve(aa_all)
             else:
-                out[key] = [o[key] for o in out_list]
+                out[key] = torch.concat(vals, dim=0)
         return out
+
+    def _raster_prompt(self, mesh: Mesh, mvp_mtx: Tensor, height: int, width: int, render_rgb: bool):
+        """The raster stage of one prompt in instance mode: its G-buffer and its antialias."""
+        v_pos_clip = self.ctx.vertex_transform(mesh.v_pos, mvp_mtx)
+        tri = mesh.t_pos_idx
+        topo = raster.mesh_topology(mesh)
+        if self.training:
+            rast, _ = self.ctx.rasterize(v_pos_clip, tri, (height, width))
+            gb_feat, _ = self.ctx.interpolate(v_pos_clip, rast, tri)
+            depth = gb_feat[..., -2:-1]
+        else:  # about 40 views: rasterize 4 at a time (reference :145-156)
+            rast_list, depth_list = [], []
+            n_views_per_rasterize = 4
+            for i in range(0, v_pos_clip.shape[0], n_views_per_rasterize):
+                r, _ = self.ctx.rasterize(v_pos_clip[i:i + n_views_per_rasterize], tri, (height, width))
+                rast_list.append(r)
+                gb_feat, _ = self.ctx.interpolate(v_pos_clip[i:i + n_views_per_rasterize], r, tri)
+                depth_list.append(gb_feat[..., -2:-1])
+            rast = torch.cat(rast_list, dim=0)
+            depth = torch.cat(depth_list, dim=0)
+        gb_normal, _ = self.ctx.interpolate_one(mesh.v_nrm, rast, tri)
+        gb_pos = self.ctx.interpolate_one(mesh.v_pos, rast, tri)[0] if render_rgb else None
+
+        def aa(img: Tensor) -> Tensor:
+            return self.ctx.antialias(img, rast, v_pos_clip, tri, topology=topo)
+
+        return _GBuffer(rast, depth, gb_normal, gb_pos), aa
+
+    def _raster_batched(self, mesh_list: List[Mesh], mvp_mtx: Tensor, n_view: int, height: int, width: int,
+                        render_rgb: bool):
+        """The raster stage of all prompts in range mode (batch_prompts): every (prompt, view) image is one range of
+        one packed vertex buffer, so one rasterize, one interpolate per attribute and, later, one antialias per
+        output serve the whole step.  Returns the per-prompt G-buffers and the antialias of the (P n_view) images."""
+        pos, tri, topo, nrm, v_pos = [], [], [], [], []
+        for batch_idx, mesh in enumerate(mesh_list):
+            # the looped path's call, so the clip positions have its bits
+            clip = self.ctx.vertex_transform(mesh.v_pos, mvp_mtx[batch_idx * n_view:(batch_idx + 1) * n_view])
+            pos += [clip[v] for v in range(n_view)]
+            tri += [mesh.t_pos_idx] * n_view
+            topo += [raster.mesh_topology(mesh)] * n_view
+            nrm += [mesh.v_nrm] * n_view
+            v_pos += [mesh.v_pos] * n_view
+        pk = raster.pack_ranges(pos, tri, topo)
+        rast, _ = self.ctx.rasterize(pk.pos, pk.tri, (height, width), ranges=pk.ranges)
+        depth = self.ctx.interpolate(pk.pos, rast, pk.tri)[0][..., -2:-1]
+        gb_normal, _ = self.ctx.interpolate(torch.cat(nrm), rast, pk.tri)
+        gb_pos = self.ctx.interpolate(torch.cat(v_pos), rast, pk.tri)[0] if render_rgb else None
+
+        def aa(img: Tensor) -> Tensor:
+            return self.ctx.antialias(img, rast, pk.pos, pk.tri, topology=pk.topology)
+
+        gbuffers = []
+        for batch_idx in range(len(mesh_list)):
+            sl = slice(batch_idx * n_view, (batch_idx + 1) * n_view)
+            gbuffers.append(_GBuffer(rast[sl], depth[sl], gb_normal[sl], gb_pos[sl] if render_rgb else None))
+        return gbuffers, aa
 
     def update_step(self, epoch: int, global_step: int, on_load_weights: bool = False) -> None:
         self.sdf_grad_shrink = C(self.cfg.sdf_grad_shrink, epoch, global_step)

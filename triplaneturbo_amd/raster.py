@@ -1,5 +1,5 @@
 """Differentiable rasterization on the HIP kernels of tt_raster.hip (include/tt_abi.h, "rasterize / interpolate /
-antialias"): the drop-in for nvdiffrast's `rasterize`, `interpolate` and `antialias` in instance mode, and
+antialias"): the drop-in for nvdiffrast's `rasterize`, `interpolate` and `antialias` in instance and range mode, and
 `RasterizerContext`, a drop-in for threestudio's `NVDiffRasterizerContext` (threestudio/utils/rasterize.py).
 
     from triplaneturbo_amd.raster import RasterizerContext
@@ -9,10 +9,17 @@ antialias"): the drop-in for nvdiffrast's `rasterize`, `interpolate` and `antial
     feat, _ = ctx.interpolate(pos, rast, tri)              # (B,H,W,4)
     img = ctx.antialias(color, rast, pos, tri)             # (B,H,W,C)
 
-No rast_db / diff_attrs (mip texturing), no range mode, no texture(); there is no CPU path."""
+Range mode renders different meshes in one call: one vertex buffer (V,4), per image a (first, count) range of tri.
+
+    pk = pack_ranges([pos_a, pos_b], [tri_a, tri_b])       # pos (Va+Vb,4), tri (Ta+Tb,3), ranges (2,2) on the CPU
+    rast, _ = ctx.rasterize(pk.pos, pk.tri, (H, W), ranges=pk.ranges)   # (2,H,W,4), ids index pk.tri
+    feat, _ = ctx.interpolate(pk.pos, rast, pk.tri)        # a 2-D attr (V,C) is shared by the images
+    img = ctx.antialias(color, rast, pk.pos, pk.tri)       # gradients come back (V,4)
+
+No rast_db / diff_attrs (mip texturing), no texture(); there is no CPU path."""
 from __future__ import annotations
 
-from typing import Optional, Tuple, Union
+from typing import List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -67,7 +74,7 @@ class _RasterizeFn(torch.autograd.Function):
         T = tri.shape[0]
         ws = _workspace("tt_rast_workspace_bytes", B, T, H, W, device=pos.device)
         rast = torch.empty((B, H, W, 4), device=pos.device, dtype=torch.float32)
-        _launch("tt_rast_fwd", pos, tri, B, V, T, H, W, ws, rast)
+        _launch("tt_rast_fwd", pos, tri, B, V, T, H, W, ws, rast, label="tt_rast_fwd")
         ctx.save_for_backward(pos, tri, rast)
         return rast
 
@@ -84,13 +91,59 @@ class _RasterizeFn(torch.autograd.Function):
         return g_pos, None, None, None
 
 
-def rasterize(pos: Tensor, tri: Tensor, resolution: Union[int, Tuple[int, int]]) -> Tensor:
+class _RasterizeRangeFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pos, tri, ranges, H, W):
+        V, T, B = pos.shape[0], tri.shape[0], ranges.shape[0]
+        ranges_dev = ranges.to(pos.device)
+        ws = _workspace("tt_rast_range_workspace_bytes", B, int(ranges[:, 1].sum()), H, W, device=pos.device)
+        rast = torch.empty((B, H, W, 4), device=pos.device, dtype=torch.float32)
+        # `ranges` (host memory) is read during the call only
+        _launch("tt_rast_range_fwd", pos, tri, ranges_dev, ranges, B, V, T, H, W, ws, rast, label="tt_rast_range_fwd")
+        ctx.save_for_backward(pos, tri, rast)
+        return rast
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_rast):
+        pos, tri, rast = ctx.saved_tensors
+        if g_rast is None or not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        B, H, W, _ = rast.shape
+        g_pos = torch.empty_like(pos)
+        _launch("tt_rast_range_bwd", pos, tri, rast, g_rast.contiguous(), B, pos.shape[0], tri.shape[0], H, W, g_pos)
+        return g_pos, None, None, None, None
+
+
+def _check_ranges(ranges, n_tri: int) -> Tensor:
+    if not isinstance(ranges, torch.Tensor) or ranges.is_cuda or ranges.dtype != torch.int32:
+        raise ValueError("ranges must be an int32 CPU tensor (B,2) of (first triangle, triangle count) rows")
+    if ranges.dim() != 2 or ranges.shape[1] != 2 or ranges.shape[0] < 1:
+        raise ValueError(f"ranges must be (B,2) with B >= 1, got {tuple(ranges.shape)}")
+    ranges = ranges.contiguous()
+    for b, (first, count) in enumerate(ranges.tolist()):
+        if first < 0 or count < 0 or first + count > n_tri:
+            raise ValueError(f"ranges[{b}] = (first {first}, count {count}) leaves the {n_tri} triangles of tri")
+    return ranges
+
+
+def rasterize(pos: Tensor, tri: Tensor, resolution: Union[int, Tuple[int, int]],
+              ranges: Optional[Tensor] = None) -> Tensor:
     """rast (B,H,W,4) = (u, v, z/w, tri + 1), 0 where empty.  pos (B,V,4) clip space, tri (T,3) int32.
-    Differentiable w.r.t. pos through u, v (dr.rasterize without rast_db)."""
+    Differentiable w.r.t. pos through u, v (dr.rasterize without rast_db).
+    Range mode: pos (V,4) and `ranges`, an int32 CPU tensor (B,2) of (first triangle, triangle count) per image;
+    the id channel indexes the whole tri."""
     H, W = (resolution, resolution) if isinstance(resolution, int) else (int(resolution[0]), int(resolution[1]))
     if H < 1 or W < 1:
         raise ValueError(f"resolution must be positive, got {(H, W)}")
     pos = _chk(pos, "pos")
+    if pos.dim() == 2 or ranges is not None:
+        if pos.dim() != 2 or pos.shape[-1] != 4:
+            raise ValueError(f"ranges go with a 2-D pos (V,4) (range mode), got pos {tuple(pos.shape)}")
+        if ranges is None:
+            raise ValueError("a 2-D pos (V,4) selects range mode and needs ranges (B,2)")
+        tri = _check_tri(tri)
+        return _RasterizeRangeFn.apply(pos, tri, _check_ranges(ranges, tri.shape[0]), H, W)
     if pos.dim() != 3 or pos.shape[-1] != 4 or pos.shape[0] < 1:
         raise ValueError(f"pos must be (B,V,4) with B >= 1, got {tuple(pos.shape)}")
     return _RasterizeFn.apply(pos, _check_tri(tri), H, W)
@@ -122,11 +175,14 @@ class _InterpolateFn(torch.autograd.Function):
 
 def interpolate(attr: Tensor, rast: Tensor, tri: Tensor, rast_db=None, diff_attrs=None) -> Tensor:
     """out (B,H,W,C) = u a0 + v a1 + (1-u-v) a2 (0 where empty); attr (B,V,C) or (1,V,C) (broadcast over views).
-    Differentiable w.r.t. attr and rast (its u, v channels).  rast_db / diff_attrs are not supported."""
+    Differentiable w.r.t. attr and rast (its u, v channels).  rast_db / diff_attrs are not supported.
+    A 2-D attr (V,C) means (1,V,C): with a range-mode rast (global ids) that is range-mode interpolation."""
     if rast_db is not None or diff_attrs is not None:
         raise NotImplementedError("rast_db / diff_attrs (attribute derivatives for mip texturing) are not supported")
     attr = _chk(attr, "attr")
     rast = _check_rast(rast)
+    if attr.dim() == 2:
+        attr = attr[None]
     if attr.dim() != 3 or attr.shape[0] not in (1, rast.shape[0]) or attr.shape[2] < 1:
         raise ValueError(f"attr must be (B,V,C) or (1,V,C) with C >= 1, got {tuple(attr.shape)} for B={rast.shape[0]}")
     return _InterpolateFn.apply(attr, rast, _check_tri(tri))
@@ -136,9 +192,10 @@ class _AntialiasFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, color, rast, pos, tri, edge_ofs, edge_tri):
         B, H, W, C = color.shape
-        V = pos.shape[1]
+        V = pos.shape[-2]
         out = torch.empty_like(color)
-        _launch("tt_aa_fwd", color, rast, pos, tri, edge_ofs, edge_tri, B, V, tri.shape[0], H, W, C, out)
+        _launch("tt_aa_fwd" if pos.dim() == 3 else "tt_aa_range_fwd", color, rast, pos, tri, edge_ofs, edge_tri, B, V,
+                tri.shape[0], H, W, C, out)
         ctx.save_for_backward(color, rast, pos, tri, edge_ofs, edge_tri)
         return out
 
@@ -149,11 +206,11 @@ class _AntialiasFn(torch.autograd.Function):
         if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[2]):
             return (None,) * 6
         B, H, W, C = color.shape
-        V = pos.shape[1]
+        V = pos.shape[-2]
         g_color = torch.empty_like(color)
         g_pos = torch.empty_like(pos) if ctx.needs_input_grad[2] else None
-        _launch("tt_aa_bwd", color, rast, pos, tri, edge_ofs, edge_tri, g_out.contiguous(), B, V, tri.shape[0], H, W, C,
-                g_color, g_pos)
+        _launch("tt_aa_bwd" if pos.dim() == 3 else "tt_aa_range_bwd", color, rast, pos, tri, edge_ofs, edge_tri,
+                g_out.contiguous(), B, V, tri.shape[0], H, W, C, g_color, g_pos)
         return (g_color if ctx.needs_input_grad[0] else None), None, g_pos, None, None, None
 
 
@@ -161,17 +218,19 @@ def antialias(color: Tensor, rast: Tensor, pos: Tensor, tri: Tensor,
               topology: Optional[Tuple[Tensor, Tensor]] = None) -> Tensor:
     """Analytic silhouette antialiasing (Laine et al. 2020, section 4.3; tt_abi.h "antialias"): color (B,H,W,C),
     rast from rasterize(pos, tri), pos (B,V,4).  Differentiable w.r.t. color and pos (none to rast).  `topology`
-    = edge_topology(tri), computed here when not given."""
+    = edge_topology(tri), computed here when not given.  Range mode: pos (V,4), rast from rasterize(pos, tri, ranges=..);
+    the topology is that of the whole tri, so only meshes that share vertices see each other's edges."""
     color = _chk(color, "color")
     rast = _check_rast(rast)
     pos = _chk(pos, "pos")
     tri = _check_tri(tri)
     if color.dim() != 4 or tuple(color.shape[:3]) != tuple(rast.shape[:3]):
         raise ValueError(f"color must be (B,H,W,C) matching rast {tuple(rast.shape)}, got {tuple(color.shape)}")
-    if pos.dim() != 3 or pos.shape[0] != rast.shape[0] or pos.shape[2] != 4:
-        raise ValueError(f"pos must be (B,V,4) with B={rast.shape[0]}, got {tuple(pos.shape)}")
+    if pos.dim() == 2 and pos.shape[1] != 4 or pos.dim() != 2 and (
+            pos.dim() != 3 or pos.shape[0] != rast.shape[0] or pos.shape[2] != 4):
+        raise ValueError(f"pos must be (B,V,4) with B={rast.shape[0]}, or (V,4) in range mode, got {tuple(pos.shape)}")
     if topology is None:
-        topology = edge_topology(tri, pos.shape[1])
+        topology = edge_topology(tri, pos.shape[-2])
     edge_ofs = _chk(topology[0], "edge_ofs", (tri.shape[0] * 3, 2), dtype=torch.int32)
     edge_tri = _chk(topology[1], "edge_tri", (tri.shape[0] * 3,), dtype=torch.int32)
     return _AntialiasFn.apply(color, rast, pos, tri, edge_ofs, edge_tri)
@@ -184,6 +243,47 @@ def mesh_topology(mesh) -> Tuple[Tensor, Tensor]:
         topo = edge_topology(mesh.t_pos_idx.int(), mesh.v_pos.shape[0])
         mesh._aa_topology = topo
     return topo
+
+
+class PackedRanges(NamedTuple):
+    """pack_ranges' result: the arguments of a range-mode rasterize / interpolate / antialias."""
+    pos: Tensor                  # (sum V_i, 4): torch.cat of the pieces, so autograd reaches every one
+    tri: Tensor                  # (sum T_i, 3) int32, piece i's indices shifted by vertex_offsets[i]
+    ranges: Tensor               # (B,2) int32 on the CPU: (tri_offsets[i], T_i)
+    vertex_offsets: List[int]    # first row of piece i in pos
+    tri_offsets: List[int]       # first row of piece i in tri
+    topology: Optional[Tuple[Tensor, Tensor]]  # edge_topology(tri, sum V_i), when the pieces' tables were given
+
+
+def pack_ranges(pos_list: Sequence[Tensor], tri_list: Sequence[Tensor],
+                topologies: Optional[Sequence[Tuple[Tensor, Tensor]]] = None) -> PackedRanges:
+    """One image per piece: B clip-space buffers (V_i,4) and B triangle lists (T_i,3) (the same tensor may appear
+    several times) as one range-mode batch.  With the pieces' edge_topology tables, the table of the concatenation is
+    assembled by offsetting them (no sort): the pieces share no vertices and the sorted edge list is ordered by
+    (lower, higher) vertex index and stable, so it is the pieces' lists one after the other."""
+    n = len(pos_list)
+    if n < 1 or n != len(tri_list) or (topologies is not None and len(topologies) != n):
+        raise ValueError("pack_ranges needs B >= 1 positions, B triangle lists (and B topologies, when given)")
+    v_ofs, t_ofs, tris, rows = [], [], [], []
+    nv = nt = 0
+    for pos, tri in zip(pos_list, tri_list):
+        if pos.dim() != 2 or pos.shape[1] != 4 or tri.dim() != 2 or tri.shape[1] != 3:
+            raise ValueError(f"pack_ranges takes pieces pos (V,4), tri (T,3), got {tuple(pos.shape)}, {tuple(tri.shape)}")
+        v_ofs.append(nv)
+        t_ofs.append(nt)
+        tris.append(tri.int() + nv)
+        rows.append((nt, tri.shape[0]))
+        nv += pos.shape[0]
+        nt += tri.shape[0]
+    if nt >= MAX_TRIS:
+        raise ValueError(f"{nt} triangles: at most {MAX_TRIS - 1} (the id channel is a float)")
+    topology = None
+    if topologies is not None:
+        edge_ofs = torch.cat([torch.stack([ofs[:, 0] + 3 * t0, ofs[:, 1]], 1) for (ofs, _), t0 in zip(topologies, t_ofs)])
+        edge_tri = torch.cat([et + t0 for (_, et), t0 in zip(topologies, t_ofs)])
+        topology = (edge_ofs, edge_tri)
+    return PackedRanges(torch.cat(list(pos_list)), torch.cat(tris), torch.tensor(rows, dtype=torch.int32).reshape(-1, 2),
+                        v_ofs, t_ofs, topology)
 
 
 class RasterizerContext:
@@ -201,9 +301,10 @@ class RasterizerContext:
         verts_homo = torch.cat([verts, torch.ones([verts.shape[0], 1]).to(verts)], dim=-1)
         return torch.matmul(verts_homo, mvp_mtx.permute(0, 2, 1))
 
-    def rasterize(self, pos: Tensor, tri: Tensor, resolution: Union[int, Tuple[int, int]]):
-        """(rast, None): there is no rast_db."""
-        return rasterize(pos.float(), tri.int(), resolution), None
+    def rasterize(self, pos: Tensor, tri: Tensor, resolution: Union[int, Tuple[int, int]],
+                  ranges: Optional[Tensor] = None):
+        """(rast, None): there is no rast_db.  A 2-D pos with `ranges` is range mode."""
+        return rasterize(pos.float(), tri.int(), resolution, ranges=ranges), None
 
     def rasterize_one(self, pos: Tensor, tri: Tensor, resolution: Union[int, Tuple[int, int]]):
         rast, _ = self.rasterize(pos[None, ...], tri, resolution)
@@ -213,9 +314,9 @@ class RasterizerContext:
                   topology: Optional[Tuple[Tensor, Tensor]] = None) -> Tensor:
         tri = tri.int()
         if topology is None:  # one cached table: consecutive calls on the same mesh reuse it
-            key = (tri._version, pos.shape[1])
+            key = (tri._version, pos.shape[-2])
             if tri is not self._topo_tri or key != self._topo_key:
-                self._topo_tri, self._topo_key, self._topo = tri, key, edge_topology(tri, pos.shape[1])
+                self._topo_tri, self._topo_key, self._topo = tri, key, edge_topology(tri, pos.shape[-2])
             topology = self._topo
         return antialias(color.float(), rast, pos.float(), tri, topology)
 
