@@ -64,6 +64,9 @@
  *   tt_uv_* / tt_tex_fill   the mesh exporter's xatlas UV unwrap (threestudio/models/mesh.py:207-249) and cv2.inpaint
  *                           texture padding (multiprompt_mesh_exporter.py:96-107): axis-projection charts, shelf
  *                           packing, an overlap guard, nearest-texel fill.
+ *   tt_tex_fwd / _bwd       nvdiffrast's 2-D `texture` without mipmaps (CUDA-only, un-vendored): sampling map_Kd at
+ *                           interpolated UVs, the step the reference's export render (evaluation/mesh_visualize.py)
+ *                           leaves to external tools.
  */
 #ifndef TT_ABI_H
 #define TT_ABI_H
@@ -576,6 +579,45 @@ int tt_aa_range_fwd(const float* color, const float* rast, const float* pos, con
 int tt_aa_range_bwd(const float* color, const float* rast, const float* pos, const int32_t* tri,
                     const int32_t* edge_ofs, const int32_t* edge_tri, const float* grad_out, int32_t B, int32_t V,
                     int32_t T, int32_t H, int32_t W, int32_t C, float* grad_color, float* grad_pos, void* stream);
+
+/* ---- texture sampling (tt_texture.hip): the drop-in for nvdiffrast's 2-D `texture`, without mipmaps ----
+ * Replaces dr.texture(tex, uv, filter_mode = "nearest" | "linear", boundary_mode = "wrap" | "clamp" | "zero"): with
+ * rasterize, interpolate and antialias above, what a consumer of an exported OBJ + map_Kd needs to put the texture
+ * back on the mesh (triplaneturbo_amd/viewer.py; the reference renders its exports with CUDA-only tools,
+ * evaluation/mesh_visualize.py).  No mip levels, no uv_da / mip_level_bias, no cube maps: minification is the caller's
+ * (the viewer supersamples).  Every tensor contiguous fp32.
+ *   shapes      tex (tex_batch,TH,TW,C), tex_batch = B or 1 (one texture shared by all images); uv (B,H,W,2);
+ *               out (B,H,W,C).  u runs along the width, v along the height; row 0 is at v = 0; texel (i, j) has its
+ *               centre at ((i + 0.5) / TW, (j + 0.5) / TH).
+ *   linear      x = u TW - 0.5, y = v TH - 0.5 (fp32, multiply then subtract); taps floor(x), floor(x) + 1 with weights
+ *               1 - f, f, f = x - floor(x); the same in y; out = the sum over the four taps of wy wx tex.
+ *   nearest     the texel floor(u TW), floor(v TH), weight 1.
+ *   boundary    wrap: tap indices modulo the size (a negative index wraps to the far side; u is first reduced
+ *               to u - trunc(u), which is exact in fp32 and the same sample); clamp: tap indices clamped to
+ *               [0, size - 1]; zero: a tap outside [0, size - 1] has weight 0.
+ *   non-finite  a pixel whose u or v is NaN or +-inf gets out = 0 and contributes no gradient.
+ *   addresses   tap indices are formed as floats (floor, a floating-point modulo for wrap), clamped to [0, size - 1]
+ *               by fmin / fmax and only then converted to integers: no uv value produces an address outside tex.  They
+ *               are exact integers below 2^24, hence TT_TEX_MAX_SIZE.  Element offsets are 64-bit.
+ *   gradient    tt_tex_bwd: grad_out (B,H,W,C) -> grad_tex (tex_batch,TH,TW,C) (summed over the images when tex_batch
+ *               = 1) and grad_uv (B,H,W,2) = (TW d out/dx, TH d out/dy) . grad_out with the tap weights' derivatives
+ *               (-1, +1, times the zero boundary's in-range factors); exactly 0 under nearest.  Either may be NULL.  Every
+ *               element of a given output is written (grad_tex is zeroed inside): the caller does not pre-clear.
+ *   sizes       B H W = 0 is legal and does nothing (tt_tex_bwd still zeroes grad_tex).  TH, TW or C < 1, TH or TW >
+ *               TT_TEX_MAX_SIZE, tex_batch other than 1 or B, an unknown filter or boundary: TT_ERR_BAD_ARG.
+ * Determinism: out and grad_uv are per-pixel gathers, bit-identical across launches; grad_tex uses fp32 atomic adds
+ * (like grad_attr and grad_pos above) and is NOT bit-reproducible.  No workspace, no host round trip: capturable. */
+#define TT_TEX_FILTER_NEAREST 0
+#define TT_TEX_FILTER_LINEAR 1
+#define TT_TEX_BOUNDARY_WRAP 0
+#define TT_TEX_BOUNDARY_CLAMP 1
+#define TT_TEX_BOUNDARY_ZERO 2
+#define TT_TEX_MAX_SIZE 16777216
+int tt_tex_fwd(const float* tex, int32_t tex_batch, const float* uv, int32_t B, int32_t H, int32_t W, int32_t TH,
+               int32_t TW, int32_t C, int32_t filter, int32_t boundary, float* out, void* stream);
+int tt_tex_bwd(const float* tex, int32_t tex_batch, const float* uv, const float* grad_out, int32_t B, int32_t H,
+               int32_t W, int32_t TH, int32_t TW, int32_t C, int32_t filter, int32_t boundary, float* grad_tex,
+               float* grad_uv, void* stream);
 
 /* ---- mesh regularisers and outlier removal (tt_mesh.hip): threestudio Mesh.normal_consistency / laplacian /
  * remove_outlier (threestudio/models/mesh.py:31-95,255-308) ----

@@ -7,6 +7,7 @@ kernels in libtt_hip.so behind the C ABI of include/tt_abi.h.  No CPU fallback.
     Renderer = find("generative-space-sdf-volume-renderer")
     from triplaneturbo_amd.isosurface import DiffMarchingCubeHelper, isosurface, colorize_mesh  # mesh extraction
     from triplaneturbo_amd.export import save_obj      # `multiprompt-mesh-exporter` + OBJ / MTL / texture files
+    from triplaneturbo_amd.viewer import load_obj, turntable   # read the export back, textured turntable renders
 """
 from . import _lib  # noqa: F401
 from . import isosurface  # noqa: F401

@@ -1,12 +1,15 @@
-"""Differentiable rasterization on the HIP kernels of tt_raster.hip (include/tt_abi.h, "rasterize / interpolate /
-antialias"): the drop-in for nvdiffrast's `rasterize`, `interpolate` and `antialias` in instance and range mode, and
-`RasterizerContext`, a drop-in for threestudio's `NVDiffRasterizerContext` (threestudio/utils/rasterize.py).
+"""Differentiable rasterization on the HIP kernels of tt_raster.hip and tt_texture.hip (include/tt_abi.h, "rasterize /
+interpolate / antialias" and "texture sampling"): the drop-in for nvdiffrast's `rasterize`, `interpolate`, `texture`
+and `antialias` in instance and range mode, and `RasterizerContext`, a drop-in for threestudio's
+`NVDiffRasterizerContext` (threestudio/utils/rasterize.py).
 
     from triplaneturbo_amd.raster import RasterizerContext
     ctx = RasterizerContext("cuda", device)
     pos = ctx.vertex_transform(v_pos, mvp)                 # (B,V,4) clip space
     rast, _ = ctx.rasterize(pos, tri, (H, W))              # (B,H,W,4) = (u, v, z/w, tri + 1)
     feat, _ = ctx.interpolate(pos, rast, tri)              # (B,H,W,4)
+    uv, _ = ctx.interpolate(v_tex, rast, t_tex_idx)        # (B,H,W,2)
+    color = ctx.texture(map_Kd[None], uv, boundary_mode="clamp")   # (B,H,W,3); tex (B or 1,TH,TW,C)
     img = ctx.antialias(color, rast, pos, tri)             # (B,H,W,C)
 
 Range mode renders different meshes in one call: one vertex buffer (V,4), per image a (first, count) range of tri.
@@ -16,13 +19,17 @@ Range mode renders different meshes in one call: one vertex buffer (V,4), per im
     feat, _ = ctx.interpolate(pk.pos, rast, pk.tri)        # a 2-D attr (V,C) is shared by the images
     img = ctx.antialias(color, rast, pk.pos, pk.tri)       # gradients come back (V,4)
 
-No rast_db / diff_attrs (mip texturing), no texture(); there is no CPU path."""
+texture() filters "nearest" and "linear" with boundary "wrap", "clamp" and "zero" and is differentiable w.r.t. the
+texture and the UVs.  No mipmaps: no rast_db / diff_attrs, no uv_da / mip_level_bias / mip / max_mip_level, no
+"linear-mipmap-*" filters and no cube maps (each raises NotImplementedError); minification is the caller's
+(triplaneturbo_amd.viewer supersamples).  There is no CPU path."""
 from __future__ import annotations
 
 from typing import List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import torch
 
+from . import _lib
 from .ops import _chk, _launch, _workspace
 
 Tensor = torch.Tensor
@@ -188,6 +195,67 @@ def interpolate(attr: Tensor, rast: Tensor, tri: Tensor, rast_db=None, diff_attr
     return _InterpolateFn.apply(attr, rast, _check_tri(tri))
 
 
+_TEX_FILTERS = {"nearest": _lib.TT_TEX_FILTER_NEAREST, "linear": _lib.TT_TEX_FILTER_LINEAR}
+_TEX_BOUNDARIES = {"wrap": _lib.TT_TEX_BOUNDARY_WRAP, "clamp": _lib.TT_TEX_BOUNDARY_CLAMP,
+                   "zero": _lib.TT_TEX_BOUNDARY_ZERO}
+_TEX_MIP_OPTIONS = ("uv_da", "mip_level_bias", "mip", "max_mip_level")
+
+
+class _TextureFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, tex, uv, filt, boundary):
+        N, TH, TW, C = tex.shape
+        B, H, W, _ = uv.shape
+        out = torch.empty((B, H, W, C), device=tex.device, dtype=torch.float32)
+        _launch("tt_tex_fwd", tex, N, uv, B, H, W, TH, TW, C, filt, boundary, out)
+        ctx.save_for_backward(tex, uv)
+        ctx.modes = (filt, boundary)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out):
+        tex, uv = ctx.saved_tensors
+        N, TH, TW, C = tex.shape
+        B, H, W, _ = uv.shape
+        g_tex = torch.empty_like(tex) if ctx.needs_input_grad[0] else None
+        g_uv = torch.empty_like(uv) if ctx.needs_input_grad[1] else None
+        if g_tex is None and g_uv is None:
+            return None, None, None, None
+        _launch("tt_tex_bwd", tex, N, uv, g_out.contiguous(), B, H, W, TH, TW, C, *ctx.modes, g_tex, g_uv)
+        return g_tex, g_uv, None, None
+
+
+def texture(tex: Tensor, uv: Tensor, filter_mode: str = "linear", boundary_mode: str = "wrap", **kw) -> Tensor:
+    """out (B,H,W,C) = tex (B,TH,TW,C) or (1,TH,TW,C) (shared by the images) sampled at uv (B,H,W,2) (dr.texture
+    without mipmaps; tt_abi.h "texture sampling"): u along the width, v along the height, texel (i, j) centred at
+    ((i + 0.5) / TW, (j + 0.5) / TH).  filter_mode "nearest" | "linear", boundary_mode "wrap" | "clamp" | "zero".
+    Differentiable w.r.t. tex and uv (grad_uv is 0 under "nearest"); a non-finite uv gives 0 and no gradient.
+    The mipmap filters, "cube" and uv_da / mip_level_bias / mip / max_mip_level raise NotImplementedError."""
+    for k, v in kw.items():
+        if k not in _TEX_MIP_OPTIONS:
+            raise TypeError(f"texture() got an unexpected keyword argument {k!r}")
+        if v is not None:
+            raise NotImplementedError(f"{k}: mipmapped texture sampling is not supported (supersample instead)")
+    if filter_mode in ("linear-mipmap-nearest", "linear-mipmap-linear"):
+        raise NotImplementedError(f"filter_mode {filter_mode!r}: mipmapped texture sampling is not supported "
+                                  f"(supersample instead)")
+    if boundary_mode == "cube":
+        raise NotImplementedError("boundary_mode 'cube': cube maps are not supported")
+    if filter_mode not in _TEX_FILTERS:
+        raise ValueError(f"filter_mode must be one of {sorted(_TEX_FILTERS)}, got {filter_mode!r}")
+    if boundary_mode not in _TEX_BOUNDARIES:
+        raise ValueError(f"boundary_mode must be one of {sorted(_TEX_BOUNDARIES)}, got {boundary_mode!r}")
+    tex = _chk(tex, "tex")
+    uv = _chk(uv, "uv")
+    if uv.dim() != 4 or uv.shape[-1] != 2:
+        raise ValueError(f"uv must be (B,H,W,2), got {tuple(uv.shape)}")
+    if tex.dim() != 4 or tex.shape[0] not in (1, uv.shape[0]) or min(tex.shape[1:]) < 1:
+        raise ValueError(f"tex must be (B,TH,TW,C) or (1,TH,TW,C) with TH, TW, C >= 1, got {tuple(tex.shape)} for "
+                         f"B={uv.shape[0]}")
+    return _TextureFn.apply(tex, uv, _TEX_FILTERS[filter_mode], _TEX_BOUNDARIES[boundary_mode])
+
+
 class _AntialiasFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, color, rast, pos, tri, edge_ofs, edge_tri):
@@ -327,3 +395,6 @@ class RasterizerContext:
 
     def interpolate_one(self, attr: Tensor, rast: Tensor, tri: Tensor, rast_db=None, diff_attrs=None):
         return self.interpolate(attr[None, ...], rast, tri, rast_db, diff_attrs)
+
+    def texture(self, tex: Tensor, uv: Tensor, filter_mode: str = "linear", boundary_mode: str = "wrap", **kw) -> Tensor:
+        return texture(tex.float(), uv.float(), filter_mode=filter_mode, boundary_mode=boundary_mode, **kw)

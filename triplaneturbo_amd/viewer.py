@@ -1,0 +1,186 @@
+"""Render what the exporter wrote: read an OBJ + MTL + map_Kd back (`load_obj`, the inverse of export.save_obj) and
+put the texture on the mesh with the HIP rasterizer and texture sampler (`render_textured`, `turntable`) -- the last
+step of the reference's text -> mesh -> images pipeline (evaluation/mesh_visualize.py renders the exported OBJs from a
+few azimuths for CLIPScore, with CUDA-only tools).
+
+    mesh, map_Kd = load_obj("model.obj", device="cuda")
+    imgs = turntable(mesh, map_Kd, n_views=4, height=512, width=512, ssaa=2)      # (4,512,512,3) in [0,1]
+
+    python -m triplaneturbo_amd.viewer model.obj --out views [--num_views 4] [--normal] [--size 512] [--ssaa 2]
+    # views/rgb_0.png ... (and normal_0.png ... with --normal)
+
+Torch plumbing between kernels, like mesh_renderer.py: rasterize, interpolate, texture and antialias are
+triplaneturbo_amd.raster.  The sampler has no mipmaps (tt_abi.h "texture sampling"): a texture that is minified on
+screen is antialiased by supersampling (`ssaa`: render at ssaa x the size, average down), which is this module's only
+answer to minification.  Differentiable w.r.t. map_Kd and mesh.v_pos, so a baked map can be refined against renders."""
+from __future__ import annotations
+
+import argparse
+import math
+import os
+from typing import Optional, Tuple
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from . import export, synthetic
+from .isosurface import Mesh
+from .raster import RasterizerContext
+
+Tensor = torch.Tensor
+
+
+def _read_image(path: str) -> np.ndarray:
+    if os.path.splitext(path)[1].lower() == ".png":
+        return export.read_png(path)
+    try:
+        from PIL import Image
+    except ImportError:
+        raise RuntimeError(f"reading {path!r} needs PIL (Pillow), which is not installed; use map_format='png' "
+                           f"(read with the standard library)") from None
+    return np.asarray(Image.open(path).convert("RGB"))
+
+
+def _map_kd_path(mtl_path: str) -> Optional[str]:
+    if not os.path.exists(mtl_path):
+        return None
+    for line in open(mtl_path):
+        tok = line.split(None, 1)
+        if len(tok) == 2 and tok[0] == "map_Kd":
+            return os.path.join(os.path.dirname(mtl_path), tok[1].strip())
+    return None
+
+
+def load_obj(path: str, device=None) -> Tuple[Mesh, Optional[Tensor]]:
+    """(mesh, map_Kd) from what export.save_obj writes: `v x y z [r g b]` -> v_pos (and v_rgb), `vt u v` -> v_tex with
+    the writer's 1 - v flip undone, `f a/b/c` triangles -> t_pos_idx, t_tex_idx (int32), `mtllib` -> the MTL's map_Kd
+    image as float (N,N,3) in [0,1] (uint8 / 255), None without one.  `vn` lines are read and ignored (Mesh.v_nrm
+    recomputes the normals).  Quads, negative indices and several materials are not read (save_obj never writes them)."""
+    v, rgb, vt, f_pos, f_tex, mtllib = [], [], [], [], [], None
+    with open(path) as fh:
+        for line in fh:
+            tok = line.split()
+            if not tok:
+                continue
+            if tok[0] == "v":
+                v.append([float(x) for x in tok[1:4]])
+                if len(tok) >= 7:
+                    rgb.append([float(x) for x in tok[4:7]])
+            elif tok[0] == "vt":
+                vt.append([float(tok[1]), 1.0 - float(tok[2])])
+            elif tok[0] == "f":
+                if len(tok) != 4:
+                    raise ValueError(f"{path}: only triangles are read, got {line.strip()!r}")
+                corners = [c.split("/") for c in tok[1:]]
+                f_pos.append([int(c[0]) - 1 for c in corners])
+                if all(len(c) > 1 and c[1] for c in corners):
+                    f_tex.append([int(c[1]) - 1 for c in corners])
+            elif tok[0] == "mtllib":
+                mtllib = line.split(None, 1)[1].strip()
+    if rgb and len(rgb) != len(v):
+        raise ValueError(f"{path}: {len(rgb)} of {len(v)} vertices carry a colour")
+    if f_tex and (len(f_tex) != len(f_pos) or not vt):
+        raise ValueError(f"{path}: {len(f_tex)} of {len(f_pos)} faces carry texture indices")
+    if min((i for f in f_pos + f_tex for i in f), default=0) < 0:
+        raise ValueError(f"{path}: negative (relative) indices are not read")
+
+    def tensor(rows, dtype, width):
+        return torch.tensor(rows, dtype=torch.float64 if dtype.is_floating_point else dtype).reshape(-1, width).to(
+            device=device, dtype=dtype)
+
+    mesh = Mesh(tensor(v, torch.float32, 3), tensor(f_pos, torch.int32, 3))
+    if rgb:
+        mesh.set_vertex_color(tensor(rgb, torch.float32, 3))
+    if f_tex:
+        mesh._v_tex, mesh._t_tex_idx = tensor(vt, torch.float32, 2), tensor(f_tex, torch.int32, 3)
+    map_kd = None
+    kd_path = _map_kd_path(os.path.join(os.path.dirname(path), mtllib)) if mtllib else None
+    if kd_path is not None:
+        img = _read_image(kd_path)
+        if img.ndim == 2:
+            img = img[..., None]
+        if img.shape[-1] < 3:
+            img = np.repeat(img[..., :1], 3, axis=-1)
+        map_kd = (torch.from_numpy(np.ascontiguousarray(img[..., :3])).to(torch.float32) / 255.0).to(device=device)
+    return mesh, map_kd
+
+
+def get_projection_matrix(fovy_deg: float, aspect_wh: float, near: float = 0.1, far: float = 1000.0) -> Tensor:
+    """threestudio's get_projection_matrix (threestudio/utils/ops.py): OpenGL perspective with [1,1] negated, so image
+    row 0 is the top."""
+    t = math.tan(math.radians(fovy_deg) / 2)
+    proj = torch.zeros(4, 4)
+    proj[0, 0] = 1 / (t * aspect_wh)
+    proj[1, 1] = -1 / t
+    proj[2, 2] = -(far + near) / (far - near)
+    proj[2, 3] = -2 * far * near / (far - near)
+    proj[3, 2] = -1
+    return proj
+
+
+def render_textured(mesh: Mesh, map_Kd: Optional[Tensor], mvp_mtx: Tensor, height: int, width: int, mode: str = "rgb",
+                    ssaa: int = 1, background: float = 1.0, filter_mode: str = "linear", antialias: bool = True,
+                    ctx: Optional[RasterizerContext] = None) -> Tensor:
+    """(B,height,width,3) views of `mesh` under mvp_mtx (B,4,4).  mode "rgb": map_Kd (TH,TW,3) sampled at the
+    interpolated v_tex (boundary "clamp"), or the interpolated v_rgb when the mesh has no UVs; mode "normal":
+    (normalize(interpolated v_nrm) + 1) / 2.  Then a lerp to `background` by the coverage mask, silhouette antialiasing
+    and, for ssaa > 1, the average of ssaa x ssaa samples per pixel (rendered at ssaa x the size).
+    Differentiable w.r.t. map_Kd and mesh.v_pos."""
+    if mode not in ("rgb", "normal"):
+        raise ValueError(f"mode must be 'rgb' or 'normal', got {mode!r}")
+    if ssaa < 1:
+        raise ValueError(f"ssaa must be >= 1, got {ssaa}")
+    ctx = ctx or RasterizerContext("cuda", mesh.v_pos.device)
+    tri = mesh.t_pos_idx.int()
+    pos = ctx.vertex_transform(mesh.v_pos, mvp_mtx)
+    rast, _ = ctx.rasterize(pos, tri, (ssaa * height, ssaa * width))
+    mask = (rast[..., 3:] > 0).float()
+    if mode == "normal":
+        nrm, _ = ctx.interpolate(mesh.v_nrm[None], rast, tri)
+        color = (F.normalize(nrm, dim=-1) + 1.0) / 2.0
+    elif mesh._v_tex is not None and map_Kd is not None:
+        uv, _ = ctx.interpolate(mesh.v_tex[None], rast, mesh.t_tex_idx)
+        color = ctx.texture(map_Kd[None], uv, filter_mode=filter_mode, boundary_mode="clamp")
+    elif mesh.v_rgb is not None:
+        color, _ = ctx.interpolate(mesh.v_rgb[None], rast, tri)
+    else:
+        raise ValueError("mode 'rgb' needs a mesh with v_tex and a map_Kd, or with vertex colours")
+    img = torch.lerp(torch.full_like(color, float(background)), color, mask)
+    if antialias:
+        img = ctx.antialias(img, rast, pos, tri)
+    if ssaa > 1:
+        img = F.avg_pool2d(img.permute(0, 3, 1, 2), ssaa).permute(0, 2, 3, 1)
+    return img
+
+
+def turntable(mesh: Mesh, map_Kd: Optional[Tensor], n_views: int = 4, elevation_deg: float = 15.0,
+              fovy_deg: float = 40.0, height: int = 512, width: int = 512, **render_kw) -> Tensor:
+    """(n_views,height,width,3): render_textured from n_views equally spaced azimuths at one elevation, cameras from
+    synthetic.make_cameras (z up, looking at the origin)."""
+    _, _, c2w, _ = synthetic.make_cameras(n_views, height, width, fovy_deg=fovy_deg, elevation_deg=elevation_deg)
+    mvp = get_projection_matrix(fovy_deg, width / height)[None] @ torch.inverse(c2w)
+    return render_textured(mesh, map_Kd, mvp.to(mesh.v_pos.device), height, width, **render_kw)
+
+
+def main(argv=None) -> None:
+    ap = argparse.ArgumentParser(prog="python -m triplaneturbo_amd.viewer", description=__doc__.split("\n\n")[0])
+    ap.add_argument("obj", metavar="MODEL.obj")
+    ap.add_argument("--out", required=True, help="directory for rgb_{i}.png (and normal_{i}.png)")
+    ap.add_argument("--num_views", type=int, default=4)
+    ap.add_argument("--normal", action="store_true", help="also write normal_{i}.png")
+    ap.add_argument("--size", type=int, default=512)
+    ap.add_argument("--ssaa", type=int, default=2)
+    a = ap.parse_args(argv)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    mesh, map_kd = load_obj(a.obj, device=dev)
+    os.makedirs(a.out, exist_ok=True)
+    with torch.no_grad():
+        for name in ("rgb", "normal") if a.normal else ("rgb",):
+            imgs = turntable(mesh, map_kd, n_views=a.num_views, height=a.size, width=a.size, mode=name, ssaa=a.ssaa)
+            for i, img in enumerate(imgs.cpu().numpy()):
+                print(export.save_image(os.path.join(a.out, f"{name}_{i}.png"), export._rgb_u8(img)))
+
+
+if __name__ == "__main__":
+    main()
