@@ -106,6 +106,20 @@ def vertex_normals(v_pos, tri):
     return n / np.maximum(np.linalg.norm(n, axis=1, keepdims=True), 1e-12)
 
 
+def vertex_normals_torch(v_pos, tri):
+    """vertex_normals in torch, in the dtype of v_pos and autograd-connected to it (the gradient arbiter of the mesh
+    renderer's oracle); tests/test_mesh_renderer_oracle.py holds it to the numpy one"""
+    import torch
+    tri = torch.as_tensor(np.asarray(tri, dtype=np.int64).reshape(-1, 3))
+    v0, v1, v2 = v_pos[tri[:, 0]], v_pos[tri[:, 1]], v_pos[tri[:, 2]]
+    fn = torch.linalg.cross(v1 - v0, v2 - v0)
+    n = torch.zeros_like(v_pos)
+    for k in range(3):
+        n = n.index_add(0, tri[:, k], fn)
+    n = torch.where((n * n).sum(1, keepdim=True) > 1e-20, n, torch.tensor([0.0, 0.0, 1.0], dtype=n.dtype))
+    return n / n.norm(dim=1, keepdim=True).clamp_min(1e-12)
+
+
 def normal_consistency_of_normals(v_nrm, tri):
     """(loss, d loss / d v_nrm) in float64: mean over edges of 1 - cosine_similarity(n_a, n_b, eps=1e-8)"""
     x = np.asarray(v_nrm, dtype=np.float64)
