@@ -15,7 +15,7 @@ import pytest
 import torch
 
 import triplaneturbo_amd as tt
-from triplaneturbo_amd import ops
+from triplaneturbo_amd import ops, raster
 from triplaneturbo_amd.isosurface import DiffMarchingCubeHelper, Mesh, isosurface
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -46,6 +46,48 @@ def _loss_and_grad(v, t, loss_name, dev):
     loss = getattr(m, loss_name)()
     loss.backward()
     return loss.detach(), m.v_pos.grad
+
+
+def _sphere16(dev):
+    v, t = ops.marching_cubes(torch.from_numpy(M.sphere_field(16)).to(dev))
+    return Mesh(v, t)
+
+
+@pytest.mark.parametrize("which", ["hand", "sphere16"])
+def test_topology_antialias_tables_are_edge_topology(dev, which):
+    """Mesh.topology's antialias tables are raster.edge_topology's: values, dtype, shape and contiguity"""
+    mesh = _mesh(*M.hand_mesh(), dev) if which == "hand" else _sphere16(dev)
+    got = mesh.topology.antialias_tables
+    want = raster.edge_topology(mesh.t_pos_idx.int(), mesh.v_pos.shape[0])
+    assert want[0].shape[0] == 3 * mesh.t_pos_idx.shape[0] > 0
+    for g, w in zip(got, want):
+        assert torch.equal(g, w) and g.dtype == w.dtype == torch.int32
+        assert g.is_contiguous() and w.is_contiguous()
+    assert mesh.topology.antialias_tables is got  # derived once and kept
+
+
+def test_one_face_edge_sort_serves_every_consumer(dev, monkeypatch):
+    """torch.sort calls of a mesh that is rendered and regularised: the shared face-edge sort, and the neighbour
+    CSR's once the Laplacian asks for it (three before the antialias tables moved into MeshTopology)"""
+    mesh = _sphere16(dev)
+    assert not mesh.requires_grad and mesh.t_pos_idx.shape[0] > 0
+    calls = []
+    real_sort = torch.sort
+
+    def counting_sort(*args, **kwargs):
+        calls.append(1)
+        return real_sort(*args, **kwargs)
+
+    monkeypatch.setattr(torch, "sort", counting_sort)
+    mesh.topology.antialias_tables
+    assert len(calls) == 1
+    mesh.laplacian()
+    assert len(calls) == 2
+    mesh.normal_consistency()
+    mesh.edges
+    assert mesh.remove_outlier(0.01) is not mesh
+    mesh.topology.antialias_tables
+    assert len(calls) == 2
 
 
 @pytest.mark.parametrize("name", NAMES)

@@ -11,7 +11,7 @@ import pytest
 import torch
 
 import triplaneturbo_amd as tt
-from triplaneturbo_amd import synthetic
+from triplaneturbo_amd import raster, synthetic
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from test_gpu_raster import perspective  # noqa: E402
@@ -97,6 +97,33 @@ def test_analytic_sphere(dev):
     bmask = vo["opacity"].reshape(n, H, W) > 0.5
     iou = (a & bmask).sum().item() / (a | bmask).sum().item()
     assert iou > 0.98, iou
+
+
+@pytest.mark.parametrize("mode", ["eval", "train", "train_batched"])
+def test_opacity_is_the_antialias_with_the_bare_tensor_topology(dev, mode):
+    """the renderer antialiases with Mesh.topology's tables; the same ctx calls on out["mesh"] with
+    raster.edge_topology's give the same bits (the antialias forward is bit-reproducible)"""
+    P, n_view, H, W = 2, 2, 32, 32
+    r, g, m, b = _sphere_modules(dev, isosurface_resolution=16)
+    r.train(mode != "eval")
+    r.batch_prompts = mode == "train_batched"
+    cam = _cameras(P * n_view, H, W, dev)
+    cache = torch.randn(P, 6, 32, 32, 32, device=dev)
+    with torch.set_grad_enabled(mode != "eval"):  # training decodes the normals with autograd
+        out = r(cam["mvp_mtx"], cam["camera_positions"], cam["light_positions"], H, W, space_cache=cache,
+                text_embed=torch.zeros(P, 1024, device=dev), camera_distances=cam["camera_distances"], c2w=cam["c2w"])
+    assert out["opacity"].shape == (P * n_view, H, W, 1) and len(out["mesh"]) == P
+    for i, mesh in enumerate(out["mesh"]):
+        sl = slice(i * n_view, (i + 1) * n_view)
+        tri = mesh.t_pos_idx
+        pos = r.ctx.vertex_transform(mesh.v_pos, cam["mvp_mtx"][sl])
+        rast, _ = r.ctx.rasterize(pos, tri, (H, W))
+        mask = rast[..., 3:] > 0
+        assert 0 < mask.sum() < mask.numel()  # a silhouette inside the image: antialias has edges to blend
+        want = r.ctx.antialias(mask.float(), rast, pos, tri,
+                               topology=raster.edge_topology(tri.int(), mesh.v_pos.shape[0]))
+        assert torch.equal(out["opacity"][sl], want), (mode, i)
+        assert (want != mask.float()).any()  # and it did blend
 
 
 def test_training_shape_backward(dev):

@@ -1,6 +1,7 @@
 """Mesh regularisers and outlier removal without a GPU: the numpy oracle (tests/mesh_reference.py) against the
 reference's own Mesh (tests/golden/reference_mesh_ops.npz, make_golden_mesh_ops.py), the C ABI's argument checks,
-the ops' refusal of CPU tensors, and the threestudio Mesh API's names and signatures."""
+the ops' refusal of CPU tensors, the threestudio Mesh API's names and signatures, and the tables of the shared
+face-edge sort (ops.sort_face_edges) against plain-Python grouping."""
 import ctypes
 import inspect
 import os
@@ -10,12 +11,13 @@ import numpy as np
 import pytest
 import torch
 
-from triplaneturbo_amd import _lib, ops
+from triplaneturbo_amd import _lib, ops, raster
 from triplaneturbo_amd import isosurface as I
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import mesh_reference as M  # noqa: E402
+import uv_reference as U  # noqa: E402
 
 GOLDEN = np.load(os.path.join(HERE, "golden", "reference_mesh_ops.npz"))
 NAMES = sorted({k.rsplit("_v_pos", 1)[0] for k in GOLDEN.files if k.endswith("_v_pos")})
@@ -92,6 +94,47 @@ def test_ops_refuse_cpu_tensors():
         I.Mesh(v, t).edges
     with pytest.raises(RuntimeError, match="no CPU path"):
         I.Mesh(v, t).remove_outlier(0.5)
+
+
+def _random_tri(n_vert, n_tri, seed):
+    return torch.randint(0, n_vert, (n_tri, 3), generator=torch.Generator().manual_seed(seed), dtype=torch.int32)
+
+
+@pytest.mark.parametrize("tri, n_vert", [(torch.from_numpy(M.hand_mesh()[1]), 11), (_random_tri(5, 40, 0), 5),
+                                         (_random_tri(5, 40, 1), 5), (_random_tri(7, 5, 2), 7),
+                                         (_random_tri(7, 5, 3), 7)])
+def test_shared_sort_groups_the_face_edges_like_a_dictionary(tri, n_vert):
+    T = tri.shape[0]
+    groups = {}  # unordered vertex pair -> its face edges 3f + k, ascending
+    for fe in range(3 * T):
+        a, b = int(tri[fe // 3, fe % 3]), int(tri[fe // 3, (fe % 3 + 1) % 3])
+        groups.setdefault((min(a, b), max(a, b)), []).append(fe)
+    srt = ops.sort_face_edges(tri, n_vert)
+    edge_ofs, edge_tri = srt.antialias_tables()
+    assert edge_ofs.dtype == edge_tri.dtype == torch.int32
+    assert tuple(edge_ofs.shape) == (3 * T, 2) and tuple(edge_tri.shape) == (3 * T,)
+    for pair, members in groups.items():
+        firsts = {int(edge_ofs[fe, 0]) for fe in members}
+        assert len(firsts) == 1, pair  # one group per pair ...
+        first = firsts.pop()
+        assert all(int(edge_ofs[fe, 1]) == len(members) for fe in members), pair  # ... of the right size ...
+        # ... that lists the triangles of exactly these face edges, in ascending face-edge order (stable sort)
+        assert edge_tri[first:first + len(members)].tolist() == [fe // 3 for fe in members], pair
+    assert len({int(edge_ofs[m[0], 0]) for m in groups.values()}) == len(groups)  # distinct pairs, distinct groups
+    assert srt.edges().tolist() == sorted(map(list, groups))
+    for got, want in zip(raster.edge_topology(tri, n_vert), (edge_ofs, edge_tri)):
+        assert torch.equal(got, want)
+
+
+def test_shared_sort_gives_the_hand_mesh_its_edges_and_face_pairs():
+    tri = M.hand_mesh()[1]
+    srt = ops.sort_face_edges(torch.from_numpy(tri), 11)
+    assert np.array_equal(srt.edges().numpy(), M.edges(tri))
+    pairs = srt.face_pairs()
+    assert pairs.dtype == torch.int32 and np.array_equal(pairs.numpy(), U.face_pairs(tri))
+    # five tetrahedron edges (its sixth, (1,2), has three users), (2,4) of the strip 4-5 and (7,8) of the strip 7-8;
+    # (6,7) has three users too: twice the degenerate face 6, once face 7
+    assert len(pairs) == 7
 
 
 def test_mesh_has_the_threestudio_api():

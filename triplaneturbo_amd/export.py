@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import ops, raster
+from .isosurface import prompt_slice
 from .registry import Updateable, parse_structured, register
 
 Tensor = torch.Tensor
@@ -77,12 +78,6 @@ class Exporter(Updateable):
         raise NotImplementedError
 
 
-def _prompt_slice(space_cache: Any, i: int) -> Any:
-    if torch.is_tensor(space_cache):
-        return space_cache[i:i + 1]
-    return {k: [w[i:i + 1] for w in v] for k, v in space_cache.items()}
-
-
 @register("multiprompt-mesh-exporter")
 class MultipromptMeshExporter(Exporter):
     @dataclass
@@ -114,7 +109,7 @@ class MultipromptMeshExporter(Exporter):
         if type(mesh) == list:
             mesh = mesh[0]
         # the texture belongs to mesh[0]: decode it from the first prompt's slice of the space cache
-        space_cache = _prompt_slice(space_cache, 0)
+        space_cache = prompt_slice(space_cache, 0)
         if self.cfg.fmt == "obj-mtl":
             return self.export_obj_with_mtl(mesh, space_cache)
         elif self.cfg.fmt == "obj":

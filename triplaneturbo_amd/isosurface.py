@@ -13,6 +13,7 @@ training system's regularisers and outlier removal, and threestudio's UV unwrap 
 texture) is triplaneturbo_amd.export: `multiprompt-mesh-exporter` and `save_obj`."""
 from __future__ import annotations
 
+from functools import cached_property
 from typing import Any, Callable, Dict, List, Optional, Tuple, Union
 
 import torch
@@ -37,6 +38,19 @@ def scale_tensor(dat: Tensor, inp_scale, tgt_scale) -> Tensor:
     return dat
 
 
+def cache_batch_device(space_cache: Any) -> Tuple[int, torch.device]:
+    """Prompts and device of a space cache: a (P,6,32,R,R) tensor, or the hyper net's Dict[str, List[Tensor]]."""
+    first = space_cache if torch.is_tensor(space_cache) else next(iter(space_cache.values()))[0]
+    return first.shape[0], first.device
+
+
+def prompt_slice(space_cache: Any, i: int) -> Any:
+    """Prompt i's slice of a space cache, batch dimension kept: a view of a tensor, lists of views of a dict."""
+    if torch.is_tensor(space_cache):
+        return space_cache[i:i + 1]
+    return {k: [w[i:i + 1] for w in v] for k, v in space_cache.items()}
+
+
 class Mesh:
     """The part of threestudio's Mesh (threestudio/models/mesh.py; triplaneturbo_executable/utils/mesh.py is its
     subset) that mesh extraction, colouring, the mesh renderer and the training system use: positions, int32
@@ -51,7 +65,6 @@ class Mesh:
         self._v_tex: Optional[Tensor] = None
         self._t_tex_idx: Optional[Tensor] = None
         self.uv_info: Optional[Dict[str, Any]] = None  # ops.uv_atlas's info of the last unwrap
-        self._topology: Optional[ops.MeshTopology] = None  # depends on t_pos_idx and V only: built once
         self.extras: Dict[str, Any] = {}
         for k, v in kwargs.items():
             self.add_extra(k, v)
@@ -110,11 +123,10 @@ class Mesh:
     def requires_grad(self) -> bool:
         return self.v_pos.requires_grad
 
-    @property
+    @cached_property
     def topology(self) -> ops.MeshTopology:
-        if self._topology is None:
-            self._topology = ops.mesh_topology(self.t_pos_idx, self.v_pos.shape[0])
-        return self._topology
+        """The mesh's one connectivity object; depends on t_pos_idx and V only, so it is built once."""
+        return ops.mesh_topology(self.t_pos_idx, self.v_pos.shape[0])
 
     @property
     def edges(self) -> Tensor:
@@ -209,14 +221,7 @@ class DiffMarchingCubeHelper(IsosurfaceHelper):
 def isosurface(space_cache: Any, forward_field: Callable, isosurface_helper: Callable) -> List[Mesh]:
     """mesh_exporter.py:78-141: query the field on the helper's grid (mapped to the hard-coded [-1, 1] bbox), one
     mesh per prompt, |p| - 1 in place of a field without a level set, vertices mapped back to [-1, 1]."""
-    if torch.is_tensor(space_cache):
-        batch_size = space_cache.shape[0]
-        device = space_cache.device
-    elif isinstance(space_cache, dict):
-        for key in space_cache.keys():
-            batch_size = space_cache[key][0].shape[0]
-            device = space_cache[key][0].device
-            break
+    batch_size, device = cache_batch_device(space_cache)
     points = scale_tensor(isosurface_helper.grid_vertices.to(device), isosurface_helper.points_range, [-1, 1])
     sdf_batch, deformation_batch = forward_field(points[None, ...].expand(batch_size, -1, -1), space_cache)
     mesh_list = []
@@ -237,11 +242,7 @@ def colorize_mesh(space_cache: Any, export_fn: Callable, mesh_list: List[Mesh], 
     activation(features) as the vertex colours."""
     for i, mesh in enumerate(mesh_list):
         points = mesh.v_pos[None, ...]
-        if torch.is_tensor(space_cache):
-            space_cache_slice = space_cache[i:i + 1]
-        elif isinstance(space_cache, dict):
-            space_cache_slice = {key: [w[i:i + 1] for w in space_cache[key]] for key in space_cache.keys()}
-        out = export_fn(points, space_cache_slice)
+        out = export_fn(points, prompt_slice(space_cache, i))
         if "features" in out:
             mesh._v_rgb = activation(out["features"].squeeze(0))
     return mesh_list

@@ -13,7 +13,7 @@ import torch
 import torch.nn.functional as F
 
 from . import raster
-from .isosurface import DiffMarchingCubeHelper, Mesh, scale_tensor
+from .isosurface import DiffMarchingCubeHelper, Mesh, cache_batch_device, prompt_slice, scale_tensor
 from .registry import BaseModule, C, register
 
 Tensor = torch.Tensor
@@ -164,10 +164,7 @@ class GenerativeSpaceMeshRasterizeRenderer(BaseModule):
                                                           is_empty)
 
             if render_rgb:
-                if torch.is_tensor(space_cache):
-                    space_cache_slice = space_cache[batch_idx:batch_idx + 1]
-                else:  # hyper net: Dict[str, List[Tensor]]
-                    space_cache_slice = {k: [w[batch_idx:batch_idx + 1] for w in v] for k, v in space_cache.items()}
+                space_cache_slice = prompt_slice(space_cache, batch_idx)
                 selector = mask[..., 0]
                 gb_pos = g.pos
                 gb_viewdirs = F.normalize(gb_pos - camera_positions[sl, None, None, :], dim=-1)
@@ -233,7 +230,7 @@ class GenerativeSpaceMeshRasterizeRenderer(BaseModule):
         """The raster stage of one prompt in instance mode: its G-buffer and its antialias."""
         v_pos_clip = self.ctx.vertex_transform(mesh.v_pos, mvp_mtx)
         tri = mesh.t_pos_idx
-        topo = raster.mesh_topology(mesh)
+        topo = mesh.topology.antialias_tables
         if self.training:
             rast, _ = self.ctx.rasterize(v_pos_clip, tri, (height, width))
             gb_feat, _ = self.ctx.interpolate(v_pos_clip, rast, tri)
@@ -267,7 +264,7 @@ class GenerativeSpaceMeshRasterizeRenderer(BaseModule):
             clip = self.ctx.vertex_transform(mesh.v_pos, mvp_mtx[batch_idx * n_view:(batch_idx + 1) * n_view])
             pos += [clip[v] for v in range(n_view)]
             tri += [mesh.t_pos_idx] * n_view
-            topo += [raster.mesh_topology(mesh)] * n_view
+            topo += [mesh.topology.antialias_tables] * n_view
             nrm += [mesh.v_nrm] * n_view
             v_pos += [mesh.v_pos] * n_view
         pk = raster.pack_ranges(pos, tri, topo)
@@ -292,12 +289,7 @@ class GenerativeSpaceMeshRasterizeRenderer(BaseModule):
     def isosurface(self, space_cache: Any) -> List[Mesh]:
         """reference :416-514: grid query on the [-1, 1] box, gradient shrink, the InstantMesh fix-up of an empty
         field, one marching-cubes helper per prompt, vertices mapped back to [-1, 1]."""
-        if torch.is_tensor(space_cache):
-            batch_size = space_cache.shape[0]
-            device = space_cache.device
-        else:
-            first = next(iter(space_cache.values()))[0]
-            batch_size, device = first.shape[0], first.device
+        batch_size, device = cache_batch_device(space_cache)
         helper = self.isosurface_helper
         points = scale_tensor(helper.grid_vertices.to(device), helper.points_range, [-1, 1])
         sdf_batch, deformation_batch = self.geometry.forward_field(points[None, ...].expand(batch_size, -1, -1),

@@ -8,7 +8,8 @@ from __future__ import annotations
 import ctypes
 import dataclasses
 from dataclasses import dataclass
-from typing import List, Optional, Sequence, Tuple
+from functools import cached_property
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -869,14 +870,55 @@ def marching_cubes(level: Tensor, deformation: Optional[Tensor] = None, isovalue
     return _MarchingCubesFn.apply(level, deformation, float(isovalue))
 
 
+class FaceEdgeSort(NamedTuple):
+    """sort_face_edges' result, all int64: sorted position p holds face edge perm[p] = 3f + k (vertices k, (k+1) % 3
+    of face f) and lies in group inverse[p]; group g has the key uniq[g] = min(a,b) * base + max(a,b), counts[g] face
+    edges and the first position starts[g].  Every connectivity table of a mesh is derived from these."""
+    perm: Tensor
+    uniq: Tensor
+    inverse: Tensor
+    counts: Tensor
+    starts: Tensor
+    base: int
+
+    def edges(self) -> Tensor:  # (E,2) int64: the unique sorted vertex pairs, lexicographic, self pairs included
+        return torch.stack([self.uniq // self.base, self.uniq % self.base], dim=1)
+
+    def face_pairs(self) -> Tensor:  # (P,2) int32: the two faces of every edge that exactly two face edges use
+        two = self.starts[self.counts == 2]
+        return torch.stack([self.perm[two] // 3, self.perm[two + 1] // 3], dim=1).int().contiguous()
+
+    def antialias_tables(self) -> Tuple[Tensor, Tensor]:  # raster.edge_topology's (edge_ofs, edge_tri)
+        ofs = torch.empty((self.perm.shape[0], 2), dtype=torch.int32, device=self.perm.device)
+        ofs[self.perm, 0] = self.starts[self.inverse].int()
+        ofs[self.perm, 1] = self.counts[self.inverse].int()
+        return ofs.contiguous(), (self.perm // 3).int().contiguous()
+
+
+def sort_face_edges(tri: Tensor, n_vertices: int) -> FaceEdgeSort:
+    """The face edges of tri (T,3) grouped by their unordered vertex pair: one stable torch.sort and one
+    unique_consecutive of the key min(a,b) * max(n_vertices,1) + max(a,b) over face edge 3f + k (plumbing; it syncs).
+    Any device, CPU included, and no validation."""
+    base = max(int(n_vertices), 1)
+    a = tri.long()
+    b = a[:, [1, 2, 0]]
+    key = torch.add(torch.maximum(a, b), torch.minimum(a, b), alpha=base).reshape(-1)
+    skey, perm = torch.sort(key, stable=True)
+    uniq, inverse, counts = torch.unique_consecutive(skey, return_inverse=True, return_counts=True)
+    return FaceEdgeSort(perm, uniq, inverse, counts, torch.cumsum(counts, 0) - counts, base)
+
+
 class MeshTopology:
-    """What the tt_mesh_* kernels need of a mesh's connectivity (include/tt_abi.h, "mesh regularisers and outlier
-    removal"), built once per mesh from t_pos_idx with torch sorts (plumbing; this is the one place that syncs):
+    """The one connectivity object of a mesh (Mesh.topology), from t_pos_idx alone: what the tt_mesh_* and tt_uv_*
+    kernels and antialias need (include/tt_abi.h).  The constructor validates and runs sort_face_edges once:
+      tri         (T,3) int32
       edges       (E,2), dtype of t_pos_idx: the unique sorted face edges in lexicographic order, self pairs included
-                  (threestudio Mesh._compute_edges)
+                  (threestudio Mesh._compute_edges); edges_i32 is its int32 copy
+    Derived from that sort on first use and kept, so a consumer pays for its own tables only:
       face_pairs  (P,2) int32: the two faces of every edge that exactly two face edges use
-      nbr_ptr     (V+1) int32, nbr_col (2E) int32: vertex -> neighbour CSR, each row ascending
-      ws          the device workspace every entry point of this mesh shares"""
+      nbr_ptr     (V+1) int32, nbr_col (2E) int32: vertex -> neighbour CSR, each row ascending (the second sort)
+      ws          the device workspace every tt_mesh_* entry point of this mesh shares
+      antialias_tables  (edge_ofs (3T,2), edge_tri (3T)) int32, as raster.edge_topology(tri, V) returns them"""
 
     def __init__(self, t_pos_idx: Tensor, n_vertices: int):
         if not isinstance(t_pos_idx, torch.Tensor) or not t_pos_idx.is_cuda:
@@ -887,34 +929,44 @@ class MeshTopology:
         lim = 1 << 28  # TT_MESH_MAX_ITEMS
         if V > lim or T > lim:
             raise ValueError(f"mesh too large for tt_mesh_*: V={V}, T={T} (limit {lim})")
-        dev = t_pos_idx.device
         self.n_vertices, self.n_faces = V, T
-        tri = t_pos_idx.long()
-        if T > 0 and (int(tri.min()) < 0 or int(tri.max()) >= V):
+        lo, hi = torch.stack(t_pos_idx.aminmax()).tolist() if T > 0 else (0, -1)  # one read-back
+        if lo < 0 or hi >= V:
             raise ValueError(f"t_pos_idx holds an index outside [0, {V})")
         self.tri = t_pos_idx.int().contiguous()
-        a, b = tri, tri[:, [1, 2, 0]]
-        key = (torch.minimum(a, b) * max(V, 1) + torch.maximum(a, b)).reshape(-1)  # face edge 3f + k
-        skey, perm = torch.sort(key, stable=True)
-        uniq, counts = torch.unique_consecutive(skey, return_counts=True)
-        e0, e1 = uniq // max(V, 1), uniq % max(V, 1)
-        self.edges = torch.stack([e0, e1], dim=1).to(t_pos_idx.dtype).contiguous()
+        self._sort = sort_face_edges(t_pos_idx, V)
+        self.edges = self._sort.edges().to(t_pos_idx.dtype).contiguous()
         self.edges_i32 = self.edges if self.edges.dtype == torch.int32 else self.edges.int().contiguous()
-        starts = torch.cumsum(counts, 0) - counts
-        two = starts[counts == 2]
-        self.face_pairs = torch.stack([perm[two] // 3, perm[two + 1] // 3], dim=1).int().contiguous()
-        # both directions of every unique edge, sorted by (row, column): a second stable sort
-        src, dst = torch.cat([e0, e1]), torch.cat([e1, e0])
-        order = torch.sort(src * max(V, 1) + dst, stable=True)[1]
-        self.nbr_col = dst[order].int().contiguous()
-        self.nbr_ptr = torch.zeros(V + 1, dtype=torch.int64, device=dev)
-        self.nbr_ptr[1:] = torch.cumsum(torch.bincount(src, minlength=V), 0)
-        self.nbr_ptr = self.nbr_ptr.int().contiguous()
-        self.ws = _workspace("tt_mesh_workspace_bytes", V, T, device=dev)
 
     @property
     def n_edges(self) -> int:
         return self.edges.shape[0]
+
+    @cached_property
+    def face_pairs(self) -> Tensor:
+        return self._sort.face_pairs()
+
+    @cached_property
+    def antialias_tables(self) -> Tuple[Tensor, Tensor]:
+        return self._sort.antialias_tables()
+
+    @cached_property
+    def _nbr(self) -> Tuple[Tensor, Tensor]:
+        # both directions of every unique edge, sorted by (row, column): a second stable sort
+        V = self.n_vertices
+        e0, e1 = self.edges.long().unbind(1)
+        src, dst = torch.cat([e0, e1]), torch.cat([e1, e0])
+        order = torch.sort(torch.add(dst, src, alpha=max(V, 1)), stable=True)[1]
+        nbr_ptr = torch.zeros(V + 1, dtype=torch.int64, device=src.device)
+        nbr_ptr[1:] = torch.cumsum(torch.bincount(src, minlength=V), 0)
+        return nbr_ptr.int().contiguous(), dst[order].int().contiguous()
+
+    nbr_ptr = property(lambda self: self._nbr[0])
+    nbr_col = property(lambda self: self._nbr[1])
+
+    @cached_property
+    def ws(self) -> Tensor:
+        return _workspace("tt_mesh_workspace_bytes", self.n_vertices, self.n_faces, device=self.tri.device)
 
 
 def mesh_topology(t_pos_idx: Tensor, n_vertices: int) -> MeshTopology:

@@ -30,7 +30,7 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple, Union
 import torch
 
 from . import _lib
-from .ops import _chk, _launch, _workspace
+from .ops import _chk, _launch, _workspace, sort_face_edges
 
 Tensor = torch.Tensor
 MAX_TRIS = 1 << 24  # TT_RAST_MAX_TRIS: tri + 1 is stored as a float
@@ -56,22 +56,8 @@ def edge_topology(tri: Tensor, n_vertices: Optional[int] = None) -> Tuple[Tensor
     """The edge -> triangles table antialias() needs (tt_abi.h "topology"): edge_ofs (3T,2) int32 = (first, count)
     of the group of triangle edge 3t + k (vertices k, (k+1) % 3) in the sorted edge list, edge_tri (3T) int32 = the
     triangle of each sorted entry.  Depends on tri only (torch sort as plumbing): build it once per mesh."""
-    T = tri.shape[0]
-    dev = tri.device
-    if T == 0:
-        return torch.zeros((0, 2), dtype=torch.int32, device=dev), torch.zeros(0, dtype=torch.int32, device=dev)
-    a = tri.long()
-    b = a[:, [1, 2, 0]]
-    lo, hi = torch.minimum(a, b), torch.maximum(a, b)
-    n = int(n_vertices) if n_vertices is not None else int(a.max().item()) + 1
-    key = (lo * max(n, 1) + hi).reshape(-1)
-    skey, perm = torch.sort(key, stable=True)
-    _, inverse, counts = torch.unique_consecutive(skey, return_inverse=True, return_counts=True)
-    starts = torch.cumsum(counts, 0) - counts
-    ofs = torch.empty((3 * T, 2), dtype=torch.int32, device=dev)
-    ofs[perm, 0] = starts[inverse].int()
-    ofs[perm, 1] = counts[inverse].int()
-    return ofs.contiguous(), (perm // 3).int().contiguous()
+    n = int(n_vertices) if n_vertices is not None else int(tri.max().item()) + 1 if tri.shape[0] else 0
+    return sort_face_edges(tri, n).antialias_tables()
 
 
 class _RasterizeFn(torch.autograd.Function):
@@ -302,15 +288,6 @@ def antialias(color: Tensor, rast: Tensor, pos: Tensor, tri: Tensor,
     edge_ofs = _chk(topology[0], "edge_ofs", (tri.shape[0] * 3, 2), dtype=torch.int32)
     edge_tri = _chk(topology[1], "edge_tri", (tri.shape[0] * 3,), dtype=torch.int32)
     return _AntialiasFn.apply(color, rast, pos, tri, edge_ofs, edge_tri)
-
-
-def mesh_topology(mesh) -> Tuple[Tensor, Tensor]:
-    """edge_topology of a Mesh, cached on it (the mesh renderer antialiases about six images per mesh)."""
-    topo = getattr(mesh, "_aa_topology", None)
-    if topo is None:
-        topo = edge_topology(mesh.t_pos_idx.int(), mesh.v_pos.shape[0])
-        mesh._aa_topology = topo
-    return topo
 
 
 class PackedRanges(NamedTuple):
