@@ -152,8 +152,10 @@ typedef struct {
                                   that pass the exact skip tests: some texel in bounds -- a tile without one decodes to exact
                                   zeros --, and in the backward some non-zero upstream gradient), [2] (plane, sample) pairs
                                   with an in-bounds texel over the gathers that ran (3 planes per sample; the samples a launch
-                                  visits are exactly n_rays * n_samples), [3] reserved.  Measurement only (bench.py:
-                                  live_tile_frac, inbounds_plane_frac) */
+                                  visits are exactly n_rays * n_samples), [3] executed tile steps that took the single-plane path
+                                  (exactly one plane had an in-bounds texel in the tile: the other two planes' products and
+                                  scatter passes are left out; forward: counted in the texture decode).  Measurement only
+                                  (bench.py: live_tile_frac, inbounds_plane_frac) */
 } tt_render_cfg;
 
 #define TT_R_PER_SAMPLE 1 /* also write per-sample sdf / sdf_grad / features (training extras, renderer :532-545) */

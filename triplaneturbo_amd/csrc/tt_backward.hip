@@ -181,13 +181,16 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
                         Z = scale_coord(pz, cfg.radius);
             // ---- recompute the geometry decode ----
             float f[16], u[16];  // u = sbar f + J gbar
-            bool anyp[3];
+            unsigned pmask;
             const bool any = __any(gather_geo_bwd_c(p.packed, (unsigned)(pofs / TT_C), H, W, X, Y, Z, rvalid, sbar, gbx,
-                                                    gby, gbz, ju, jv, lane, Xs, f, u, anyp,
+                                                    gby, gbz, ju, jv, lane, Xs, f, u, pmask,
                                                     tile_stat_ptr(st, TT_STAT_INBOUNDS)));
             TT_PHASE(1);
             if (!any) continue;  // exact: no in-bounds texel => f = J = 0, every mask false
-            tile_stat(st, TT_STAT_EXECUTED);
+            // one plane with an in-bounds texel (tt_device.h, "plane mask"): the sdf net sees the SUM of the planes, so only
+            // the scatter knows -- the other two planes' coefficients are exact zeros and their passes flush nothing
+            const bool one = single_plane(pmask);
+            tile_stat_executed(st, one);
             // h1, h2 (and a1 under WG16) stay in RAW form: accumulators + a per-lane power-of-two factor (tt_mfma16.h,
             // "deferred factors"); their consumers are signs, the next product, and fmas that take the factor on the scalar
             float h1[32], h2[32], a2[32], a1[32], q[16], u1, u2;
@@ -279,8 +282,7 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
                     float* Qs = Xs + SCATTER_M_FLOATS;  // the sample's row of Q: q scaled per plane, stride 33
                     TT_PHASE(9);
                     const int tex0 = (int)(pofs / TT_C);
-                    scatter_planes<EXACT>(grad_out, grad_bytes, Qs, Xs, tags, Qs + 32 * 33, i, hi,
-                                          [&](int pl, PlaneRefs& refs) {
+                    auto prep = [&](int pl, PlaneRefs& refs) {
                         Corners c;
                         float coef[4];  // per corner: w sbar + dw/dx . gbar -- gather AND scatter coefficient
                         geo_corner_coefs(pl, H, W, X, Y, Z, rvalid, sbar, gbx, gby, gbz, ju, jv, c, coef);
@@ -290,11 +292,17 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
                         refs = plane_refs<!EXACT>(coef, aoff, c.hs, hi);
 #pragma unroll
                         for (int r = 0; r < 16; ++r) Qs[i * 33 + LIDX(r, hi)] = q[r] * refs.qs;
-                    }
+                    };
 #ifdef TT_TUNING
-                    , ph_acc + 14
+                    unsigned long long* const sc_st = ph_acc + 14;
+#else
+                    unsigned long long* const sc_st = nullptr;
 #endif
-                    );
+                    if (one)
+                        scatter_one_plane<EXACT>(grad_out, grad_bytes, Qs, Xs, tags, Qs + 32 * 33, i, hi,
+                                                 single_plane_index(pmask), prep, sc_st);
+                    else
+                        scatter_planes<EXACT>(grad_out, grad_bytes, Qs, Xs, tags, Qs + 32 * 33, i, hi, prep, sc_st);
                     TT_PHASE(10);
                 }
             }

@@ -709,6 +709,59 @@ __device__ __forceinline__ void scatter_planes(float* __restrict__ grad, unsigne
     }
 }
 
+// ---- one plane only (single-plane tile steps: the plane mask of the gather has one bit, tt_device.h) -------------------------
+// The other two planes' coefficients are exact zeros there: their claims are all inactive, n = 0, nothing is flushed.  This
+// is plane `pl` (wave-uniform, known at run time) of scatter_planes with nothing to overlap it with, so the pieces run in
+// their plain order: prep, claims + ranks, lost references, rows -> M; operands -> registers, M back to zero; GEMM; flush
+// (and the second 64-row pass when n > 64).  Same arguments and the same state on exit as scatter_planes: M all-zero, the
+// table empty, the dummy words <= -2.
+template <bool EXACT, class Prep>
+__device__ __forceinline__ void scatter_one_plane(float* __restrict__ grad, unsigned grad_bytes, const float* Qs, float* M,
+                                                  int* tags, float* Ls, int i, int hi, int pl, Prep&& prep,
+                                                  unsigned long long* st = nullptr) {
+    const __amdgpu_buffer_rsrc_t grsrc = __builtin_amdgcn_make_buffer_rsrc(grad, 0, (int)grad_bytes, 0x00020000);
+    const unsigned lane_b = 4u * (unsigned)i;
+    const int lane = i + 32 * hi;
+    int* const dummy = tags + i;
+    int* const htab = reinterpret_cast<int*>(Ls + 256);
+    int* const ct = htab + SC2_HT;
+    int* const cdump = ct + 2 * SC2_CT;
+    typename std::conditional<EXACT, ScA32, ScA16>::type A;
+    typename std::conditional<EXACT, ScB32, ScB16>::type B;
+    {
+        const i32x4 e4 = {-1, -1, -1, -1};
+        *reinterpret_cast<i32x4*>(htab + 4 * lane) = e4;
+    }
+    PlaneRefs rc;
+    prep(pl, rc);
+    const Sc2State sc = sc2_claim_rank(rc, htab, ct, cdump, dummy, lane, st);
+    scatter_lost(rc, sc.l0, sc.l1, Qs, Ls, grsrc, i, hi);
+    m_store<EXACT>(M, sc2_row_a(sc.rx0), i, rc.c0);
+    m_store<EXACT>(M, sc2_row_a(sc.rx1), i, rc.c1);
+    const bool pass_b = sc.n > 64;  // wave-uniform
+    f32x16 acc0, acc1;
+    sc2_load_a(M, i, hi, sc.n, A);
+    m_zero<EXACT>(M, sc2_row_a(sc.rx0), i);
+    m_zero<EXACT>(M, sc2_row_a(sc.rx1), i);
+    if (pass_b) {
+        m_store<EXACT>(M, sc2_row_b(sc.rx0), i, rc.c0);
+        m_store<EXACT>(M, sc2_row_b(sc.rx1), i, rc.c1);
+    }
+    sc2_load_b(Qs, i, hi, B);
+    sc2_split_b(B);
+    sc2_gemm(A, B, sc.n, acc0, acc1);
+    if (pass_b) {
+        sc2_flush(acc0, acc1, ct, 64, grsrc, lane_b, hi);
+        sc2_load_a(M, i, hi, sc.n - 64, A);
+        m_zero<EXACT>(M, sc2_row_b(sc.rx0), i);
+        m_zero<EXACT>(M, sc2_row_b(sc.rx1), i);
+        sc2_gemm(A, B, sc.n - 64, acc0, acc1);
+        sc2_flush(acc0, acc1, ct + 64, sc.n - 64, grsrc, lane_b, hi);
+    } else {
+        sc2_flush(acc0, acc1, ct, sc.n, grsrc, lane_b, hi);
+    }
+}
+
 // ---- texture half: parameters and weight-image map of tt_backward_tex.hip ----
 struct BwdTexParams {
     const float* packed;

@@ -6,6 +6,11 @@
 // texture half
 // =====================================================================================================
 #define TEX_SCRATCH_FLOATS (128 * XS)
+// a wave-uniform float the compiler cannot prove uniform (read back from LDS, derived from the wave index): through
+// readfirstlane it lives in a scalar register.  This kernel has no vector register to spare.
+__device__ __forceinline__ float uniform_f(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+}
 
 // STATS: work accounting compiled in (see k_decode_bwd_geo): production launches run the instantiation without it
 template <int PREC, bool WG16, bool STATS = false>
@@ -53,8 +58,13 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_tex(BwdTexParams p) {
         sK2B = wg16_scale(K2Bw * CBmax);
         sKB1 = wg16_scale(KB1w * CBmax);
     }
+    // the scales and their inverses (powers of two: exact) are wave-uniform: held in scalar registers.  Together with the
+    // wave index below this frees the vector registers the single-plane branches need (without: 3 - 20 spilled registers)
+    sE = uniform_f(sE), sK1 = uniform_f(sK1), sK2B = uniform_f(sK2B), sKB1 = uniform_f(sKB1);
+    const float uE = uniform_f(1.f / sE), uK1 = uniform_f(1.f / sK1);
     const TileGeom& tg = p.geom;
-    const int lane = threadIdx.x & 63, i = lane & 31, hi = lane >> 5, wave_in_blk = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, i = lane & 31, hi = lane >> 5,
+              wave_in_blk = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     // per-wave scratch: rows 0..31 = Xs (transposition window / first half of bigger operands), rows 32..127 = Ys
     float* Xs = Lt + WF + wave_in_blk * (TEX_SCRATCH_FLOATS + SCATTER_TAG_INTS);
     float* Ys = Xs + 32 * XS;  // 96 rows: the parked e
@@ -170,12 +180,21 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_tex(BwdTexParams p) {
         sample_position(ox, oy, oz, dx, dy, dz, in.ts, in.te, tm, px, py, pz);
         const float X = scale_coord(px, cfg.radius), Y = scale_coord(py, cfg.radius), Z = scale_coord(pz, cfg.radius);
         float e[48];
+        unsigned pmask;
         const bool any =
-            __any(gather_tex_c(p.packed, (unsigned)(pofs / TT_C), H, W, X, Y, Z, valid, lane, Xs, e,
+            __any(gather_tex_c(p.packed, (unsigned)(pofs / TT_C), H, W, X, Y, Z, valid, lane, Xs, e, pmask,
                                tile_stat_ptr(st, TT_STAT_INBOUNDS)));
         TT_PHASE(1);
         if (!any) continue;  // exact: e == 0 => k1 = k2 = 0 and every mask is false
-        tile_stat(st, TT_STAT_EXECUTED);
+        // Exactly ONE plane has an in-bounds texel in this tile (38 % of the executed tile steps of the headline scene: every
+        // ray enters and leaves the cube through such a region): the other two thirds of e are exact zeros, and so is
+        // everything that is multiplied by them or scattered for them.  Such a step runs V1 e over the live plane's two
+        // k-steps and scatters that plane alone; every other mask takes the general code.  Wave-uniform.
+        // (The staging of e, the dV1 outer products and V1^T k1bar stay common to both: with a three-way switch over the
+        // column blocks of dV1 hipcc spilled ~100 registers to scratch memory, with the 32-row V1^T product ~20 -- DESIGN.md.)
+        const bool one = single_plane(pmask);
+        const int pl1 = single_plane_index(pmask);
+        tile_stat_executed(st, one);
         // e is needed again only as the Y operand of the dV1 outer product: park it in LDS now ([idx][sample]
         // layout, 96 rows) so its 48 registers are free during the MLP chain.
         // (`region`: always true -- tt_validate_cfg rejects negative flags -- but opaque to the compiler.  The two
@@ -193,11 +212,23 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_tex(BwdTexParams p) {
             split16_vec<96, PAIR_SEQ, NT>(e, sE, es);
             if (do_wgrad) stage_rows16_pre<96>(Ys, es, i, hi);
             TT_PHASE(2);
-            mv16_pre<64, 96, false, NT>(Lt + TV1, es, 1.f / sE, k1, i, hi, nullptr, Lt + TLO_V1);
+            if (one) {  // V1 e over the live plane's two k-steps (the split of an exact zero is zero: OR again)
+                Split16<32, PAIR_SEQ, NT> e1s;
+                live_split32(es, e1s);
+                mv16_pre_ks<64, 96, 2, NT>(Lt + TV1, e1s, 2 * pl1, uE, k1, i, hi, Lt + TLO_V1);
+            } else {
+                mv16_pre<64, 96, false, NT>(Lt + TV1, es, uE, k1, i, hi, nullptr, Lt + TLO_V1);
+            }
         } else {
             if (do_wgrad) stage_rows<96>(Ys, e, i, hi);
             TT_PHASE(2);
-            mvx<PREC, 64, 96>(Lt + TV1, Lt + TLO_V1, e, k1, i, hi);
+            if (one) {
+                float e1[16];
+                live_block16(e, e1);
+                mvx_plane<PREC, 64, 96>(Lt + TV1, Lt + TLO_V1, e1, pl1, k1, i, hi);
+            } else {
+                mvx<PREC, 64, 96>(Lt + TV1, Lt + TLO_V1, e, k1, i, hi);
+            }
         }
 #pragma unroll
         for (int r = 0; r < 32; ++r) k1[r] = fmaxf(k1[r], 0.f);
@@ -205,7 +236,7 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_tex(BwdTexParams p) {
         Split16<64, PAIR_SEQ, NT> k1s;  // k1 likewise: V2 k1 now, the dV2 outer product later
         if (WG16) {
             split16_vec<64, PAIR_SEQ, NT>(k1, sK1, k1s);
-            mv16_pre<64, 64, false, NT>(Lt + TV2, k1s, 1.f / sK1, k2, i, hi, nullptr, Lt + TLO_V2);
+            mv16_pre<64, 64, false, NT>(Lt + TV2, k1s, uK1, k2, i, hi, nullptr, Lt + TLO_V2);
         } else {
             mvx<PREC, 64, 64>(Lt + TV2, Lt + TLO_V2, k1, k2, i, hi);
         }
@@ -301,6 +332,7 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_tex(BwdTexParams p) {
             float* M = Xs;              // rows 0..63: the slot x sample coefficient matrix (fp32), row 64: dump row
             float* Es = Xs + (EXACT ? 65 * XS : SCATTER_M_FLOATS);  // ebar rows [sample][32], stride 33; fallback lists
             scatter_clear<EXACT>(M, lane);
+            const int tex0 = (int)(pofs / TT_C);
             // ebar = V1^T k1bar for the three planes in ONE product (96 rows: k1bar is split into fp16 terms once)
             float eb[48];
             if constexpr (COPIES)
@@ -308,7 +340,28 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_tex(BwdTexParams p) {
             else
                 mvtx<PREC, 96, 64, 96>(Lt + TV1, Lt + TLO_V1, 0, kb1, eb, i, hi);
             TT_PHASE(9);
-            const int tex0 = (int)(pofs / TT_C);
+            if (one) {  // the live plane's 16 registers of ebar (selects, no runtime register indexing), its scatter alone
+                float eb1[16];
+#pragma unroll
+                for (int r = 0; r < 16; ++r) eb1[r] = pl1 == 0 ? eb[r] : (pl1 == 1 ? eb[16 + r] : eb[32 + r]);
+                scatter_one_plane<EXACT>(grad_out, grad_bytes, Es, M, tags, Es + 32 * 33, i, hi, pl1,
+                                         [&](int pl, PlaneRefs& refs) {
+                    Corners c;
+                    corners_setup(PLANE_U(pl, X, Y, Z), PLANE_V(pl, X, Y, Z), H, W, valid, c);
+                    int aoff[4];
+#pragma unroll
+                    for (int q4 = 0; q4 < 4; ++q4) aoff[q4] = tex0 + (int)((3 + pl) * HW) + c.off[q4];
+                    refs = plane_refs<!EXACT>(c.w, aoff, c.hs, hi);
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) Es[i * 33 + LIDX(r, hi)] = eb1[r] * refs.qs;
+                }
+#ifdef TT_TUNING
+                , scat_st
+#endif
+                );
+                TT_PHASE(10);
+                continue;
+            }
             scatter_planes<EXACT>(grad_out, grad_bytes, Es, M, tags, Es + 32 * 33, i, hi, [&](int pl, PlaneRefs& refs) {
                 Corners c;
                 corners_setup(PLANE_U(pl, X, Y, Z), PLANE_V(pl, X, Y, Z), H, W, valid, c);

@@ -129,6 +129,35 @@ __device__ __forceinline__ void mv_fwd(const float* Wl, const float (&x)[NIN / 2
         for (int k = 0; k < 16; ++k) y[16 * m + k] = acc[m][k];
 }
 
+// The same product over the 8 NG columns that start at column 8 g0 only (g0 wave-uniform, known at run time): x holds
+// those 8 NG entries, every other entry of the full vector is an exact zero (single-plane tile steps).  The accumulator
+// chain is the full product's with its zero terms left out: bit-identical.
+template <int NOUT, int NIN, int NG>
+__device__ __forceinline__ void mv_fwd_cols(const float* Wl, const float (&x)[4 * NG], int g0, float (&y)[NOUT / 2], int i,
+                                            int hi) {
+    constexpr int MT = NOUT / 32;
+    f32x16 acc[MT];
+    const float* row = Wl + i * (NIN + 4) + 4 * hi + 8 * g0;
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+        acc[m] = f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+        f32x4 a[MT];
+#pragma unroll
+        for (int m = 0; m < MT; ++m) a[m] = *reinterpret_cast<const f32x4*>(row + 32 * m * (NIN + 4) + 8 * g);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int m = 0; m < MT; ++m)
+                acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m][k], x[4 * g + k], acc[m], 0, 0, 0);
+    }
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int k = 0; k < 16; ++k) y[16 * m + k] = acc[m][k];
+}
+
 // y[NOUT] = W[NIN][NOUT]^T * x[NIN]   (W in LDS as stored, row stride STRIDE = NOUT+4).
 // STRIDE != NOUT+4 selects a 32m-column slice of a wider stored matrix (Wl already offset to its first column).
 // With a single row tile (NOUT = 32) the k range is split into two independent accumulator chains.
@@ -372,14 +401,15 @@ __device__ __forceinline__ bool gather_tex(const float* __restrict__ planes, int
 
 // Work accounting (tt_render_cfg.stats, measurement only).  NOTHING is kept in registers: the pointer is a kernel argument
 // (wave-uniform), so a production launch (null) pays one scalar branch per counting site; a measuring launch counts in a
-// wave-private LDS slot (one lane, plain read-modify-write) and adds the slot to the caller's counters with three atomics
+// wave-private LDS slot (one lane, plain read-modify-write) and adds the slot to the caller's counters with four atomics
 // per wave at kernel end.  (Round 4 first kept per-wave counters in registers: 0.09 ms of the 7.85 ms step -- the decode
 // kernels have no registers to spare; then one global atomic per site: free when off, but 15 ms per measuring launch.)
 struct TileStats {
-    unsigned long long* p;  // null, or the caller's 4 counters: [0] visited, [1] executed, [2] in-bounds pairs
+    unsigned long long* p;  // null, or the caller's 4 counters: [0] visited, [1] executed, [2] in-bounds pairs,
+                            // [3] executed tile steps that took the single-plane path
     unsigned* w;            // this wave's LDS slot (4 ints) when p != null
 };
-enum { TT_STAT_VISITED = 0, TT_STAT_EXECUTED = 1, TT_STAT_INBOUNDS = 2 };
+enum { TT_STAT_VISITED = 0, TT_STAT_EXECUTED = 1, TT_STAT_INBOUNDS = 2, TT_STAT_SINGLE = 3 };
 __device__ __forceinline__ TileStats tile_stats(uint64_t* stats64) {
     TileStats st = {nullptr, nullptr};
     __shared__ unsigned tt_stat_slots[16 * 4];  // <= 16 waves per workgroup
@@ -396,12 +426,38 @@ __device__ __forceinline__ void tile_stat(const TileStats& st, int which, unsign
         if ((threadIdx.x & 63) == 0) st.w[which] += v;
     }
 }
+// an executed tile step, and whether it took the single-plane path (wave-uniform): one counting site for both
+__device__ __forceinline__ void tile_stat_executed(const TileStats& st, bool single) {
+    if (st.p) {
+        if ((threadIdx.x & 63) == 0) {
+            st.w[TT_STAT_EXECUTED] += 1u;
+            st.w[TT_STAT_SINGLE] += single ? 1u : 0u;
+        }
+    }
+}
 __device__ __forceinline__ unsigned* tile_stat_ptr(const TileStats& st, int which) { return st.p ? st.w + which : nullptr; }
 __device__ __forceinline__ void tile_stats_flush(const TileStats& st) {
     if (st.p) {
         const int l = threadIdx.x & 63;
-        if (l < 3) atomicAdd(st.p + l, (unsigned long long)st.w[l]);
+        if (l < 4) atomicAdd(st.p + l, (unsigned long long)st.w[l]);
     }
+}
+
+// ---- plane mask of a tile step ------------------------------------------------------------------------------------------
+// The coalesced gathers below return, next to the per-lane `any`, the WAVE-UNIFORM mask of the planes that have an in-bounds
+// texel somewhere in the tile (bit p <-> plane p; built from the ballots the gathers take anyway).  A sample that has left
+// the cube along exactly one axis is still inside the one plane that does not use that axis: every ray enters and leaves
+// the cube through such a region, and there the other two planes contribute exact zeros to everything downstream.  A mask
+// with exactly ONE bit selects the kernels' single-plane routines; every other mask takes the general code.
+__device__ __forceinline__ bool single_plane(unsigned pmask) { return pmask != 0u && (pmask & (pmask - 1u)) == 0u; }
+__device__ __forceinline__ int single_plane_index(unsigned pmask) { return __builtin_ctz(pmask | 8u); }
+// the live 16-register block of a 48-register vector whose two other blocks are exact +0 (the gathers write 0.f into the
+// blocks of a plane without an in-bounds texel): a bitwise OR of the three blocks, no runtime register indexing
+__device__ __forceinline__ void live_block16(const float (&e)[48], float (&e1)[16]) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+        e1[r] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, e[r]) | __builtin_bit_cast(unsigned, e[16 + r]) |
+                                              __builtin_bit_cast(unsigned, e[32 + r]));
 }
 
 // ---- coalesced gathers ------------------------------------------------------------------------------------------------
@@ -460,7 +516,7 @@ template <bool NEED_J>
 __device__ __forceinline__ bool gather_geo_c(const float* __restrict__ planes, unsigned tex0, int H, int W, float X,
                                              float Y, float Z, bool valid, float jscale_u, float jscale_v, int lane,
                                              float* T, float (&f)[16], float (&jx)[16], float (&jy)[16],
-                                             float (&jz)[16], unsigned* inb = nullptr) {
+                                             float (&jz)[16], unsigned& pmask, unsigned* inb = nullptr) {
     const int i = lane & 31, hi = lane >> 5, js = lane >> 3, c = lane & 7;
     int* Toff = reinterpret_cast<int*>(T);
     float* Tw = T + 32 * 4;
@@ -471,6 +527,7 @@ __device__ __forceinline__ bool gather_geo_c(const float* __restrict__ planes, u
     const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
     f32x4 af[4] = {z4, z4, z4, z4}, ax[4] = {z4, z4, z4, z4}, ay[4] = {z4, z4, z4, z4}, az[4] = {z4, z4, z4, z4};
     bool any = false;
+    pmask = 0u;
 #pragma unroll
     for (int p = 0; p < 3; ++p) {
         Corners cn;
@@ -481,6 +538,7 @@ __device__ __forceinline__ bool gather_geo_c(const float* __restrict__ planes, u
             if ((threadIdx.x & 63) == 0) *inb += (unsigned)__popcll(inmask & 0xffffffffull);
         }
         if (inmask == 0) continue;  // exact: every contribution of this plane is 0 for the whole tile
+        pmask |= 1u << p;
         if (hi == 0) {
             const unsigned b = tex0 + (unsigned)(p * HW);
             const ti32x4 o = {(int)(b + cn.off[0]), (int)(b + cn.off[1]), (int)(b + cn.off[2]), (int)(b + cn.off[3])};
@@ -535,13 +593,15 @@ __device__ __forceinline__ bool gather_geo_c(const float* __restrict__ planes, u
 
 // texture planes, forward: e[48] as gather_tex
 __device__ __forceinline__ bool gather_tex_cp(const float* __restrict__ planes, unsigned tex0, int H, int W, float X,
-                                              float Y, float Z, bool valid, int lane, float* T, float (&e)[48]) {
+                                              float Y, float Z, bool valid, int lane, float* T, float (&e)[48],
+                                              unsigned& pmask) {
     const int i = lane & 31, hi = lane >> 5, js = lane >> 3, c = lane & 7;
     int* Toff = reinterpret_cast<int*>(T);
     float* Tw = T + 32 * 4;
     float* R = T + GC_PLANE_TABLE_FLOATS;
     const size_t HW = (size_t)H * W;
     bool any = false;
+    pmask = 0u;
 #pragma unroll
     for (int p = 0; p < 3; ++p) {
         Corners cn;
@@ -552,6 +612,7 @@ __device__ __forceinline__ bool gather_tex_cp(const float* __restrict__ planes, 
             for (int r = 0; r < 16; ++r) e[16 * p + r] = 0.f;
             continue;
         }
+        pmask |= 1u << p;
         if (hi == 0) {
             const unsigned b = tex0 + (unsigned)((3 + p) * HW);
             const ti32x4 o = {(int)(b + cn.off[0]), (int)(b + cn.off[1]), (int)(b + cn.off[2]), (int)(b + cn.off[3])};
@@ -583,13 +644,14 @@ __device__ __forceinline__ bool gather_tex_cp(const float* __restrict__ planes, 
 // prompts, and the lane that loads a texel is not the lane that owns the sample: the table holds absolute indices).
 __device__ __forceinline__ bool gather_tex_c(const float* __restrict__ planes, unsigned tex0, int H, int W, float X,
                                              float Y, float Z, bool valid, int lane, float* T, float (&e)[48],
-                                             unsigned* inb = nullptr) {
+                                             unsigned& pmask, unsigned* inb = nullptr) {
     const int i = lane & 31, hi = lane >> 5, js = lane >> 3, c = lane & 7;
     int* Toff = reinterpret_cast<int*>(T);
     float* Tw = T + 3 * 32 * 4;
     float* R = T + GC_TABLE_FLOATS(1);
     const size_t HW = (size_t)H * W;
     bool any = false, anyp[3];
+    pmask = 0u;
 #pragma unroll
     for (int p = 0; p < 3; ++p) {
         Corners cn;
@@ -599,6 +661,7 @@ __device__ __forceinline__ bool gather_tex_c(const float* __restrict__ planes, u
             if ((threadIdx.x & 63) == 0) *inb += (unsigned)__popcll(inmask & 0xffffffffull);
         }
         anyp[p] = inmask != 0;
+        pmask |= anyp[p] ? 1u << p : 0u;
         any = any || cn.any;
         if (hi == 0) {
             const unsigned b = tex0 + (unsigned)((3 + p) * HW);
@@ -664,7 +727,7 @@ __device__ __forceinline__ void geo_corner_coefs(int p, int H, int W, float X, f
 __device__ __forceinline__ bool gather_geo_bwd_c(const float* __restrict__ planes, unsigned tex0, int H, int W, float X,
                                                  float Y, float Z, bool valid, float sbar, float gux, float guy,
                                                  float guz, float jscale_u, float jscale_v, int lane, float* T,
-                                                 float (&f)[16], float (&u)[16], bool (&anyp)[3],
+                                                 float (&f)[16], float (&u)[16], unsigned& pmask,
                                                  unsigned* inb = nullptr) {
     const int i = lane & 31, hi = lane >> 5, js = lane >> 3, c = lane & 7;
     int* Toff = reinterpret_cast<int*>(T);
@@ -672,7 +735,8 @@ __device__ __forceinline__ bool gather_geo_bwd_c(const float* __restrict__ plane
     float* Tc = T + 2 * 3 * 32 * 4;
     float* R = T + GC_TABLE_FLOATS(2);
     const size_t HW = (size_t)H * W;
-    bool any = false;
+    bool any = false, anyp[3];
+    pmask = 0u;
 #pragma unroll
     for (int p = 0; p < 3; ++p) {
         Corners cn;
@@ -683,6 +747,7 @@ __device__ __forceinline__ bool gather_geo_bwd_c(const float* __restrict__ plane
             if ((threadIdx.x & 63) == 0) *inb += (unsigned)__popcll(inmask & 0xffffffffull);
         }
         anyp[p] = inmask != 0;
+        pmask |= anyp[p] ? 1u << p : 0u;
         any = any || cn.any;
         if (hi == 0) {
             const unsigned b = tex0 + (unsigned)(p * HW);

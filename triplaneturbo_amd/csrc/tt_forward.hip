@@ -147,7 +147,8 @@ __device__ __forceinline__ void decode_tex_fwd(const float* L, const DecodeCfg& 
                                                bool valid, int i, int hi, float (&c)[3]) {
     c[0] = c[1] = c[2] = 0.f;
     float e[48];
-    bool any = gather_tex_cp(dc.planes, dc.tex0, dc.H, dc.W, X, Y, Z, valid, 32 * hi + i, dc.T, e);
+    unsigned pmask;
+    bool any = gather_tex_cp(dc.planes, dc.tex0, dc.H, dc.W, X, Y, Z, valid, 32 * hi + i, dc.T, e, pmask);
     if (TT_DBG(dc.dbg, TT_DBG_NO_MLP)) {
         float t = 0.f;
 #pragma unroll
@@ -157,7 +158,17 @@ __device__ __forceinline__ void decode_tex_fwd(const float* L, const DecodeCfg& 
         // hidden vectors stay in RAW form (accumulators + a per-lane power-of-two factor, tt_mfma16.h): ReLU and the next
         // product's normalisation do not care, the factor is applied once to the three outputs
         float k1[32], k2[32], u1, u2;
-        mvx<PREC, 64, 96, true>(L + OFF_V1, L + LO_V1, e, k1, i, hi, 1.f, &u1);
+        if (single_plane(pmask)) {
+            // one plane with an in-bounds texel (tt_device.h, "plane mask"): the other 64 entries of e are exact zeros, so
+            // V1 e runs over the live plane's two k-steps and the exponent search over its 32 entries (same maximum, same
+            // scale, same operand bits: bit-identical k1)
+            tile_stat(dc.st, TT_STAT_SINGLE);
+            float e1[16];
+            live_block16(e, e1);
+            mvx_plane<PREC, 64, 96, true>(L + OFF_V1, L + LO_V1, e1, single_plane_index(pmask), k1, i, hi, &u1);
+        } else {
+            mvx<PREC, 64, 96, true>(L + OFF_V1, L + LO_V1, e, k1, i, hi, 1.f, &u1);
+        }
 #pragma unroll
         for (int r = 0; r < 32; ++r) k1[r] = fmaxf(k1[r], 0.f);
         mvx<PREC, 64, 64, true>(L + OFF_V2, L + LO_V2, k1, k2, i, hi, u1, &u2);
@@ -175,8 +186,9 @@ __device__ __forceinline__ void decode_geo_fwd(const float* L, const DecodeCfg& 
     s0 = 0.f;
     gq[0] = gq[1] = gq[2] = 0.f;
     float f[16], jx[16], jy[16], jz[16];
+    unsigned pmask;  // (the texture decode acts on its own gather's mask; the sdf net sees the sum of the planes)
     bool any = gather_geo_c<NEED_N>(dc.planes, dc.tex0, dc.H, dc.W, X, Y, Z, valid, dc.ju, dc.jv, 32 * hi + i, dc.T, f, jx,
-                                 jy, jz, tile_stat_ptr(dc.st, TT_STAT_INBOUNDS));
+                                 jy, jz, pmask, tile_stat_ptr(dc.st, TT_STAT_INBOUNDS));
     if (TT_DBG(dc.dbg, TT_DBG_NO_MLP)) {
         float t = 0.f, tx = 0.f, ty = 0.f, tz = 0.f;
 #pragma unroll
@@ -389,8 +401,9 @@ __global__ __launch_bounds__(64 * QueryFieldWaves<PREC>::value, PREC == PREC_S3 
         const float px = p.points[idx * 3 + 0], py = p.points[idx * 3 + 1], pz = p.points[idx * 3 + 2];
         const float X = scale_coord(px, p.radius), Y = scale_coord(py, p.radius), Z = scale_coord(pz, p.radius);
         float f[16], jx[16], jy[16], jz[16];
+        unsigned pmask;
         const bool any =
-            __any(gather_geo_c<false>(p.packed, tex0, p.H, p.W, X, Y, Z, valid, 0.f, 0.f, lane, T, f, jx, jy, jz));
+            __any(gather_geo_c<false>(p.packed, tex0, p.H, p.W, X, Y, Z, valid, 0.f, 0.f, lane, T, f, jx, jy, jz, pmask));
         float s0 = 0.f, d[3] = {0.f, 0.f, 0.f};
         if (any) {  // exact skip otherwise: bias-free MLPs of a zero vector
             float h1[32], h2[32];

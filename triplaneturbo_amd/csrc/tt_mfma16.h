@@ -327,6 +327,17 @@ __device__ __forceinline__ void split16_vec(const float (&x)[N / 2], float sc, S
             split_pair(as.x, as.y, o.h[t], o.l[t]);
     }
 }
+// the live 32-entry block of a split 96-entry vector whose other two blocks are exact zeros (single-plane tile steps,
+// tt_device.h): the pieces of +0 are +0, so a bitwise OR of the three blocks' dwords is the live block's split
+template <int NT>
+__device__ __forceinline__ void live_split32(const Split16<96, PAIR_SEQ, NT>& x, Split16<32, PAIR_SEQ, NT>& o) {
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        o.h[t] = x.h[t] | x.h[8 + t] | x.h[16 + t];
+        o.l[t] = x.l[t] | x.l[8 + t] | x.l[16 + t];
+        if constexpr (NT == 3) o.t[t] = x.t[t] | x.t[8 + t] | x.t[16 + t];
+    }
+}
 // mv16 on a pre-split operand: y = M x with x = (hi + lo) * un_x
 template <int NOUT, int NIN, bool RAW = false, int NT = 2>
 __device__ __forceinline__ void mv16_pre(const float* img_f, const Split16<NIN, PAIR_SEQ, NT>& x, float un_x,
@@ -363,6 +374,93 @@ __device__ __forceinline__ void mv16_pre(const float* img_f, const Split16<NIN, 
     for (int m = 0; m < MT; ++m)
 #pragma unroll
         for (int k = 0; k < 16; ++k) y[16 * m + k] = RAW ? acc[m][k] : acc[m][k] * un;
+}
+
+// ---- the same products over NK consecutive k-steps only (single-plane tile steps) ---------------------------------------
+// x holds the 16 NK entries of the k-steps s0 .. s0 + NK - 1 (s0 wave-uniform, known at run time); every other entry of the
+// full vector is an exact zero.  Same operand bits (the per-sample maximum is the maximum of these entries), same fragments,
+// same order: the accumulators see the full product's chain with its zero terms left out -- bit-identical results.
+template <int K>
+__device__ __forceinline__ h8_t lo_frag_rt(const half_t* lrow, int m, int s) {
+    constexpr int RSL = K + 8, KH = K / 32;
+    const int t = s >= KH ? 1 : 0;  // (s < 2 KH)
+    return *reinterpret_cast<const h8_t*>(lrow + (size_t)(32 * m) * RSL + 32 * (s - KH * t) + 16 * t);
+}
+template <int NOUT, int NIN, int NK, bool RAW = false, int NT = 2>
+__device__ __forceinline__ void mv16_ks(const float* img_f, const float (&x)[8 * NK], int s0, float (&y)[NOUT / 2], int i,
+                                        int hi, float xf = 1.f, float* yf = nullptr, const float* lo_f = nullptr) {
+    constexpr int MT = NOUT / 32, RS = 2 * NIN + 8;
+    const half_t* row = reinterpret_cast<const half_t*>(img_f) + (size_t)i * RS + 8 * hi + 32 * s0;
+    const half_t* lrow = reinterpret_cast<const half_t*>(lo_f) + (size_t)i * (NIN + 8) + 8 * hi;
+    const float wun = img_f[(size_t)i * (NIN + 4) + NIN];
+    float m = 0.f;
+#pragma unroll
+    for (int r = 0; r < 8 * NK; ++r) m = fmaxf(m, __builtin_fabsf(x[r]));
+    m = fmaxf(m, __shfl_xor(m, 32));
+    int E = (int)(__builtin_bit_cast(unsigned, m) >> 23);
+    E = E < 16 ? 16 : (E > 240 ? 240 : E);
+    const float sc = __builtin_bit_cast(float, (unsigned)(268 - E) << 23);
+    const float un = wun * __builtin_bit_cast(float, (unsigned)(E - 14) << 23) * xf;
+    f32x16 acc[MT];
+#pragma unroll
+    for (int mm = 0; mm < MT; ++mm)
+        acc[mm] = f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (TT_MV16_FENCE) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int s = 0; s < NK; ++s) {
+        h8_t bh, bl, bt;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) split_bfrag<NT, true>(x[8 * s + 2 * j], x[8 * s + 2 * j + 1], sc, j, bh, bl, bt);
+        h8_t ah[MT], al[MT], at[MT];
+#pragma unroll
+        for (int mm = 0; mm < MT; ++mm) {
+            const half_t* a = row + (size_t)(32 * mm) * RS + 32 * s;
+            ah[mm] = *reinterpret_cast<const h8_t*>(a);
+            al[mm] = *reinterpret_cast<const h8_t*>(a + 16);
+            if constexpr (NT == 3) at[mm] = lo_frag_rt<NIN>(lrow, mm, s0 + s);
+        }
+        mfma_terms<MT, NT>(acc, ah, al, at, bh, bl, bt);
+    }
+    if (RAW) *yf = un;
+#pragma unroll
+    for (int mm = 0; mm < MT; ++mm)
+#pragma unroll
+        for (int k = 0; k < 16; ++k) y[16 * mm + k] = RAW ? acc[mm][k] : acc[mm][k] * un;
+}
+// ... and on a pre-split operand (mv16_pre): x = the split of the 16 NK live entries under the per-launch scale
+template <int NOUT, int NIN, int NK, int NT = 2>
+__device__ __forceinline__ void mv16_pre_ks(const float* img_f, const Split16<16 * NK, PAIR_SEQ, NT>& x, int s0, float un_x,
+                                            float (&y)[NOUT / 2], int i, int hi, const float* lo_f = nullptr) {
+    constexpr int MT = NOUT / 32, RS = 2 * NIN + 8;
+    const half_t* row = reinterpret_cast<const half_t*>(img_f) + (size_t)i * RS + 8 * hi + 32 * s0;
+    const half_t* lrow = reinterpret_cast<const half_t*>(lo_f) + (size_t)i * (NIN + 8) + 8 * hi;
+    const float un = img_f[(size_t)i * (NIN + 4) + NIN] * un_x;
+    f32x16 acc[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+        acc[m] = f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    typedef unsigned u4_t __attribute__((ext_vector_type(4)));
+#pragma unroll
+    for (int s = 0; s < NK; ++s) {
+        const h8_t bh = __builtin_bit_cast(h8_t, u4_t{x.h[4 * s], x.h[4 * s + 1], x.h[4 * s + 2], x.h[4 * s + 3]});
+        const h8_t bl = __builtin_bit_cast(h8_t, u4_t{x.l[4 * s], x.l[4 * s + 1], x.l[4 * s + 2], x.l[4 * s + 3]});
+        h8_t bt;
+        if constexpr (NT == 3)
+            bt = __builtin_bit_cast(h8_t, u4_t{x.t[4 * s], x.t[4 * s + 1], x.t[4 * s + 2], x.t[4 * s + 3]});
+        h8_t ah[MT], al[MT], at[MT];
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            const half_t* a = row + (size_t)(32 * m) * RS + 32 * s;
+            ah[m] = *reinterpret_cast<const h8_t*>(a);
+            al[m] = *reinterpret_cast<const h8_t*>(a + 16);
+            if constexpr (NT == 3) at[m] = lo_frag_rt<NIN>(lrow, m, s0 + s);
+        }
+        mfma_terms<MT, NT>(acc, ah, al, at, bh, bl, bt);
+    }
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int k = 0; k < 16; ++k) y[16 * m + k] = acc[m][k] * un;
 }
 
 // ---- TRANSPOSED products from the forward image: y = M^T x without a second (transposed) image ----------------------------
@@ -544,6 +642,18 @@ __device__ __forceinline__ void mvtx(const float* img, const float* lo, int col0
     }
 }
 
+// ---- single-plane forms (a tile step whose plane mask has one bit, tt_device.h) -----------------------------------------
+// y[NOUT] = M[NOUT][32 pl .. 32 pl + 31] x1, x1 = the 32 live entries of the 96-entry input (the other 64 are exact zeros)
+template <int PREC, int NOUT, int NIN, bool RAW = false>
+__device__ __forceinline__ void mvx_plane(const float* img, const float* lo, const float (&x1)[16], int pl,
+                                          float (&y)[NOUT / 2], int i, int hi, float* yf = nullptr) {
+    if constexpr (PREC == PREC_F32) {
+        mv_fwd_cols<NOUT, NIN, 4>(img, x1, 4 * pl, y, i, hi);
+        if (RAW) *yf = 1.f;
+    } else {
+        mv16_ks<NOUT, NIN, 2, RAW, PrecNT<PREC>::value>(img, x1, 2 * pl, y, i, hi, 1.f, yf, lo);
+    }
+}
 // ---- LDS map of the third-term images (PREC_S3) of the forward-shaped kernels: appended to the fp32-sized map of
 // tt_device.h (OFF_W1 ... LDS_W_FLOATS), so the (hi, mid) images keep their offsets in every mode ----
 #define LO_W1 LDS_W_FLOATS
