@@ -79,8 +79,8 @@ names = ["upstream cbar + skip test", "gather e (12 corners)", "park e in LDS", 
          "", "", "", "", "",  # (slots 12..16 carry the live-lane / scatter statistics printed above)
          "end of tile step -> pop", "item pop (queue atomic)", "ray set-up (issue)"]
 geo_names = ["upstream (d sdf, d sdf_grad) + skip test", "gather f, u (12 corners)", "", "sdf net recompute + reverse chain (5 products)",
-             "a1bar = W1 qbar, v", "a2bar = W2 b1bar, dw3 (transpose + VALU)", "", "dW1 outer products",
-             "dW2 outer products", "scatter: q staging + corner set-up", "scatter epilogue", "tail",
+             "a1bar = W1 qbar, v", "", "", "dW1 outer products",
+             "D = m2 v^T outer products (dW2, dw3)", "scatter: q staging + corner set-up", "scatter epilogue", "tail",
              "", "", "", "", "", "  (of the epilogue) operands -> registers, next plane's set-up, operand split + MFMAs",
              "  (of the epilogue) next plane's slot claims", "  (of the epilogue) flush atomics, tag reset, lost references"]
 print(f"texture backward: {buf[12] / n / 1024:.0f} live tile steps per wave per launch, {buf[13] / max(buf[12], 1):.1f} of 32 lanes live on average, {buf[14] / max(buf[12], 1):.1f} with |cbar| > 1e-12")

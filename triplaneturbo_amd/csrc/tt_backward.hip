@@ -6,6 +6,11 @@
 //       input-gradient chain of the sdf net (the reference's second-order path: gridsample_cuda.cu:27-210 +
 //       aten grid_sampler_2d_backward + transposed GEMMs), accumulates dW1/dW2 with MFMA outer products
 //       (K = the 32 samples of the tile) and scatters d/d planes 0..2.
+//       Row-scaling identity of the last hidden layer: with m2 the 0/1 mask of h2 = relu(W2 h1), a2 = m2 . w3 and
+//       v = sbar h1 + b1bar, the kernel accumulates only D = sum_samples m2 v^T, and at its end
+//           dW2_ij = w3_i D_ij            dw3_i = sum_j W2_ij D_ij
+//       (h2_i = m2_i (W2 h1)_i, and m2 depends on neither w3 nor the upstream: exact, second-order chain and rows with
+//       w3_i = 0 included, no division).  The reference's sixth product W2 b1bar has no other consumer and is not formed.
 //   k_decode_bwd_tex : feature net backward, dV1/dV2/dV3, scatter of d/d planes 3..5.
 // Both are purely per-sample: tiles are 32 adjacent rays at one sample index (see tt_device.h).
 //
@@ -67,7 +72,7 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
         stage_weights_t<PREC, 64, 64>(L + GOFF_W2T, L + GLO_W2T, w.w2);
     }
     const tt_render_cfg& cfg = p.cfg;
-    // ---- per-launch operand scales of the fp16 outer products dW1 += a1 u^T, dW2 += a2 v^T (wgrad16 above) ----
+    // ---- per-launch operand scales of the fp16 outer products dW1 += a1 u^T, D += m2 v^T (wgrad16 above; m2 is 0/1: no scale) ----
     // rigorous magnitude bounds from the weights and the launch's maxima (planes, upstream: reduced on the stream in front
     // of this kernel into the queue slot, tt_host.h):   |a2| <= max |w3|,   |a1_j| <= sum_i |W2[i][j]| |w3_i|,
     //   |f| <= 3 P,  |h1| <= max_i ||W1_i||_1 3 P,  |u| = |sum_corners coef texel| <= 3 P (Sb + 2 (ju + jv) Gb)  (the four
@@ -120,7 +125,6 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
     const TileStats st = STATS ? tile_stats(cfg.stats) : TileStats{nullptr};
     f32x16 accW1[2][1] = {{ZERO16}, {ZERO16}};
     f32x16 accW2[2][2] = {{ZERO16, ZERO16}, {ZERO16, ZERO16}};
-    float accw3 = 0.f;
 #ifdef TT_TUNING
     unsigned long long ph_acc[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long ph_t = __builtin_amdgcn_s_memtime();
@@ -191,13 +195,14 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
             // the scatter knows -- the other two planes' coefficients are exact zeros and their passes flush nothing
             const bool one = single_plane(pmask);
             tile_stat_executed(st, one);
-            // h1, h2 (and a1 under WG16) stay in RAW form: accumulators + a per-lane power-of-two factor (tt_mfma16.h,
-            // "deferred factors"); their consumers are signs, the next product, and fmas that take the factor on the scalar
-            float h1[32], h2[32], a2[32], a1[32], q[16], u1, u2;
+            // h1 (and a1 under WG16) stay in RAW form: accumulators + a per-lane power-of-two factor (tt_mfma16.h,
+            // "deferred factors"); their consumers are signs, the next product, and fmas that take the factor on the scalar;
+            // h2 is used for its sign only (its factor uh2 is dead)
+            float h1[32], h2[32], a2[32], a1[32], q[16], u1, uh2;
             mvx<PREC, 64, 32, true>(L + OFF_W1, L + GLO_W1, f, h1, i, hi, 1.f, &u1);
 #pragma unroll
             for (int r = 0; r < 32; ++r) h1[r] = fmaxf(h1[r], 0.f);
-            mvx<PREC, 64, 64, true>(L + OFF_W2, L + GLO_W2, h1, h2, i, hi, u1, &u2);
+            mvx<PREC, 64, 64, true>(L + OFF_W2, L + GLO_W2, h1, h2, i, hi, u1, &uh2);
 #pragma unroll
             for (int r = 0; r < 32; ++r) h2[r] = fmaxf(h2[r], 0.f);
 #pragma unroll
@@ -206,8 +211,8 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
 #pragma unroll
                 for (int e2 = 0; e2 < 4; ++e2) a2[4 * g + e2] = h2[4 * g + e2] > 0.f ? w3[e2] : 0.f;
             }
-            // a2 and a1 feed a product AND an outer product (dW2, dW1): split once under the per-launch scales
-            Split16<64, PAIR_SEQ, NT> a2s, a1s;  // (consumed by the transposed products and the outer-product staging)
+            // a1 feeds a product AND an outer product (dW1): split once under the per-launch scale; a2 feeds W2^T a2 only
+            Split16<64, PAIR_SEQ, NT> a2s, a1s;
             float ua1 = 1.f;                     // factor of a1 where it is RAW
             if (WG16) {
                 split16_vec<64, PAIR_SEQ, NT>(a2, sA2, a2s);
@@ -255,27 +260,19 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
 #pragma unroll
                 for (int r = 0; r < 32; ++r) v[r] = fmaf(sbar * u1, h1[r], t1[r]);
                 TT_PHASE(4);
-                // dW2 += a2 v^T
+                // D += m2 v^T: dW2 and dw3 both come out of it at the kernel-end flush (row-scaling identity, top of file)
                 if (do_wgrad) {
                     if (WG16) {
-                        stage_rows16_pre<64>(Xs, a2s, i, hi);
+                        stage_rows16_mask<64>(Xs, h2, i, hi);
                         stage_rows16<64>(Ys, v, i, hi, sV);
-                        wgrad16<64, 64>(accW2, Xs, Ys, i, hi);
+                        wgrad16_mask<64, 64>(accW2, Xs, Ys, i, hi);
                     } else {
-                        stage_rows<64>(Xs, a2, i, hi);
+                        stage_rows_mask<64>(Xs, h2, i, hi);
                         stage_rows<64>(Ys, v, i, hi);
                         wgrad<64, 64>(accW2, Xs, Ys, i, hi);
                     }
                 }
                 TT_PHASE(8);
-                // a2bar = W2 b1bar ; dw3 += sbar h2 + m2 . a2bar
-                float t2[32];
-                mvx<PREC, 64, 64>(L + OFF_W2, L + GLO_W2, t1, t2, i, hi);
-#pragma unroll
-                for (int r = 0; r < 32; ++r) t2[r] = fmaf(sbar * u2, h2[r], h2[r] > 0.f ? t2[r] : 0.f);
-                stage_rows<64>(Xs, t2, i, hi);
-                accw3 += rowsum32(Xs, lane);
-                TT_PHASE(5);
                 // ---- scatter d/d geometry planes: texel(p,c)[ch] += q[ch] * coef(p,c) ----
                 if (region && !TT_DBG(cfg.flags, TT_DBG_NO_SCATTER)) {
                     scatter_clear<EXACT>(Xs, lane);  // M = 0 (Xs held wgrad staging; SCATTER_M_FLOATS reach into Ys)
@@ -318,8 +315,7 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
     __syncthreads();
     int parity = 0;
     flush_wgrad_reduced<64, 32>(L, parity, accW1, p.grads.w1, wave_in_blk, lane, 1.f / sA1, 1.f / sU);
-    flush_wgrad_reduced<64, 64>(L, parity, accW2, p.grads.w2, wave_in_blk, lane, 1.f / sA2, 1.f / sV);
-    atomicAdd(p.grads.w3 + lane, accw3);
+    flush_d_reduced<64, 64>(L, parity, accW2, p.w.w2, p.w.w3, p.grads.w2, p.grads.w3, wave_in_blk, lane, 1.f / sV);
     tile_stats_flush(st);
 }
 

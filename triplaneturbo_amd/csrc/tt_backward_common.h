@@ -40,6 +40,12 @@ __device__ __forceinline__ void stage_rows_sub(float* S, const float (&v)[TOT], 
 #pragma unroll
     for (int r = 0; r < N / 2; ++r) S[LIDX(r, hi) * XS + j] = v[OFF + r];
 }
+// the 0/1 mask (v > 0) of a register vector as 1.0f / 0.0f rows: one compare + one select per entry (tt_mask.h)
+template <int N>
+__device__ __forceinline__ void stage_rows_mask(float* S, const float (&v)[N / 2], int j, int hi) {
+#pragma unroll
+    for (int r = 0; r < N / 2; ++r) S[LIDX(r, hi) * XS + j] = v[r] > 0.f ? 1.f : 0.f;
+}
 
 // acc[m][n] += X[32m.., s] * Y[32n.., s]^T summed over the 32 samples s of the tile
 template <int NX, int NY>
@@ -80,17 +86,6 @@ __device__ __forceinline__ void wgrad_row(f32x16 (&acc)[NY / 32], const float* X
             for (int n = 0; n < NY / 32; ++n)
                 acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(xa[k], yb[n][k], acc[n], 0, 0, 0);
     }
-}
-
-// row sum over the 32 samples of scratch row `lane` (lane <-> index 0..63)
-__device__ __forceinline__ float rowsum32(const float* Xs, int lane) {
-    float s = 0.f;
-#pragma unroll
-    for (int g = 0; g < 8; ++g) {
-        f32x4 a = *reinterpret_cast<const f32x4*>(Xs + lane * XS + 4 * g);
-        s += (a[0] + a[1]) + (a[2] + a[3]);
-    }
-    return s;
 }
 
 // ---- weight-gradient outer products on the fp16 pipe -----------------------------------------------------------------
@@ -147,6 +142,14 @@ __device__ __forceinline__ void stage_rows16_pre(float* S, const Split16<N, PAIR
         U[LIDX(pair_reg<PAIR>(t, 1), hi) * XS + j] = __builtin_amdgcn_perm(v.l[t], v.h[t], 0x07060302u);
     }
 }
+// the 0/1 mask (v > 0) of a register vector as the X operand of wgrad16_mask: 1.0 is exact in ONE fp16 piece, and the dword
+// (1.0 | 1.0 << 16) puts it into both k-slots of the sample.  One compare + one select per entry (tt_mask.h)
+template <int N>
+__device__ __forceinline__ void stage_rows16_mask(float* S, const float (&v)[N / 2], int j, int hi) {
+    unsigned* U = reinterpret_cast<unsigned*>(S);
+#pragma unroll
+    for (int r = 0; r < N / 2; ++r) U[LIDX(r, hi) * XS + j] = v[r] > 0.f ? 0x3C003C00u : 0u;
+}
 __device__ __forceinline__ h8_t wg16_frag(const float* S, int row, int t, int hi) {
     return __builtin_bit_cast(h8_t, *reinterpret_cast<const u32x4*>(S + row * XS + 8 * t + 4 * hi));
 }
@@ -179,6 +182,25 @@ __device__ __forceinline__ void wgrad16(f32x16 (&acc)[NX / 32][NY / 32], const f
 #pragma unroll
             for (int n = 0; n < NY / 32; ++n)
                 acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(xa[m], ys[n], acc[m][n], 0, 0, 0);
+    }
+}
+// X staged by stage_rows16_mask: mfma(A, B) = sum_s m (hi_y + lo_y) is already the full product, so the pass with the
+// rotated B operand falls away -- 4 MFMAs per 32 x 32 tile
+template <int NX, int NY>
+__device__ __forceinline__ void wgrad16_mask(f32x16 (&acc)[NX / 32][NY / 32], const float* Xs, const float* Ys, int i,
+                                             int hi) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        h8_t xa[NX / 32], yb[NY / 32];
+#pragma unroll
+        for (int m = 0; m < NX / 32; ++m) xa[m] = wg16_frag(Xs, 32 * m + i, t, hi);
+#pragma unroll
+        for (int n = 0; n < NY / 32; ++n) yb[n] = wg16_frag(Ys, 32 * n + i, t, hi);
+#pragma unroll
+        for (int m = 0; m < NX / 32; ++m)
+#pragma unroll
+            for (int n = 0; n < NY / 32; ++n)
+                acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(xa[m], yb[n], acc[m][n], 0, 0, 0);
     }
 }
 // one 32-row slice of the left operand (see wgrad_row)
@@ -258,6 +280,45 @@ __device__ __forceinline__ void flush_wgrad_reduced(float* R, int& parity, const
                                [&](int r) { return dst + (32 * m + LIDX(r, hi)) * NY + 32 * n + i; });
             parity ^= 1;
         }
+}
+
+// The last layer of a bias-free ReLU net from ONE accumulator: acc = D = sum_samples m v^T with m the 0/1 mask of the
+// layer's output (tt_backward.hip, "row-scaling identity").  Per reduced 32 x 32 tile of D * uy:
+//     dW[row][col] += wo[row] * D[row][col]          dwo[row] += sum_col W[row][col] * D[row][col]
+// W (NX x NY) and wo (NX) are read in fp32 from memory (L2-resident, once per workgroup).  A thread holds the same four
+// rows in every column tile, so the row sums are carried over n and leave as one atomic per row and workgroup.
+template <int NX, int NY>
+__device__ __forceinline__ void flush_d_reduced(float* R, int& parity, const f32x16 (&acc)[NX / 32][NY / 32],
+                                                const float* __restrict__ W, const float* __restrict__ wo,
+                                                float* __restrict__ dW, float* __restrict__ dwo, int wave, int lane,
+                                                float uy) {
+    const int i = lane & 31, hi = lane >> 5;
+#pragma unroll
+    for (int m = 0; m < NX / 32; ++m) {
+        float part[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int n = 0; n < NY / 32; ++n) {
+            float* B = R + parity * 4096;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) B[(wave * 16 + r) * 64 + lane] = acc[m][n][r] * uy;
+            __syncthreads();
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int r = 4 * wave + q, at = (32 * m + LIDX(r, hi)) * NY + 32 * n + i;
+                const float d = (B[r * 64 + lane] + B[(16 + r) * 64 + lane]) + (B[(32 + r) * 64 + lane] + B[(48 + r) * 64 + lane]);
+                atomicAdd(dW + at, wo[32 * m + LIDX(r, hi)] * d);
+                part[q] = fmaf(W[at], d, part[q]);
+            }
+            parity ^= 1;
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            float s = part[q];
+#pragma unroll
+            for (int o = 16; o > 0; o >>= 1) s += __shfl_xor(s, o);  // over the 32 columns of this half-wave's row
+            if (i == 0) atomicAdd(dwo + 32 * m + LIDX(4 * wave + q, hi), s);
+        }
+    }
 }
 
 #define ZERO16 \

@@ -31,7 +31,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define TT_DBG(flags, bit) false
 #endif
 #define TT_DBG_NO_SCATTER 0x100
-#define TT_DBG_NO_WGRAD 0x200
+#define TT_DBG_NO_WGRAD 0x200 /* also zeroes the geometry dw3: it comes out of the dW2 accumulators (tt_backward.hip) */
 #define TT_DBG_NO_GATHER 0x400
 #define TT_DBG_NO_MLP 0x800
 #define TT_DBG_NO_STORE 0x1000
