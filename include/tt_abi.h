@@ -286,6 +286,16 @@ int tt_render_fwd(const float* packed, const tt_mlp_weights* w, const float* ray
                   float* rgb_fg, float* z_variance, float* normal_acc, float* weights, float* trans, float* sdf,
                   float* sdf_grad, float* features, void* stream);
 
+/* tt_render_fwd that also writes h2_mask (n_rays*S, 2) uint32: the signs of the sdf net's last hidden layer,
+ * h2 = relu(W2 relu(W1 f)), as the forward computed them.  Dword 2*sample + hi (hi = 0, 1) holds bit r =
+ * (h2[(r & 3) + 8 * (r >> 2) + 4 * hi] > 0), r = 0..31 -- the register layout both decode kernels keep h2 in.  Every
+ * sample's two dwords are written (0 where the tile step had no in-bounds texel).  Same arithmetic and outputs as
+ * tt_render_fwd; the mask is the extra saved state of tt_render_bwd_geo_h2mask. */
+int tt_render_fwd_h2mask(const float* packed, const tt_mlp_weights* w, const float* rays_o, const float* rays_d,
+                         const float* t_starts, const float* t_ends, const tt_render_cfg* cfg, float* opacity,
+                         float* depth, float* rgb_fg, float* z_variance, float* normal_acc, float* weights, float* trans,
+                         float* sdf, float* sdf_grad, float* features, uint32_t* h2_mask, void* stream);
+
 /* Eval-mode render (the renderer returns no per-sample tensors outside training, renderer :532-545): the per-ray outputs
  * of tt_render_fwd from ONE kernel that decodes and marches each 8x4-pixel ray tile front to back.
  * transmittance_eps > 0: a ray stops contributing once its transmittance is below it and a tile stops when all its rays
@@ -332,6 +342,18 @@ int tt_render_bwd_geo(const float* packed, const tt_mlp_weights* w, const float*
                       const float* g_z_variance, const float* g_normal_acc, const float* g_weights,
                       const float* g_sdf, const float* g_sdf_grad, float* g_inv_std_rays, float* workspace,
                       float* grad_packed, const tt_mlp_grads* grads, void* stream);
+
+/* tt_render_bwd_geo with the h2 sign mask of tt_render_fwd_h2mask (same planes, weights, rays and intervals as that
+ * call): the decode backward reads the signs instead of recomputing W2 h1 for them.  Gradients agree with
+ * tt_render_bwd_geo up to the rounding of a pre-activation within an ulp of zero. */
+int tt_render_bwd_geo_h2mask(const float* packed, const tt_mlp_weights* w, const float* rays_o, const float* rays_d,
+                             const float* t_starts, const float* t_ends, const tt_render_cfg* cfg,
+                             const float* opacity, const float* depth, const float* trans, const float* sdf,
+                             const float* sdf_grad, const float* features, const float* g_opacity,
+                             const float* g_depth, const float* g_rgb_fg, const float* g_z_variance,
+                             const float* g_normal_acc, const float* g_weights, const float* g_sdf,
+                             const float* g_sdf_grad, float* g_inv_std_rays, float* workspace, float* grad_packed,
+                             const tt_mlp_grads* grads, const uint32_t* h2_mask, void* stream);
 
 /* Backward, texture half: d/d(texture planes 3..5) and d/d(feature net).
  * Needs saved weights (per sample) and features; g_rgb_fg (per ray), g_features (per sample; null = 0). */

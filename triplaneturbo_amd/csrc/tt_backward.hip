@@ -11,6 +11,10 @@
 //           dW2_ij = w3_i D_ij            dw3_i = sum_j W2_ij D_ij
 //       (h2_i = m2_i (W2 h1)_i, and m2 depends on neither w3 nor the upstream: exact, second-order chain and rows with
 //       w3_i = 0 included, no division).  The reference's sixth product W2 b1bar has no other consumer and is not formed.
+//       Mask products: nothing reads h2's values, so (i) a1 = m1 . W2^T (m2 . w3) is formed as m1 . (C^T m2) with the launch
+//       constant C = diag(w3) W2 staged once per workgroup and the 0/1 mask as the B operand (half the MFMAs, no split of a2),
+//       and (ii) the FMASK instantiations take m2 from the forward (tt_render_fwd_h2mask: 8 bytes per sample) instead of
+//       recomputing W2 h1 for its signs.  The fp32-MFMA mode keeps its fp32 product W2^T (m2 . w3).
 //   k_decode_bwd_tex : feature net backward, dV1/dV2/dV3, scatter of d/d planes 3..5.
 // Both are purely per-sample: tiles are 32 adjacent rays at one sample index (see tt_device.h).
 //
@@ -32,6 +36,7 @@ struct BwdGeoParams {
     long long n_items;
     int* queue;  // per-XCD item counters (tt_queue_counters)
     const float* ws;  // (n_rays*S, 4): d/d sdf, d/d sdf_grad xyz  (from k_march_bwd)
+    const unsigned* h2_mask;  // (n_rays*S, 2): sign masks of h2 from tt_render_fwd_h2mask (FMASK instantiations), else null
     int n_copies;     // privatised copies of grad_packed
     float* grad_packed;
     MlpGradPtrs grads;
@@ -39,66 +44,69 @@ struct BwdGeoParams {
 };
 
 #define GEO_SCRATCH_FLOATS (2 * 64 * XS)
-// split-fp16 weight images (tt_mfma16.h): W1, W2 at their fp32 offsets (same bytes); the transposed products use
-// transposed COPIES appended to them (tt_backward_common.h: 26 KB of LDS nothing else wants at one wave per SIMD)
-#define GOFF_W1T LDS_GEO_FLOATS
-#define GOFF_W2T (GOFF_W1T + IMG16_FLOATS(32, 64))
-#define LDS_GEO16_FLOATS (GOFF_W2T + IMG16_FLOATS(64, 64))
-// PREC_S3: the images of the third terms, appended (28 KB with the transposed copies: 157 KB per workgroup in all)
-#define GLO_W1 LDS_GEO16_FLOATS
-#define GLO_W2 (GLO_W1 + LO16_FLOATS(64, 32))
-#define GLO_W1T (GLO_W2 + LO16_FLOATS(64, 64))
-#define GLO_W2T (GLO_W1T + LO16_FLOATS(32, 64))
-#define LDS_GEO3_FLOATS (GLO_W2T + LO16_FLOATS(64, 64))
-template <int PREC>
-struct GeoWFloats {
-    static constexpr int value = PREC == PREC_S3 ? LDS_GEO3_FLOATS : LDS_GEO16_FLOATS;
+// LDS map of the weight images.  Split-fp16 images (tt_mfma16.h) of W1, W2 sit where the fp32 images would (same bytes); the
+// transposed products use transposed COPIES appended to them (tt_backward_common.h: LDS nothing else wants at one wave per
+// SIMD): W1^T, and C^T for C = diag(w3) W2 in place of W2^T.  PREC_S3 appends the images of the third terms.
+// NOW2 (the split modes with the forward's h2 mask): W2 h1 is not formed, so W2 has no image at all.
+template <int PREC, bool FMASK>
+struct GeoMap {
+    static constexpr bool NOW2 = FMASK && PREC != PREC_F32;
+    static constexpr int W1 = 0, W2 = W1 + 64 * W1S, W3 = W2 + (NOW2 ? 0 : 64 * W2S);
+    static constexpr int W1T = W3 + 64, CT = W1T + IMG16_FLOATS(32, 64), END16 = CT + IMG16_FLOATS(64, 64);
+    static constexpr int L3_W1 = END16, L3_W2 = L3_W1 + LO16_FLOATS(64, 32);
+    static constexpr int L3_W1T = L3_W2 + (NOW2 ? 0 : LO16_FLOATS(64, 64)), L3_CT = L3_W1T + LO16_FLOATS(32, 64);
+    static constexpr int END3 = L3_CT + LO16_FLOATS(64, 64);
+    static constexpr int FLOATS = PREC == PREC_S3 ? END3 : END16;
 };
 
 // STATS: the work accounting (tt_render_cfg.stats) compiled in.  In this kernel even a never-taken scalar branch per
 // counting site costs 2-3 % (2.95 vs 2.85 ms: the branches cut hipcc's scheduling regions), so production launches
 // (stats == null) run the instantiation without it.
-template <int PREC, bool WG16, bool STATS = false>
+// FMASK: the sign mask of h2 = relu(W2 h1) comes from the forward (p.h2_mask) instead of being recomputed: nothing here
+// reads h2's values (row-scaling identity, top of file).
+template <int PREC, bool WG16, bool STATS = false, bool FMASK = false>
 __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
     constexpr bool EXACT = PREC == PREC_F32;
-    constexpr int NT = PrecNT<PREC>::value, WF = GeoWFloats<PREC>::value;
+    typedef GeoMap<PREC, FMASK> G;
+    constexpr int NT = PrecNT<PREC>::value, WF = G::FLOATS;
     __shared__ __attribute__((aligned(16))) float L[WF + 4 * (GEO_SCRATCH_FLOATS + SCATTER_TAG_INTS)];
     {
         MlpPtrs w = p.w;
-        stage_weights<PREC, 64, 32>(L + OFF_W1, L + GLO_W1, w.w1);
-        stage_weights<PREC, 64, 64>(L + OFF_W2, L + GLO_W2, w.w2);
-        lds_load_matrix(L + OFF_W3, w.w3, 1, 64, 64);
-        stage_weights_t<PREC, 64, 32>(L + GOFF_W1T, L + GLO_W1T, w.w1);
-        stage_weights_t<PREC, 64, 64>(L + GOFF_W2T, L + GLO_W2T, w.w2);
+        stage_weights<PREC, 64, 32>(L + G::W1, L + G::L3_W1, w.w1);
+        if constexpr (!G::NOW2) stage_weights<PREC, 64, 64>(L + G::W2, L + G::L3_W2, w.w2);
+        lds_load_matrix(L + G::W3, w.w3, 1, 64, 64);
+        stage_weights_t<PREC, 64, 32>(L + G::W1T, L + G::L3_W1T, w.w1);
+        // C^T for C = diag(w3) W2 where W2^T used to sit (it had no other reader): a1 = m1 . (C^T m2) is then a product of a
+        // launch constant with a 0/1 mask (mv16_mask).  PREC_F32 keeps its fp32 product W2^T (m2 . w3) from the W2 image.
+        if constexpr (!EXACT)
+            stage_image16_rowscaled_t<64, 64, NT>(L + G::CT, w.w2, w.w3, 64, L + G::L3_CT);
     }
     const tt_render_cfg& cfg = p.cfg;
     // ---- per-launch operand scales of the fp16 outer products dW1 += a1 u^T, D += m2 v^T (wgrad16 above; m2 is 0/1: no scale) ----
     // rigorous magnitude bounds from the weights and the launch's maxima (planes, upstream: reduced on the stream in front
-    // of this kernel into the queue slot, tt_host.h):   |a2| <= max |w3|,   |a1_j| <= sum_i |W2[i][j]| |w3_i|,
+    // of this kernel into the queue slot, tt_host.h):   |a1_j| <= sum_i |W2[i][j]| |w3_i|,
     //   |f| <= 3 P,  |h1| <= max_i ||W1_i||_1 3 P,  |u| = |sum_corners coef texel| <= 3 P (Sb + 2 (ju + jv) Gb)  (the four
     //   bilinear weights of a plane sum to <= 1, their derivatives to <= 2 per axis),  |qbar| = |u - sbar f| <= 3 P 2 (ju +
     //   jv) Gb,  |b1bar| <= max_i ||W1_i||_1 |qbar|,  |v| = |sbar h1 + b1bar|.
-    float sA1 = 1.f, sU = 1.f, sA2 = 1.f, sV = 1.f;
+    float sA1 = 1.f, sU = 1.f, sV = 1.f;
     if (WG16) {
         const unsigned* bnd = reinterpret_cast<const unsigned*>(p.queue) + TT_SLOT_BOUNDS;
         const float Pm = __builtin_bit_cast(float, bnd[TT_BOUND_PLANES]), Sb = __builtin_bit_cast(float, bnd[TT_BOUND_UP0]),
                     Gb = __builtin_bit_cast(float, bnd[TT_BOUND_UP1]);
         unsigned* word = reinterpret_cast<unsigned*>(L + WF);  // scratch is free until the main loop
         const int t = threadIdx.x;
-        float w1row = 0.f, a1col = 0.f, w3abs = 0.f;
+        float w1row = 0.f, a1col = 0.f;
         if (t < 64) {
             for (int c = 0; c < 32; ++c) w1row += __builtin_fabsf(p.w.w1[t * 32 + c]);
             for (int r = 0; r < 64; ++r) a1col += __builtin_fabsf(p.w.w2[r * 64 + t]) * __builtin_fabsf(p.w.w3[r]);
-            w3abs = __builtin_fabsf(p.w.w3[t]);
         }
-        const float W1max = block_max(w1row, word), A1max = block_max(a1col, word), A2max = block_max(w3abs, word);
+        const float W1max = block_max(w1row, word), A1max = block_max(a1col, word);
         const float jsum = (0.5f * cfg.plane_w + 0.5f * cfg.plane_h) / cfg.radius;
         const float Fmax = 3.f * Pm, H1max = W1max * Fmax;
         const float Umax = Fmax * (Sb + 2.f * jsum * Gb), QBmax = Fmax * 2.f * jsum * Gb;
         const float Vmax = Sb * H1max + W1max * QBmax;
         sA1 = wg16_scale(A1max);
         sU = wg16_scale(Umax);
-        sA2 = wg16_scale(A2max);
         sV = wg16_scale(Vmax);
     }
     const TileGeom& tg = p.geom;
@@ -152,6 +160,7 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
         struct StepIn {
             f32x4 up;  // upstream (from the march backward): d/d sdf and d/d sdf_grad of this sample
             float ts, te;
+            unsigned m2;  // FMASK: this lane's dword of the forward's h2 sign mask
         };
         auto load_step = [&](int sb0) {
             StepIn r;
@@ -160,6 +169,7 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
             r.up = *reinterpret_cast<const f32x4*>(p.ws + sidx * 4);
             r.ts = p.rays_d ? p.t_starts[sidx] : 0.f;
             r.te = p.rays_d ? p.t_ends[sidx] : 0.f;
+            r.m2 = FMASK ? p.h2_mask[2 * sidx + hi] : 0u;
             return r;
         };
         StepIn in = load_step(ck * tg.chunk), in_next;
@@ -198,35 +208,50 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
             // h1 (and a1 under WG16) stay in RAW form: accumulators + a per-lane power-of-two factor (tt_mfma16.h,
             // "deferred factors"); their consumers are signs, the next product, and fmas that take the factor on the scalar;
             // h2 is used for its sign only (its factor uh2 is dead)
-            float h1[32], h2[32], a2[32], a1[32], q[16], u1, uh2;
-            mvx<PREC, 64, 32, true>(L + OFF_W1, L + GLO_W1, f, h1, i, hi, 1.f, &u1);
+            float h1[32], h2[32], a1[32], q[16], u1, uh2;
+            mvx<PREC, 64, 32, true>(L + G::W1, L + G::L3_W1, f, h1, i, hi, 1.f, &u1);
 #pragma unroll
             for (int r = 0; r < 32; ++r) h1[r] = fmaxf(h1[r], 0.f);
-            mvx<PREC, 64, 64, true>(L + OFF_W2, L + GLO_W2, h1, h2, i, hi, u1, &uh2);
+            // FMASK: bit r of the lane's mask word is (h2[r] > 0) as the forward saw it; a lane that is not rvalid loaded
+            // another sample's word from the clamped address: forced to 0 through the 0/1 validity factor
+            const unsigned m2w = FMASK ? in.m2 & (0u - (unsigned)vf) : 0u;
+            if constexpr (!FMASK) {
+                mvx<PREC, 64, 64, true>(L + G::W2, L + G::L3_W2, h1, h2, i, hi, u1, &uh2);
 #pragma unroll
-            for (int r = 0; r < 32; ++r) h2[r] = fmaxf(h2[r], 0.f);
+                for (int r = 0; r < 32; ++r) h2[r] = fmaxf(h2[r], 0.f);
+            } else if constexpr (EXACT) {  // the fp32 reference mode keeps its float form of the mask
 #pragma unroll
-            for (int g = 0; g < 8; ++g) {
-                f32x4 w3 = *reinterpret_cast<const f32x4*>(L + OFF_W3 + 8 * g + 4 * hi);
-#pragma unroll
-                for (int e2 = 0; e2 < 4; ++e2) a2[4 * g + e2] = h2[4 * g + e2] > 0.f ? w3[e2] : 0.f;
+                for (int r = 0; r < 32; ++r) h2[r] = (float)((m2w >> r) & 1u);
             }
-            // a1 feeds a product AND an outer product (dW1): split once under the per-launch scale; a2 feeds W2^T a2 only
-            Split16<64, PAIR_SEQ, NT> a2s, a1s;
+            // a1 = m1 . W2^T (m2 . w3) = m1 . (C^T m2): the mask m2 as fp16 pairs is the B operand of the product and, further
+            // down, the X operand of D += m2 v^T.  a1 feeds a product AND an outer product (dW1): split once under the
+            // per-launch scale
+            unsigned m2p[16];
+            Split16<64, PAIR_SEQ, NT> a1s;
             float ua1 = 1.f;                     // factor of a1 where it is RAW
             if (WG16) {
-                split16_vec<64, PAIR_SEQ, NT>(a2, sA2, a2s);
-                mv16_pre<64, 64, true, NT>(L + GOFF_W2T, a2s, 1.f / sA2, a1, i, hi, &ua1, L + GLO_W2T);
+                if constexpr (FMASK)
+                    mask16_pairs_bits<64>(m2w, m2p);
+                else
+                    mask16_pairs<64>(h2, m2p);
+                mv16_mask<64, 64, NT>(L + G::CT, m2p, a1, i, hi, &ua1, L + G::L3_CT);
             } else {
-                mvtx_copy<PREC, 64, 64, 64>(L + GOFF_W2T, L + GLO_W2T, L + OFF_W2, a2, a1, i, hi);
+                float a2[32];
+#pragma unroll
+                for (int g = 0; g < 8; ++g) {
+                    f32x4 w3 = *reinterpret_cast<const f32x4*>(L + G::W3 + 8 * g + 4 * hi);
+#pragma unroll
+                    for (int e2 = 0; e2 < 4; ++e2) a2[4 * g + e2] = h2[4 * g + e2] > 0.f ? w3[e2] : 0.f;
+                }
+                mvtx_copy<PREC, 64, 64, 64>(L + G::CT, L + G::L3_CT, L + G::W2, a2, a1, i, hi);
             }
 #pragma unroll
             for (int r = 0; r < 32; ++r) a1[r] = h1[r] > 0.f ? a1[r] : 0.f;
             if (WG16) {
                 split16_vec<64, PAIR_SEQ, NT>(a1, sA1 * ua1, a1s);
-                mv16_pre<32, 64, false, NT>(L + GOFF_W1T, a1s, 1.f / sA1, q, i, hi, nullptr, L + GLO_W1T);
+                mv16_pre<32, 64, false, NT>(L + G::W1T, a1s, 1.f / sA1, q, i, hi, nullptr, L + G::L3_W1T);
             } else {
-                mvtx_copy<PREC, 32, 64, 32>(L + GOFF_W1T, L + GLO_W1T, L + OFF_W1, a1, q, i, hi);
+                mvtx_copy<PREC, 32, 64, 32>(L + G::W1T, L + G::L3_W1T, L + G::W1, a1, q, i, hi);
             }
             TT_PHASE(3);
             // ---- network + plane gradients ----
@@ -253,7 +278,7 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
                 TT_PHASE(7);
                 // a1bar = W1 qbar ; b1bar = m1 . a1bar ; v = sbar h1 + b1bar
                 float t1[32];
-                mvx<PREC, 64, 32>(L + OFF_W1, L + GLO_W1, qb, t1, i, hi);
+                mvx<PREC, 64, 32>(L + G::W1, L + G::L3_W1, qb, t1, i, hi);
 #pragma unroll
                 for (int r = 0; r < 32; ++r) t1[r] = h1[r] > 0.f ? t1[r] : 0.f;  // b1bar
                 float v[32];
@@ -263,7 +288,7 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
                 // D += m2 v^T: dW2 and dw3 both come out of it at the kernel-end flush (row-scaling identity, top of file)
                 if (do_wgrad) {
                     if (WG16) {
-                        stage_rows16_mask<64>(Xs, h2, i, hi);
+                        stage_rows16_mask<64>(Xs, m2p, i, hi);
                         stage_rows16<64>(Ys, v, i, hi, sV);
                         wgrad16_mask<64, 64>(accW2, Xs, Ys, i, hi);
                     } else {
@@ -350,21 +375,26 @@ static void launch_bwd_geo(const BwdGeoParams& p0, long long blocks, hipStream_t
     tt_dispatch_prec(tt_prec_of_r(p.cfg.flags), [&](auto P) {
         constexpr int PREC = decltype(P)::value;
         constexpr bool WG16 = PREC != PREC_F32;
-        if (p.cfg.stats)
-            hipLaunchKernelGGL((k_decode_bwd_geo<PREC, WG16, true>), dim3((unsigned)blocks), dim3(256), 0, s, p);
+        const dim3 grid((unsigned)blocks), block(256);
+        if (p.cfg.stats && p.h2_mask)
+            hipLaunchKernelGGL((k_decode_bwd_geo<PREC, WG16, true, true>), grid, block, 0, s, p);
+        else if (p.cfg.stats)
+            hipLaunchKernelGGL((k_decode_bwd_geo<PREC, WG16, true>), grid, block, 0, s, p);
+        else if (p.h2_mask)
+            hipLaunchKernelGGL((k_decode_bwd_geo<PREC, WG16, false, true>), grid, block, 0, s, p);
         else
-            hipLaunchKernelGGL((k_decode_bwd_geo<PREC, WG16>), dim3((unsigned)blocks), dim3(256), 0, s, p);
+            hipLaunchKernelGGL((k_decode_bwd_geo<PREC, WG16>), grid, block, 0, s, p);
     });
 }
 
-extern "C" int tt_render_bwd_geo(const float* packed, const tt_mlp_weights* w, const float* rays_o,
-                                 const float* rays_d, const float* t_starts, const float* t_ends,
-                                 const tt_render_cfg* cfg, const float* opacity, const float* depth,
-                                 const float* trans, const float* sdf, const float* sdf_grad, const float* features,
-                                 const float* g_opacity, const float* g_depth, const float* g_rgb_fg,
-                                 const float* g_z_variance, const float* g_normal_acc, const float* g_weights,
-                                 const float* g_sdf, const float* g_sdf_grad, float* g_inv_std_rays, float* workspace,
-                                 float* grad_packed, const tt_mlp_grads* grads, void* stream) {
+// tt_render_bwd_geo (h2_mask null: the decode backward recomputes W2 h1 for its signs) / tt_render_bwd_geo_h2mask
+static int render_bwd_geo(const float* packed, const tt_mlp_weights* w, const float* rays_o, const float* rays_d,
+                          const float* t_starts, const float* t_ends, const tt_render_cfg* cfg, const float* opacity,
+                          const float* depth, const float* trans, const float* sdf, const float* sdf_grad,
+                          const float* features, const float* g_opacity, const float* g_depth, const float* g_rgb_fg,
+                          const float* g_z_variance, const float* g_normal_acc, const float* g_weights,
+                          const float* g_sdf, const float* g_sdf_grad, float* g_inv_std_rays, float* workspace,
+                          float* grad_packed, const tt_mlp_grads* grads, const uint32_t* h2_mask, void* stream) {
     int st = tt_validate_cfg(cfg);
     if (st != TT_OK) return st;
     if (!packed || !w || !rays_o || !rays_d || !t_starts || !t_ends || !opacity || !depth || !trans || !sdf ||
@@ -383,6 +413,7 @@ extern "C" int tt_render_bwd_geo(const float* packed, const tt_mlp_weights* w, c
     tt_fill_rays(p, packed, w, rays_o, rays_d, t_starts, t_ends, *cfg);
     p.cfg.flags |= debug_flags();
     p.ws = workspace;
+    p.h2_mask = h2_mask;
     p.grad_packed = grad_packed;
     p.n_copies = cfg->grad_copies > 0 ? cfg->grad_copies : 1;
     p.grads = to_gptrs(grads);
@@ -390,6 +421,34 @@ extern "C" int tt_render_bwd_geo(const float* packed, const tt_mlp_weights* w, c
     if (st != TT_OK) return st;
     launch_bwd_geo(p, tt_persistent_blocks(p.n_items, cus, 4), s);
     return tt_check_launch();
+}
+
+extern "C" int tt_render_bwd_geo(const float* packed, const tt_mlp_weights* w, const float* rays_o,
+                                 const float* rays_d, const float* t_starts, const float* t_ends,
+                                 const tt_render_cfg* cfg, const float* opacity, const float* depth,
+                                 const float* trans, const float* sdf, const float* sdf_grad, const float* features,
+                                 const float* g_opacity, const float* g_depth, const float* g_rgb_fg,
+                                 const float* g_z_variance, const float* g_normal_acc, const float* g_weights,
+                                 const float* g_sdf, const float* g_sdf_grad, float* g_inv_std_rays, float* workspace,
+                                 float* grad_packed, const tt_mlp_grads* grads, void* stream) {
+    return render_bwd_geo(packed, w, rays_o, rays_d, t_starts, t_ends, cfg, opacity, depth, trans, sdf, sdf_grad, features,
+                          g_opacity, g_depth, g_rgb_fg, g_z_variance, g_normal_acc, g_weights, g_sdf, g_sdf_grad,
+                          g_inv_std_rays, workspace, grad_packed, grads, nullptr, stream);
+}
+
+extern "C" int tt_render_bwd_geo_h2mask(const float* packed, const tt_mlp_weights* w, const float* rays_o,
+                                        const float* rays_d, const float* t_starts, const float* t_ends,
+                                        const tt_render_cfg* cfg, const float* opacity, const float* depth,
+                                        const float* trans, const float* sdf, const float* sdf_grad,
+                                        const float* features, const float* g_opacity, const float* g_depth,
+                                        const float* g_rgb_fg, const float* g_z_variance, const float* g_normal_acc,
+                                        const float* g_weights, const float* g_sdf, const float* g_sdf_grad,
+                                        float* g_inv_std_rays, float* workspace, float* grad_packed,
+                                        const tt_mlp_grads* grads, const uint32_t* h2_mask, void* stream) {
+    if (!h2_mask) return TT_ERR_BAD_ARG;
+    return render_bwd_geo(packed, w, rays_o, rays_d, t_starts, t_ends, cfg, opacity, depth, trans, sdf, sdf_grad, features,
+                          g_opacity, g_depth, g_rgb_fg, g_z_variance, g_normal_acc, g_weights, g_sdf, g_sdf_grad,
+                          g_inv_std_rays, workspace, grad_packed, grads, h2_mask, stream);
 }
 
 // ---- backward of the per-point queries (tt_query_points / tt_query_field): the same decode-backward kernels, with
@@ -427,6 +486,7 @@ extern "C" int tt_points_bwd_geo(const float* packed, const tt_mlp_weights* w, c
     BwdGeoParams p;
     tt_fill_rays(p, packed, w, points, nullptr, nullptr, nullptr, cfg);
     p.ws = workspace;
+    p.h2_mask = nullptr;
     p.grad_packed = grad_packed;
     p.n_copies = 1;
     p.grads = to_gptrs(grads);

@@ -142,13 +142,17 @@ __device__ __forceinline__ void stage_rows16_pre(float* S, const Split16<N, PAIR
         U[LIDX(pair_reg<PAIR>(t, 1), hi) * XS + j] = __builtin_amdgcn_perm(v.l[t], v.h[t], 0x07060302u);
     }
 }
-// the 0/1 mask (v > 0) of a register vector as the X operand of wgrad16_mask: 1.0 is exact in ONE fp16 piece, and the dword
-// (1.0 | 1.0 << 16) puts it into both k-slots of the sample.  One compare + one select per entry (tt_mask.h)
+// the 0/1 mask of a register vector as the X operand of wgrad16_mask: 1.0 is exact in ONE fp16 piece, and the dword
+// (1.0 | 1.0 << 16) puts it into both k-slots of the sample.  The mask comes as the fp16 pairs of mask16_pairs
+// (tt_mfma16.h; dword t <-> registers 2 t, 2 t + 1): one v_perm per entry replicates the entry's half
 template <int N>
-__device__ __forceinline__ void stage_rows16_mask(float* S, const float (&v)[N / 2], int j, int hi) {
+__device__ __forceinline__ void stage_rows16_mask(float* S, const unsigned (&mb)[N / 4], int j, int hi) {
     unsigned* U = reinterpret_cast<unsigned*>(S);
 #pragma unroll
-    for (int r = 0; r < N / 2; ++r) U[LIDX(r, hi) * XS + j] = v[r] > 0.f ? 0x3C003C00u : 0u;
+    for (int t = 0; t < N / 4; ++t) {
+        U[LIDX(2 * t, hi) * XS + j] = __builtin_amdgcn_perm(0u, mb[t], 0x01000100u);
+        U[LIDX(2 * t + 1, hi) * XS + j] = __builtin_amdgcn_perm(0u, mb[t], 0x03020302u);
+    }
 }
 __device__ __forceinline__ h8_t wg16_frag(const float* S, int row, int t, int hi) {
     return __builtin_bit_cast(h8_t, *reinterpret_cast<const u32x4*>(S + row * XS + 8 * t + 4 * hi));

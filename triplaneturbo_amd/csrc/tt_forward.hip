@@ -179,10 +179,41 @@ __device__ __forceinline__ void decode_tex_fwd(const float* L, const DecodeCfg& 
     }
 }
 
+// bit r of the word = (h[r] > 0): the sign mask of a hidden vector in its LIDX register layout.  Built from the top
+// register down as m = 2 m + (h > 0): one compare and one add-with-carry per entry, eight entries per asm block.
+__device__ __forceinline__ unsigned sign_mask32(const float (&h)[32]) {
+    unsigned m = 0u;
+#pragma unroll
+    for (int g = 3; g >= 0; --g)
+        asm("v_cmp_lt_f32 vcc, 0, %8\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc\n\t"
+            "v_cmp_lt_f32 vcc, 0, %7\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc\n\t"
+            "v_cmp_lt_f32 vcc, 0, %6\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc\n\t"
+            "v_cmp_lt_f32 vcc, 0, %5\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc\n\t"
+            "v_cmp_lt_f32 vcc, 0, %4\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc\n\t"
+            "v_cmp_lt_f32 vcc, 0, %3\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc\n\t"
+            "v_cmp_lt_f32 vcc, 0, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc\n\t"
+            "v_cmp_lt_f32 vcc, 0, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc"
+            : "+v"(m)
+            : "v"(h[8 * g]), "v"(h[8 * g + 1]), "v"(h[8 * g + 2]), "v"(h[8 * g + 3]), "v"(h[8 * g + 4]), "v"(h[8 * g + 5]),
+              "v"(h[8 * g + 6]), "v"(h[8 * g + 7])
+            : "vcc");
+    return m;
+}
+
+__device__ __forceinline__ void store_mask_word(unsigned* mask, long long sidx, int hi, bool valid, unsigned m) {
+    asm volatile("" : "+v"(sidx));
+    if (valid) mask[2 * sidx + hi] = m;
+}
+
 // geometry half: f (+ J) -> sdf net -> s0 and, if NEED_N, gq = J^T q (WITHOUT the sphere term)
-template <bool NEED_N, int PREC>
+// MASK: valid lanes also store the sign mask of h2 to mask[2 sidx + hi] (tt_render_fwd_h2mask's h2_mask), right after the
+// ReLU so that the word is not live across the normal chain; a skipped tile step stores 0 (every mask false).  The address
+// is formed at the store from the sample index, which is live anyway (opaque copy: hipcc would otherwise keep the pointer
+// pair alive across the whole decode, and the S3 instantiation has no register left for it).
+template <bool NEED_N, int PREC, bool MASK = false>
 __device__ __forceinline__ void decode_geo_fwd(const float* L, const DecodeCfg& dc, float X, float Y, float Z,
-                                               bool valid, int i, int hi, float& s0, float (&gq)[3]) {
+                                               bool valid, int i, int hi, float& s0, float (&gq)[3],
+                                               unsigned* mask = nullptr, long long sidx = 0) {
     s0 = 0.f;
     gq[0] = gq[1] = gq[2] = 0.f;
     float f[16], jx[16], jy[16], jz[16];
@@ -211,6 +242,9 @@ __device__ __forceinline__ void decode_geo_fwd(const float* L, const DecodeCfg& 
         mvx<PREC, 64, 64, true>(L + OFF_W2, L + LO_W2, h1, h2, i, hi, u1, &u2);
 #pragma unroll
         for (int r = 0; r < 32; ++r) h2[r] = fmaxf(h2[r], 0.f);
+        if constexpr (MASK) {
+            store_mask_word(mask, sidx, hi, valid, sign_mask32(h2));
+        }
         s0 = dot_lds<64>(L + OFF_W3, h2, hi) * u2;
         if (NEED_N) {
             // reverse-mode input gradient: a2 = m2 . w3 ; a1 = m1 . (W2^T a2) ; q = W1^T a1
@@ -237,16 +271,19 @@ __device__ __forceinline__ void decode_geo_fwd(const float* L, const DecodeCfg& 
             gq[1] = sy + __shfl_xor(sy, 32);
             gq[2] = sz + __shfl_xor(sz, 32);
         }
+    } else if constexpr (MASK) {
+        store_mask_word(mask, sidx, hi, valid, 0u);
     }
 }
 
-template <bool NEED_N, bool NEED_TEX, int PREC>
+template <bool NEED_N, bool NEED_TEX, int PREC, bool MASK = false>
 __device__ __forceinline__ void decode_fwd(const float* L, const DecodeCfg& dc, float px, float py, float pz,
-                                           bool valid, int i, int hi, float& s0, float (&gq)[3], float (&c)[3]) {
+                                           bool valid, int i, int hi, float& s0, float (&gq)[3], float (&c)[3],
+                                           unsigned* mask = nullptr, long long sidx = 0) {
     const float X = scale_coord(px, dc.radius), Y = scale_coord(py, dc.radius), Z = scale_coord(pz, dc.radius);
     c[0] = c[1] = c[2] = 0.f;
     if (NEED_TEX) decode_tex_fwd<PREC>(L, dc, X, Y, Z, valid, i, hi, c);
-    decode_geo_fwd<NEED_N, PREC>(L, dc, X, Y, Z, valid, i, hi, s0, gq);
+    decode_geo_fwd<NEED_N, PREC, MASK>(L, dc, X, Y, Z, valid, i, hi, s0, gq, mask, sidx);
 }
 
 // =====================================================================================================
@@ -451,9 +488,11 @@ struct DecodeRaysParams {
     float* sdf;
     float* sdf_grad;
     float* features;
+    unsigned* h2_mask;  // (n_rays*S, 2) sign masks of h2 for the geometry backward (MASK instantiation), else null
 };
 
-template <bool NEED_N, bool NEED_TEX, int PREC>
+// MASK: the instantiation tt_render_fwd_h2mask launches; the arithmetic and every other store are the same
+template <bool NEED_N, bool NEED_TEX, int PREC, bool MASK = false>
 __global__ __launch_bounds__(DECODE_THREADS) void k_decode_rays(DecodeRaysParams p) {
     __shared__ __attribute__((aligned(16))) float L[FwdWFloats<PREC>::value + (DECODE_THREADS / 64) * GC_SCRATCH_FLOATS];
     float* T = L + FwdWFloats<PREC>::value + (threadIdx.x >> 6) * GC_SCRATCH_FLOATS;
@@ -515,7 +554,7 @@ __global__ __launch_bounds__(DECODE_THREADS) void k_decode_rays(DecodeRaysParams
             float tm, px, py, pz;
             sample_position(ox, oy, oz, dx, dy, dz, ts, te, tm, px, py, pz);
             float s0, gq[3], c[3];
-            decode_fwd<NEED_N, NEED_TEX, PREC>(L, dc, px, py, pz, rvalid, i, hi, s0, gq, c);
+            decode_fwd<NEED_N, NEED_TEX, PREC, MASK>(L, dc, px, py, pz, rvalid, i, hi, s0, gq, c, p.h2_mask, sidx);
             float nrm;
             const float sdf = s0 + sphere_bias(px, py, pz, cfg.sdf_bias_radius, nrm);
             if (rvalid && hi == 0 && !TT_DBG(cfg.flags, TT_DBG_NO_STORE)) {
@@ -875,10 +914,11 @@ long long tt_make_geom(const tt_render_cfg* cfg, long long wave_slots, TileGeom*
     return n_blocks * g->n_chunks;
 }
 
-extern "C" int tt_render_fwd(const float* packed, const tt_mlp_weights* w, const float* rays_o, const float* rays_d,
-                             const float* t_starts, const float* t_ends, const tt_render_cfg* cfg, float* opacity,
-                             float* depth, float* rgb_fg, float* z_variance, float* normal_acc, float* weights,
-                             float* trans, float* sdf, float* sdf_grad, float* features, void* stream) {
+// tt_render_fwd (h2_mask null) / tt_render_fwd_h2mask
+static int render_fwd(const float* packed, const tt_mlp_weights* w, const float* rays_o, const float* rays_d,
+                      const float* t_starts, const float* t_ends, const tt_render_cfg* cfg, float* opacity, float* depth,
+                      float* rgb_fg, float* z_variance, float* normal_acc, float* weights, float* trans, float* sdf,
+                      float* sdf_grad, float* features, uint32_t* h2_mask, void* stream) {
     int st = tt_validate_cfg(cfg);
     if (st != TT_OK) return st;
     if (!packed || !w || !rays_o || !rays_d || !t_starts || !t_ends || !opacity || !depth || !rgb_fg || !z_variance ||
@@ -893,18 +933,40 @@ extern "C" int tt_render_fwd(const float* packed, const tt_mlp_weights* w, const
     p.sdf = sdf;
     p.sdf_grad = sdf_grad;
     p.features = features;
+    p.h2_mask = h2_mask;
     hipStream_t s = (hipStream_t)stream;
     // one 8-wave workgroup per CU (LDS 93 KB)
     st = tt_plan_queue(cfg, (long long)cus * (DECODE_THREADS / 64), s, &p.geom, &p.n_items, &p.queue, 12);
     if (st != TT_OK) return st;
     const dim3 grid((unsigned)tt_persistent_blocks(p.n_items, cus, DECODE_THREADS / 64));
     tt_dispatch_prec(tt_prec_of_r(cfg->flags), [&](auto P) {
-        hipLaunchKernelGGL((k_decode_rays<true, true, decltype(P)::value>), grid, dim3(DECODE_THREADS), 0, s, p);
+        if (h2_mask)
+            hipLaunchKernelGGL((k_decode_rays<true, true, decltype(P)::value, true>), grid, dim3(DECODE_THREADS), 0, s, p);
+        else
+            hipLaunchKernelGGL((k_decode_rays<true, true, decltype(P)::value>), grid, dim3(DECODE_THREADS), 0, s, p);
     });
     st = tt_check_launch();
     if (st != TT_OK) return st;
     return tt_launch_march_fwd(rays_d, t_starts, t_ends, cfg, sdf, sdf_grad, features, opacity, depth, rgb_fg,
                                z_variance, normal_acc, weights, trans, s);
+}
+
+extern "C" int tt_render_fwd(const float* packed, const tt_mlp_weights* w, const float* rays_o, const float* rays_d,
+                             const float* t_starts, const float* t_ends, const tt_render_cfg* cfg, float* opacity,
+                             float* depth, float* rgb_fg, float* z_variance, float* normal_acc, float* weights,
+                             float* trans, float* sdf, float* sdf_grad, float* features, void* stream) {
+    return render_fwd(packed, w, rays_o, rays_d, t_starts, t_ends, cfg, opacity, depth, rgb_fg, z_variance, normal_acc,
+                      weights, trans, sdf, sdf_grad, features, nullptr, stream);
+}
+
+extern "C" int tt_render_fwd_h2mask(const float* packed, const tt_mlp_weights* w, const float* rays_o,
+                                    const float* rays_d, const float* t_starts, const float* t_ends,
+                                    const tt_render_cfg* cfg, float* opacity, float* depth, float* rgb_fg,
+                                    float* z_variance, float* normal_acc, float* weights, float* trans, float* sdf,
+                                    float* sdf_grad, float* features, uint32_t* h2_mask, void* stream) {
+    if (!h2_mask) return TT_ERR_BAD_ARG;
+    return render_fwd(packed, w, rays_o, rays_d, t_starts, t_ends, cfg, opacity, depth, rgb_fg, z_variance, normal_acc,
+                      weights, trans, sdf, sdf_grad, features, h2_mask, stream);
 }
 
 // Decode only (no march): sdf [+ sdf_grad] [+ features] at the mid-points of the given intervals.  Used by the
@@ -927,6 +989,7 @@ extern "C" int tt_decode_rays(const float* packed, const tt_mlp_weights* w, cons
     p.sdf = sdf;
     p.sdf_grad = sdf_grad;
     p.features = features;
+    p.h2_mask = nullptr;
     hipStream_t s = (hipStream_t)stream;
     const long long slots = (long long)cus * (DECODE_THREADS / 64);
     // The sdf-only decode (the sampler's proposal pass) is so cheap per tile step that an item's ray set-up, its queue pop and

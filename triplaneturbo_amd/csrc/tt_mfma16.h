@@ -166,6 +166,53 @@ __device__ __forceinline__ void stage_image16(float* dst_f, const float* __restr
     for (int R = threadIdx.x; R < ROWS; R += blockDim.x) dst_f[(size_t)R * (K + 4) + K] = un;
 }
 
+// Image of C^T for C = diag(rs) src (src: K rows x ROWS columns, row-major, rs: its K row factors), i.e.
+// M[R][c] = rs[c] * src[c * ld + R]: the launch-constant operand of `C^T m` for a 0/1 mask m (mv16_mask below).  Every
+// product is formed in double (24 x 24 significand bits: exact, no intermediate fp32 rounding) and split from there.
+// Format, normalisation, pad factor and synchronisation exactly as stage_image16 (the maximum is searched on the fp32
+// products: rounding can only raise one into the next binade, which costs at most one bit of headroom).
+template <int ROWS, int K, int NT>
+__device__ __forceinline__ void stage_image16_rowscaled_t(float* dst_f, const float* __restrict__ src,
+                                                          const float* __restrict__ rs, int ld, float* lo_f = nullptr) {
+    half_t* dst = reinterpret_cast<half_t*>(dst_f);
+    half_t* dlo = reinterpret_cast<half_t*>(lo_f);
+    constexpr int RS = 2 * K + 8, RSL = K + 8;
+    unsigned* slot = reinterpret_cast<unsigned*>(dst_f + K);
+    if (threadIdx.x == 0) *slot = 0u;
+    __syncthreads();
+    unsigned mb = 0u;
+    for (int e = threadIdx.x; e < ROWS * K; e += blockDim.x) {
+        const int c = e / ROWS;
+        const unsigned b = __builtin_bit_cast(unsigned, src[(size_t)c * ld + (e - c * ROWS)] * rs[c]) & 0x7fffffffu;
+        mb = b > mb ? b : mb;
+    }
+    atomicMax(slot, mb);
+    __syncthreads();
+    int E = (int)(*slot >> 23);
+    E = E < 16 ? 16 : (E > 240 ? 240 : E);
+    const float sc = __builtin_bit_cast(float, (unsigned)(268 - E) << 23);
+    const float un = __builtin_bit_cast(float, (unsigned)(E - 14) << 23);
+    __syncthreads();
+    for (int e = threadIdx.x; e < ROWS * K; e += blockDim.x) {
+        const int R = e / K, c = e - R * K;
+        const double v = ((double)src[(size_t)c * ld + R] * (double)rs[c]) * (double)sc;
+        const half_t hi = cvt_pk16((float)v, 0.f).x;
+        const double r1 = v - (double)(float)hi;  // residuals are exact in double
+        const half_t lo = cvt_pk16((float)r1, 0.f).x;
+        const int s = c >> 4, w = c & 15;
+        const int h = (w >> 2) & 1, j = (w & 3) + 4 * (w >> 3);
+        half_t* p = dst + (size_t)R * RS + (size_t)(4 * s + h) * 8 + j;
+        p[0] = hi;
+        p[16] = lo;
+        if (NT == 3) {
+            const half_t l3 = cvt_pk16((float)(r1 - (double)(float)lo), 0.f).x;
+            const int hf = c >= K / 2 ? 1 : 0, s2 = (c - hf * (K / 2)) >> 4;
+            dlo[(size_t)R * RSL + (size_t)(4 * s2 + h) * 8 + j + 16 * hf] = l3;
+        }
+    }
+    for (int R = threadIdx.x; R < ROWS; R += blockDim.x) dst_f[(size_t)R * (K + 4) + K] = un;
+}
+
 // Compiler scheduling fence in front of the split + MFMA loop of a product (after the per-sample scale search): hipcc may
 // not mix the tail of the previous product / the scale search into the loop, nor hoist the loop's LDS reads above it.
 // Measured per translation unit: the forward kernels gain 6-7 % (k_decode_rays 1.80 -> 1.68 ms, the fused eval kernel
@@ -374,6 +421,65 @@ __device__ __forceinline__ void mv16_pre(const float* img_f, const Split16<NIN, 
     for (int m = 0; m < MT; ++m)
 #pragma unroll
         for (int k = 0; k < 16; ++k) y[16 * m + k] = RAW ? acc[m][k] : acc[m][k] * un;
+}
+
+// ---- products with a 0/1 MASK as the B operand ------------------------------------------------------------------------
+// 1.0 is exact in ONE fp16 piece, so M m needs one MFMA per piece of M and k-step -- three (NT = 3) or two instead of six or
+// three -- no split and no per-sample scale search.  The mask comes as fp16 1.0 / 0 pairs in PAIR_SEQ order: dword t =
+// (m[2t] ? 0x3C00 : 0) | (m[2t+1] ? 0x3C000000 : 0).  Pieces are issued small to large; the result is RAW (factor in *yf).
+#define MASK16_ONE 0x3C00u
+template <int N>
+__device__ __forceinline__ void mask16_pairs(const float (&v)[N / 2], unsigned (&mb)[N / 4]) {
+#pragma unroll
+    for (int t = 0; t < N / 4; ++t)
+        mb[t] = (v[2 * t] > 0.f ? MASK16_ONE : 0u) | (v[2 * t + 1] > 0.f ? MASK16_ONE << 16 : 0u);
+}
+// the same pairs from a word of mask bits (bit r <-> register r; N = 64: the 32 registers of a lane): a sign-extended
+// one-bit field and an AND per entry
+template <int N>
+__device__ __forceinline__ void mask16_pairs_bits(unsigned w, unsigned (&mb)[N / 4]) {
+#pragma unroll
+    for (int t = 0; t < N / 4; ++t) {
+        const unsigned a = (unsigned)((int)(w << (31 - 2 * t)) >> 31), b = (unsigned)((int)(w << (30 - 2 * t)) >> 31);
+        mb[t] = (a & MASK16_ONE) | (b & (MASK16_ONE << 16));
+    }
+}
+template <int NOUT, int NIN, int NT = 2>
+__device__ __forceinline__ void mv16_mask(const float* img_f, const unsigned (&mb)[NIN / 4], float (&y)[NOUT / 2], int i,
+                                          int hi, float* yf, const float* lo_f = nullptr) {
+    constexpr int MT = NOUT / 32, KS = NIN / 16, RS = 2 * NIN + 8;
+    const half_t* row = reinterpret_cast<const half_t*>(img_f) + (size_t)i * RS + 8 * hi;
+    const half_t* lrow = reinterpret_cast<const half_t*>(lo_f) + (size_t)i * (NIN + 8) + 8 * hi;
+    f32x16 acc[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+        acc[m] = f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    typedef unsigned u4_t __attribute__((ext_vector_type(4)));
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+        const h8_t b = __builtin_bit_cast(h8_t, u4_t{mb[4 * s], mb[4 * s + 1], mb[4 * s + 2], mb[4 * s + 3]});
+        h8_t ah[MT], al[MT], at[MT];
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            const half_t* a = row + (size_t)(32 * m) * RS + 32 * s;
+            ah[m] = *reinterpret_cast<const h8_t*>(a);
+            al[m] = *reinterpret_cast<const h8_t*>(a + 16);
+            if constexpr (NT == 3) at[m] = lo_frag<NIN>(lrow, m, s);
+        }
+        if constexpr (NT == 3) {
+#pragma unroll
+            for (int m = 0; m < MT; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(at[m], b, acc[m], 0, 0, 0);
+        }
+#pragma unroll
+        for (int m = 0; m < MT; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[m], b, acc[m], 0, 0, 0);
+#pragma unroll
+        for (int m = 0; m < MT; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[m], b, acc[m], 0, 0, 0);
+    }
+    *yf = img_f[(size_t)i * (NIN + 4) + NIN];  // inverse of the matrix normalisation
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int k = 0; k < 16; ++k) y[16 * m + k] = acc[m][k];
 }
 
 // ---- the same products over NK consecutive k-steps only (single-plane tile steps) ---------------------------------------

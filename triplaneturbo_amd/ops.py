@@ -9,7 +9,7 @@ import ctypes
 import dataclasses
 from dataclasses import dataclass
 from functools import cached_property
-from typing import List, NamedTuple, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -163,6 +163,10 @@ class RenderConfig:
     # texture backward decode kernel, columns = tile steps visited, tile steps executed, in-bounds (plane, sample) pairs,
     # reserved.  bench.py reads `live_tile_frac` from it; None = off
     stats: Optional[Tensor] = None
+    # the differentiable render's forward also writes the sign mask of the sdf net's last hidden layer and its geometry
+    # backward reads it (tt_render_fwd_h2mask / tt_render_bwd_geo_h2mask); False = the backward recomputes the layer for
+    # its signs (tt_render_fwd / tt_render_bwd_geo: the A/B reference of the mask path)
+    fwd_mask: bool = True
 
 
 def planes_pack(space_cache: Tensor) -> Tensor:
@@ -422,9 +426,11 @@ def _ray_outputs(n_rays: int, device, S: Optional[int] = None) -> dict:
 
 def render_forward_raw(packed: Tensor, sdf_w: Sequence[Tensor], feat_w: Sequence[Tensor], rays_o: Tensor,
                        rays_d: Tensor, t_starts: Tensor, t_ends: Tensor, rays_per_view: int, rc: RenderConfig,
-                       per_sample: bool = True, image_w: int = 0):
+                       per_sample: bool = True, image_w: int = 0, h2_mask: Union[bool, Tensor] = False):
     """One tt_render_fwd call (decode kernel + march kernel).  rays_* (n_rays,3); t_* (n_rays,S); image_w = width
-    of each view's ray image (enables 8x4 pixel tiles).  Returns a dict of raw kernel outputs."""
+    of each view's ray image (enables 8x4 pixel tiles).  Returns a dict of raw kernel outputs.  h2_mask=True (or the
+    int32 buffer to write): the tt_render_fwd_h2mask form, which also returns "h2_mask" (n_rays*S, 2) int32, the saved
+    state of tt_render_bwd_geo_h2mask."""
     packed, rays_o, rays_d, t_starts, t_ends = _ray_args(packed, rays_o, rays_d, t_starts, t_ends)
     n_rays, S = t_starts.shape
     cfg = _make_cfg(packed, n_rays, rays_per_view, S, rc, per_sample, image_w)
@@ -434,7 +440,17 @@ def render_forward_raw(packed: Tensor, sdf_w: Sequence[Tensor], feat_w: Sequence
     # per-sample decode results: outputs in training, inter-kernel workspace always
     out.update(sdf=torch.empty((n_rays * S, 1), **f32), sdf_grad=torch.empty((n_rays * S, 3), **f32),
                features=torch.empty((n_rays * S, 3), **f32))
-    _launch("tt_render_fwd", packed, wst, rays_o, rays_d, t_starts, t_ends, cfg, *out.values(), label="tt_render_fwd")
+    if h2_mask is not False:
+        if h2_mask is True:
+            h2_mask = torch.empty((n_rays * S, 2), device=packed.device, dtype=torch.int32)
+        out["h2_mask"] = _chk(h2_mask, "h2_mask", (n_rays * S, 2), torch.int32)
+        if out["h2_mask"].data_ptr() != h2_mask.data_ptr():
+            raise ValueError("h2_mask must be contiguous (the kernel writes it in place)")
+        _launch("tt_render_fwd_h2mask", packed, wst, rays_o, rays_d, t_starts, t_ends, cfg, *out.values(),
+                label="tt_render_fwd")
+    else:
+        _launch("tt_render_fwd", packed, wst, rays_o, rays_d, t_starts, t_ends, cfg, *out.values(),
+                label="tt_render_fwd")
     return out
 
 
@@ -589,7 +605,7 @@ class _TriplaneRenderFn(torch.autograd.Function):
         ctx.set_materialize_grads(False)  # unused outputs (e.g. `features`, `weights`) reach backward as None, not as
         #                                    100 MB of zeros the kernels would have to read
         raw = render_forward_raw(packed, (w1, w2, w3), (v1, v2, v3), rays_o, rays_d, t_starts, t_ends, rays_per_view,
-                                 rc, per_sample=True, image_w=image_w)
+                                 rc, per_sample=True, image_w=image_w, h2_mask=need_grad and rc.fwd_mask)
         ctx.rays_per_view = rays_per_view
         ctx.rc = rc
         ctx.image_w = image_w
@@ -597,7 +613,7 @@ class _TriplaneRenderFn(torch.autograd.Function):
         if need_grad:
             ctx.save_for_backward(packed, w1, w2, w3, v1, v2, v3, rays_o, rays_d, t_starts, t_ends, raw["opacity"],
                                   raw["depth"], raw["trans"], raw["weights"], raw["features"], raw["sdf"],
-                                  raw["sdf_grad"])
+                                  raw["sdf_grad"], *([raw["h2_mask"]] if rc.fwd_mask else []))
         ctx.mark_non_differentiable(raw["trans"])
         return (raw["opacity"], raw["depth"], raw["rgb_fg"], raw["z_variance"], raw["normal_acc"], raw["weights"],
                 raw["sdf"], raw["sdf_grad"], raw["features"], raw["trans"])
@@ -606,7 +622,8 @@ class _TriplaneRenderFn(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_op, g_depth, g_rgb, g_zvar, g_nacc, g_weights, g_sdf, g_sdf_grad, g_features, _g_trans):
         (packed, w1, w2, w3, v1, v2, v3, rays_o, rays_d, t_starts, t_ends, opacity, depth, trans, weights,
-         features, sdf, sdf_grad) = ctx.saved_tensors
+         features, sdf, sdf_grad) = ctx.saved_tensors[:18]
+        h2_mask = ctx.saved_tensors[18:]  # (the forward's h2 sign mask) or nothing: rc.fwd_mask
         n_rays, S = t_starts.shape
         cfg = _make_cfg(packed, n_rays, ctx.rays_per_view, S, ctx.rc, True, ctx.image_w, stats_row=1)
         cfg_tex = _make_cfg(packed, n_rays, ctx.rays_per_view, S, ctx.rc, True, ctx.image_w, stats_row=2)
@@ -622,9 +639,9 @@ class _TriplaneRenderFn(torch.autograd.Function):
         g_k_rays = None
         if ctx.needs_input_grad[14]:  # d loss / d inv_std, one partial per ray (summed below in a fixed order)
             g_k_rays = torch.empty((n_rays,), device=packed.device, dtype=torch.float32)
-        _launch("tt_render_bwd_geo", packed, wst, rays_o, rays_d, t_starts, t_ends, cfg, opacity, depth, trans, sdf,
-                sdf_grad, features, g_op, g_depth, g_rgb, g_zvar, g_nacc, g_weights, g_sdf, g_sdf_grad, g_k_rays,
-                workspace, grad_packed, gst, label="tt_render_bwd_geo")
+        _launch("tt_render_bwd_geo_h2mask" if h2_mask else "tt_render_bwd_geo", packed, wst, rays_o, rays_d, t_starts,
+                t_ends, cfg, opacity, depth, trans, sdf, sdf_grad, features, g_op, g_depth, g_rgb, g_zvar, g_nacc,
+                g_weights, g_sdf, g_sdf_grad, g_k_rays, workspace, grad_packed, gst, *h2_mask, label="tt_render_bwd_geo")
         _launch("tt_render_bwd_tex", packed, wst, rays_o, rays_d, t_starts, t_ends, cfg_tex, weights, features, g_rgb,
                 g_features, grad_packed, gst, label="tt_render_bwd_tex")
         g_packed = None
