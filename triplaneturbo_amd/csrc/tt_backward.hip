@@ -45,18 +45,18 @@ struct BwdGeoParams {
 
 #define GEO_SCRATCH_FLOATS (2 * 64 * XS)
 // LDS map of the weight images.  Split-fp16 images (tt_mfma16.h) of W1, W2 sit where the fp32 images would (same bytes); the
-// transposed products use transposed COPIES appended to them (tt_backward_common.h: LDS nothing else wants at one wave per
-// SIMD): W1^T, and C^T for C = diag(w3) W2 in place of W2^T.  PREC_S3 appends the images of the third terms.
+// transposed products use transposed COPIES appended to them (LDS nothing else wants at one wave per SIMD, read by plain
+// ds_read_b128 fragments): W1^T, and C^T for C = diag(w3) W2 in place of W2^T.  PREC_S3 appends the images of the third terms.
 // NOW2 (the split modes with the forward's h2 mask): W2 h1 is not formed, so W2 has no image at all.
 template <int PREC, bool FMASK>
-struct GeoMap {
+struct GeoMap : LdsMap<PREC, LdsImage<64, 32>, LdsImage<64, 64, !(FMASK && PREC != PREC_F32)>, LdsRows<1, 64>,
+                       LdsImage<32, 64>, LdsImage<64, 64>> {
     static constexpr bool NOW2 = FMASK && PREC != PREC_F32;
-    static constexpr int W1 = 0, W2 = W1 + 64 * W1S, W3 = W2 + (NOW2 ? 0 : 64 * W2S);
-    static constexpr int W1T = W3 + 64, CT = W1T + IMG16_FLOATS(32, 64), END16 = CT + IMG16_FLOATS(64, 64);
-    static constexpr int L3_W1 = END16, L3_W2 = L3_W1 + LO16_FLOATS(64, 32);
-    static constexpr int L3_W1T = L3_W2 + (NOW2 ? 0 : LO16_FLOATS(64, 64)), L3_CT = L3_W1T + LO16_FLOATS(32, 64);
-    static constexpr int END3 = L3_CT + LO16_FLOATS(64, 64);
-    static constexpr int FLOATS = PREC == PREC_S3 ? END3 : END16;
+    typedef typename GeoMap::template at<0> W1;
+    typedef typename GeoMap::template at<1> W2;
+    typedef typename GeoMap::template at<2> W3;
+    typedef typename GeoMap::template at<3> W1T;
+    typedef typename GeoMap::template at<4> CT;
 };
 
 // STATS: the work accounting (tt_render_cfg.stats) compiled in.  In this kernel even a never-taken scalar branch per
@@ -70,17 +70,11 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
     typedef GeoMap<PREC, FMASK> G;
     constexpr int NT = PrecNT<PREC>::value, WF = G::FLOATS;
     __shared__ __attribute__((aligned(16))) float L[WF + 4 * (GEO_SCRATCH_FLOATS + SCATTER_TAG_INTS)];
-    {
-        MlpPtrs w = p.w;
-        stage_weights<PREC, 64, 32>(L + G::W1, L + G::L3_W1, w.w1);
-        if constexpr (!G::NOW2) stage_weights<PREC, 64, 64>(L + G::W2, L + G::L3_W2, w.w2);
-        lds_load_matrix(L + G::W3, w.w3, 1, 64, 64);
-        stage_weights_t<PREC, 64, 32>(L + G::W1T, L + G::L3_W1T, w.w1);
-        // C^T for C = diag(w3) W2 where W2^T used to sit (it had no other reader): a1 = m1 . (C^T m2) is then a product of a
-        // launch constant with a 0/1 mask (mv16_mask).  PREC_F32 keeps its fp32 product W2^T (m2 . w3) from the W2 image.
-        if constexpr (!EXACT)
-            stage_image16_rowscaled_t<64, 64, NT>(L + G::CT, w.w2, w.w3, 64, L + G::L3_CT);
-    }
+    stage_weights<PREC>(L, typename G::W1{}, p.w.w1);
+    if constexpr (!G::NOW2) stage_weights<PREC>(L, typename G::W2{}, p.w.w2);
+    stage_weights<PREC>(L, typename G::W3{}, p.w.w3);
+    stage_weights_t<PREC>(L, typename G::W1T{}, p.w.w1);
+    if constexpr (!EXACT) stage_image16_rowscaled_t<NT>(L, typename G::CT{}, p.w.w2, p.w.w3);
     const tt_render_cfg& cfg = p.cfg;
     // ---- per-launch operand scales of the fp16 outer products dW1 += a1 u^T, D += m2 v^T (wgrad16 above; m2 is 0/1: no scale) ----
     // rigorous magnitude bounds from the weights and the launch's maxima (planes, upstream: reduced on the stream in front
@@ -209,14 +203,14 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
             // "deferred factors"); their consumers are signs, the next product, and fmas that take the factor on the scalar;
             // h2 is used for its sign only (its factor uh2 is dead)
             float h1[32], h2[32], a1[32], q[16], u1, uh2;
-            mvx<PREC, 64, 32, true>(L + G::W1, L + G::L3_W1, f, h1, i, hi, 1.f, &u1);
+            mvx<PREC, true>(L, typename G::W1{}, f, h1, i, hi, 1.f, &u1);
 #pragma unroll
             for (int r = 0; r < 32; ++r) h1[r] = fmaxf(h1[r], 0.f);
             // FMASK: bit r of the lane's mask word is (h2[r] > 0) as the forward saw it; a lane that is not rvalid loaded
             // another sample's word from the clamped address: forced to 0 through the 0/1 validity factor
             const unsigned m2w = FMASK ? in.m2 & (0u - (unsigned)vf) : 0u;
             if constexpr (!FMASK) {
-                mvx<PREC, 64, 64, true>(L + G::W2, L + G::L3_W2, h1, h2, i, hi, u1, &uh2);
+                mvx<PREC, true>(L, typename G::W2{}, h1, h2, i, hi, u1, &uh2);
 #pragma unroll
                 for (int r = 0; r < 32; ++r) h2[r] = fmaxf(h2[r], 0.f);
             } else if constexpr (EXACT) {  // the fp32 reference mode keeps its float form of the mask
@@ -234,24 +228,24 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
                     mask16_pairs_bits<64>(m2w, m2p);
                 else
                     mask16_pairs<64>(h2, m2p);
-                mv16_mask<64, 64, NT>(L + G::CT, m2p, a1, i, hi, &ua1, L + G::L3_CT);
+                mv16_mask<NT>(L, typename G::CT{}, m2p, a1, i, hi, &ua1);
             } else {
                 float a2[32];
 #pragma unroll
                 for (int g = 0; g < 8; ++g) {
-                    f32x4 w3 = *reinterpret_cast<const f32x4*>(L + G::W3 + 8 * g + 4 * hi);
+                    f32x4 w3 = *reinterpret_cast<const f32x4*>(lds_at(L, typename G::W3{}) + 8 * g + 4 * hi);
 #pragma unroll
                     for (int e2 = 0; e2 < 4; ++e2) a2[4 * g + e2] = h2[4 * g + e2] > 0.f ? w3[e2] : 0.f;
                 }
-                mvtx_copy<PREC, 64, 64, 64>(L + G::CT, L + G::L3_CT, L + G::W2, a2, a1, i, hi);
+                mvtx_copy<PREC>(L, typename G::CT{}, typename G::W2{}, a2, a1, i, hi);
             }
 #pragma unroll
             for (int r = 0; r < 32; ++r) a1[r] = h1[r] > 0.f ? a1[r] : 0.f;
             if (WG16) {
                 split16_vec<64, PAIR_SEQ, NT>(a1, sA1 * ua1, a1s);
-                mv16_pre<32, 64, false, NT>(L + G::W1T, a1s, 1.f / sA1, q, i, hi, nullptr, L + G::L3_W1T);
+                mv16_pre(L, typename G::W1T{}, a1s, 1.f / sA1, q, i, hi);
             } else {
-                mvtx_copy<PREC, 32, 64, 32>(L + G::W1T, L + G::L3_W1T, L + G::W1, a1, q, i, hi);
+                mvtx_copy<PREC>(L, typename G::W1T{}, typename G::W1{}, a1, q, i, hi);
             }
             TT_PHASE(3);
             // ---- network + plane gradients ----
@@ -278,7 +272,7 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
                 TT_PHASE(7);
                 // a1bar = W1 qbar ; b1bar = m1 . a1bar ; v = sbar h1 + b1bar
                 float t1[32];
-                mvx<PREC, 64, 32>(L + G::W1, L + G::L3_W1, qb, t1, i, hi);
+                mvx<PREC>(L, typename G::W1{}, qb, t1, i, hi);
 #pragma unroll
                 for (int r = 0; r < 32; ++r) t1[r] = h1[r] > 0.f ? t1[r] : 0.f;  // b1bar
                 float v[32];

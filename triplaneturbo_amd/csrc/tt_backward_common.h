@@ -240,24 +240,12 @@ __device__ __forceinline__ float block_max(float v, unsigned* word) {
     return r;
 }
 
-// dst += acc * ux * uy  (ux, uy: the inverse operand scales of the fp16 outer products, 1 for the fp32 ones; two
-// factors so that extreme scales cannot overflow their product)
-template <int NX, int NY>
-__device__ __forceinline__ void flush_wgrad(const f32x16 (&acc)[NX / 32][NY / 32], float* __restrict__ dst, int i,
-                                            int hi, float ux = 1.f, float uy = 1.f) {
-#pragma unroll
-    for (int m = 0; m < NX / 32; ++m)
-#pragma unroll
-        for (int n = 0; n < NY / 32; ++n)
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                atomicAdd(dst + (32 * m + LIDX(r, hi)) * NY + 32 * n + i, (acc[m][n][r] * ux) * uy);
-}
-
 // Workgroup pre-reduction of one 32 x 32 accumulator tile at kernel end: the four waves' copies are summed through LDS
 // (R: 2 x 4096 floats, alternating by `parity` so that one barrier per tile is enough) and wave w adds registers
 // 4 w .. 4 w + 3 of the sum to memory -- a quarter of the same-address float atomics, which serialise at the memory side
 // (~1 000 waves add into the same 66 KB).  All 256 threads call it, in the same order, after the main loop.
+// What is added is acc * ux * uy (ux, uy: the inverse operand scales of the fp16 outer products, 1 for the fp32 ones; two
+// factors so that extreme scales cannot overflow their product).
 template <class Addr>
 __device__ __forceinline__ void flush_tile_reduced(float* R, int parity, const f32x16& acc, int wave, int lane,
                                                    float ux, float uy, Addr addr) {
@@ -827,7 +815,7 @@ __device__ __forceinline__ void scatter_one_plane(float* __restrict__ grad, unsi
     }
 }
 
-// ---- texture half: parameters and weight-image map of tt_backward_tex.hip ----
+// ---- texture half: parameters of tt_backward_tex.hip ----
 struct BwdTexParams {
     const float* packed;
     MlpPtrs w;
@@ -847,29 +835,6 @@ struct BwdTexParams {
     float* grad_packed;
     MlpGradPtrs grads;
     unsigned long long* phase_cycles;  // tuning build only (TT_PHASE), else null
-};
-
-#define TEX_W_FLOATS (LDS_W_FLOATS - OFF_V1)
-#define TV1 0
-#define TV2 (OFF_V2 - OFF_V1)
-#define TV3 (OFF_V3 - OFF_V1)
-// V1, V2 as split-fp16 images (tt_mfma16.h): every mat-vec product of the kernel runs on the fp16 pipe.  The V2^T / V1^T
-// products use transposed COPIES of the images (43 KB more LDS that nothing else wants at one wave per SIMD) and plain
-// ds_read_b128 fragments instead of ds_read_b64_tr_b16 reads of the forward images.
-// The per-wave scratch is 128 rows: the parked e (96 rows) shares it with a 32-row window through which k2 (for dV3)
-// and k1bar (for dV1) are transposed in two halves.
-#define TV1T TEX_W_FLOATS
-#define TV2T (TV1T + IMG16_FLOATS(96, 64))
-#define TEX_W16_FLOATS (TV2T + IMG16_FLOATS(64, 64))
-// PREC_S3 (three-piece products): the images of the third terms follow V3, and there are NO transposed copies -- with them
-// the kernel would need 204 KB of LDS -- so the V2^T / V1^T products read the forward images through ds_read_b64_tr_b16
-// (mv16t, as the forward kernels do): 66 KB of images + 76 KB of per-wave scratch = 143 KB.
-#define TLO_V1 TEX_W_FLOATS
-#define TLO_V2 (TLO_V1 + LO16_FLOATS(64, 96))
-#define TEX_W3P_FLOATS (TLO_V2 + LO16_FLOATS(64, 64))
-template <int PREC>
-struct TexWFloats {
-    static constexpr int value = PREC == PREC_S3 ? TEX_W3P_FLOATS : TEX_W16_FLOATS;
 };
 
 // =====================================================================================================

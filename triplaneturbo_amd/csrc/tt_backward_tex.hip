@@ -5,7 +5,25 @@
 // =====================================================================================================
 // texture half
 // =====================================================================================================
+// The per-wave scratch is 128 rows: the parked e (96 rows) shares it with a 32-row window through which k2 (for dV3)
+// and k1bar (for dV1) are transposed in two halves.
 #define TEX_SCRATCH_FLOATS (128 * XS)
+// LDS map of the weight images.  V1, V2 as split-fp16 images (tt_mfma16.h): every mat-vec product of the kernel runs on the
+// fp16 pipe.  COPIES: the V2^T / V1^T products use transposed copies of the images (43 KB more LDS that nothing else wants at
+// one wave per SIMD) and plain ds_read_b128 fragments instead of ds_read_b64_tr_b16 reads of the forward images.
+// PREC_S3 (three-piece products) appends the images of the third terms and has NO transposed copies -- with them the kernel
+// would need 204 KB of LDS -- so its V2^T / V1^T products read the forward images through ds_read_b64_tr_b16 (mvtx, as the
+// forward kernels do): 66 KB of images + 76 KB of per-wave scratch = 143 KB.
+template <int PREC>
+struct TexMap : LdsMap<PREC, LdsImage<64, 96>, LdsImage<64, 64>, LdsRows<3, 64>, LdsImage<96, 64, PREC != PREC_S3>,
+                       LdsImage<64, 64, PREC != PREC_S3>> {
+    static constexpr bool COPIES = PREC != PREC_S3;
+    typedef typename TexMap::template at<0> V1;
+    typedef typename TexMap::template at<1> V2;
+    typedef typename TexMap::template at<2> V3;
+    typedef typename TexMap::template at<3> V1T;
+    typedef typename TexMap::template at<4> V2T;
+};
 // a wave-uniform float the compiler cannot prove uniform (read back from LDS, derived from the wave index): through
 // readfirstlane it lives in a scalar register.  This kernel has no vector register to spare.
 __device__ __forceinline__ float uniform_f(float v) {
@@ -16,18 +34,15 @@ __device__ __forceinline__ float uniform_f(float v) {
 template <int PREC, bool WG16, bool STATS = false>
 __global__ __launch_bounds__(256, 1) void k_decode_bwd_tex(BwdTexParams p) {
     constexpr bool EXACT = PREC == PREC_F32;
-    constexpr bool COPIES = PREC != PREC_S3;  // transposed weight copies (tt_backward_common.h)
-    constexpr int NT = PrecNT<PREC>::value, WF = TexWFloats<PREC>::value;
+    typedef TexMap<PREC> F;
+    constexpr int NT = PrecNT<PREC>::value, WF = F::FLOATS;
     __shared__ __attribute__((aligned(16))) float Lt[WF + 4 * (TEX_SCRATCH_FLOATS + SCATTER_TAG_INTS)];
-    {
-        MlpPtrs w = p.w;
-        stage_weights<PREC, 64, 96>(Lt + TV1, Lt + TLO_V1, w.v1);
-        stage_weights<PREC, 64, 64>(Lt + TV2, Lt + TLO_V2, w.v2);
-        lds_load_matrix(Lt + TV3, w.v3, 3, 64, 64);
-        if constexpr (COPIES) {
-            stage_weights_t<PREC, 64, 96>(Lt + TV1T, nullptr, w.v1);
-            stage_weights_t<PREC, 64, 64>(Lt + TV2T, nullptr, w.v2);
-        }
+    stage_weights<PREC>(Lt, typename F::V1{}, p.w.v1);
+    stage_weights<PREC>(Lt, typename F::V2{}, p.w.v2);
+    stage_weights<PREC>(Lt, typename F::V3{}, p.w.v3);
+    if constexpr (F::COPIES) {
+        stage_weights_t<PREC>(Lt, typename F::V1T{}, p.w.v1);
+        stage_weights_t<PREC>(Lt, typename F::V2T{}, p.w.v2);
     }
     const tt_render_cfg& cfg = p.cfg;
     // ---- per-launch operand scales of the fp16 outer products dV1 += k1bar e^T, dV2 += k2bar k1^T (wgrad16) ----
@@ -215,9 +230,9 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_tex(BwdTexParams p) {
             if (one) {  // V1 e over the live plane's two k-steps (the split of an exact zero is zero: OR again)
                 Split16<32, PAIR_SEQ, NT> e1s;
                 live_split32(es, e1s);
-                mv16_pre_ks<64, 96, 2, NT>(Lt + TV1, e1s, 2 * pl1, uE, k1, i, hi, Lt + TLO_V1);
+                mv16_pre_ks(Lt, typename F::V1{}, e1s, 2 * pl1, uE, k1, i, hi);
             } else {
-                mv16_pre<64, 96, false, NT>(Lt + TV1, es, uE, k1, i, hi, nullptr, Lt + TLO_V1);
+                mv16_pre(Lt, typename F::V1{}, es, uE, k1, i, hi);
             }
         } else {
             if (do_wgrad) stage_rows<96>(Ys, e, i, hi);
@@ -225,9 +240,9 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_tex(BwdTexParams p) {
             if (one) {
                 float e1[16];
                 live_block16(e, e1);
-                mvx_plane<PREC, 64, 96>(Lt + TV1, Lt + TLO_V1, e1, pl1, k1, i, hi);
+                mvx_plane<PREC>(Lt, typename F::V1{}, e1, pl1, k1, i, hi);
             } else {
-                mvx<PREC, 64, 96>(Lt + TV1, Lt + TLO_V1, e, k1, i, hi);
+                mvx<PREC>(Lt, typename F::V1{}, e, k1, i, hi);
             }
         }
 #pragma unroll
@@ -236,9 +251,9 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_tex(BwdTexParams p) {
         Split16<64, PAIR_SEQ, NT> k1s;  // k1 likewise: V2 k1 now, the dV2 outer product later
         if (WG16) {
             split16_vec<64, PAIR_SEQ, NT>(k1, sK1, k1s);
-            mv16_pre<64, 64, false, NT>(Lt + TV2, k1s, uK1, k2, i, hi, nullptr, Lt + TLO_V2);
+            mv16_pre(Lt, typename F::V2{}, k1s, uK1, k2, i, hi);
         } else {
-            mvx<PREC, 64, 64>(Lt + TV2, Lt + TLO_V2, k1, k2, i, hi);
+            mvx<PREC>(Lt, typename F::V2{}, k1, k2, i, hi);
         }
 #pragma unroll
         for (int r = 0; r < 32; ++r) k2[r] = fmaxf(k2[r], 0.f);
@@ -271,9 +286,9 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_tex(BwdTexParams p) {
         // ---- k2bar = n2 . (V3^T cbar) ----
 #pragma unroll
         for (int g = 0; g < 8; ++g) {
-            f32x4 v0 = *reinterpret_cast<const f32x4*>(Lt + TV3 + 0 * 64 + 8 * g + 4 * hi);
-            f32x4 v1 = *reinterpret_cast<const f32x4*>(Lt + TV3 + 1 * 64 + 8 * g + 4 * hi);
-            f32x4 v2 = *reinterpret_cast<const f32x4*>(Lt + TV3 + 2 * 64 + 8 * g + 4 * hi);
+            f32x4 v0 = *reinterpret_cast<const f32x4*>(lds_at(Lt, typename F::V3{}) + 0 * 64 + 8 * g + 4 * hi);
+            f32x4 v1 = *reinterpret_cast<const f32x4*>(lds_at(Lt, typename F::V3{}) + 1 * 64 + 8 * g + 4 * hi);
+            f32x4 v2 = *reinterpret_cast<const f32x4*>(lds_at(Lt, typename F::V3{}) + 2 * 64 + 8 * g + 4 * hi);
 #pragma unroll
             for (int e2 = 0; e2 < 4; ++e2) {
                 const float t = fmaf(v0[e2], cb[0], fmaf(v1[e2], cb[1], v2[e2] * cb[2]));
@@ -282,10 +297,10 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_tex(BwdTexParams p) {
         }
         // ---- k1bar = n1 . (V2^T k2bar) ----
         float kb1[32];
-        if constexpr (COPIES)
-            mvtx_copy<PREC, 64, 64, 64>(Lt + TV2T, nullptr, Lt + TV2, k2, kb1, i, hi);
+        if constexpr (F::COPIES)
+            mvtx_copy<PREC>(Lt, typename F::V2T{}, typename F::V2{}, k2, kb1, i, hi);
         else
-            mvtx<PREC, 64, 64, 64>(Lt + TV2, Lt + TLO_V2, 0, k2, kb1, i, hi);
+            mvtx<PREC>(Lt, typename F::V2{}, k2, kb1, i, hi);
 #pragma unroll
         for (int r = 0; r < 32; ++r) kb1[r] = k1[r] > 0.f ? kb1[r] : 0.f;
         TT_PHASE(6);
@@ -335,10 +350,10 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_tex(BwdTexParams p) {
             const int tex0 = (int)(pofs / TT_C);
             // ebar = V1^T k1bar for the three planes in ONE product (96 rows: k1bar is split into fp16 terms once)
             float eb[48];
-            if constexpr (COPIES)
-                mvtx_copy<PREC, 96, 64, 96>(Lt + TV1T, nullptr, Lt + TV1, kb1, eb, i, hi);
+            if constexpr (F::COPIES)
+                mvtx_copy<PREC>(Lt, typename F::V1T{}, typename F::V1{}, kb1, eb, i, hi);
             else
-                mvtx<PREC, 96, 64, 96>(Lt + TV1, Lt + TLO_V1, 0, kb1, eb, i, hi);
+                mvtx<PREC>(Lt, typename F::V1{}, kb1, eb, i, hi);
             TT_PHASE(9);
             if (one) {  // the live plane's 16 registers of ebar (selects, no runtime register indexing), its scatter alone
                 float eb1[16];

@@ -40,29 +40,15 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // pre-pipelining scatter, results in profiles/r02_ablations.txt; the straight-line scatter_planes has no switches)
 
 #define TT_C 32
-#define TT_HID 64
 #define TT_TILE 32
 
 #define LIDX(r, hi) (((r) & 3) + 8 * ((r) >> 2) + 4 * (hi))
 
 #include "tt_mask.h"
 
-// ---- LDS image of the MLP weights: row-major, row stride = cols + 4 floats -----------------------
+// ---- LDS image of an MLP weight matrix: row-major, row stride = cols + 4 floats (placement: LdsMap, tt_mfma16.h) ----
 // (+4 keeps 16-byte alignment and makes the per-lane-row ds_read_b128 of mv_fwd conflict-free:
 //  36*i, 68*i, 100*i mod 64 hit 16 distinct 4-bank slots for the 16 lanes of a b128 lane group.)
-#define W1S 36
-#define W2S 68
-#define V1S 100
-#define V2S 68
-#define OFF_W1 0
-#define OFF_W2 (OFF_W1 + 64 * W1S)
-#define OFF_W3 (OFF_W2 + 64 * W2S)
-#define OFF_V1 (OFF_W3 + 64)
-#define OFF_V2 (OFF_V1 + 64 * V1S)
-#define OFF_V3 (OFF_V2 + 64 * V2S)
-#define LDS_W_FLOATS (OFF_V3 + 3 * 64)
-#define LDS_GEO_FLOATS (OFF_W3 + 64) /* W1, W2, w3 only */
-
 struct MlpPtrs {
     const float* w1;
     const float* w2;
@@ -78,17 +64,6 @@ __device__ __forceinline__ void lds_load_matrix(float* dst, const float* __restr
         int r = e / cols, c = e - r * cols;
         dst[r * stride + c] = src[e];
     }
-}
-
-__device__ __forceinline__ void lds_load_geo_weights(float* L, const MlpPtrs& w) {
-    lds_load_matrix(L + OFF_W1, w.w1, 64, 32, W1S);
-    lds_load_matrix(L + OFF_W2, w.w2, 64, 64, W2S);
-    lds_load_matrix(L + OFF_W3, w.w3, 1, 64, 64);
-}
-__device__ __forceinline__ void lds_load_tex_weights(float* L, const MlpPtrs& w) {
-    lds_load_matrix(L + OFF_V1, w.v1, 64, 96, V1S);
-    lds_load_matrix(L + OFF_V2, w.v2, 64, 64, V2S);
-    lds_load_matrix(L + OFF_V3, w.v3, 3, 64, 64);
 }
 
 // ---- MFMA mat-vec products on a 32-sample tile -----------------------------------------------------

@@ -126,6 +126,11 @@ __global__ __launch_bounds__(256) void k_planes_pack4(const float* __restrict__ 
 // =====================================================================================================
 // per-tile decode (forward): gather -> sdf net (+ input-gradient chain) -> feature net
 // =====================================================================================================
+// LDS map of the forward decode kernels (k_query_points, k_decode_rays, k_render_eval): both nets, whatever the instantiation
+// decodes.  The W2^T / W1^T products of the normal chain read the SAME images (mvtx): rounds 1-3 kept 26 KB of copies here.
+template <int PREC>
+using FwdMap = DecodeMap<PREC, 96>;
+
 struct DecodeCfg {
     const float* planes;  // packed planes: n_prompts x 6 x H x W x 32
     unsigned tex0;        // texel index of this lane's prompt
@@ -138,13 +143,13 @@ struct DecodeCfg {
 };
 
 // outputs are identical in both half-waves.  gq = J^T q (WITHOUT the sphere term).
-// the weight images in L are split-fp16 images (tt_mfma16.h); the W2^T / W1^T products of the normal chain read the SAME
-// images through transposed LDS reads (mv16t) -- rounds 1-3 kept 26 KB of transposed copies here
+// the weight images in L (FwdMap) are split-fp16 images (tt_mfma16.h)
 
 // texture half: e -> feature net -> c (3 raw features).  Lanes with !valid gather nothing (their c is 0).
 template <int PREC>
 __device__ __forceinline__ void decode_tex_fwd(const float* L, const DecodeCfg& dc, float X, float Y, float Z,
                                                bool valid, int i, int hi, float (&c)[3]) {
+    typedef FwdMap<PREC> F;
     c[0] = c[1] = c[2] = 0.f;
     float e[48];
     unsigned pmask;
@@ -165,17 +170,17 @@ __device__ __forceinline__ void decode_tex_fwd(const float* L, const DecodeCfg& 
             tile_stat(dc.st, TT_STAT_SINGLE);
             float e1[16];
             live_block16(e, e1);
-            mvx_plane<PREC, 64, 96, true>(L + OFF_V1, L + LO_V1, e1, single_plane_index(pmask), k1, i, hi, &u1);
+            mvx_plane<PREC, true>(L, typename F::V1{}, e1, single_plane_index(pmask), k1, i, hi, &u1);
         } else {
-            mvx<PREC, 64, 96, true>(L + OFF_V1, L + LO_V1, e, k1, i, hi, 1.f, &u1);
+            mvx<PREC, true>(L, typename F::V1{}, e, k1, i, hi, 1.f, &u1);
         }
 #pragma unroll
         for (int r = 0; r < 32; ++r) k1[r] = fmaxf(k1[r], 0.f);
-        mvx<PREC, 64, 64, true>(L + OFF_V2, L + LO_V2, k1, k2, i, hi, u1, &u2);
+        mvx<PREC, true>(L, typename F::V2{}, k1, k2, i, hi, u1, &u2);
 #pragma unroll
         for (int r = 0; r < 32; ++r) k2[r] = fmaxf(k2[r], 0.f);
 #pragma unroll
-        for (int o = 0; o < 3; ++o) c[o] = dot_lds<64>(L + OFF_V3 + 64 * o, k2, hi) * u2;
+        for (int o = 0; o < 3; ++o) c[o] = dot_lds<64>(lds_at(L, typename F::V3{}) + 64 * o, k2, hi) * u2;
     }
 }
 
@@ -214,6 +219,7 @@ template <bool NEED_N, int PREC, bool MASK = false>
 __device__ __forceinline__ void decode_geo_fwd(const float* L, const DecodeCfg& dc, float X, float Y, float Z,
                                                bool valid, int i, int hi, float& s0, float (&gq)[3],
                                                unsigned* mask = nullptr, long long sidx = 0) {
+    typedef FwdMap<PREC> F;
     s0 = 0.f;
     gq[0] = gq[1] = gq[2] = 0.f;
     float f[16], jx[16], jy[16], jz[16];
@@ -236,30 +242,30 @@ __device__ __forceinline__ void decode_geo_fwd(const float* L, const DecodeCfg& 
     } else if (__any(any)) {
         tile_stat(dc.st, TT_STAT_EXECUTED);
         float h1[32], h2[32], u1, u2;  // RAW hidden vectors (see decode_tex_fwd): only their signs and the dot product matter
-        mvx<PREC, 64, 32, true>(L + OFF_W1, L + LO_W1, f, h1, i, hi, 1.f, &u1);
+        mvx<PREC, true>(L, typename F::W1{}, f, h1, i, hi, 1.f, &u1);
 #pragma unroll
         for (int r = 0; r < 32; ++r) h1[r] = fmaxf(h1[r], 0.f);
-        mvx<PREC, 64, 64, true>(L + OFF_W2, L + LO_W2, h1, h2, i, hi, u1, &u2);
+        mvx<PREC, true>(L, typename F::W2{}, h1, h2, i, hi, u1, &u2);
 #pragma unroll
         for (int r = 0; r < 32; ++r) h2[r] = fmaxf(h2[r], 0.f);
         if constexpr (MASK) {
             store_mask_word(mask, sidx, hi, valid, sign_mask32(h2));
         }
-        s0 = dot_lds<64>(L + OFF_W3, h2, hi) * u2;
+        s0 = dot_lds<64>(lds_at(L, typename F::W3{}), h2, hi) * u2;
         if (NEED_N) {
             // reverse-mode input gradient: a2 = m2 . w3 ; a1 = m1 . (W2^T a2) ; q = W1^T a1
             float a2[32], a1[32], q[16];
 #pragma unroll
             for (int g = 0; g < 8; ++g) {
-                f32x4 w3 = *reinterpret_cast<const f32x4*>(L + OFF_W3 + 8 * g + 4 * hi);
+                f32x4 w3 = *reinterpret_cast<const f32x4*>(lds_at(L, typename F::W3{}) + 8 * g + 4 * hi);
 #pragma unroll
                 for (int e2 = 0; e2 < 4; ++e2) a2[4 * g + e2] = h2[4 * g + e2] > 0.f ? w3[e2] : 0.f;
             }
             float ua1;
-            mvtx<PREC, 64, 64, 64, true>(L + OFF_W2, L + LO_W2, 0, a2, a1, i, hi, 1.f, &ua1);
+            mvtx<PREC, true>(L, typename F::W2{}, a2, a1, i, hi, 1.f, &ua1);
 #pragma unroll
             for (int r = 0; r < 32; ++r) a1[r] = h1[r] > 0.f ? a1[r] : 0.f;
-            mvtx<PREC, 32, 64, 32>(L + OFF_W1, L + LO_W1, 0, a1, q, i, hi, ua1);
+            mvtx<PREC>(L, typename F::W1{}, a1, q, i, hi, ua1);
             float sx = 0.f, sy = 0.f, sz = 0.f;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -303,19 +309,6 @@ struct QueryParams {
     float* out_feat;
 };
 
-// weight images of the forward decode kernels: split-fp16 (tt_mfma16.h)
-template <bool NEED_N, bool NEED_TEX, int PREC>
-__device__ __forceinline__ void stage_decode_images(float* L, const MlpPtrs& w) {
-    stage_weights<PREC, 64, 32>(L + OFF_W1, L + LO_W1, w.w1);
-    stage_weights<PREC, 64, 64>(L + OFF_W2, L + LO_W2, w.w2);
-    lds_load_matrix(L + OFF_W3, w.w3, 1, 64, 64);
-    if (NEED_TEX) {
-        stage_weights<PREC, 64, 96>(L + OFF_V1, L + LO_V1, w.v1);
-        stage_weights<PREC, 64, 64>(L + OFF_V2, L + LO_V2, w.v2);
-        lds_load_matrix(L + OFF_V3, w.v3, 3, 64, 64);
-    }
-}
-
 #define TT_DR_GEO_SAMPLES 64   // samples of a ray block per work item of the sdf-only decode (tt_decode_rays)
 #define TT_DR_GEO_MIN_ITEMS 0  // ... and no minimum number of items per wave slot
 // 8 waves (2 per SIMD) share one set of split-fp16 weight images (93 KB: one workgroup per CU)
@@ -323,9 +316,9 @@ __device__ __forceinline__ void stage_decode_images(float* L, const MlpPtrs& w) 
 
 template <bool NEED_N, bool NEED_TEX, int PREC>
 __global__ __launch_bounds__(DECODE_THREADS) void k_query_points(QueryParams p) {
-    __shared__ __attribute__((aligned(16))) float L[FwdWFloats<PREC>::value + (DECODE_THREADS / 64) * GC_SCRATCH_FLOATS];
-    float* T = L + FwdWFloats<PREC>::value + (threadIdx.x >> 6) * GC_SCRATCH_FLOATS;
-    stage_decode_images<NEED_N, NEED_TEX, PREC>(L, p.w);
+    __shared__ __attribute__((aligned(16))) float L[FwdMap<PREC>::FLOATS + (DECODE_THREADS / 64) * GC_SCRATCH_FLOATS];
+    float* T = L + FwdMap<PREC>::FLOATS + (threadIdx.x >> 6) * GC_SCRATCH_FLOATS;
+    stage_weights(L, FwdMap<PREC>{}, p.w, NEED_TEX);
     __syncthreads();
     const int lane = threadIdx.x & 63, i = lane & 31, hi = lane >> 5;
     const long long tiles_per_batch = (p.n_points + TT_TILE - 1) / TT_TILE;
@@ -373,21 +366,6 @@ __global__ __launch_bounds__(DECODE_THREADS) void k_query_points(QueryParams p) 
 // =====================================================================================================
 // tt_query_field: sdf + deformation head on the geometry planes (forward_field, few_step...:375-394)
 // =====================================================================================================
-#define OFF_D1 LDS_GEO_FLOATS
-#define OFF_D2 (OFF_D1 + 64 * W1S)
-#define OFF_D3 (OFF_D2 + 64 * W2S)
-#define LDS_FIELD_FLOATS (OFF_D3 + 3 * 64)
-// third-term images (PREC_S3), appended
-#define LO_FW1 LDS_FIELD_FLOATS
-#define LO_FW2 (LO_FW1 + LO16_FLOATS(64, 32))
-#define LO_D1 (LO_FW2 + LO16_FLOATS(64, 64))
-#define LO_D2 (LO_D1 + LO16_FLOATS(64, 32))
-#define LDS_FIELD3_FLOATS (LO_D2 + LO16_FLOATS(64, 64))
-template <int PREC>
-struct FieldWFloats {
-    static constexpr int value = PREC == PREC_S3 ? LDS_FIELD3_FLOATS : LDS_FIELD_FLOATS;
-};
-
 struct QueryFieldParams {
     const float* packed;
     MlpPtrs w;  // sdf net in w1..w3, deformation net in v1..v3 (32->64->64->3)
@@ -410,17 +388,10 @@ struct QueryFieldWaves {
 };
 template <int PREC>
 __global__ __launch_bounds__(64 * QueryFieldWaves<PREC>::value, PREC == PREC_S3 ? 1 : 2) void k_query_field(QueryFieldParams p) {
-    __shared__ __attribute__((aligned(16))) float L[FieldWFloats<PREC>::value + QueryFieldWaves<PREC>::value * GC_SCRATCH_FLOATS];
-    float* T = L + FieldWFloats<PREC>::value + (threadIdx.x >> 6) * GC_SCRATCH_FLOATS;
-    {  // split-fp16 images (tt_mfma16.h), same footprint as the fp32 ones
-        MlpPtrs w = p.w;
-        stage_weights<PREC, 64, 32>(L + OFF_W1, L + LO_FW1, w.w1);
-        stage_weights<PREC, 64, 64>(L + OFF_W2, L + LO_FW2, w.w2);
-        lds_load_matrix(L + OFF_W3, w.w3, 1, 64, 64);
-        stage_weights<PREC, 64, 32>(L + OFF_D1, L + LO_D1, w.v1);
-        stage_weights<PREC, 64, 64>(L + OFF_D2, L + LO_D2, w.v2);
-        lds_load_matrix(L + OFF_D3, w.v3, 3, 64, 64);
-    }
+    typedef DecodeMap<PREC, 32> F;  // LDS map: the sdf net, and the deformation net (w.v1 .. w.v3) as V1, V2, V3
+    __shared__ __attribute__((aligned(16))) float L[DecodeMap<PREC, 32>::FLOATS + QueryFieldWaves<PREC>::value * GC_SCRATCH_FLOATS];
+    float* T = L + DecodeMap<PREC, 32>::FLOATS + (threadIdx.x >> 6) * GC_SCRATCH_FLOATS;
+    stage_weights(L, F{}, p.w, true);  // split-fp16 images (tt_mfma16.h), same footprint as the fp32 ones
     __syncthreads();
     const int lane = threadIdx.x & 63, i = lane & 31, hi = lane >> 5;
     const long long tiles_per_batch = (p.n_points + TT_TILE - 1) / TT_TILE;
@@ -444,21 +415,21 @@ __global__ __launch_bounds__(64 * QueryFieldWaves<PREC>::value, PREC == PREC_S3 
         float s0 = 0.f, d[3] = {0.f, 0.f, 0.f};
         if (any) {  // exact skip otherwise: bias-free MLPs of a zero vector
             float h1[32], h2[32];
-            mvx<PREC, 64, 32>(L + OFF_W1, L + LO_FW1, f, h1, i, hi);
+            mvx<PREC>(L, typename F::W1{}, f, h1, i, hi);
 #pragma unroll
             for (int r = 0; r < 32; ++r) h1[r] = fmaxf(h1[r], 0.f);
-            mvx<PREC, 64, 64>(L + OFF_W2, L + LO_FW2, h1, h2, i, hi);
+            mvx<PREC>(L, typename F::W2{}, h1, h2, i, hi);
 #pragma unroll
             for (int r = 0; r < 32; ++r) h2[r] = fmaxf(h2[r], 0.f);
-            s0 = dot_lds<64>(L + OFF_W3, h2, hi);
-            mvx<PREC, 64, 32>(L + OFF_D1, L + LO_D1, f, h1, i, hi);
+            s0 = dot_lds<64>(lds_at(L, typename F::W3{}), h2, hi);
+            mvx<PREC>(L, typename F::V1{}, f, h1, i, hi);
 #pragma unroll
             for (int r = 0; r < 32; ++r) h1[r] = fmaxf(h1[r], 0.f);
-            mvx<PREC, 64, 64>(L + OFF_D2, L + LO_D2, h1, h2, i, hi);
+            mvx<PREC>(L, typename F::V2{}, h1, h2, i, hi);
 #pragma unroll
             for (int r = 0; r < 32; ++r) h2[r] = fmaxf(h2[r], 0.f);
 #pragma unroll
-            for (int o = 0; o < 3; ++o) d[o] = dot_lds<64>(L + OFF_D3 + 64 * o, h2, hi);
+            for (int o = 0; o < 3; ++o) d[o] = dot_lds<64>(lds_at(L, typename F::V3{}) + 64 * o, h2, hi);
         }
         float nrm;
         const float sdf = s0 + sphere_bias(px, py, pz, p.bias_radius, nrm);
@@ -494,9 +465,9 @@ struct DecodeRaysParams {
 // MASK: the instantiation tt_render_fwd_h2mask launches; the arithmetic and every other store are the same
 template <bool NEED_N, bool NEED_TEX, int PREC, bool MASK = false>
 __global__ __launch_bounds__(DECODE_THREADS) void k_decode_rays(DecodeRaysParams p) {
-    __shared__ __attribute__((aligned(16))) float L[FwdWFloats<PREC>::value + (DECODE_THREADS / 64) * GC_SCRATCH_FLOATS];
-    float* T = L + FwdWFloats<PREC>::value + (threadIdx.x >> 6) * GC_SCRATCH_FLOATS;
-    stage_decode_images<NEED_N, NEED_TEX, PREC>(L, p.w);
+    __shared__ __attribute__((aligned(16))) float L[FwdMap<PREC>::FLOATS + (DECODE_THREADS / 64) * GC_SCRATCH_FLOATS];
+    float* T = L + FwdMap<PREC>::FLOATS + (threadIdx.x >> 6) * GC_SCRATCH_FLOATS;
+    stage_weights(L, FwdMap<PREC>{}, p.w, NEED_TEX);
     __syncthreads();
     const tt_render_cfg& cfg = p.cfg;
     const TileGeom& tg = p.geom;
@@ -608,9 +579,9 @@ struct RenderEvalParams {
 
 template <int PREC>
 __global__ __launch_bounds__(DECODE_THREADS) void k_render_eval(RenderEvalParams p) {
-    __shared__ __attribute__((aligned(16))) float L[FwdWFloats<PREC>::value + (DECODE_THREADS / 64) * GC_SCRATCH_FLOATS];
-    float* T = L + FwdWFloats<PREC>::value + (threadIdx.x >> 6) * GC_SCRATCH_FLOATS;
-    stage_decode_images<true, true, PREC>(L, p.w);
+    __shared__ __attribute__((aligned(16))) float L[FwdMap<PREC>::FLOATS + (DECODE_THREADS / 64) * GC_SCRATCH_FLOATS];
+    float* T = L + FwdMap<PREC>::FLOATS + (threadIdx.x >> 6) * GC_SCRATCH_FLOATS;
+    stage_weights(L, FwdMap<PREC>{}, p.w, true);
     __syncthreads();
     const tt_render_cfg& cfg = p.cfg;
     const TileGeom& tg = p.geom;

@@ -35,6 +35,83 @@ typedef float f2_t __attribute__((ext_vector_type(2)));
 #define IMG16_FLOATS(ROWS, K) ((ROWS) * ((K) + 4)) /* LDS floats one (hi, mid) image occupies */
 #define LO16_FLOATS(ROWS, K) ((ROWS) * ((K) / 2 + 4)) /* ... and the image of the THIRD terms (three-piece mode) */
 
+// ---- LDS maps of weight images ------------------------------------------------------------------------------------------
+// A kernel that keeps MLP weights in LDS declares ONE map next to itself: an LdsMap over the ordered list of its members,
+//   LdsImage<ROWS, K>  a ROWS x K matrix: its (hi, mid) split-fp16 image -- or, PREC_F32, its plain fp32 image, the same floats
+//                      (row stride K + 4) -- and, PREC_S3, the image of its third terms.  A transposed copy is an image of its
+//                      own (ROWS x K of the TRANSPOSED matrix).  ON = false: the member takes no space in this instantiation;
+//   LdsRows<ROWS, K>   plain fp32 rows, row stride K (w3 / v3): consumers only need lds_at();
+// and gets every member back PLACED (at<I>): an empty tag type that carries the shape and the float offsets OFF / LO of the
+// two images.  The staging helpers and the products below take the kernel's LDS base and the tag, so the shape of an
+// operand, its image and its third-term image can only be named together.
+// Placement: the (hi, mid) / fp32 images in list order from offset 0, then -- PREC_S3 only -- the third-term images in the
+// same order, so that the first group keeps its offsets in every mode; FLOATS is the total.
+#define LDS_NONE (-1)
+template <int ROWS_, int K_, bool ON = true, int OFF_ = LDS_NONE, int LO_ = LDS_NONE>
+struct LdsImage {
+    static constexpr int ROWS = ROWS_, K = K_, OFF = OFF_, LO = LO_;
+    static constexpr int HI_FLOATS = ON ? IMG16_FLOATS(ROWS, K) : 0, LO_FLOATS = ON ? LO16_FLOATS(ROWS, K) : 0;
+    template <int O, int L>
+    using placed = LdsImage<ROWS, K, ON, ON ? O : LDS_NONE, ON ? L : LDS_NONE>;
+};
+template <int ROWS_, int K_, int OFF_ = LDS_NONE>
+struct LdsRows {
+    static constexpr int ROWS = ROWS_, K = K_, OFF = OFF_;
+    static constexpr int HI_FLOATS = ROWS * K, LO_FLOATS = 0;
+    template <int O, int L>
+    using placed = LdsRows<ROWS, K, O>;
+};
+// float offset of member n's first (third = false) / third-term image; n = number of members: the end of that group
+template <class... M>
+constexpr int lds_off(bool third, int n) {
+    const int hi[] = {M::HI_FLOATS...}, lo[] = {M::LO_FLOATS...};
+    int o = 0;
+    for (int j = 0; j < (third ? (int)sizeof...(M) : n); ++j) o += hi[j];
+    for (int j = 0; third && j < n; ++j) o += lo[j];
+    return o;
+}
+// every image starts on a multiple of 4 floats (16-byte ds_read_b128 / ds_read_b64_tr_b16 fragments) and no two overlap
+template <bool S3, class... M>
+constexpr bool lds_map_ok() {
+    constexpr int N = sizeof...(M);
+    const int size[] = {M::HI_FLOATS..., (S3 ? M::LO_FLOATS : 0)...};
+    int b[2 * N] = {};
+    for (int j = 0; j < 2 * N; ++j) b[j] = lds_off<M...>(j >= N, j % N);
+    for (int j = 0; j < 2 * N; ++j)
+        for (int k = 0; k <= j; ++k)
+            if (b[j] % 4 != 0 || (k < j && b[j] < b[k] + size[k] && b[k] < b[j] + size[j])) return false;
+    return true;
+}
+template <int PREC, class... M>
+struct LdsMap {
+    static constexpr bool S3 = PREC == PREC_S3;
+    static_assert(lds_map_ok<S3, M...>(), "LDS map: misaligned or overlapping images");
+    static constexpr int FLOATS = lds_off<M...>(S3, sizeof...(M));
+    template <int I, class T = __type_pack_element<I, M...>>
+    using at = typename T::template placed<lds_off<M...>(false, I),
+                                           S3 && T::LO_FLOATS != 0 ? lds_off<M...>(true, I) : LDS_NONE>;
+};
+// The map of the kernels that decode with BOTH nets from one set of images: the sdf net in W1, W2, w3 and a second net over
+// KV inputs (texture: 96, deformation: 32) in V1, V2, v3.  Their W^T products read the same images (mvtx).
+template <int PREC, int KV>
+struct DecodeMap : LdsMap<PREC, LdsImage<64, 32>, LdsImage<64, 64>, LdsRows<1, 64>, LdsImage<64, KV>, LdsImage<64, 64>,
+                          LdsRows<3, 64>> {
+    typedef typename DecodeMap::template at<0> W1;
+    typedef typename DecodeMap::template at<1> W2;
+    typedef typename DecodeMap::template at<2> W3;
+    typedef typename DecodeMap::template at<3> V1;
+    typedef typename DecodeMap::template at<4> V2;
+    typedef typename DecodeMap::template at<5> V3;
+};
+// address of a placed member's (hi, mid) / fp32 image, and of its third-term image (null in the modes that have none)
+template <class F, class T>
+__device__ __forceinline__ F* lds_at(F* L, T) {
+    static_assert(T::OFF != LDS_NONE, "this instantiation's map has no such member");
+    return L + T::OFF;
+}
+template <class F, class T>
+__device__ __forceinline__ F* lds_lo_at(F* L, T) { return T::LO == LDS_NONE ? nullptr : L + T::LO; }
+
 // ---- THREE-PIECE mode (NT = 3; TT_R_SPLIT3, "fp32-grade products on the fp16 pipe", round 5) -----------------------------
 // The two-piece product above carries ~2^-21.5 per product (tools/mfma16_probe.hip): each operand is represented to 2^-23
 // and the lo x lo term is dropped.  The reference multiplies in fp32 (threestudio/models/networks.py:91-97, autocast off),
@@ -171,9 +248,11 @@ __device__ __forceinline__ void stage_image16(float* dst_f, const float* __restr
 // product is formed in double (24 x 24 significand bits: exact, no intermediate fp32 rounding) and split from there.
 // Format, normalisation, pad factor and synchronisation exactly as stage_image16 (the maximum is searched on the fp32
 // products: rounding can only raise one into the next binade, which costs at most one bit of headroom).
-template <int ROWS, int K, int NT>
-__device__ __forceinline__ void stage_image16_rowscaled_t(float* dst_f, const float* __restrict__ src,
-                                                          const float* __restrict__ rs, int ld, float* lo_f = nullptr) {
+template <int NT, int ROWS, int K, bool ON, int OFF, int LO>
+__device__ __forceinline__ void stage_image16_rowscaled_t(float* L, LdsImage<ROWS, K, ON, OFF, LO> m,
+                                                          const float* __restrict__ src, const float* __restrict__ rs) {
+    constexpr int ld = ROWS;
+    float *dst_f = lds_at(L, m), *lo_f = lds_lo_at(L, m);
     half_t* dst = reinterpret_cast<half_t*>(dst_f);
     half_t* dlo = reinterpret_cast<half_t*>(lo_f);
     constexpr int RS = 2 * K + 8, RSL = K + 8;
@@ -422,6 +501,12 @@ __device__ __forceinline__ void mv16_pre(const float* img_f, const Split16<NIN, 
 #pragma unroll
         for (int k = 0; k < 16; ++k) y[16 * m + k] = RAW ? acc[m][k] : acc[m][k] * un;
 }
+// ... on a member of the kernel's LDS map (the pointer form above is what tools/split3_probe.hip drives)
+template <bool RAW = false, int NT, int ROWS, int K, bool ON, int OFF, int LO>
+__device__ __forceinline__ void mv16_pre(const float* L, LdsImage<ROWS, K, ON, OFF, LO> m, const Split16<K, PAIR_SEQ, NT>& x,
+                                         float un_x, float (&y)[ROWS / 2], int i, int hi, float* yf = nullptr) {
+    mv16_pre<ROWS, K, RAW, NT>(lds_at(L, m), x, un_x, y, i, hi, yf, lds_lo_at(L, m));
+}
 
 // ---- products with a 0/1 MASK as the B operand ------------------------------------------------------------------------
 // 1.0 is exact in ONE fp16 piece, so M m needs one MFMA per piece of M and k-step -- three (NT = 3) or two instead of six or
@@ -444,10 +529,11 @@ __device__ __forceinline__ void mask16_pairs_bits(unsigned w, unsigned (&mb)[N /
         mb[t] = (a & MASK16_ONE) | (b & (MASK16_ONE << 16));
     }
 }
-template <int NOUT, int NIN, int NT = 2>
-__device__ __forceinline__ void mv16_mask(const float* img_f, const unsigned (&mb)[NIN / 4], float (&y)[NOUT / 2], int i,
-                                          int hi, float* yf, const float* lo_f = nullptr) {
+template <int NT, int NOUT, int NIN, bool ON, int OFF, int LO>
+__device__ __forceinline__ void mv16_mask(const float* L, LdsImage<NOUT, NIN, ON, OFF, LO> im, const unsigned (&mb)[NIN / 4],
+                                          float (&y)[NOUT / 2], int i, int hi, float* yf) {
     constexpr int MT = NOUT / 32, KS = NIN / 16, RS = 2 * NIN + 8;
+    const float *img_f = lds_at(L, im), *lo_f = lds_lo_at(L, im);
     const half_t* row = reinterpret_cast<const half_t*>(img_f) + (size_t)i * RS + 8 * hi;
     const half_t* lrow = reinterpret_cast<const half_t*>(lo_f) + (size_t)i * (NIN + 8) + 8 * hi;
     f32x16 acc[MT];
@@ -534,10 +620,13 @@ __device__ __forceinline__ void mv16_ks(const float* img_f, const float (&x)[8 *
         for (int k = 0; k < 16; ++k) y[16 * mm + k] = RAW ? acc[mm][k] : acc[mm][k] * un;
 }
 // ... and on a pre-split operand (mv16_pre): x = the split of the 16 NK live entries under the per-launch scale
-template <int NOUT, int NIN, int NK, int NT = 2>
-__device__ __forceinline__ void mv16_pre_ks(const float* img_f, const Split16<16 * NK, PAIR_SEQ, NT>& x, int s0, float un_x,
-                                            float (&y)[NOUT / 2], int i, int hi, const float* lo_f = nullptr) {
-    constexpr int MT = NOUT / 32, RS = 2 * NIN + 8;
+template <int NX, int NT, int NOUT, int NIN, bool ON, int OFF, int LO>
+__device__ __forceinline__ void mv16_pre_ks(const float* L, LdsImage<NOUT, NIN, ON, OFF, LO> im,
+                                            const Split16<NX, PAIR_SEQ, NT>& x, int s0, float un_x, float (&y)[NOUT / 2],
+                                            int i, int hi) {
+    constexpr int MT = NOUT / 32, RS = 2 * NIN + 8, NK = NX / 16;
+    static_assert(NX % 16 == 0 && NX <= NIN, "x holds whole k-steps of the image's columns");
+    const float *img_f = lds_at(L, im), *lo_f = lds_lo_at(L, im);
     const half_t* row = reinterpret_cast<const half_t*>(img_f) + (size_t)i * RS + 8 * hi + 32 * s0;
     const half_t* lrow = reinterpret_cast<const half_t*>(lo_f) + (size_t)i * (NIN + 8) + 8 * hi;
     const float un = img_f[(size_t)i * (NIN + 4) + NIN] * un_x;
@@ -686,91 +775,103 @@ __device__ __forceinline__ void mv16t(const float* img_f, int col0, const float 
 // PREC_F32 (cfg.flags & TT_R_EXACT_F32): every matrix product on v_mfma_f32_32x32x2_f32 (bit-for-bit a k-ordered fmaf
 //   chain, 1/16 of the fp16 pipe's rate) from plain fp32 weight images -- the A/B reference of both split modes.
 // The fp32 image of a matrix occupies the same LDS floats as its (hi, mid) split-fp16 image (row stride K + 4), so the
-// kernels' LDS maps do not depend on F32-vs-split; PREC_S3 appends the images of the third terms (`lo` pointers below,
-// ignored by the other two modes).  The PREC_* values themselves: tt_host.h.
+// kernels' LDS maps do not depend on F32-vs-split; PREC_S3 appends the images of the third terms (lds_lo_at: null in
+// the other two modes, which ignore it).  The PREC_* values themselves: tt_host.h.
 template <int PREC>
 struct PrecNT {
     static constexpr int value = PREC == PREC_S3 ? 3 : 2;
 };
-template <int PREC, int ROWS, int K>
-__device__ __forceinline__ void stage_weights(float* dst_f, float* lo_f, const float* __restrict__ src) {
+// Staging of one member of the kernel's LDS map from its row-major source.  All threads of the workgroup must call these.
+template <int PREC, int ROWS, int K, bool ON, int OFF, int LO>
+__device__ __forceinline__ void stage_weights(float* L, LdsImage<ROWS, K, ON, OFF, LO> m, const float* __restrict__ src) {
     if constexpr (PREC == PREC_F32) {
-        lds_load_matrix(dst_f, src, ROWS, K, K + 4);
+        lds_load_matrix(lds_at(L, m), src, ROWS, K, K + 4);
     } else {
-        stage_image16<ROWS, K, false, PrecNT<PREC>::value>(dst_f, src, K, lo_f);
+        stage_image16<ROWS, K, false, PrecNT<PREC>::value>(lds_at(L, m), src, K, lds_lo_at(L, m));
+    }
+}
+template <int PREC, int ROWS, int K, int OFF>
+__device__ __forceinline__ void stage_weights(float* L, LdsRows<ROWS, K, OFF> m, const float* __restrict__ src) {
+    lds_load_matrix(lds_at(L, m), src, ROWS, K, K);
+}
+// every member of a DecodeMap from the launch's weights: the sdf net and, if `second` (block-uniform), the second net
+template <int PREC, int KV>
+__device__ __forceinline__ void stage_weights(float* L, DecodeMap<PREC, KV>, const MlpPtrs& w, bool second) {
+    typedef DecodeMap<PREC, KV> F;
+    stage_weights<PREC>(L, typename F::W1{}, w.w1);
+    stage_weights<PREC>(L, typename F::W2{}, w.w2);
+    stage_weights<PREC>(L, typename F::W3{}, w.w3);
+    if (second) {
+        stage_weights<PREC>(L, typename F::V1{}, w.v1);
+        stage_weights<PREC>(L, typename F::V2{}, w.v2);
+        stage_weights<PREC>(L, typename F::V3{}, w.v3);
     }
 }
 
-// image of src^T (src is ROWS_SRC x K_SRC row-major) for kernels that keep a transposed COPY for their `M^T x` products
+// `mt` = the image of src^T (src is K x ROWS row-major) for kernels that keep a transposed COPY for their `M^T x` products
 // instead of reading the forward image through ds_read_b64_tr_b16: the one-wave backward kernels, where LDS is not scarce
 // (occupancy is register-bound) and ds_read_b128 fragments issue at twice the rate of the transposed reads.  Nothing to
 // do under PREC_F32.
-template <int PREC, int ROWS_SRC, int K_SRC>
-__device__ __forceinline__ void stage_weights_t(float* dst_f, float* lo_f, const float* __restrict__ src) {
-    if constexpr (PREC != PREC_F32) stage_image16<K_SRC, ROWS_SRC, true, PrecNT<PREC>::value>(dst_f, src, K_SRC, lo_f);
+template <int PREC, int ROWS, int K, bool ON, int OFF, int LO>
+__device__ __forceinline__ void stage_weights_t(float* L, LdsImage<ROWS, K, ON, OFF, LO> mt, const float* __restrict__ src) {
+    if constexpr (PREC != PREC_F32)
+        stage_image16<ROWS, K, true, PrecNT<PREC>::value>(lds_at(L, mt), src, ROWS, lds_lo_at(L, mt));
 }
 
-// y[NOUT] = M[NOUT][NIN] x
+// y[ROWS] = M[ROWS][K] x, M = the member `m` of the map at L; x and y are sized by the member
 // RAW (deferred factors, see mv16): y comes back unscaled with its per-lane factor in *yf, x may carry a factor xf.  The
 // fp32 path has no factors: it returns true values and *yf = 1 (callers pass 1 on as xf).
-template <int PREC, int NOUT, int NIN, bool RAW = false>
-__device__ __forceinline__ void mvx(const float* img, const float* lo, const float (&x)[NIN / 2], float (&y)[NOUT / 2],
-                                    int i, int hi, float xf = 1.f, float* yf = nullptr) {
+template <int PREC, bool RAW = false, int ROWS, int K, bool ON, int OFF, int LO>
+__device__ __forceinline__ void mvx(const float* L, LdsImage<ROWS, K, ON, OFF, LO> m, const float (&x)[K / 2],
+                                    float (&y)[ROWS / 2], int i, int hi, float xf = 1.f, float* yf = nullptr) {
     if constexpr (PREC == PREC_F32) {
-        mv_fwd<NOUT, NIN>(img, x, y, i, hi);
+        mv_fwd<ROWS, K>(lds_at(L, m), x, y, i, hi);
         if (RAW) *yf = 1.f;
     } else {
-        mv16<NOUT, NIN, true, RAW, PrecNT<PREC>::value>(img, x, y, i, hi, xf, yf, lo);
+        mv16<ROWS, K, true, RAW, PrecNT<PREC>::value>(lds_at(L, m), x, y, i, hi, xf, yf, lds_lo_at(L, m));
     }
 }
-// y[NOUT] = M^T x with `img_t` / `lo_t` the split-fp16 images of M^T (stage_weights_t) and `img` the fp32 image of M (F32)
-template <int PREC, int NOUT, int NIN, int KM, bool RAW = false>
-__device__ __forceinline__ void mvtx_copy(const float* img_t, const float* lo_t, const float* img,
-                                          const float (&x)[NIN / 2], float (&y)[NOUT / 2], int i, int hi, float xf = 1.f,
+// y = M^T x from the pair (`mt`: split-fp16 image of M^T, stage_weights_t; `m`: fp32 image of M, read under PREC_F32 only)
+template <int PREC, bool RAW = false, int ROWS, int K, bool ON, int OFF, int LO, bool ON_M, int OFF_M, int LO_M>
+__device__ __forceinline__ void mvtx_copy(const float* L, LdsImage<ROWS, K, ON, OFF, LO> mt, LdsImage<K, ROWS, ON_M, OFF_M, LO_M> m,
+                                          const float (&x)[K / 2], float (&y)[ROWS / 2], int i, int hi, float xf = 1.f,
                                           float* yf = nullptr) {
     if constexpr (PREC == PREC_F32) {
-        mv_bwd<NOUT, NIN, KM + 4>(img, x, y, i, hi);
+        mv_bwd<ROWS, K, ROWS + 4>(lds_at(L, m), x, y, i, hi);
         if (RAW) *yf = 1.f;
     } else {
-        mv16<NOUT, NIN, true, RAW, PrecNT<PREC>::value>(img_t, x, y, i, hi, xf, yf, lo_t);
+        mv16<ROWS, K, true, RAW, PrecNT<PREC>::value>(lds_at(L, mt), x, y, i, hi, xf, yf, lds_lo_at(L, mt));
     }
 }
-// y[NOUT] = M[:, col0 .. col0 + NOUT)^T x for M (NIN rows, KM columns) staged by stage_weights at `img` (+ `lo`): from the
-// fp32 image by strided column reads (F32), from the split-fp16 images by transposed reads (mv16t)
-template <int PREC, int NOUT, int NIN, int KM, bool RAW = false>
-__device__ __forceinline__ void mvtx(const float* img, const float* lo, int col0, const float (&x)[NIN / 2],
-                                     float (&y)[NOUT / 2], int i, int hi, float xf = 1.f, float* yf = nullptr) {
+// y[NOUT] = M[:, col0 .. col0 + NOUT)^T x for the member `m` (ROWS x K) staged by stage_weights: from the fp32 image by
+// strided column reads (F32), from the split-fp16 images by transposed reads (mv16t)
+template <int PREC, int NOUT, bool RAW = false, int ROWS, int K, bool ON, int OFF, int LO>
+__device__ __forceinline__ void mvtx_cols(const float* L, LdsImage<ROWS, K, ON, OFF, LO> m, int col0, const float (&x)[ROWS / 2],
+                                          float (&y)[NOUT / 2], int i, int hi, float xf = 1.f, float* yf = nullptr) {
+    static_assert(NOUT <= K, "a column slice of the member");
     if constexpr (PREC == PREC_F32) {
-        mv_bwd<NOUT, NIN, KM + 4>(img + col0, x, y, i, hi);
+        mv_bwd<NOUT, ROWS, K + 4>(lds_at(L, m) + col0, x, y, i, hi);
         if (RAW) *yf = 1.f;
     } else {
-        mv16t<NOUT, NIN, KM, true, RAW, PrecNT<PREC>::value>(img, col0, x, y, 32 * hi + i, xf, yf, lo);
+        mv16t<NOUT, ROWS, K, true, RAW, PrecNT<PREC>::value>(lds_at(L, m), col0, x, y, 32 * hi + i, xf, yf, lds_lo_at(L, m));
     }
+}
+// ... over all K columns: y[K] = M^T x
+template <int PREC, bool RAW = false, int ROWS, int K, bool ON, int OFF, int LO>
+__device__ __forceinline__ void mvtx(const float* L, LdsImage<ROWS, K, ON, OFF, LO> m, const float (&x)[ROWS / 2],
+                                     float (&y)[K / 2], int i, int hi, float xf = 1.f, float* yf = nullptr) {
+    mvtx_cols<PREC, K, RAW>(L, m, 0, x, y, i, hi, xf, yf);
 }
 
 // ---- single-plane forms (a tile step whose plane mask has one bit, tt_device.h) -----------------------------------------
-// y[NOUT] = M[NOUT][32 pl .. 32 pl + 31] x1, x1 = the 32 live entries of the 96-entry input (the other 64 are exact zeros)
-template <int PREC, int NOUT, int NIN, bool RAW = false>
-__device__ __forceinline__ void mvx_plane(const float* img, const float* lo, const float (&x1)[16], int pl,
-                                          float (&y)[NOUT / 2], int i, int hi, float* yf = nullptr) {
+// y[ROWS] = M[ROWS][32 pl .. 32 pl + 31] x1, x1 = the 32 live entries of the 96-entry input (the other 64 are exact zeros)
+template <int PREC, bool RAW = false, int ROWS, int K, bool ON, int OFF, int LO>
+__device__ __forceinline__ void mvx_plane(const float* L, LdsImage<ROWS, K, ON, OFF, LO> m, const float (&x1)[16], int pl,
+                                          float (&y)[ROWS / 2], int i, int hi, float* yf = nullptr) {
     if constexpr (PREC == PREC_F32) {
-        mv_fwd_cols<NOUT, NIN, 4>(img, x1, 4 * pl, y, i, hi);
+        mv_fwd_cols<ROWS, K, 4>(lds_at(L, m), x1, 4 * pl, y, i, hi);
         if (RAW) *yf = 1.f;
     } else {
-        mv16_ks<NOUT, NIN, 2, RAW, PrecNT<PREC>::value>(img, x1, 2 * pl, y, i, hi, 1.f, yf, lo);
+        mv16_ks<ROWS, K, 2, RAW, PrecNT<PREC>::value>(lds_at(L, m), x1, 2 * pl, y, i, hi, 1.f, yf, lds_lo_at(L, m));
     }
 }
-// ---- LDS map of the third-term images (PREC_S3) of the forward-shaped kernels: appended to the fp32-sized map of
-// tt_device.h (OFF_W1 ... LDS_W_FLOATS), so the (hi, mid) images keep their offsets in every mode ----
-#define LO_W1 LDS_W_FLOATS
-#define LO_W2 (LO_W1 + LO16_FLOATS(64, 32))
-#define LO_V1 (LO_W2 + LO16_FLOATS(64, 64))
-#define LO_V2 (LO_V1 + LO16_FLOATS(64, 96))
-#define LDS_W3P_FLOATS (LO_V2 + LO16_FLOATS(64, 64))
-// floats of weight images a forward-shaped kernel keeps in LDS
-template <int PREC>
-struct FwdWFloats {
-    static constexpr int value = PREC == PREC_S3 ? LDS_W3P_FLOATS : LDS_W_FLOATS;
-};
-// host side: precision of a launch from the flag bits of tt_abi.h (EXACT_F32 wins; SPLIT2 = the fast mode; default S3)
-#define TT_PREC_OF(exact, split2) ((exact) ? PREC_F32 : ((split2) ? PREC_S2 : PREC_S3))
