@@ -67,6 +67,8 @@
  *   tt_tex_fwd / _bwd       nvdiffrast's 2-D `texture` without mipmaps (CUDA-only, un-vendored): sampling map_Kd at
  *                           interpolated UVs, the step the reference's export render (evaluation/mesh_visualize.py)
  *                           leaves to external tools.
+ *   tt_simplify_*           mesh simplification for export: vertex clustering with quadric-error placement.  The
+ *                           reference exports the raw marching-cubes mesh; this step has no counterpart there.
  */
 #ifndef TT_ABI_H
 #define TT_ABI_H
@@ -776,6 +778,76 @@ int tt_uv_overlap(const float* v_tex, const int32_t* t_tex_idx, int32_t Vt, int3
 int64_t tt_tex_fill_workspace_bytes(int32_t H, int32_t W);
 int tt_tex_fill(const float* img, const uint8_t* mask, int32_t H, int32_t W, int32_t C, void* workspace, float* out,
                 void* stream);
+
+/* ---- mesh simplification (tt_simplify.hip): vertex clustering with quadric-error placement ----
+ * Lindstrom 2000 ("Out-of-core simplification of large polygonal models") with the quadrics of Garland & Heckbert
+ * 1997.  The reference has no such step; it makes the low-poly mesh the exporter's baked texture is meant for.  A mesh
+ * is v_pos (V,3) fp32 and t_pos_idx (T,3) int32 with every index in [0, V) (the host checks it; a face with an index
+ * outside takes part in nothing).  Inputs besides: grid G, TT_SIMPLIFY_MIN_GRID <= G <= TT_SIMPLIFY_MAX_GRID, and
+ * lam >= 0 (the host's default is 1e-3).
+ *   box         in fp32: lo_a = min over the vertices of v_a; ext = the largest of the three extents max v_a - lo_a;
+ *               h = ext / (float)G; inv_h = (float)G / ext (two IEEE divisions).  ext == 0, V == 0 or T == 0: the host
+ *               returns the mesh as it is and calls nothing here.
+ *   cell        of EVERY vertex, referenced or not: c_a = min(G-1, max(0, (int)floorf((v_a - lo_a) * inv_h))), the
+ *               subtraction and the product each rounded to fp32 (this form has no sum behind its product, so nothing
+ *               contracts into an FMA and a float32 restatement gets bit-identical keys); key = (c_x G + c_y) G + c_z.
+ *               tt_simplify_keys writes keys (V) int64.
+ *   clusters    the distinct keys, ranked by ascending key; C of them.  The host sorts the keys (stable, so a cluster's
+ *               vertices are in ascending vertex index); tt_simplify_ranks, from the sorted keys and the permutation,
+ *               writes rank (V) int32 and leaves the cluster keys and member segments in the workspace; C goes to
+ *               out_totals[0] (DEVICE memory, read back).  centre_a = lo_a + ((float)c_a + 0.5f) * h, product and sum
+ *               each rounded to fp32.  C > TT_SIMPLIFY_MAX_CLUSTERS (three ranks must fit one 63-bit key) is
+ *               TT_ERR_UNSUPPORTED in every entry point that takes C (the host raises ValueError before it calls one).
+ *   quadric     corner k (k = 0, 1, 2) of face f contributes to the cluster r_k of that corner iff r_k differs from r_j
+ *               for all j < k: a face counts once per distinct cluster it touches.  tt_simplify_pairs writes pair_keys
+ *               (3T) int64 = r_k << 32 | 3f + k, INT64_MAX for a corner that does not contribute; the host sorts them.
+ *               n = (p1 - p0) x (p2 - p0), l = |n|; l == 0 contributes nothing; else n^ = n / l, area = l / 2,
+ *               d = -n^ . (p0 - centre); A += area n^ n^T, b += area d n^, w += area.  Everything relative to the cell
+ *               centre, for fp32 conditioning.
+ *   mean        m = mean of (v - centre) over the cluster's vertices.
+ *   placement   x solves (A + lam w I) x = lam w m - b, symmetric positive definite whenever w > 0 and lam > 0;
+ *               w == 0 (or a solve that is not finite: lam == 0 on a rank-deficient A): x = m.  Each component of x is
+ *               clamped to [-h/2, h/2]; the cluster's vertex is centre + x.  tt_simplify_solve: sums in fp32, the 3x3
+ *               Cholesky solve in double, cluster_pos (C,3) fp32.
+ *   faces       r = rank[face].  A face with two equal corners is dropped; the rest are rotated so that the smallest
+ *               rank comes first (orientation kept: (a,b,c) and (a,c,b) are different faces).  tt_simplify_faces writes
+ *               face_keys (T) int64 = r0 << 42 | r1 << 21 | r2 of the rotated triple, INT64_MAX for a dropped face; the
+ *               host sorts them (stable).  Among the faces with the same rotated triple the one with the smallest
+ *               original index stays; survivors keep their original order and hold the rotated triple.
+ *   output      the output vertices are the clusters a surviving face references, in ascending key order, renumbered
+ *               densely.  tt_simplify_emit_count leaves (V', T') in out_totals (2 int32, DEVICE memory, read back);
+ *               tt_simplify_emit, with the same workspace, writes v_out (V',3) fp32, t_out (T',3) int32 and
+ *               vertex_map (V) int32 = the output vertex of each input vertex's cluster, -1 when that cluster is not
+ *               kept.  Every write is bounded by those totals.  T' == 0: the host returns empty tensors.
+ * Guarantees: every input vertex lies within sqrt(3) h of its cluster's vertex (both are in the same cell of side h).
+ * Identical inputs give bit-identical outputs: no float atomics (the pair counts are integer atomics), and the sums
+ * run in a fixed order -- a cluster's pairs in ascending (f, k) and its members in ascending vertex index are dealt
+ * to the 64 lanes of one wave round-robin, each lane adds its share in ascending order, a fixed shuffle tree adds the
+ * lanes.  NOT guaranteed: that the output is manifold (a cell that holds two sheets of the surface welds them), free
+ * of self-intersections, or of the input's genus; faces may flip where the surface folds inside one cell.
+ * Use: bytes = tt_simplify_workspace_bytes(V, T) (V, T >= 1; one workspace for every call of one run), in the order
+ * keys, ranks, pairs, solve, faces, emit_count, emit.  Every entry point validates its arguments before any HIP call
+ * (TT_ERR_BAD_ARG); V, T <= TT_MESH_MAX_ITEMS. */
+#define TT_SIMPLIFY_MIN_GRID 2
+#define TT_SIMPLIFY_MAX_GRID 1024
+#define TT_SIMPLIFY_MAX_CLUSTERS 2097151
+int64_t tt_simplify_workspace_bytes(int32_t V, int32_t T);
+int tt_simplify_keys(const float* v_pos, int32_t V, int32_t grid, float lo_x, float lo_y, float lo_z, float inv_h,
+                     int64_t* keys, void* stream);
+int tt_simplify_ranks(const int64_t* sorted_keys, const int64_t* perm, int32_t V, int32_t T, int32_t grid,
+                      void* workspace, int32_t* rank, int32_t* out_totals, void* stream);
+int tt_simplify_pairs(const int32_t* t_pos_idx, const int32_t* rank, int32_t V, int32_t T, int32_t C, void* workspace,
+                      int64_t* pair_keys, void* stream);
+int tt_simplify_solve(const float* v_pos, const int32_t* t_pos_idx, const int64_t* sorted_pair_keys,
+                      const int64_t* perm, int32_t V, int32_t T, int32_t C, int32_t grid, float lo_x, float lo_y,
+                      float lo_z, float h, double lam, void* workspace, float* cluster_pos, void* stream);
+int tt_simplify_faces(const int32_t* t_pos_idx, const int32_t* rank, int32_t V, int32_t T, int32_t C,
+                      int64_t* face_keys, void* stream);
+int tt_simplify_emit_count(const int64_t* sorted_face_keys, const int64_t* face_perm, const int32_t* t_pos_idx,
+                           const int32_t* rank, int32_t V, int32_t T, int32_t C, void* workspace, int32_t* out_totals,
+                           void* stream);
+int tt_simplify_emit(const float* cluster_pos, const int32_t* t_pos_idx, const int32_t* rank, int32_t V, int32_t T,
+                     int32_t C, void* workspace, float* v_out, int32_t* t_out, int32_t* vertex_map, void* stream);
 
 #ifdef __cplusplus
 }

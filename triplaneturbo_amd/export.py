@@ -98,6 +98,10 @@ class MultipromptMeshExporter(Exporter):
     def configure(self, geometry, material, background) -> None:
         super().configure(geometry, material, background)
         self.ctx = raster.RasterizerContext(self.cfg.context_type, None)
+        # Mesh.simplify's arguments; attributes, not Config fields (the Config mirrors the reference's).  With either
+        # set the exported mesh is the simplified mesh[0]; with both None it is the isosurface mesh untouched.
+        self.simplify_grid: Optional[int] = None
+        self.simplify_target_faces: Optional[int] = None
 
     @torch.no_grad()
     def __call__(self, space_cache) -> List[ExporterOutput]:
@@ -108,6 +112,8 @@ class MultipromptMeshExporter(Exporter):
         mesh = isosurface(space_cache)
         if type(mesh) == list:
             mesh = mesh[0]
+        if self.simplify_grid is not None or self.simplify_target_faces is not None:
+            mesh = mesh.simplify(grid=self.simplify_grid, target_faces=self.simplify_target_faces)
         # the texture belongs to mesh[0]: decode it from the first prompt's slice of the space cache
         space_cache = prompt_slice(space_cache, 0)
         if self.cfg.fmt == "obj-mtl":

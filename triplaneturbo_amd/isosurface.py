@@ -165,6 +165,41 @@ class Mesh:
             clean_mesh.extras = self.extras
         return clean_mesh
 
+    def simplify(self, grid: Optional[int] = None, target_faces: Optional[int] = None) -> Mesh:
+        """A low-poly copy for export: vertex clustering on a grid^3 lattice with quadric-error placement
+        (ops.mesh_simplify; include/tt_abi.h "mesh simplification").  Exactly one of `grid` (2..1024) and
+        `target_faces` must be given; target_faces bisects over grids 2..256 for the largest one whose result has at
+        most that many faces (at most 8 runs; the grid-2 result when even that has more).  A new Mesh that inherits
+        extras, with extras["simplify"] = {grid, cell, n_clusters, vertex_map}; the mesh itself comes back when it has
+        no vertices, faces or extent.  The result never requires grad.  Not guaranteed manifold."""
+        if (grid is None) == (target_faces is None):
+            raise ValueError("simplify: give exactly one of grid and target_faces")
+        if grid is not None:
+            result = ops.mesh_simplify(self.v_pos, self.t_pos_idx, grid)
+        else:
+            if isinstance(target_faces, bool) or not isinstance(target_faces, int) or target_faces < 1:
+                raise ValueError(f"target_faces must be a positive int, got {target_faces!r}")
+            lo, hi = 1, 256  # lo = 1: no grid fits; every grid above hi has been seen to give too many faces
+            result = None
+            while lo < hi:
+                mid = (lo + hi + 1) // 2
+                probe = ops.mesh_simplify(self.v_pos, self.t_pos_idx, mid)
+                if probe[2]["unchanged"]:
+                    return self
+                if probe[1].shape[0] <= target_faces:
+                    lo, result = mid, probe
+                else:
+                    hi = mid - 1
+                    if hi == 1:
+                        result = probe  # grid 2 still has more: its result is returned
+        v_pos, t_pos_idx, info = result
+        if info["unchanged"]:
+            return self
+        mesh = Mesh(v_pos, t_pos_idx)
+        mesh.extras = dict(self.extras)
+        mesh.extras["simplify"] = {k: info[k] for k in ("grid", "cell", "n_clusters", "vertex_map")}
+        return mesh
+
     def _compute_vertex_normal(self) -> Tensor:
         i0, i1, i2 = (self.t_pos_idx[:, c].long() for c in range(3))
         v0, v1, v2 = self.v_pos[i0, :], self.v_pos[i1, :], self.v_pos[i2, :]

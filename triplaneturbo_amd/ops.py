@@ -11,6 +11,7 @@ from dataclasses import dataclass
 from functools import cached_property
 from typing import List, NamedTuple, Optional, Sequence, Tuple, Union
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1194,3 +1195,98 @@ def texture_fill(img: Tensor, mask: Tensor) -> Tensor:
     out = torch.empty_like(x)
     _launch("tt_tex_fill", x, m, H, W, C, ws, out, label="tex_fill")
     return out[..., 0] if squeeze else out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# mesh simplification (include/tt_abi.h, "mesh simplification"): vertex clustering with quadric-error placement
+SIMPLIFY_DEFAULT_LAM = 1e-3
+
+
+def _simplify_unchanged(v_pos: Tensor, t_pos_idx: Tensor, grid: int, cell: float) -> Tuple[Tensor, Tensor, dict]:
+    V = v_pos.shape[0]
+    info = {"grid": grid, "cell": cell, "n_clusters": V, "unchanged": True,
+            "vertex_map": torch.arange(V, device=v_pos.device, dtype=torch.int32)}
+    return v_pos, t_pos_idx, info
+
+
+@torch.no_grad()
+def mesh_simplify(v_pos: Tensor, t_pos_idx: Tensor, grid: int, lam: float = SIMPLIFY_DEFAULT_LAM
+                  ) -> Tuple[Tensor, Tensor, dict]:
+    """Vertex clustering on a grid^3 lattice over the mesh's bounding cube, one output vertex per occupied cell placed
+    by its quadric (regularised towards the mean of the cell's vertices with weight lam, clamped to the cell); faces
+    that collapse are dropped and duplicates of a surviving face removed (tt_simplify_*; three stable torch sorts and
+    three small read-backs).  Returns v_pos' (V',3) fp32, t_pos_idx' (T',3) int32 and info = {grid, cell (the cell
+    side h), n_clusters, vertex_map (V,) int32: the output vertex of each input vertex's cluster, -1 if dropped,
+    unchanged}.  Every input vertex lies within sqrt(3) h of its output vertex; bit-identical from call to call.  A
+    mesh without vertices, faces or extent comes back as it is (unchanged = True).  The output need not be manifold or
+    free of self-intersections.  Positions are detached; the result never requires grad."""
+    if isinstance(grid, bool) or not isinstance(grid, int):
+        raise TypeError(f"grid must be an int, got {type(grid).__name__}")
+    if not _lib.TT_SIMPLIFY_MIN_GRID <= grid <= _lib.TT_SIMPLIFY_MAX_GRID:
+        raise ValueError(f"grid must be in [{_lib.TT_SIMPLIFY_MIN_GRID}, {_lib.TT_SIMPLIFY_MAX_GRID}], got {grid}")
+    lam = float(lam)
+    if not 0.0 <= lam <= 1e300:
+        raise ValueError(f"lam must be a finite number >= 0, got {lam}")
+    if not isinstance(v_pos, torch.Tensor) or v_pos.dim() != 2 or v_pos.shape[1] != 3:
+        raise ValueError("v_pos must be a (V,3) tensor")
+    if not isinstance(t_pos_idx, torch.Tensor) or t_pos_idx.dim() != 2 or t_pos_idx.shape[1] != 3:
+        raise ValueError("t_pos_idx must be a (T,3) tensor")
+    if t_pos_idx.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"t_pos_idx must be int32 / int64, got {t_pos_idx.dtype}")
+    V, T = v_pos.shape[0], t_pos_idx.shape[0]
+    v_pos = v_pos.detach()
+    if V == 0 or T == 0:
+        return _simplify_unchanged(v_pos, t_pos_idx, grid, 0.0)
+    v_pos = _chk(v_pos, "v_pos")
+    if not t_pos_idx.is_cuda or t_pos_idx.device != v_pos.device:
+        raise RuntimeError("t_pos_idx must live on the GPU of v_pos")
+    lim = 1 << 28  # TT_MESH_MAX_ITEMS
+    if V > lim or T > lim:
+        raise ValueError(f"mesh too large for tt_simplify_*: V={V}, T={T} (limit {lim})")
+    dev = v_pos.device
+    # the box in fp32: minima, maxima and their difference on the device, the two divisions in IEEE fp32 on the host
+    lo_t = v_pos.amin(0)
+    box = torch.cat([lo_t.double(), (v_pos.amax(0) - lo_t).amax().reshape(1).double(),
+                     torch.stack(t_pos_idx.aminmax()).double()]).cpu()  # one read-back; every value exact in double
+    lo, ext = box[:3].float().numpy(), box[3].float().numpy()
+    if box[4] < 0 or box[5] >= V:
+        raise ValueError(f"t_pos_idx holds an index outside [0, {V})")
+    if not bool(torch.isfinite(box[:4]).all()):
+        raise ValueError("v_pos holds a value that is not finite")
+    if ext == 0:
+        return _simplify_unchanged(v_pos, t_pos_idx, grid, 0.0)
+    h, inv_h = ext / np.float32(grid), np.float32(grid) / ext
+    if not (np.isfinite(inv_h) and h > 0):
+        raise ValueError(f"the mesh's extent {float(ext)} is too small for grid {grid} in fp32")
+    lo3 = [float(x) for x in lo]
+    h, inv_h = float(h), float(inv_h)
+    tri = t_pos_idx.int().contiguous()
+    ws = _workspace("tt_simplify_workspace_bytes", V, T, device=dev)
+    i32 = dict(device=dev, dtype=torch.int32)
+    i64 = dict(device=dev, dtype=torch.int64)
+    totals = torch.empty(2, **i32)
+    keys = torch.empty(V, **i64)
+    _launch("tt_simplify_keys", v_pos, V, grid, *lo3, inv_h, keys, label="simplify_keys")
+    skeys, perm = torch.sort(keys, stable=True)
+    rank = torch.empty(V, **i32)
+    _launch("tt_simplify_ranks", skeys, perm, V, T, grid, ws, rank, totals, label="simplify_ranks")
+    C = int(totals[0].item())
+    if C > _lib.TT_SIMPLIFY_MAX_CLUSTERS:
+        raise ValueError(f"grid {grid} gives {C} clusters, more than {_lib.TT_SIMPLIFY_MAX_CLUSTERS}: use a coarser grid")
+    pkeys = torch.empty(3 * T, **i64)
+    _launch("tt_simplify_pairs", tri, rank, V, T, C, ws, pkeys, label="simplify_pairs")
+    spkeys = torch.sort(pkeys, stable=True)[0]
+    cpos = torch.empty((C, 3), device=dev, dtype=torch.float32)
+    _launch("tt_simplify_solve", v_pos, tri, spkeys, perm, V, T, C, grid, *lo3, h, lam, ws, cpos,
+            label="simplify_solve")
+    fkeys = torch.empty(T, **i64)
+    _launch("tt_simplify_faces", tri, rank, V, T, C, fkeys, label="simplify_faces")
+    sfkeys, fperm = torch.sort(fkeys, stable=True)
+    _launch("tt_simplify_emit_count", sfkeys, fperm, tri, rank, V, T, C, ws, totals, label="simplify_emit_count")
+    n_vert, n_tri = (int(x) for x in totals.cpu())
+    v_out = torch.empty((n_vert, 3), device=dev, dtype=torch.float32)
+    t_out = torch.empty((n_tri, 3), **i32)
+    vertex_map = torch.full((V,), -1, **i32)
+    if n_tri > 0:
+        _launch("tt_simplify_emit", cpos, tri, rank, V, T, C, ws, v_out, t_out, vertex_map, label="simplify_emit")
+    return v_out, t_out, {"grid": grid, "cell": h, "n_clusters": C, "vertex_map": vertex_map, "unchanged": False}
