@@ -526,9 +526,15 @@ int tt_mc_bwd(const float* level, const float* deformation, int32_t res, float i
  *     edges     every edge function is evaluated from its endpoints in canonical order (lower vertex index first), so
  *               two triangles sharing an edge see exactly negated values.  Tie (value exactly 0): the triangle owns
  *               the pixel iff its inward edge normal (sign * (n.x, n.y)) has n.x > 0, or n.x = 0 and n.y > 0 -- one
- *               of the two triangles of a shared edge.
- *     depth     the smallest z/w wins; on equal z/w the smaller triangle id.  64-bit atomicMin of
- *               (order-preserving z/w bits << 32 | tri) per pixel: bit-identical across launches.
+ *               of the two triangles of a shared edge.  The form is chosen per EDGE where it decides coverage: an edge
+ *               whose two endpoints both have w > 0 takes its sign and its tie from the screen-space form, also in a
+ *               triangle whose third vertex has w <= 0 (its neighbour across that edge may have every w > 0, and the
+ *               two forms are not each other's negation in float); such a triangle still computes (u, v, z/w) from
+ *               the homogeneous values of all three edges, that edge's clamped at 0 where the two forms disagree in
+ *               sign.  An edge with an endpoint at w <= 0 uses the homogeneous form in both of its triangles.
+ *     depth     the smallest z/w wins; on equal z/w the smaller triangle id.  z/w = -0 is stored, and compared, as
+ *               +0: the two zeros are equal depths.  64-bit atomicMin of (order-preserving bits of z/w + 0 << 32 |
+ *               tri) per pixel: bit-identical across launches.
  *     gradient  tt_rast_bwd: grad_rast (B,H,W,4) -> grad_pos (B,V,4) through u, v only (z/w and the id carry none;
  *               pos[...,2] receives nothing: u, v do not depend on clip z).
  *   interpolate out (B,H,W,C) = u a0 + v a1 + (1-u-v) a2, 0 on empty pixels; attr (attr_batch,V,C), attr_batch = B or

@@ -1,8 +1,12 @@
 """The float64 raster oracle (tests/raster_reference.py) against first principles, without a GPU: its gradients
 against central finite differences, exact single coverage of a split quad, the perimeter property of the antialias,
-and near-plane clipping against an independent per-pixel solve."""
+and near-plane clipping against an independent per-pixel solve; and on the tie scenes of tests/raster_lattice.py, what
+tests/test_gpu_raster_ties.py asks of the kernel: the oracle itself covers every pixel of the exact scenes once and
+gives a depth tie to the smaller id."""
+import pytest
 import torch
 
+import raster_lattice as L
 import raster_reference as R
 
 F64 = torch.float64
@@ -176,3 +180,95 @@ def test_near_plane_fragments_are_dropped():
             b, s = sol[:3], sol[3]
             want = bool((b >= 0).all()) and s > 0  # s = the interpolated w: in front of the camera
             assert (rast2[0, py, px, 3] > 0) == want
+
+
+def _count(pos, tri, H, W):
+    """(H,W) how many triangles, each rasterized alone, cover the pixel; and the whole mesh's ids"""
+    count = torch.zeros(H, W, dtype=torch.long)
+    for t in range(tri.shape[0]):
+        count += (R.rasterize(pos[None].double(), tri[t:t + 1], H, W)[0][0, ..., 3] > 0).long()
+    whole, amb = R.rasterize(pos[None].double(), tri, H, W)
+    return count, whole[0, ..., 3], amb[0]
+
+
+@pytest.mark.parametrize("case", [(16, 16, 2, "one", 0), (16, 16, 2, "one", 1), (16, 8, 2, "pow2", 0),
+                                  (16, 8, 2, "pow2", 1), (8, 8, 1, "pow2", 2), (16, 16, 4, "one", 3)])
+def test_exact_lattice_is_partitioned_by_the_oracle(case):
+    H, W = case[:2]
+    pos, tri = L.lattice_grid(*case)
+    assert tri.shape[0] == 2 * (H // case[2]) * (W // case[2]) and len(set(map(tuple, tri.sort(1).values.tolist()))) == tri.shape[0]
+    count, ids, amb = _count(pos, tri, H, W)
+    assert amb.any()  # the diagonals do run through pixel centres
+    assert count.min() == 1 and count.max() == 1
+    assert (ids > 0).all()
+
+
+@pytest.mark.parametrize("name", ["centre_grid", "fan"])
+def test_exact_mesh_is_partitioned_by_the_oracle_inside_and_on_its_outline(name):
+    N = 16
+    pos, tri = L.centre_grid(N, 2) if name == "centre_grid" else L.fan(N, 8)
+    count, ids, amb = _count(pos, tri, N, N)
+    assert amb.any()
+    assert count.max() == 1 and torch.equal(count > 0, ids > 0)
+    c = torch.arange(N) + 0.5  # pixel centres; both outlines are the square 2 .. 14 (centre_grid: 2.5 .. 14.5)
+    lo, hi = (2.5, 14.5) if name == "centre_grid" else (2.0, 14.0)
+    inside = ((c > lo) & (c < hi))[:, None] & ((c > lo) & (c < hi))[None, :]
+    outside = ~(((c >= lo) & (c <= hi))[:, None] & ((c >= lo) & (c <= hi))[None, :])
+    assert (count[inside] == 1).all() and (count[outside] == 0).all()
+    if name == "centre_grid":  # on the outline: the tie rule gives the mesh its low-x and low-y sides, not the others
+        assert (~inside & ~outside).any()
+        assert count[2, 3] == 1 and count[3, 2] == 1 and count[14, 3] == 0 and count[3, 14] == 0
+
+
+def test_rand_lattice_tiles_the_image_away_from_its_edges():
+    # x = fl(X w) is inexact: the oracle is no reference on the diagonals' pixel centres (the partition property is
+    # the kernel's whole assertion there); away from them the builder's mesh covers every pixel once
+    pos, tri = L.lattice_grid(12, 20, 2, "rand", 0)
+    w = pos[:, 3]
+    assert ((w >= 0.5) & (w < 2)).all() and (torch.frexp(w)[0] * 2 ** 24 % 2 ** 12 != 0).any()  # non-dyadic
+    count, ids, amb = _count(pos, tri, 12, 20)
+    assert amb.any() and (~amb).sum() > 100
+    assert (count[~amb] == 1).all()
+
+
+@pytest.mark.parametrize("W,d", [(32, (1, 3)), (32, (3, 1)), (64, (1, 1)), (64, (3, 5))])
+def test_mixed_edge_scene_is_what_it_says(W, d):
+    for seed in range(8):
+        pos, tri, pix = L.mixed_edge(W, d, seed)
+        p = pos.double()
+        n_front = [(p[t.long(), 3] > 0).sum().item() for t in tri]
+        assert sorted(n_front) == [2, 3]  # one triangle in front, one with a vertex behind the camera
+        shared = sorted(set(tri[0].tolist()) & set(tri[1].tolist()))
+        assert len(shared) == 2 and (p[shared, 3] > 0).all()
+        a, b = (p[i, :2] / p[i, 3:4] for i in shared)
+        X, Y = R.pixel_ndc(W, W)
+        c = torch.stack([X[pix[:, 0]], Y[pix[:, 1]]], -1)
+        cross = (b - a)[0] * (c - a)[:, 1] - (b - a)[1] * (c - a)[:, 0]
+        assert cross.abs().max() < 1e-6  # the returned pixel centres lie on the edge, up to the rounding of x = fl(X w)
+        s = ((c - a) * (b - a)).sum(-1) / ((b - a) ** 2).sum()
+        assert ((s > 0) & (s < 1)).all() and len(pix) >= 2
+        count, _, amb = _count(pos, tri, W, W)
+        assert amb[pix[:, 1], pix[:, 0]].all()  # the oracle is no reference there
+        assert (count[~amb] <= 1).all()  # the visible parts lie on opposite sides of the edge
+        for k in range(len(pix)):  # and meet along it: around an on-edge centre both triangles show
+            y0, x0 = max(pix[k, 1] - 1, 0), max(pix[k, 0] - 1, 0)
+            near = [(R.rasterize(pos[None].double(), tri[t:t + 1], W, W)[0][0, y0:y0 + 3, x0:x0 + 3, 3] > 0).any() for t in (0, 1)]
+            assert all(near)
+            if k == 1:
+                break
+
+
+@pytest.mark.parametrize("signed_zero", [False, True])
+def test_oracle_gives_a_depth_tie_to_the_smaller_id(signed_zero):
+    N = 16
+    pos, tri = L.coincident_quads(N, signed_zero)
+    if signed_zero:
+        assert not torch.signbit(pos[:4, 2]).any() and torch.signbit(pos[4:, 2]).all() and (pos[:, 2] == 0).all()
+    for t, first in ((tri, 0), (tri[[2, 3, 0, 1]], 4)):
+        r, amb = R.rasterize(pos[None].double(), t, N, N)
+        ids = r[0, ..., 3]
+        assert (ids > 0).sum() == 12 * 12 and amb[0][ids > 0].all()  # every covered pixel is a depth tie
+        assert ids.max() == 2  # the two triangles listed first
+        assert (t.long()[ids[ids > 0].long() - 1, 0] // 4 * 4 == first).all()
+        alone, _ = R.rasterize(pos[None].double(), t[2:], N, N)  # the quad listed second covers the same pixels
+        assert torch.equal(alone[0, ..., 3] > 0, ids > 0)

@@ -169,7 +169,9 @@ __global__ __launch_bounds__(RS_BLOCK) void k_rast_cover(const float* __restrict
         if (!rast_slot(m, lo, b, t, pb) || !tri_setup(pos, tri, pb, t, V, s)) continue;
         float u, v, zw, S;
         if (!tri_cover(s, pix_ndc(px, W), pix_ndc_lo(px, W), pix_ndc(py, H), pix_ndc_lo(py, H), u, v, zw, S)) continue;
-        const unsigned long long key = ((unsigned long long)ordered_bits(zw) << 32) | (unsigned)t;
+        // zw + 0: -0 becomes +0, so that the key ranks the two zeros as the equal depths they are (ordered_bits alone
+        // puts -0 in front)
+        const unsigned long long key = ((unsigned long long)ordered_bits(zw + 0.f) << 32) | (unsigned)t;
         atomicMin(keys + ((long long)b * H + py) * W + px, key);
     }
 }
@@ -191,7 +193,7 @@ __global__ __launch_bounds__(RS_BLOCK) void k_rast_resolve(const float* __restri
         float u, v, zw, S;
         if (t < T && tri_setup(pos, tri, pos_batch == 1 ? 0 : b, t, V, s) &&
             tri_cover(s, pix_ndc(px, W), pix_ndc_lo(px, W), pix_ndc(py, H), pix_ndc_lo(py, H), u, v, zw, S))
-            out = make_float4(u, v, zw, (float)(t + 1));
+            out = make_float4(u, v, zw + 0.f, (float)(t + 1));  // the depth of the key: never -0
     }
     reinterpret_cast<float4*>(rast)[p] = out;
 }

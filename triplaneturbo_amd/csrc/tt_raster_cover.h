@@ -12,7 +12,8 @@
 struct TriSetup {
     int idx[3];
     float x[3], y[3], z[3], w[3];
-    bool homog;     // some w <= 0: homogeneous edge functions; else screen-space ones (all w > 0, the common case)
+    bool homog;     // some w <= 0: homogeneous edge functions (but an edge with both endpoints at w > 0 is decided by
+                    // the screen-space form: tri_cover); else screen-space ones (all w > 0, the common case)
     float X[3], Y[3], ZW[3];  // screen path: NDC x/w, y/w, z/w of the vertices
     float n[3][3];  // homogeneous path: canonical edge k (opposite vertex k) v_lo x v_hi over (x, y, w)
     float XL[3], YL[3];       // their rounding residuals (x/w = X + XL to about twice float precision)
@@ -66,7 +67,9 @@ __device__ __forceinline__ bool tri_setup(const float* __restrict__ pos, const i
     }
     s.homog = !(fminf(fminf(s.w[0], s.w[1]), s.w[2]) > 0.f);  // one compare (finite here): see pix_tri
     // screen-space edge functions from coordinate differences when all w > 0: accurate for triangles of a few pixels,
-    // where the homogeneous cross products lose the small area to cancellation (unused on the homogeneous path)
+    // where the homogeneous cross products lose the small area to cancellation (the homogeneous path uses them on the
+    // edges whose two endpoints have w > 0; a quotient by w <= 0 stays in its own vertex's entries, which no such
+    // edge reads)
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         s.X[k] = s.x[k] / s.w[k];
@@ -122,17 +125,23 @@ __device__ __forceinline__ bool tri_cover(const TriSetup& s, float X, float XL, 
     float te[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
+        // An edge whose endpoints both have w > 0 is decided (sign and tie) by the screen-space form, on either path:
+        // its neighbour across the edge may be a screen-path triangle, and the two forms, which differ by the factor
+        // w_lo w_hi > 0 in exact arithmetic, are not each other's negation in float.  The same operands in the same
+        // order on both sides are.
         float c, gx, gy;
-        if (s.homog) {
-            c = (s.n[k][0] * X + s.n[k][1] * Y) + s.n[k][2];
-            gx = s.n[k][0];
-            gy = s.n[k][1];
-        } else {
+        // (ex / el of such an edge hold quotients by its own two w only: nothing of a vertex at w <= 0 reaches it)
+        const bool scr = fminf(s.w[(k + 1) % 3], s.w[(k + 2) % 3]) > 0.f;  // one compare; every edge of the screen path
+        if (scr) {
             const float ax = (s.ex[k][0] - X) + (s.el[k][0] - XL), ay = (s.ex[k][1] - Y) + (s.el[k][1] - YL);
             const float bx = (s.ex[k][2] - X) + (s.el[k][2] - XL), by = (s.ex[k][3] - Y) + (s.el[k][3] - YL);
             c = ax * by - ay * bx;
             gx = s.ex[k][1] - s.ex[k][3];
             gy = s.ex[k][2] - s.ex[k][0];
+        } else {
+            c = (s.n[k][0] * X + s.n[k][1] * Y) + s.n[k][2];
+            gx = s.n[k][0];
+            gy = s.n[k][1];
         }
         const float t = s.sg[k] * c;
         if (t < 0.f) return false;
@@ -143,6 +152,15 @@ __device__ __forceinline__ bool tri_cover(const TriSetup& s, float X, float XL, 
         }
         if (!(t >= 0.f)) return false;  // NaN
         te[k] = t;
+        if (s.homog) {
+            if (scr) {
+                // (u, v, z/w) of a homogeneous-path triangle weigh every edge by its homogeneous value; where rounding
+                // puts it on the other side of the edge than the deciding screen-space form, the weight is 0
+                const float th = s.sg[k] * ((s.n[k][0] * X + s.n[k][1] * Y) + s.n[k][2]);
+                if (th != th) return false;
+                te[k] = fmaxf(th, 0.f);
+            }
+        }
     }
     if (s.homog) {
         const float sum = (te[0] + te[1]) + te[2];
