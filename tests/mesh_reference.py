@@ -167,6 +167,15 @@ def hand_mesh():
     return v, tri
 
 
+def sheet(n):
+    """v_pos (n*n, 3) float32 at z = 0, tri (2 (n-1)^2, 3) int64: an n x n vertex grid, vertex i * n + j at (i, j, 0);
+    the cell with lowest corner a gives (a, a+n, a+1) and (a+1, a+n, a+n+1); all first faces, then all second faces"""
+    i, j = np.meshgrid(np.arange(n), np.arange(n), indexing="ij")
+    v = np.stack([i, j, np.zeros_like(i)], -1).reshape(-1, 3).astype(np.float32)
+    a = (i[:-1, :-1] * n + j[:-1, :-1]).reshape(-1).astype(np.int64)
+    return v, np.concatenate([np.stack([a, a + n, a + 1], 1), np.stack([a + 1, a + n, a + n + 1], 1)])
+
+
 def sphere_field(R, centre=(0.5, 0.5, 0.5), radius=0.3):
     x = np.linspace(0.0, 1.0, R)
     X, Y, Z = np.meshgrid(x, x, x, indexing="ij")

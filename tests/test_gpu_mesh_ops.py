@@ -211,6 +211,17 @@ def test_remove_outlier_edge_cases(dev):
     assert m.remove_outlier(0.5) is m
 
 
+def test_remove_outlier_of_a_cut_sheet_crosses_the_scan_seam_in_both_counters(dev):
+    """520 x 520 sheet without the faces of cell row 3: components of 3114 and 534570 faces.  remove_outlier(0.5) drops
+    the small one, which sits first, so every surviving id shifts; V' = 268320 and T' = 534570 both exceed the 262144
+    items (1024 blocks of 256) that one chunk of the block-total scan covers."""
+    n = 520
+    v, t = M.sheet(n)
+    t = t[t.min(1) // n != 3]
+    out = _check_remove(v, t, 0.5, dev)
+    assert tuple(out.v_pos.shape) == (268320, 3) and tuple(out.t_pos_idx.shape) == (534570, 3)
+
+
 def _mesh_renderer(dev):
     s = json.load(open(os.path.join(HERE, "golden", "reference_mesh_renderer_config.json")))
     tc = json.load(open(os.path.join(HERE, "golden", "reference_training_config.json")))

@@ -62,6 +62,41 @@ def test_matches_the_restatement(dev, name, grid):
         assert t2.tolist() == [[0, 2, 1], [0, 1, 2]]  # [[A,B,C],[A,C,B]] with ranks A = 0, C = 1, B = 2
 
 
+def test_heightfield_crosses_the_scan_seam_in_both_counters(dev):
+    """A 520 x 520 heightfield with unreferenced vertices spliced into the middle of the vertex array, grid 1024:
+    309029 clusters of which 270400 are marked, 538722 kept faces.  Both counters exceed the 262144 items that one chunk
+    of the block-total scan covers, and the cluster compaction is not the identity.  Faces, vertex_map and cluster
+    count must equal the restatement's; positions are held to the contract's own bound (a mapped vertex and its output
+    vertex share a cell: at most sqrt(3) h apart), the deviation from the restatement is printed."""
+    import mesh_reference as M
+    n = 520
+    v, t = M.sheet(n)
+    rng = np.random.default_rng(0)
+    x, y = v[:, 0].reshape(n, n), v[:, 1].reshape(n, n)
+    noise = rng.uniform(-0.3, 0.3, (n, n)).astype(np.float32)
+    v[:, 2] = (np.float32(40) * np.sin(x / np.float32(23)) * np.cos(y / np.float32(17)) + noise).reshape(-1)
+    loose = v[::7].copy()  # referenced by no face
+    loose[:, 2] += 100
+    mid = n * n // 2
+    v = np.concatenate([v[:mid], loose, v[mid:]])
+    t = np.where(t >= mid, t + len(loose), t).astype(np.int32)
+    v_ref, t_ref, i_ref = S.simplify(v, t, 1024)
+    assert i_ref["n_clusters"] == 309029 and int((i_ref["vertex_map"] == -1).sum()) == 38629
+    assert v_ref.shape == (270400, 3) and t_ref.shape == (538722, 3)
+    v2, t2, info = ops.mesh_simplify(torch.from_numpy(v).to(dev), torch.from_numpy(t).to(dev), 1024)
+    assert info["n_clusters"] == i_ref["n_clusters"]
+    vmap = info["vertex_map"].cpu().numpy()
+    assert np.array_equal(vmap, i_ref["vertex_map"])
+    assert np.array_equal(t2.cpu().numpy(), t_ref)
+    assert tuple(v2.shape) == v_ref.shape
+    got = v2.cpu().numpy().astype(np.float64)
+    print(f"heightfield G=1024: max |v' - ref| = {np.abs(got - v_ref.astype(np.float64)).max() / info['cell']:.3e} h")
+    mapped = vmap >= 0
+    dist = np.linalg.norm(v[mapped].astype(np.float64) - got[vmap[mapped]], axis=1)
+    print(f"heightfield G=1024: max |v - v'[vertex_map]| = {dist.max() / info['cell']:.4f} h")
+    assert dist.max() <= np.sqrt(3.0) * info["cell"]
+
+
 def test_two_calls_are_bit_identical(dev):
     mesh = gpu_mesh("sphere32", dev)
     a = ops.mesh_simplify(mesh.v_pos, mesh.t_pos_idx, 8)

@@ -1,6 +1,6 @@
 """Dev tool: latency of the marching-cubes mesh extraction (tt_mc_*, triplaneturbo_amd.isosurface) at the exporter's
 resolution on one random sphere-biased cache (as tests/test_gpu_baseline_configs.py::test_config4_...), with HIP events,
-warm-up and repeats.  Reports the count launch (k_mc_classify + k_mc_scan_blocks), the 8-byte read-back, the emit, the
+warm-up and repeats.  Reports the count launch (k_mc_classify + k_compact2_blocks), the 8-byte read-back, the emit, the
 backward, the extraction end to end (ops.marching_cubes forward) and isosurface() + colorize_mesh() for one prompt, and
 a bytes roofline of the kernels (algorithmic bytes from the shapes and V / T over the kernel time, against the HBM peak).
 Per-kernel durations of the two count kernels: run it under `rocprofv3 --kernel-trace --stats`.
@@ -17,6 +17,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import triplaneturbo_amd as tt  # noqa: E402
 from triplaneturbo_amd import _lib, ops  # noqa: E402
 from triplaneturbo_amd.isosurface import DiffMarchingCubeHelper, colorize_mesh, isosurface  # noqa: E402
+
+if os.environ.get("TT_LIB_VARIANT"):  # dev A/B of an experiment build (tools/build_variants.py)
+    _lib.use_variant(os.environ["TT_LIB_VARIANT"])
 
 HBM_PEAK = 8.0e12      # MI355X HBM3E, spec
 HBM_MEASURED = 6.29e12  # float4 copy

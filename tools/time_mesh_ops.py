@@ -23,8 +23,11 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import triplaneturbo_amd as tt  # noqa: E402
-from triplaneturbo_amd import ops  # noqa: E402
+from triplaneturbo_amd import _lib, ops  # noqa: E402
 from triplaneturbo_amd.isosurface import DiffMarchingCubeHelper, Mesh, isosurface  # noqa: E402
+
+if os.environ.get("TT_LIB_VARIANT"):  # dev A/B of an experiment build (tools/build_variants.py)
+    _lib.use_variant(os.environ["TT_LIB_VARIANT"])
 
 
 def timed(fn, iters, warmup):

@@ -76,6 +76,10 @@ static inline int tt_validate_points(int32_t n_batch, int64_t n_points, int32_t 
     return TT_OK;
 }
 
+// The mesh-stage kernels take one item per thread in blocks of TT_ITEM_BLOCK threads: the grid for n items
+#define TT_ITEM_BLOCK 256
+static inline unsigned tt_grid(long long n) { return (unsigned)((n + TT_ITEM_BLOCK - 1) / TT_ITEM_BLOCK); }
+
 // Carves the sections of one workspace allocation: every section starts 256-byte aligned, in the order of the take()
 // calls.  With a null base take() returns null and only bytes() means something (the tt_*_workspace_bytes queries run
 // the same function as the launches, so a section cannot be sized in one place and placed in another).

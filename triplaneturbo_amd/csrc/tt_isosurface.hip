@@ -8,52 +8,43 @@
 // Four launches, no atomics (identical launches give bit-identical results), wave64, 256 threads = 256 consecutive
 // grid points per block (k fastest, so every level load is coalesced):
 //   k_mc_classify     per point: 3-bit crossing mask of its +x/+y/+z edges; per cell origin: case index and triangle
-//                     count; in-block exclusive scan of (n_vert, n_tri) packed as two 16-bit halves (a block holds at
-//                     most 256 x 3 vertices and 256 x TT_MC_MAX_TRIS triangles); block totals
-//   k_mc_scan_blocks  one block scans the block totals (64-bit: vertices low, triangles high) -> block offsets and the
-//                     grand totals (the host reads those 8 bytes: the only round trip)
+//                     count; first level of the compaction of tt_compact.h (vertices low, triangles high)
+//   k_compact2_blocks (tt_compact.h) block offsets and grand totals (the host reads those 8 bytes: the only round trip)
 //   k_mc_emit         per point: its vertices (interpolated, optionally deformed) and its cell's triangles, vertex ids
-//                     via table edge -> (owner point, axis) -> block offset + in-block offset + rank of the axis
+//                     via table edge -> (owner point, axis) -> the owner's vertex offset + rank of the axis
 //   k_mc_bwd          gather per point over its 6 incident edges: dense grad_level and grad_deformation, no scatter
-#include "tt_host.h"
-#include "tt_scan.h"
+#include "tt_compact.h"
 
 #pragma clang fp contract(off)  // the interpolation exactly as written in tt_abi.h (the numpy oracle replays it)
 
 #define TT_MC_TABLE static __constant__ const
 #include "tt_mc_tables.h"
 
-#define MC_BLOCK 256
-#define MC_SCAN_BLOCK TT_SCAN_BLOCK
+#define MC_BLOCK TT_COMPACT_BLOCK
+static_assert(TT_MC_MAX_TRIS >= 3, "a point owns up to 3 vertices: the larger per-item count bounds both counters");
 
 // base-corner offset (di | dj << 1 | dk << 2) of each of the 12 cube edges (tools/gen_mc_tables.py)
 static __constant__ const unsigned char k_edge_base[12] = {0, 2, 4, 6, 0, 1, 4, 5, 0, 1, 2, 3};
 
 struct McWs {
     unsigned char *mask, *cas;
-    int* local;
-    unsigned* bsum;
-    unsigned long long* boff;
-    int* tot;
+    TtCompact2 c;  // items: grid points; low counter: vertices, high: triangles
 };
 
 struct McLayout {
     McWs w;
-    long long n, nblk, bytes;  // grid points, blocks of MC_BLOCK of them, size of the workspace
+    long long bytes;  // size of the workspace
 };
 
 // the workspace sections (tt_mc_workspace_bytes); base may be null for the size alone
 static McLayout mc_layout(void* base, int res) {
     TtCarver c{(char*)base};
     McLayout l;
-    l.n = (long long)res * res * res;
-    l.nblk = (l.n + MC_BLOCK - 1) / MC_BLOCK;
-    l.w.mask = c.take<unsigned char>(l.n);          // [n] bit a: the edge p -> p + e_a crosses
-    l.w.cas = c.take<unsigned char>(l.n);           // [n] case index of the cell with origin p (0: no cell origin)
-    l.w.local = c.take<int>(l.n);                   // [n] in-block exclusive prefix: n_vert | n_tri << 16
-    l.w.bsum = c.take<unsigned>(l.nblk);            // [nblk] block totals, same packing
-    l.w.boff = c.take<unsigned long long>(l.nblk);  // [nblk] block offsets: vertices | triangles << 32
-    l.w.tot = c.take<int>(64);                      // [2] grand totals: vertices, triangles
+    const long long n = (long long)res * res * res;
+    l.w.mask = c.take<unsigned char>(n);  // [n] bit a: the edge p -> p + e_a crosses
+    l.w.cas = c.take<unsigned char>(n);   // [n] case index of the cell with origin p (0: no cell origin)
+    l.w.c = tt_compact2_carve(c, n, nullptr);
+    l.w.c.tot = c.take<int>(64);  // [2] grand totals: vertices, triangles (behind the compaction's sections, as ever)
     l.bytes = c.bytes();
     return l;
 }
@@ -61,7 +52,7 @@ static McLayout mc_layout(void* base, int res) {
 __global__ __launch_bounds__(MC_BLOCK) void k_mc_classify(const float* __restrict__ level, int R, float iso, McWs w) {
     const int n = R * R * R;
     const int p = blockIdx.x * MC_BLOCK + threadIdx.x;
-    unsigned packed = 0;
+    unsigned n_vert = 0, n_tri = 0;
     if (p < n) {
         const int k = p % R, j = (p / R) % R, i = p / (R * R);
         // neighbour strides, 0 on the far boundary (the point is then its own neighbour: no crossing, no cell)
@@ -76,22 +67,16 @@ __global__ __launch_bounds__(MC_BLOCK) void k_mc_classify(const float* __restric
         const int origin = max(max(i, j), k) < R - 1 ? cas : 0;
         w.mask[p] = (unsigned char)mask;
         w.cas[p] = (unsigned char)origin;
-        packed = (unsigned)__popc(mask) | ((unsigned)tt_mc_tri_count[origin] << 16);
+        n_vert = (unsigned)__popc(mask);
+        n_tri = (unsigned)tt_mc_tri_count[origin];
     }
-    unsigned total;
-    const unsigned before = tt_block_exclusive_scan<unsigned, MC_BLOCK>(packed, &total);
-    if (p < n) w.local[p] = (int)before;
-    if (threadIdx.x == 0) w.bsum[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(MC_SCAN_BLOCK) void k_mc_scan_blocks(McWs w, int nblk, int* __restrict__ out_totals) {
-    tt_scan_block_totals(w.bsum, nblk, w.boff, w.tot, out_totals);
+    tt_compact2_first_level<TT_MC_MAX_TRIS>(w.c, n_vert, n_tri);
 }
 
 // vertex id of the edge (owner point q, axis a): requires bit a of mask[q]
 __device__ __forceinline__ int mc_vertex_id(const McWs& w, int q, int a) {
     const int m = w.mask[q];
-    return (int)(unsigned)(w.boff[q >> 8] & 0xffffffffull) + (w.local[q] & 0xffff) + __popc(m & ((1 << a) - 1));
+    return tt_compact2_lo(w.c, q) + __popc(m & ((1 << a) - 1));
 }
 
 template <bool DEF>
@@ -101,7 +86,7 @@ __global__ __launch_bounds__(MC_BLOCK) void k_mc_emit(const float* __restrict__ 
     const int n = R * R * R;
     const int p = blockIdx.x * MC_BLOCK + threadIdx.x;
     if (p >= n) return;
-    const int n_vert = w.tot[0], n_tri = w.tot[1];  // bound of every write: the counts the scan produced
+    const int n_vert = w.c.tot[0], n_tri = w.c.tot[1];  // bound of every write: the counts the scan produced
     const int m = w.mask[p];
     if (m) {
         const int coord[3] = {p / (R * R), (p / R) % R, p % R};
@@ -135,7 +120,7 @@ __global__ __launch_bounds__(MC_BLOCK) void k_mc_emit(const float* __restrict__ 
     const int cas = w.cas[p];
     const int nt = tt_mc_tri_count[cas];
     if (nt == 0) return;
-    const int tb = (int)(unsigned)(w.boff[p >> 8] >> 32) + (w.local[p] >> 16);
+    const int tb = tt_compact2_hi(w.c, p);
     for (int t = 0; t < TT_MC_MAX_TRIS; ++t) {
         if (t >= nt) break;
         int ids[3];
@@ -190,7 +175,7 @@ __global__ __launch_bounds__(MC_BLOCK) void k_mc_bwd(const float* __restrict__ l
     const int n = R * R * R;
     const int p = blockIdx.x * MC_BLOCK + threadIdx.x;
     if (p >= n) return;
-    const int n_vert = w.tot[0];
+    const int n_vert = w.c.tot[0];
     const int coord[3] = {p / (R * R), (p / R) % R, p % R};
     const int stride[3] = {R * R, R, 1};
     float gl = 0.f, gd[3] = {0.f, 0.f, 0.f};
@@ -228,25 +213,23 @@ extern "C" int64_t tt_mc_workspace_bytes(int32_t res) {
 extern "C" int tt_mc_count(const float* level, int32_t res, float isovalue, void* workspace, int32_t* out_totals,
                            void* stream) {
     if (!mc_res_ok(res) || !level || !workspace || !out_totals) return TT_ERR_BAD_ARG;
-    const McLayout l = mc_layout(workspace, res);
-    const McWs& w = l.w;
+    const McWs w = mc_layout(workspace, res).w;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_mc_classify, dim3((unsigned)l.nblk), dim3(MC_BLOCK), 0, s, level, res, isovalue, w);
-    hipLaunchKernelGGL(k_mc_scan_blocks, dim3(1), dim3(MC_SCAN_BLOCK), 0, s, w, (int)l.nblk, out_totals);
+    hipLaunchKernelGGL(k_mc_classify, dim3((unsigned)w.c.nblk), dim3(MC_BLOCK), 0, s, level, res, isovalue, w);
+    tt_compact2_scan_blocks(w.c, out_totals, s);
     return tt_check_launch();
 }
 
 extern "C" int tt_mc_emit(const float* level, const float* deformation, int32_t res, float isovalue, void* workspace,
                           float* v_pos, int32_t* t_pos_idx, void* stream) {
     if (!mc_res_ok(res) || !level || !workspace || !v_pos || !t_pos_idx) return TT_ERR_BAD_ARG;
-    const McLayout l = mc_layout(workspace, res);
-    const McWs& w = l.w;
+    const McWs w = mc_layout(workspace, res).w;
     hipStream_t s = (hipStream_t)stream;
     if (deformation)
-        hipLaunchKernelGGL(k_mc_emit<true>, dim3((unsigned)l.nblk), dim3(MC_BLOCK), 0, s, level, deformation, res,
+        hipLaunchKernelGGL(k_mc_emit<true>, dim3((unsigned)w.c.nblk), dim3(MC_BLOCK), 0, s, level, deformation, res,
                            isovalue, w, v_pos, (int*)t_pos_idx);
     else
-        hipLaunchKernelGGL(k_mc_emit<false>, dim3((unsigned)l.nblk), dim3(MC_BLOCK), 0, s, level, nullptr, res,
+        hipLaunchKernelGGL(k_mc_emit<false>, dim3((unsigned)w.c.nblk), dim3(MC_BLOCK), 0, s, level, nullptr, res,
                            isovalue, w, v_pos, (int*)t_pos_idx);
     return tt_check_launch();
 }
@@ -255,14 +238,13 @@ extern "C" int tt_mc_bwd(const float* level, const float* deformation, int32_t r
                          const float* grad_v, float* grad_level, float* grad_deformation, void* stream) {
     if (!mc_res_ok(res) || !level || !workspace || !grad_v || !grad_level) return TT_ERR_BAD_ARG;
     if ((deformation == nullptr) != (grad_deformation == nullptr)) return TT_ERR_BAD_ARG;
-    const McLayout l = mc_layout(workspace, res);
-    const McWs& w = l.w;
+    const McWs w = mc_layout(workspace, res).w;
     hipStream_t s = (hipStream_t)stream;
     if (deformation)
-        hipLaunchKernelGGL(k_mc_bwd<true>, dim3((unsigned)l.nblk), dim3(MC_BLOCK), 0, s, level, deformation, res,
+        hipLaunchKernelGGL(k_mc_bwd<true>, dim3((unsigned)w.c.nblk), dim3(MC_BLOCK), 0, s, level, deformation, res,
                            isovalue, w, grad_v, grad_level, grad_deformation);
     else
-        hipLaunchKernelGGL(k_mc_bwd<false>, dim3((unsigned)l.nblk), dim3(MC_BLOCK), 0, s, level, nullptr, res, isovalue,
-                           w, grad_v, grad_level, nullptr);
+        hipLaunchKernelGGL(k_mc_bwd<false>, dim3((unsigned)w.c.nblk), dim3(MC_BLOCK), 0, s, level, nullptr, res,
+                           isovalue, w, grad_v, grad_level, nullptr);
     return tt_check_launch();
 }

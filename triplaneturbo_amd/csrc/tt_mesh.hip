@@ -14,32 +14,28 @@
 //   k_uf_hook     per face pair: union
 //   k_uf_flatten  label[f] = root(f) (path halving), count[label] += 1 (integer atomics)
 //   k_uf_max      max count over the roots (integer atomicMax)
-// Compaction (count -> 8-byte read-back -> emit, as tt_mc_count / tt_mc_emit; scans of tt_scan.h):
+// Compaction (count -> 8-byte read-back -> emit, as tt_mc_count / tt_mc_emit):
 //   k_cc_keep     threshold on the device, fkeep[f], vmark[v] = 0
 //   k_cc_mark     vmark[v] = 1 for the vertices of kept faces
-//   k_cc_scan     in-block scan of vmark | fkeep << 16, block totals
-//   k_cc_blocks   one block: block offsets, (V', T')
+//   k_compact2_flags / k_compact2_blocks   (tt_compact.h) offsets of the marked vertices and kept faces, (V', T')
 //   k_cc_emit     kept vertices and remapped kept faces, in their original order
 // Losses: per-item kernels write fixed-order block partials, one block sums them in fixed order; the gradients are
 // CSR gathers (no atomics).  Every value is bit-identical from launch to launch.
-#include "tt_host.h"
-#include "tt_scan.h"
+#include "tt_compact.h"
 
-#define MESH_BLOCK 256
+#define MESH_BLOCK TT_ITEM_BLOCK
 #define MESH_FINAL_BLOCK 256
 
 struct MeshWs {
     int *parent, *count, *misc;
     unsigned char *fkeep, *vmark;
-    int* local;
-    unsigned* bsum;
-    unsigned long long* boff;
+    TtCompact2 c;  // items: max(V, T); low counter: marked vertices, high: kept faces; totals in misc[2..3]
     float *part, *w;
 };
 
 struct MeshLayout {
     MeshWs w;
-    long long n, nblk, nblk_loss, bytes;  // compaction items and blocks, loss-reduction blocks, size of the workspace
+    long long bytes;  // size of the workspace
 };
 
 // the sections tt_mesh_components touches: they sit first and depend on T only, so a workspace of
@@ -62,18 +58,13 @@ long long tt_mesh_components_bytes(long long T) {
 static MeshLayout mesh_layout(void* base, long long V, long long T) {
     TtCarver c{(char*)base};
     MeshLayout l;
-    l.n = V > T ? V : T;
-    l.nblk = (l.n + MESH_BLOCK - 1) / MESH_BLOCK;
     const long long nl = V > 3 * T ? V : 3 * T;  // items of a loss reduction: V vertices or E <= 3T edges
-    l.nblk_loss = (nl + MESH_BLOCK - 1) / MESH_BLOCK;
     l.w = mesh_components_ws(c, T);
-    l.w.fkeep = c.take<unsigned char>(T);           // [T] face kept
-    l.w.vmark = c.take<unsigned char>(V);           // [V] vertex referenced by a kept face
-    l.w.local = c.take<int>(l.n);                   // [n] in-block exclusive prefix: vertex | face << 16
-    l.w.bsum = c.take<unsigned>(l.nblk);            // [nblk] block totals, same packing
-    l.w.boff = c.take<unsigned long long>(l.nblk);  // [nblk] block offsets: vertices | faces << 32
-    l.w.part = c.take<float>(l.nblk_loss);          // [nblk_loss] loss partials
-    l.w.w = c.take<float>(3 * V);                   // [3V] Laplacian backward: d loss / d r
+    l.w.fkeep = c.take<unsigned char>(T);  // [T] face kept
+    l.w.vmark = c.take<unsigned char>(V);  // [V] vertex referenced by a kept face
+    l.w.c = tt_compact2_carve(c, V > T ? V : T, base ? l.w.misc + 2 : nullptr);
+    l.w.part = c.take<float>(tt_grid(nl));  // [blocks of nl items] loss partials
+    l.w.w = c.take<float>(3 * V);           // [3V] Laplacian backward: d loss / d r
     l.bytes = c.bytes();
     return l;
 }
@@ -172,41 +163,23 @@ __global__ __launch_bounds__(MESH_BLOCK) void k_cc_mark(const int* __restrict__ 
     for (int k = 0; k < 3; ++k) w.vmark[tri[(size_t)f * 3 + k]] = 1;  // in range: k_cc_keep checked it
 }
 
-__global__ __launch_bounds__(MESH_BLOCK) void k_cc_scan(int V, int T, int n, MeshWs w) {
-    const int i = blockIdx.x * MESH_BLOCK + threadIdx.x;
-    unsigned packed = 0;
-    if (i < n) packed = (i < V ? (unsigned)w.vmark[i] : 0u) | ((i < T ? (unsigned)w.fkeep[i] : 0u) << 16);
-    unsigned total;
-    const unsigned before = tt_block_exclusive_scan<unsigned, MESH_BLOCK>(packed, &total);
-    if (i < n) w.local[i] = (int)before;
-    if (threadIdx.x == 0) w.bsum[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(TT_SCAN_BLOCK) void k_cc_blocks(MeshWs w, int nblk, int* __restrict__ out_totals) {
-    tt_scan_block_totals(w.bsum, nblk, w.boff, w.misc + 2, out_totals);
-}
-
-__device__ __forceinline__ int cc_vertex_id(const MeshWs& w, int v) {
-    return (int)(unsigned)(w.boff[v / MESH_BLOCK] & 0xffffffffull) + (w.local[v] & 0xffff);
-}
-
 __global__ __launch_bounds__(MESH_BLOCK) void k_cc_emit(const float* __restrict__ v_pos, const int* __restrict__ tri,
                                                         int V, int T, MeshWs w, float* __restrict__ v_out,
                                                         int* __restrict__ t_out) {
     const int i = blockIdx.x * MESH_BLOCK + threadIdx.x;
     const int nv = w.misc[2], nt = w.misc[3];  // bound of every write: the totals the scan produced
     if (i < V && w.vmark[i]) {
-        const int o = cc_vertex_id(w, i);
+        const int o = tt_compact2_lo(w.c, i);
         if (o < nv) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) v_out[(size_t)o * 3 + c] = v_pos[(size_t)i * 3 + c];
         }
     }
     if (i < T && w.fkeep[i]) {
-        const int o = (int)(unsigned)(w.boff[i / MESH_BLOCK] >> 32) + (w.local[i] >> 16);
+        const int o = tt_compact2_hi(w.c, i);
         if (o < nt) {
 #pragma unroll
-            for (int k = 0; k < 3; ++k) t_out[(size_t)o * 3 + k] = cc_vertex_id(w, tri[(size_t)i * 3 + k]);
+            for (int k = 0; k < 3; ++k) t_out[(size_t)o * 3 + k] = tt_compact2_lo(w.c, tri[(size_t)i * 3 + k]);
         }
     }
 }
@@ -218,8 +191,7 @@ __global__ __launch_bounds__(MESH_BLOCK) void k_cc_emit(const float* __restrict_
 __device__ __forceinline__ float block_sum(float v) {
     __shared__ float wave_sum[MESH_BLOCK / 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
+    v = tt_wave_sum(v);
     if (lane == 0) wave_sum[wave] = v;
     __syncthreads();
     float t = 0.f;
@@ -360,8 +332,6 @@ __global__ __launch_bounds__(MESH_BLOCK) void k_nc_bwd(const float* __restrict__
 // ---------------------------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------------------------
-static inline unsigned mesh_grid(long long n) { return (unsigned)((n + MESH_BLOCK - 1) / MESH_BLOCK); }
-
 extern "C" int64_t tt_mesh_workspace_bytes(int32_t V, int32_t T) {
     if (V < 0 || T < 0 || V > TT_MESH_MAX_ITEMS || T > TT_MESH_MAX_ITEMS) return TT_ERR_BAD_ARG;
     return mesh_layout(nullptr, V, T).bytes;
@@ -375,12 +345,12 @@ extern "C" int tt_mesh_components(const int32_t* face_pairs, int32_t P, int32_t 
     TtCarver c{(char*)workspace};
     const MeshWs w = mesh_components_ws(c, T);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_uf_init, dim3(mesh_grid(T)), dim3(MESH_BLOCK), 0, s, (int)T, w);
+    hipLaunchKernelGGL(k_uf_init, dim3(tt_grid(T)), dim3(MESH_BLOCK), 0, s, (int)T, w);
     if (P > 0)
-        hipLaunchKernelGGL(k_uf_hook, dim3(mesh_grid(P)), dim3(MESH_BLOCK), 0, s, (const int*)face_pairs, (int)P,
+        hipLaunchKernelGGL(k_uf_hook, dim3(tt_grid(P)), dim3(MESH_BLOCK), 0, s, (const int*)face_pairs, (int)P,
                            (int)T, w);
-    hipLaunchKernelGGL(k_uf_flatten, dim3(mesh_grid(T)), dim3(MESH_BLOCK), 0, s, (int)T, w, (int*)labels);
-    hipLaunchKernelGGL(k_uf_max, dim3(mesh_grid(T)), dim3(MESH_BLOCK), 0, s, (const int*)labels, (int)T, w);
+    hipLaunchKernelGGL(k_uf_flatten, dim3(tt_grid(T)), dim3(MESH_BLOCK), 0, s, (int)T, w, (int*)labels);
+    hipLaunchKernelGGL(k_uf_max, dim3(tt_grid(T)), dim3(MESH_BLOCK), 0, s, (const int*)labels, (int)T, w);
     return tt_check_launch();
 }
 
@@ -391,14 +361,12 @@ extern "C" int tt_mesh_compact_count(const int32_t* t_pos_idx, const int32_t* la
     if (!t_pos_idx || !labels || !workspace || !out_totals) return TT_ERR_BAD_ARG;
     if (frac_mode != 0 && frac_mode != 1) return TT_ERR_BAD_ARG;
     if (frac_mode == 1 && !(frac >= -1e300 && frac <= 1e300)) return TT_ERR_BAD_ARG;  // NaN / inf
-    const MeshLayout l = mesh_layout(workspace, V, T);
-    const MeshWs& w = l.w;
+    const MeshWs w = mesh_layout(workspace, V, T).w;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_cc_keep, dim3(mesh_grid(l.n)), dim3(MESH_BLOCK), 0, s, (const int*)t_pos_idx,
+    hipLaunchKernelGGL(k_cc_keep, dim3((unsigned)w.c.nblk), dim3(MESH_BLOCK), 0, s, (const int*)t_pos_idx,
                        (const int*)labels, (int)V, (int)T, (int)frac_mode, frac, (long long)threshold, w);
-    hipLaunchKernelGGL(k_cc_mark, dim3(mesh_grid(T)), dim3(MESH_BLOCK), 0, s, (const int*)t_pos_idx, (int)T, w);
-    hipLaunchKernelGGL(k_cc_scan, dim3((unsigned)l.nblk), dim3(MESH_BLOCK), 0, s, (int)V, (int)T, (int)l.n, w);
-    hipLaunchKernelGGL(k_cc_blocks, dim3(1), dim3(TT_SCAN_BLOCK), 0, s, w, (int)l.nblk, (int*)out_totals);
+    hipLaunchKernelGGL(k_cc_mark, dim3(tt_grid(T)), dim3(MESH_BLOCK), 0, s, (const int*)t_pos_idx, (int)T, w);
+    tt_compact2_scan_flags(w.vmark, V, w.fkeep, T, w.c, (int*)out_totals, s);
     return tt_check_launch();
 }
 
@@ -406,10 +374,9 @@ extern "C" int tt_mesh_compact_emit(const float* v_pos, const int32_t* t_pos_idx
                                     void* workspace, float* v_out, int32_t* t_out, void* stream) {
     if (V < 0 || T < 1 || V > TT_MESH_MAX_ITEMS || T > TT_MESH_MAX_ITEMS) return TT_ERR_BAD_ARG;
     if (!t_pos_idx || !workspace || !t_out || (V > 0 && (!v_pos || !v_out))) return TT_ERR_BAD_ARG;
-    const MeshLayout l = mesh_layout(workspace, V, T);
-    const MeshWs& w = l.w;
+    const MeshWs w = mesh_layout(workspace, V, T).w;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_cc_emit, dim3((unsigned)l.nblk), dim3(MESH_BLOCK), 0, s, v_pos, (const int*)t_pos_idx,
+    hipLaunchKernelGGL(k_cc_emit, dim3((unsigned)w.c.nblk), dim3(MESH_BLOCK), 0, s, v_pos, (const int*)t_pos_idx,
                        (int)V, (int)T, w, v_out, (int*)t_out);
     return tt_check_launch();
 }
@@ -424,10 +391,9 @@ extern "C" int tt_mesh_laplacian_fwd(const float* v_pos, const int32_t* nbr_ptr,
     if (!mesh_csr_ok(nbr_ptr, V) || T < 0 || T > TT_MESH_MAX_ITEMS || !workspace || !loss)
         return TT_ERR_BAD_ARG;
     if (V > 0 && !v_pos) return TT_ERR_BAD_ARG;
-    const MeshLayout l = mesh_layout(workspace, V, T);
-    const MeshWs& w = l.w;
+    const MeshWs w = mesh_layout(workspace, V, T).w;
     hipStream_t s = (hipStream_t)stream;
-    const unsigned nb = mesh_grid(V);
+    const unsigned nb = tt_grid(V);
     if (nb > 0)
         hipLaunchKernelGGL(k_lap_fwd, dim3(nb), dim3(MESH_BLOCK), 0, s, v_pos, (const int*)nbr_ptr,
                            (const int*)nbr_col, (int)V, w.part);
@@ -442,12 +408,11 @@ extern "C" int tt_mesh_laplacian_bwd(const float* v_pos, const int32_t* nbr_ptr,
         return TT_ERR_BAD_ARG;
     if (V > 0 && (!v_pos || !grad_v)) return TT_ERR_BAD_ARG;
     if (V == 0) return 0;
-    const MeshLayout l = mesh_layout(workspace, V, T);
-    const MeshWs& w = l.w;
+    const MeshWs w = mesh_layout(workspace, V, T).w;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_lap_bwd_w, dim3(mesh_grid(V)), dim3(MESH_BLOCK), 0, s, v_pos, (const int*)nbr_ptr,
+    hipLaunchKernelGGL(k_lap_bwd_w, dim3(tt_grid(V)), dim3(MESH_BLOCK), 0, s, v_pos, (const int*)nbr_ptr,
                        (const int*)nbr_col, (int)V, grad_loss, w.w);
-    hipLaunchKernelGGL(k_lap_bwd_g, dim3(mesh_grid(V)), dim3(MESH_BLOCK), 0, s, (const float*)w.w,
+    hipLaunchKernelGGL(k_lap_bwd_g, dim3(tt_grid(V)), dim3(MESH_BLOCK), 0, s, (const float*)w.w,
                        (const int*)nbr_ptr, (const int*)nbr_col, (int)V, grad_v);
     return tt_check_launch();
 }
@@ -457,10 +422,9 @@ extern "C" int tt_mesh_nc_fwd(const float* v_nrm, const int32_t* edges, int32_t 
     if (V < 0 || T < 0 || E < 0 || V > TT_MESH_MAX_ITEMS || T > TT_MESH_MAX_ITEMS || (int64_t)E > 3 * (int64_t)T)
         return TT_ERR_BAD_ARG;
     if (!workspace || !loss || (E > 0 && (!edges || !v_nrm))) return TT_ERR_BAD_ARG;
-    const MeshLayout l = mesh_layout(workspace, V, T);
-    const MeshWs& w = l.w;
+    const MeshWs w = mesh_layout(workspace, V, T).w;
     hipStream_t s = (hipStream_t)stream;
-    const unsigned nb = mesh_grid(E);
+    const unsigned nb = tt_grid(E);
     if (nb > 0)
         hipLaunchKernelGGL(k_nc_fwd, dim3(nb), dim3(MESH_BLOCK), 0, s, v_nrm, (const int*)edges, (int)V, (int)E,
                            TT_MESH_COS_EPS, w.part);
@@ -475,7 +439,7 @@ extern "C" int tt_mesh_nc_bwd(const float* v_nrm, const int32_t* nbr_ptr, const 
     if (V > 0 && (!v_nrm || !grad_nrm)) return TT_ERR_BAD_ARG;
     if (V == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_nc_bwd, dim3(mesh_grid(V)), dim3(MESH_BLOCK), 0, s, v_nrm, (const int*)nbr_ptr,
+    hipLaunchKernelGGL(k_nc_bwd, dim3(tt_grid(V)), dim3(MESH_BLOCK), 0, s, v_nrm, (const int*)nbr_ptr,
                        (const int*)nbr_col, (int)V, (int)E, TT_MESH_COS_EPS, grad_loss, grad_nrm);
     return tt_check_launch();
 }

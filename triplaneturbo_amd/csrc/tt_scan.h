@@ -1,15 +1,16 @@
-// tt_scan.h -- the only prefix scans of the mesh stages (tt_isosurface.hip, tt_mesh.hip, tt_raster.hip, tt_uv.hip):
+// tt_scan.h -- the only prefix scans and the fixed-order wave sum of the mesh stages (tt_isosurface.hip, tt_mesh.hip,
+// tt_simplify.hip, tt_raster.hip, tt_uv.hip):
 //   wave_inclusive_scan / tt_block_exclusive_scan   the building blocks
-//   tt_scan_block_totals   the second level of the compaction scans: the first level is an in-block scan of two 16-bit
-//                          counters packed in one 32-bit word (the caller's kernel), this one block scans the block
-//                          totals in 64 bits (low half: first counter, high half: second)
-//   tt_exclusive_scan      exclusive scan of an int / long long array in three launches
-// Fixed summation order (lanes, then waves, then blocks, each ascending) and no atomics: identical inputs give
-// bit-identical offsets.
+//   tt_wave_sum            64-lane sum by a fixed shuffle tree
+//   tt_exclusive_scan      exclusive scan of an int / long long array in three launches; the caller owns the input, the
+//                          block-sum scratch (tt_xscan_blocks(n) elements) and the slot of the total
+// The two-counter compaction (both scan levels, its workspace sections, the decoding of its result) is tt_compact.h, on
+// these blocks; its callers own their counts and the slot of the two totals.  Fixed summation order (lanes, then waves,
+// then blocks, each ascending) and no atomics: identical inputs give bit-identical offsets.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#define TT_SCAN_BLOCK 1024
+#define TT_SCAN_BLOCK 1024  // threads of a one-block scan of block totals (tt_compact.h)
 
 template <typename T>
 __device__ __forceinline__ T wave_inclusive_scan(T v, int lane) {
@@ -18,6 +19,14 @@ __device__ __forceinline__ T wave_inclusive_scan(T v, int lane) {
         const T x = __shfl_up(v, d, 64);
         if (lane >= d) v += x;
     }
+    return v;
+}
+
+// sum over the 64 lanes in a fixed order (the result is valid in lane 0)
+template <typename T>
+__device__ __forceinline__ T tt_wave_sum(T v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
     return v;
 }
 
@@ -39,31 +48,6 @@ __device__ __forceinline__ T tt_block_exclusive_scan(T v, T* total) {
     }
     *total = tot;
     return before + incl - v;
-}
-
-// One block of TT_SCAN_BLOCK threads: boff[b] = exclusive prefix of the unpacked block totals bsum[b] (lo | hi << 16
-// -> lo | hi << 32); the grand totals go to tot[0..1] and out_totals[0..1] (lo, hi).
-__device__ __forceinline__ void tt_scan_block_totals(const unsigned* __restrict__ bsum, int nblk,
-                                                     unsigned long long* __restrict__ boff, int* __restrict__ tot,
-                                                     int* __restrict__ out_totals) {
-    unsigned long long carry = 0;
-    for (int base = 0; base < nblk; base += TT_SCAN_BLOCK) {
-        const int b = base + threadIdx.x;
-        const unsigned s = b < nblk ? bsum[b] : 0u;
-        const unsigned long long v = (unsigned long long)(s & 0xffffu) | ((unsigned long long)(s >> 16) << 32);
-        unsigned long long total;
-        const unsigned long long before = tt_block_exclusive_scan<unsigned long long, TT_SCAN_BLOCK>(v, &total);
-        if (b < nblk) boff[b] = carry + before;
-        carry += total;
-        __syncthreads();  // the scan's wave totals are rewritten by the next chunk
-    }
-    if (threadIdx.x == 0) {
-        const int lo = (int)(carry & 0xffffffffull), hi = (int)(carry >> 32);
-        tot[0] = lo;
-        tot[1] = hi;
-        out_totals[0] = lo;
-        out_totals[1] = hi;
-    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------

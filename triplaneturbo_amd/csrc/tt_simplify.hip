@@ -12,35 +12,30 @@
 //   k_simp_faces    63-bit key of every face's rotated rank triple
 //   k_simp_keep     first face of every run of equal sorted keys
 //   k_simp_mark     clusters a kept face references
-//   k_simp_scan / k_simp_blocks   the packed two-counter compaction scan of tt_scan.h (clusters | faces << 16)
+//   k_compact2_flags / k_compact2_blocks   (tt_compact.h) offsets of the marked clusters and kept faces, (V', T')
 //   k_simp_emit     vertices, faces, vertex_map
 // No float atomics; identical inputs give bit-identical outputs.
-#include "tt_host.h"
-#include "tt_scan.h"
+#include "tt_compact.h"
 
-#define SIMP_BLOCK 256
+#define SIMP_BLOCK TT_ITEM_BLOCK
 #define SIMP_WAVES (SIMP_BLOCK / 64)
 #define SIMP_SENTINEL 0x7fffffffffffffffll
 
 struct SimpWs {
     int *excl, *xs, *ckey, *mptr, *pptr, *misc;
     unsigned char *fkeep, *cmark;
-    int* local;
-    unsigned* bsum;
-    unsigned long long* boff;
+    TtCompact2 c;  // items: max(V, T); low counter: marked clusters, high: kept faces; totals in misc[2..3]
 };
 
 struct SimpLayout {
     SimpWs w;
-    long long n, nblk, bytes;  // compaction items and blocks, size of the workspace
+    long long bytes;  // size of the workspace
 };
 
 // the workspace sections (tt_simplify_workspace_bytes); base may be null for the size alone
 static SimpLayout simp_layout(void* base, long long V, long long T) {
     TtCarver c{(char*)base};
     SimpLayout l;
-    l.n = V > T ? V : T;
-    l.nblk = (l.n + SIMP_BLOCK - 1) / SIMP_BLOCK;
     l.w.excl = c.take<int>(V);                      // [V] run starts of the sorted keys, scanned in place
     l.w.xs = c.take<int>(tt_xscan_blocks(V) + 1);   // block sums of both tt_exclusive_scan calls (V, then C <= V items)
     l.w.ckey = c.take<int>(V);                      // [C] cell key of a cluster
@@ -49,9 +44,7 @@ static SimpLayout simp_layout(void* base, long long V, long long T) {
     l.w.misc = c.take<int>(64);                     // [0] C, [2..3] (V', T')
     l.w.fkeep = c.take<unsigned char>(T);           // [T] face kept
     l.w.cmark = c.take<unsigned char>(V);           // [C] cluster referenced by a kept face
-    l.w.local = c.take<int>(l.n);                   // [n] in-block exclusive prefix: cluster | face << 16
-    l.w.bsum = c.take<unsigned>(l.nblk);            // [nblk] block totals, same packing
-    l.w.boff = c.take<unsigned long long>(l.nblk);  // [nblk] block offsets: clusters | faces << 32
+    l.w.c = tt_compact2_carve(c, V > T ? V : T, base ? l.w.misc + 2 : nullptr);
     l.bytes = c.bytes();
     return l;
 }
@@ -154,12 +147,6 @@ __global__ __launch_bounds__(SIMP_BLOCK) void k_simp_pairs(const int* __restrict
 // ---------------------------------------------------------------------------------------------------------------
 // quadrics and placement
 // ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float simp_wave_sum(float v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
-    return v;  // valid in lane 0
-}
-
 __global__ __launch_bounds__(SIMP_BLOCK) void k_simp_solve(const float* __restrict__ v_pos, const int* __restrict__ tri,
                                                            const long long* __restrict__ spkeys,
                                                            const long long* __restrict__ perm, int V, int T, int C,
@@ -218,9 +205,9 @@ __global__ __launch_bounds__(SIMP_BLOCK) void k_simp_solve(const float* __restri
         for (int a = 0; a < 3; ++a) m[a] += v_pos[(size_t)v * 3 + a] - ctr[a];
     }
 #pragma unroll
-    for (int j = 0; j < 10; ++j) q[j] = simp_wave_sum(q[j]);
+    for (int j = 0; j < 10; ++j) q[j] = tt_wave_sum(q[j]);
 #pragma unroll
-    for (int a = 0; a < 3; ++a) m[a] = simp_wave_sum(m[a]);
+    for (int a = 0; a < 3; ++a) m[a] = tt_wave_sum(m[a]);
     if (lane != 0) return;
     const int cnt = me - mb;
     double x[3];
@@ -299,24 +286,6 @@ __global__ __launch_bounds__(SIMP_BLOCK) void k_simp_mark(const int* __restrict_
     for (int k = 0; k < 3; ++k) w.cmark[r[k]] = 1;  // in range: simp_face_ranks checked it
 }
 
-__global__ __launch_bounds__(SIMP_BLOCK) void k_simp_scan(int C, int T, int n, SimpWs w) {
-    const int i = blockIdx.x * SIMP_BLOCK + threadIdx.x;
-    unsigned packed = 0;
-    if (i < n) packed = (i < C ? (unsigned)(w.cmark[i] != 0) : 0u) | ((i < T ? (unsigned)(w.fkeep[i] != 0) : 0u) << 16);
-    unsigned total;
-    const unsigned before = tt_block_exclusive_scan<unsigned, SIMP_BLOCK>(packed, &total);
-    if (i < n) w.local[i] = (int)before;
-    if (threadIdx.x == 0) w.bsum[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(TT_SCAN_BLOCK) void k_simp_blocks(SimpWs w, int nblk, int* __restrict__ out_totals) {
-    tt_scan_block_totals(w.bsum, nblk, w.boff, w.misc + 2, out_totals);
-}
-
-__device__ __forceinline__ int simp_cluster_id(const SimpWs& w, int c) {
-    return (int)(unsigned)(w.boff[c / SIMP_BLOCK] & 0xffffffffull) + (w.local[c] & 0xffff);
-}
-
 __global__ __launch_bounds__(SIMP_BLOCK) void k_simp_emit(const float* __restrict__ cpos, const int* __restrict__ tri,
                                                           const int* __restrict__ rank, int V, int T, int C, SimpWs w,
                                                           float* __restrict__ v_out, int* __restrict__ t_out,
@@ -324,31 +293,29 @@ __global__ __launch_bounds__(SIMP_BLOCK) void k_simp_emit(const float* __restric
     const int i = blockIdx.x * SIMP_BLOCK + threadIdx.x;
     const int nv = w.misc[2], nt = w.misc[3];  // bound of every write: the totals the scan produced
     if (i < C && w.cmark[i]) {
-        const int o = simp_cluster_id(w, i);
+        const int o = tt_compact2_lo(w.c, i);
         if (o < nv) {
 #pragma unroll
             for (int a = 0; a < 3; ++a) v_out[(size_t)o * 3 + a] = cpos[(size_t)i * 3 + a];
         }
     }
     if (i < T && w.fkeep[i]) {
-        const int o = (int)(unsigned)(w.boff[i / SIMP_BLOCK] >> 32) + (w.local[i] >> 16);
+        const int o = tt_compact2_hi(w.c, i);
         int r[3];
         if (o < nt && simp_rotated(tri, rank, V, C, i, r)) {
 #pragma unroll
-            for (int k = 0; k < 3; ++k) t_out[(size_t)o * 3 + k] = simp_cluster_id(w, r[k]);
+            for (int k = 0; k < 3; ++k) t_out[(size_t)o * 3 + k] = tt_compact2_lo(w.c, r[k]);
         }
     }
     if (i < V) {
         const int r = rank[i];
-        vertex_map[i] = ((unsigned)r < (unsigned)C && w.cmark[r]) ? simp_cluster_id(w, r) : -1;
+        vertex_map[i] = ((unsigned)r < (unsigned)C && w.cmark[r]) ? tt_compact2_lo(w.c, r) : -1;
     }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------------------------
-static inline unsigned simp_grid(long long n) { return (unsigned)((n + SIMP_BLOCK - 1) / SIMP_BLOCK); }
-
 static bool simp_sizes_ok(int32_t V, int32_t T) {
     return V >= 1 && T >= 1 && V <= TT_MESH_MAX_ITEMS && T <= TT_MESH_MAX_ITEMS;
 }
@@ -371,7 +338,7 @@ extern "C" int tt_simplify_keys(const float* v_pos, int32_t V, int32_t grid, flo
     if (!simp_finite(lo_x) || !simp_finite(lo_y) || !simp_finite(lo_z) || !simp_finite(inv_h) || !(inv_h > 0.f))
         return TT_ERR_BAD_ARG;
     const SimpBox b{{lo_x, lo_y, lo_z}, 0.f, inv_h, (int)grid};
-    hipLaunchKernelGGL(k_simp_keys, dim3(simp_grid(V)), dim3(SIMP_BLOCK), 0, (hipStream_t)stream, v_pos, (int)V, b,
+    hipLaunchKernelGGL(k_simp_keys, dim3(tt_grid(V)), dim3(SIMP_BLOCK), 0, (hipStream_t)stream, v_pos, (int)V, b,
                        (long long*)keys);
     return tt_check_launch();
 }
@@ -382,10 +349,10 @@ extern "C" int tt_simplify_ranks(const int64_t* sorted_keys, const int64_t* perm
     if (!sorted_keys || !perm || !workspace || !rank || !out_totals) return TT_ERR_BAD_ARG;
     const SimpWs w = simp_layout(workspace, V, T).w;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_simp_starts, dim3(simp_grid(V)), dim3(SIMP_BLOCK), 0, s, (const long long*)sorted_keys,
+    hipLaunchKernelGGL(k_simp_starts, dim3(tt_grid(V)), dim3(SIMP_BLOCK), 0, s, (const long long*)sorted_keys,
                        (int)V, w);
     tt_exclusive_scan<int>(w.excl, V, w.excl, w.xs, w.misc, s);
-    hipLaunchKernelGGL(k_simp_ranks, dim3(simp_grid(V)), dim3(SIMP_BLOCK), 0, s, (const long long*)sorted_keys,
+    hipLaunchKernelGGL(k_simp_ranks, dim3(tt_grid(V)), dim3(SIMP_BLOCK), 0, s, (const long long*)sorted_keys,
                        (const long long*)perm, (int)V, (int)grid, w, (int*)rank, (int*)out_totals);
     return tt_check_launch();
 }
@@ -396,7 +363,7 @@ extern "C" int tt_simplify_pairs(const int32_t* t_pos_idx, const int32_t* rank, 
     if (const int st = simp_clusters_status(V, C)) return st;
     const SimpWs w = simp_layout(workspace, V, T).w;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_simp_pairs, dim3(simp_grid(T)), dim3(SIMP_BLOCK), 0, s, (const int*)t_pos_idx,
+    hipLaunchKernelGGL(k_simp_pairs, dim3(tt_grid(T)), dim3(SIMP_BLOCK), 0, s, (const int*)t_pos_idx,
                        (const int*)rank, (int)V, (int)T, (int)C, w, (long long*)pair_keys);
     tt_exclusive_scan<int>(w.pptr, C, w.pptr, w.xs, w.pptr + C, s);
     return tt_check_launch();
@@ -424,7 +391,7 @@ extern "C" int tt_simplify_faces(const int32_t* t_pos_idx, const int32_t* rank, 
                                  int64_t* face_keys, void* stream) {
     if (!simp_sizes_ok(V, T) || !t_pos_idx || !rank || !face_keys) return TT_ERR_BAD_ARG;
     if (const int st = simp_clusters_status(V, C)) return st;
-    hipLaunchKernelGGL(k_simp_faces, dim3(simp_grid(T)), dim3(SIMP_BLOCK), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(k_simp_faces, dim3(tt_grid(T)), dim3(SIMP_BLOCK), 0, (hipStream_t)stream,
                        (const int*)t_pos_idx, (const int*)rank, (int)V, (int)T, (int)C, (long long*)face_keys);
     return tt_check_launch();
 }
@@ -435,15 +402,13 @@ extern "C" int tt_simplify_emit_count(const int64_t* sorted_face_keys, const int
     if (!simp_sizes_ok(V, T)) return TT_ERR_BAD_ARG;
     if (!sorted_face_keys || !face_perm || !t_pos_idx || !rank || !workspace || !out_totals) return TT_ERR_BAD_ARG;
     if (const int st = simp_clusters_status(V, C)) return st;
-    const SimpLayout l = simp_layout(workspace, V, T);
-    const SimpWs& w = l.w;
+    const SimpWs w = simp_layout(workspace, V, T).w;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_simp_keep, dim3(simp_grid(l.n)), dim3(SIMP_BLOCK), 0, s, (const long long*)sorted_face_keys,
-                       (const long long*)face_perm, (int)T, (int)C, w);
-    hipLaunchKernelGGL(k_simp_mark, dim3(simp_grid(T)), dim3(SIMP_BLOCK), 0, s, (const int*)t_pos_idx,
+    hipLaunchKernelGGL(k_simp_keep, dim3((unsigned)w.c.nblk), dim3(SIMP_BLOCK), 0, s,
+                       (const long long*)sorted_face_keys, (const long long*)face_perm, (int)T, (int)C, w);
+    hipLaunchKernelGGL(k_simp_mark, dim3(tt_grid(T)), dim3(SIMP_BLOCK), 0, s, (const int*)t_pos_idx,
                        (const int*)rank, (int)V, (int)T, (int)C, w);
-    hipLaunchKernelGGL(k_simp_scan, dim3((unsigned)l.nblk), dim3(SIMP_BLOCK), 0, s, (int)C, (int)T, (int)l.n, w);
-    hipLaunchKernelGGL(k_simp_blocks, dim3(1), dim3(TT_SCAN_BLOCK), 0, s, w, (int)l.nblk, (int*)out_totals);
+    tt_compact2_scan_flags(w.cmark, C, w.fkeep, T, w.c, (int*)out_totals, s);
     return tt_check_launch();
 }
 
@@ -453,9 +418,9 @@ extern "C" int tt_simplify_emit(const float* cluster_pos, const int32_t* t_pos_i
     if (!simp_sizes_ok(V, T)) return TT_ERR_BAD_ARG;
     if (!cluster_pos || !t_pos_idx || !rank || !workspace || !v_out || !t_out || !vertex_map) return TT_ERR_BAD_ARG;
     if (const int st = simp_clusters_status(V, C)) return st;
-    const SimpLayout l = simp_layout(workspace, V, T);
-    hipLaunchKernelGGL(k_simp_emit, dim3((unsigned)l.nblk), dim3(SIMP_BLOCK), 0, (hipStream_t)stream, cluster_pos,
-                       (const int*)t_pos_idx, (const int*)rank, (int)V, (int)T, (int)C, l.w, v_out, (int*)t_out,
+    const SimpWs w = simp_layout(workspace, V, T).w;
+    hipLaunchKernelGGL(k_simp_emit, dim3((unsigned)w.c.nblk), dim3(SIMP_BLOCK), 0, (hipStream_t)stream, cluster_pos,
+                       (const int*)t_pos_idx, (const int*)rank, (int)V, (int)T, (int)C, w, v_out, (int*)t_out,
                        (int*)vertex_map);
     return tt_check_launch();
 }

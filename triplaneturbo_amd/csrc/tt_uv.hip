@@ -28,7 +28,7 @@
 #include "tt_raster_cover.h"  // tri_setup / tri_cover / pix_ndc (and fp contract off for this file)
 #include "tt_scan.h"
 
-#define UV_BLOCK 256
+#define UV_BLOCK TT_ITEM_BLOCK
 
 // ---------------------------------------------------------------------------------------------------------------
 // workspace
@@ -74,7 +74,6 @@ static UvWs uv_ws(void* base, long long V, long long T, long long N, long long* 
     return w;
 }
 
-static inline unsigned uv_grid(long long n) { return (unsigned)((n + UV_BLOCK - 1) / UV_BLOCK); }
 
 __global__ void k_copy_total(const int* __restrict__ src, int* __restrict__ dst, int* __restrict__ out) {
     if (threadIdx.x == 0) {
@@ -376,9 +375,7 @@ __global__ __launch_bounds__(UV_BLOCK) void k_ov_flag(const int* __restrict__ t_
 __global__ __launch_bounds__(UV_BLOCK) void k_ov_texels(int n, UvWs w) {
     const int i = blockIdx.x * UV_BLOCK + threadIdx.x;
     const int c = i < n ? w.cnt[min(i, n - 1)] : 0;
-    int k = c > 0 ? 1 : 0;  // a shuffle sum per wave, one integer atomic per wave
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) k += __shfl_down(k, d, 64);
+    const int k = tt_wave_sum(c > 0 ? 1 : 0);  // a shuffle sum per wave, one integer atomic per wave
     if ((threadIdx.x & 63) == 0 && k > 0) atomicAdd(w.tot + 3, k);
 }
 
@@ -468,15 +465,15 @@ extern "C" int tt_uv_labels(const float* v_pos, const int32_t* t_pos_idx, const 
     const UvWs w = uv_ws(workspace, V, T, N);
     hipStream_t s = (hipStream_t)stream;
     const double tau2 = (double)tau * (double)tau;
-    hipLaunchKernelGGL(k_lab_init, dim3(uv_grid(T)), dim3(UV_BLOCK), 0, s, v_pos, (const int*)t_pos_idx, (int)V,
+    hipLaunchKernelGGL(k_lab_init, dim3(tt_grid(T)), dim3(UV_BLOCK), 0, s, v_pos, (const int*)t_pos_idx, (int)V,
                        (int)T, tau2, (int*)labels, w);
     if (P > 0)
-        hipLaunchKernelGGL(k_adj_fill, dim3(uv_grid(P)), dim3(UV_BLOCK), 0, s, (const int*)face_pairs, (int)P, (int)T,
+        hipLaunchKernelGGL(k_adj_fill, dim3(tt_grid(P)), dim3(UV_BLOCK), 0, s, (const int*)face_pairs, (int)P, (int)T,
                            w);
     for (int r = 0; r < rounds; ++r) {  // Jacobi: labels -> lab2 -> labels -> ...
         const int* in = (r & 1) ? (const int*)w.lab2 : (const int*)labels;
         int* out = (r & 1) ? (int*)labels : w.lab2;
-        hipLaunchKernelGGL(k_lab_round, dim3(uv_grid(T)), dim3(UV_BLOCK), 0, s, in, (int)T, w, out);
+        hipLaunchKernelGGL(k_lab_round, dim3(tt_grid(T)), dim3(UV_BLOCK), 0, s, in, (int)T, w, out);
     }
     if (rounds & 1) hipMemcpyAsync(labels, w.lab2, 4 * (size_t)T, hipMemcpyDeviceToDevice, s);
     return tt_check_launch();
@@ -495,17 +492,17 @@ extern "C" int tt_uv_charts(const float* v_pos, const int32_t* t_pos_idx, const 
     }
     const UvWs w = uv_ws(workspace, V, T, N);
     if (P > 0)
-        hipLaunchKernelGGL(k_pair_filter, dim3(uv_grid(P)), dim3(UV_BLOCK), 0, s, (const int*)face_pairs, (int)P,
+        hipLaunchKernelGGL(k_pair_filter, dim3(tt_grid(P)), dim3(UV_BLOCK), 0, s, (const int*)face_pairs, (int)P,
                            (int)T, (const int*)labels, (const unsigned char*)singleton, w);
     const int st = tt_mesh_components(w.pairs, P, T, w.mesh, w.comp, stream);
     if (st != 0) return st;
-    hipLaunchKernelGGL(k_root_flag, dim3(uv_grid(T)), dim3(UV_BLOCK), 0, s, (int)T, w);
+    hipLaunchKernelGGL(k_root_flag, dim3(tt_grid(T)), dim3(UV_BLOCK), 0, s, (int)T, w);
     tt_exclusive_scan<int>(w.flag, T, w.rootid, w.bsum, w.tot + 8, s);
     hipLaunchKernelGGL(k_copy_total, dim3(1), dim3(64), 0, s, (const int*)(w.tot + 8), w.tot, (int*)out_totals);
-    hipLaunchKernelGGL(k_chart_assign, dim3(uv_grid(T)), dim3(UV_BLOCK), 0, s, (int)T, w, (int*)chart);
-    hipLaunchKernelGGL(k_box_reduce, dim3(uv_grid(T)), dim3(UV_BLOCK), 0, s, v_pos, (const int*)t_pos_idx, (int)V,
+    hipLaunchKernelGGL(k_chart_assign, dim3(tt_grid(T)), dim3(UV_BLOCK), 0, s, (int)T, w, (int*)chart);
+    hipLaunchKernelGGL(k_box_reduce, dim3(tt_grid(T)), dim3(UV_BLOCK), 0, s, v_pos, (const int*)t_pos_idx, (int)V,
                        (int)T, (const int*)labels, (const int*)chart, w);
-    hipLaunchKernelGGL(k_box_out, dim3(uv_grid(T)), dim3(UV_BLOCK), 0, s, (int)T, w, chart_box);
+    hipLaunchKernelGGL(k_box_out, dim3(tt_grid(T)), dim3(UV_BLOCK), 0, s, (int)T, w, chart_box);
     return tt_check_launch();
 }
 
@@ -521,12 +518,12 @@ extern "C" int tt_uv_emit_count(const int32_t* t_pos_idx, const int32_t* chart, 
     const UvWs w = uv_ws(workspace, V, T, N);
     hipMemsetAsync(w.vdeg, 0, 4 * ((size_t)V + 1), s);
     hipMemsetAsync(w.vfill, 0, 4 * (size_t)V, s);
-    hipLaunchKernelGGL(k_vc_count, dim3(uv_grid(3ll * T)), dim3(UV_BLOCK), 0, s, (const int*)t_pos_idx, (int)V,
+    hipLaunchKernelGGL(k_vc_count, dim3(tt_grid(3ll * T)), dim3(UV_BLOCK), 0, s, (const int*)t_pos_idx, (int)V,
                        (int)T, w);
     tt_exclusive_scan<int>(w.vdeg, V + 1, w.vptr, w.bsum, w.tot + 9, s);
-    hipLaunchKernelGGL(k_vc_fill, dim3(uv_grid(3ll * T)), dim3(UV_BLOCK), 0, s, (const int*)t_pos_idx, (int)V,
+    hipLaunchKernelGGL(k_vc_fill, dim3(tt_grid(3ll * T)), dim3(UV_BLOCK), 0, s, (const int*)t_pos_idx, (int)V,
                        (int)T, w);
-    hipLaunchKernelGGL(k_rep, dim3(uv_grid(3ll * T)), dim3(UV_BLOCK), 0, s, (const int*)t_pos_idx,
+    hipLaunchKernelGGL(k_rep, dim3(tt_grid(3ll * T)), dim3(UV_BLOCK), 0, s, (const int*)t_pos_idx,
                        (const int*)chart, (int)V, (int)T, w);
     tt_exclusive_scan<int>(w.isrep, 3 * T, w.uvid, w.bsum, w.tot + 10, s);
     hipLaunchKernelGGL(k_copy_total, dim3(1), dim3(64), 0, s, (const int*)(w.tot + 10), w.tot + 1, (int*)out_totals);
@@ -545,7 +542,7 @@ extern "C" int tt_uv_emit(const float* v_pos, const int32_t* t_pos_idx, const in
         return TT_ERR_BAD_ARG;
     const UvWs w = uv_ws(workspace, V, T, N);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_uv_emit, dim3(uv_grid(3ll * T)), dim3(UV_BLOCK), 0, s, v_pos, (const int*)t_pos_idx, (int)V,
+    hipLaunchKernelGGL(k_uv_emit, dim3(tt_grid(3ll * T)), dim3(UV_BLOCK), 0, s, v_pos, (const int*)t_pos_idx, (int)V,
                        (int)T, (const int*)labels, (const int*)chart, chart_box, (const int*)offsets, (int)C, scale,
                        (int)N, (int)padding, w, v_tex, (int*)t_tex_idx);
     return tt_check_launch();
@@ -563,13 +560,13 @@ extern "C" int tt_uv_overlap(const float* v_tex, const int32_t* t_tex_idx, int32
     hipMemsetAsync(w.cnt, 0, 4 * (size_t)n, s);
     hipLaunchKernelGGL(k_ov_zero_tot, dim3(1), dim3(64), 0, s, w);
     if (T > 0) {
-        if (Vt > 0) hipLaunchKernelGGL(k_ov_clip, dim3(uv_grid(Vt)), dim3(UV_BLOCK), 0, s, v_tex, (int)Vt, w);
-        hipLaunchKernelGGL(k_ov_count, dim3(uv_grid(T)), dim3(UV_BLOCK), 0, s, (const int*)t_tex_idx, (int)Vt,
+        if (Vt > 0) hipLaunchKernelGGL(k_ov_clip, dim3(tt_grid(Vt)), dim3(UV_BLOCK), 0, s, v_tex, (int)Vt, w);
+        hipLaunchKernelGGL(k_ov_count, dim3(tt_grid(T)), dim3(UV_BLOCK), 0, s, (const int*)t_tex_idx, (int)Vt,
                            (int)T, (int)N, w);
-        hipLaunchKernelGGL(k_ov_flag, dim3(uv_grid(T)), dim3(UV_BLOCK), 0, s, (const int*)t_tex_idx, (int)Vt,
+        hipLaunchKernelGGL(k_ov_flag, dim3(tt_grid(T)), dim3(UV_BLOCK), 0, s, (const int*)t_tex_idx, (int)Vt,
                            (int)T, (int)N, w, (unsigned char*)flags);
     }
-    hipLaunchKernelGGL(k_ov_texels, dim3(uv_grid(n)), dim3(UV_BLOCK), 0, s, (int)n, w);
+    hipLaunchKernelGGL(k_ov_texels, dim3(tt_grid(n)), dim3(UV_BLOCK), 0, s, (int)n, w);
     hipLaunchKernelGGL(k_ov_totals, dim3(1), dim3(64), 0, s, w, (int*)out_totals);
     return tt_check_launch();
 }
@@ -602,7 +599,7 @@ extern "C" int tt_tex_fill(const float* img, const uint8_t* mask, int32_t H, int
     const int n = H * W;
     const TexFillWs w = tex_fill_ws(workspace, H, W);
     int *a = w.a, *b = w.b;
-    hipLaunchKernelGGL(k_jfa_init, dim3(uv_grid(n)), dim3(UV_BLOCK), 0, s, (const unsigned char*)mask, n, a);
+    hipLaunchKernelGGL(k_jfa_init, dim3(tt_grid(n)), dim3(UV_BLOCK), 0, s, (const unsigned char*)mask, n, a);
     // steps: the largest power of two below max(H, W) down to 1, then the JFA+2 refinement steps 2 and 1
     int step = 1;
     while (2 * step < (H > W ? H : W)) step *= 2;
@@ -611,13 +608,13 @@ extern "C" int tt_tex_fill(const float* img, const uint8_t* mask, int32_t H, int
     steps[ns++] = 2;
     steps[ns++] = 1;
     for (int k = 0; k < ns; ++k) {
-        hipLaunchKernelGGL(k_jfa_step, dim3(uv_grid(n)), dim3(UV_BLOCK), 0, s, (const int*)a, (int)H, (int)W,
+        hipLaunchKernelGGL(k_jfa_step, dim3(tt_grid(n)), dim3(UV_BLOCK), 0, s, (const int*)a, (int)H, (int)W,
                            steps[k], b);
         int* t = a;
         a = b;
         b = t;
     }
-    hipLaunchKernelGGL(k_fill_out, dim3(uv_grid((long long)n * C)), dim3(UV_BLOCK), 0, s, img, (const int*)a, n,
+    hipLaunchKernelGGL(k_fill_out, dim3(tt_grid((long long)n * C)), dim3(UV_BLOCK), 0, s, img, (const int*)a, n,
                        (int)C, out);
     return tt_check_launch();
 }
