@@ -69,6 +69,8 @@
  *                           leaves to external tools.
  *   tt_simplify_*           mesh simplification for export: vertex clustering with quadric-error placement.  The
  *                           reference exports the raw marching-cubes mesh; this step has no counterpart there.
+ *   tt_bake_*               Mesh.v_tng (threestudio/models/mesh.py:162-205) and the tangent-space normal map (map_Bump)
+ *                           the exporter bakes for a simplified mesh from the field's analytic normals.
  */
 #ifndef TT_ABI_H
 #define TT_ABI_H
@@ -854,6 +856,61 @@ int tt_simplify_emit_count(const int64_t* sorted_face_keys, const int64_t* face_
                            void* stream);
 int tt_simplify_emit(const float* cluster_pos, const int32_t* t_pos_idx, const int32_t* rank, int32_t V, int32_t T,
                      int32_t C, void* workspace, float* v_out, int32_t* t_out, int32_t* vertex_map, void* stream);
+
+/* ---- tangents and normal-map baking (tt_bake.hip): Mesh.v_tng (threestudio/models/mesh.py:162-205) and the
+ * exporter's map_Bump ----
+ * A mesh is v_pos (V,3) fp32, t_pos_idx (T,3) int32, its UVs v_tex (Vt,2) fp32, t_tex_idx (T,3) int32 (row f is face f)
+ * and its unit vertex normals v_nrm (V,3).  Corner 3f + k is corner k of face f.  In this file nothing contracts into a
+ * fused multiply-add: every product, quotient and sum is rounded to fp32 on its own, in the order written, and a dot
+ * product is (a_x b_x + a_y b_y) + a_z b_z.
+ *   face tangent  pe_j = p_j - p_0, uve_j = uv_j - uv_0 (j = 1, 2); denom = uve1.x uve2.y - uve1.y uve2.x;
+ *               d = denom > 0 ? max(denom, 1e-6) : min(denom, -1e-6) (the reference's sign test; denom = 0 and NaN
+ *               take the negative branch); tang_f = (pe1 uve2.y - pe2 uve1.y) / d, per component.
+ *   groups      tt_bake_tangents writes one tangent per group: TT_BAKE_GROUP_POS, the V position vertices (a corner
+ *               belongs to t_pos_idx[f,k]; the reference's v_tng), or TT_BAKE_GROUP_TEX, the Vt UV vertices (a corner
+ *               belongs to t_tex_idx[f,k]; tangents that split at chart seams).  The host passes the group -> corner CSR:
+ *               group_ptr (G+1) int32 and group_corner (3T) int32, the corner ids ordered by (group, corner id) -- one
+ *               stable sort of the flattened index array.  A corner whose face has an index outside [0, V) / [0, Vt)
+ *               contributes nothing.
+ *   normal      n of a POS group = v_nrm of that vertex.  n of a TEX group = v_nrm of the position vertex of the group's
+ *               smallest contributing corner id ((0,0,1) for a group without one).
+ *   tangent     s = the sum of tang_f over the group's contributing corners in ascending corner id (a face adds its
+ *               tangent once per corner it has in the group); t = s / sqrt(s.s); r = t - (t.n) n; out = r / sqrt(r.r).
+ *               (The reference divides s by the corner count first, which normalising undoes.)
+ *   degenerate  a group with no contributing corner, with s.s <= 1e-20 or not finite, or with r.r <= 1e-12 or not finite
+ *               (a tangent parallel to the normal) gets perp(n) instead, where the reference yields NaN:
+ *               perp(n) = q / sqrt(q.q), q = e_a - n_a n, a = the first of x, y, z with the smallest |n_a| (q.q >= 2/3
+ *               for a unit n); (1,0,0) if q.q <= 0.25 or is not finite (n not a unit vector).
+ *   project     tt_bake_project, one step of pulling points (M,3) (in place) onto the iso-surface given the field's
+ *               sdf (M) and sdf_grad (M,3) there: gg = g.g; a = min(max(sdf / max(gg, 1e-12), -1), 1);
+ *               len = |a| sqrt(gg); c = len > max_step ? a (max_step / len) : a; p_k -= c g_k.  So a step is the Newton
+ *               step -sdf g / |g|^2, its factor clamped to [-1, 1] and its length limited to max_step (>= 0, finite).
+ *               A point whose sdf or gradient (|sdf| + g.g) is not finite stays; so does point i when mask (M) uint8,
+ *               which may be NULL, has mask[i] = 0 (an uncovered texel).
+ *   encode      tt_bake_encode, per texel p of rast (H,W,4) = (u, v, z/w, face + 1) of the UV-space rasterisation
+ *               (the rasterizer's layout above): a texel whose id is not in [1, T], or whose face has an index outside
+ *               its range, is uncovered and gets (0.5, 0.5, 1).  Else, with interpolate's weights, x = (u x_0 + v x_1) +
+ *               (1 - u - v) x_2: n from v_nrm through t_pos_idx, t from tng_tex (Vt,3) through t_tex_idx;
+ *               n^ = unit(n) ((0,0,1) where n.n <= 1e-20); t^ = unit(t - (t.n^) n^) (perp(n^) where that is <= 1e-20);
+ *               b^ = t^ x n^; m^ = unit(field_nrm[p]) (n^ where it is <= 1e-20 or not finite: a flat texel);
+ *               out[p] = 0.5 + 0.5 (m^.t^, m^.b^, m^.n^).  b^ = t^ x n^ is the direction of increasing OBJ v (green
+ *               up, the OpenGL convention): the atlas gives every UV triangle positive area in (u, v), so dP/dv is
+ *               parallel to n^ x t^, and the OBJ writer flips v.  out_counts (2 int32, DEVICE memory) = (covered texels,
+ *               covered texels with m^.n^ <= 0: the field normal points into the face; stored as computed).
+ * Determinism: gathers in a fixed order and integer atomics only; identical inputs give bit-identical outputs.  No
+ * workspace, no host round trip.  Every entry point validates its arguments before any HIP call (TT_ERR_BAD_ARG); G, M
+ * or H W = 0 does nothing (tt_bake_encode still zeroes out_counts). */
+#define TT_BAKE_GROUP_POS 0
+#define TT_BAKE_GROUP_TEX 1
+#define TT_BAKE_MAX_POINTS 268435456
+int tt_bake_tangents(const float* v_pos, const int32_t* t_pos_idx, const float* v_tex, const int32_t* t_tex_idx,
+                     const float* v_nrm, const int32_t* group_ptr, const int32_t* group_corner, int32_t V, int32_t Vt,
+                     int32_t T, int32_t group, float* out, void* stream);
+int tt_bake_project(float* points, const float* sdf, const float* sdf_grad, const uint8_t* mask, int64_t M,
+                    float max_step, void* stream);
+int tt_bake_encode(const float* rast, const float* v_nrm, const int32_t* t_pos_idx, const float* tng_tex,
+                   const int32_t* t_tex_idx, const float* field_nrm, int32_t V, int32_t Vt, int32_t T, int32_t H,
+                   int32_t W, float* out, int32_t* out_counts, void* stream);
 
 #ifdef __cplusplus
 }

@@ -102,6 +102,12 @@ class MultipromptMeshExporter(Exporter):
         # set the exported mesh is the simplified mesh[0]; with both None it is the isosurface mesh untouched.
         self.simplify_grid: Optional[int] = None
         self.simplify_target_faces: Optional[int] = None
+        # the tangent-space normal map of the exported mesh (map_Bump, ops.bake_normal_map) on the obj-mtl path with
+        # save_texture, and the number of projection steps it takes towards the iso-surface; attributes for the same
+        # reason.  Unset, params are exactly what they are without the bake.
+        self.bake_normal_map: bool = False
+        self.bake_project_steps: int = 2
+        self.bake_info: Optional[Dict[str, Any]] = None  # ops.bake_normal_map's info of the last bake
 
     @torch.no_grad()
     def __call__(self, space_cache) -> List[ExporterOutput]:
@@ -130,6 +136,18 @@ class MultipromptMeshExporter(Exporter):
 
     def _unwrap(self, mesh) -> None:
         mesh.unwrap_uv(self.cfg.xatlas_chart_options, self.cfg.xatlas_pack_options, texture_size=self.cfg.texture_size)
+
+    def _bake_max_step(self, mesh) -> float:
+        """The longest projection step: the cell of a simplified mesh, else one cell of the isosurface grid."""
+        simp = mesh.extras.get("simplify")
+        if simp is not None:
+            return float(simp["cell"])
+        renderer = getattr(getattr(self.geometry, "isosurface", None), "__self__", None)
+        res = getattr(getattr(renderer, "cfg", None), "isosurface_resolution", None)
+        if res is None:
+            raise RuntimeError("bake_normal_map: the isosurface resolution is unknown (geometry.isosurface is not a "
+                               "mesh renderer's); simplify the mesh or call ops.bake_normal_map with max_step")
+        return 2.0 * float(self.geometry.cfg.radius) / float(res)
 
     def export_obj_with_mtl(self, mesh, space_cache) -> List[ExporterOutput]:
         params = self._params(mesh, True)
@@ -161,6 +179,14 @@ class MultipromptMeshExporter(Exporter):
                 params["map_Pr"] = uv_padding(mat_out["roughness"])
             if "bump" in mat_out:
                 params["map_Bump"] = uv_padding(mat_out["bump"])
+            if self.bake_normal_map:
+                def field(p: Tensor):
+                    out = self.geometry.forward(p[None], space_cache, output_normal=True)
+                    return out["sdf"], out["sdf_grad"]
+
+                bump, self.bake_info = ops.bake_normal_map(mesh, field, N, project_steps=self.bake_project_steps,
+                                                           max_step=self._bake_max_step(mesh), rast=rast)
+                params["map_Bump"] = uv_padding(bump)
         return [ExporterOutput(save_name=f"{self.cfg.save_name}.obj", save_type="obj", params=params)]
 
     def export_obj(self, mesh, space_cache) -> List[ExporterOutput]:

@@ -9,7 +9,8 @@ include/tt_abi.h) instead of the CUDA-only `diso.DiffMC`.
 
 Same signatures and behaviour as the reference; Mesh keeps what these functions and their users touch plus the
 training system's regularisers and outlier removal, and threestudio's UV unwrap (`unwrap_uv`, lazy `v_tex` /
-`t_tex_idx`) on the HIP axis-projection atlas (ops.uv_atlas) instead of xatlas.  No tangents.  File output (OBJ + MTL +
+`t_tex_idx`) on the HIP axis-projection atlas (ops.uv_atlas) instead of xatlas, and its tangents (`v_tng`, and `v_tng_tex`
+per UV vertex; ops.mesh_tangents).  File output (OBJ + MTL +
 texture) is triplaneturbo_amd.export: `multiprompt-mesh-exporter` and `save_obj`."""
 from __future__ import annotations
 
@@ -51,6 +52,15 @@ def prompt_slice(space_cache: Any, i: int) -> Any:
     return {k: [w[i:i + 1] for w in v] for k, v in space_cache.items()}
 
 
+def obj_uv(v_tex: Tensor) -> Tensor:
+    """The UVs an OBJ file carries for v_tex (N,2) fp32, back in the internal orientation: (u, 1 - (1 - v)) with both
+    subtractions rounded to fp32.  save_obj writes `vt u (1 - v)` with 1 - v in fp32, which costs a v below 0.5 up to
+    2^-25; viewer.load_obj undoes the flip, so its v_tex is exactly obj_uv(the exporter's v_tex), and obj_uv is
+    idempotent (one of the two subtractions is always exact).  Mesh.v_tng_tex is built on these."""
+    v = v_tex.detach()
+    return torch.stack([v[:, 0], 1.0 - (1.0 - v[:, 1])], dim=1)
+
+
 class Mesh:
     """The part of threestudio's Mesh (threestudio/models/mesh.py; triplaneturbo_executable/utils/mesh.py is its
     subset) that mesh extraction, colouring, the mesh renderer and the training system use: positions, int32
@@ -64,6 +74,8 @@ class Mesh:
         self._v_rgb: Optional[Tensor] = None
         self._v_tex: Optional[Tensor] = None
         self._t_tex_idx: Optional[Tensor] = None
+        self._v_tng: Optional[Tensor] = None
+        self._v_tng_tex: Optional[Tensor] = None
         self.uv_info: Optional[Dict[str, Any]] = None  # ops.uv_atlas's info of the last unwrap
         self.extras: Dict[str, Any] = {}
         for k, v in kwargs.items():
@@ -96,6 +108,32 @@ class Mesh:
             self._v_tex, self._t_tex_idx = self._unwrap_uv()
         return self._t_tex_idx
 
+    @property
+    def v_tng(self) -> Tensor:
+        """(V,3) unit tangents per position vertex, perpendicular to v_nrm (mesh.py:162-205; ops.mesh_tangents,
+        group "pos"); unwraps the UVs on first use, as v_tex does.  Computed from detached positions, UVs and normals:
+        it never requires grad.  Where the reference yields NaN (an unreferenced vertex, a tangent parallel to the
+        normal) it holds a fixed unit vector perpendicular to the normal."""
+        if self._v_tng is None:
+            self._v_tng = ops.mesh_tangents(self.v_pos, self.t_pos_idx, self.v_tex, self.t_tex_idx, self.v_nrm, "pos")
+        return self._v_tng
+
+    @property
+    def v_tng_tex(self) -> Tensor:
+        """(Vt,3) unit tangents per UV vertex (ops.mesh_tangents, group "tex"): the corners of one UV vertex only, so
+        tangents split at chart seams, perpendicular to v_nrm of the UV vertex's position vertex.  What the normal-map
+        bake and the viewer interpolate through t_tex_idx.  Detached like v_tng: it never requires grad.
+
+        Built on obj_uv(v_tex), the UVs as an OBJ file carries them, not on v_tex itself: the frame a normal map is
+        encoded in has to be the one a reader of the files rebuilds.  A simplified mesh has UV triangles well under a
+        texel wide, whose tangents amplify the 2^-25 that the file's `1 - v` costs by 1 / (UV edge length), to 2e-5 of
+        tangent at a 256^2 atlas; with obj_uv the exported mesh and the loaded one feed the kernel the same numbers
+        (up to v_nrm, whose scatter_add may differ by an ulp from run to run)."""
+        if self._v_tng_tex is None:
+            self._v_tng_tex = ops.mesh_tangents(self.v_pos, self.t_pos_idx, obj_uv(self.v_tex), self.t_tex_idx,
+                                                self.v_nrm, "tex")
+        return self._v_tng_tex
+
     def _unwrap_uv(self, xatlas_chart_options: Optional[dict] = None, xatlas_pack_options: Optional[dict] = None,
                    texture_size: Optional[int] = None) -> Tuple[Tensor, Tensor]:
         """mesh.py:207-242 on the HIP axis-projection atlas (ops.uv_atlas, include/tt_abi.h "UV atlas and texture
@@ -118,6 +156,7 @@ class Mesh:
                   texture_size: Optional[int] = None) -> None:
         """mesh.py:244-249; `texture_size` (the exporter's) sizes the atlas unless the pack options name a resolution."""
         self._v_tex, self._t_tex_idx = self._unwrap_uv(xatlas_chart_options, xatlas_pack_options, texture_size)
+        self._v_tng = self._v_tng_tex = None  # tangents belong to the UVs they were built from
 
     @property
     def requires_grad(self) -> bool:

@@ -1290,3 +1290,183 @@ def mesh_simplify(v_pos: Tensor, t_pos_idx: Tensor, grid: int, lam: float = SIMP
     if n_tri > 0:
         _launch("tt_simplify_emit", cpos, tri, rank, V, T, C, ws, v_out, t_out, vertex_map, label="simplify_emit")
     return v_out, t_out, {"grid": grid, "cell": h, "n_clusters": C, "vertex_map": vertex_map, "unchanged": False}
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# tangents and normal-map baking (include/tt_abi.h, "tangents and normal-map baking")
+_BAKE_GROUPS = {"pos": _lib.TT_BAKE_GROUP_POS, "tex": _lib.TT_BAKE_GROUP_TEX}
+
+
+def _chk_faces(t: Tensor, name: str, T: Optional[int], dev) -> Tensor:
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != 3 or t.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"{name} must be a (T,3) int32 / int64 tensor")
+    if not t.is_cuda or t.device != dev:
+        raise RuntimeError(f"{name} must live on the GPU of v_pos")
+    if T is not None and t.shape[0] != T:
+        raise ValueError(f"{name} has {t.shape[0]} faces, t_pos_idx has {T}")
+    return t
+
+
+@torch.no_grad()
+def mesh_tangents(v_pos: Tensor, t_pos_idx: Tensor, v_tex: Tensor, t_tex_idx: Tensor, v_nrm: Tensor,
+                  group: str = "pos") -> Tensor:
+    """Unit tangents of a UV-mapped mesh, perpendicular to the normals (tt_bake_tangents): the reference's per-face
+    tangent (threestudio/models/mesh.py:162-205) summed over the corners of a group, normalised and Gram-Schmidt
+    against the group's normal.  group="pos": one per position vertex, (V,3), the reference's Mesh.v_tng;
+    group="tex": one per UV vertex, (Vt,3), with the normal of the UV vertex's position vertex -- tangents that split at
+    chart seams, what the normal-map bake and the viewer use.  A group without a usable tangent (no corner, a zero sum,
+    a tangent parallel to the normal) gets a fixed unit vector perpendicular to its normal where the reference yields
+    NaN.  The group -> corner CSR is one stable sort here; each group's corners are added in ascending corner id, so the
+    result is bit-identical from call to call.  Inputs are detached; the result never requires grad."""
+    if group not in _BAKE_GROUPS:
+        raise ValueError(f"group must be 'pos' or 'tex', got {group!r}")
+    v_pos = _chk(v_pos.detach(), "v_pos")
+    if v_pos.dim() != 2 or v_pos.shape[1] != 3:
+        raise ValueError(f"v_pos must be (V,3), got {tuple(v_pos.shape)}")
+    V, dev = v_pos.shape[0], v_pos.device
+    v_nrm = _chk(v_nrm.detach(), "v_nrm", (V, 3))
+    v_tex = _chk(v_tex.detach(), "v_tex")
+    if v_tex.dim() != 2 or v_tex.shape[1] != 2:
+        raise ValueError(f"v_tex must be (Vt,2), got {tuple(v_tex.shape)}")
+    Vt = v_tex.shape[0]
+    t_pos_idx = _chk_faces(t_pos_idx, "t_pos_idx", None, dev)
+    T = t_pos_idx.shape[0]
+    t_tex_idx = _chk_faces(t_tex_idx, "t_tex_idx", T, dev)
+    lim = 1 << 28  # TT_MESH_MAX_ITEMS
+    if max(V, Vt, T) > lim:
+        raise ValueError(f"mesh too large for tt_bake_tangents: V={V}, Vt={Vt}, T={T} (limit {lim})")
+    G = Vt if group == "tex" else V
+    out = torch.empty((G, 3), device=dev, dtype=torch.float32)
+    if G == 0:
+        return out
+    if T > 0:
+        rng = torch.stack(t_pos_idx.aminmax() + t_tex_idx.aminmax()).tolist()  # one read-back
+        if rng[0] < 0 or rng[1] >= V:
+            raise ValueError(f"t_pos_idx holds an index outside [0, {V})")
+        if rng[2] < 0 or rng[3] >= Vt:
+            raise ValueError(f"t_tex_idx holds an index outside [0, {Vt})")
+    key = (t_tex_idx if group == "tex" else t_pos_idx).reshape(-1).long()
+    corner = torch.sort(key, stable=True)[1].int().contiguous()  # corner ids 3f + k by (group, corner id)
+    ptr = torch.zeros(G + 1, device=dev, dtype=torch.int64)
+    ptr[1:] = torch.cumsum(torch.bincount(key, minlength=G), 0)
+    _launch("tt_bake_tangents", v_pos, t_pos_idx.int().contiguous(), v_tex, t_tex_idx.int().contiguous(), v_nrm,
+            ptr.int().contiguous(), corner, V, Vt, T, _BAKE_GROUPS[group], out, label="bake_tangents")
+    return out
+
+
+@torch.no_grad()
+def bake_project_step(points: Tensor, sdf: Tensor, sdf_grad: Tensor, max_step: float,
+                      mask: Optional[Tensor] = None) -> Tensor:
+    """One bounded Newton step of `points` (M,3) towards the iso-surface, in place (tt_bake_project): p -= c g with
+    c = clamp(sdf / max(|g|^2, 1e-12), -1, 1), scaled down so that the step is no longer than max_step.  sdf (M) or
+    (M,1) and sdf_grad (M,3) are the field's values at the points; a point with mask (M) == 0 stays.  Returns points."""
+    points = _chk(points, "points")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"points must be (M,3), got {tuple(points.shape)}")
+    M = points.shape[0]
+    sdf = _chk(sdf.detach().reshape(-1), "sdf", (M,))
+    sdf_grad = _chk(sdf_grad.detach().reshape(-1, 3), "sdf_grad", (M, 3))
+    max_step = float(max_step)
+    if not 0.0 <= max_step <= 3.0e38:
+        raise ValueError(f"max_step must be a finite number >= 0, got {max_step}")
+    m = None
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or not mask.is_cuda or mask.numel() != M:
+            raise ValueError(f"mask must be a GPU tensor of {M} elements")
+        m = (mask.reshape(-1) != 0).to(torch.uint8).contiguous()
+    _launch("tt_bake_project", points, sdf, sdf_grad, m, M, max_step, label="bake_project")
+    return points
+
+
+@torch.no_grad()
+def bake_encode(rast: Tensor, v_nrm: Tensor, t_pos_idx: Tensor, tng_tex: Tensor, t_tex_idx: Tensor,
+                field_nrm: Tensor) -> Tuple[Tensor, Tensor]:
+    """The tangent-space normal map of one UV-space rasterisation (tt_bake_encode): per covered texel of rast (H,W,4)
+    the field normal field_nrm (H,W,3) (any length; normalised inside) in the frame (t^, b^ = t^ x n^, n^) interpolated
+    from tng_tex (Vt,3) and v_nrm (V,3), as 0.5 + 0.5 x; uncovered texels are (0.5, 0.5, 1).  Returns (map (H,W,3),
+    counts (2,) int32 on the device = covered texels, covered texels whose field normal points into the face)."""
+    rast = _chk(rast, "rast")
+    if rast.dim() != 3 or rast.shape[2] != 4:
+        raise ValueError(f"rast must be (H,W,4), got {tuple(rast.shape)}")
+    H, W = rast.shape[:2]
+    v_nrm = _chk(v_nrm.detach(), "v_nrm")
+    tng_tex = _chk(tng_tex.detach(), "tng_tex")
+    if v_nrm.dim() != 2 or v_nrm.shape[1] != 3 or tng_tex.dim() != 2 or tng_tex.shape[1] != 3:
+        raise ValueError("v_nrm must be (V,3) and tng_tex (Vt,3)")
+    field_nrm = _chk(field_nrm.detach(), "field_nrm", (H, W, 3))
+    t_pos_idx = _chk_faces(t_pos_idx, "t_pos_idx", None, rast.device)
+    T = t_pos_idx.shape[0]
+    t_tex_idx = _chk_faces(t_tex_idx, "t_tex_idx", T, rast.device)
+    out = torch.empty((H, W, 3), device=rast.device, dtype=torch.float32)
+    counts = torch.empty(2, device=rast.device, dtype=torch.int32)
+    _launch("tt_bake_encode", rast, v_nrm, t_pos_idx.int().contiguous(), tng_tex, t_tex_idx.int().contiguous(),
+            field_nrm, v_nrm.shape[0], tng_tex.shape[0], T, H, W, out, counts, label="bake_encode")
+    return out, counts
+
+
+def uv_rasterize(v_tex: Tensor, t_tex_idx: Tensor, texture_size: int) -> Tensor:
+    """rast (N,N,4) of the UV triangles over the N^2 texel centres, exactly as the exporter rasterises them: clip
+    position (2u - 1, 2v - 1, 0, 1)."""
+    from . import raster  # (raster imports this module)
+    uv_clip = v_tex * 2.0 - 1.0
+    uv_clip4 = torch.cat((uv_clip, torch.zeros_like(uv_clip[..., 0:1]), torch.ones_like(uv_clip[..., 0:1])), dim=-1)
+    N = int(texture_size)
+    return raster.rasterize(uv_clip4[None].float(), t_tex_idx.int(), (N, N))[0]
+
+
+@torch.no_grad()
+def bake_normal_map(mesh, normal_fn, texture_size: int, project_steps: int = 2, max_step: Optional[float] = None,
+                    rast: Optional[Tensor] = None) -> Tuple[Tensor, dict]:
+    """Tangent-space normal map (N,N,3) fp32 in [0,1] of `mesh` (a Mesh with UVs) from an analytic field:
+    normal_fn(points (M,3)) -> (sdf (M,1), sdf_grad (M,3)).  Per covered texel of the UV rasterisation `rast` (N,N,4)
+    (computed as the exporter does when None): the surface point interpolated from v_pos is pulled onto the field's
+    iso-surface by `project_steps` bounded Newton steps (tt_bake_project, each at most max_step long: a texel of a
+    simplified mesh lies up to sqrt(3) cells off the surface), the field's gradient there is normalised and written in
+    the frame (t^, b^ = t^ x n^, n^) interpolated from mesh.v_tng_tex and mesh.v_nrm (tt_bake_encode; green = increasing
+    OBJ v).  Uncovered texels are (0.5, 0.5, 1): fill them with texture_fill.  Only covered texels are queried
+    (project_steps + 1 queries).  max_step defaults to extras["simplify"]["cell"] of a simplified mesh and must be given
+    otherwise.  info = {n_covered, n_backfacing (field normal pointing into the face; stored as computed),
+    mean_abs_sdf_before, mean_abs_sdf_after (|sdf| at the queried points before / after the projection), points (M,3):
+    the projected points, texel (M,) int64: their flat texel ids, sdf_grad (M,3): the gradient the map encodes}.
+    Nothing here is differentiable."""
+    from . import raster  # (raster imports this module)
+    N, steps = int(texture_size), int(project_steps)
+    if steps < 0:
+        raise ValueError(f"project_steps must be >= 0, got {project_steps}")
+    if max_step is None:
+        simp = mesh.extras.get("simplify") if hasattr(mesh, "extras") else None
+        if simp is None:
+            raise ValueError("max_step must be given for a mesh that was not simplified (no extras['simplify'])")
+        max_step = float(simp["cell"])
+    if rast is None:
+        rast = uv_rasterize(mesh.v_tex, mesh.t_tex_idx, N)
+    rast = _chk(rast, "rast", (N, N, 4))
+    T = mesh.t_pos_idx.shape[0]
+    tid = rast[..., 3].reshape(-1)
+    texel = torch.nonzero((tid >= 1) & (tid <= T)).reshape(-1)
+    pos = raster.interpolate(mesh.v_pos.detach().float()[None], rast[None], mesh.t_pos_idx.int())[0].reshape(-1, 3)
+    pts = pos[texel].contiguous()
+    M = pts.shape[0]
+
+    def query(p):
+        sdf, grad = normal_fn(p)
+        return sdf.detach().float().reshape(-1), grad.detach().float().reshape(-1, 3)
+
+    field = torch.zeros((N * N, 3), device=rast.device, dtype=torch.float32)
+    before = after = 0.0
+    grad = torch.zeros((0, 3), device=rast.device)
+    if M > 0:
+        sdf, grad = query(pts)
+        before_t = sdf.abs().mean()
+        for k in range(steps):
+            if k > 0:
+                sdf, grad = query(pts)
+            bake_project_step(pts, sdf, grad, max_step)
+        if steps > 0:
+            sdf, grad = query(pts)
+        before, after = (float(x) for x in torch.stack([before_t, sdf.abs().mean()]).cpu())
+        field[texel] = grad
+    out, counts = bake_encode(rast, mesh.v_nrm, mesh.t_pos_idx, mesh.v_tng_tex, mesh.t_tex_idx, field.reshape(N, N, 3))
+    n_cov, n_back = (int(x) for x in counts.cpu())
+    return out, {"n_covered": n_cov, "n_backfacing": n_back, "mean_abs_sdf_before": before, "mean_abs_sdf_after": after,
+                 "points": pts, "texel": texel, "sdf_grad": grad}

@@ -6,8 +6,11 @@ few azimuths for CLIPScore, with CUDA-only tools).
     mesh, map_Kd = load_obj("model.obj", device="cuda")
     imgs = turntable(mesh, map_Kd, n_views=4, height=512, width=512, ssaa=2)      # (4,512,512,3) in [0,1]
 
-    python -m triplaneturbo_amd.viewer model.obj --out views [--num_views 4] [--normal] [--size 512] [--ssaa 2]
-    # views/rgb_0.png ... (and normal_0.png ... with --normal)
+    map_Bump = load_normal_map("model.obj", device="cuda")                        # the MTL's map_Bump, or None
+    imgs = turntable(mesh, map_Kd, mode="normal_map", map_Bump=map_Bump)          # the detail normals, (n + 1) / 2
+
+    python -m triplaneturbo_amd.viewer model.obj --out views [--num_views 4] [--normal] [--bump] [--size 512] [--ssaa 2]
+    # views/rgb_0.png ... (normal_0.png ... with --normal, bump_0.png ... with --bump when the MTL names a normal map)
 
 Torch plumbing between kernels, like mesh_renderer.py: rasterize, interpolate, texture and antialias are
 triplaneturbo_amd.raster.  The sampler has no mipmaps (tt_abi.h "texture sampling"): a texture that is minified on
@@ -42,14 +45,37 @@ def _read_image(path: str) -> np.ndarray:
     return np.asarray(Image.open(path).convert("RGB"))
 
 
-def _map_kd_path(mtl_path: str) -> Optional[str]:
+def _map_path(mtl_path: str, key: str = "map_Kd") -> Optional[str]:
     if not os.path.exists(mtl_path):
         return None
     for line in open(mtl_path):
         tok = line.split(None, 1)
-        if len(tok) == 2 and tok[0] == "map_Kd":
+        if len(tok) == 2 and tok[0] == key:
             return os.path.join(os.path.dirname(mtl_path), tok[1].strip())
     return None
+
+
+def _image_tensor(path: str, device) -> Tensor:
+    img = _read_image(path)
+    if img.ndim == 2:
+        img = img[..., None]
+    if img.shape[-1] < 3:
+        img = np.repeat(img[..., :1], 3, axis=-1)
+    return (torch.from_numpy(np.ascontiguousarray(img[..., :3])).to(torch.float32) / 255.0).to(device=device)
+
+
+def load_normal_map(obj_path: str, device=None) -> Optional[Tensor]:
+    """The tangent-space normal map an exported OBJ's MTL names (`map_Bump`, export.save_obj's texture_nrm.<fmt>) as
+    float (N,N,3) in [0,1] (uint8 / 255), None when the OBJ has no MTL or the MTL no map_Bump.  Row 0 is v = 0 of
+    load_obj's v_tex, like map_Kd."""
+    mtllib = None
+    with open(obj_path) as fh:
+        for line in fh:
+            if line.startswith("mtllib"):
+                mtllib = line.split(None, 1)[1].strip()
+                break
+    path = _map_path(os.path.join(os.path.dirname(obj_path), mtllib), "map_Bump") if mtllib else None
+    return _image_tensor(path, device) if path is not None else None
 
 
 def load_obj(path: str, device=None) -> Tuple[Mesh, Optional[Tensor]]:
@@ -95,14 +121,9 @@ def load_obj(path: str, device=None) -> Tuple[Mesh, Optional[Tensor]]:
     if f_tex:
         mesh._v_tex, mesh._t_tex_idx = tensor(vt, torch.float32, 2), tensor(f_tex, torch.int32, 3)
     map_kd = None
-    kd_path = _map_kd_path(os.path.join(os.path.dirname(path), mtllib)) if mtllib else None
+    kd_path = _map_path(os.path.join(os.path.dirname(path), mtllib), "map_Kd") if mtllib else None
     if kd_path is not None:
-        img = _read_image(kd_path)
-        if img.ndim == 2:
-            img = img[..., None]
-        if img.shape[-1] < 3:
-            img = np.repeat(img[..., :1], 3, axis=-1)
-        map_kd = (torch.from_numpy(np.ascontiguousarray(img[..., :3])).to(torch.float32) / 255.0).to(device=device)
+        map_kd = _image_tensor(kd_path, device)
     return mesh, map_kd
 
 
@@ -119,16 +140,40 @@ def get_projection_matrix(fovy_deg: float, aspect_wh: float, near: float = 0.1, 
     return proj
 
 
+def world_normal_from_map(mesh: Mesh, rast: Tensor, map_Bump: Tensor, filter_mode: str = "linear",
+                          ctx: Optional[RasterizerContext] = None) -> Tensor:
+    """(B,H,W,3) unit world normals at the pixels of rast (B,H,W,4) (any rasterisation of the mesh's faces: a camera
+    view, or the UV-space one the map was baked on), rebuilt from the tangent-space normal map map_Bump (TH,TW,3):
+    x = 2 map - 1 sampled at the interpolated v_tex (boundary "clamp"), n = normalize(x_0 t^ + x_1 b^ + x_2 n^) in the
+    frame n^ = normalize(interpolated v_nrm), t^ = normalize(t - (t . n^) n^) with t the interpolated v_tng_tex,
+    b^ = t^ x n^ -- the frame tt_bake_encode writes the map in (include/tt_abi.h, "tangents and normal-map baking").
+    Empty pixels hold zeros.  Composed from the differentiable interpolate / texture ops and torch arithmetic."""
+    ctx = ctx or RasterizerContext("cuda", mesh.v_pos.device)
+    uv, _ = ctx.interpolate(mesh.v_tex[None], rast, mesh.t_tex_idx)
+    n_hat = F.normalize(ctx.interpolate(mesh.v_nrm[None], rast, mesh.t_pos_idx.int())[0], dim=-1)
+    tng, _ = ctx.interpolate(mesh.v_tng_tex[None], rast, mesh.t_tex_idx)
+    t_hat = F.normalize(tng - (tng * n_hat).sum(-1, keepdim=True) * n_hat, dim=-1)
+    b_hat = torch.cross(t_hat, n_hat, dim=-1)
+    x = ctx.texture(map_Bump[None], uv, filter_mode=filter_mode, boundary_mode="clamp") * 2.0 - 1.0
+    return F.normalize(x[..., 0:1] * t_hat + x[..., 1:2] * b_hat + x[..., 2:3] * n_hat, dim=-1)
+
+
 def render_textured(mesh: Mesh, map_Kd: Optional[Tensor], mvp_mtx: Tensor, height: int, width: int, mode: str = "rgb",
                     ssaa: int = 1, background: float = 1.0, filter_mode: str = "linear", antialias: bool = True,
-                    ctx: Optional[RasterizerContext] = None) -> Tensor:
+                    ctx: Optional[RasterizerContext] = None, map_Bump: Optional[Tensor] = None,
+                    light_dir: Optional[Tensor] = None) -> Tensor:
     """(B,height,width,3) views of `mesh` under mvp_mtx (B,4,4).  mode "rgb": map_Kd (TH,TW,3) sampled at the
-    interpolated v_tex (boundary "clamp"), or the interpolated v_rgb when the mesh has no UVs; mode "normal":
-    (normalize(interpolated v_nrm) + 1) / 2.  Then a lerp to `background` by the coverage mask, silhouette antialiasing
-    and, for ssaa > 1, the average of ssaa x ssaa samples per pixel (rendered at ssaa x the size).
-    Differentiable w.r.t. map_Kd and mesh.v_pos."""
-    if mode not in ("rgb", "normal"):
-        raise ValueError(f"mode must be 'rgb' or 'normal', got {mode!r}")
+    interpolated v_tex (boundary "clamp"), or the interpolated v_rgb when the mesh has no UVs; with both map_Bump and
+    light_dir (3,) (towards the light, world space) that colour times max(0, n . l), n the world normal of mode
+    "normal_map".  mode "normal": (normalize(interpolated v_nrm) + 1) / 2.  mode "normal_map": (n + 1) / 2 with n the
+    world normal rebuilt per pixel from map_Bump (TH,TW,3), a tangent-space normal map as the exporter bakes it:
+    x = 2 map - 1 sampled at the interpolated v_tex, n = normalize(x_0 t^ + x_1 b^ + x_2 n^) in the frame n^ =
+    normalize(interpolated v_nrm), t^ = normalize(t - (t . n^) n^) with t the interpolated v_tng_tex, b^ = t^ x n^
+    (include/tt_abi.h, "tangents and normal-map baking").  Then a lerp to `background` by the coverage mask, silhouette
+    antialiasing and, for ssaa > 1, the average of ssaa x ssaa samples per pixel (rendered at ssaa x the size).
+    Differentiable w.r.t. map_Kd, map_Bump and mesh.v_pos (v_tng_tex is a constant)."""
+    if mode not in ("rgb", "normal", "normal_map"):
+        raise ValueError(f"mode must be 'rgb', 'normal' or 'normal_map', got {mode!r}")
     if ssaa < 1:
         raise ValueError(f"ssaa must be >= 1, got {ssaa}")
     ctx = ctx or RasterizerContext("cuda", mesh.v_pos.device)
@@ -136,12 +181,23 @@ def render_textured(mesh: Mesh, map_Kd: Optional[Tensor], mvp_mtx: Tensor, heigh
     pos = ctx.vertex_transform(mesh.v_pos, mvp_mtx)
     rast, _ = ctx.rasterize(pos, tri, (ssaa * height, ssaa * width))
     mask = (rast[..., 3:] > 0).float()
-    if mode == "normal":
+    if mode == "normal_map" and (map_Bump is None or mesh._v_tex is None):
+        raise ValueError("mode 'normal_map' needs a mesh with v_tex and a map_Bump")
+    shaded = mode == "rgb" and map_Bump is not None and light_dir is not None and mesh._v_tex is not None
+    world_nrm = None
+    if mode == "normal_map" or shaded:
+        world_nrm = world_normal_from_map(mesh, rast, map_Bump, filter_mode=filter_mode, ctx=ctx)
+    if mode == "normal_map":
+        color = (world_nrm + 1.0) / 2.0
+    elif mode == "normal":
         nrm, _ = ctx.interpolate(mesh.v_nrm[None], rast, tri)
         color = (F.normalize(nrm, dim=-1) + 1.0) / 2.0
     elif mesh._v_tex is not None and map_Kd is not None:
         uv, _ = ctx.interpolate(mesh.v_tex[None], rast, mesh.t_tex_idx)
         color = ctx.texture(map_Kd[None], uv, filter_mode=filter_mode, boundary_mode="clamp")
+        if shaded:
+            l = F.normalize(torch.as_tensor(light_dir, dtype=torch.float32, device=color.device).reshape(3), dim=0)
+            color = color * (world_nrm * l).sum(-1, keepdim=True).clamp_min(0.0)
     elif mesh.v_rgb is not None:
         color, _ = ctx.interpolate(mesh.v_rgb[None], rast, tri)
     else:
@@ -166,18 +222,26 @@ def turntable(mesh: Mesh, map_Kd: Optional[Tensor], n_views: int = 4, elevation_
 def main(argv=None) -> None:
     ap = argparse.ArgumentParser(prog="python -m triplaneturbo_amd.viewer", description=__doc__.split("\n\n")[0])
     ap.add_argument("obj", metavar="MODEL.obj")
-    ap.add_argument("--out", required=True, help="directory for rgb_{i}.png (and normal_{i}.png)")
+    ap.add_argument("--out", required=True, help="directory for rgb_{i}.png (and normal_{i}.png, bump_{i}.png)")
     ap.add_argument("--num_views", type=int, default=4)
     ap.add_argument("--normal", action="store_true", help="also write normal_{i}.png")
+    ap.add_argument("--bump", action="store_true",
+                    help="also write bump_{i}.png (mode normal_map) when the MTL names a map_Bump")
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--ssaa", type=int, default=2)
     a = ap.parse_args(argv)
     dev = torch.device("cuda", torch.cuda.current_device())
     mesh, map_kd = load_obj(a.obj, device=dev)
+    map_bump = load_normal_map(a.obj, device=dev) if a.bump else None
     os.makedirs(a.out, exist_ok=True)
+    modes = [("rgb", "rgb")] + ([("normal", "normal")] if a.normal else [])
+    if map_bump is not None:
+        modes.append(("bump", "normal_map"))
     with torch.no_grad():
-        for name in ("rgb", "normal") if a.normal else ("rgb",):
-            imgs = turntable(mesh, map_kd, n_views=a.num_views, height=a.size, width=a.size, mode=name, ssaa=a.ssaa)
+        for name, mode in modes:
+            kw = {"map_Bump": map_bump} if mode == "normal_map" else {}
+            imgs = turntable(mesh, map_kd, n_views=a.num_views, height=a.size, width=a.size, mode=mode, ssaa=a.ssaa,
+                             **kw)
             for i, img in enumerate(imgs.cpu().numpy()):
                 print(export.save_image(os.path.join(a.out, f"{name}_{i}.png"), export._rgb_u8(img)))
 
