@@ -58,6 +58,8 @@
  *   tt_mc_*                 marching cubes with a backward pass: the `diso.DiffMC` call of DiffMarchingCubeHelper
  *                           (triplaneturbo_executable/utils/mesh_exporter.py:29-75, isosurface() :78-141;
  *                           threestudio/models/isosurface.py:18-65); diso is a CUDA-only, un-vendored extension.
+ *   tt_mt_*                 marching tetrahedra with a backward pass: MarchingTetrahedraHelper._forward
+ *                           (threestudio/models/isosurface.py:231-301) without its per-call torch.unique.
  *   tt_mesh_*               Mesh.normal_consistency / laplacian and their backward, Mesh.remove_outlier's connected
  *                           components and compaction (threestudio/models/mesh.py:31-95,255-308; trimesh on the host
  *                           in the reference).
@@ -507,6 +509,44 @@ int tt_mc_emit(const float* level, const float* deformation, int32_t res, float 
  * written (zero off the surface); a gather over each point's 6 incident edges. */
 int tt_mc_bwd(const float* level, const float* deformation, int32_t res, float isovalue, void* workspace,
               const float* grad_v, float* grad_level, float* grad_deformation, void* stream);
+
+/* ---- marching tetrahedra (tt_tets.hip): the drop-in for MarchingTetrahedraHelper._forward ----
+ * Replaces the extraction of threestudio/models/isosurface.py:231-301 (DMTet) and reproduces its outputs: same vertices,
+ * same faces, same order.  The reference finds the unique edges of the surface tets with torch.unique(dim=0) on every
+ * call; the tet grid is static, so here the tables are built once per grid (ops.TetGrid) and passed in:
+ *   tets        (Nt,4) int32: the grid's tetrahedra, vertex ids in [0, Nv).
+ *   edges       (Ne,2) int32: the unique vertex pairs (a < b) of the six base edges 01 02 03 12 13 23 of every tet, in
+ *               lexicographic order (the helper's all_edges, isosurface.py:206-219).
+ *   tet_edge    (Nt,6) int32: the row of `edges` of each base edge of each tet, in that base order.
+ *   vert_ptr    (Nv+1) int32, vert_col int32: vertex -> incident rows of `edges` (CSR, each row ascending).
+ * The entry points TRUST these tables (ops.TetGrid validates them once: every id in range, counts within
+ * TT_MESH_MAX_ITEMS); with valid tables no kernel indexes out of range whatever the level values.
+ *   occupied    a grid vertex is occupied iff level > 0 (isosurface.py:236; NOT marching cubes' level < iso); a NaN
+ *               level is unoccupied.  An edge crosses iff exactly one end is occupied; a tet's case is
+ *               sum_k occupied[v_k] << k into the 16-row triangle table of isosurface.py:141-169.
+ *   vertex      vertex i is the i-th crossing edge in `edges` order.  On the edge (a < b), with s = level, p = pos:
+ *               D = s_a - s_b,  w_a = (-s_b) / D,  w_b = s_a / D,  v = p_a * w_a + p_b * w_b, evaluated in fp32 in that
+ *               order without contraction (isosurface.py:269-276).  D adds like-signed magnitudes: it never cancels.
+ *   faces       the faces of the one-triangle tets in tet order, then two rows per two-triangle tet in tet order
+ *               (isosurface.py:285-299); vertex ids through tet_edge and the triangle table.
+ *   outputs     v_pos fp32 (V,3); t_pos_idx int32 (T1 + 2 T2, 3).  pos (Nv,3) fp32 is the (deformed) grid.
+ *   gradients   tt_mt_bwd: from d loss / d v_pos to level (Nv) and pos (Nv,3), dense, every element written (exact
+ *               zeros off the crossing edges): a gather over each vertex's CSR row in ascending edge order.
+ *               dv/ds_a = (p_b - p_a)(-s_b)/D^2, dv/ds_b = (p_b - p_a) s_a/D^2, dv/dp_a = w_a, dv/dp_b = w_b.
+ * Use: bytes = tt_mt_workspace_bytes(Ne, Nt); tt_mt_count(...) writes (V, T1, T2) to out_totals (3 int32 in DEVICE
+ * memory; read them back -- the only host round trip); allocate v_pos (V,3) and t_pos_idx (T1 + 2 T2, 3); tt_mt_emit
+ * with the SAME tables / workspace; the backward reads the crossing flags and vertex offsets the count left in the
+ * workspace, so keep it.  Every kernel write is bounded by the totals the count itself computed.  No atomics:
+ * identical launches give bit-identical outputs and gradients.  1 <= Ne, Nt, Nv <= TT_MESH_MAX_ITEMS, anything else
+ * is TT_ERR_BAD_ARG. */
+int64_t tt_mt_workspace_bytes(int32_t n_edges, int32_t n_tets);
+int tt_mt_count(const float* level, const int32_t* edges, const int32_t* tets, int32_t n_edges, int32_t n_tets,
+                void* workspace, int32_t* out_totals, void* stream);
+int tt_mt_emit(const float* pos, const float* level, const int32_t* edges, const int32_t* tet_edge, int32_t n_edges,
+               int32_t n_tets, void* workspace, float* v_pos, int32_t* t_pos_idx, void* stream);
+int tt_mt_bwd(const float* pos, const float* level, const int32_t* edges, const int32_t* vert_ptr,
+              const int32_t* vert_col, int32_t n_vertices, int32_t n_edges, int32_t n_tets, void* workspace,
+              const float* grad_v, float* grad_level, float* grad_pos, void* stream);
 
 /* ---- rasterize / interpolate / antialias (tt_raster.hip): the drop-in for nvdiffrast ----
  * Replaces dr.rasterize, dr.interpolate and dr.antialias as NVDiffRasterizerContext calls them

@@ -7,6 +7,9 @@ include/tt_abi.h) instead of the CUDA-only `diso.DiffMC`.
     meshes = isosurface(space_cache, geometry.forward_field, helper)
     meshes = colorize_mesh(space_cache, geometry.export, meshes, torch.sigmoid)
 
+MarchingTetrahedraHelper (threestudio/models/isosurface.py:126-327, isosurface_method "mt") runs on the HIP marching
+tetrahedra (ops.marching_tets, tt_mt_*); kuhn_tet_grid / write_tet_grid make the tet grid the reference loads from a file.
+
 Same signatures and behaviour as the reference; Mesh keeps what these functions and their users touch plus the
 training system's regularisers and outlier removal, and threestudio's UV unwrap (`unwrap_uv`, lazy `v_tex` /
 `t_tex_idx`) on the HIP axis-projection atlas (ops.uv_atlas) instead of xatlas, and its tangents (`v_tng`, and `v_tng_tex`
@@ -290,6 +293,114 @@ class DiffMarchingCubeHelper(IsosurfaceHelper):
         v_pos, t_pos_idx = self.mc_func(level, deformation, isovalue=isovalue)
         v_pos = v_pos * (self.points_range[1] - self.points_range[0]) + self.points_range[0]
         return Mesh(v_pos=v_pos, t_pos_idx=t_pos_idx)
+
+
+_KUHN_PATHS = ((0, 1, 2), (1, 2, 0), (2, 0, 1), (0, 2, 1), (2, 1, 0), (1, 0, 2))  # three even, three odd permutations
+
+
+def kuhn_tet_grid(resolution: int) -> Tuple[Tensor, Tensor]:
+    """A tetrahedral grid on the unit cube for MarchingTetrahedraHelper: `vertices` (R^3,3) fp32, the R points per axis
+    of DiffMarchingCubeHelper(R).grid_vertices in its order (index i R^2 + j R + k = (x_i, y_j, z_k)), and `indices`
+    (6 (R-1)^3, 4) int64, six Kuhn tetrahedra per cell: one per order in which a path from the cell's corner (i,j,k) to
+    (i+1,j+1,k+1) takes its x, y and z step.  All cells are cut alike, so neighbouring cells agree on the diagonal of
+    the face they share and the grid is conforming.  Every tet is positively oriented, det[v1-v0, v2-v0, v3-v0] > 0
+    (the odd step orders list their two middle corners the other way round): with that the reference's triangle table
+    (threestudio/models/isosurface.py:141-169) yields closed surfaces whose normals point toward level > 0.  CPU
+    tensors.  The reference loads such grids from load/tets/{R}_tets.npz, files it does not ship."""
+    R = int(resolution)
+    if R < 2:
+        raise ValueError(f"kuhn_tet_grid needs at least 2 points per axis, got {R}")
+    x = torch.linspace(0, 1, R)
+    vertices = torch.stack(torch.meshgrid(x, x, x, indexing="ij"), dim=-1).reshape(-1, 3)
+    c = torch.arange(R - 1)
+    origin = (c[:, None, None] * R * R + c[None, :, None] * R + c[None, None, :]).reshape(-1, 1)
+    stride = (R * R, R, 1)
+    corners = []
+    for n, (a, b, d) in enumerate(_KUHN_PATHS):
+        v1, v2 = stride[a], stride[a] + stride[b]
+        if n >= 3:  # an odd permutation: swap the middle corners for a positive volume
+            v1, v2 = v2, v1
+        corners.append([0, v1, v2, stride[0] + stride[1] + stride[2]])
+    indices = (origin[:, None, :] + torch.tensor(corners)[None, :, :]).reshape(-1, 4)
+    return vertices, indices
+
+
+def write_tet_grid(path: str, resolution: int) -> None:
+    """kuhn_tet_grid(resolution) as an npz file in the reference's format (arrays `vertices`, `indices`,
+    isosurface.py:179-189), e.g. load/tets/{R}_tets.npz."""
+    import numpy as np
+    vertices, indices = kuhn_tet_grid(resolution)
+    np.savez_compressed(path, vertices=vertices.numpy(), indices=indices.numpy())
+
+
+class MarchingTetrahedraHelper(IsosurfaceHelper):
+    """threestudio/models/isosurface.py:126-327 on the HIP marching tetrahedra (ops.marching_tets, tt_mt_* in
+    include/tt_abi.h): same attributes, same meshes (vertices, faces and their order), same extras.  The grid comes from
+    `tets_path` (the reference's npz: `vertices`, `indices`), from a ready ops.TetGrid, or, with neither, from
+    kuhn_tet_grid(resolution).  The static tables (ops.TetGrid) are built on the first use on the GPU.
+
+    center_indices / border_indices, (n,1) int64: the vertex sets of the mesh renderer's empty-field fix-up, chosen by
+    position so that any grid works (the reference indexes an R^3 lattice whatever the file holds).  With the bounding
+    box of the vertices and h = its extent / (R - 1) per axis: the border is every vertex with a coordinate closer than
+    1.5 h to a face of the box; the centre is the one vertex nearest to box_min + (R // 2) h (lowest index on a tie).
+    On an R^3 lattice these are the two outer layers and the vertex (R//2, R//2, R//2), the reference's sets."""
+
+    def __init__(self, resolution: int, tets_path: Optional[str] = None, point_range: Tuple[float, float] = (0, 1),
+                 tet_grid: Optional[ops.TetGrid] = None) -> None:
+        super().__init__()
+        self.resolution = resolution
+        self.tets_path = tets_path
+        self.points_range = point_range
+        self._tet_grid = tet_grid
+        if tet_grid is not None:
+            if tets_path is not None:
+                raise ValueError("give tets_path or tet_grid, not both")
+            vertices, indices = tet_grid.vertices, tet_grid.tets.long()
+        elif tets_path is not None:
+            import numpy as np
+            tets = np.load(tets_path)
+            vertices, indices = torch.from_numpy(tets["vertices"]).float(), torch.from_numpy(tets["indices"]).long()
+        else:
+            vertices, indices = kuhn_tet_grid(resolution)
+        self.register_buffer("_grid_vertices", vertices, persistent=False)
+        self.register_buffer("indices", indices, persistent=False)
+        lo, hi = vertices.amin(0), vertices.amax(0)
+        h = (hi - lo) / max(resolution - 1, 1)
+        border = ((vertices - lo < 1.5 * h) | (hi - vertices < 1.5 * h)).any(dim=1)
+        centre = (vertices - (lo + (resolution // 2) * h)).square().sum(dim=1).argmin()
+        self.register_buffer("border_indices", torch.nonzero(border), persistent=False)
+        self.register_buffer("center_indices", centre.reshape(1, 1), persistent=False)
+        self._all_edges: Optional[Tensor] = None
+
+    def normalize_grid_deformation(self, grid_vertex_offsets: Tensor) -> Tensor:
+        # half a tet is about 1 / resolution (isosurface.py:193-200)
+        return (self.points_range[1] - self.points_range[0]) / self.resolution * torch.tanh(grid_vertex_offsets)
+
+    @property
+    def grid_vertices(self) -> Tensor:
+        return self._grid_vertices
+
+    @property
+    def tet_grid(self) -> ops.TetGrid:
+        if self._tet_grid is None or self._tet_grid.tets.device != self.indices.device:
+            self._tet_grid = ops.TetGrid(self._grid_vertices, self.indices)
+            self._all_edges = None
+        return self._tet_grid
+
+    @property
+    def all_edges(self) -> Tensor:
+        if self._all_edges is None:
+            self._all_edges = self.tet_grid.edges.long()
+        return self._all_edges
+
+    def forward(self, level: Tensor, deformation: Optional[Tensor] = None) -> Mesh:
+        if deformation is not None:
+            grid_vertices = self.grid_vertices + self.normalize_grid_deformation(deformation)
+        else:
+            grid_vertices = self.grid_vertices
+        v_pos, t_pos_idx = ops.marching_tets(grid_vertices, level, self.tet_grid)
+        return Mesh(v_pos=v_pos, t_pos_idx=t_pos_idx, grid_vertices=grid_vertices, tet_edges=self.all_edges,
+                    grid_level=level, grid_deformation=deformation)
 
 
 def isosurface(space_cache: Any, forward_field: Callable, isosurface_helper: Callable) -> List[Mesh]:

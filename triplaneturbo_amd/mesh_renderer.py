@@ -1,19 +1,22 @@
 """`generative-space-mesh-rasterize-renderer`: the reference's first training renderer
 (custom/triplaneturbo/models/renderers/generative_space_mesh_rasterize_renderer.py) on this package's pieces: the
-grid query `geometry.forward_field`, the HIP marching cubes (isosurface.DiffMarchingCubeHelper), the HIP rasterizer
+grid query `geometry.forward_field`, the HIP marching cubes (isosurface.DiffMarchingCubeHelper, "diffmc") or marching
+tetrahedra (isosurface.MarchingTetrahedraHelper, "mt"), the HIP rasterizer
 (raster.RasterizerContext in place of nvdiffrast) and the per-pixel `geometry(points, output_normal=True)` decode.
 Same registry name, Config fields, forward signature, per-prompt loop and output keys as the reference; the image
 plumbing between the kernels (normal rotation, lerps, disparity) stays torch, as in the reference."""
 from __future__ import annotations
 
+import os
 from dataclasses import dataclass
 from typing import Any, Callable, Dict, List, NamedTuple, Optional, Union
 
 import torch
 import torch.nn.functional as F
 
-from . import raster
-from .isosurface import DiffMarchingCubeHelper, Mesh, cache_batch_device, prompt_slice, scale_tensor
+from . import ops, raster
+from .isosurface import (DiffMarchingCubeHelper, MarchingTetrahedraHelper, Mesh, cache_batch_device, prompt_slice,
+                         scale_tensor)
 from .registry import BaseModule, C, register
 
 Tensor = torch.Tensor
@@ -46,7 +49,7 @@ class GenerativeSpaceMeshRasterizeRenderer(BaseModule):
         isosurface_resolution: int = 128
         isosurface_remove_outliers: bool = False
         isosurface_outlier_n_faces_threshold: Union[int, float] = 0.01
-        isosurface_method: str = "mt"  # "mt" or "mc-cpu" or "diffmc" (only "diffmc" is built here)
+        isosurface_method: str = "mt"  # "mt" or "mc-cpu" or "diffmc" ("diffmc" and "mt" are built here)
         enable_bg_rays: bool = False
         normal_direction: str = "camera"  # "camera" or "world" or "front"
         sdf_grad_shrink: Any = 1.0
@@ -55,11 +58,30 @@ class GenerativeSpaceMeshRasterizeRenderer(BaseModule):
 
     cfg: Config
 
-    def configure(self, geometry, material, background) -> None:
+    def configure(self, geometry, material, background, tet_grid=None) -> None:
+        """`tet_grid` (isosurface_method="mt" only): the tetrahedral grid, an ops.TetGrid (e.g. of
+        isosurface.kuhn_tet_grid(R)) or the path of an npz file in the reference's format; without it the reference's
+        load/tets/{R}_tets.npz is used when that file exists."""
         c = self.cfg
-        if c.isosurface_method != "diffmc":
-            raise NotImplementedError(f"isosurface_method={c.isosurface_method!r}: only 'diffmc' (the reference "
-                                      f"training config) is built; 'mt' / 'mc-cpu' need tetrahedra / CPU helpers")
+        R = c.isosurface_resolution
+        if c.isosurface_method == "diffmc":
+            helper = DiffMarchingCubeHelper(R)
+        elif c.isosurface_method == "mt":
+            default_path = f"load/tets/{R}_tets.npz"  # reference :72-77
+            if isinstance(tet_grid, ops.TetGrid):
+                helper = MarchingTetrahedraHelper(R, tet_grid=tet_grid)
+            elif tet_grid is not None:
+                helper = MarchingTetrahedraHelper(R, os.fspath(tet_grid))
+            elif os.path.exists(default_path):
+                helper = MarchingTetrahedraHelper(R, default_path)
+            else:
+                raise NotImplementedError(
+                    f"isosurface_method='mt' needs a tetrahedral grid and {default_path} does not exist: pass "
+                    f"tet_grid=ops.TetGrid(*isosurface.kuhn_tet_grid({R})) (tensors on the GPU) or the path of an npz "
+                    f"file with `vertices` and `indices` (isosurface.write_tet_grid writes one) to the renderer")
+        else:
+            raise NotImplementedError(f"isosurface_method={c.isosurface_method!r}: 'diffmc' (the reference training "
+                                      f"config) and 'mt' are built; 'mc-cpu' needs a CPU helper")
         if c.isosurface_remove_outliers:
             raise NotImplementedError("isosurface_remove_outliers=True (Mesh.remove_outlier) is not built")
         if getattr(material, "requires_tangent", False):
@@ -67,7 +89,7 @@ class GenerativeSpaceMeshRasterizeRenderer(BaseModule):
         self.geometry, self.material, self.background = geometry, material, background
         self.ctx = raster.RasterizerContext(c.context_type, None)
         self.geometry.isosurface = self.isosurface  # overwrite the geometry's (reference :74)
-        self.isosurface_helper = DiffMarchingCubeHelper(c.isosurface_resolution)
+        self.isosurface_helper = helper
         self.sdf_grad_shrink = C(c.sdf_grad_shrink, 0, 0)
         self.def_grad_shrink = C(c.def_grad_shrink, 0, 0)
         self.empty_flag = False
@@ -75,7 +97,9 @@ class GenerativeSpaceMeshRasterizeRenderer(BaseModule):
         # antialias every prompt's views in one range-mode call each instead of once per prompt
         self.batch_prompts = False
         # follow InstantMesh (reference :97-107): a positive shell and a negative centre for an empty field
-        R = c.isosurface_resolution
+        if c.isosurface_method == "mt":  # by position, for any tet grid (MarchingTetrahedraHelper's docstring)
+            self.center_indices, self.border_indices = helper.center_indices, helper.border_indices
+            return
         v = torch.zeros([R] * 3, dtype=torch.bool)
         v[R // 2:R // 2 + 1, R // 2:R // 2 + 1, R // 2:R // 2 + 1] = True
         self.center_indices = torch.nonzero(v.reshape(-1))
@@ -288,7 +312,7 @@ class GenerativeSpaceMeshRasterizeRenderer(BaseModule):
 
     def isosurface(self, space_cache: Any) -> List[Mesh]:
         """reference :416-514: grid query on the [-1, 1] box, gradient shrink, the InstantMesh fix-up of an empty
-        field, one marching-cubes helper per prompt, vertices mapped back to [-1, 1]."""
+        field, one marching-cubes helper per prompt ("mt": one helper for all), vertices mapped back to [-1, 1]."""
         batch_size, device = cache_batch_device(space_cache)
         helper = self.isosurface_helper
         points = scale_tensor(helper.grid_vertices.to(device), helper.points_range, [-1, 1])
@@ -321,7 +345,7 @@ class GenerativeSpaceMeshRasterizeRenderer(BaseModule):
                 new_sdf = sdf + update_sdf
                 update_mask = (new_sdf == 0).float()
                 sdf = new_sdf * (1 - update_mask) + sdf * update_mask
-            if index > 0:  # one helper per prompt (reference :490-500)
+            if index > 0 and self.cfg.isosurface_method == "diffmc":  # one helper per prompt (reference :514-524)
                 name = f"isosurface_helper_{index}"
                 if not hasattr(self, name):
                     setattr(self, name, DiffMarchingCubeHelper(self.cfg.isosurface_resolution))

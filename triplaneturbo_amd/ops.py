@@ -888,6 +888,109 @@ def marching_cubes(level: Tensor, deformation: Optional[Tensor] = None, isovalue
     return _MarchingCubesFn.apply(level, deformation, float(isovalue))
 
 
+_TET_BASE_EDGES = (0, 1, 0, 2, 0, 3, 1, 2, 1, 3, 2, 3)  # isosurface.py:175: the six edges of a tet, as corner pairs
+
+
+class TetGrid:
+    """The static tables of a tetrahedral grid for ops.marching_tets (include/tt_abi.h "marching tetrahedra"), built
+    once with one torch.unique and one stable sort on the grid's device (plumbing; it syncs):
+      vertices    (Nv,3) fp32, tets (Nt,4) int32: the grid as given
+      edges       (Ne,2) int32: the unique vertex pairs (a < b) of the six base edges of every tet, lexicographic: the
+                  reference helper's all_edges (threestudio/models/isosurface.py:206-219)
+      tet_edge    (Nt,6) int32: the row of `edges` of each base edge of each tet
+      vert_ptr    (Nv+1) int32, vert_col (2 Ne) int32: vertex -> incident rows of `edges`, each row ascending
+    The constructor validates what the kernels trust: indices inside [0, Nv), counts within TT_MESH_MAX_ITEMS."""
+
+    def __init__(self, vertices: Tensor, indices: Tensor):
+        for t, name in ((vertices, "vertices"), (indices, "indices")):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise RuntimeError(f"{name} must live on the GPU (triplaneturbo_amd has no CPU path)")
+        if vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 3:
+            raise TypeError(f"vertices must be (Nv,3) float32, got {tuple(vertices.shape)} {vertices.dtype}")
+        if indices.dtype not in (torch.int32, torch.int64) or indices.dim() != 2 or indices.shape[1] != 4:
+            raise TypeError(f"indices must be (Nt,4) int32 / int64, got {tuple(indices.shape)} {indices.dtype}")
+        Nv, Nt = int(vertices.shape[0]), int(indices.shape[0])
+        lim = 1 << 28  # TT_MESH_MAX_ITEMS
+        if Nv < 1 or Nt < 1 or Nv > lim or Nt > lim:
+            raise ValueError(f"tet grid outside the supported sizes: Nv={Nv}, Nt={Nt} (1 ... {lim})")
+        lo, hi = torch.stack(indices.aminmax()).tolist()  # one read-back
+        if lo < 0 or hi >= Nv:
+            raise ValueError(f"indices holds a vertex id outside [0, {Nv})")
+        self.n_vertices, self.n_tets = Nv, Nt
+        self.vertices = vertices.contiguous()
+        self.tets = indices.int().contiguous()
+        pairs = indices.long()[:, list(_TET_BASE_EDGES)].reshape(-1, 2)
+        key = torch.add(pairs.amax(1), pairs.amin(1), alpha=Nv)
+        uniq, inverse = torch.unique(key, return_inverse=True)  # sorted: lexicographic in (a, b)
+        self.edges = torch.stack([uniq // Nv, uniq % Nv], dim=1).int().contiguous()
+        self.tet_edge = inverse.reshape(Nt, 6).int().contiguous()
+        Ne = self.n_edges = int(uniq.shape[0])
+        if Ne > lim:
+            raise ValueError(f"tet grid outside the supported sizes: Ne={Ne} (limit {lim})")
+        src = self.edges.long().t().reshape(-1)  # the a ends, then the b ends
+        eid = torch.arange(Ne, device=src.device).repeat(2)
+        order = torch.sort(torch.add(eid, src, alpha=Ne), stable=True)[1]
+        ptr = torch.zeros(Nv + 1, dtype=torch.int64, device=src.device)
+        ptr[1:] = torch.cumsum(torch.bincount(src, minlength=Nv), 0)
+        self.vert_ptr, self.vert_col = ptr.int().contiguous(), eid[order].int().contiguous()
+
+
+class _MarchingTetsFn(torch.autograd.Function):
+    """Marching tetrahedra with a backward pass (tt_mt_*, include/tt_abi.h "marching tetrahedra"):
+    MarchingTetrahedraHelper._forward (threestudio/models/isosurface.py:231-301).  Forward = count, one 12-byte
+    read-back, allocate, emit; the workspace (crossing flags + vertex offsets) stays in ctx for the gather tt_mt_bwd."""
+
+    @staticmethod
+    def forward(ctx, pos, level, grid):
+        dev = level.device
+        ws = _workspace("tt_mt_workspace_bytes", grid.n_edges, grid.n_tets, device=dev)
+        totals = torch.empty(3, device=dev, dtype=torch.int32)
+        _launch("tt_mt_count", level, grid.edges, grid.tets, grid.n_edges, grid.n_tets, ws, totals)
+        n_vert, n_one, n_two = (int(x) for x in totals.cpu())
+        v_pos = torch.empty((n_vert, 3), device=dev, dtype=torch.float32)
+        t_pos_idx = torch.empty((n_one + 2 * n_two, 3), device=dev, dtype=torch.int32)
+        if n_vert > 0:
+            _launch("tt_mt_emit", pos, level, grid.edges, grid.tet_edge, grid.n_edges, grid.n_tets, ws, v_pos,
+                    t_pos_idx)
+        ctx.save_for_backward(pos, level, ws)
+        ctx.grid = grid
+        ctx.mark_non_differentiable(t_pos_idx)
+        return v_pos, t_pos_idx
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_v, g_t):
+        pos, level, ws = ctx.saved_tensors
+        grid = ctx.grid
+        if g_v is None or not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return None, None, None
+        g_level, g_pos = torch.empty_like(level), torch.empty_like(pos)
+        if g_v.shape[0] == 0:
+            g_level.zero_()
+            g_pos.zero_()
+        else:
+            _launch("tt_mt_bwd", pos, level, grid.edges, grid.vert_ptr, grid.vert_col, grid.n_vertices, grid.n_edges,
+                    grid.n_tets, ws, g_v.contiguous(), g_level, g_pos)
+        return (g_pos if ctx.needs_input_grad[0] else None, g_level if ctx.needs_input_grad[1] else None, None)
+
+
+def marching_tets(pos: Tensor, level: Tensor, grid: TetGrid) -> Tuple[Tensor, Tensor]:
+    """The surface level = 0 of a field on a tet grid: `pos` (Nv,3) the (deformed) grid vertices, `level` (Nv) or
+    (Nv,1), `grid` the TetGrid of the topology.  Returns v_pos (V,3) fp32 and t_pos_idx (T,3) int32, vertices and faces
+    in the reference helper's order; differentiable w.r.t. level and pos (through v_pos).  Contract: include/tt_abi.h,
+    "marching tetrahedra"."""
+    if not isinstance(grid, TetGrid):
+        raise TypeError("grid must be an ops.TetGrid")
+    Nv = grid.n_vertices
+    if not isinstance(level, torch.Tensor) or level.numel() != Nv:
+        raise ValueError(f"level must hold one value per grid vertex ({Nv})")
+    pos = _chk(pos, "pos", (Nv, 3))
+    level = _chk(level.reshape(Nv), "level")
+    if pos.device != grid.tets.device:
+        raise RuntimeError(f"pos lives on {pos.device}, the tet grid on {grid.tets.device}")
+    return _MarchingTetsFn.apply(pos, level, grid)
+
+
 class FaceEdgeSort(NamedTuple):
     """sort_face_edges' result, all int64: sorted position p holds face edge perm[p] = 3f + k (vertices k, (k+1) % 3
     of face f) and lies in group inverse[p]; group g has the key uniq[g] = min(a,b) * base + max(a,b), counts[g] face
