@@ -282,3 +282,67 @@ def test_remove_outlier_160_through_isosurface(dev):
         want_v, want_t = M.remove_small_components(v, t, thr)
         assert np.array_equal(clean.v_pos.cpu().numpy(), want_v)
         assert np.array_equal(clean.t_pos_idx.cpu().numpy(), want_t)
+
+
+def _csr_by_loop(pairs, n_rows):
+    rows = [[] for _ in range(n_rows)]
+    for r, c in pairs:
+        rows[r].append(c)
+    ptr = np.cumsum([0] + [len(r) for r in rows]).tolist()
+    return ptr, [c for r in rows for c in sorted(r)]
+
+
+def test_shared_csr_builder_and_validators_on_the_smallest_meshes(dev):
+    """ops._csr behind MeshTopology.nbr_*, TetGrid.vert_* and mesh_tangents' group -> corner table, and the shared index
+    checks, at the smallest shapes that reach every branch: a tetrahedron, the same with a degenerate face (a self
+    pair), the R = 3 Kuhn lattice and a two-triangle quad cut along its diagonal in UV space."""
+    from triplaneturbo_amd.isosurface import kuhn_tet_grid
+    tet = torch.tensor([[0, 1, 2], [0, 3, 1], [0, 2, 3], [1, 3, 2]])
+    for tri in (tet, torch.cat([tet, torch.tensor([[0, 0, 1]])])):
+        a, b = ops.MeshTopology(tri.to(dev, torch.int32), 4), ops.MeshTopology(tri.to(dev), 4)
+        edges = a.edges.cpu().tolist()
+        assert ([0, 0] in edges) == (len(tri) == 5) and b.edges.dtype == torch.int64
+        want = _csr_by_loop(edges + [e[::-1] for e in edges], 4)
+        for topo in (a, b):
+            assert topo.nbr_ptr.dtype == topo.nbr_col.dtype == torch.int32
+            assert (topo.nbr_ptr.tolist(), topo.nbr_col.tolist()) == want
+    v, t = kuhn_tet_grid(3)
+    grid = ops.TetGrid(v.to(dev), t.to(dev))
+    edges = grid.edges.cpu().tolist()
+    want = _csr_by_loop([(a_, e) for e, (a_, _) in enumerate(edges)] + [(b_, e) for e, (_, b_) in enumerate(edges)], 27)
+    assert (grid.vert_ptr.tolist(), grid.vert_col.tolist()) == want and grid.vert_col.dtype == torch.int32
+    assert torch.equal(ops.TetGrid(v.to(dev), t.to(dev, torch.int32)).vert_col, grid.vert_col)
+
+    v_pos = torch.tensor([[0., 0, 0], [1, 0, 0], [1, 1, 0], [0, 1, 0]], device=dev)
+    v_nrm = torch.tensor([[0., 0, 1]], device=dev).repeat(4, 1)
+    quad = torch.tensor([[0, 1, 2], [0, 2, 3]], device=dev, dtype=torch.int32)
+    v_tex = torch.tensor([[0., 0], [.4, 0], [.4, .4], [.5, .1], [.9, .5], [.5, .5]], device=dev)  # Vt = 6: a seam
+    t_tex = torch.tensor([[0, 1, 2], [3, 4, 5]], device=dev)
+    got = ops.mesh_tangents(v_pos, quad, v_tex, t_tex, v_nrm, group="tex")
+    key = t_tex.reshape(-1).long()  # the table as it was built before ops._csr: a stable sort by the row alone
+    corner = torch.sort(key, stable=True)[1].int().contiguous()
+    ptr = torch.zeros(7, device=dev, dtype=torch.int64)
+    ptr[1:] = torch.cumsum(torch.bincount(key, minlength=6), 0)
+    want = torch.empty_like(got)
+    ops._launch("tt_bake_tangents", v_pos, quad, v_tex, t_tex.int(), v_nrm, ptr.int(), corner, 4, 6, 2,
+                ops._BAKE_GROUPS["tex"], want)
+    assert got.shape == (6, 3) and torch.equal(got, want) and torch.isfinite(got).all()
+    assert torch.equal(got, ops.mesh_tangents(v_pos, quad.long(), v_tex, t_tex.int(), v_nrm, group="tex"))
+
+    rast, field = torch.zeros(2, 2, 4, device=dev), torch.zeros(2, 2, 3, device=dev)
+    users = {"MeshTopology": lambda x: ops.MeshTopology(x, 4), "mesh_simplify": lambda x: ops.mesh_simplify(v_pos, x, 4),
+             "mesh_tangents": lambda x: ops.mesh_tangents(v_pos, x, v_tex, t_tex, v_nrm),
+             "bake_encode": lambda x: ops.bake_encode(rast, v_nrm, x, got, t_tex, field)}
+    for name, fn in users.items():
+        for bad in (quad.short(), quad.float(), quad[:, :2], quad.reshape(-1)):
+            with pytest.raises(TypeError, match="int32 / int64"):
+                fn(bad)
+        if name != "bake_encode":  # (its kernel reads the ids of covered texels only: no range check, as before)
+            for bad in (quad + 2, quad - 1):
+                with pytest.raises(ValueError, match="outside"):
+                    fn(bad)
+    for bad in (t.to(dev, torch.int16), t.to(dev).float(), t.to(dev)[:, :3]):
+        with pytest.raises(TypeError, match="int32 / int64"):
+            ops.TetGrid(v.to(dev), bad)
+    with pytest.raises(ValueError, match="outside"):
+        ops.TetGrid(v.to(dev)[:-1], t.to(dev))

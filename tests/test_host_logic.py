@@ -233,7 +233,7 @@ int64_t tt_c(const float* x, int64_t n,
         "tt_a": (ctypes.c_int32, []), "tt_b": (ctypes.c_char_p, [ctypes.c_int32]),
         "tt_c": (ctypes.c_int64, [P, ctypes.c_int64, ctypes.POINTER(_lib.RenderCfg), ctypes.POINTER(_lib.MlpWeights),
                                   ctypes.c_double, P])}
-    assert defines == {"TT_A": 3, "TT_B": 31}  # no expression evaluator: (1 << 4) and float macros are not constants
+    assert defines == {"TT_A": 3, "TT_B": 31, "TT_C": 16, "TT_D": 0.5}  # every value-carrying define, none skipped
     for bad in ("int tt_x(size_t n, void* stream);", "int tt_x(unsigned int n);", "size_t tt_x(int n);",
                 "int tt_x(float** p);"):
         with pytest.raises(ValueError, match="tt_x"):  # never a silent c_void_p / c_int

@@ -5,8 +5,10 @@ any op fails loudly.  ``build()`` cross-compiles for gfx950 with hipcc (works wi
 """
 from __future__ import annotations
 
+import ast
 import ctypes
 import hashlib
+import operator
 import os
 import re
 import subprocess
@@ -233,7 +235,10 @@ _STRUCT_POINTERS = {"tt_mlp_weights": MlpWeights, "tt_mlp_grads": MlpWeights,  #
                     "tt_render_cfg": RenderCfg, "tt_hashgrid_cfg": HashGridCfg}
 _PROTO_RE = re.compile(r"^[ \t]*((?:const\s+)?\w+\s*\*?)\s*(tt_\w+)\s*\(([^()]*)\)\s*;", re.M)
 _PARAM_RE = re.compile(r"(?:const\s+)?(\w+)\s*(\*?)\s*\w*")
-_DEFINE_RE = re.compile(r"^#define[ \t]+(TT_\w+)[ \t]+(0[xX][0-9a-fA-F]+|\d+)[ \t]*$", re.M)
+_DEFINE_RE = re.compile(r"^#define[ \t]+(TT_\w+)[ \t]+(\S.*?)[ \t]*$", re.M)
+_ENUM_RE = re.compile(r"\benum\b[^{};]*\{([^{}]*)\}")
+_FLOAT_RE = re.compile(r"(?=.*[.eE])(\d*\.?\d*(?:[eE][+-]?\d+)?)[fF]?")
+_INT_OPS = {ast.LShift: operator.lshift, ast.Add: operator.add, ast.Sub: operator.sub}
 
 
 def _ctype(decl: str, proto: str):
@@ -249,10 +254,32 @@ def _ctype(decl: str, proto: str):
     return _SCALARS[base]
 
 
+def _int_expr(node: ast.AST) -> int:
+    """An integer constant expression as a tree: integer literals, parentheses, <<, +, - and unary minus, nothing else."""
+    if isinstance(node, ast.Constant) and type(node.value) is int:
+        return node.value
+    if isinstance(node, ast.UnaryOp) and isinstance(node.op, ast.USub):
+        return -_int_expr(node.operand)
+    if isinstance(node, ast.BinOp) and type(node.op) in _INT_OPS:
+        return _INT_OPS[type(node.op)](_int_expr(node.left), _int_expr(node.right))
+    raise ValueError(ast.dump(node))
+
+
+def _constant(name: str, expr: str):
+    """The value of one `#define TT_*` / enumerator: a float literal (its f suffix dropped) or an integer constant
+    expression.  Parsed, never evaluated as code; anything else raises (never skip: a constant that silently went
+    missing would come back as a hand-written copy)."""
+    m = _FLOAT_RE.fullmatch(expr)
+    try:
+        return float(m.group(1)) if m else _int_expr(ast.parse(expr, mode="eval").body)
+    except (SyntaxError, ValueError):
+        raise ValueError(f"include/tt_abi.h: {name}: no constant for {expr!r}") from None
+
+
 def _parse_abi(text: Optional[str] = None):
     """include/tt_abi.h (or `text`) as ({name: (restype, argtypes)} of every tt_* prototype, {name: value} of every
-    #define TT_* that is a plain integer literal).  The header is the one description of the C ABI: load() binds from
-    this, SYMBOLS and the TT_* flag constants below are read from it."""
+    value-carrying #define TT_* and every enumerator).  The header is the one description of the C ABI: load() binds
+    from this, SYMBOLS and the TT_* constants below are read from it."""
     if text is None:
         text = open(os.path.join(INCLUDE, "tt_abi.h")).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
@@ -260,12 +287,15 @@ def _parse_abi(text: Optional[str] = None):
     for ret, name, params in _PROTO_RE.findall(text):
         params = [] if params.strip() in ("", "void") else params.split(",")
         protos[name] = (_ctype(ret, name), [_ctype(p, name) for p in params])
-    return protos, {k: int(v, 0) for k, v in _DEFINE_RE.findall(text)}
+    consts = _DEFINE_RE.findall(text)
+    for body in _ENUM_RE.findall(text):  # enumerators carry explicit values here: `NAME = value`, nothing to count
+        consts += [tuple(x.strip() for x in item.partition("=")[::2]) for item in body.split(",") if item.strip()]
+    return protos, {name: _constant(name, expr) for name, expr in consts}
 
 
 _PROTOS, _DEFINES = _parse_abi()
 SYMBOLS = list(_PROTOS)  # every symbol include/tt_abi.h declares
-globals().update(_DEFINES)  # TT_R_*, TT_Q_*, TT_PLACE_VOLSDF, TT_DTYPE_*, ... as module attributes
+globals().update(_DEFINES)  # TT_R_*, TT_Q_*, TT_ERR_*, TT_MESH_MAX_ITEMS, TT_UV_DEFAULT_TAU, ... as module attributes
 
 # Precision of the per-point MLP products (include/tt_abi.h, "precision of the matrix products"):
 #   "split3" (default)  fp32-grade: three fp16 pieces per operand, six product terms on the fp16 matrix pipe
@@ -299,7 +329,7 @@ def q_flag(name: str) -> int:
     return _PRECISION_FLAGS[name][1]
 
 
-PLACEMENTS = {"tt": 0, "center": 1}  # enum tt_sample_placement
+PLACEMENTS = {"tt": _DEFINES["TT_PLACE_TT"], "center": _DEFINES["TT_PLACE_CENTER"]}  # enum tt_sample_placement
 
 
 def load() -> ctypes.CDLL:

@@ -99,21 +99,65 @@ def _workspace(name: str, *dims: int, device) -> Tensor:
     return torch.empty(nbytes, device=device, dtype=torch.uint8)
 
 
-def _chk(t: Tensor, name: str, shape: Optional[Sequence[int]] = None, dtype=torch.float32) -> Tensor:
+def _chk_gpu(t: Tensor, name: str) -> None:
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name} must be a tensor")
     if not t.is_cuda:
         raise RuntimeError(f"{name} must live on the GPU (triplaneturbo_amd has no CPU path)")
-    if t.dtype != dtype:
-        raise TypeError(f"{name} must be {dtype}, got {t.dtype}")
     if t.device.index != torch.cuda.current_device():
         # the kernels run on the current device's current stream (one process per GPU): a tensor of another GPU
         # would be a wild pointer there
         raise RuntimeError(f"{name} lives on {t.device} but the current device is cuda:{torch.cuda.current_device()}; "
                            f"call torch.cuda.set_device (one process per GPU)")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+
+
+def _chk(t: Tensor, name: str, shape: Optional[Sequence[Optional[int]]] = None, dtype=torch.float32) -> Tensor:
+    """`t` as a kernel argument: a `dtype` tensor on the current GPU, made contiguous; `shape` with None for any size."""
+    _chk_gpu(t, name)
+    if t.dtype != dtype:
+        raise TypeError(f"{name} must be {dtype}, got {t.dtype}")
+    if shape is not None and (t.dim() != len(shape) or any(e not in (None, n) for e, n in zip(shape, t.shape))):
+        raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {str(tuple(shape)).replace('None', '*')}")
     return t.contiguous()
+
+
+def _chk_index(t: Tensor, name: str, width: int, rows: Optional[int] = None) -> Tensor:
+    """An index table of the mesh stage: (N, width) int32 / int64 on the current GPU, N = `rows` when given.  Its values
+    are checked with _minmax (one read-back, the caller's) and _chk_range."""
+    _chk_gpu(t, name)
+    if t.dtype not in (torch.int32, torch.int64) or t.dim() != 2 or t.shape[1] != width:
+        raise TypeError(f"{name} must be (N,{width}) int32 / int64, got {tuple(t.shape)} {t.dtype}")
+    if rows is not None and t.shape[0] != rows:
+        raise ValueError(f"{name} has {t.shape[0]} rows, expected {rows}")
+    return t
+
+
+def _minmax(*tables: Tensor) -> Tensor:
+    """(min, max) of every table, as one tensor on their device: (0, -1), in range for every n, for an empty table."""
+    return torch.stack([x for t in tables for x in (t.aminmax() if t.numel() else t.new_tensor([0, -1]).unbind())])
+
+
+def _chk_range(name: str, lo: int, hi: int, n: int) -> None:
+    if lo < 0 or hi >= n:
+        raise ValueError(f"{name} holds an index outside [0, {n})")
+
+
+def _chk_size(what: str, **counts: int) -> None:
+    if max(counts.values()) > _lib.TT_MESH_MAX_ITEMS:
+        sizes = ", ".join(f"{k}={v}" for k, v in counts.items())
+        raise ValueError(f"{what}: {sizes} (limit TT_MESH_MAX_ITEMS = {_lib.TT_MESH_MAX_ITEMS})")
+
+
+def _csr(row: Tensor, col: Optional[Tensor], n_rows: int, n_cols: int) -> Tuple[Tensor, Tensor]:
+    """The pairs (row[i], col[i]) (int64, any device; row < n_rows, col < n_cols) as a CSR table: ptr (n_rows + 1) int32
+    and col int32 sorted by (row, col), from one stable sort of row * n_cols + col.  With n_rows <= TT_MESH_MAX_ITEMS =
+    2^28 and n_cols <= 3 * 2^28 (the corners of that many faces) the key stays below 2^58.  col = None is col[i] = i:
+    the stable sort of the rows alone is that order already (0.05 ms of 0.25 for mesh_tangents at 28 k faces)."""
+    order = torch.sort(row if col is None else torch.add(col, row, alpha=max(n_cols, 1)), stable=True)[1]
+    out = (order if col is None else col[order]).int().contiguous()  # (queued before the row count, which syncs)
+    ptr = torch.zeros(n_rows + 1, dtype=torch.int64, device=row.device)
+    ptr[1:] = torch.cumsum(torch.bincount(row, minlength=n_rows), 0)
+    return ptr.int().contiguous(), out
 
 
 def _weights_struct(sdf_w: Sequence[Tensor], net2_w: Optional[Sequence[Tensor]], net2: str = "feat v",
@@ -172,9 +216,7 @@ class RenderConfig:
 
 def planes_pack(space_cache: Tensor) -> Tensor:
     """(P,6,32,H,W) generator output -> (P,6,H,W,32) channels-last, rotate_planes 'v1' folded in."""
-    space_cache = _chk(space_cache, "space_cache")
-    if space_cache.ndim != 5 or space_cache.shape[1] != 6 or space_cache.shape[2] != 32:
-        raise ValueError(f"space_cache must be (P,6,32,H,W), got {tuple(space_cache.shape)}")
+    space_cache = _chk(space_cache, "space_cache", (None, 6, 32, None, None))
     P, _, _, H, W = space_cache.shape
     out = torch.empty((P, 6, H, W, 32), device=space_cache.device, dtype=torch.float32)
     _launch("tt_planes_pack", space_cache, out, P, H, W)
@@ -811,9 +853,7 @@ class _EikonalFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, sdf_grad):
-        g = _chk(sdf_grad, "sdf_grad")
-        if g.ndim != 2 or g.shape[1] != 3:
-            raise ValueError(f"sdf_grad must be (n, 3), got {tuple(g.shape)}")
+        g = _chk(sdf_grad, "sdf_grad", (None, 3))
         loss = torch.empty((), device=g.device, dtype=torch.float32)
         _launch("tt_eikonal_fwd", g, g.shape[0], loss)
         ctx.save_for_backward(g)
@@ -902,22 +942,14 @@ class TetGrid:
     The constructor validates what the kernels trust: indices inside [0, Nv), counts within TT_MESH_MAX_ITEMS."""
 
     def __init__(self, vertices: Tensor, indices: Tensor):
-        for t, name in ((vertices, "vertices"), (indices, "indices")):
-            if not isinstance(t, torch.Tensor) or not t.is_cuda:
-                raise RuntimeError(f"{name} must live on the GPU (triplaneturbo_amd has no CPU path)")
-        if vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 3:
-            raise TypeError(f"vertices must be (Nv,3) float32, got {tuple(vertices.shape)} {vertices.dtype}")
-        if indices.dtype not in (torch.int32, torch.int64) or indices.dim() != 2 or indices.shape[1] != 4:
-            raise TypeError(f"indices must be (Nt,4) int32 / int64, got {tuple(indices.shape)} {indices.dtype}")
+        self.vertices = _chk(vertices, "vertices", (None, 3))
+        indices = _chk_index(indices, "indices", 4)
         Nv, Nt = int(vertices.shape[0]), int(indices.shape[0])
-        lim = 1 << 28  # TT_MESH_MAX_ITEMS
-        if Nv < 1 or Nt < 1 or Nv > lim or Nt > lim:
-            raise ValueError(f"tet grid outside the supported sizes: Nv={Nv}, Nt={Nt} (1 ... {lim})")
-        lo, hi = torch.stack(indices.aminmax()).tolist()  # one read-back
-        if lo < 0 or hi >= Nv:
-            raise ValueError(f"indices holds a vertex id outside [0, {Nv})")
+        if Nv < 1 or Nt < 1:
+            raise ValueError(f"a tet grid needs a vertex and a tet: Nv={Nv}, Nt={Nt}")
+        _chk_size("tet grid too large for tt_mt_*", Nv=Nv, Nt=Nt)
+        _chk_range("indices", *_minmax(indices).tolist(), Nv)  # one read-back
         self.n_vertices, self.n_tets = Nv, Nt
-        self.vertices = vertices.contiguous()
         self.tets = indices.int().contiguous()
         pairs = indices.long()[:, list(_TET_BASE_EDGES)].reshape(-1, 2)
         key = torch.add(pairs.amax(1), pairs.amin(1), alpha=Nv)
@@ -925,14 +957,9 @@ class TetGrid:
         self.edges = torch.stack([uniq // Nv, uniq % Nv], dim=1).int().contiguous()
         self.tet_edge = inverse.reshape(Nt, 6).int().contiguous()
         Ne = self.n_edges = int(uniq.shape[0])
-        if Ne > lim:
-            raise ValueError(f"tet grid outside the supported sizes: Ne={Ne} (limit {lim})")
-        src = self.edges.long().t().reshape(-1)  # the a ends, then the b ends
-        eid = torch.arange(Ne, device=src.device).repeat(2)
-        order = torch.sort(torch.add(eid, src, alpha=Ne), stable=True)[1]
-        ptr = torch.zeros(Nv + 1, dtype=torch.int64, device=src.device)
-        ptr[1:] = torch.cumsum(torch.bincount(src, minlength=Nv), 0)
-        self.vert_ptr, self.vert_col = ptr.int().contiguous(), eid[order].int().contiguous()
+        _chk_size("tet grid too large for tt_mt_*", Ne=Ne)
+        ends = self.edges.long().t().reshape(-1)  # the a ends, then the b ends
+        self.vert_ptr, self.vert_col = _csr(ends, torch.arange(Ne, device=ends.device).repeat(2), Nv, Ne)
 
 
 class _MarchingTetsFn(torch.autograd.Function):
@@ -1042,18 +1069,11 @@ class MeshTopology:
       antialias_tables  (edge_ofs (3T,2), edge_tri (3T)) int32, as raster.edge_topology(tri, V) returns them"""
 
     def __init__(self, t_pos_idx: Tensor, n_vertices: int):
-        if not isinstance(t_pos_idx, torch.Tensor) or not t_pos_idx.is_cuda:
-            raise RuntimeError("t_pos_idx must live on the GPU (triplaneturbo_amd has no CPU path)")
-        if t_pos_idx.dtype not in (torch.int32, torch.int64) or t_pos_idx.dim() != 2 or t_pos_idx.shape[1] != 3:
-            raise TypeError(f"t_pos_idx must be (T,3) int32 / int64, got {tuple(t_pos_idx.shape)} {t_pos_idx.dtype}")
+        t_pos_idx = _chk_index(t_pos_idx, "t_pos_idx", 3)
         V, T = int(n_vertices), int(t_pos_idx.shape[0])
-        lim = 1 << 28  # TT_MESH_MAX_ITEMS
-        if V > lim or T > lim:
-            raise ValueError(f"mesh too large for tt_mesh_*: V={V}, T={T} (limit {lim})")
+        _chk_size("mesh too large for tt_mesh_*", V=V, T=T)
         self.n_vertices, self.n_faces = V, T
-        lo, hi = torch.stack(t_pos_idx.aminmax()).tolist() if T > 0 else (0, -1)  # one read-back
-        if lo < 0 or hi >= V:
-            raise ValueError(f"t_pos_idx holds an index outside [0, {V})")
+        _chk_range("t_pos_idx", *(_minmax(t_pos_idx).tolist() if T > 0 else (0, -1)), V)  # one read-back
         self.tri = t_pos_idx.int().contiguous()
         self._sort = sort_face_edges(t_pos_idx, V)
         self.edges = self._sort.edges().to(t_pos_idx.dtype).contiguous()
@@ -1074,13 +1094,8 @@ class MeshTopology:
     @cached_property
     def _nbr(self) -> Tuple[Tensor, Tensor]:
         # both directions of every unique edge, sorted by (row, column): a second stable sort
-        V = self.n_vertices
         e0, e1 = self.edges.long().unbind(1)
-        src, dst = torch.cat([e0, e1]), torch.cat([e1, e0])
-        order = torch.sort(torch.add(dst, src, alpha=max(V, 1)), stable=True)[1]
-        nbr_ptr = torch.zeros(V + 1, dtype=torch.int64, device=src.device)
-        nbr_ptr[1:] = torch.cumsum(torch.bincount(src, minlength=V), 0)
-        return nbr_ptr.int().contiguous(), dst[order].int().contiguous()
+        return _csr(torch.cat([e0, e1]), torch.cat([e1, e0]), self.n_vertices, self.n_vertices)
 
     nbr_ptr = property(lambda self: self._nbr[0])
     nbr_col = property(lambda self: self._nbr[1])
@@ -1092,13 +1107,6 @@ class MeshTopology:
 
 def mesh_topology(t_pos_idx: Tensor, n_vertices: int) -> MeshTopology:
     return MeshTopology(t_pos_idx, n_vertices)
-
-
-def _chk_mesh_attr(x: Tensor, name: str, topo: MeshTopology) -> Tensor:
-    x = _chk(x, name)
-    if x.dim() != 2 or x.shape[1] != 3 or x.shape[0] != topo.n_vertices:
-        raise ValueError(f"{name} must be ({topo.n_vertices}, 3), got {tuple(x.shape)}")
-    return x
 
 
 class _MeshLaplacianFn(torch.autograd.Function):
@@ -1127,7 +1135,7 @@ class _MeshLaplacianFn(torch.autograd.Function):
 def mesh_laplacian_loss(v_pos: Tensor, topo: MeshTopology) -> Tensor:
     """(1/V) sum_i |sum_{j in N(i), j != i} (v_i - v_j)|: threestudio Mesh.laplacian() (mesh.py:282-288) as HIP
     kernels, differentiable w.r.t. v_pos (V,3) fp32.  No host round trip, no allocation beyond the outputs."""
-    return _MeshLaplacianFn.apply(_chk_mesh_attr(v_pos, "v_pos", topo), topo)
+    return _MeshLaplacianFn.apply(_chk(v_pos, "v_pos", (topo.n_vertices, 3)), topo)
 
 
 class _MeshNormalConsistencyFn(torch.autograd.Function):
@@ -1157,7 +1165,7 @@ def mesh_normal_consistency_loss(v_nrm: Tensor, topo: MeshTopology) -> Tensor:
     """mean over the mesh edges (a,b) of 1 - cosine_similarity(n_a, n_b, eps=1e-8): threestudio
     Mesh.normal_consistency() (mesh.py:269-274) as HIP kernels, differentiable w.r.t. v_nrm (V,3) fp32 (the caller's
     autograd carries it on to v_pos)."""
-    return _MeshNormalConsistencyFn.apply(_chk_mesh_attr(v_nrm, "v_nrm", topo), topo)
+    return _MeshNormalConsistencyFn.apply(_chk(v_nrm, "v_nrm", (topo.n_vertices, 3)), topo)
 
 
 def mesh_face_components(topo: MeshTopology) -> Tensor:
@@ -1177,7 +1185,7 @@ def mesh_remove_small_components(v_pos: Tensor, t_pos_idx: Tensor, threshold, to
     faces >= threshold stay) and the vertices no kept face references.  Kept vertices and faces keep their original
     order; faces are renumbered.  Returns (v_pos', t_pos_idx') with t_pos_idx's dtype; a mesh without faces comes
     back as it is.  One 8-byte read-back."""
-    v_pos = _chk_mesh_attr(v_pos, "v_pos", topo)
+    v_pos = _chk(v_pos, "v_pos", (topo.n_vertices, 3))
     if t_pos_idx.shape != topo.tri.shape:
         raise ValueError(f"t_pos_idx {tuple(t_pos_idx.shape)} is not the topology's {tuple(topo.tri.shape)}")
     if isinstance(threshold, bool) or not isinstance(threshold, (int, float)):
@@ -1204,9 +1212,8 @@ def mesh_remove_small_components(v_pos: Tensor, t_pos_idx: Tensor, threshold, to
 
 # ---------------------------------------------------------------------------------------------------------------
 # UV atlas and texture fill (include/tt_abi.h, "UV atlas and texture fill"): the exporter's xatlas / cv2.inpaint
-UV_DEFAULT_ROUNDS = 8  # TT_UV_DEFAULT_ROUNDS
-UV_DEFAULT_TAU = 0.3  # TT_UV_DEFAULT_TAU
-UV_MAX_OVERLAP_ROUNDS = 4  # TT_UV_MAX_OVERLAP_ROUNDS
+UV_DEFAULT_ROUNDS, UV_DEFAULT_TAU = _lib.TT_UV_DEFAULT_ROUNDS, _lib.TT_UV_DEFAULT_TAU
+UV_MAX_OVERLAP_ROUNDS = _lib.TT_UV_MAX_OVERLAP_ROUNDS
 
 
 @torch.no_grad()
@@ -1221,9 +1228,7 @@ def uv_atlas(v_pos: Tensor, t_pos_idx: Tensor, topology: Optional[MeshTopology] 
     faces on a texel centre that two UV triangles cover become singleton charts and the atlas is redone; after
     max_overlap_rounds such rounds every face of a chart that still overlaps becomes a singleton.  Bit-identical from
     call to call."""
-    v_pos = _chk(v_pos.detach(), "v_pos")
-    if v_pos.dim() != 2 or v_pos.shape[1] != 3:
-        raise ValueError(f"v_pos must be (V,3), got {tuple(v_pos.shape)}")
+    v_pos = _chk(v_pos.detach(), "v_pos", (None, 3))
     V = v_pos.shape[0]
     topo = topology if topology is not None else mesh_topology(t_pos_idx, V)
     if topo.n_vertices != V or tuple(topo.tri.shape) != tuple(t_pos_idx.shape):
@@ -1253,7 +1258,7 @@ def uv_atlas(v_pos: Tensor, t_pos_idx: Tensor, topology: Optional[MeshTopology] 
         off_h = torch.empty((C, 2), dtype=torch.int32)
         scale_h = torch.zeros(1, dtype=torch.float32)
         st = _lib.load().tt_uv_pack(_ptr(box_h), C, N, pad, _ptr(off_h), _ptr(scale_h))  # on the host: no stream
-        if st == -2:  # TT_ERR_UNSUPPORTED
+        if st == _lib.TT_ERR_UNSUPPORTED:
             raise RuntimeError(f"uv_atlas: {C} charts do not fit a {N}^2 atlas with padding {pad} (every chart box is at "
                                f"least {2 * pad + 1}^2 texels): use a larger texture_size or a smaller padding")
         _lib.check(st, "tt_uv_pack")
@@ -1287,9 +1292,7 @@ def texture_fill(img: Tensor, mask: Tensor) -> Tensor:
     True texel (jump flooding, tt_tex_fill); True texels come back bit for bit.  The exporter's stand-in for
     cv2.inpaint(TELEA) (multiprompt_mesh_exporter.py:96-107).  A (H,W) image is filled as one channel."""
     squeeze = img.dim() == 2
-    x = _chk((img[..., None] if squeeze else img).detach(), "img")
-    if x.dim() != 3:
-        raise ValueError(f"img must be (H,W) or (H,W,C), got {tuple(img.shape)}")
+    x = _chk((img[..., None] if squeeze else img).detach(), "img", (None, None, None))  # (H,W) came in as (H,W,1)
     H, W, C = x.shape
     if not isinstance(mask, torch.Tensor) or not mask.is_cuda or tuple(mask.shape) != (H, W):
         raise ValueError(f"mask must be a GPU tensor of shape {(H, W)}")
@@ -1330,30 +1333,19 @@ def mesh_simplify(v_pos: Tensor, t_pos_idx: Tensor, grid: int, lam: float = SIMP
     lam = float(lam)
     if not 0.0 <= lam <= 1e300:
         raise ValueError(f"lam must be a finite number >= 0, got {lam}")
-    if not isinstance(v_pos, torch.Tensor) or v_pos.dim() != 2 or v_pos.shape[1] != 3:
-        raise ValueError("v_pos must be a (V,3) tensor")
-    if not isinstance(t_pos_idx, torch.Tensor) or t_pos_idx.dim() != 2 or t_pos_idx.shape[1] != 3:
-        raise ValueError("t_pos_idx must be a (T,3) tensor")
-    if t_pos_idx.dtype not in (torch.int32, torch.int64):
-        raise TypeError(f"t_pos_idx must be int32 / int64, got {t_pos_idx.dtype}")
-    V, T = v_pos.shape[0], t_pos_idx.shape[0]
-    v_pos = v_pos.detach()
-    if V == 0 or T == 0:
-        return _simplify_unchanged(v_pos, t_pos_idx, grid, 0.0)
-    v_pos = _chk(v_pos, "v_pos")
-    if not t_pos_idx.is_cuda or t_pos_idx.device != v_pos.device:
-        raise RuntimeError("t_pos_idx must live on the GPU of v_pos")
-    lim = 1 << 28  # TT_MESH_MAX_ITEMS
-    if V > lim or T > lim:
-        raise ValueError(f"mesh too large for tt_simplify_*: V={V}, T={T} (limit {lim})")
-    dev = v_pos.device
+    if (isinstance(v_pos, Tensor) and isinstance(t_pos_idx, Tensor) and v_pos.shape[1:] == t_pos_idx.shape[1:] == (3,)
+            and t_pos_idx.dtype in (torch.int32, torch.int64) and 0 in (v_pos.shape[0], t_pos_idx.shape[0])):
+        return _simplify_unchanged(v_pos.detach(), t_pos_idx, grid, 0.0)  # an empty mesh, wherever it lives
+    v_pos = _chk(v_pos, "v_pos", (None, 3)).detach()
+    t_pos_idx = _chk_index(t_pos_idx, "t_pos_idx", 3)
+    V, T, dev = v_pos.shape[0], t_pos_idx.shape[0], v_pos.device
+    _chk_size("mesh too large for tt_simplify_*", V=V, T=T)
     # the box in fp32: minima, maxima and their difference on the device, the two divisions in IEEE fp32 on the host
     lo_t = v_pos.amin(0)
     box = torch.cat([lo_t.double(), (v_pos.amax(0) - lo_t).amax().reshape(1).double(),
-                     torch.stack(t_pos_idx.aminmax()).double()]).cpu()  # one read-back; every value exact in double
+                     _minmax(t_pos_idx).double()]).cpu()  # one read-back; every value exact in double
     lo, ext = box[:3].float().numpy(), box[3].float().numpy()
-    if box[4] < 0 or box[5] >= V:
-        raise ValueError(f"t_pos_idx holds an index outside [0, {V})")
+    _chk_range("t_pos_idx", int(box[4]), int(box[5]), V)
     if not bool(torch.isfinite(box[:4]).all()):
         raise ValueError("v_pos holds a value that is not finite")
     if ext == 0:
@@ -1400,16 +1392,6 @@ def mesh_simplify(v_pos: Tensor, t_pos_idx: Tensor, grid: int, lam: float = SIMP
 _BAKE_GROUPS = {"pos": _lib.TT_BAKE_GROUP_POS, "tex": _lib.TT_BAKE_GROUP_TEX}
 
 
-def _chk_faces(t: Tensor, name: str, T: Optional[int], dev) -> Tensor:
-    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != 3 or t.dtype not in (torch.int32, torch.int64):
-        raise TypeError(f"{name} must be a (T,3) int32 / int64 tensor")
-    if not t.is_cuda or t.device != dev:
-        raise RuntimeError(f"{name} must live on the GPU of v_pos")
-    if T is not None and t.shape[0] != T:
-        raise ValueError(f"{name} has {t.shape[0]} faces, t_pos_idx has {T}")
-    return t
-
-
 @torch.no_grad()
 def mesh_tangents(v_pos: Tensor, t_pos_idx: Tensor, v_tex: Tensor, t_tex_idx: Tensor, v_nrm: Tensor,
                   group: str = "pos") -> Tensor:
@@ -1423,37 +1405,27 @@ def mesh_tangents(v_pos: Tensor, t_pos_idx: Tensor, v_tex: Tensor, t_tex_idx: Te
     result is bit-identical from call to call.  Inputs are detached; the result never requires grad."""
     if group not in _BAKE_GROUPS:
         raise ValueError(f"group must be 'pos' or 'tex', got {group!r}")
-    v_pos = _chk(v_pos.detach(), "v_pos")
-    if v_pos.dim() != 2 or v_pos.shape[1] != 3:
-        raise ValueError(f"v_pos must be (V,3), got {tuple(v_pos.shape)}")
+    v_pos = _chk(v_pos.detach(), "v_pos", (None, 3))
     V, dev = v_pos.shape[0], v_pos.device
     v_nrm = _chk(v_nrm.detach(), "v_nrm", (V, 3))
-    v_tex = _chk(v_tex.detach(), "v_tex")
-    if v_tex.dim() != 2 or v_tex.shape[1] != 2:
-        raise ValueError(f"v_tex must be (Vt,2), got {tuple(v_tex.shape)}")
+    v_tex = _chk(v_tex.detach(), "v_tex", (None, 2))
     Vt = v_tex.shape[0]
-    t_pos_idx = _chk_faces(t_pos_idx, "t_pos_idx", None, dev)
+    t_pos_idx = _chk_index(t_pos_idx, "t_pos_idx", 3)
     T = t_pos_idx.shape[0]
-    t_tex_idx = _chk_faces(t_tex_idx, "t_tex_idx", T, dev)
-    lim = 1 << 28  # TT_MESH_MAX_ITEMS
-    if max(V, Vt, T) > lim:
-        raise ValueError(f"mesh too large for tt_bake_tangents: V={V}, Vt={Vt}, T={T} (limit {lim})")
+    t_tex_idx = _chk_index(t_tex_idx, "t_tex_idx", 3, T)
+    _chk_size("mesh too large for tt_bake_tangents", V=V, Vt=Vt, T=T)
     G = Vt if group == "tex" else V
     out = torch.empty((G, 3), device=dev, dtype=torch.float32)
     if G == 0:
         return out
     if T > 0:
-        rng = torch.stack(t_pos_idx.aminmax() + t_tex_idx.aminmax()).tolist()  # one read-back
-        if rng[0] < 0 or rng[1] >= V:
-            raise ValueError(f"t_pos_idx holds an index outside [0, {V})")
-        if rng[2] < 0 or rng[3] >= Vt:
-            raise ValueError(f"t_tex_idx holds an index outside [0, {Vt})")
+        rng = _minmax(t_pos_idx, t_tex_idx).tolist()  # one read-back
+        _chk_range("t_pos_idx", *rng[:2], V)
+        _chk_range("t_tex_idx", *rng[2:], Vt)
     key = (t_tex_idx if group == "tex" else t_pos_idx).reshape(-1).long()
-    corner = torch.sort(key, stable=True)[1].int().contiguous()  # corner ids 3f + k by (group, corner id)
-    ptr = torch.zeros(G + 1, device=dev, dtype=torch.int64)
-    ptr[1:] = torch.cumsum(torch.bincount(key, minlength=G), 0)
+    ptr, corner = _csr(key, None, G, 3 * T)  # corner ids 3f + k by (group, corner id)
     _launch("tt_bake_tangents", v_pos, t_pos_idx.int().contiguous(), v_tex, t_tex_idx.int().contiguous(), v_nrm,
-            ptr.int().contiguous(), corner, V, Vt, T, _BAKE_GROUPS[group], out, label="bake_tangents")
+            ptr, corner, V, Vt, T, _BAKE_GROUPS[group], out, label="bake_tangents")
     return out
 
 
@@ -1463,9 +1435,7 @@ def bake_project_step(points: Tensor, sdf: Tensor, sdf_grad: Tensor, max_step: f
     """One bounded Newton step of `points` (M,3) towards the iso-surface, in place (tt_bake_project): p -= c g with
     c = clamp(sdf / max(|g|^2, 1e-12), -1, 1), scaled down so that the step is no longer than max_step.  sdf (M) or
     (M,1) and sdf_grad (M,3) are the field's values at the points; a point with mask (M) == 0 stays.  Returns points."""
-    points = _chk(points, "points")
-    if points.dim() != 2 or points.shape[1] != 3:
-        raise ValueError(f"points must be (M,3), got {tuple(points.shape)}")
+    points = _chk(points, "points", (None, 3))
     M = points.shape[0]
     sdf = _chk(sdf.detach().reshape(-1), "sdf", (M,))
     sdf_grad = _chk(sdf_grad.detach().reshape(-1, 3), "sdf_grad", (M, 3))
@@ -1488,18 +1458,14 @@ def bake_encode(rast: Tensor, v_nrm: Tensor, t_pos_idx: Tensor, tng_tex: Tensor,
     the field normal field_nrm (H,W,3) (any length; normalised inside) in the frame (t^, b^ = t^ x n^, n^) interpolated
     from tng_tex (Vt,3) and v_nrm (V,3), as 0.5 + 0.5 x; uncovered texels are (0.5, 0.5, 1).  Returns (map (H,W,3),
     counts (2,) int32 on the device = covered texels, covered texels whose field normal points into the face)."""
-    rast = _chk(rast, "rast")
-    if rast.dim() != 3 or rast.shape[2] != 4:
-        raise ValueError(f"rast must be (H,W,4), got {tuple(rast.shape)}")
+    rast = _chk(rast, "rast", (None, None, 4))
     H, W = rast.shape[:2]
-    v_nrm = _chk(v_nrm.detach(), "v_nrm")
-    tng_tex = _chk(tng_tex.detach(), "tng_tex")
-    if v_nrm.dim() != 2 or v_nrm.shape[1] != 3 or tng_tex.dim() != 2 or tng_tex.shape[1] != 3:
-        raise ValueError("v_nrm must be (V,3) and tng_tex (Vt,3)")
+    v_nrm = _chk(v_nrm.detach(), "v_nrm", (None, 3))
+    tng_tex = _chk(tng_tex.detach(), "tng_tex", (None, 3))
     field_nrm = _chk(field_nrm.detach(), "field_nrm", (H, W, 3))
-    t_pos_idx = _chk_faces(t_pos_idx, "t_pos_idx", None, rast.device)
+    t_pos_idx = _chk_index(t_pos_idx, "t_pos_idx", 3)
     T = t_pos_idx.shape[0]
-    t_tex_idx = _chk_faces(t_tex_idx, "t_tex_idx", T, rast.device)
+    t_tex_idx = _chk_index(t_tex_idx, "t_tex_idx", 3, T)
     out = torch.empty((H, W, 3), device=rast.device, dtype=torch.float32)
     counts = torch.empty(2, device=rast.device, dtype=torch.int32)
     _launch("tt_bake_encode", rast, v_nrm, t_pos_idx.int().contiguous(), tng_tex, t_tex_idx.int().contiguous(),

@@ -33,23 +33,14 @@ from . import _lib
 from .ops import _chk, _launch, _workspace, sort_face_edges
 
 Tensor = torch.Tensor
-MAX_TRIS = 1 << 24  # TT_RAST_MAX_TRIS: tri + 1 is stored as a float
+MAX_TRIS = _lib.TT_RAST_MAX_TRIS  # tri + 1 is stored as a float
 
 
 def _check_tri(tri: Tensor) -> Tensor:
-    tri = _chk(tri, "tri", dtype=torch.int32)
-    if tri.dim() != 2 or tri.shape[1] != 3:
-        raise ValueError(f"tri must be (T,3), got {tuple(tri.shape)}")
+    tri = _chk(tri, "tri", (None, 3), torch.int32)
     if tri.shape[0] >= MAX_TRIS:
         raise ValueError(f"{tri.shape[0]} triangles: at most {MAX_TRIS - 1} (the id channel is a float)")
     return tri
-
-
-def _check_rast(rast: Tensor) -> Tensor:
-    rast = _chk(rast, "rast")
-    if rast.dim() != 4 or rast.shape[-1] != 4:
-        raise ValueError(f"rast must be (B,H,W,4), got {tuple(rast.shape)}")
-    return rast
 
 
 def edge_topology(tri: Tensor, n_vertices: Optional[int] = None) -> Tuple[Tensor, Tensor]:
@@ -173,7 +164,7 @@ def interpolate(attr: Tensor, rast: Tensor, tri: Tensor, rast_db=None, diff_attr
     if rast_db is not None or diff_attrs is not None:
         raise NotImplementedError("rast_db / diff_attrs (attribute derivatives for mip texturing) are not supported")
     attr = _chk(attr, "attr")
-    rast = _check_rast(rast)
+    rast = _chk(rast, "rast", (None, None, None, 4))
     if attr.dim() == 2:
         attr = attr[None]
     if attr.dim() != 3 or attr.shape[0] not in (1, rast.shape[0]) or attr.shape[2] < 1:
@@ -233,9 +224,7 @@ def texture(tex: Tensor, uv: Tensor, filter_mode: str = "linear", boundary_mode:
     if boundary_mode not in _TEX_BOUNDARIES:
         raise ValueError(f"boundary_mode must be one of {sorted(_TEX_BOUNDARIES)}, got {boundary_mode!r}")
     tex = _chk(tex, "tex")
-    uv = _chk(uv, "uv")
-    if uv.dim() != 4 or uv.shape[-1] != 2:
-        raise ValueError(f"uv must be (B,H,W,2), got {tuple(uv.shape)}")
+    uv = _chk(uv, "uv", (None, None, None, 2))
     if tex.dim() != 4 or tex.shape[0] not in (1, uv.shape[0]) or min(tex.shape[1:]) < 1:
         raise ValueError(f"tex must be (B,TH,TW,C) or (1,TH,TW,C) with TH, TW, C >= 1, got {tuple(tex.shape)} for "
                          f"B={uv.shape[0]}")
@@ -275,7 +264,7 @@ def antialias(color: Tensor, rast: Tensor, pos: Tensor, tri: Tensor,
     = edge_topology(tri), computed here when not given.  Range mode: pos (V,4), rast from rasterize(pos, tri, ranges=..);
     the topology is that of the whole tri, so only meshes that share vertices see each other's edges."""
     color = _chk(color, "color")
-    rast = _check_rast(rast)
+    rast = _chk(rast, "rast", (None, None, None, 4))
     pos = _chk(pos, "pos")
     tri = _check_tri(tri)
     if color.dim() != 4 or tuple(color.shape[:3]) != tuple(rast.shape[:3]):
