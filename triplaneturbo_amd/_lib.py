@@ -33,10 +33,25 @@ SOURCES = ["tt_forward.hip", "tt_march.hip", "tt_backward.hip", "tt_backward_tex
 # profiles/experiments/README.md
 # Round 6 (dense-rank scatter): the texture unit is now faster WITHOUT max-ILP and, like the geometry unit, without the
 # register-pressure rescheduling stage (same-box A/B, texture backward 3.36 max-ilp / 3.32 no flags / 3.30 this).
-SOURCE_FLAGS = {"tt_backward_tex.hip": ["-mllvm", "-amdgpu-disable-unclustered-high-rp-reschedule"],
+# Register-form scatter operand: the texture unit now takes -amdgpu-mfma-vgpr-form as well -- with ebar^T
+# held in registers across the three planes it spills 28-30 registers without the flag and none with it, and it is the
+# faster setting on the parent's code too (same-box A/B 3.274 / 3.243 ms without / with: profiles/scatter_regs_ab.txt).
+SOURCE_FLAGS = {"tt_backward_tex.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form",
+                                        "-mllvm", "-amdgpu-disable-unclustered-high-rp-reschedule"],
                 "tt_backward.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form",
                                     "-mllvm", "-amdgpu-disable-unclustered-high-rp-reschedule"]}
+# the -DTT_TUNING build only: with -amdgpu-mfma-vgpr-form hipcc (ROCm 7.2) crashes in its AGPR-copy rewrite pass on the
+# texture unit's phase-timer + STATS instantiation (the pass that removes spills of reassigned registers: the product
+# build's split-mode instantiations have none), so the tuning build keeps that unit's earlier flags
+TUNING_SOURCE_FLAGS = {"tt_backward_tex.hip": ["-mllvm", "-amdgpu-disable-unclustered-high-rp-reschedule"]}
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-munsafe-fp-atomics", "-fPIC", "-shared", "-fno-gpu-rdc"]
+
+def _unit_flags(tuning: bool, source_flags: Optional[dict]) -> dict:
+    """Per-translation-unit flags of a build: `source_flags` if given (dev A/B), else SOURCE_FLAGS (+ the tuning build's)."""
+    if source_flags is not None:
+        return dict(source_flags)
+    return dict(SOURCE_FLAGS, **TUNING_SOURCE_FLAGS) if tuning else dict(SOURCE_FLAGS)
+
 
 def _sources() -> List[str]:
     return [os.path.join(CSRC, s) for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
@@ -64,7 +79,7 @@ def source_hash(tuning: bool = False, defines: Optional[List[str]] = None, sourc
         h.update(os.path.basename(d).encode() + b"\0")
         h.update(open(d, "rb").read())
         h.update(b"\0")
-    flags = dict(SOURCE_FLAGS if source_flags is None else source_flags)
+    flags = _unit_flags(tuning, source_flags)
     h.update(repr((HIPCC_FLAGS, sorted(flags.items()), bool(tuning), list(defines or []))).encode())
     return h.hexdigest()
 
@@ -161,7 +176,7 @@ def _build_locked(out: str, objdir: str, verbose: bool, tuning: bool, defines: O
     procs = []
     for s in _sources():
         obj = os.path.join(objdir, os.path.basename(s) + ".o")
-        per_unit = _usable_flags(hipcc, (SOURCE_FLAGS if source_flags is None else source_flags).get(os.path.basename(s), []))
+        per_unit = _usable_flags(hipcc, _unit_flags(tuning, source_flags).get(os.path.basename(s), []))
         cmd = [hipcc] + flags + per_unit + ["-I", INCLUDE, "-I", CSRC, "-x", "hip", "-c", s, "-o", obj]
         if verbose:
             print(" ".join(cmd))

@@ -241,9 +241,13 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
             }
 #pragma unroll
             for (int r = 0; r < 32; ++r) a1[r] = h1[r] > 0.f ? a1[r] : 0.f;
+            // q = W1^T a1 has one consumer, the scatter, which wants it as the B operand of its combine GEMM: the split modes
+            // form q^T (lane <-> channel, register <-> sample, raw accumulators; uq = the factor) by swapping the MFMA's two
+            // arguments -- one tile for the three planes (tt_backward_common.h, sc2_regs_b)
+            float uq = 1.f;
             if (WG16) {
                 split16_vec<64, PAIR_SEQ, NT>(a1, sA1 * ua1, a1s);
-                mv16_pre(L, typename G::W1T{}, a1s, 1.f / sA1, q, i, hi);
+                mv16_pre<true, true>(L, typename G::W1T{}, a1s, 1.f / sA1, q, i, hi, &uq);
             } else {
                 mvtx_copy<PREC>(L, typename G::W1T{}, typename G::W1{}, a1, q, i, hi);
             }
@@ -295,7 +299,9 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
                 // ---- scatter d/d geometry planes: texel(p,c)[ch] += q[ch] * coef(p,c) ----
                 if (region && !TT_DBG(cfg.flags, TT_DBG_NO_SCATTER)) {
                     scatter_clear<EXACT>(Xs, lane);  // M = 0 (Xs held wgrad staging; SCATTER_M_FLOATS reach into Ys)
-                    float* Qs = Xs + SCATTER_M_FLOATS;  // the sample's row of Q: q scaled per plane, stride 33
+                    // rows of Q, q scaled per plane, stride 33: the fp32 form's B operand; the register form writes them for a
+                    // plane's lost references only
+                    float* Qs = Xs + SCATTER_M_FLOATS;
                     TT_PHASE(9);
                     const int tex0 = (int)(pofs / TT_C);
                     auto prep = [&](int pl, PlaneRefs& refs) {
@@ -306,8 +312,21 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
 #pragma unroll
                         for (int q4 = 0; q4 < 4; ++q4) aoff[q4] = tex0 + (int)(pl * HW) + c.off[q4];
                         refs = plane_refs<!EXACT>(coef, aoff, c.hs, hi);
+                        if constexpr (EXACT) {
 #pragma unroll
-                        for (int r = 0; r < 16; ++r) Qs[i * 33 + LIDX(r, hi)] = q[r] * refs.qs;
+                            for (int r = 0; r < 16; ++r) Qs[i * 33 + LIDX(r, hi)] = q[r] * refs.qs;
+                        } else {  // the sample's factor for the lanes that hold its q^T (both half-waves: the same value)
+                            sc2_factor_table(tags, pl)[i] = uq * refs.qs;
+                        }
+                    };
+                    auto load_b = [&](int pl, auto& B) {
+                        if constexpr (EXACT)
+                            sc2_load_b(Qs, i, hi, B);
+                        else
+                            sc2_regs_b(q, sc2_factor_table(tags, pl), hi, B);
+                    };
+                    auto stage_q = [&](int pl) {  // rows of Q for a plane's lost references (fp32 form: staged by prep)
+                        if constexpr (!EXACT) sc2_regs_stage_q(q, sc2_factor_table(tags, pl), Qs, i, hi);
                     };
 #ifdef TT_TUNING
                     unsigned long long* const sc_st = ph_acc + 14;
@@ -316,9 +335,10 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
 #endif
                     if (one)
                         scatter_one_plane<EXACT>(grad_out, grad_bytes, Qs, Xs, tags, Qs + 32 * 33, i, hi,
-                                                 single_plane_index(pmask), prep, sc_st);
+                                                 single_plane_index(pmask), prep, load_b, stage_q, sc_st);
                     else
-                        scatter_planes<EXACT>(grad_out, grad_bytes, Qs, Xs, tags, Qs + 32 * 33, i, hi, prep, sc_st);
+                        scatter_planes<EXACT>(grad_out, grad_bytes, Qs, Xs, tags, Qs + 32 * 33, i, hi, prep, load_b, stage_q,
+                                              sc_st);
                     TT_PHASE(10);
                 }
             }

@@ -354,8 +354,10 @@ __device__ __forceinline__ void scatter_clear(float* M, int lane) {
 }
 
 // LDS per wave: M = 64 rows + 1 dump row (stride MS), and SCATTER_TAG_INTS ints of which the first 32 are the dummy words
-// (scatter_init_tags; the rest is unused since the texel table moved behind the lost-reference lists).
+// (scatter_init_tags) and the next 96 the three planes' factor tables of the register-form B operand (sc2_regs_b: 32 floats
+// per plane, 16-byte aligned; the rest is unused since the texel table moved behind the lost-reference lists).
 #define SCATTER_TAG_INTS 160
+__device__ __forceinline__ float* sc2_factor_table(int* tags, int pl) { return reinterpret_cast<float*>(tags + 32) + 32 * pl; }
 
 struct PlaneRefs {  // the two corners (2hi, 2hi+1) of this lane's sample in one plane
     float c0, c1;   // coefficient (0: no reference), normalised per sample unless EXACT
@@ -392,7 +394,16 @@ __device__ __forceinline__ void scatter_init_tags(int* tags, int lane) {
     if (lane < 32) tags[lane] = -2;  // the dummy words inactive references CAS: never empty, never equal to a texel index
 }
 
-// store / clear one coefficient of M (column i = this lane's sample; row 64 = dump row)
+// Column of M that sample s goes to.  fp32 matrix (EXACT): s itself.  Split-fp16 image: bits 2 and 3 of s exchanged -- the
+// order in which the B operand comes out of the TRANSPOSED last product (tt_mfma16.h, SWAP): k-slot j of k-step ks of lane
+// (ch, hi) is register 8 ks + j of that product = sample 16 ks + 8 (j >> 2) + 4 hi + (j & 3), and sc2_load_a hands the same
+// slot the column 16 ks + 8 hi + j.  A permutation of the 32 samples inside the reduction: M Q is the same sum, added by the
+// MFMA in another order (fp32 rounding of the sum only).
+template <bool EXACT>
+__device__ __forceinline__ int sc2_col(int s) {
+    return EXACT ? s : ((s & ~12) | ((s & 4) << 1) | ((s & 8) >> 1));
+}
+// store / clear one coefficient of M (column i = sc2_col of this lane's sample; row 64 = dump row)
 template <bool EXACT>
 __device__ __forceinline__ void m_store(float* M, int row, int i, float c) {
     if (EXACT) {
@@ -417,12 +428,16 @@ __device__ __forceinline__ void m_zero(float* M, int row, int i) {
 }
 
 // references that lost their table entry (tile footprint wider than the texel table: sparse rays) go straight to global
-// memory, one half-wave per reference (lanes <-> channels: a coalesced 128-byte atomic each)
+// memory, one half-wave per reference (lanes <-> channels: a coalesced 128-byte atomic each).
+// stage_q(): called (wave-uniformly) only when the plane has a lost reference, before Qs is read -- the register form of
+// the B operand writes its [sample][33] rows of Q there and then, so the common case never stages them.
+template <class StageQ>
 __device__ __forceinline__ void scatter_lost(const PlaneRefs& r, bool l0, bool l1, const float* Qs, float* Ls,
-                                             __amdgpu_buffer_rsrc_t grsrc, int i, int hi) {
+                                             __amdgpu_buffer_rsrc_t grsrc, int i, int hi, StageQ&& stage_q) {
     const float lc0 = l0 ? r.c0 : 0.f, lc1 = l1 ? r.c1 : 0.f;  // coefficient of a lost corner, else 0
     const unsigned long long bal = __ballot(__builtin_fabsf(lc0) + __builtin_fabsf(lc1) != 0.f);
     if (bal == 0) return;
+    stage_q();
     float* Lc = Ls;                                 // [sample][4] coefficient of a lost corner, else 0
     int* Lo = reinterpret_cast<int*>(Ls + 32 * 4);  // [sample][4] absolute texel index
     Lc[4 * i + 2 * hi] = lc0;
@@ -582,6 +597,27 @@ __device__ __forceinline__ void sc2_load_b(const float* Qs, int i, int hi, ScB32
 #pragma unroll
     for (int t = 0; t < 16; ++t) B.bq[t] = Qs[(t + 16 * hi) * 33 + i];
 }
+// The B operand straight from the registers of the transposed last product (qt[16]: lane (ch, hi), register r <-> sample
+// (r&3) + 8(r>>2) + 4hi; raw accumulators) and the plane's factor table T[32] (per sample: the product's deferred factor
+// times refs.qs, both powers of two, written by the lane that owns the sample): four broadcast ds_read_b128 and 16
+// multiplies give the numbers the LDS round trip through Qs gave.  M's columns are in the matching order (sc2_col).
+__device__ __forceinline__ void sc2_regs_b(const float* qt, const float* T, int hi, ScB16& B) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const f32x4 t4 = *reinterpret_cast<const f32x4*>(T + 8 * g + 4 * hi);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) B.bs[g >> 1][4 * (g & 1) + e] = qt[4 * g + e] * t4[e];
+    }
+}
+// ... and the [sample][33] rows of Q that scatter_lost reads, from the same registers (16 conflict-free stores)
+__device__ __forceinline__ void sc2_regs_stage_q(const float* qt, const float* T, float* Qs, int i, int hi) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const f32x4 t4 = *reinterpret_cast<const f32x4*>(T + 8 * g + 4 * hi);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) Qs[LIDX(4 * g + e, hi) * 33 + i] = qt[4 * g + e] * t4[e];
+    }
+}
 __device__ __forceinline__ void sc2_split_b(ScB32&) {}
 // per-channel normalisation of the B operand to the top of the fp16 range (column = this lane and lane ^ 32) + split
 __device__ __forceinline__ void sc2_split_b(ScB16& B) {
@@ -667,16 +703,19 @@ __device__ __forceinline__ void sc2_flush(const f32x16& acc0, const f32x16& acc1
     }
 }
 
-// prep(pl, refs): corner set-up of plane pl for this lane's sample AND the staging of its row of Q, scaled by refs.qs,
-// into Qs[j*33 + ch] (the previous plane's B operand is in registers by then).  M: all-zero on entry and on exit.
+// prep(pl, refs): corner set-up of plane pl for this lane's sample AND what hands the sample's factor to the B operand:
+//   fp32 form: the staging of its row of Q, scaled by refs.qs, into Qs[j*33 + ch] (the previous plane's B operand is in
+//   registers by then);  register form: one store of the sample's factor into the plane's table (sc2_regs_b).
+// load_b(pl, B): the B operand of plane pl (sc2_load_b from Qs / sc2_regs_b).  stage_q(pl): writes plane pl's rows of Q to
+// Qs for scatter_lost (register form; the fp32 form has them there already).  M: all-zero on entry and on exit.
 // tags: the 32 dummy words (scatter_init_tags).  Ls: 256 floats of lost-reference lists, followed by SC2_INTS ints.
 // Pipeline per plane p:  operands A(p) -> registers, M rows back to zero, [n > 64: rows of pass B -> M]; prep(p+1);
 //   GEMM A(p); [pass B: flush A(p), operands B(p) -> registers, M back to zero]; claims + ranks(p+1), lost references of
 //   p+1 (under the MFMAs); [pass B: GEMM B(p), flush B(p) | else: flush A(p)]; rows of pass A(p+1) -> M.
-template <bool EXACT, class Prep>
+template <bool EXACT, class Prep, class LoadB, class StageQ>
 __device__ __forceinline__ void scatter_planes(float* __restrict__ grad, unsigned grad_bytes, const float* Qs, float* M,
-                                               int* tags, float* Ls, int i, int hi, Prep&& prep,
-                                               unsigned long long* st = nullptr) {
+                                               int* tags, float* Ls, int i, int hi, Prep&& prep, LoadB&& load_b,
+                                               StageQ&& stage_q, unsigned long long* st = nullptr) {
     // BUFFER atomics with a 32-bit BYTE offset (texel << 7 | channel * 4) from the gradient copy: a tag of -1 gives the
     // offset 0xFFFFFF80 + 4 ch, beyond num_records (the host refuses gradient buffers of 4 GB - 256 B and more), and the
     // hardware range check drops the atomic -- no compare, no exec-mask branch per row.
@@ -710,13 +749,14 @@ __device__ __forceinline__ void scatter_planes(float* __restrict__ grad, unsigne
         const i32x4 e4 = {-1, -1, -1, -1};
         *reinterpret_cast<i32x4*>(htab + 4 * lane) = e4;
     }
+    const int mc = sc2_col<EXACT>(i);  // this lane's column of M
     PlaneRefs rc, rn;
     Sc2State sc, sn;
     prep(0, rc);
     sc = sc2_claim_rank(rc, htab, ctag, cdump, dummy, lane, st);
-    scatter_lost(rc, sc.l0, sc.l1, Qs, Ls, grsrc, i, hi);
-    m_store<EXACT>(M, sc2_row_a(sc.rx0), i, rc.c0);
-    m_store<EXACT>(M, sc2_row_a(sc.rx1), i, rc.c1);
+    scatter_lost(rc, sc.l0, sc.l1, Qs, Ls, grsrc, i, hi, [&]() { stage_q(0); });
+    m_store<EXACT>(M, sc2_row_a(sc.rx0), mc, rc.c0);
+    m_store<EXACT>(M, sc2_row_a(sc.rx1), mc, rc.c1);
 #pragma unroll
     for (int pl = 0; pl < 3; ++pl) {
         const int* const ct = ctag + SC2_CT * (pl & 1);
@@ -726,13 +766,13 @@ __device__ __forceinline__ void scatter_planes(float* __restrict__ grad, unsigne
         AOp A;
         BOp B;
         sc2_load_a(M, i, hi, sc.n, A);
-        m_zero<EXACT>(M, sc2_row_a(sc.rx0), i);
-        m_zero<EXACT>(M, sc2_row_a(sc.rx1), i);
+        m_zero<EXACT>(M, sc2_row_a(sc.rx0), mc);
+        m_zero<EXACT>(M, sc2_row_a(sc.rx1), mc);
         if (pass_b) {
-            m_store<EXACT>(M, sc2_row_b(sc.rx0), i, rc.c0);
-            m_store<EXACT>(M, sc2_row_b(sc.rx1), i, rc.c1);
+            m_store<EXACT>(M, sc2_row_b(sc.rx0), mc, rc.c0);
+            m_store<EXACT>(M, sc2_row_b(sc.rx1), mc, rc.c1);
         }
-        sc2_load_b(Qs, i, hi, B);
+        load_b(pl, B);
         if (pl < 2) prep(pl + 1, rn);
         sc2_split_b(B);
         sc2_gemm(A, B, sc.n, acc0, acc1);
@@ -740,8 +780,8 @@ __device__ __forceinline__ void scatter_planes(float* __restrict__ grad, unsigne
         if (pass_b) {  // (rare on dense rays: the first pass is flushed before the next plane's claims)
             sc2_flush(acc0, acc1, ct, 64, grsrc, lane_b, hi);
             sc2_load_a(M, i, hi, sc.n - 64, A);
-            m_zero<EXACT>(M, sc2_row_b(sc.rx0), i);
-            m_zero<EXACT>(M, sc2_row_b(sc.rx1), i);
+            m_zero<EXACT>(M, sc2_row_b(sc.rx0), mc);
+            m_zero<EXACT>(M, sc2_row_b(sc.rx1), mc);
         }
         if (pl < 2) sn = sc2_claim_rank(rn, htab, ct_next, cdump, dummy, lane, st);
         TT_SUBPHASE(4);
@@ -752,9 +792,9 @@ __device__ __forceinline__ void scatter_planes(float* __restrict__ grad, unsigne
             sc2_flush(acc0, acc1, ct, sc.n, grsrc, lane_b, hi);
         }
         if (pl < 2) {
-            scatter_lost(rn, sn.l0, sn.l1, Qs, Ls, grsrc, i, hi);
-            m_store<EXACT>(M, sc2_row_a(sn.rx0), i, rn.c0);
-            m_store<EXACT>(M, sc2_row_a(sn.rx1), i, rn.c1);
+            scatter_lost(rn, sn.l0, sn.l1, Qs, Ls, grsrc, i, hi, [&]() { stage_q(pl + 1); });
+            m_store<EXACT>(M, sc2_row_a(sn.rx0), mc, rn.c0);
+            m_store<EXACT>(M, sc2_row_a(sn.rx1), mc, rn.c1);
             rc = rn;
             sc = sn;
         }
@@ -768,10 +808,10 @@ __device__ __forceinline__ void scatter_planes(float* __restrict__ grad, unsigne
 // their plain order: prep, claims + ranks, lost references, rows -> M; operands -> registers, M back to zero; GEMM; flush
 // (and the second 64-row pass when n > 64).  Same arguments and the same state on exit as scatter_planes: M all-zero, the
 // table empty, the dummy words <= -2.
-template <bool EXACT, class Prep>
+template <bool EXACT, class Prep, class LoadB, class StageQ>
 __device__ __forceinline__ void scatter_one_plane(float* __restrict__ grad, unsigned grad_bytes, const float* Qs, float* M,
-                                                  int* tags, float* Ls, int i, int hi, int pl, Prep&& prep,
-                                                  unsigned long long* st = nullptr) {
+                                                  int* tags, float* Ls, int i, int hi, int pl, Prep&& prep, LoadB&& load_b,
+                                                  StageQ&& stage_q, unsigned long long* st = nullptr) {
     const __amdgpu_buffer_rsrc_t grsrc = __builtin_amdgcn_make_buffer_rsrc(grad, 0, (int)grad_bytes, 0x00020000);
     const unsigned lane_b = 4u * (unsigned)i;
     const int lane = i + 32 * hi;
@@ -785,29 +825,30 @@ __device__ __forceinline__ void scatter_one_plane(float* __restrict__ grad, unsi
         const i32x4 e4 = {-1, -1, -1, -1};
         *reinterpret_cast<i32x4*>(htab + 4 * lane) = e4;
     }
+    const int mc = sc2_col<EXACT>(i);  // this lane's column of M
     PlaneRefs rc;
     prep(pl, rc);
     const Sc2State sc = sc2_claim_rank(rc, htab, ct, cdump, dummy, lane, st);
-    scatter_lost(rc, sc.l0, sc.l1, Qs, Ls, grsrc, i, hi);
-    m_store<EXACT>(M, sc2_row_a(sc.rx0), i, rc.c0);
-    m_store<EXACT>(M, sc2_row_a(sc.rx1), i, rc.c1);
+    scatter_lost(rc, sc.l0, sc.l1, Qs, Ls, grsrc, i, hi, [&]() { stage_q(pl); });
+    m_store<EXACT>(M, sc2_row_a(sc.rx0), mc, rc.c0);
+    m_store<EXACT>(M, sc2_row_a(sc.rx1), mc, rc.c1);
     const bool pass_b = sc.n > 64;  // wave-uniform
     f32x16 acc0, acc1;
     sc2_load_a(M, i, hi, sc.n, A);
-    m_zero<EXACT>(M, sc2_row_a(sc.rx0), i);
-    m_zero<EXACT>(M, sc2_row_a(sc.rx1), i);
+    m_zero<EXACT>(M, sc2_row_a(sc.rx0), mc);
+    m_zero<EXACT>(M, sc2_row_a(sc.rx1), mc);
     if (pass_b) {
-        m_store<EXACT>(M, sc2_row_b(sc.rx0), i, rc.c0);
-        m_store<EXACT>(M, sc2_row_b(sc.rx1), i, rc.c1);
+        m_store<EXACT>(M, sc2_row_b(sc.rx0), mc, rc.c0);
+        m_store<EXACT>(M, sc2_row_b(sc.rx1), mc, rc.c1);
     }
-    sc2_load_b(Qs, i, hi, B);
+    load_b(pl, B);
     sc2_split_b(B);
     sc2_gemm(A, B, sc.n, acc0, acc1);
     if (pass_b) {
         sc2_flush(acc0, acc1, ct, 64, grsrc, lane_b, hi);
         sc2_load_a(M, i, hi, sc.n - 64, A);
-        m_zero<EXACT>(M, sc2_row_b(sc.rx0), i);
-        m_zero<EXACT>(M, sc2_row_b(sc.rx1), i);
+        m_zero<EXACT>(M, sc2_row_b(sc.rx0), mc);
+        m_zero<EXACT>(M, sc2_row_b(sc.rx1), mc);
         sc2_gemm(A, B, sc.n - 64, acc0, acc1);
         sc2_flush(acc0, acc1, ct + 64, sc.n - 64, grsrc, lane_b, hi);
     } else {

@@ -348,36 +348,22 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_tex(BwdTexParams p) {
             float* Es = Xs + (EXACT ? 65 * XS : SCATTER_M_FLOATS);  // ebar rows [sample][32], stride 33; fallback lists
             scatter_clear<EXACT>(M, lane);
             const int tex0 = (int)(pofs / TT_C);
-            // ebar = V1^T k1bar for the three planes in ONE product (96 rows: k1bar is split into fp16 terms once)
-            float eb[48];
-            if constexpr (F::COPIES)
+            // ebar = V1^T k1bar for the three planes in ONE product (96 rows: k1bar is split into fp16 terms once).  Its one
+            // consumer is the scatter, which wants it as the B operand of the combine GEMM: the split modes form ebar^T by
+            // swapping the MFMA's two arguments -- three 16-register tiles, one per plane: lane <-> channel, register <->
+            // sample, raw accumulators; ueb = this lane's SAMPLE's factor, handed over through the factor table
+            // (tt_backward_common.h, sc2_regs_b)
+            float eb[48], ueb = 1.f;
+            if constexpr (EXACT)
                 mvtx_copy<PREC>(Lt, typename F::V1T{}, typename F::V1{}, kb1, eb, i, hi);
+            else if constexpr (F::COPIES)
+                mvtx_copy<PREC, true, true>(Lt, typename F::V1T{}, typename F::V1{}, kb1, eb, i, hi, 1.f, &ueb);
             else
-                mvtx<PREC>(Lt, typename F::V1{}, kb1, eb, i, hi);
+                mvtx<PREC, true, true>(Lt, typename F::V1{}, kb1, eb, i, hi, 1.f, &ueb);
             TT_PHASE(9);
-            if (one) {  // the live plane's 16 registers of ebar (selects, no runtime register indexing), its scatter alone
-                float eb1[16];
-#pragma unroll
-                for (int r = 0; r < 16; ++r) eb1[r] = pl1 == 0 ? eb[r] : (pl1 == 1 ? eb[16 + r] : eb[32 + r]);
-                scatter_one_plane<EXACT>(grad_out, grad_bytes, Es, M, tags, Es + 32 * 33, i, hi, pl1,
-                                         [&](int pl, PlaneRefs& refs) {
-                    Corners c;
-                    corners_setup(PLANE_U(pl, X, Y, Z), PLANE_V(pl, X, Y, Z), H, W, valid, c);
-                    int aoff[4];
-#pragma unroll
-                    for (int q4 = 0; q4 < 4; ++q4) aoff[q4] = tex0 + (int)((3 + pl) * HW) + c.off[q4];
-                    refs = plane_refs<!EXACT>(c.w, aoff, c.hs, hi);
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) Es[i * 33 + LIDX(r, hi)] = eb1[r] * refs.qs;
-                }
-#ifdef TT_TUNING
-                , scat_st
-#endif
-                );
-                TT_PHASE(10);
-                continue;
-            }
-            scatter_planes<EXACT>(grad_out, grad_bytes, Es, M, tags, Es + 32 * 33, i, hi, [&](int pl, PlaneRefs& refs) {
+            // corner set-up of plane pl and the hand-over of the sample's factor: the fp32 form stages the sample's row of
+            // ebar (ebp: the plane's 16 registers), the register form stores one factor
+            auto prep_plane = [&](int pl, PlaneRefs& refs, const float* ebp) {
                 Corners c;
                 corners_setup(PLANE_U(pl, X, Y, Z), PLANE_V(pl, X, Y, Z), H, W, valid, c);
                 int aoff[4];
@@ -385,13 +371,48 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_tex(BwdTexParams p) {
                 for (int q4 = 0; q4 < 4; ++q4)  // absolute texel index, prompt included
                     aoff[q4] = tex0 + (int)((3 + pl) * HW) + c.off[q4];
                 refs = plane_refs<!EXACT>(c.w, aoff, c.hs, hi);
+                if constexpr (EXACT) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) Es[i * 33 + LIDX(r, hi)] = eb[16 * pl + r] * refs.qs;
-            }
+                    for (int r = 0; r < 16; ++r) Es[i * 33 + LIDX(r, hi)] = ebp[r] * refs.qs;
+                } else {
+                    sc2_factor_table(tags, pl)[i] = ueb * refs.qs;
+                }
+            };
+            auto load_plane_b = [&](int pl, auto& B, const float* ebp) {
+                if constexpr (EXACT)
+                    sc2_load_b(Es, i, hi, B);
+                else
+                    sc2_regs_b(ebp, sc2_factor_table(tags, pl), hi, B);
+            };
+            auto stage_plane_q = [&](int pl, const float* ebp) {  // (fp32 form: staged by prep)
+                if constexpr (!EXACT) sc2_regs_stage_q(ebp, sc2_factor_table(tags, pl), Es, i, hi);
+            };
+            // plane pl's tile of eb (pl: a constant after unrolling)
+#define EB_TILE(pl) (eb + 16 * (pl))
+            if (one) {  // the live plane's 16 registers of ebar (selects, no runtime register indexing), its scatter alone
+                float eb1[16];
+#pragma unroll
+                for (int r = 0; r < 16; ++r) eb1[r] = pl1 == 0 ? eb[r] : (pl1 == 1 ? eb[16 + r] : eb[32 + r]);
+                scatter_one_plane<EXACT>(
+                    grad_out, grad_bytes, Es, M, tags, Es + 32 * 33, i, hi, pl1,
+                    [&](int pl, PlaneRefs& refs) { prep_plane(pl, refs, eb1); },
+                    [&](int pl, auto& B) { load_plane_b(pl, B, eb1); }, [&](int pl) { stage_plane_q(pl, eb1); }
 #ifdef TT_TUNING
-            , scat_st
+                    , scat_st
+#endif
+                );
+                TT_PHASE(10);
+                continue;
+            }
+            scatter_planes<EXACT>(
+                grad_out, grad_bytes, Es, M, tags, Es + 32 * 33, i, hi,
+                [&](int pl, PlaneRefs& refs) { prep_plane(pl, refs, EB_TILE(pl)); },
+                [&](int pl, auto& B) { load_plane_b(pl, B, EB_TILE(pl)); }, [&](int pl) { stage_plane_q(pl, EB_TILE(pl)); }
+#ifdef TT_TUNING
+                , scat_st
 #endif
             );
+#undef EB_TILE
             TT_PHASE(10);
         }
       }

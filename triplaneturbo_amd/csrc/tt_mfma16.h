@@ -318,29 +318,41 @@ __device__ __forceinline__ void stage_image16_rowscaled_t(float* L, LdsImage<ROW
 // NT = 2: hh, hl, lh (the three terms above 2^-20).  NT = 3: the six terms above 2^-33, small to large (a0 / b0 = hi,
 // a1 / b1 = mid, a2 / b2 = lo): h.l, l.h, m.m ; h.m, m.h ; h.h.  Row tiles are interleaved so that consecutive MFMAs never
 // depend on each other when MT > 1.
-template <int MT, int NT>
+// SWAP (transposed output): the same MFMAs with their two arguments exchanged.  The A and B fragments of
+// v_mfma_f32_32x32x16_f16 have the same per-lane shape (index lane & 31, the eight k-values of lane >> 5), so the accumulators
+// then hold the TRANSPOSED tile: lane (c, hi) <-> row c of the image, register r <-> sample (r&3) + 8(r>>2) + 4hi.  Same
+// fragments, same k order, same terms in the same order, same number of MFMAs (tools/scatter_regs_probe.hip compares the
+// two forms element for element).
+template <bool SWAP>
+__device__ __forceinline__ f32x16 mfma16_ab(const h8_t& a, const h8_t& b, const f32x16& c) {
+    if constexpr (SWAP)
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(b, a, c, 0, 0, 0);
+    else
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+}
+template <int MT, int NT, bool SWAP = false>
 __device__ __forceinline__ void mfma_terms(f32x16 (&acc)[MT], const h8_t (&a0)[MT], const h8_t (&a1)[MT],
                                            const h8_t (&a2)[MT], const h8_t& b0, const h8_t& b1, const h8_t& b2) {
     if constexpr (NT == 3) {
 #pragma unroll
-        for (int m = 0; m < MT; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0[m], b2, acc[m], 0, 0, 0);
+        for (int m = 0; m < MT; ++m) acc[m] = mfma16_ab<SWAP>(a0[m], b2, acc[m]);
 #pragma unroll
-        for (int m = 0; m < MT; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a2[m], b0, acc[m], 0, 0, 0);
+        for (int m = 0; m < MT; ++m) acc[m] = mfma16_ab<SWAP>(a2[m], b0, acc[m]);
 #pragma unroll
-        for (int m = 0; m < MT; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1[m], b1, acc[m], 0, 0, 0);
+        for (int m = 0; m < MT; ++m) acc[m] = mfma16_ab<SWAP>(a1[m], b1, acc[m]);
 #pragma unroll
-        for (int m = 0; m < MT; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0[m], b1, acc[m], 0, 0, 0);
+        for (int m = 0; m < MT; ++m) acc[m] = mfma16_ab<SWAP>(a0[m], b1, acc[m]);
 #pragma unroll
-        for (int m = 0; m < MT; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1[m], b0, acc[m], 0, 0, 0);
+        for (int m = 0; m < MT; ++m) acc[m] = mfma16_ab<SWAP>(a1[m], b0, acc[m]);
 #pragma unroll
-        for (int m = 0; m < MT; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0[m], b0, acc[m], 0, 0, 0);
+        for (int m = 0; m < MT; ++m) acc[m] = mfma16_ab<SWAP>(a0[m], b0, acc[m]);
     } else {
 #pragma unroll
-        for (int m = 0; m < MT; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0[m], b0, acc[m], 0, 0, 0);
+        for (int m = 0; m < MT; ++m) acc[m] = mfma16_ab<SWAP>(a0[m], b0, acc[m]);
 #pragma unroll
-        for (int m = 0; m < MT; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0[m], b1, acc[m], 0, 0, 0);
+        for (int m = 0; m < MT; ++m) acc[m] = mfma16_ab<SWAP>(a0[m], b1, acc[m]);
 #pragma unroll
-        for (int m = 0; m < MT; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1[m], b0, acc[m], 0, 0, 0);
+        for (int m = 0; m < MT; ++m) acc[m] = mfma16_ab<SWAP>(a1[m], b0, acc[m]);
     }
 }
 // the 8 activations of k-step s (registers r0 .. of x, paired as PAIR says) -> B fragments (NT pieces)
@@ -370,9 +382,13 @@ __device__ __forceinline__ h8_t lo_frag(const half_t* lrow, int m, int s) {
     return *reinterpret_cast<const h8_t*>(lrow + (size_t)(32 * m) * RSL + 32 * (s % KH) + 16 * (s / KH));
 }
 
-template <int NOUT, int NIN, bool SCALED = true, bool RAW = false, int NT = 2>
+// SWAP: the transposed output of mfma_terms -- y[16 m + r] = row 32 m + (lane & 31) of the product for sample
+// (r&3) + 8(r>>2) + 4hi.  A sample is then a register, not a lane, so the per-sample factor cannot be applied here: RAW
+// only, *yf = the factor of THIS lane's sample (lane & 31), for the consumer to hand to the lanes that hold the values.
+template <int NOUT, int NIN, bool SCALED = true, bool RAW = false, int NT = 2, bool SWAP = false>
 __device__ __forceinline__ void mv16(const float* img_f, const float (&x)[NIN / 2], float (&y)[NOUT / 2], int i,
                                      int hi, float xf = 1.f, float* yf = nullptr, const float* lo_f = nullptr) {
+    static_assert(!SWAP || RAW, "a transposed product returns raw accumulators");
     constexpr int MT = NOUT / 32, KS = NIN / 16, RS = 2 * NIN + 8;
     const half_t* row = reinterpret_cast<const half_t*>(img_f) + (size_t)i * RS + 8 * hi;
     const half_t* lrow = reinterpret_cast<const half_t*>(lo_f) + (size_t)i * (NIN + 8) + 8 * hi;
@@ -409,7 +425,7 @@ __device__ __forceinline__ void mv16(const float* img_f, const float (&x)[NIN / 
             al[m] = *reinterpret_cast<const h8_t*>(a + 16);
             if constexpr (NT == 3) at[m] = lo_frag<NIN>(lrow, m, s);
         }
-        mfma_terms<MT, NT>(acc, ah, al, at, bh, bl, bt);
+        mfma_terms<MT, NT, SWAP>(acc, ah, al, at, bh, bl, bt);
     }
     if (RAW) *yf = un;
 #pragma unroll
@@ -465,10 +481,11 @@ __device__ __forceinline__ void live_split32(const Split16<96, PAIR_SEQ, NT>& x,
     }
 }
 // mv16 on a pre-split operand: y = M x with x = (hi + lo) * un_x
-template <int NOUT, int NIN, bool RAW = false, int NT = 2>
+template <int NOUT, int NIN, bool RAW = false, int NT = 2, bool SWAP = false>
 __device__ __forceinline__ void mv16_pre(const float* img_f, const Split16<NIN, PAIR_SEQ, NT>& x, float un_x,
                                          float (&y)[NOUT / 2], int i, int hi, float* yf = nullptr,
                                          const float* lo_f = nullptr) {
+    static_assert(!SWAP || RAW, "a transposed product returns raw accumulators");
     constexpr int MT = NOUT / 32, KS = NIN / 16, RS = 2 * NIN + 8;
     const half_t* row = reinterpret_cast<const half_t*>(img_f) + (size_t)i * RS + 8 * hi;
     const half_t* lrow = reinterpret_cast<const half_t*>(lo_f) + (size_t)i * (NIN + 8) + 8 * hi;
@@ -493,7 +510,7 @@ __device__ __forceinline__ void mv16_pre(const float* img_f, const Split16<NIN, 
             al[m] = *reinterpret_cast<const h8_t*>(a + 16);
             if constexpr (NT == 3) at[m] = lo_frag<NIN>(lrow, m, s);
         }
-        mfma_terms<MT, NT>(acc, ah, al, at, bh, bl, bt);
+        mfma_terms<MT, NT, SWAP>(acc, ah, al, at, bh, bl, bt);
     }
     if (RAW) *yf = un;
 #pragma unroll
@@ -502,10 +519,10 @@ __device__ __forceinline__ void mv16_pre(const float* img_f, const Split16<NIN, 
         for (int k = 0; k < 16; ++k) y[16 * m + k] = RAW ? acc[m][k] : acc[m][k] * un;
 }
 // ... on a member of the kernel's LDS map (the pointer form above is what tools/split3_probe.hip drives)
-template <bool RAW = false, int NT, int ROWS, int K, bool ON, int OFF, int LO>
+template <bool RAW = false, bool SWAP = false, int NT, int ROWS, int K, bool ON, int OFF, int LO>
 __device__ __forceinline__ void mv16_pre(const float* L, LdsImage<ROWS, K, ON, OFF, LO> m, const Split16<K, PAIR_SEQ, NT>& x,
                                          float un_x, float (&y)[ROWS / 2], int i, int hi, float* yf = nullptr) {
-    mv16_pre<ROWS, K, RAW, NT>(lds_at(L, m), x, un_x, y, i, hi, yf, lds_lo_at(L, m));
+    mv16_pre<ROWS, K, RAW, NT, SWAP>(lds_at(L, m), x, un_x, y, i, hi, yf, lds_lo_at(L, m));
 }
 
 // ---- products with a 0/1 MASK as the B operand ------------------------------------------------------------------------
@@ -718,9 +735,10 @@ __device__ __forceinline__ h8_t tr_frag_lo(const lds_sv4_t* base_m, int ks) {
 }
 
 // y[NOUT] = M[NIN][col0 .. col0 + NOUT)^T x[NIN]; img_f = forward image of M (NIN rows, KM columns)
-template <int NOUT, int NIN, int KM, bool SCALED = true, bool RAW = false, int NT = 2>
+template <int NOUT, int NIN, int KM, bool SCALED = true, bool RAW = false, int NT = 2, bool SWAP = false>
 __device__ __forceinline__ void mv16t(const float* img_f, int col0, const float (&x)[NIN / 2], float (&y)[NOUT / 2],
                                       int lane, float xf = 1.f, float* yf = nullptr, const float* lo_f = nullptr) {
+    static_assert(!SWAP || RAW, "a transposed product returns raw accumulators");
     constexpr int MT = NOUT / 32, KS = NIN / 16;
     const lds_sv4_t* base = tr_lane_base<KM>(img_f, col0, lane);
     const lds_sv4_t* base_lo[MT];
@@ -759,7 +777,7 @@ __device__ __forceinline__ void mv16t(const float* img_f, int col0, const float 
             al[m] = tr_frag<KM>(base, s, m, 1);
             if constexpr (NT == 3) at[m] = tr_frag_lo<KM>(base_lo[m], s);
         }
-        mfma_terms<MT, NT>(acc, ah, al, at, bh, bl, bt);
+        mfma_terms<MT, NT, SWAP>(acc, ah, al, at, bh, bl, bt);
     }
     if (RAW) *yf = un;
 #pragma unroll
@@ -832,35 +850,39 @@ __device__ __forceinline__ void mvx(const float* L, LdsImage<ROWS, K, ON, OFF, L
     }
 }
 // y = M^T x from the pair (`mt`: split-fp16 image of M^T, stage_weights_t; `m`: fp32 image of M, read under PREC_F32 only)
-template <int PREC, bool RAW = false, int ROWS, int K, bool ON, int OFF, int LO, bool ON_M, int OFF_M, int LO_M>
+// SWAP (split modes only): the transposed output, see mv16
+template <int PREC, bool RAW = false, bool SWAP = false, int ROWS, int K, bool ON, int OFF, int LO, bool ON_M, int OFF_M, int LO_M>
 __device__ __forceinline__ void mvtx_copy(const float* L, LdsImage<ROWS, K, ON, OFF, LO> mt, LdsImage<K, ROWS, ON_M, OFF_M, LO_M> m,
                                           const float (&x)[K / 2], float (&y)[ROWS / 2], int i, int hi, float xf = 1.f,
                                           float* yf = nullptr) {
+    static_assert(!SWAP || PREC != PREC_F32, "the fp32-MFMA products have no transposed form");
     if constexpr (PREC == PREC_F32) {
         mv_bwd<ROWS, K, ROWS + 4>(lds_at(L, m), x, y, i, hi);
         if (RAW) *yf = 1.f;
     } else {
-        mv16<ROWS, K, true, RAW, PrecNT<PREC>::value>(lds_at(L, mt), x, y, i, hi, xf, yf, lds_lo_at(L, mt));
+        mv16<ROWS, K, true, RAW, PrecNT<PREC>::value, SWAP>(lds_at(L, mt), x, y, i, hi, xf, yf, lds_lo_at(L, mt));
     }
 }
 // y[NOUT] = M[:, col0 .. col0 + NOUT)^T x for the member `m` (ROWS x K) staged by stage_weights: from the fp32 image by
 // strided column reads (F32), from the split-fp16 images by transposed reads (mv16t)
-template <int PREC, int NOUT, bool RAW = false, int ROWS, int K, bool ON, int OFF, int LO>
+template <int PREC, int NOUT, bool RAW = false, bool SWAP = false, int ROWS, int K, bool ON, int OFF, int LO>
 __device__ __forceinline__ void mvtx_cols(const float* L, LdsImage<ROWS, K, ON, OFF, LO> m, int col0, const float (&x)[ROWS / 2],
                                           float (&y)[NOUT / 2], int i, int hi, float xf = 1.f, float* yf = nullptr) {
     static_assert(NOUT <= K, "a column slice of the member");
+    static_assert(!SWAP || PREC != PREC_F32, "the fp32-MFMA products have no transposed form");
     if constexpr (PREC == PREC_F32) {
         mv_bwd<NOUT, ROWS, K + 4>(lds_at(L, m) + col0, x, y, i, hi);
         if (RAW) *yf = 1.f;
     } else {
-        mv16t<NOUT, ROWS, K, true, RAW, PrecNT<PREC>::value>(lds_at(L, m), col0, x, y, 32 * hi + i, xf, yf, lds_lo_at(L, m));
+        mv16t<NOUT, ROWS, K, true, RAW, PrecNT<PREC>::value, SWAP>(lds_at(L, m), col0, x, y, 32 * hi + i, xf, yf,
+                                                                  lds_lo_at(L, m));
     }
 }
 // ... over all K columns: y[K] = M^T x
-template <int PREC, bool RAW = false, int ROWS, int K, bool ON, int OFF, int LO>
+template <int PREC, bool RAW = false, bool SWAP = false, int ROWS, int K, bool ON, int OFF, int LO>
 __device__ __forceinline__ void mvtx(const float* L, LdsImage<ROWS, K, ON, OFF, LO> m, const float (&x)[ROWS / 2],
                                      float (&y)[K / 2], int i, int hi, float xf = 1.f, float* yf = nullptr) {
-    mvtx_cols<PREC, K, RAW>(L, m, 0, x, y, i, hi, xf, yf);
+    mvtx_cols<PREC, K, RAW, SWAP>(L, m, 0, x, y, i, hi, xf, yf);
 }
 
 // ---- single-plane forms (a tile step whose plane mask has one bit, tt_device.h) -----------------------------------------
