@@ -175,8 +175,10 @@ typedef struct {
  *                   the reference's precision at ~1/3 of the fp32 MFMA's matrix-pipe time.  SCOPE: the mat-vec chains of
  *                   every kernel (forward, recompute, both gradient chains, per-point queries, eval, d/d points) are
  *                   three-piece; the REDUCTIONS OVER SAMPLES of the backward -- the weight-gradient outer products and
- *                   the scatter's combine GEMM -- use TWO-piece operands (hi + lo, all four cross terms, per-launch /
- *                   per-sample power-of-two scales): each operand is represented to 2^-23 and the round-to-nearest
+ *                   the scatter's combine GEMM -- use TWO-piece operands (hi + lo, per-launch / per-sample power-of-two
+ *                   scales).  The outer products form all four cross terms; the combine GEMM forms three (hh, hl, lh):
+ *                   its dropped lo x lo term is at most 2^-22 |a b| per product (|lo| <= 2^-11 |v|: half an ulp of
+ *                   fp16's 11-bit significand).  Each operand is represented to 2^-23 and the round-to-nearest
  *                   errors average over the thousands to millions of samples such a sum runs over (measured: weight
  *                   and plane gradients 4e-7 ... 1e-6 from the fp32 oracle in all three modes).
  *   TT_R_EXACT_F32  every product on the fp32-input MFMA (v_mfma_f32_32x32x2_f32: a k-ordered fmaf chain).  The A/B

@@ -64,9 +64,10 @@ struct GeoMap : LdsMap<PREC, LdsImage<64, 32>, LdsImage<64, 64, !(FMASK && PREC 
 // (stats == null) run the instantiation without it.
 // FMASK: the sign mask of h2 = relu(W2 h1) comes from the forward (p.h2_mask) instead of being recomputed: nothing here
 // reads h2's values (row-scaling identity, top of file).
-template <int PREC, bool WG16, bool STATS = false, bool FMASK = false>
+template <int PREC, bool STATS = false, bool FMASK = false>
 __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
     constexpr bool EXACT = PREC == PREC_F32;
+    constexpr bool WG16 = !EXACT;  // the split modes: outer products on the fp16 pipe, a1 and q in raw form
     typedef GeoMap<PREC, FMASK> G;
     constexpr int NT = PrecNT<PREC>::value, WF = G::FLOATS;
     __shared__ __attribute__((aligned(16))) float L[WF + 4 * (GEO_SCRATCH_FLOATS + SCATTER_TAG_INTS)];
@@ -243,7 +244,7 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
             for (int r = 0; r < 32; ++r) a1[r] = h1[r] > 0.f ? a1[r] : 0.f;
             // q = W1^T a1 has one consumer, the scatter, which wants it as the B operand of its combine GEMM: the split modes
             // form q^T (lane <-> channel, register <-> sample, raw accumulators; uq = the factor) by swapping the MFMA's two
-            // arguments -- one tile for the three planes (tt_backward_common.h, sc2_regs_b)
+            // arguments -- one tile for the three planes (tt_backward_common.h, ScatterQ)
             float uq = 1.f;
             if (WG16) {
                 split16_vec<64, PAIR_SEQ, NT>(a1, sA1 * ua1, a1s);
@@ -259,7 +260,7 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
                 for (int r = 0; r < 16; ++r) qb[r] = fmaf(-sbar, f[r], u[r]);  // qbar = J gbar = u - sbar f
                 // (no opaque scheduling region here, unlike the texture kernel: with the outer products on the fp16 pipe
                 // this kernel has register slack and one scheduling region is faster: 3.22 -> 3.14 ms)
-                const bool region = WG16 ? true : cfg.flags >= 0;  // (always true; opaque to the compiler unless WG16)
+                const bool region = WG16 || cfg.flags >= 0;  // (always true; opaque to the compiler in the fp32 mode)
                 const bool do_wgrad = region && !TT_DBG(cfg.flags, TT_DBG_NO_WGRAD);
                 // dW1 += a1 (sbar f + qbar)^T
                 if (do_wgrad) {
@@ -304,7 +305,7 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
                     float* Qs = Xs + SCATTER_M_FLOATS;
                     TT_PHASE(9);
                     const int tex0 = (int)(pofs / TT_C);
-                    auto prep = [&](int pl, PlaneRefs& refs) {
+                    auto corners = [&](int pl, PlaneRefs& refs) {
                         Corners c;
                         float coef[4];  // per corner: w sbar + dw/dx . gbar -- gather AND scatter coefficient
                         geo_corner_coefs(pl, H, W, X, Y, Z, rvalid, sbar, gbx, gby, gbz, ju, jv, c, coef);
@@ -312,33 +313,19 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
 #pragma unroll
                         for (int q4 = 0; q4 < 4; ++q4) aoff[q4] = tex0 + (int)(pl * HW) + c.off[q4];
                         refs = plane_refs<!EXACT>(coef, aoff, c.hs, hi);
-                        if constexpr (EXACT) {
-#pragma unroll
-                            for (int r = 0; r < 16; ++r) Qs[i * 33 + LIDX(r, hi)] = q[r] * refs.qs;
-                        } else {  // the sample's factor for the lanes that hold its q^T (both half-waves: the same value)
-                            sc2_factor_table(tags, pl)[i] = uq * refs.qs;
-                        }
-                    };
-                    auto load_b = [&](int pl, auto& B) {
-                        if constexpr (EXACT)
-                            sc2_load_b(Qs, i, hi, B);
-                        else
-                            sc2_regs_b(q, sc2_factor_table(tags, pl), hi, B);
-                    };
-                    auto stage_q = [&](int pl) {  // rows of Q for a plane's lost references (fp32 form: staged by prep)
-                        if constexpr (!EXACT) sc2_regs_stage_q(q, sc2_factor_table(tags, pl), Qs, i, hi);
                     };
 #ifdef TT_TUNING
                     unsigned long long* const sc_st = ph_acc + 14;
 #else
                     unsigned long long* const sc_st = nullptr;
 #endif
+                    // q is the one tile of all three planes, uq its deferred factor (ScatterQ, tt_backward_common.h)
+                    const ScatterQ<EXACT> sq{Qs, tags, i, hi};
                     if (one)
-                        scatter_one_plane<EXACT>(grad_out, grad_bytes, Qs, Xs, tags, Qs + 32 * 33, i, hi,
-                                                 single_plane_index(pmask), prep, load_b, stage_q, sc_st);
+                        scatter_one_plane<EXACT>(grad_out, grad_bytes, sq, Xs, Qs + 32 * 33,
+                                                 single_plane_index(pmask), corners, q, uq, sc_st);
                     else
-                        scatter_planes<EXACT>(grad_out, grad_bytes, Qs, Xs, tags, Qs + 32 * 33, i, hi, prep, load_b, stage_q,
-                                              sc_st);
+                        scatter_planes<EXACT>(grad_out, grad_bytes, sq, Xs, Qs + 32 * 33, corners, [&](int) { return q; }, uq, sc_st);
                     TT_PHASE(10);
                 }
             }
@@ -388,16 +375,15 @@ static void launch_bwd_geo(const BwdGeoParams& p0, long long blocks, hipStream_t
     }
     tt_dispatch_prec(tt_prec_of_r(p.cfg.flags), [&](auto P) {
         constexpr int PREC = decltype(P)::value;
-        constexpr bool WG16 = PREC != PREC_F32;
         const dim3 grid((unsigned)blocks), block(256);
         if (p.cfg.stats && p.h2_mask)
-            hipLaunchKernelGGL((k_decode_bwd_geo<PREC, WG16, true, true>), grid, block, 0, s, p);
+            hipLaunchKernelGGL((k_decode_bwd_geo<PREC, true, true>), grid, block, 0, s, p);
         else if (p.cfg.stats)
-            hipLaunchKernelGGL((k_decode_bwd_geo<PREC, WG16, true>), grid, block, 0, s, p);
+            hipLaunchKernelGGL((k_decode_bwd_geo<PREC, true>), grid, block, 0, s, p);
         else if (p.h2_mask)
-            hipLaunchKernelGGL((k_decode_bwd_geo<PREC, WG16, false, true>), grid, block, 0, s, p);
+            hipLaunchKernelGGL((k_decode_bwd_geo<PREC, false, true>), grid, block, 0, s, p);
         else
-            hipLaunchKernelGGL((k_decode_bwd_geo<PREC, WG16>), grid, block, 0, s, p);
+            hipLaunchKernelGGL((k_decode_bwd_geo<PREC>), grid, block, 0, s, p);
     });
 }
 

@@ -618,6 +618,37 @@ __device__ __forceinline__ void sc2_regs_stage_q(const float* qt, const float* T
         for (int e = 0; e < 4; ++e) Qs[LIDX(4 * g + e, hi) * 33 + i] = qt[4 * g + e] * t4[e];
     }
 }
+// The hand-over of the last product to the combine GEMM's B operand.  `tile`: the 16 registers of that product that belong to
+// plane pl; qs: the plane's PlaneRefs::qs of this lane's sample.  Qs: 32 rows of Q, stride 33; tags: scatter_init_tags.
+//   fp32 form (EXACT; tile = the SAMPLE's row of Q): hand_over stages the row, scaled by qs, into Qs (the previous plane's B
+//     operand is in registers by then; one row pointer: profiles/bwd_handover_ab.txt), load_b reads the operand back.
+//   register form (tile = the transposed tile of sc2_regs_b): hand_over stores ONE number, the product's deferred factor times
+//     qs, into slot i of the plane's factor table; stage_q writes the plane's rows of Q, only when it has a lost reference.
+template <bool EXACT>
+struct ScatterQ {
+    float* Qs;
+    int* tags;
+    int i, hi;
+    __device__ __forceinline__ void hand_over(int pl, const float* tile, float factor, float qs) const {
+        if constexpr (EXACT) {
+            float* const row = Qs + i * 33;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) row[LIDX(r, hi)] = tile[r] * qs;
+        } else {  // (both half-waves: the same value)
+            sc2_factor_table(tags, pl)[i] = factor * qs;
+        }
+    }
+    template <class BOp>
+    __device__ __forceinline__ void load_b(int pl, const float* tile, BOp& B) const {
+        if constexpr (EXACT)
+            sc2_load_b(Qs, i, hi, B);
+        else
+            sc2_regs_b(tile, sc2_factor_table(tags, pl), hi, B);
+    }
+    __device__ __forceinline__ void stage_q(int pl, const float* tile) const {
+        if constexpr (!EXACT) sc2_regs_stage_q(tile, sc2_factor_table(tags, pl), Qs, i, hi);
+    }
+};
 __device__ __forceinline__ void sc2_split_b(ScB32&) {}
 // per-channel normalisation of the B operand to the top of the fp16 range (column = this lane and lane ^ 32) + split
 __device__ __forceinline__ void sc2_split_b(ScB16& B) {
@@ -703,29 +734,50 @@ __device__ __forceinline__ void sc2_flush(const f32x16& acc0, const f32x16& acc1
     }
 }
 
-// prep(pl, refs): corner set-up of plane pl for this lane's sample AND what hands the sample's factor to the B operand:
-//   fp32 form: the staging of its row of Q, scaled by refs.qs, into Qs[j*33 + ch] (the previous plane's B operand is in
-//   registers by then);  register form: one store of the sample's factor into the plane's table (sc2_regs_b).
-// load_b(pl, B): the B operand of plane pl (sc2_load_b from Qs / sc2_regs_b).  stage_q(pl): writes plane pl's rows of Q to
-// Qs for scatter_lost (register form; the fp32 form has them there already).  M: all-zero on entry and on exit.
-// tags: the 32 dummy words (scatter_init_tags).  Ls: 256 floats of lost-reference lists, followed by SC2_INTS ints.
-// Pipeline per plane p:  operands A(p) -> registers, M rows back to zero, [n > 64: rows of pass B -> M]; prep(p+1);
-//   GEMM A(p); [pass B: flush A(p), operands B(p) -> registers, M back to zero]; claims + ranks(p+1), lost references of
-//   p+1 (under the MFMAs); [pass B: GEMM B(p), flush B(p) | else: flush A(p)]; rows of pass A(p+1) -> M.
-template <bool EXACT, class Prep, class LoadB, class StageQ>
-__device__ __forceinline__ void scatter_planes(float* __restrict__ grad, unsigned grad_bytes, const float* Qs, float* M,
-                                               int* tags, float* Ls, int i, int hi, Prep&& prep, LoadB&& load_b,
-                                               StageQ&& stage_q, unsigned long long* st = nullptr) {
+// What both scatter drivers start from: the gradient copy as a buffer resource, this lane's places in the per-wave tables
+// (sq.tags: the 32 dummy words, scatter_init_tags; Ls: 256 floats of lost-reference lists, followed by SC2_INTS ints), the
+// texel table cleared (its LDS is shared with the other phases of the tile step) and this lane's column of M.
+struct ScatterCtx {
+    __amdgpu_buffer_rsrc_t grsrc;
+    unsigned lane_b;
+    int lane, mc;
+    int *dummy, *htab, *ctag, *cdump;
+};
+template <bool EXACT>
+__device__ __forceinline__ ScatterCtx scatter_ctx(float* __restrict__ grad, unsigned grad_bytes, const ScatterQ<EXACT>& sq, float* Ls) {
+    ScatterCtx cx;
     // BUFFER atomics with a 32-bit BYTE offset (texel << 7 | channel * 4) from the gradient copy: a tag of -1 gives the
     // offset 0xFFFFFF80 + 4 ch, beyond num_records (the host refuses gradient buffers of 4 GB - 256 B and more), and the
     // hardware range check drops the atomic -- no compare, no exec-mask branch per row.
-    const __amdgpu_buffer_rsrc_t grsrc = __builtin_amdgcn_make_buffer_rsrc(grad, 0, (int)grad_bytes, 0x00020000);
-    const unsigned lane_b = 4u * (unsigned)i;
-    const int lane = i + 32 * hi;
-    int* const dummy = tags + i;
-    int* const htab = reinterpret_cast<int*>(Ls + 256);
-    int* const ctag = htab + SC2_HT;
-    int* const cdump = ctag + 2 * SC2_CT;
+    cx.grsrc = __builtin_amdgcn_make_buffer_rsrc(grad, 0, (int)grad_bytes, 0x00020000);
+    cx.lane_b = 4u * (unsigned)sq.i;
+    cx.lane = sq.i + 32 * sq.hi;
+    cx.dummy = sq.tags + sq.i;
+    cx.htab = reinterpret_cast<int*>(Ls + 256);
+    cx.ctag = cx.htab + SC2_HT;
+    cx.cdump = cx.ctag + 2 * SC2_CT;
+    *reinterpret_cast<i32x4*>(cx.htab + 4 * cx.lane) = i32x4{-1, -1, -1, -1};
+    cx.mc = sc2_col<EXACT>(sq.i);
+    return cx;
+}
+
+// corners(pl, refs): the kernel's corner set-up of plane pl for this lane's sample, ending in plane_refs<!EXACT>.
+// tile(pl): the 16 registers of the last product that belong to plane pl; factor: that product's deferred factor (1 in the
+// fp32 form) -- what sq, the kernel's ScatterQ, hands over (both by reference, as the kernels' lambdas captured them: by value
+// hipcc allocates the kernels differently, profiles/bwd_handover_ab.txt).  M: all-zero on entry and on exit.  Ls: ScatterCtx.
+// Pipeline per plane p:  operands A(p) -> registers, M rows back to zero, [n > 64: rows of pass B -> M]; prep(p+1) = corners
+//   + hand-over; GEMM A(p); [pass B: flush A(p), operands B(p) -> registers, M back to zero]; claims + ranks(p+1), lost
+//   references of p+1 (under the MFMAs); [pass B: GEMM B(p), flush B(p) | else: flush A(p)]; rows of pass A(p+1) -> M.
+template <bool EXACT, class Corners, class Tile>
+__device__ __forceinline__ void scatter_planes(float* __restrict__ grad, unsigned grad_bytes, const ScatterQ<EXACT>& sq, float* M,
+                                               float* Ls, Corners&& corners, Tile&& tile, const float& factor,
+                                               unsigned long long* st = nullptr) {
+    float* const Qs = sq.Qs;
+    const int i = sq.i, hi = sq.hi;
+    auto prep = [&](int pl, PlaneRefs& refs) {
+        corners(pl, refs);
+        sq.hand_over(pl, tile(pl), factor, refs.qs);
+    };
     typedef typename std::conditional<EXACT, ScA32, ScA16>::type AOp;
     typedef typename std::conditional<EXACT, ScB32, ScB16>::type BOp;
 #ifdef TT_TUNING  // sub-phase cycles of the epilogue (st[3..5] = operands+prep / GEMM+claim / flush+reset+lost)
@@ -745,56 +797,52 @@ __device__ __forceinline__ void scatter_planes(float* __restrict__ grad, unsigne
     do {               \
     } while (0)
 #endif
-    {  // the table starts empty (its LDS is shared with the other phases of the tile step)
-        const i32x4 e4 = {-1, -1, -1, -1};
-        *reinterpret_cast<i32x4*>(htab + 4 * lane) = e4;
-    }
-    const int mc = sc2_col<EXACT>(i);  // this lane's column of M
+    const ScatterCtx cx = scatter_ctx<EXACT>(grad, grad_bytes, sq, Ls);  // (inside sub-phase 3)
     PlaneRefs rc, rn;
     Sc2State sc, sn;
     prep(0, rc);
-    sc = sc2_claim_rank(rc, htab, ctag, cdump, dummy, lane, st);
-    scatter_lost(rc, sc.l0, sc.l1, Qs, Ls, grsrc, i, hi, [&]() { stage_q(0); });
-    m_store<EXACT>(M, sc2_row_a(sc.rx0), mc, rc.c0);
-    m_store<EXACT>(M, sc2_row_a(sc.rx1), mc, rc.c1);
+    sc = sc2_claim_rank(rc, cx.htab, cx.ctag, cx.cdump, cx.dummy, cx.lane, st);
+    scatter_lost(rc, sc.l0, sc.l1, Qs, Ls, cx.grsrc, i, hi, [&]() { sq.stage_q(0, tile(0)); });
+    m_store<EXACT>(M, sc2_row_a(sc.rx0), cx.mc, rc.c0);
+    m_store<EXACT>(M, sc2_row_a(sc.rx1), cx.mc, rc.c1);
 #pragma unroll
     for (int pl = 0; pl < 3; ++pl) {
-        const int* const ct = ctag + SC2_CT * (pl & 1);
-        int* const ct_next = ctag + SC2_CT * ((pl + 1) & 1);
+        const int* const ct = cx.ctag + SC2_CT * (pl & 1);
+        int* const ct_next = cx.ctag + SC2_CT * ((pl + 1) & 1);
         const bool pass_b = sc.n > 64;  // wave-uniform
         f32x16 acc0, acc1;
         AOp A;
         BOp B;
         sc2_load_a(M, i, hi, sc.n, A);
-        m_zero<EXACT>(M, sc2_row_a(sc.rx0), mc);
-        m_zero<EXACT>(M, sc2_row_a(sc.rx1), mc);
+        m_zero<EXACT>(M, sc2_row_a(sc.rx0), cx.mc);
+        m_zero<EXACT>(M, sc2_row_a(sc.rx1), cx.mc);
         if (pass_b) {
-            m_store<EXACT>(M, sc2_row_b(sc.rx0), mc, rc.c0);
-            m_store<EXACT>(M, sc2_row_b(sc.rx1), mc, rc.c1);
+            m_store<EXACT>(M, sc2_row_b(sc.rx0), cx.mc, rc.c0);
+            m_store<EXACT>(M, sc2_row_b(sc.rx1), cx.mc, rc.c1);
         }
-        load_b(pl, B);
+        sq.load_b(pl, tile(pl), B);
         if (pl < 2) prep(pl + 1, rn);
         sc2_split_b(B);
         sc2_gemm(A, B, sc.n, acc0, acc1);
         TT_SUBPHASE(3);
         if (pass_b) {  // (rare on dense rays: the first pass is flushed before the next plane's claims)
-            sc2_flush(acc0, acc1, ct, 64, grsrc, lane_b, hi);
+            sc2_flush(acc0, acc1, ct, 64, cx.grsrc, cx.lane_b, hi);
             sc2_load_a(M, i, hi, sc.n - 64, A);
-            m_zero<EXACT>(M, sc2_row_b(sc.rx0), mc);
-            m_zero<EXACT>(M, sc2_row_b(sc.rx1), mc);
+            m_zero<EXACT>(M, sc2_row_b(sc.rx0), cx.mc);
+            m_zero<EXACT>(M, sc2_row_b(sc.rx1), cx.mc);
         }
-        if (pl < 2) sn = sc2_claim_rank(rn, htab, ct_next, cdump, dummy, lane, st);
+        if (pl < 2) sn = sc2_claim_rank(rn, cx.htab, ct_next, cx.cdump, cx.dummy, cx.lane, st);
         TT_SUBPHASE(4);
         if (pass_b) {
             sc2_gemm(A, B, sc.n - 64, acc0, acc1);
-            sc2_flush(acc0, acc1, ct + 64, sc.n - 64, grsrc, lane_b, hi);
+            sc2_flush(acc0, acc1, ct + 64, sc.n - 64, cx.grsrc, cx.lane_b, hi);
         } else {
-            sc2_flush(acc0, acc1, ct, sc.n, grsrc, lane_b, hi);
+            sc2_flush(acc0, acc1, ct, sc.n, cx.grsrc, cx.lane_b, hi);
         }
         if (pl < 2) {
-            scatter_lost(rn, sn.l0, sn.l1, Qs, Ls, grsrc, i, hi, [&]() { stage_q(pl + 1); });
-            m_store<EXACT>(M, sc2_row_a(sn.rx0), mc, rn.c0);
-            m_store<EXACT>(M, sc2_row_a(sn.rx1), mc, rn.c1);
+            scatter_lost(rn, sn.l0, sn.l1, Qs, Ls, cx.grsrc, i, hi, [&]() { sq.stage_q(pl + 1, tile(pl + 1)); });
+            m_store<EXACT>(M, sc2_row_a(sn.rx0), cx.mc, rn.c0);
+            m_store<EXACT>(M, sc2_row_a(sn.rx1), cx.mc, rn.c1);
             rc = rn;
             sc = sn;
         }
@@ -805,54 +853,46 @@ __device__ __forceinline__ void scatter_planes(float* __restrict__ grad, unsigne
 // ---- one plane only (single-plane tile steps: the plane mask of the gather has one bit, tt_device.h) -------------------------
 // The other two planes' coefficients are exact zeros there: their claims are all inactive, n = 0, nothing is flushed.  This
 // is plane `pl` (wave-uniform, known at run time) of scatter_planes with nothing to overlap it with, so the pieces run in
-// their plain order: prep, claims + ranks, lost references, rows -> M; operands -> registers, M back to zero; GEMM; flush
+// their plain order: corners, hand-over, claims + ranks, lost references, rows -> M; operands -> registers, M back to zero; GEMM; flush
 // (and the second 64-row pass when n > 64).  Same arguments and the same state on exit as scatter_planes: M all-zero, the
 // table empty, the dummy words <= -2.
-template <bool EXACT, class Prep, class LoadB, class StageQ>
-__device__ __forceinline__ void scatter_one_plane(float* __restrict__ grad, unsigned grad_bytes, const float* Qs, float* M,
-                                                  int* tags, float* Ls, int i, int hi, int pl, Prep&& prep, LoadB&& load_b,
-                                                  StageQ&& stage_q, unsigned long long* st = nullptr) {
-    const __amdgpu_buffer_rsrc_t grsrc = __builtin_amdgcn_make_buffer_rsrc(grad, 0, (int)grad_bytes, 0x00020000);
-    const unsigned lane_b = 4u * (unsigned)i;
-    const int lane = i + 32 * hi;
-    int* const dummy = tags + i;
-    int* const htab = reinterpret_cast<int*>(Ls + 256);
-    int* const ct = htab + SC2_HT;
-    int* const cdump = ct + 2 * SC2_CT;
+template <bool EXACT, class Corners>
+__device__ __forceinline__ void scatter_one_plane(float* __restrict__ grad, unsigned grad_bytes, const ScatterQ<EXACT>& sq, float* M,
+                                                  float* Ls, int pl, Corners&& corners, const float* tile,
+                                                  const float& factor, unsigned long long* st = nullptr) {
+    float* const Qs = sq.Qs;
+    const int i = sq.i, hi = sq.hi;
+    const ScatterCtx cx = scatter_ctx<EXACT>(grad, grad_bytes, sq, Ls);
     typename std::conditional<EXACT, ScA32, ScA16>::type A;
     typename std::conditional<EXACT, ScB32, ScB16>::type B;
-    {
-        const i32x4 e4 = {-1, -1, -1, -1};
-        *reinterpret_cast<i32x4*>(htab + 4 * lane) = e4;
-    }
-    const int mc = sc2_col<EXACT>(i);  // this lane's column of M
     PlaneRefs rc;
-    prep(pl, rc);
-    const Sc2State sc = sc2_claim_rank(rc, htab, ct, cdump, dummy, lane, st);
-    scatter_lost(rc, sc.l0, sc.l1, Qs, Ls, grsrc, i, hi, [&]() { stage_q(pl); });
-    m_store<EXACT>(M, sc2_row_a(sc.rx0), mc, rc.c0);
-    m_store<EXACT>(M, sc2_row_a(sc.rx1), mc, rc.c1);
+    corners(pl, rc);
+    sq.hand_over(pl, tile, factor, rc.qs);
+    const Sc2State sc = sc2_claim_rank(rc, cx.htab, cx.ctag, cx.cdump, cx.dummy, cx.lane, st);
+    scatter_lost(rc, sc.l0, sc.l1, Qs, Ls, cx.grsrc, i, hi, [&]() { sq.stage_q(pl, tile); });
+    m_store<EXACT>(M, sc2_row_a(sc.rx0), cx.mc, rc.c0);
+    m_store<EXACT>(M, sc2_row_a(sc.rx1), cx.mc, rc.c1);
     const bool pass_b = sc.n > 64;  // wave-uniform
     f32x16 acc0, acc1;
     sc2_load_a(M, i, hi, sc.n, A);
-    m_zero<EXACT>(M, sc2_row_a(sc.rx0), mc);
-    m_zero<EXACT>(M, sc2_row_a(sc.rx1), mc);
+    m_zero<EXACT>(M, sc2_row_a(sc.rx0), cx.mc);
+    m_zero<EXACT>(M, sc2_row_a(sc.rx1), cx.mc);
     if (pass_b) {
-        m_store<EXACT>(M, sc2_row_b(sc.rx0), mc, rc.c0);
-        m_store<EXACT>(M, sc2_row_b(sc.rx1), mc, rc.c1);
+        m_store<EXACT>(M, sc2_row_b(sc.rx0), cx.mc, rc.c0);
+        m_store<EXACT>(M, sc2_row_b(sc.rx1), cx.mc, rc.c1);
     }
-    load_b(pl, B);
+    sq.load_b(pl, tile, B);
     sc2_split_b(B);
     sc2_gemm(A, B, sc.n, acc0, acc1);
     if (pass_b) {
-        sc2_flush(acc0, acc1, ct, 64, grsrc, lane_b, hi);
+        sc2_flush(acc0, acc1, cx.ctag, 64, cx.grsrc, cx.lane_b, hi);
         sc2_load_a(M, i, hi, sc.n - 64, A);
-        m_zero<EXACT>(M, sc2_row_b(sc.rx0), mc);
-        m_zero<EXACT>(M, sc2_row_b(sc.rx1), mc);
+        m_zero<EXACT>(M, sc2_row_b(sc.rx0), cx.mc);
+        m_zero<EXACT>(M, sc2_row_b(sc.rx1), cx.mc);
         sc2_gemm(A, B, sc.n - 64, acc0, acc1);
-        sc2_flush(acc0, acc1, ct + 64, sc.n - 64, grsrc, lane_b, hi);
+        sc2_flush(acc0, acc1, cx.ctag + 64, sc.n - 64, cx.grsrc, cx.lane_b, hi);
     } else {
-        sc2_flush(acc0, acc1, ct, sc.n, grsrc, lane_b, hi);
+        sc2_flush(acc0, acc1, cx.ctag, sc.n, cx.grsrc, cx.lane_b, hi);
     }
 }
 

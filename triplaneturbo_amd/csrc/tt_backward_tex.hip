@@ -31,9 +31,10 @@ __device__ __forceinline__ float uniform_f(float v) {
 }
 
 // STATS: work accounting compiled in (see k_decode_bwd_geo): production launches run the instantiation without it
-template <int PREC, bool WG16, bool STATS = false>
+template <int PREC, bool STATS = false>
 __global__ __launch_bounds__(256, 1) void k_decode_bwd_tex(BwdTexParams p) {
     constexpr bool EXACT = PREC == PREC_F32;
+    constexpr bool WG16 = !EXACT;  // the split modes: outer products (and every product) on the fp16 pipe
     typedef TexMap<PREC> F;
     constexpr int NT = PrecNT<PREC>::value, WF = F::FLOATS;
     __shared__ __attribute__((aligned(16))) float Lt[WF + 4 * (TEX_SCRATCH_FLOATS + SCATTER_TAG_INTS)];
@@ -219,7 +220,7 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_tex(BwdTexParams p) {
         // With the outer products on the fp16 pipe (WG16) only the scatter keeps its own region: 27 -> 0 spilled
         // registers, 3.37 -> 3.18 ms (no region at all: 67 spills, 3.99 ms; region around the outer products only: 3.57).
         const bool region = cfg.flags >= 0;
-        const bool region_w = WG16 ? true : region;
+        const bool region_w = WG16 || region;
         const bool do_wgrad = region_w && !TT_DBG(cfg.flags, TT_DBG_NO_WGRAD);
         float k1[32], k2[32];
         if (WG16) {  // e is split once, under its per-launch scale, for the outer product and for V1 e
@@ -352,7 +353,7 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_tex(BwdTexParams p) {
             // consumer is the scatter, which wants it as the B operand of the combine GEMM: the split modes form ebar^T by
             // swapping the MFMA's two arguments -- three 16-register tiles, one per plane: lane <-> channel, register <->
             // sample, raw accumulators; ueb = this lane's SAMPLE's factor, handed over through the factor table
-            // (tt_backward_common.h, sc2_regs_b)
+            // (tt_backward_common.h, ScatterQ)
             float eb[48], ueb = 1.f;
             if constexpr (EXACT)
                 mvtx_copy<PREC>(Lt, typename F::V1T{}, typename F::V1{}, kb1, eb, i, hi);
@@ -361,9 +362,7 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_tex(BwdTexParams p) {
             else
                 mvtx<PREC, true, true>(Lt, typename F::V1{}, kb1, eb, i, hi, 1.f, &ueb);
             TT_PHASE(9);
-            // corner set-up of plane pl and the hand-over of the sample's factor: the fp32 form stages the sample's row of
-            // ebar (ebp: the plane's 16 registers), the register form stores one factor
-            auto prep_plane = [&](int pl, PlaneRefs& refs, const float* ebp) {
+            auto corners = [&](int pl, PlaneRefs& refs) {
                 Corners c;
                 corners_setup(PLANE_U(pl, X, Y, Z), PLANE_V(pl, X, Y, Z), H, W, valid, c);
                 int aoff[4];
@@ -371,48 +370,24 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_tex(BwdTexParams p) {
                 for (int q4 = 0; q4 < 4; ++q4)  // absolute texel index, prompt included
                     aoff[q4] = tex0 + (int)((3 + pl) * HW) + c.off[q4];
                 refs = plane_refs<!EXACT>(c.w, aoff, c.hs, hi);
-                if constexpr (EXACT) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) Es[i * 33 + LIDX(r, hi)] = ebp[r] * refs.qs;
-                } else {
-                    sc2_factor_table(tags, pl)[i] = ueb * refs.qs;
-                }
             };
-            auto load_plane_b = [&](int pl, auto& B, const float* ebp) {
-                if constexpr (EXACT)
-                    sc2_load_b(Es, i, hi, B);
-                else
-                    sc2_regs_b(ebp, sc2_factor_table(tags, pl), hi, B);
-            };
-            auto stage_plane_q = [&](int pl, const float* ebp) {  // (fp32 form: staged by prep)
-                if constexpr (!EXACT) sc2_regs_stage_q(ebp, sc2_factor_table(tags, pl), Es, i, hi);
-            };
-            // plane pl's tile of eb (pl: a constant after unrolling)
-#define EB_TILE(pl) (eb + 16 * (pl))
+#ifdef TT_TUNING
+            unsigned long long* const sc_st = scat_st;
+#else
+            unsigned long long* const sc_st = nullptr;
+#endif
+            const ScatterQ<EXACT> sq{Es, tags, i, hi};
             if (one) {  // the live plane's 16 registers of ebar (selects, no runtime register indexing), its scatter alone
                 float eb1[16];
 #pragma unroll
                 for (int r = 0; r < 16; ++r) eb1[r] = pl1 == 0 ? eb[r] : (pl1 == 1 ? eb[16 + r] : eb[32 + r]);
-                scatter_one_plane<EXACT>(
-                    grad_out, grad_bytes, Es, M, tags, Es + 32 * 33, i, hi, pl1,
-                    [&](int pl, PlaneRefs& refs) { prep_plane(pl, refs, eb1); },
-                    [&](int pl, auto& B) { load_plane_b(pl, B, eb1); }, [&](int pl) { stage_plane_q(pl, eb1); }
-#ifdef TT_TUNING
-                    , scat_st
-#endif
-                );
+                scatter_one_plane<EXACT>(grad_out, grad_bytes, sq, M, Es + 32 * 33, pl1, corners, eb1, ueb, sc_st);
                 TT_PHASE(10);
                 continue;
             }
-            scatter_planes<EXACT>(
-                grad_out, grad_bytes, Es, M, tags, Es + 32 * 33, i, hi,
-                [&](int pl, PlaneRefs& refs) { prep_plane(pl, refs, EB_TILE(pl)); },
-                [&](int pl, auto& B) { load_plane_b(pl, B, EB_TILE(pl)); }, [&](int pl) { stage_plane_q(pl, EB_TILE(pl)); }
-#ifdef TT_TUNING
-                , scat_st
-#endif
-            );
-#undef EB_TILE
+            // plane pl's tile of eb (pl: a constant after unrolling)
+            scatter_planes<EXACT>(grad_out, grad_bytes, sq, M, Es + 32 * 33, corners, [&](int pl) { return eb + 16 * pl; }, ueb,
+                                  sc_st);
             TT_PHASE(10);
         }
       }
@@ -472,11 +447,10 @@ static void launch_bwd_tex(const BwdTexParams& p0, long long blocks, hipStream_t
     }
     tt_dispatch_prec(tt_prec_of_r(p.cfg.flags), [&](auto P) {
         constexpr int PREC = decltype(P)::value;
-        constexpr bool WG16 = PREC != PREC_F32;
         if (p.cfg.stats)
-            hipLaunchKernelGGL((k_decode_bwd_tex<PREC, WG16, true>), dim3((unsigned)blocks), dim3(256), 0, s, p);
+            hipLaunchKernelGGL((k_decode_bwd_tex<PREC, true>), dim3((unsigned)blocks), dim3(256), 0, s, p);
         else
-            hipLaunchKernelGGL((k_decode_bwd_tex<PREC, WG16>), dim3((unsigned)blocks), dim3(256), 0, s, p);
+            hipLaunchKernelGGL((k_decode_bwd_tex<PREC>), dim3((unsigned)blocks), dim3(256), 0, s, p);
     });
 }
 
