@@ -73,6 +73,9 @@
  *                           reference exports the raw marching-cubes mesh; this step has no counterpart there.
  *   tt_bake_*               Mesh.v_tng (threestudio/models/mesh.py:162-205) and the tangent-space normal map (map_Bump)
  *                           the exporter bakes for a simplified mesh from the field's analytic normals.
+ *   tt_dist_*               closest point on a triangle mesh with a backward pass, and a surface sampler: what
+ *                           Mesh.distance_to and Mesh.simplify(max_error=) measure a simplified export with.  No
+ *                           counterpart in the reference.
  */
 #ifndef TT_ABI_H
 #define TT_ABI_H
@@ -953,6 +956,96 @@ int tt_bake_project(float* points, const float* sdf, const float* sdf_grad, cons
 int tt_bake_encode(const float* rast, const float* v_nrm, const int32_t* t_pos_idx, const float* tng_tex,
                    const int32_t* t_tex_idx, const float* field_nrm, int32_t V, int32_t Vt, int32_t T, int32_t H,
                    int32_t W, float* out, int32_t* out_counts, void* stream);
+
+/* ---- point-to-mesh distance (tt_dist.hip): closest point on a triangle mesh, its backward, a surface sampler ----
+ * The geometric query the export chain measures itself with (Mesh.distance_to, Mesh.simplify(max_error=)) and a
+ * point-to-surface loss stands on.  The reference has no such step.  A mesh is v_pos (V,3) fp32 and t_pos_idx (T,3)
+ * int32, T >= 1, every index in [0, V) and every coordinate finite (the host checks both); query points are (N,3) fp32.
+ *   pair        the closest point on triangle f = (a, b, c) to p, in fp32, by ONE device function (dist_closest) with
+ *               one call site: Voronoi regions (Ericson, Real-Time Collision Detection 5.1.5).  The vertex regions
+ *               come from the six projections d1..d6 of p - a, p - b, p - c on ab and ac; the edge and face regions
+ *               from the signed areas taken as n . (ab x ap), n . (ap x ac), n . (bc x bp) with n = ab x ac (the
+ *               book's differences of products of d1..d6 cancel to noise once |p - a| is a few hundred edge lengths).
+ *               Edge parameters are t = clamp(num / den, 0, 1), 0 where den <= 0.  A triangle with
+ *               n.n <= 1e-12 (ab.ab) (ac.ac) -- zero area, equal vertices, collinear -- is the union of its three edge
+ *               segments: the nearest of ab, ac, bc, in that order at equal distance.  Never NaN for finite input.
+ *               Yields v, w (barycentrics b = (max(1 - v - w, 0), v, w), each >= 0, sum 1 to rounding), the point
+ *               c = a + v ab + w ac and d2 = |p - c|^2.
+ *   answer      per point the lexicographic minimum of (d2, f) over ALL T triangles: equal distance goes to the smaller
+ *               face index.  d2 (N) fp32, face (N) int32, bary (N,3) fp32.  It does not depend on the grid, on the order
+ *               of triangles inside a cell, on the order of the points or on the launch, bit for bit.  A point with a
+ *               coordinate that is not finite gives d2 = NaN, face = -1, bary = 0 and leaves the kernel before the
+ *               search.
+ *   grid        G^3 cells over the mesh's bounding cube, 1 <= G <= TT_DIST_MAX_GRID: lo_a = min v_a, ext = the largest
+ *               of the three extents, h = ext / (float)G, inv_h = (float)G / ext (ext == 0: h = inv_h = 0, everything
+ *               is in cell 0).  cell(x) = min(G-1, max(0, (int)floorf((x - lo_a) * inv_h))), difference and product
+ *               each rounded to fp32; key = (c_x G + c_y) G + c_z, so consecutive cells along z are consecutive rows.
+ *               tt_dist_build_count packs every triangle into a 48-byte record (three float4: a, b, c, w unused),
+ *               counts per cell the triangles whose axis-aligned box overlaps it (cells of the box's two corners,
+ *               integer atomics) and scans (tt_scan.h): cell_ptr (G^3 + 1) int32; M = the number of (cell, triangle)
+ *               pairs goes to out_total (int64, DEVICE memory, read back: the one host round trip of the build).  M and
+ *               G^3 + 1 must not exceed TT_MESH_MAX_ITEMS (the host raises ValueError before the fill).
+ *               tt_dist_build_fill writes cell_tri (M) int32; the order inside a row is arrival order and means
+ *               nothing.  G = 1 is brute force and runs the same code.  A triangle is binned by its box, so one that
+ *               spans the cube is a member of every cell.
+ *   default G   clamp(ceil(sqrt(T) / 8), 1, 256), the host's rule when the caller names no grid.  A surface occupies
+ *               about G^2 cells; the first rule, sqrt(T) / 2 (a few triangles per occupied cell, M / T = 8), lost to
+ *               coarser grids on the GPU: at T = 84 k a query of 100 k points near the surface took 11.0 / 5.2 / 4.0 ms at
+ *               sqrt(T) / 2, / 4, / 8 and one of 100 k points uniform in the box 786 / 265 / 157 ms -- a thread walks its
+ *               empty cells one dependent load at a time, so empty rings cost more than spare triangles
+ *               (profiles/mesh_distance.json).  A point far from the surface in units of h visits O((d / h)^3) cells:
+ *               the grid suits points near the surface; far ones want a coarser grid.
+ *   search      one thread per point.  q = p clamped to the cube [lo, lo + ext]^3, c0 = cell(q).  Rings r = 0, 1, 2, ...
+ *               of cells at Chebyshev distance r from c0, clipped to the grid; a triangle met in several cells is
+ *               evaluated again.  After ring r every triangle not yet seen lies inside the cube and outside the block of
+ *               rings <= r, hence (projection onto the convex cube) at squared distance >= |p - q|^2 + (r h)^2.  The
+ *               search stops when the best d2 is STRICTLY below (1 - 2^-16) |p - q|^2 + (max(r - 1/64, 0) h)^2: equality
+ *               goes on, or a smaller face index at equal distance would be lost; the two factors keep the bound
+ *               conservative under the fp32 rounding of the cell assignment of points and boxes (h >= ext / 256 is far
+ *               above an ulp of ext) and of d2 itself for a far point.  It ends at the latest when the block covers the
+ *               grid.  Every loop is bounded by G or a CSR row clamped to [0, M]; no spin wait, no dependence between
+ *               workgroups.  tt_dist_keys writes key(c0) (N) int64 (-1 for a point that is not finite): the host may
+ *               sort it (stable) and pass the permutation as `order` (N) int64 -- thread t then serves point order[t]
+ *               and writes row order[t]; order = NULL serves point t.
+ *   backward    tt_dist_bwd, the face and its barycentrics fixed (envelope theorem): with c = sum b_k v_k,
+ *               grad_points[i] = 2 g_i (p - c) is written, grad_v_pos[t_pos_idx[face, k]] += -2 g_i b_k (p - c) by float
+ *               atomicAdd (the caller zeroes grad_v_pos; the sum's last bits depend on arrival order).  Either output
+ *               may be NULL.  A row with face outside [0, T) writes zeros and adds nothing.
+ *   sampler     a deterministic sample set with every point of the surface within `spacing` of a sample: face f with
+ *               fp32 longest edge L_f (squares, sums and the root each rounded to fp32) gets k_f = max(1,
+ *               ceil(L_f / spacing)) and the samples a + (i/k)(b - a) + (j/k)(c - a), i, j >= 0, i + j <= k:
+ *               (k+1)(k+2)/2 of them, ordered face-major, then i, then j (a sub-triangle has edges <= spacing).
+ *               tt_dist_sample_count writes offsets (T+1) int64, the exclusive scan of the counts with the total S at
+ *               [T] (DEVICE memory, read back once; a face's k is capped at 2^17, whose count alone exceeds the limit);
+ *               S > TT_DIST_MAX_SAMPLES is the host's ValueError before anything is allocated.  tt_dist_sample_emit,
+ *               one thread per sample: points (S,3) fp32, face (S) int32.  Shared edges and vertices are sampled more
+ *               than once.
+ * Use: ws = tt_dist_workspace_bytes(G); build_count, read M, build_fill with the same workspace; then any number of
+ * tt_dist_query / tt_dist_bwd.  tt_dist_sample_workspace_bytes(T) sizes the sampler's scan scratch.  Every entry point
+ * validates its arguments before any HIP call (TT_ERR_BAD_ARG); N = 0 does nothing; N, V, T, M <= TT_MESH_MAX_ITEMS.
+ * Out of scope: signed distance, ray casting, a BVH, area weighting. */
+#define TT_DIST_MAX_GRID 256
+#define TT_DIST_MAX_SAMPLES (1 << 26)
+int64_t tt_dist_workspace_bytes(int32_t grid);
+int tt_dist_build_count(const float* v_pos, const int32_t* t_pos_idx, int32_t V, int32_t T, int32_t grid, float lo_x,
+                        float lo_y, float lo_z, float ext, float inv_h, void* workspace, float* records,
+                        int32_t* cell_ptr, int64_t* out_total, void* stream);
+int tt_dist_build_fill(const float* records, int32_t T, int32_t grid, float lo_x, float lo_y, float lo_z, float ext,
+                       float inv_h, void* workspace, const int32_t* cell_ptr, int32_t M, int32_t* cell_tri,
+                       void* stream);
+int tt_dist_keys(const float* points, int32_t N, int32_t grid, float lo_x, float lo_y, float lo_z, float ext,
+                 float inv_h, int64_t* keys, void* stream);
+int tt_dist_query(const float* points, const int64_t* order, int32_t N, const float* records, const int32_t* cell_ptr,
+                  const int32_t* cell_tri, int32_t T, int32_t M, int32_t grid, float lo_x, float lo_y, float lo_z,
+                  float ext, float h, float inv_h, float* d2, int32_t* face, float* bary, void* stream);
+int tt_dist_bwd(const float* points, const float* v_pos, const int32_t* t_pos_idx, const int32_t* face,
+                const float* bary, const float* g_d2, int32_t N, int32_t V, int32_t T, float* grad_points,
+                float* grad_v_pos, void* stream);
+int64_t tt_dist_sample_workspace_bytes(int32_t T);
+int tt_dist_sample_count(const float* v_pos, const int32_t* t_pos_idx, int32_t V, int32_t T, float spacing,
+                         void* workspace, int64_t* offsets, void* stream);
+int tt_dist_sample_emit(const float* v_pos, const int32_t* t_pos_idx, const int64_t* offsets, int32_t V, int32_t T,
+                        float spacing, int32_t S, float* points, int32_t* face, void* stream);
 
 #ifdef __cplusplus
 }

@@ -98,10 +98,12 @@ class MultipromptMeshExporter(Exporter):
     def configure(self, geometry, material, background) -> None:
         super().configure(geometry, material, background)
         self.ctx = raster.RasterizerContext(self.cfg.context_type, None)
-        # Mesh.simplify's arguments; attributes, not Config fields (the Config mirrors the reference's).  With either
-        # set the exported mesh is the simplified mesh[0]; with both None it is the isosurface mesh untouched.
+        # Mesh.simplify's arguments; attributes, not Config fields (the Config mirrors the reference's).  With one of
+        # them set the exported mesh is the simplified mesh[0] (more than one is a ValueError at call time); with all
+        # None it is the isosurface mesh untouched.
         self.simplify_grid: Optional[int] = None
         self.simplify_target_faces: Optional[int] = None
+        self.simplify_max_error: Optional[float] = None
         # the tangent-space normal map of the exported mesh (map_Bump, ops.bake_normal_map) on the obj-mtl path with
         # save_texture, and the number of projection steps it takes towards the iso-surface; attributes for the same
         # reason.  Unset, params are exactly what they are without the bake.
@@ -111,6 +113,11 @@ class MultipromptMeshExporter(Exporter):
 
     @torch.no_grad()
     def __call__(self, space_cache) -> List[ExporterOutput]:
+        simplify = {"grid": self.simplify_grid, "target_faces": self.simplify_target_faces,
+                    "max_error": self.simplify_max_error}
+        if sum(v is not None for v in simplify.values()) > 1:
+            raise ValueError("multiprompt-mesh-exporter: set at most one of simplify_grid, simplify_target_faces and "
+                             "simplify_max_error")
         isosurface = getattr(self.geometry, "isosurface", None)
         if isosurface is None:
             raise RuntimeError("geometry.isosurface is not set: configure a generative-space-mesh-rasterize-renderer "
@@ -118,8 +125,8 @@ class MultipromptMeshExporter(Exporter):
         mesh = isosurface(space_cache)
         if type(mesh) == list:
             mesh = mesh[0]
-        if self.simplify_grid is not None or self.simplify_target_faces is not None:
-            mesh = mesh.simplify(grid=self.simplify_grid, target_faces=self.simplify_target_faces)
+        if any(v is not None for v in simplify.values()):
+            mesh = mesh.simplify(**simplify)
         # the texture belongs to mesh[0]: decode it from the first prompt's slice of the space cache
         space_cache = prompt_slice(space_cache, 0)
         if self.cfg.fmt == "obj-mtl":

@@ -207,15 +207,102 @@ class Mesh:
             clean_mesh.extras = self.extras
         return clean_mesh
 
-    def simplify(self, grid: Optional[int] = None, target_faces: Optional[int] = None) -> Mesh:
+    @cached_property
+    def triangle_grid(self) -> ops.TriangleGrid:
+        """The mesh's uniform grid for closest-point queries, built on first use from the detached positions (a Mesh
+        whose v_pos is replaced afterwards needs a new Mesh, as for `topology`)."""
+        return ops.TriangleGrid(self.v_pos, self.t_pos_idx)
+
+    def closest_point(self, points: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+        """(d2, face, bary) of the closest point of this mesh to every row of points (N,3): ops.mesh_closest_point on
+        `triangle_grid` (include/tt_abi.h "point-to-mesh distance").  Not differentiable; ops.point_mesh_distance2 is."""
+        return ops.mesh_closest_point(points, self.triangle_grid)
+
+    def _bbox_diagonal(self) -> Tensor:
+        v = self.v_pos.detach()
+        return (v.amax(0) - v.amin(0)).norm()
+
+    def distance_to(self, other: Mesh, spacing: Optional[float] = None, _cache: Optional[dict] = None) -> Dict[str, Any]:
+        """How far this mesh (a) and `other` (b) lie apart, measured on surface samples: both surfaces are sampled so
+        that every surface point is within `spacing` of a sample (ops.mesh_surface_samples; default: the larger
+        bounding-box diagonal / 200) and every sample is sent to the other mesh (ops.mesh_closest_point).  Returns
+        {a_to_b, b_to_a: {max, mean, rms, argmax_point} over the samples -- NOT area-weighted: a face contributes by
+        its lattice, shared edges more than once --, hausdorff: the larger of the two maxima, spacing, n_samples:
+        (S_a, S_b)}.  Distance to a surface is 1-Lipschitz, so the true symmetric Hausdorff distance of the two
+        surfaces is at most hausdorff + spacing (and at least hausdorff)."""
+        if not isinstance(other, Mesh):
+            raise TypeError(f"other must be a Mesh, got {type(other).__name__}")
+        if spacing is None:
+            spacing = float(torch.maximum(self._bbox_diagonal(), other._bbox_diagonal())) / 200.0
+        spacing = ops._chk_spacing(spacing)
+        cache = {} if _cache is None else _cache  # simplify(max_error=): one side's samples and grid serve every probe
+        sides = []
+        for key, m in (("a", self), ("b", other)):
+            if key not in cache:
+                cache[key] = (ops.mesh_surface_samples(m.v_pos, m.t_pos_idx, spacing)[0], m.triangle_grid)
+            sides.append(cache[key])
+        (sa, ga), (sb, gb) = sides
+        a_to_b, b_to_a = ops.one_sided_distance(sa, gb), ops.one_sided_distance(sb, ga)
+        return {"a_to_b": a_to_b, "b_to_a": b_to_a, "hausdorff": max(a_to_b["max"], b_to_a["max"]),
+                "spacing": spacing, "n_samples": (sa.shape[0], sb.shape[0])}
+
+    def _simplify_max_error(self, max_error: float) -> Mesh:
+        """The bisection of simplify(max_error=): the smallest grid in 2..256 the bisection finds whose result passes
+        hausdorff + spacing <= max_error, spacing = max_error / 4, both directions measured per probe."""
+        spacing = max_error / 4.0
+        cache: dict = {}
+        lo, hi, best = 2, 257, None  # every grid below lo failed; hi passed (257: none has yet)
+        while lo < hi:
+            mid = (lo + hi) // 2
+            probe = ops.mesh_simplify(self.v_pos, self.t_pos_idx, mid)
+            if probe[2]["unchanged"]:
+                return self
+            err = None
+            if probe[1].shape[0] > 0:
+                cache.pop("a", None)
+                err = Mesh(probe[0], probe[1]).distance_to(self, spacing, _cache=cache)
+            if err is not None and err["hausdorff"] + spacing <= max_error:
+                hi, best = mid, (probe, err)
+            else:
+                lo = mid + 1
+        if best is None:
+            return self
+        (v_pos, t_pos_idx, info), err = best
+        mesh = Mesh(v_pos, t_pos_idx)
+        mesh.extras = dict(self.extras)
+        mesh.extras["simplify"] = {k: info[k] for k in ("grid", "cell", "n_clusters", "vertex_map")}
+        mesh.extras["simplify"]["error"] = dict(err, max_error=max_error)
+        return mesh
+
+    def simplify(self, grid: Optional[int] = None, target_faces: Optional[int] = None,
+                 max_error: Optional[float] = None) -> Mesh:
         """A low-poly copy for export: vertex clustering on a grid^3 lattice with quadric-error placement
-        (ops.mesh_simplify; include/tt_abi.h "mesh simplification").  Exactly one of `grid` (2..1024) and
-        `target_faces` must be given; target_faces bisects over grids 2..256 for the largest one whose result has at
+        (ops.mesh_simplify; include/tt_abi.h "mesh simplification").  Exactly one of `grid` (2..1024), `target_faces`
+        and `max_error` must be given; target_faces bisects over grids 2..256 for the largest one whose result has at
         most that many faces (at most 8 runs; the grid-2 result when even that has more).  A new Mesh that inherits
         extras, with extras["simplify"] = {grid, cell, n_clusters, vertex_map}; the mesh itself comes back when it has
-        no vertices, faces or extent.  The result never requires grad.  Not guaranteed manifold."""
-        if (grid is None) == (target_faces is None):
-            raise ValueError("simplify: give exactly one of grid and target_faces")
+        no vertices, faces or extent.  The result never requires grad.  Not guaranteed manifold.
+
+        max_error (a finite positive length) bounds the deviation instead: with spacing = max_error / 4 the full mesh
+        is sampled and gridded once, and grids 2..256 are bisected (8 runs) for the coarsest whose result r has
+        r.distance_to(self)["hausdorff"] + spacing <= max_error, both directions measured per probe -- so the symmetric
+        Hausdorff distance between the two surfaces is at most max_error.  The returned mesh is always one whose check
+        passed (the mesh itself if none did) and carries the measurement as a fifth key, extras["simplify"]["error"] =
+        that distance_to dict (a = the result, b = this mesh) plus max_error.  The bisection assumes that the deviation
+        falls as the grid grows, as target_faces assumes for the face count: the result meets the budget but need not
+        be the coarsest possible.  A max_error so small that its sampling exceeds TT_DIST_MAX_SAMPLES is a ValueError."""
+        if sum(x is not None for x in (grid, target_faces, max_error)) != 1:
+            raise ValueError("simplify: give exactly one of grid, target_faces and max_error")
+        if max_error is not None:
+            try:
+                ok = not isinstance(max_error, bool) and 0.0 < float(max_error) < float("inf")
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError(f"max_error must be a finite positive number, got {max_error!r}")
+            if 0 in (self.v_pos.shape[0], self.t_pos_idx.shape[0]):
+                return self
+            return self._simplify_max_error(float(max_error))
         if grid is not None:
             result = ops.mesh_simplify(self.v_pos, self.t_pos_idx, grid)
         else:

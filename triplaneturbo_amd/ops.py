@@ -1388,6 +1388,185 @@ def mesh_simplify(v_pos: Tensor, t_pos_idx: Tensor, grid: int, lam: float = SIMP
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# point-to-mesh distance (include/tt_abi.h, "point-to-mesh distance"): closest point on a triangle mesh, surface samples
+def dist_default_grid(n_faces: int) -> int:
+    """The grid a TriangleGrid takes when the caller names none: clamp(ceil(sqrt(T) / 8), 1, TT_DIST_MAX_GRID), about two (cell, triangle) pairs
+    per triangle; the fastest of the grids measured on both loads of profiles/mesh_distance.json."""
+    return int(min(max(int(np.ceil(np.sqrt(float(n_faces)) / 8.0)), 1), _lib.TT_DIST_MAX_GRID))
+
+
+def _chk_mesh(v_pos: Tensor, t_pos_idx: Tensor, what: str) -> Tuple[Tensor, Tensor]:
+    """A mesh as the tt_dist_* kernels take it: v_pos (V,3) fp32 detached, t_pos_idx (T,3) int32, V, T >= 1 and within
+    TT_MESH_MAX_ITEMS.  The index range and the positions' finiteness are the caller's one read-back."""
+    v_pos = _chk(v_pos, "v_pos", (None, 3)).detach()
+    t_pos_idx = _chk_index(t_pos_idx, "t_pos_idx", 3)
+    if v_pos.shape[0] < 1 or t_pos_idx.shape[0] < 1:
+        raise ValueError(f"{what}: the mesh needs at least one vertex and one face, got V={v_pos.shape[0]}, "
+                         f"T={t_pos_idx.shape[0]}")
+    _chk_size(f"mesh too large for {what}", V=v_pos.shape[0], T=t_pos_idx.shape[0])
+    return v_pos, t_pos_idx.int().contiguous()
+
+
+class TriangleGrid:
+    """The uniform grid of a triangle mesh for ops.mesh_closest_point / ops.point_mesh_distance2, built once per mesh
+    (tt_dist_build_count / _fill; one 8-byte read-back for the number of (cell, triangle) pairs): 48-byte triangle
+    records, the cell -> triangle CSR (cell_ptr, cell_tri), the cube (lo, ext, h, inv_h) and G; keeps the detached
+    v_pos and the int32 t_pos_idx it was built from.  grid=None takes dist_default_grid(T); grid=1 is brute force.
+    The answer of a query does not depend on the grid, only its cost does."""
+
+    def __init__(self, v_pos: Tensor, t_pos_idx: Tensor, grid: Optional[int] = None):
+        if grid is not None:
+            if isinstance(grid, bool) or not isinstance(grid, int):
+                raise TypeError(f"grid must be an int or None, got {type(grid).__name__}")
+            if not 1 <= grid <= _lib.TT_DIST_MAX_GRID:
+                raise ValueError(f"grid must be in [1, {_lib.TT_DIST_MAX_GRID}], got {grid}")
+        self.v_pos, self.t_pos_idx = _chk_mesh(v_pos, t_pos_idx, "tt_dist_*")
+        V, T, dev = self.v_pos.shape[0], self.t_pos_idx.shape[0], self.v_pos.device
+        G = dist_default_grid(T) if grid is None else grid
+        _chk_size("grid too large for tt_dist_*", cells=G ** 3 + 1)
+        lo_t = self.v_pos.amin(0)
+        box = torch.cat([lo_t.double(), (self.v_pos.amax(0) - lo_t).amax().reshape(1).double(),
+                         _minmax(self.t_pos_idx).double()]).cpu()  # one read-back; every value exact in double
+        _chk_range("t_pos_idx", int(box[4]), int(box[5]), V)
+        if not bool(torch.isfinite(box[:4]).all()):
+            raise ValueError("v_pos holds a value that is not finite")
+        lo, ext = box[:3].float().numpy(), box[3].float().numpy()
+        h, inv_h = ext / np.float32(G), (np.float32(G) / ext if ext > 0 else np.float32(0))
+        if not np.isfinite(inv_h) or (ext > 0 and not h > 0):
+            raise ValueError(f"the mesh's extent {float(ext)} is too small for grid {G} in fp32")
+        self.G, self.lo, self.ext, self.h, self.inv_h = G, [float(x) for x in lo], float(ext), float(h), float(inv_h)
+        ws = _workspace("tt_dist_workspace_bytes", G, device=dev)
+        self.records = torch.empty((T, 3, 4), device=dev, dtype=torch.float32)
+        self.cell_ptr = torch.empty(G ** 3 + 1, device=dev, dtype=torch.int32)
+        total = torch.empty(1, device=dev, dtype=torch.int64)
+        _launch("tt_dist_build_count", self.v_pos, self.t_pos_idx, V, T, G, *self.lo, self.ext, self.inv_h, ws,
+                self.records, self.cell_ptr, total, label="dist_build_count")
+        self.M = int(total.item())
+        _chk_size(f"grid {G} gives too many (cell, triangle) pairs for tt_dist_*: use a coarser grid", M=self.M)
+        self.cell_tri = torch.empty(self.M, device=dev, dtype=torch.int32)
+        _launch("tt_dist_build_fill", self.records, T, G, *self.lo, self.ext, self.inv_h, ws, self.cell_ptr, self.M,
+                self.cell_tri, label="dist_build_fill")
+
+    @property
+    def n_faces(self) -> int:
+        return self.t_pos_idx.shape[0]
+
+
+@torch.no_grad()
+def mesh_closest_point(points: Tensor, tg: TriangleGrid, cell_order: bool = False) -> Tuple[Tensor, Tensor, Tensor]:
+    """The closest point of the mesh in `tg` to every row of points (N,3) fp32 (tt_dist_query): d2 (N,) fp32 the squared
+    distance, face (N,) int32 the lexicographic minimum of (d2, face) over all triangles (equal distance: the smaller
+    face index), bary (N,3) fp32 with the closest point = sum_k bary[k] v_pos[t_pos_idx[face, k]].  Exact, and bit for
+    bit independent of the grid, the order of the points and the launch.  A row with a coordinate that is not finite
+    gives (NaN, -1, 0).  cell_order=True serves the points in the order of their cell key (tt_dist_keys, one stable
+    torch.sort) and writes the rows back in the caller's order: the same answer, a different memory access pattern."""
+    if not isinstance(tg, TriangleGrid):
+        raise TypeError(f"tg must be a TriangleGrid, got {type(tg).__name__}")
+    points = _chk(points, "points", (None, 3)).detach()
+    N, dev = points.shape[0], points.device
+    _chk_size("too many points for tt_dist_query", N=N)
+    d2 = torch.empty(N, device=dev, dtype=torch.float32)
+    face = torch.empty(N, device=dev, dtype=torch.int32)
+    bary = torch.empty((N, 3), device=dev, dtype=torch.float32)
+    if N == 0:
+        return d2, face, bary
+    order = None
+    if cell_order:
+        keys = torch.empty(N, device=dev, dtype=torch.int64)
+        _launch("tt_dist_keys", points, N, tg.G, *tg.lo, tg.ext, tg.inv_h, keys, label="dist_keys")
+        order = torch.sort(keys, stable=True)[1]
+    _launch("tt_dist_query", points, order, N, tg.records, tg.cell_ptr, tg.cell_tri, tg.n_faces, tg.M, tg.G, *tg.lo,
+            tg.ext, tg.h, tg.inv_h, d2, face, bary, label="dist_query")
+    return d2, face, bary
+
+
+class _PointMeshDistance2Fn(torch.autograd.Function):
+    """d2 of ops.mesh_closest_point with the backward tt_dist_bwd: the nearest face and its barycentrics are fixed
+    (envelope theorem), d(d2)/dp = 2 (p - c), d(d2)/dv_k = -2 b_k (p - c)."""
+
+    @staticmethod
+    def forward(ctx, points, v_pos, tg):
+        d2, face, bary = mesh_closest_point(points, tg)
+        ctx.save_for_backward(points.detach(), v_pos.detach(), face, bary)
+        ctx.tri = tg.t_pos_idx
+        return d2
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_d2):
+        points, v_pos, face, bary = ctx.saved_tensors
+        need_p, need_v = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if g_d2 is None or not (need_p or need_v):
+            return None, None, None
+        N, V, T = points.shape[0], v_pos.shape[0], ctx.tri.shape[0]
+        g_p = torch.empty_like(points) if need_p else None
+        g_v = torch.zeros_like(v_pos) if need_v else None
+        if N > 0:
+            _launch("tt_dist_bwd", points, v_pos, ctx.tri, face, bary, g_d2.contiguous(), N, V, T, g_p, g_v,
+                    label="dist_bwd")
+        return g_p, g_v, None
+
+
+def point_mesh_distance2(points: Tensor, v_pos: Tensor, t_pos_idx: Tensor, tg: Optional[TriangleGrid] = None) -> Tensor:
+    """Squared distance d2 (N,) of every row of points (N,3) to the mesh (v_pos, t_pos_idx), differentiable w.r.t.
+    points and v_pos (the nearest face fixed).  `tg`: a TriangleGrid of the same mesh to reuse; else one is built here
+    from the detached positions.  A point that is not finite gives NaN and no gradient."""
+    points = _chk(points, "points", (None, 3))
+    v_pos = _chk(v_pos, "v_pos", (None, 3))
+    if tg is None:
+        tg = TriangleGrid(v_pos, t_pos_idx)
+    elif not isinstance(tg, TriangleGrid):
+        raise TypeError(f"tg must be a TriangleGrid, got {type(tg).__name__}")
+    elif tg.v_pos.shape != v_pos.shape:
+        raise ValueError(f"tg was built for {tg.v_pos.shape[0]} vertices, v_pos has {v_pos.shape[0]}")
+    return _PointMeshDistance2Fn.apply(points, v_pos, tg)
+
+
+def _chk_spacing(spacing) -> float:
+    try:
+        spacing = float(spacing)
+    except (TypeError, ValueError):
+        raise ValueError(f"spacing must be a finite positive number, got {spacing!r}") from None
+    if not 0.0 < spacing < float("inf"):
+        raise ValueError(f"spacing must be a finite positive number, got {spacing!r}")
+    return spacing
+
+
+@torch.no_grad()
+def mesh_surface_samples(v_pos: Tensor, t_pos_idx: Tensor, spacing: float) -> Tuple[Tensor, Tensor]:
+    """A deterministic sample set of the surface with every surface point within `spacing` of a sample
+    (tt_dist_sample_*): face f with longest edge L_f gets the (k+1)(k+2)/2 lattice points of k = max(1, ceil(L_f /
+    spacing)) subdivisions, face-major.  points (S,3) fp32, face (S,) int32.  More than TT_DIST_MAX_SAMPLES samples is a
+    ValueError raised before they are allocated.  Shared edges and vertices are sampled more than once."""
+    spacing = _chk_spacing(spacing)
+    v_pos, tri = _chk_mesh(v_pos, t_pos_idx, "tt_dist_sample_*")
+    V, T, dev = v_pos.shape[0], tri.shape[0], v_pos.device
+    ws = _workspace("tt_dist_sample_workspace_bytes", T, device=dev)
+    offs = torch.empty(T + 1, device=dev, dtype=torch.int64)
+    _launch("tt_dist_sample_count", v_pos, tri, V, T, spacing, ws, offs, label="dist_sample_count")
+    lo, hi, S = (int(x) for x in torch.cat([_minmax(tri).long(), offs[T:]]).cpu())  # one read-back
+    _chk_range("t_pos_idx", lo, hi, V)
+    if S > _lib.TT_DIST_MAX_SAMPLES:
+        raise ValueError(f"spacing {spacing} needs S = {S} samples or more, above TT_DIST_MAX_SAMPLES = "
+                         f"{_lib.TT_DIST_MAX_SAMPLES}: use a larger spacing")
+    points = torch.empty((S, 3), device=dev, dtype=torch.float32)
+    face = torch.empty(S, device=dev, dtype=torch.int32)
+    _launch("tt_dist_sample_emit", v_pos, tri, offs, V, T, spacing, S, points, face, label="dist_sample_emit")
+    return points, face
+
+
+@torch.no_grad()
+def one_sided_distance(samples: Tensor, tg: TriangleGrid) -> dict:
+    """{max, mean, rms, argmax_point} of the distance from `samples` (S,3) to the mesh in `tg`, over the samples as
+    they are (not area-weighted); one read-back."""
+    d = mesh_closest_point(samples, tg)[0].sqrt()
+    i = torch.argmax(d)
+    row = torch.cat([d[i].reshape(1), d.mean().reshape(1), (d * d).mean().sqrt().reshape(1), samples[i]]).double().cpu()
+    return {"max": float(row[0]), "mean": float(row[1]), "rms": float(row[2]),
+            "argmax_point": tuple(float(x) for x in row[3:6])}
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # tangents and normal-map baking (include/tt_abi.h, "tangents and normal-map baking")
 _BAKE_GROUPS = {"pos": _lib.TT_BAKE_GROUP_POS, "tex": _lib.TT_BAKE_GROUP_TEX}
 
