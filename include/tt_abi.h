@@ -1023,7 +1023,7 @@ int tt_bake_encode(const float* rast, const float* v_nrm, const int32_t* t_pos_i
  * Use: ws = tt_dist_workspace_bytes(G); build_count, read M, build_fill with the same workspace; then any number of
  * tt_dist_query / tt_dist_bwd.  tt_dist_sample_workspace_bytes(T) sizes the sampler's scan scratch.  Every entry point
  * validates its arguments before any HIP call (TT_ERR_BAD_ARG); N = 0 does nothing; N, V, T, M <= TT_MESH_MAX_ITEMS.
- * Out of scope: signed distance, ray casting, a BVH, area weighting. */
+ * Out of scope: ray casting, a BVH, area weighting.  The sign of the distance comes from "winding number" below. */
 #define TT_DIST_MAX_GRID 256
 #define TT_DIST_MAX_SAMPLES (1 << 26)
 int64_t tt_dist_workspace_bytes(int32_t grid);
@@ -1046,6 +1046,73 @@ int tt_dist_sample_count(const float* v_pos, const int32_t* t_pos_idx, int32_t V
                          void* workspace, int64_t* offsets, void* stream);
 int tt_dist_sample_emit(const float* v_pos, const int32_t* t_pos_idx, const int64_t* offsets, int32_t V, int32_t T,
                         float spacing, int32_t S, float* points, int32_t* face, void* stream);
+
+/* ---- winding number (tt_wind.hip): generalized winding number of a triangle mesh, exact and by a dipole tree ----
+ * The inside test the distance above lacks (ops.mesh_winding_number, mesh_contains, mesh_signed_distance; shape.MeshOBJ
+ * and ShapeLoss, the reference's libigl-based threestudio/utils/ops.py:482-584).  A mesh is v_pos (V,3) fp32 and
+ * t_pos_idx (T,3) int32 as for the distance; query points are (N,3) fp32; the answer is w (N) fp32.
+ *   pair        the signed solid angle of triangle (a, b, c) seen from p (Van Oosterom-Strackee), in fp32, by ONE device
+ *               function (wind_pair) with one call site per query kernel.  With A = a - p, B = b - p, C = c - p:
+ *               num = A . (B x C), den = |A||B||C| + (A.B)|C| + (B.C)|A| + (C.A)|B|, Omega = 2 atan2(num, den); the atan2
+ *               is the file's own (wind_atan2, about 2 ulp, every select on a single compare: tt_mask.h).
+ *               num == 0 (either sign) contributes exactly 0: a triangle without area, a point in the triangle's plane;
+ *               the sign of a zero never picks +-pi.  Never NaN for finite input (coordinate differences beyond 2^40
+ *               overflow the products; such a pair counts 0).
+ *   w           w(p) = sum_f Omega_f / 4 pi: 1 inside and 0 outside an outward-oriented closed surface (the orientation
+ *               of the marching-cubes, marching-tetrahedra and simplify outputs), fractional near an open one.
+ *   exact       tt_wind_exact: per point the sum over ALL T faces in ascending face order; the pairs fp32, the running
+ *               sum a double, converted to fp32 after the division by 4 pi.  Bit for bit independent of the launch and
+ *               of the order of the points.  One thread per point; the block stages tiles of TT_ITEM_BLOCK 48-byte
+ *               records (three float4: a, b, c, w unused -- the distance grid's layout) in LDS.  A point with a
+ *               coordinate that is not finite gives NaN and takes no part in the pair loop.
+ *   tree        a dense octree over the bounding cube (lo_a = min v_a, ext = the largest extent, as the distance grid)
+ *               with L levels below the root, 0 <= L <= TT_WIND_MAX_LEVELS; G = 2^L leaf cells per axis, inv_h = G / ext
+ *               (0 where ext == 0).  A face belongs to the leaf cell of its centroid ((a + b) + c) * (1/3 in fp32), every
+ *               operation rounded to fp32, cell(x) as for the distance grid.  The Morton key of cell (c_x, c_y, c_z) puts
+ *               bit b of c_x, c_y, c_z at bits 3b+2, 3b+1, 3b.  tt_wind_face_keys writes the records in face order and
+ *               keys (T) int64; the host sorts (key, face) (one stable sort) and gathers the records into that order:
+ *               sorted_records, and leaf_ptr (8^L + 1) int32, the CSR of the leaves.  The faces under node (l, m) are
+ *               then the range leaf_ptr[m 8^(L-l)] .. leaf_ptr[(m+1) 8^(L-l)] of the sorted list.
+ *   node table  level l holds its 8^l nodes in Morton order from node (8^l - 1) / 7 on; tt_wind_node_count(L) =
+ *               (8^(L+1) - 1) / 7 nodes of 8 floats: N_x, N_y, N_z, r, c_x, c_y, c_z, A.  N = sum 1/2 (b-a) x (c-a), the
+ *               sum of the area vectors; A = sum of the areas |1/2 (b-a) x (c-a)|; c the area-weighted centroid
+ *               sum A_f cen_f / A (the plain mean where A == 0); r a bounding radius about the STORED c.  r = -1 marks an
+ *               empty node.  A leaf (one thread per leaf, tt_wind_build's first launch) sums its faces in sorted
+ *               order, r = the largest distance from c to a vertex of its faces.  An inner node (one launch per level,
+ *               bottom up) combines its eight children in child order: N and A summed, c = sum A_k c_k / A, r =
+ *               max_k (|c - c_k| + r_k) over the occupied children.  Per-face terms are fp32, every sum a double rounded
+ *               to fp32 when stored.  No float atomics: two builds give the same bits.
+ *   fast        tt_wind_fast (Barnes-Hut; Barill et al. 2018, the dipole term only), one thread per point, depth first
+ *               from the root: an empty node is skipped; a node with |c-p|^2 > (beta r)^2 (fp32) contributes
+ *               N . (c-p) / |c-p|^3; any other inner node is descended; any other leaf is summed pair by pair over its
+ *               faces in sorted order.  w = sum / 4 pi, accumulated in double in walk order: for a given (L, beta) bit
+ *               for bit independent of the launch and the order of the points.  The walk keeps no stack, its state is
+ *               (l, m): descend (l+1, 8m); advance: while (l > 0 && (m & 7) == 7) { m >>= 3; --l; }, stop at l == 0,
+ *               else ++m.  It visits a node at most once.  beta > 0; a beta whose (beta r)^2 overflows (1e30, inf)
+ *               never takes the far branch and gives the pair sum in sorted order.  tt_wind_point_keys writes the Morton
+ *               key of the leaf cell of every point clamped to the cube (-1 for a point that is not finite): the host
+ *               may sort it and pass the permutation as `order` (N) int64, as for tt_dist_query.
+ *   default L   ops.wind_default_levels(T) = the smallest L with 6 * 4^L >= T, at most 6 (clamp(ceil(log4(T / 6)), 0, 6)):
+ *               about two faces per occupied leaf.  The first rule, 8 faces per occupied leaf, lost to deeper trees on
+ *               every mesh measured, 1.8 k to 473 k faces: 100 k points near the surface of a 28 k-face mesh took 6.1 /
+ *               1.94 / 1.06 ms at L = 4 / 5 / 6, of a 3 040-face torus 3.26 / 1.58 / 0.92 / 0.99 ms at L = 3 .. 6 -- the walk
+ *               waits for one node's 32 bytes at a time and its lanes diverge in the leaves' pair loops, so small leaves
+ *               win until they hold a face or two (profiles/mesh_winding.json).
+ * Every entry point validates its arguments before any HIP call (TT_ERR_BAD_ARG); N = 0 does nothing; N, V, T <=
+ * TT_MESH_MAX_ITEMS; leaf_ptr values are clamped to [0, T] where they are read.
+ * Out of scope: the quadrupole terms, a gradient of w, ray casting, watertightness repair. */
+#define TT_WIND_MAX_LEVELS 6
+int64_t tt_wind_node_count(int32_t levels);
+int tt_wind_face_keys(const float* v_pos, const int32_t* t_pos_idx, int32_t V, int32_t T, int32_t levels, float lo_x,
+                      float lo_y, float lo_z, float ext, float inv_h, float* records, int64_t* keys, void* stream);
+int tt_wind_build(const float* sorted_records, const int32_t* leaf_ptr, int32_t T, int32_t levels, float* nodes,
+                  void* stream);
+int tt_wind_point_keys(const float* points, int32_t N, int32_t levels, float lo_x, float lo_y, float lo_z, float ext,
+                       float inv_h, int64_t* keys, void* stream);
+int tt_wind_exact(const float* points, int32_t N, const float* records, int32_t T, float* out, void* stream);
+int tt_wind_fast(const float* points, const int64_t* order, int32_t N, const float* sorted_records,
+                 const int32_t* leaf_ptr, const float* nodes, int32_t T, int32_t levels, float beta, float* out,
+                 void* stream);
 
 #ifdef __cplusplus
 }

@@ -218,6 +218,27 @@ class Mesh:
         `triangle_grid` (include/tt_abi.h "point-to-mesh distance").  Not differentiable; ops.point_mesh_distance2 is."""
         return ops.mesh_closest_point(points, self.triangle_grid)
 
+    @cached_property
+    def winding_tree(self) -> ops.WindingTree:
+        """The mesh's dipole octree for winding-number queries, built on first use from the detached positions (as
+        `triangle_grid`: a Mesh whose v_pos is replaced afterwards needs a new Mesh)."""
+        return ops.WindingTree(self.v_pos, self.t_pos_idx)
+
+    def winding_number(self, points: Tensor, beta: float = 2.0, exact: bool = False, cell_order: bool = False) -> Tensor:
+        """w (N,) fp32 of this mesh about every row of points (N,3): ops.mesh_winding_number on `winding_tree`
+        (include/tt_abi.h "winding number"); 1 inside, 0 outside for the outward orientation the extractors give."""
+        return ops.mesh_winding_number(points, self.winding_tree, beta=beta, exact=exact, cell_order=cell_order)
+
+    def contains(self, points: Tensor) -> Tensor:
+        """(N,) bool: which rows of points (N,3) lie inside this mesh (winding number above 0.5)."""
+        return ops.mesh_contains(points, self.winding_tree)
+
+    def signed_distance(self, points: Tensor) -> Tensor:
+        """Signed distance (N,) of every row of points (N,3) to this mesh, negative inside (ops.mesh_signed_distance on
+        `triangle_grid` and `winding_tree`); differentiable w.r.t. points and v_pos."""
+        return ops.mesh_signed_distance(points, self.v_pos, self.t_pos_idx, tg=self.triangle_grid,
+                                        tree=self.winding_tree)
+
     def _bbox_diagonal(self) -> Tensor:
         v = self.v_pos.detach()
         return (v.amax(0) - v.amin(0)).norm()

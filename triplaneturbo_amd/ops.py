@@ -1567,6 +1567,179 @@ def one_sided_distance(samples: Tensor, tg: TriangleGrid) -> dict:
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# winding number (include/tt_abi.h, "winding number"): inside test, signed distance
+def wind_default_levels(n_faces: int) -> int:
+    """The octree depth a WindingTree takes when the caller names none: the smallest L with 6 * 4^L >= T, at most
+    TT_WIND_MAX_LEVELS -- clamp(ceil(log4(T / 6)), 0, 6), about two faces per occupied leaf.  The fastest depth of the
+    sweep in profiles/mesh_winding.json on every mesh measured (1.8 k to 473 k faces): the walk is bound by its
+    dependent node loads and a leaf's pair loop, so deeper wins until leaves hold a face or two."""
+    return next((L for L in range(_lib.TT_WIND_MAX_LEVELS) if 6 * 4 ** L >= n_faces), _lib.TT_WIND_MAX_LEVELS)
+
+
+def _chk_beta(beta) -> float:
+    if isinstance(beta, bool) or not isinstance(beta, (int, float)) or not beta > 0:  # NaN fails the comparison
+        raise ValueError(f"beta must be a positive number, got {beta!r}")
+    return float(beta)
+
+
+class WindingTree:
+    """The dipole octree of a triangle mesh for ops.mesh_winding_number / mesh_contains / mesh_signed_distance, built
+    once per mesh (tt_wind_face_keys, one stable sort, tt_wind_build; one read-back for the box and the index range):
+    `records` (T,3,4) in face order (the exact sum), `sorted_records` in (Morton key, face) order with `face_order`
+    (T,) int32 the face of every sorted row, `leaf_ptr` (8^L + 1) int32, `nodes` (n_nodes, 8) fp32 = N, r, c, A per
+    node (r = -1: empty), level l from row (8^l - 1) / 7 on.  levels=None takes wind_default_levels(T); levels=0 is a
+    root whose one leaf holds every face.  Keeps the detached v_pos and the int32 t_pos_idx it was built from."""
+
+    def __init__(self, v_pos: Tensor, t_pos_idx: Tensor, levels: Optional[int] = None):
+        if levels is not None:
+            if isinstance(levels, bool) or not isinstance(levels, int):
+                raise TypeError(f"levels must be an int or None, got {type(levels).__name__}")
+            if not 0 <= levels <= _lib.TT_WIND_MAX_LEVELS:
+                raise ValueError(f"levels must be in [0, {_lib.TT_WIND_MAX_LEVELS}], got {levels}")
+        self.v_pos, self.t_pos_idx = _chk_mesh(v_pos, t_pos_idx, "tt_wind_*")
+        V, T, dev = self.v_pos.shape[0], self.t_pos_idx.shape[0], self.v_pos.device
+        L = wind_default_levels(T) if levels is None else levels
+        lo_t = self.v_pos.amin(0)
+        box = torch.cat([lo_t.double(), (self.v_pos.amax(0) - lo_t).amax().reshape(1).double(),
+                         _minmax(self.t_pos_idx).double()]).cpu()  # one read-back; every value exact in double
+        _chk_range("t_pos_idx", int(box[4]), int(box[5]), V)
+        if not bool(torch.isfinite(box[:4]).all()):
+            raise ValueError("v_pos holds a value that is not finite")
+        lo, ext = box[:3].float().numpy(), box[3].float().numpy()
+        inv_h = np.float32(1 << L) / ext if ext > 0 else np.float32(0)
+        if not np.isfinite(inv_h):
+            raise ValueError(f"the mesh's extent {float(ext)} is too small for {L} levels in fp32")
+        self.L, self.lo, self.ext, self.inv_h = L, [float(x) for x in lo], float(ext), float(inv_h)
+        self.records = torch.empty((T, 3, 4), device=dev, dtype=torch.float32)
+        keys = torch.empty(T, device=dev, dtype=torch.int64)
+        _launch("tt_wind_face_keys", self.v_pos, self.t_pos_idx, V, T, L, *self.lo, self.ext, self.inv_h, self.records,
+                keys, label="wind_face_keys")
+        self.leaf_ptr, self.face_order = _csr(keys, None, 8 ** L, T)
+        self.sorted_records = self.records if L == 0 else self.records[self.face_order.long()].contiguous()
+        self.nodes = torch.empty((int(_lib.load().tt_wind_node_count(L)), 8), device=dev, dtype=torch.float32)
+        _launch("tt_wind_build", self.sorted_records, self.leaf_ptr, T, L, self.nodes, label="wind_build")
+
+    @property
+    def n_faces(self) -> int:
+        return self.t_pos_idx.shape[0]
+
+    def level(self, l: int) -> Tensor:
+        """The (8^l, 8) rows of level l of the node table."""
+        base = (8 ** l - 1) // 7
+        return self.nodes[base:base + 8 ** l]
+
+    def node_ranges(self, l: int) -> Tensor:
+        """(8^l, 2) int32: the range of sorted faces under every node of level l."""
+        ptr = self.leaf_ptr[::8 ** (self.L - l)]
+        return torch.stack([ptr[:-1], ptr[1:]], 1)
+
+
+def _wind_records(v_pos: Tensor, t_pos_idx: Tensor) -> Tensor:
+    """The (T,3,4) records of a mesh in face order, which is all the exact sum reads: tt_wind_face_keys with a box
+    without extent (every key 0, dropped); one read-back for the index range.  No sort, no node table."""
+    v_pos, tri = _chk_mesh(v_pos, t_pos_idx, "tt_wind_*")
+    V, T = v_pos.shape[0], tri.shape[0]
+    lo, hi = (int(x) for x in _minmax(tri).cpu())
+    _chk_range("t_pos_idx", lo, hi, V)
+    records = torch.empty((T, 3, 4), device=v_pos.device, dtype=torch.float32)
+    _launch("tt_wind_face_keys", v_pos, tri, V, T, 0, 0.0, 0.0, 0.0, 0.0, 0.0, records,
+            torch.empty(T, device=v_pos.device, dtype=torch.int64), label="wind_face_keys")
+    return records
+
+
+def _wind_tree(v_pos_or_tree, t_pos_idx, levels: Optional[int] = None) -> WindingTree:
+    if isinstance(v_pos_or_tree, WindingTree):
+        if t_pos_idx is not None:
+            raise ValueError("t_pos_idx goes with v_pos, not with a WindingTree")
+        return v_pos_or_tree
+    if not isinstance(v_pos_or_tree, torch.Tensor):
+        raise TypeError(f"expected v_pos or a WindingTree, got {type(v_pos_or_tree).__name__}")
+    if t_pos_idx is None:
+        raise TypeError("v_pos needs t_pos_idx")
+    return WindingTree(v_pos_or_tree, t_pos_idx, levels)
+
+
+@torch.no_grad()
+def mesh_winding_number(points: Tensor, v_pos_or_tree, t_pos_idx: Optional[Tensor] = None, beta: float = 2.0,
+                        exact: bool = False, cell_order: bool = False) -> Tensor:
+    """The generalized winding number w (N,) fp32 of the mesh about every row of points (N,3) fp32: 1 inside and 0
+    outside an outward-oriented closed surface.  `v_pos_or_tree`: a WindingTree to reuse, or v_pos with t_pos_idx (a tree
+    is built here; for exact=True only the face records, no tree).  exact=True sums every face (tt_wind_exact): bit for bit independent
+    of the launch and the order of the points.  Otherwise the tree's dipole approximation (tt_wind_fast): nodes
+    farther than beta bounding radii contribute N . (c - p) / (4 pi |c - p|^3); for a given (levels, beta) as
+    independent.  cell_order=True serves the points in the order of their leaf cell (tt_wind_point_keys, one stable
+    sort): the same bits.  A row with a coordinate that is not finite gives NaN."""
+    beta = _chk_beta(beta)
+    if exact and isinstance(v_pos_or_tree, torch.Tensor) and t_pos_idx is not None:
+        tree, records = None, _wind_records(v_pos_or_tree, t_pos_idx)
+    else:
+        tree = _wind_tree(v_pos_or_tree, t_pos_idx)
+        records = tree.records
+    points = _chk(points, "points", (None, 3)).detach()
+    N, dev = points.shape[0], points.device
+    _chk_size("too many points for tt_wind_*", N=N)
+    w = torch.empty(N, device=dev, dtype=torch.float32)
+    if N == 0:
+        return w
+    if exact:
+        _launch("tt_wind_exact", points, N, records, records.shape[0], w, label="wind_exact")
+        return w
+    order = None
+    if cell_order:
+        keys = torch.empty(N, device=dev, dtype=torch.int64)
+        _launch("tt_wind_point_keys", points, N, tree.L, *tree.lo, tree.ext, tree.inv_h, keys, label="wind_point_keys")
+        order = torch.sort(keys, stable=True)[1]
+    _launch("tt_wind_fast", points, order, N, tree.sorted_records, tree.leaf_ptr, tree.nodes, tree.n_faces, tree.L,
+            beta, w, label="wind_fast")
+    return w
+
+
+def mesh_contains(points: Tensor, v_pos_or_tree, t_pos_idx: Optional[Tensor] = None, beta: float = 2.0,
+                  exact: bool = False, cell_order: bool = False) -> Tensor:
+    """(N,) bool: w > 0.5 of ops.mesh_winding_number (a row that is not finite: False)."""
+    return mesh_winding_number(points, v_pos_or_tree, t_pos_idx, beta, exact, cell_order) > 0.5
+
+
+class _SignedRootFn(torch.autograd.Function):
+    """sign * sqrt(d2) with the sign fixed; the gradient w.r.t. d2 is sign / (2 d), and exactly 0 where d == 0 (so the
+    chain through d(d2)/dp = 2 (p - c) gives sign (p - c) / d, never inf)."""
+
+    @staticmethod
+    def forward(ctx, d2, sign):
+        d = d2.sqrt()
+        ctx.save_for_backward(d, sign)
+        return sign * d
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        d, sign = ctx.saved_tensors
+        return torch.where(d > 0, g * sign / (2 * d), torch.zeros_like(d)), None
+
+
+def mesh_signed_distance(points: Tensor, v_pos: Tensor, t_pos_idx: Tensor, tg: Optional[TriangleGrid] = None,
+                         tree: Optional[WindingTree] = None, beta: float = 2.0) -> Tensor:
+    """Signed distance (N,) of every row of points (N,3) to the mesh, in the field's convention (negative inside):
+    sign * sqrt(d2) with d2 of ops.point_mesh_distance2 and sign = -1 where ops.mesh_winding_number > 0.5, else +1.
+    Differentiable w.r.t. points and v_pos with the sign and the nearest face fixed: the gradient w.r.t. a point is
+    sign (p - c) / d, and exactly 0 where d == 0.  `tg`, `tree`: a TriangleGrid / WindingTree of the same mesh to
+    reuse.  A point that is not finite gives NaN."""
+    beta = _chk_beta(beta)
+    points = _chk(points, "points", (None, 3))
+    v_pos = _chk(v_pos, "v_pos", (None, 3))
+    if tree is None:
+        tree = WindingTree(v_pos, t_pos_idx)
+    elif not isinstance(tree, WindingTree):
+        raise TypeError(f"tree must be a WindingTree, got {type(tree).__name__}")
+    elif tree.v_pos.shape != v_pos.shape:
+        raise ValueError(f"tree was built for {tree.v_pos.shape[0]} vertices, v_pos has {v_pos.shape[0]}")
+    d2 = point_mesh_distance2(points, v_pos, t_pos_idx, tg)
+    inside = mesh_winding_number(points, tree, beta=beta) > 0.5
+    sign = torch.where(inside, -torch.ones_like(d2), torch.ones_like(d2)).detach()
+    return _SignedRootFn.apply(d2, sign)
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # tangents and normal-map baking (include/tt_abi.h, "tangents and normal-map baking")
 _BAKE_GROUPS = {"pos": _lib.TT_BAKE_GROUP_POS, "tex": _lib.TT_BAKE_GROUP_TEX}
 

@@ -78,6 +78,32 @@ def load_normal_map(obj_path: str, device=None) -> Optional[Tensor]:
     return _image_tensor(path, device) if path is not None else None
 
 
+def read_obj_geometry(path: str) -> Tuple[np.ndarray, np.ndarray]:
+    """(v (V,3) float64, f (T,3) int64) of any OBJ file: `v x y z ...` and `f` corners in the forms i, i/j, i/j/k and
+    i//k (only the position index is read; negative indices count back from the last vertex read so far); a polygon
+    becomes the fan (0, k, k+1) about its first corner.  Everything else (vt, vn, groups, materials) is skipped."""
+    v, f = [], []
+    with open(path) as fh:
+        for line in fh:
+            tok = line.split()
+            if not tok:
+                continue
+            if tok[0] == "v":
+                v.append([float(x) for x in tok[1:4]])
+            elif tok[0] == "f":
+                idx = [int(c.split("/")[0]) for c in tok[1:]]
+                if len(idx) < 3:
+                    raise ValueError(f"{path}: a face needs three corners, got {line.strip()!r}")
+                idx = [i - 1 if i > 0 else len(v) + i for i in idx]
+                if min(idx) < 0 or "0" in (c.split("/")[0] for c in tok[1:]):
+                    raise ValueError(f"{path}: index out of range in {line.strip()!r}")
+                f += [[idx[0], idx[k], idx[k + 1]] for k in range(1, len(idx) - 1)]
+    v_arr, f_arr = np.asarray(v, np.float64).reshape(-1, 3), np.asarray(f, np.int64).reshape(-1, 3)
+    if f_arr.size and f_arr.max() >= len(v_arr):
+        raise ValueError(f"{path}: a face names vertex {int(f_arr.max()) + 1} of {len(v_arr)}")
+    return v_arr, f_arr
+
+
 def load_obj(path: str, device=None) -> Tuple[Mesh, Optional[Tensor]]:
     """(mesh, map_Kd) from what export.save_obj writes: `v x y z [r g b]` -> v_pos (and v_rgb), `vt u v` -> v_tex with
     the writer's 1 - v flip undone, `f a/b/c` triangles -> t_pos_idx, t_tex_idx (int32), `mtllib` -> the MTL's map_Kd
