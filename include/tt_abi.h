@@ -1023,7 +1023,8 @@ int tt_bake_encode(const float* rast, const float* v_nrm, const int32_t* t_pos_i
  * Use: ws = tt_dist_workspace_bytes(G); build_count, read M, build_fill with the same workspace; then any number of
  * tt_dist_query / tt_dist_bwd.  tt_dist_sample_workspace_bytes(T) sizes the sampler's scan scratch.  Every entry point
  * validates its arguments before any HIP call (TT_ERR_BAD_ARG); N = 0 does nothing; N, V, T, M <= TT_MESH_MAX_ITEMS.
- * Out of scope: ray casting, a BVH, area weighting.  The sign of the distance comes from "winding number" below. */
+ * Out of scope: a BVH, area weighting.  The sign of the distance comes from "winding number" below, rays from "ray
+ * casting". */
 #define TT_DIST_MAX_GRID 256
 #define TT_DIST_MAX_SAMPLES (1 << 26)
 int64_t tt_dist_workspace_bytes(int32_t grid);
@@ -1100,7 +1101,7 @@ int tt_dist_sample_emit(const float* v_pos, const int32_t* t_pos_idx, const int6
  *               win until they hold a face or two (profiles/mesh_winding.json).
  * Every entry point validates its arguments before any HIP call (TT_ERR_BAD_ARG); N = 0 does nothing; N, V, T <=
  * TT_MESH_MAX_ITEMS; leaf_ptr values are clamped to [0, T] where they are read.
- * Out of scope: the quadrupole terms, a gradient of w, ray casting, watertightness repair. */
+ * Out of scope: the quadrupole terms, a gradient of w, watertightness repair. */
 #define TT_WIND_MAX_LEVELS 6
 int64_t tt_wind_node_count(int32_t levels);
 int tt_wind_face_keys(const float* v_pos, const int32_t* t_pos_idx, int32_t V, int32_t T, int32_t levels, float lo_x,
@@ -1113,6 +1114,97 @@ int tt_wind_exact(const float* points, int32_t N, const float* records, int32_t 
 int tt_wind_fast(const float* points, const int64_t* order, int32_t N, const float* sorted_records,
                  const int32_t* leaf_ptr, const float* nodes, int32_t T, int32_t levels, float beta, float* out,
                  void* stream);
+
+/* ---- ray casting (tt_ray.hip): closest hit and any hit of rays with a triangle mesh, an ambient-occlusion count ----
+ * The query behind ops.mesh_ray_cast / mesh_ray_occluded / ray_mesh_depth, Mesh.ray_cast and the ambient-occlusion map
+ * of a simplified export (ops.bake_ambient_occlusion, map_Ka).  The reference has no such step.  The mesh is the
+ * TriangleGrid of "point-to-mesh distance" above, unchanged: records (T,3,4), cell_ptr (G^3 + 1), cell_tri (M), lo, ext,
+ * h, inv_h, G.  A ray is a row o of origins (N,3) and a row d of dirs (N,3), fp32; d has any length, t is in units of d;
+ * t_max is one fp32 per call, >= 0, +inf allowed.  Hits have 0 <= t <= t_max.
+ *   pair        ONE device function (ray_pair) with one call site (ray_walk), shared by the three kernels: the
+ *               watertight test of Woop, Benthin and Wald (JCGT 2013) in fp32.  kz = argmax |d| (the lowest index at
+ *               equal magnitude), kx, ky the next two axes cyclically, swapped when d[kz] < 0; Sx = d[kx] / d[kz],
+ *               Sy = d[ky] / d[kz], Sz = 1 / d[kz].  Per vertex A = a - o, Ax = A[kx] - Sx A[kz], Ay = A[ky] - Sy A[kz],
+ *               likewise B, C.  U = Cx By - Cy Bx, V = Ax Cy - Ay Cx, W = Bx Ay - By Ax, each of the six products and three
+ *               differences rounded on its own (a contracted a b - c d is not antisymmetric; watertightness rests on the
+ *               two triangles of an edge seeing the same magnitude with opposite sign; the file rounds every operation
+ *               of the pair on its own, so an fp32 restatement gives the same bits).  If any of U, V, W is exactly 0 all
+ *               three are recomputed from the same fp32 operands in double and rounded to fp32.  A miss when some of
+ *               U, V, W are < 0 and some > 0; a miss when det = (U + V) + W == 0 (a ray in the triangle's plane, a
+ *               triangle without area) or is not finite (overflow).  t = ((U Az + V Bz) + W Cz) / det with Az = Sz A[kz];
+ *               a miss unless 0 <= t <= t_max.  A pair accepted so far is still a miss when the face's fp32 edge vectors
+ *               b - a and c - a are exactly parallel (their cross product, the products taken exactly in double, is
+ *               (0, 0, 0): equal vertices, exactly collinear ones): det is rounding noise on such a face, and a ray that
+ *               passes within rounding of its line would hit it.  Barycentrics (U, V, W) / det, each >= 0.  Both sides
+ *               of a triangle are hit.  Finite input never gives NaN: every NaN on the way is a miss.
+ *   answer      per ray the lexicographic minimum of (t, face) over ALL T triangles: equal t goes to the smaller face
+ *               index.  t (N) fp32, face (N) int32, bary (N,3) fp32; a miss is (+inf, -1, 0).  It does not depend on
+ *               the grid, on the order inside a cell, on the order of the rays or on the launch, bit for bit.  A row
+ *               with a coordinate that is not finite, or whose largest |d| component is below FLT_MIN (d == 0, and a
+ *               denormal direction, whose reciprocal overflows), is (NaN, -1, 0) and leaves the kernel before the walk.
+ *   walk        one thread per ray, no stack, no incremental DDA state: slices of cells along the dominant axis
+ *               ka = kz.  S = ext + max_a |o_a - centre_a| + max_a |centre_a| (centre = lo + ext / 2) is the scale of
+ *               every coordinate the walk forms; tol = 2^-16 S.  The ray's span [t_lo, t_hi] is [0, t_max] cut by the
+ *               three slabs [lo_a - tol, lo_a + ext + tol] (each bound (plane - o_a) / d_a moved outward by 2^-16 |t|;
+ *               an axis with d_a == 0 only decides whether the ray is outside, which ends the ray).  For j = 0 .. G-1,
+ *               k = j (d[ka] > 0) or G-1-j: the planes lo[ka] + k h and lo[ka] + (k+1) h, their parameters ordered as
+ *               [ta, tb], dilated to s = ta - (2^-16 |ta| + tol / |d[ka]|), e = tb + (2^-16 |tb| + tol / |d[ka]|); the
+ *               first slice has s = -inf, the last e = +inf (inf - inf opens likewise).  s > t_hi ends the walk.
+ *               [t0, t1] = [s, e] cut by the span; if it is not empty, on each lateral axis b the ray's coordinates
+ *               o_b + t0 d_b and o_b + t1 d_b (o_b itself where d_b == 0), their minimum lowered and their maximum
+ *               raised by tol, go through the grid's own cell() -- the monotone function the triangles were binned
+ *               with (here with its clamp taken before the conversion, so that an infinity lands on a cell) -- and
+ *               give the cell range.  Every triangle of every cell of that rectangle is tested against the ray; a hit
+ *               is accepted whatever cell it falls in; (t, face) is minimised.  After a slice the walk stops when the
+ *               best t is STRICTLY below s: equality goes on.  tt_ray_any and tt_ray_ao leave at the first accepted
+ *               pair instead.  G = 1 is brute force through the same code.
+ *   why it is   Let the pair accept triangle f at the fp32 value t.  P = the point of f nearest to R(t) = o + t d (in
+ *   conservative exact arithmetic).  The pair's t is within 2^-20 (L + |o|) / |d| of the exact parameter (measured 2.4e-7 of
+ *               that scale, tests/ray_reference.py), so |R(t) - P| <= eps = 2^-19 S.  P lies in f's box, so by the
+ *               monotonicity of cell() f is a member of cell(P) on every axis.  Slice: with kk = cell(P_ka), P_ka lies
+ *               between the planes of kk up to delta, the disagreement of lo + k h with the boundary cell() implies:
+ *               a few ulp of |lo| + ext, delta <= 2^-21 S.  Then t lies within (delta + eps) / |d[ka]| of the exact
+ *               [ta, tb]; the fp32 ta, tb carry three roundings (2^-22 |t|) and the rounding of plane - o
+ *               (2^-23 S / |d[ka]|): all inside the dilation 2^-16 |t| + 2^-16 S / |d[ka]|, by a factor of four.
+ *               t is in [0, t_max] as an fp32 fact, and in the span since R(t) is within eps < tol of the cube.
+ *               Lateral: t in [t0, t1] puts the exact o_b + t d_b between the two end values; the fp32 end values are
+ *               off by at most 2^-23 (|o_b| + |t d_b|) <= 2^-21 S (|t d_b| <= |t d_ka| <= |o_ka| + |centre| + ext inside
+ *               the span), and P_b is within eps of it: 2^-21 S + 2^-19 S < tol, so cell(min - tol) <= cell(P_b) <=
+ *               cell(max + tol).  Order: s does not decrease with j (every operation on the way is monotone), so a
+ *               pair first met in a later slice has t >= that slice's s >= this slice's s.  The first constant
+ *               tried, 2^-18 in tol, left a factor below two against eps; extra cells cost time only.
+ *   loops       bounded by G (slices, the two lateral ranges) or by a CSR row clamped to [0, M]; cell ids come from
+ *               clamped coordinates; no spin wait, no float atomics, no dependence between workgroups, no scratch.
+ *   tt_ray_cast   origins, dirs, order (N) int64 or NULL as for tt_dist_query (the host may sort tt_dist_keys of the
+ *               origins), N, t_max, the grid; writes t, face, bary.
+ *   tt_ray_any    the same inputs; hit (N) uint8 = 1 where some triangle is hit in [0, t_max], which does not depend on
+ *               the grid; a row that is not usable gives 0.
+ *   tt_ray_ao     points (N,3), normals (N,3) of any non-zero length, dirs_local (K,3) fp32, 1 <= K <= TT_RAY_MAX_DIRS,
+ *               bias (finite), max_distance (>= 0, +inf allowed), the grid; hits (N) int32.  n^ = the normal divided by
+ *               its largest |component|, then by its length.  Ray (i, k) starts at p_i + bias n^_i and runs along
+ *               x T + y B + z n^ with (x, y, z) = dirs_local[k] and (T, B) the branch-free orthonormal basis of Duff et
+ *               al. 2017 about n^ (every operation fp32, rounded on its own); t_max = max_distance.  hits[i] = the
+ *               number of the K rays with any hit: ray r = i K + k is thread r, so the rays of a point sit in adjacent
+ *               lanes, and the count is by integer atomicAdd onto a zero written by a launch in front -- an integer, so
+ *               the order of arrival cannot show.  The directions are a table from the host: no device sin / cos
+ *               enters the answer.  A point or normal that is not finite, or a zero normal, gives -1.
+ * Every entry point validates its arguments before any HIP call (TT_ERR_BAD_ARG); N = 0 does nothing; N, T <=
+ * TT_MESH_MAX_ITEMS, 1 <= G <= TT_DIST_MAX_GRID.
+ * Out of scope: a BVH, per-ray t_max, bent normals, a backward kernel (ops.ray_mesh_depth differentiates the plane
+ * formula of the hit face in torch: the query is the hot path). */
+#define TT_RAY_MAX_DIRS 1024
+int tt_ray_cast(const float* origins, const float* dirs, const int64_t* order, int32_t N, float t_max,
+                const float* records, const int32_t* cell_ptr, const int32_t* cell_tri, int32_t T, int32_t M,
+                int32_t grid, float lo_x, float lo_y, float lo_z, float ext, float h, float inv_h, float* t,
+                int32_t* face, float* bary, void* stream);
+int tt_ray_any(const float* origins, const float* dirs, const int64_t* order, int32_t N, float t_max,
+               const float* records, const int32_t* cell_ptr, const int32_t* cell_tri, int32_t T, int32_t M,
+               int32_t grid, float lo_x, float lo_y, float lo_z, float ext, float h, float inv_h, uint8_t* hit,
+               void* stream);
+int tt_ray_ao(const float* points, const float* normals, const float* dirs_local, int32_t N, int32_t K, float bias,
+              float max_distance, const float* records, const int32_t* cell_ptr, const int32_t* cell_tri, int32_t T,
+              int32_t M, int32_t grid, float lo_x, float lo_y, float lo_z, float ext, float h, float inv_h,
+              int32_t* hits, void* stream);
 
 #ifdef __cplusplus
 }

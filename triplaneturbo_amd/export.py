@@ -110,6 +110,13 @@ class MultipromptMeshExporter(Exporter):
         self.bake_normal_map: bool = False
         self.bake_project_steps: int = 2
         self.bake_info: Optional[Dict[str, Any]] = None  # ops.bake_normal_map's info of the last bake
+        # the ambient-occlusion map of the exported mesh (map_Ka, ops.bake_ambient_occlusion: the simplified mesh when
+        # a simplify attribute is set) on the same path: its rays per texel and their length (None: a quarter of the
+        # bounding-box diagonal).  Unset, params carry no "map_Ka" key and every other map is what it is without it.
+        self.bake_ambient_occlusion: bool = False
+        self.ao_rays: int = 64
+        self.ao_distance: Optional[float] = None
+        self.ao_info: Optional[Dict[str, Any]] = None  # ops.bake_ambient_occlusion's info of the last bake
 
     @torch.no_grad()
     def __call__(self, space_cache) -> List[ExporterOutput]:
@@ -194,6 +201,10 @@ class MultipromptMeshExporter(Exporter):
                 bump, self.bake_info = ops.bake_normal_map(mesh, field, N, project_steps=self.bake_project_steps,
                                                            max_step=self._bake_max_step(mesh), rast=rast)
                 params["map_Bump"] = uv_padding(bump)
+            if self.bake_ambient_occlusion:
+                ao, self.ao_info = ops.bake_ambient_occlusion(mesh, N, n_rays=self.ao_rays,
+                                                              max_distance=self.ao_distance, rast=rast)
+                params["map_Ka"] = uv_padding(ao)
         return [ExporterOutput(save_name=f"{self.cfg.save_name}.obj", save_type="obj", params=params)]
 
     def export_obj(self, mesh, space_cache) -> List[ExporterOutput]:
@@ -354,8 +365,9 @@ def _save_obj_text(path: str, v_pos, t_pos_idx, v_nrm=None, v_tex=None, t_tex_id
 
 
 def _save_mtl(path: str, matname: str, Ka=(0.0, 0.0, 0.0), Kd=(1.0, 1.0, 1.0), Ks=(0.0, 0.0, 0.0), map_Kd=None,
-              map_Ks=None, map_Bump=None, map_Pm=None, map_Pr=None, map_format: str = "jpg") -> List[str]:
-    """saving.py:596-691: the MTL text and the texture images next to it."""
+              map_Ks=None, map_Bump=None, map_Pm=None, map_Pr=None, map_format: str = "jpg", map_Ka=None) -> List[str]:
+    """saving.py:596-691: the MTL text and the texture images next to it.  map_Ka (not in the reference): the
+    ambient-occlusion map, written as gray texture_ao.<fmt>."""
     d = os.path.dirname(path)
     paths = [path]
     mtl = f"newmtl {matname}\n"
@@ -379,6 +391,9 @@ def _save_mtl(path: str, matname: str, Ka=(0.0, 0.0, 0.0), Kd=(1.0, 1.0, 1.0), K
     if map_Pr is not None:
         mtl += f"map_Pr texture_roughness.{map_format}\n"
         paths.append(save_image(os.path.join(d, f"texture_roughness.{map_format}"), _gray_u8(map_Pr)))
+    if map_Ka is not None:
+        mtl += f"map_Ka texture_ao.{map_format}\n"
+        paths.append(save_image(os.path.join(d, f"texture_ao.{map_format}"), _gray_u8(map_Ka)))
     with open(path, "w") as f:
         f.write(mtl)
     return paths
@@ -387,7 +402,7 @@ def _save_mtl(path: str, matname: str, Ka=(0.0, 0.0, 0.0), Kd=(1.0, 1.0, 1.0), K
 def save_obj(path: str, mesh, save_mat: bool = False, save_normal: bool = False, save_uv: bool = False,
              save_vertex_color: bool = False, map_Kd: Optional[Tensor] = None, map_Ks: Optional[Tensor] = None,
              map_Bump: Optional[Tensor] = None, map_Pm: Optional[Tensor] = None, map_Pr: Optional[Tensor] = None,
-             map_format: str = "jpg") -> List[str]:
+             map_format: str = "jpg", map_Ka: Optional[Tensor] = None) -> List[str]:
     """saving.py:491-549 as a standalone writer: `path` (".obj" appended if missing), with save_mat the MTL file
     (same name, ".mtl") and its texture images in the same directory.  Takes the exporter's params as keywords.
     Returns the written paths."""
@@ -404,7 +419,7 @@ def save_obj(path: str, mesh, save_mat: bool = False, save_normal: bool = False,
         mtl_path = path.replace(".obj", ".mtl")
         mtllib = os.path.basename(mtl_path)
         paths += _save_mtl(mtl_path, matname, map_Kd=_np(map_Kd), map_Ks=_np(map_Ks), map_Bump=_np(map_Bump),
-                           map_Pm=_np(map_Pm), map_Pr=_np(map_Pr), map_format=map_format)
+                           map_Pm=_np(map_Pm), map_Pr=_np(map_Pr), map_format=map_format, map_Ka=_np(map_Ka))
     paths.append(_save_obj_text(path, v_pos, t_pos_idx, v_nrm=v_nrm, v_tex=v_tex, t_tex_idx=t_tex_idx, v_rgb=v_rgb,
                                 matname=matname, mtllib=mtllib))
     return paths

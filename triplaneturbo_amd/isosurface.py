@@ -239,6 +239,30 @@ class Mesh:
         return ops.mesh_signed_distance(points, self.v_pos, self.t_pos_idx, tg=self.triangle_grid,
                                         tree=self.winding_tree)
 
+    def ray_cast(self, origins: Tensor, dirs: Tensor, t_max: float = float("inf"),
+                 cell_order: bool = False) -> Tuple[Tensor, Tensor, Tensor]:
+        """(t, face, bary) of the closest hit of every ray origins[i] + t dirs[i] with this mesh, 0 <= t <= t_max:
+        ops.mesh_ray_cast on `triangle_grid` (include/tt_abi.h "ray casting").  A miss is (inf, -1, 0).  Not
+        differentiable; ops.ray_mesh_depth is."""
+        return ops.mesh_ray_cast(origins, dirs, self.triangle_grid, t_max=t_max, cell_order=cell_order)
+
+    def occluded(self, origins: Tensor, dirs: Tensor, t_max: float = float("inf")) -> Tensor:
+        """(N,) bool: whether ray i meets this mesh at 0 <= t <= t_max (ops.mesh_ray_occluded on `triangle_grid`)."""
+        return ops.mesh_ray_occluded(origins, dirs, self.triangle_grid, t_max=t_max)
+
+    def ambient_occlusion(self, points: Optional[Tensor] = None, normals: Optional[Tensor] = None, n_rays: int = 64,
+                          max_distance: Optional[float] = None, bias: Optional[float] = None) -> Tensor:
+        """Ambient occlusion (N,) fp32 in [0,1], 1 = open, of `points` with `normals` against this mesh
+        (ops.mesh_ambient_occlusion on `triangle_grid`); with no points given, per vertex with v_nrm."""
+        if points is None:
+            if normals is not None:
+                raise ValueError("normals without points: give both or neither")
+            points, normals = self.v_pos.detach(), self.v_nrm.detach()
+        elif normals is None:
+            raise ValueError("points without normals: give both or neither")
+        return ops.mesh_ambient_occlusion(points, normals, self.triangle_grid, n_rays=n_rays,
+                                          max_distance=max_distance, bias=bias)
+
     def _bbox_diagonal(self) -> Tensor:
         v = self.v_pos.detach()
         return (v.amax(0) - v.amin(0)).norm()

@@ -1740,6 +1740,193 @@ def mesh_signed_distance(points: Tensor, v_pos: Tensor, t_pos_idx: Tensor, tg: O
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# ray casting (include/tt_abi.h, "ray casting"): closest hit, any hit, depth with a gradient, ambient occlusion
+def _chk_t_max(t_max, name: str = "t_max") -> float:
+    try:
+        t_max = float(t_max)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be a number >= 0 (inf allowed), got {t_max!r}") from None
+    if not t_max >= 0.0:
+        raise ValueError(f"{name} must be a number >= 0 (inf allowed), got {t_max!r}")
+    return t_max
+
+
+def _chk_rays(origins: Tensor, dirs: Tensor, tg, what: str) -> Tuple[Tensor, Tensor]:
+    if not isinstance(tg, TriangleGrid):
+        raise TypeError(f"tg must be a TriangleGrid, got {type(tg).__name__}")
+    origins = _chk(origins, "origins", (None, 3)).detach()
+    dirs = _chk(dirs, "dirs", (origins.shape[0], 3)).detach()
+    _chk_size(f"too many rays for {what}", N=origins.shape[0])
+    return origins, dirs
+
+
+def _ray_order(origins: Tensor, tg: "TriangleGrid") -> Tensor:
+    keys = torch.empty(origins.shape[0], device=origins.device, dtype=torch.int64)
+    _launch("tt_dist_keys", origins, origins.shape[0], tg.G, *tg.lo, tg.ext, tg.inv_h, keys, label="dist_keys")
+    return torch.sort(keys, stable=True)[1]
+
+
+def _grid_args(tg: "TriangleGrid") -> tuple:
+    return (tg.records, tg.cell_ptr, tg.cell_tri, tg.n_faces, tg.M, tg.G, *tg.lo, tg.ext, tg.h, tg.inv_h)
+
+
+@torch.no_grad()
+def mesh_ray_cast(origins: Tensor, dirs: Tensor, tg: TriangleGrid, t_max: float = float("inf"),
+                  cell_order: bool = False) -> Tuple[Tensor, Tensor, Tensor]:
+    """The closest hit of every ray origins[i] + t dirs[i] (both (N,3) fp32; dirs of any non-zero length, t in units of
+    dirs) with the mesh in `tg`, 0 <= t <= t_max (tt_ray_cast): t (N,) fp32, face (N,) int32, bary (N,3) fp32 with the
+    hit point = sum_k bary[k] v_pos[t_pos_idx[face, k]].  The answer is the lexicographic minimum of (t, face) over all
+    triangles of a watertight pair test (both sides of a face are hit), bit for bit independent of the grid, the order
+    of the rays and the launch.  A miss is (inf, -1, 0); a row that is not finite or has a zero direction (NaN, -1, 0).
+    cell_order=True serves the rays in the order of their origins' cell keys: the same answer."""
+    origins, dirs = _chk_rays(origins, dirs, tg, "tt_ray_cast")
+    t_max = _chk_t_max(t_max)
+    N, dev = origins.shape[0], origins.device
+    t = torch.empty(N, device=dev, dtype=torch.float32)
+    face = torch.empty(N, device=dev, dtype=torch.int32)
+    bary = torch.empty((N, 3), device=dev, dtype=torch.float32)
+    if N == 0:
+        return t, face, bary
+    order = _ray_order(origins, tg) if cell_order else None
+    _launch("tt_ray_cast", origins, dirs, order, N, t_max, *_grid_args(tg), t, face, bary, label="ray_cast")
+    return t, face, bary
+
+
+@torch.no_grad()
+def mesh_ray_occluded(origins: Tensor, dirs: Tensor, tg: TriangleGrid, t_max: float = float("inf")) -> Tensor:
+    """(N,) bool: whether ray i hits any triangle of the mesh in `tg` at 0 <= t <= t_max (tt_ray_any: the walk of
+    mesh_ray_cast, left at the first hit).  Equal to mesh_ray_cast(...).face >= 0; a row that is not finite is False."""
+    origins, dirs = _chk_rays(origins, dirs, tg, "tt_ray_any")
+    t_max = _chk_t_max(t_max)
+    N = origins.shape[0]
+    hit = torch.empty(N, device=origins.device, dtype=torch.uint8)
+    if N > 0:
+        _launch("tt_ray_any", origins, dirs, None, N, t_max, *_grid_args(tg), hit, label="ray_any")
+    return hit != 0
+
+
+def ray_mesh_depth(origins: Tensor, dirs: Tensor, v_pos: Tensor, t_pos_idx: Tensor, tg: Optional[TriangleGrid] = None,
+                   t_max: float = float("inf")) -> Tensor:
+    """t (N,) of mesh_ray_cast against the mesh (v_pos, t_pos_idx), differentiable w.r.t. origins, dirs and v_pos with
+    the hit face fixed: the value is the kernel's t; the gradient is that of the plane formula t' = n.(a - o) / n.d,
+    n = (b - a) x (c - a), recomputed in torch on the gathered rows (t + (t' - t'.detach())).  Rows that miss are inf
+    with zero gradient.  `tg`: a TriangleGrid of the same mesh to reuse."""
+    origins = _chk(origins, "origins", (None, 3))
+    dirs = _chk(dirs, "dirs", (origins.shape[0], 3))
+    v_pos = _chk(v_pos, "v_pos", (None, 3))
+    if tg is None:
+        tg = TriangleGrid(v_pos, t_pos_idx)
+    elif not isinstance(tg, TriangleGrid):
+        raise TypeError(f"tg must be a TriangleGrid, got {type(tg).__name__}")
+    elif tg.v_pos.shape != v_pos.shape:
+        raise ValueError(f"tg was built for {tg.v_pos.shape[0]} vertices, v_pos has {v_pos.shape[0]}")
+    t, face, _ = mesh_ray_cast(origins, dirs, tg, t_max)
+    hit = face >= 0
+    idx = tg.t_pos_idx[face.clamp(min=0).long()].long()
+    a, b, c = v_pos[idx[:, 0]], v_pos[idx[:, 1]], v_pos[idx[:, 2]]
+    n = torch.linalg.cross(b - a, c - a)
+    den = (n * dirs).sum(-1)
+    tp = (n * (a - origins)).sum(-1) / torch.where(hit, den, torch.ones_like(den))
+    return torch.where(hit, t + (tp - tp.detach()), t)
+
+
+def ao_directions(K: int) -> Tensor:
+    """The K local directions of the ambient-occlusion rays, (K,3) fp32 on the CPU: cosine weighted about +z, the same
+    for every point.  u1 = (k + 0.5) / K, u2 = the base-2 radical inverse of k, r = sqrt(u1), phi = 2 pi u2, direction
+    (r cos phi, r sin phi, sqrt(1 - u1)); numpy float64, rounded once."""
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= _lib.TT_RAY_MAX_DIRS:
+        raise ValueError(f"the number of rays must be an int in [1, {_lib.TT_RAY_MAX_DIRS}], got {K!r}")
+    k = np.arange(K, dtype=np.int64)
+    u1 = (k.astype(np.float64) + 0.5) / K
+    u2, f, n = np.zeros(K), 0.5, k.copy()
+    while n.any():
+        u2 += f * (n & 1)
+        n >>= 1
+        f *= 0.5
+    r, phi = np.sqrt(u1), 2.0 * np.pi * u2
+    return torch.from_numpy(np.stack([r * np.cos(phi), r * np.sin(phi), np.sqrt(1.0 - u1)], 1).astype(np.float32))
+
+
+def _tg_diagonal(tg: TriangleGrid) -> float:
+    """The bounding-box diagonal of the mesh in `tg`; one read-back, kept on the grid."""
+    if getattr(tg, "_diagonal", None) is None:
+        tg._diagonal = float((tg.v_pos.amax(0) - tg.v_pos.amin(0)).double().norm())
+    return tg._diagonal
+
+
+@torch.no_grad()
+def mesh_ao_hits(points: Tensor, normals: Tensor, tg: TriangleGrid, n_rays: int = 64,
+                 max_distance: Optional[float] = None, bias: Optional[float] = None) -> Tensor:
+    """hits (N,) int32 of tt_ray_ao: how many of the n_rays rays of ao_directions about normals[i], started at
+    points[i] + bias n^, hit the mesh in `tg` within max_distance; -1 for a point or normal that is not finite or a zero
+    normal.  Defaults as mesh_ambient_occlusion."""
+    if not isinstance(tg, TriangleGrid):
+        raise TypeError(f"tg must be a TriangleGrid, got {type(tg).__name__}")
+    points = _chk(points, "points", (None, 3)).detach()
+    normals = _chk(normals, "normals", (points.shape[0], 3)).detach()
+    N, dev = points.shape[0], points.device
+    _chk_size("too many points for tt_ray_ao", N=N)
+    table = ao_directions(n_rays).to(dev)
+    max_distance = _chk_t_max(0.25 * _tg_diagonal(tg) if max_distance is None else max_distance, "max_distance")
+    bias = float(1e-3 * _tg_diagonal(tg) if bias is None else bias)
+    if not abs(bias) <= 3.0e38:
+        raise ValueError(f"bias must be finite, got {bias}")
+    hits = torch.empty(N, device=dev, dtype=torch.int32)
+    if N > 0:
+        _launch("tt_ray_ao", points, normals, table, N, n_rays, bias, max_distance, *_grid_args(tg), hits,
+                label="ray_ao")
+    return hits
+
+
+@torch.no_grad()
+def mesh_ambient_occlusion(points: Tensor, normals: Tensor, tg: TriangleGrid, n_rays: int = 64,
+                           max_distance: Optional[float] = None, bias: Optional[float] = None) -> Tensor:
+    """Ambient occlusion (N,) fp32 = 1 - hits / n_rays of points (N,3) with normals (N,3) (any non-zero length) against
+    the mesh in `tg` (tt_ray_ao): 1 means open, 0 closed in; cosine-weighted rays (ao_directions) about the normal in the
+    frame of Duff et al., started bias off the point, max_distance long.  Defaults: max_distance = 0.25 and bias = 1e-3
+    of the mesh's bounding-box diagonal.  A row that is not finite or has a zero normal gives NaN.  Bit for bit
+    independent of the grid and the order of the points."""
+    hits = mesh_ao_hits(points, normals, tg, n_rays, max_distance, bias)
+    ao = 1.0 - hits.float() / float(n_rays)
+    return torch.where(hits < 0, torch.full_like(ao, float("nan")), ao)
+
+
+@torch.no_grad()
+def bake_ambient_occlusion(mesh, texture_size: int, n_rays: int = 64, max_distance: Optional[float] = None,
+                           bias: Optional[float] = None, rast: Optional[Tensor] = None,
+                           occluder: Optional[TriangleGrid] = None) -> Tuple[Tensor, dict]:
+    """The ambient-occlusion map (N,N,1) fp32 in [0,1] of `mesh` (a Mesh with UVs): per covered texel of the UV
+    rasterisation `rast` (N,N,4) (computed as the exporter does when None) the point interpolated from v_pos and the
+    normal interpolated from v_nrm -- flipped to the side of the face's geometric normal where the two disagree, the
+    geometric normal itself where the interpolated one vanishes -- go through mesh_ambient_occlusion against `occluder`
+    (default mesh.triangle_grid).  Uncovered texels, and texels whose face has no normal at all, are 1: fill them with
+    texture_fill.  info = {n_covered, mean (over the covered texels), texel (M,) int64: their flat ids, hits (M,) int32}."""
+    from . import raster  # (raster imports this module)
+    N = int(texture_size)
+    if rast is None:
+        rast = uv_rasterize(mesh.v_tex, mesh.t_tex_idx, N)
+    rast = _chk(rast, "rast", (N, N, 4))
+    tg = mesh.triangle_grid if occluder is None else occluder
+    tri = mesh.t_pos_idx.int()
+    T = tri.shape[0]
+    tid = rast[..., 3].reshape(-1)
+    texel = torch.nonzero((tid >= 1) & (tid <= T)).reshape(-1)
+    v_pos = mesh.v_pos.detach().float()
+    pos = raster.interpolate(v_pos[None], rast[None], tri)[0].reshape(-1, 3)[texel].contiguous()
+    nrm = raster.interpolate(mesh.v_nrm.detach().float()[None], rast[None], tri)[0].reshape(-1, 3)[texel]
+    fv = v_pos[tri[(tid[texel] - 1).long()].long()]  # (M,3,3)
+    geo = torch.linalg.cross(fv[:, 1] - fv[:, 0], fv[:, 2] - fv[:, 0])
+    nrm = torch.where(((nrm * geo).sum(-1) < 0)[:, None], -nrm, nrm)
+    nrm = torch.where((nrm.abs().amax(-1) > 0)[:, None], nrm, geo).contiguous()
+    hits = mesh_ao_hits(pos, nrm, tg, n_rays, max_distance, bias)
+    ao = torch.where(hits < 0, torch.ones_like(pos[:, 0]), 1.0 - hits.float() / float(n_rays))
+    out = torch.ones(N * N, device=rast.device, dtype=torch.float32)
+    out[texel] = ao
+    mean = float(ao.mean()) if ao.numel() else 1.0
+    return out.reshape(N, N, 1), {"n_covered": int(texel.numel()), "mean": mean, "texel": texel, "hits": hits}
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # tangents and normal-map baking (include/tt_abi.h, "tangents and normal-map baking")
 _BAKE_GROUPS = {"pos": _lib.TT_BAKE_GROUP_POS, "tex": _lib.TT_BAKE_GROUP_TEX}
 

@@ -9,8 +9,13 @@ few azimuths for CLIPScore, with CUDA-only tools).
     map_Bump = load_normal_map("model.obj", device="cuda")                        # the MTL's map_Bump, or None
     imgs = turntable(mesh, map_Kd, mode="normal_map", map_Bump=map_Bump)          # the detail normals, (n + 1) / 2
 
-    python -m triplaneturbo_amd.viewer model.obj --out views [--num_views 4] [--normal] [--bump] [--size 512] [--ssaa 2]
-    # views/rgb_0.png ... (normal_0.png ... with --normal, bump_0.png ... with --bump when the MTL names a normal map)
+    map_Ka = load_ao_map("model.obj", device="cuda")                              # the MTL's map_Ka, or None
+    imgs = turntable(mesh, map_Kd, map_Ka=map_Ka)                                 # map_Kd times the ambient occlusion
+    imgs = turntable(mesh, map_Kd, mode="ao", map_Ka=map_Ka)                      # the occlusion alone, gray
+
+    python -m triplaneturbo_amd.viewer model.obj --out views [--num_views 4] [--normal] [--bump] [--ao] [--size 512] [--ssaa 2]
+    # views/rgb_0.png ... (normal_0.png ... with --normal, bump_0.png ... with --bump when the MTL names a normal map,
+    # ao_0.png ... and occlusion-shaded rgb_0.png ... with --ao when it names an ambient-occlusion map)
 
 Torch plumbing between kernels, like mesh_renderer.py: rasterize, interpolate, texture and antialias are
 triplaneturbo_amd.raster.  The sampler has no mipmaps (tt_abi.h "texture sampling"): a texture that is minified on
@@ -64,17 +69,28 @@ def _image_tensor(path: str, device) -> Tensor:
     return (torch.from_numpy(np.ascontiguousarray(img[..., :3])).to(torch.float32) / 255.0).to(device=device)
 
 
-def load_normal_map(obj_path: str, device=None) -> Optional[Tensor]:
-    """The tangent-space normal map an exported OBJ's MTL names (`map_Bump`, export.save_obj's texture_nrm.<fmt>) as
-    float (N,N,3) in [0,1] (uint8 / 255), None when the OBJ has no MTL or the MTL no map_Bump.  Row 0 is v = 0 of
-    load_obj's v_tex, like map_Kd."""
+def _mtl_map(obj_path: str, key: str) -> Optional[str]:
     mtllib = None
     with open(obj_path) as fh:
         for line in fh:
             if line.startswith("mtllib"):
                 mtllib = line.split(None, 1)[1].strip()
                 break
-    path = _map_path(os.path.join(os.path.dirname(obj_path), mtllib), "map_Bump") if mtllib else None
+    return _map_path(os.path.join(os.path.dirname(obj_path), mtllib), key) if mtllib else None
+
+
+def load_ao_map(obj_path: str, device=None) -> Optional[Tensor]:
+    """The ambient-occlusion map an exported OBJ's MTL names (`map_Ka`, export.save_obj's texture_ao.<fmt>) as float
+    (N,N,1) in [0,1] (uint8 / 255), None when the OBJ has no MTL or the MTL no map_Ka.  Row 0 is v = 0, like map_Kd."""
+    path = _mtl_map(obj_path, "map_Ka")
+    return _image_tensor(path, device)[..., :1].contiguous() if path is not None else None
+
+
+def load_normal_map(obj_path: str, device=None) -> Optional[Tensor]:
+    """The tangent-space normal map an exported OBJ's MTL names (`map_Bump`, export.save_obj's texture_nrm.<fmt>) as
+    float (N,N,3) in [0,1] (uint8 / 255), None when the OBJ has no MTL or the MTL no map_Bump.  Row 0 is v = 0 of
+    load_obj's v_tex, like map_Kd."""
+    path = _mtl_map(obj_path, "map_Bump")
     return _image_tensor(path, device) if path is not None else None
 
 
@@ -187,7 +203,7 @@ def world_normal_from_map(mesh: Mesh, rast: Tensor, map_Bump: Tensor, filter_mod
 def render_textured(mesh: Mesh, map_Kd: Optional[Tensor], mvp_mtx: Tensor, height: int, width: int, mode: str = "rgb",
                     ssaa: int = 1, background: float = 1.0, filter_mode: str = "linear", antialias: bool = True,
                     ctx: Optional[RasterizerContext] = None, map_Bump: Optional[Tensor] = None,
-                    light_dir: Optional[Tensor] = None) -> Tensor:
+                    light_dir: Optional[Tensor] = None, map_Ka: Optional[Tensor] = None) -> Tensor:
     """(B,height,width,3) views of `mesh` under mvp_mtx (B,4,4).  mode "rgb": map_Kd (TH,TW,3) sampled at the
     interpolated v_tex (boundary "clamp"), or the interpolated v_rgb when the mesh has no UVs; with both map_Bump and
     light_dir (3,) (towards the light, world space) that colour times max(0, n . l), n the world normal of mode
@@ -195,11 +211,13 @@ def render_textured(mesh: Mesh, map_Kd: Optional[Tensor], mvp_mtx: Tensor, heigh
     world normal rebuilt per pixel from map_Bump (TH,TW,3), a tangent-space normal map as the exporter bakes it:
     x = 2 map - 1 sampled at the interpolated v_tex, n = normalize(x_0 t^ + x_1 b^ + x_2 n^) in the frame n^ =
     normalize(interpolated v_nrm), t^ = normalize(t - (t . n^) n^) with t the interpolated v_tng_tex, b^ = t^ x n^
-    (include/tt_abi.h, "tangents and normal-map baking").  Then a lerp to `background` by the coverage mask, silhouette
+    (include/tt_abi.h, "tangents and normal-map baking").  map_Ka (TH,TW,1), an ambient-occlusion map as the exporter
+    bakes it, sampled at the interpolated v_tex: it multiplies the colour of mode "rgb" (the one shading cue an unlit
+    map_Kd render can have), and mode "ao" shows it alone, as gray.  Then a lerp to `background` by the coverage mask, silhouette
     antialiasing and, for ssaa > 1, the average of ssaa x ssaa samples per pixel (rendered at ssaa x the size).
     Differentiable w.r.t. map_Kd, map_Bump and mesh.v_pos (v_tng_tex is a constant)."""
-    if mode not in ("rgb", "normal", "normal_map"):
-        raise ValueError(f"mode must be 'rgb', 'normal' or 'normal_map', got {mode!r}")
+    if mode not in ("rgb", "normal", "normal_map", "ao"):
+        raise ValueError(f"mode must be 'rgb', 'normal', 'normal_map' or 'ao', got {mode!r}")
     if ssaa < 1:
         raise ValueError(f"ssaa must be >= 1, got {ssaa}")
     ctx = ctx or RasterizerContext("cuda", mesh.v_pos.device)
@@ -209,12 +227,20 @@ def render_textured(mesh: Mesh, map_Kd: Optional[Tensor], mvp_mtx: Tensor, heigh
     mask = (rast[..., 3:] > 0).float()
     if mode == "normal_map" and (map_Bump is None or mesh._v_tex is None):
         raise ValueError("mode 'normal_map' needs a mesh with v_tex and a map_Bump")
+    if mode == "ao" and (map_Ka is None or mesh._v_tex is None):
+        raise ValueError("mode 'ao' needs a mesh with v_tex and a map_Ka")
+    occlusion = None
+    if map_Ka is not None and mesh._v_tex is not None and mode in ("rgb", "ao"):
+        uv_ka, _ = ctx.interpolate(mesh.v_tex[None], rast, mesh.t_tex_idx)
+        occlusion = ctx.texture(map_Ka[..., :1].contiguous()[None], uv_ka, filter_mode=filter_mode, boundary_mode="clamp")
     shaded = mode == "rgb" and map_Bump is not None and light_dir is not None and mesh._v_tex is not None
     world_nrm = None
     if mode == "normal_map" or shaded:
         world_nrm = world_normal_from_map(mesh, rast, map_Bump, filter_mode=filter_mode, ctx=ctx)
     if mode == "normal_map":
         color = (world_nrm + 1.0) / 2.0
+    elif mode == "ao":
+        color = occlusion.expand(-1, -1, -1, 3)
     elif mode == "normal":
         nrm, _ = ctx.interpolate(mesh.v_nrm[None], rast, tri)
         color = (F.normalize(nrm, dim=-1) + 1.0) / 2.0
@@ -228,6 +254,8 @@ def render_textured(mesh: Mesh, map_Kd: Optional[Tensor], mvp_mtx: Tensor, heigh
         color, _ = ctx.interpolate(mesh.v_rgb[None], rast, tri)
     else:
         raise ValueError("mode 'rgb' needs a mesh with v_tex and a map_Kd, or with vertex colours")
+    if mode == "rgb" and occlusion is not None:
+        color = color * occlusion
     img = torch.lerp(torch.full_like(color, float(background)), color, mask)
     if antialias:
         img = ctx.antialias(img, rast, pos, tri)
@@ -248,24 +276,31 @@ def turntable(mesh: Mesh, map_Kd: Optional[Tensor], n_views: int = 4, elevation_
 def main(argv=None) -> None:
     ap = argparse.ArgumentParser(prog="python -m triplaneturbo_amd.viewer", description=__doc__.split("\n\n")[0])
     ap.add_argument("obj", metavar="MODEL.obj")
-    ap.add_argument("--out", required=True, help="directory for rgb_{i}.png (and normal_{i}.png, bump_{i}.png)")
+    ap.add_argument("--out", required=True, help="directory for rgb_{i}.png (and normal_{i}.png, bump_{i}.png, ao_{i}.png)")
     ap.add_argument("--num_views", type=int, default=4)
     ap.add_argument("--normal", action="store_true", help="also write normal_{i}.png")
     ap.add_argument("--bump", action="store_true",
                     help="also write bump_{i}.png (mode normal_map) when the MTL names a map_Bump")
+    ap.add_argument("--ao", action="store_true",
+                    help="also write ao_{i}.png (mode ao) when the MTL names a map_Ka, and shade rgb_{i}.png with it")
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--ssaa", type=int, default=2)
     a = ap.parse_args(argv)
     dev = torch.device("cuda", torch.cuda.current_device())
     mesh, map_kd = load_obj(a.obj, device=dev)
     map_bump = load_normal_map(a.obj, device=dev) if a.bump else None
+    map_ka = load_ao_map(a.obj, device=dev) if a.ao else None
     os.makedirs(a.out, exist_ok=True)
     modes = [("rgb", "rgb")] + ([("normal", "normal")] if a.normal else [])
     if map_bump is not None:
         modes.append(("bump", "normal_map"))
+    if map_ka is not None:
+        modes.append(("ao", "ao"))
     with torch.no_grad():
         for name, mode in modes:
             kw = {"map_Bump": map_bump} if mode == "normal_map" else {}
+            if map_ka is not None and mode in ("rgb", "ao"):
+                kw["map_Ka"] = map_ka
             imgs = turntable(mesh, map_kd, n_views=a.num_views, height=a.size, width=a.size, mode=mode, ssaa=a.ssaa,
                              **kw)
             for i, img in enumerate(imgs.cpu().numpy()):
