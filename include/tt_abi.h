@@ -307,6 +307,15 @@ int tt_render_fwd_h2mask(const float* packed, const tt_mlp_weights* w, const flo
                          float* depth, float* rgb_fg, float* z_variance, float* normal_acc, float* weights, float* trans,
                          float* sdf, float* sdf_grad, float* features, uint32_t* h2_mask, void* stream);
 
+/* tt_render_fwd_h2mask that also writes h1_mask (n_rays*S, 2) uint32: the signs of the sdf net's FIRST hidden layer,
+ * h1 = relu(W1 f), in the bit layout of h2_mask (bit r of dword 2*sample + hi = (h1[(r & 3) + 8 * (r >> 2) + 4 * hi] > 0);
+ * 0 where the tile step had no in-bounds texel).  8 more bytes of saved state per sample; same arithmetic and outputs;
+ * h2_mask is bit for bit the one of tt_render_fwd_h2mask.  Both masks are the saved state of tt_render_bwd_geo_masks. */
+int tt_render_fwd_masks(const float* packed, const tt_mlp_weights* w, const float* rays_o, const float* rays_d,
+                        const float* t_starts, const float* t_ends, const tt_render_cfg* cfg, float* opacity,
+                        float* depth, float* rgb_fg, float* z_variance, float* normal_acc, float* weights, float* trans,
+                        float* sdf, float* sdf_grad, float* features, uint32_t* h2_mask, uint32_t* h1_mask, void* stream);
+
 /* Eval-mode render (the renderer returns no per-sample tensors outside training, renderer :532-545): the per-ray outputs
  * of tt_render_fwd from ONE kernel that decodes and marches each 8x4-pixel ray tile front to back.
  * transmittance_eps > 0: a ray stops contributing once its transmittance is below it and a tile stops when all its rays
@@ -365,6 +374,20 @@ int tt_render_bwd_geo_h2mask(const float* packed, const tt_mlp_weights* w, const
                              const float* g_normal_acc, const float* g_weights, const float* g_sdf,
                              const float* g_sdf_grad, float* g_inv_std_rays, float* workspace, float* grad_packed,
                              const tt_mlp_grads* grads, const uint32_t* h2_mask, void* stream);
+
+/* tt_render_bwd_geo with both sign masks of tt_render_fwd_masks.  In the split precisions nothing reads the values of h1
+ * any more: with u = sbar f + J gbar (gathered directly) the kernel forms v = m1 . (W1 u) from ONE product with W1, where the
+ * other entries form sbar relu(W1 f) + m1 . W1 (J gbar) from two, and it gathers u alone.  d/d planes and d/d w1 are computed
+ * as by tt_render_bwd_geo_h2mask; d/d w2 and d/d w3 differ from it by the rounding of v.  The fp32-MFMA precision ignores
+ * h1_mask and runs tt_render_bwd_geo_h2mask's kernel. */
+int tt_render_bwd_geo_masks(const float* packed, const tt_mlp_weights* w, const float* rays_o, const float* rays_d,
+                            const float* t_starts, const float* t_ends, const tt_render_cfg* cfg,
+                            const float* opacity, const float* depth, const float* trans, const float* sdf,
+                            const float* sdf_grad, const float* features, const float* g_opacity,
+                            const float* g_depth, const float* g_rgb_fg, const float* g_z_variance,
+                            const float* g_normal_acc, const float* g_weights, const float* g_sdf,
+                            const float* g_sdf_grad, float* g_inv_std_rays, float* workspace, float* grad_packed,
+                            const tt_mlp_grads* grads, const uint32_t* h2_mask, const uint32_t* h1_mask, void* stream);
 
 /* Backward, texture half: d/d(texture planes 3..5) and d/d(feature net).
  * Needs saved weights (per sample) and features; g_rgb_fg (per ray), g_features (per sample; null = 0). */

@@ -78,8 +78,10 @@ names = ["upstream cbar + skip test", "gather e (12 corners)", "park e in LDS", 
          "ebar_p = V1_p^T k1bar + stage (x3)", "scatter_plane epilogue", "tail",
          "", "", "", "", "",  # (slots 12..16 carry the live-lane / scatter statistics printed above)
          "end of tile step -> pop", "item pop (queue atomic)", "ray set-up (issue)"]
-geo_names = ["upstream (d sdf, d sdf_grad) + skip test", "gather f, u (12 corners)", "", "sdf net recompute + reverse chain (5 products)",
-             "a1bar = W1 qbar, v", "", "", "dW1 outer products",
+# (both masks from the forward, the default: no recompute and no f; with RenderConfig.fwd_mask_h1=False phase 1 also gathers f,
+# phase 3 also forms h1 = relu(W1 f) and phase 4 is a1bar = W1 qbar, v = sbar h1 + m1 . a1bar)
+geo_names = ["upstream (d sdf, d sdf_grad) + skip test", "gather u (12 corners)", "", "a1 = m1 . C^T m2, q = W1^T a1 (2 products)",
+             "t = W1 u, v = m1 . t", "", "", "dW1 outer products",
              "D = m2 v^T outer products (dW2, dw3)", "scatter: q staging + corner set-up", "scatter epilogue", "tail",
              "", "", "", "", "", "  (of the epilogue) operands -> registers, next plane's set-up, operand split + MFMAs",
              "  (of the epilogue) next plane's slot claims", "  (of the epilogue) flush atomics, tag reset, lost references"]

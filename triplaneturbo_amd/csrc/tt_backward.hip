@@ -15,6 +15,11 @@
 //       constant C = diag(w3) W2 staged once per workgroup and the 0/1 mask as the B operand (half the MFMAs, no split of a2),
 //       and (ii) the FMASK instantiations take m2 from the forward (tt_render_fwd_h2mask: 8 bytes per sample) instead of
 //       recomputing W2 h1 for its signs.  The fp32-MFMA mode keeps its fp32 product W2^T (m2 . w3).
+//       One W1 product: after that nothing reads h1's values either -- only its sign m1 and v.  With h1 = m1 . W1 f,
+//       b1bar = m1 . W1 qbar and u = sbar f + qbar (the gather's u),
+//           v = sbar h1 + b1bar = m1 . W1 (sbar f + qbar) = m1 . (W1 u)
+//       (exact, second-order chain included).  The FMASK_H1H2 instantiations (split modes) take m1 from the forward as well
+//       (tt_render_fwd_masks), form t = W1 u once instead of W1 f and W1 qbar, and gather u alone: f has no reader left.
 //   k_decode_bwd_tex : feature net backward, dV1/dV2/dV3, scatter of d/d planes 3..5.
 // Both are purely per-sample: tiles are 32 adjacent rays at one sample index (see tt_device.h).
 //
@@ -37,6 +42,7 @@ struct BwdGeoParams {
     int* queue;  // per-XCD item counters (tt_queue_counters)
     const float* ws;  // (n_rays*S, 4): d/d sdf, d/d sdf_grad xyz  (from k_march_bwd)
     const unsigned* h2_mask;  // (n_rays*S, 2): sign masks of h2 from tt_render_fwd_h2mask (FMASK instantiations), else null
+    const unsigned* h1_mask;  // (n_rays*S, 2): sign masks of h1 from tt_render_fwd_masks (FMASK_H1H2 instantiations), else null
     int n_copies;     // privatised copies of grad_packed
     float* grad_packed;
     MlpGradPtrs grads;
@@ -48,6 +54,7 @@ struct BwdGeoParams {
 // transposed products use transposed COPIES appended to them (LDS nothing else wants at one wave per SIMD, read by plain
 // ds_read_b128 fragments): W1^T, and C^T for C = diag(w3) W2 in place of W2^T.  PREC_S3 appends the images of the third terms.
 // NOW2 (the split modes with the forward's h2 mask): W2 h1 is not formed, so W2 has no image at all.
+enum { FMASK_NONE = 0, FMASK_H2 = 1, FMASK_H1H2 = 2 };
 template <int PREC, bool FMASK>
 struct GeoMap : LdsMap<PREC, LdsImage<64, 32>, LdsImage<64, 64, !(FMASK && PREC != PREC_F32)>, LdsRows<1, 64>,
                        LdsImage<32, 64>, LdsImage<64, 64>> {
@@ -63,12 +70,15 @@ struct GeoMap : LdsMap<PREC, LdsImage<64, 32>, LdsImage<64, 64, !(FMASK && PREC 
 // counting site costs 2-3 % (2.95 vs 2.85 ms: the branches cut hipcc's scheduling regions), so production launches
 // (stats == null) run the instantiation without it.
 // FMASK: the sign mask of h2 = relu(W2 h1) comes from the forward (p.h2_mask) instead of being recomputed: nothing here
-// reads h2's values (row-scaling identity, top of file).
-template <int PREC, bool STATS = false, bool FMASK = false>
+// reads h2's values (row-scaling identity, top of file).  FMASK_H1H2 (split modes only): the sign mask of h1 comes from the
+// forward too (p.h1_mask), and the body is the one-product form v = m1 . (W1 u) (top of file).
+template <int PREC, bool STATS = false, int FMASK = FMASK_NONE>
 __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
     constexpr bool EXACT = PREC == PREC_F32;
     constexpr bool WG16 = !EXACT;  // the split modes: outer products on the fp16 pipe, a1 and q in raw form
-    typedef GeoMap<PREC, FMASK> G;
+    constexpr bool M1 = FMASK == FMASK_H1H2;  // m1 from the forward, one W1 product
+    static_assert(!(M1 && EXACT), "the fp32-MFMA mode stays on the h2-only path");
+    typedef GeoMap<PREC, FMASK != FMASK_NONE> G;
     constexpr int NT = PrecNT<PREC>::value, WF = G::FLOATS;
     __shared__ __attribute__((aligned(16))) float L[WF + 4 * (GEO_SCRATCH_FLOATS + SCATTER_TAG_INTS)];
     stage_weights<PREC>(L, typename G::W1{}, p.w.w1);
@@ -156,6 +166,7 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
             f32x4 up;  // upstream (from the march backward): d/d sdf and d/d sdf_grad of this sample
             float ts, te;
             unsigned m2;  // FMASK: this lane's dword of the forward's h2 sign mask
+            unsigned m1;  // FMASK_H1H2: and of its h1 sign mask
         };
         auto load_step = [&](int sb0) {
             StepIn r;
@@ -165,6 +176,7 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
             r.ts = p.rays_d ? p.t_starts[sidx] : 0.f;
             r.te = p.rays_d ? p.t_ends[sidx] : 0.f;
             r.m2 = FMASK ? p.h2_mask[2 * sidx + hi] : 0u;
+            r.m1 = M1 ? p.h1_mask[2 * sidx + hi] : 0u;
             return r;
         };
         StepIn in = load_step(ck * tg.chunk), in_next;
@@ -191,7 +203,7 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
             // ---- recompute the geometry decode ----
             float f[16], u[16];  // u = sbar f + J gbar
             unsigned pmask;
-            const bool any = __any(gather_geo_bwd_c(p.packed, (unsigned)(pofs / TT_C), H, W, X, Y, Z, rvalid, sbar, gbx,
+            const bool any = __any(gather_geo_bwd_c<!M1>(p.packed, (unsigned)(pofs / TT_C), H, W, X, Y, Z, rvalid, sbar, gbx,
                                                     gby, gbz, ju, jv, lane, Xs, f, u, pmask,
                                                     tile_stat_ptr(st, TT_STAT_INBOUNDS)));
             TT_PHASE(1);
@@ -204,12 +216,23 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
             // "deferred factors"); their consumers are signs, the next product, and fmas that take the factor on the scalar;
             // h2 is used for its sign only (its factor uh2 is dead)
             float h1[32], h2[32], a1[32], q[16], u1, uh2;
-            mvx<PREC, true>(L, typename G::W1{}, f, h1, i, hi, 1.f, &u1);
+            if constexpr (!M1) {
+                mvx<PREC, true>(L, typename G::W1{}, f, h1, i, hi, 1.f, &u1);
 #pragma unroll
-            for (int r = 0; r < 32; ++r) h1[r] = fmaxf(h1[r], 0.f);
+                for (int r = 0; r < 32; ++r) h1[r] = fmaxf(h1[r], 0.f);
+            }
             // FMASK: bit r of the lane's mask word is (h2[r] > 0) as the forward saw it; a lane that is not rvalid loaded
             // another sample's word from the clamped address: forced to 0 through the 0/1 validity factor
             const unsigned m2w = FMASK ? in.m2 & (0u - (unsigned)vf) : 0u;
+            const unsigned m1w = M1 ? in.m1 & (0u - (unsigned)vf) : 0u;
+            // x where m1 is set, else +0: the h1 sign from its recomputed value, or (M1) from bit r of the forward's word as an
+            // all-ones / zero AND mask (a sign-extended one-bit field: no compare, no select)
+            auto m1_keep = [&](int r, float x) {
+                if constexpr (M1)
+                    return __builtin_bit_cast(float, __builtin_bit_cast(int, x) & ((int)(m1w << (31 - r)) >> 31));
+                else
+                    return h1[r] > 0.f ? x : 0.f;
+            };
             if constexpr (!FMASK) {
                 mvx<PREC, true>(L, typename G::W2{}, h1, h2, i, hi, u1, &uh2);
 #pragma unroll
@@ -241,7 +264,7 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
                 mvtx_copy<PREC>(L, typename G::CT{}, typename G::W2{}, a2, a1, i, hi);
             }
 #pragma unroll
-            for (int r = 0; r < 32; ++r) a1[r] = h1[r] > 0.f ? a1[r] : 0.f;
+            for (int r = 0; r < 32; ++r) a1[r] = m1_keep(r, a1[r]);
             // q = W1^T a1 has one consumer, the scatter, which wants it as the B operand of its combine GEMM: the split modes
             // form q^T (lane <-> channel, register <-> sample, raw accumulators; uq = the factor) by swapping the MFMA's two
             // arguments -- one tile for the three planes (tt_backward_common.h, ScatterQ)
@@ -256,8 +279,10 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
             // ---- network + plane gradients ----
             {
                 float qb[16];
+                if constexpr (!M1) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) qb[r] = fmaf(-sbar, f[r], u[r]);  // qbar = J gbar = u - sbar f
+                    for (int r = 0; r < 16; ++r) qb[r] = fmaf(-sbar, f[r], u[r]);  // qbar = J gbar = u - sbar f
+                }
                 // (no opaque scheduling region here, unlike the texture kernel: with the outer products on the fp16 pipe
                 // this kernel has register slack and one scheduling region is faster: 3.22 -> 3.14 ms)
                 const bool region = WG16 || cfg.flags >= 0;  // (always true; opaque to the compiler in the fp32 mode)
@@ -275,14 +300,19 @@ __global__ __launch_bounds__(256, 1) void k_decode_bwd_geo(BwdGeoParams p) {
                     }
                 }
                 TT_PHASE(7);
-                // a1bar = W1 qbar ; b1bar = m1 . a1bar ; v = sbar h1 + b1bar
-                float t1[32];
-                mvx<PREC>(L, typename G::W1{}, qb, t1, i, hi);
+                // a1bar = W1 qbar ; b1bar = m1 . a1bar ; v = sbar h1 + b1bar.  M1: t = W1 u ; v = m1 . t (the same v, top of file)
+                float t1[32], v[32];
+                if constexpr (M1) {
+                    mvx<PREC>(L, typename G::W1{}, u, t1, i, hi);
 #pragma unroll
-                for (int r = 0; r < 32; ++r) t1[r] = h1[r] > 0.f ? t1[r] : 0.f;  // b1bar
-                float v[32];
+                    for (int r = 0; r < 32; ++r) v[r] = m1_keep(r, t1[r]);
+                } else {
+                    mvx<PREC>(L, typename G::W1{}, qb, t1, i, hi);
 #pragma unroll
-                for (int r = 0; r < 32; ++r) v[r] = fmaf(sbar * u1, h1[r], t1[r]);
+                    for (int r = 0; r < 32; ++r) t1[r] = h1[r] > 0.f ? t1[r] : 0.f;  // b1bar
+#pragma unroll
+                    for (int r = 0; r < 32; ++r) v[r] = fmaf(sbar * u1, h1[r], t1[r]);
+                }
                 TT_PHASE(4);
                 // D += m2 v^T: dW2 and dw3 both come out of it at the kernel-end flush (row-scaling identity, top of file)
                 if (do_wgrad) {
@@ -376,25 +406,33 @@ static void launch_bwd_geo(const BwdGeoParams& p0, long long blocks, hipStream_t
     tt_dispatch_prec(tt_prec_of_r(p.cfg.flags), [&](auto P) {
         constexpr int PREC = decltype(P)::value;
         const dim3 grid((unsigned)blocks), block(256);
-        if (p.cfg.stats && p.h2_mask)
-            hipLaunchKernelGGL((k_decode_bwd_geo<PREC, true, true>), grid, block, 0, s, p);
+        // both masks: the one-product form in the split modes; the fp32-MFMA mode ignores h1_mask (h2-only path)
+        constexpr int BOTH = PREC == PREC_F32 ? FMASK_H2 : FMASK_H1H2;
+        if (p.cfg.stats && p.h2_mask && p.h1_mask)
+            hipLaunchKernelGGL((k_decode_bwd_geo<PREC, true, BOTH>), grid, block, 0, s, p);
+        else if (p.h2_mask && p.h1_mask)
+            hipLaunchKernelGGL((k_decode_bwd_geo<PREC, false, BOTH>), grid, block, 0, s, p);
+        else if (p.cfg.stats && p.h2_mask)
+            hipLaunchKernelGGL((k_decode_bwd_geo<PREC, true, FMASK_H2>), grid, block, 0, s, p);
         else if (p.cfg.stats)
             hipLaunchKernelGGL((k_decode_bwd_geo<PREC, true>), grid, block, 0, s, p);
         else if (p.h2_mask)
-            hipLaunchKernelGGL((k_decode_bwd_geo<PREC, false, true>), grid, block, 0, s, p);
+            hipLaunchKernelGGL((k_decode_bwd_geo<PREC, false, FMASK_H2>), grid, block, 0, s, p);
         else
             hipLaunchKernelGGL((k_decode_bwd_geo<PREC>), grid, block, 0, s, p);
     });
 }
 
-// tt_render_bwd_geo (h2_mask null: the decode backward recomputes W2 h1 for its signs) / tt_render_bwd_geo_h2mask
+// tt_render_bwd_geo (h2_mask null: the decode backward recomputes W2 h1 for its signs) / tt_render_bwd_geo_h2mask (h1_mask
+// null) / tt_render_bwd_geo_masks
 static int render_bwd_geo(const float* packed, const tt_mlp_weights* w, const float* rays_o, const float* rays_d,
                           const float* t_starts, const float* t_ends, const tt_render_cfg* cfg, const float* opacity,
                           const float* depth, const float* trans, const float* sdf, const float* sdf_grad,
                           const float* features, const float* g_opacity, const float* g_depth, const float* g_rgb_fg,
                           const float* g_z_variance, const float* g_normal_acc, const float* g_weights,
                           const float* g_sdf, const float* g_sdf_grad, float* g_inv_std_rays, float* workspace,
-                          float* grad_packed, const tt_mlp_grads* grads, const uint32_t* h2_mask, void* stream) {
+                          float* grad_packed, const tt_mlp_grads* grads, const uint32_t* h2_mask, const uint32_t* h1_mask,
+                          void* stream) {
     int st = tt_validate_cfg(cfg);
     if (st != TT_OK) return st;
     if (!packed || !w || !rays_o || !rays_d || !t_starts || !t_ends || !opacity || !depth || !trans || !sdf ||
@@ -414,6 +452,7 @@ static int render_bwd_geo(const float* packed, const tt_mlp_weights* w, const fl
     p.cfg.flags |= debug_flags();
     p.ws = workspace;
     p.h2_mask = h2_mask;
+    p.h1_mask = h1_mask;
     p.grad_packed = grad_packed;
     p.n_copies = cfg->grad_copies > 0 ? cfg->grad_copies : 1;
     p.grads = to_gptrs(grads);
@@ -433,7 +472,7 @@ extern "C" int tt_render_bwd_geo(const float* packed, const tt_mlp_weights* w, c
                                  float* grad_packed, const tt_mlp_grads* grads, void* stream) {
     return render_bwd_geo(packed, w, rays_o, rays_d, t_starts, t_ends, cfg, opacity, depth, trans, sdf, sdf_grad, features,
                           g_opacity, g_depth, g_rgb_fg, g_z_variance, g_normal_acc, g_weights, g_sdf, g_sdf_grad,
-                          g_inv_std_rays, workspace, grad_packed, grads, nullptr, stream);
+                          g_inv_std_rays, workspace, grad_packed, grads, nullptr, nullptr, stream);
 }
 
 extern "C" int tt_render_bwd_geo_h2mask(const float* packed, const tt_mlp_weights* w, const float* rays_o,
@@ -448,7 +487,23 @@ extern "C" int tt_render_bwd_geo_h2mask(const float* packed, const tt_mlp_weight
     if (!h2_mask) return TT_ERR_BAD_ARG;
     return render_bwd_geo(packed, w, rays_o, rays_d, t_starts, t_ends, cfg, opacity, depth, trans, sdf, sdf_grad, features,
                           g_opacity, g_depth, g_rgb_fg, g_z_variance, g_normal_acc, g_weights, g_sdf, g_sdf_grad,
-                          g_inv_std_rays, workspace, grad_packed, grads, h2_mask, stream);
+                          g_inv_std_rays, workspace, grad_packed, grads, h2_mask, nullptr, stream);
+}
+
+extern "C" int tt_render_bwd_geo_masks(const float* packed, const tt_mlp_weights* w, const float* rays_o,
+                                       const float* rays_d, const float* t_starts, const float* t_ends,
+                                       const tt_render_cfg* cfg, const float* opacity, const float* depth,
+                                       const float* trans, const float* sdf, const float* sdf_grad,
+                                       const float* features, const float* g_opacity, const float* g_depth,
+                                       const float* g_rgb_fg, const float* g_z_variance, const float* g_normal_acc,
+                                       const float* g_weights, const float* g_sdf, const float* g_sdf_grad,
+                                       float* g_inv_std_rays, float* workspace, float* grad_packed,
+                                       const tt_mlp_grads* grads, const uint32_t* h2_mask, const uint32_t* h1_mask,
+                                       void* stream) {
+    if (!h2_mask || !h1_mask) return TT_ERR_BAD_ARG;
+    return render_bwd_geo(packed, w, rays_o, rays_d, t_starts, t_ends, cfg, opacity, depth, trans, sdf, sdf_grad, features,
+                          g_opacity, g_depth, g_rgb_fg, g_z_variance, g_normal_acc, g_weights, g_sdf, g_sdf_grad,
+                          g_inv_std_rays, workspace, grad_packed, grads, h2_mask, h1_mask, stream);
 }
 
 // ---- backward of the per-point queries (tt_query_points / tt_query_field): the same decode-backward kernels, with
@@ -487,6 +542,7 @@ extern "C" int tt_points_bwd_geo(const float* packed, const tt_mlp_weights* w, c
     tt_fill_rays(p, packed, w, points, nullptr, nullptr, nullptr, cfg);
     p.ws = workspace;
     p.h2_mask = nullptr;
+    p.h1_mask = nullptr;
     p.grad_packed = grad_packed;
     p.n_copies = 1;
     p.grads = to_gptrs(grads);

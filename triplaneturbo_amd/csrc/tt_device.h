@@ -417,6 +417,14 @@ __device__ __forceinline__ void tile_stats_flush(const TileStats& st) {
         if (l < 4) atomicAdd(st.p + l, (unsigned long long)st.w[l]);
     }
 }
+// the same with the lane index counted afresh at the flush (the number of lower lanes: the wave is whole there), for a kernel
+// that has no register to keep `threadIdx.x & 63` alive across its main loop for this one use after it
+__device__ __forceinline__ void tile_stats_flush_late(const TileStats& st) {
+    if (st.p) {
+        const int l = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        if (l < 4) atomicAdd(st.p + l, (unsigned long long)st.w[l]);
+    }
+}
 
 // ---- plane mask of a tile step ------------------------------------------------------------------------------------------
 // The coalesced gathers below return, next to the per-lane `any`, the WAVE-UNIFORM mask of the planes that have an in-bounds
@@ -699,6 +707,10 @@ __device__ __forceinline__ void geo_corner_coefs(int p, int H, int W, float X, f
 // Corner order of the sums as in gather_geo.  T: GC_TABLE_FLOATS(2) +
 // GC_TILE_FLOATS floats.  Nothing of the corner set-up is kept: the scatter at the end of the tile step re-derives it
 // with geo_corner_coefs (cheap VALU) instead of holding ~40 registers across the MLP chain.
+// NEED_F = false (the kernel that takes both sign masks from the forward reads f nowhere): u only -- the same corner order,
+// `any`, pmask and in-bounds counter, one accumulation per texel value and one transpose; f is left untouched.  With the
+// registers of f and its accumulators free, a tile step with all three planes live issues its loads together (below).
+template <bool NEED_F = true>
 __device__ __forceinline__ bool gather_geo_bwd_c(const float* __restrict__ planes, unsigned tex0, int H, int W, float X,
                                                  float Y, float Z, bool valid, float sbar, float gux, float guy,
                                                  float guz, float jscale_u, float jscale_v, int lane, float* T,
@@ -728,8 +740,10 @@ __device__ __forceinline__ bool gather_geo_bwd_c(const float* __restrict__ plane
             const unsigned b = tex0 + (unsigned)(p * HW);
             const ti32x4 o = {(int)(b + cn.off[0]), (int)(b + cn.off[1]), (int)(b + cn.off[2]), (int)(b + cn.off[3])};
             *reinterpret_cast<ti32x4*>(Toff + (p * 32 + i) * 4) = o;
-            const f32x4 w = {cn.w[0], cn.w[1], cn.w[2], cn.w[3]};
-            *reinterpret_cast<f32x4*>(Tw + (p * 32 + i) * 4) = w;
+            if (NEED_F) {
+                const f32x4 w = {cn.w[0], cn.w[1], cn.w[2], cn.w[3]};
+                *reinterpret_cast<f32x4*>(Tw + (p * 32 + i) * 4) = w;
+            }
         } else {
             const f32x4 w = {coef[0], coef[1], coef[2], coef[3]};
             *reinterpret_cast<f32x4*>(Tc + (p * 32 + i) * 4) = w;
@@ -742,6 +756,30 @@ __device__ __forceinline__ bool gather_geo_bwd_c(const float* __restrict__ plane
         af[n] = z;
         au[n] = z;
     }
+    if (!NEED_F && pmask == 7u) {
+        // all three planes live (the common tile step inside the cube) and no f: the 48 loads of the step in ONE basic block,
+        // so that the planes' memory round trips overlap instead of following each other behind the per-plane branches; the
+        // sums run in the same order as below (bit-identical u)
+        f32x4 t[3][4][4];
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+#pragma unroll
+            for (int n = 0; n < 4; ++n) {
+                const ti32x4 o4 = *reinterpret_cast<const ti32x4*>(Toff + (p * 32 + 8 * n + js) * 4);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) t[p][n][k] = *gc_addr(planes, o4[k], 16u * (unsigned)c);
+            }
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+#pragma unroll
+            for (int n = 0; n < 4; ++n) {
+                const f32x4 c4 = *reinterpret_cast<const f32x4*>(Tc + (p * 32 + 8 * n + js) * 4);
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+#pragma unroll
+                    for (int ee = 0; ee < 4; ++ee) au[n][ee] = fmaf(c4[k], t[p][n][k][ee], au[n][ee]);
+            }
+    } else
 #pragma unroll
     for (int p = 0; p < 3; ++p) {
         if (!anyp[p]) continue;  // exact: every weight of this plane is 0 for the whole tile
@@ -756,24 +794,27 @@ __device__ __forceinline__ bool gather_geo_bwd_c(const float* __restrict__ plane
 #pragma unroll
         for (int n = 0; n < 4; ++n) {
             const int sidx = (p * 32 + 8 * n + js) * 4;
-            const f32x4 w4 = *reinterpret_cast<const f32x4*>(Tw + sidx);
+            f32x4 w4 = {0.f, 0.f, 0.f, 0.f};
+            if (NEED_F) w4 = *reinterpret_cast<const f32x4*>(Tw + sidx);
             const f32x4 c4 = *reinterpret_cast<const f32x4*>(Tc + sidx);
 #pragma unroll
             for (int k = 0; k < 4; ++k)
 #pragma unroll
                 for (int ee = 0; ee < 4; ++ee) {
-                    af[n][ee] = fmaf(w4[k], t[n][k][ee], af[n][ee]);
+                    if (NEED_F) af[n][ee] = fmaf(w4[k], t[n][k][ee], af[n][ee]);
                     au[n][ee] = fmaf(c4[k], t[n][k][ee], au[n][ee]);
                 }
         }
     }
+    if (NEED_F) {
 #pragma unroll
-    for (int n = 0; n < 4; ++n) *reinterpret_cast<f32x4*>(R + (8 * n + js) * 36 + 4 * c) = af[n];
+        for (int n = 0; n < 4; ++n) *reinterpret_cast<f32x4*>(R + (8 * n + js) * 36 + 4 * c) = af[n];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(R + i * 36 + 4 * (hi + 2 * q));
+        for (int q = 0; q < 4; ++q) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(R + i * 36 + 4 * (hi + 2 * q));
 #pragma unroll
-        for (int ee = 0; ee < 4; ++ee) f[4 * q + ee] = v[ee];
+            for (int ee = 0; ee < 4; ++ee) f[4 * q + ee] = v[ee];
+        }
     }
 #pragma unroll
     for (int n = 0; n < 4; ++n) *reinterpret_cast<f32x4*>(R + (8 * n + js) * 36 + 4 * c) = au[n];

@@ -215,10 +215,13 @@ __device__ __forceinline__ void store_mask_word(unsigned* mask, long long sidx, 
 // ReLU so that the word is not live across the normal chain; a skipped tile step stores 0 (every mask false).  The address
 // is formed at the store from the sample index, which is live anyway (opaque copy: hipcc would otherwise keep the pointer
 // pair alive across the whole decode, and the S3 instantiation has no register left for it).
-template <bool NEED_N, int PREC, bool MASK = false>
+// MASK == MASK_H1H2 (tt_render_fwd_masks): the sign mask of h1 goes to mask1[2 sidx + hi] in the same way, built and stored
+// right after the ReLU of h1, before W2 h1, so that it is not live across a product either.
+enum { MASK_NONE = 0, MASK_H2 = 1, MASK_H1H2 = 2 };
+template <bool NEED_N, int PREC, int MASK = MASK_NONE>
 __device__ __forceinline__ void decode_geo_fwd(const float* L, const DecodeCfg& dc, float X, float Y, float Z,
                                                bool valid, int i, int hi, float& s0, float (&gq)[3],
-                                               unsigned* mask = nullptr, long long sidx = 0) {
+                                               unsigned* mask = nullptr, long long sidx = 0, unsigned* mask1 = nullptr) {
     typedef FwdMap<PREC> F;
     s0 = 0.f;
     gq[0] = gq[1] = gq[2] = 0.f;
@@ -245,10 +248,13 @@ __device__ __forceinline__ void decode_geo_fwd(const float* L, const DecodeCfg& 
         mvx<PREC, true>(L, typename F::W1{}, f, h1, i, hi, 1.f, &u1);
 #pragma unroll
         for (int r = 0; r < 32; ++r) h1[r] = fmaxf(h1[r], 0.f);
+        if constexpr (MASK == MASK_H1H2) {
+            store_mask_word(mask1, sidx, hi, valid, sign_mask32(h1));
+        }
         mvx<PREC, true>(L, typename F::W2{}, h1, h2, i, hi, u1, &u2);
 #pragma unroll
         for (int r = 0; r < 32; ++r) h2[r] = fmaxf(h2[r], 0.f);
-        if constexpr (MASK) {
+        if constexpr (MASK != MASK_NONE) {
             store_mask_word(mask, sidx, hi, valid, sign_mask32(h2));
         }
         s0 = dot_lds<64>(lds_at(L, typename F::W3{}), h2, hi) * u2;
@@ -277,19 +283,20 @@ __device__ __forceinline__ void decode_geo_fwd(const float* L, const DecodeCfg& 
             gq[1] = sy + __shfl_xor(sy, 32);
             gq[2] = sz + __shfl_xor(sz, 32);
         }
-    } else if constexpr (MASK) {
+    } else if constexpr (MASK != MASK_NONE) {
         store_mask_word(mask, sidx, hi, valid, 0u);
+        if constexpr (MASK == MASK_H1H2) store_mask_word(mask1, sidx, hi, valid, 0u);
     }
 }
 
-template <bool NEED_N, bool NEED_TEX, int PREC, bool MASK = false>
+template <bool NEED_N, bool NEED_TEX, int PREC, int MASK = MASK_NONE>
 __device__ __forceinline__ void decode_fwd(const float* L, const DecodeCfg& dc, float px, float py, float pz,
                                            bool valid, int i, int hi, float& s0, float (&gq)[3], float (&c)[3],
-                                           unsigned* mask = nullptr, long long sidx = 0) {
+                                           unsigned* mask = nullptr, long long sidx = 0, unsigned* mask1 = nullptr) {
     const float X = scale_coord(px, dc.radius), Y = scale_coord(py, dc.radius), Z = scale_coord(pz, dc.radius);
     c[0] = c[1] = c[2] = 0.f;
     if (NEED_TEX) decode_tex_fwd<PREC>(L, dc, X, Y, Z, valid, i, hi, c);
-    decode_geo_fwd<NEED_N, PREC, MASK>(L, dc, X, Y, Z, valid, i, hi, s0, gq, mask, sidx);
+    decode_geo_fwd<NEED_N, PREC, MASK>(L, dc, X, Y, Z, valid, i, hi, s0, gq, mask, sidx, mask1);
 }
 
 // =====================================================================================================
@@ -459,11 +466,12 @@ struct DecodeRaysParams {
     float* sdf;
     float* sdf_grad;
     float* features;
-    unsigned* h2_mask;  // (n_rays*S, 2) sign masks of h2 for the geometry backward (MASK instantiation), else null
+    unsigned* h2_mask;  // (n_rays*S, 2) sign masks of h2 for the geometry backward (MASK instantiations), else null
+    unsigned* h1_mask;  // (n_rays*S, 2) sign masks of h1, same layout (MASK_H1H2 instantiation), else null
 };
 
-// MASK: the instantiation tt_render_fwd_h2mask launches; the arithmetic and every other store are the same
-template <bool NEED_N, bool NEED_TEX, int PREC, bool MASK = false>
+// MASK: the instantiations tt_render_fwd_h2mask / tt_render_fwd_masks launch; the arithmetic and every other store are the same
+template <bool NEED_N, bool NEED_TEX, int PREC, int MASK = MASK_NONE>
 __global__ __launch_bounds__(DECODE_THREADS) void k_decode_rays(DecodeRaysParams p) {
     __shared__ __attribute__((aligned(16))) float L[FwdMap<PREC>::FLOATS + (DECODE_THREADS / 64) * GC_SCRATCH_FLOATS];
     float* T = L + FwdMap<PREC>::FLOATS + (threadIdx.x >> 6) * GC_SCRATCH_FLOATS;
@@ -525,7 +533,7 @@ __global__ __launch_bounds__(DECODE_THREADS) void k_decode_rays(DecodeRaysParams
             float tm, px, py, pz;
             sample_position(ox, oy, oz, dx, dy, dz, ts, te, tm, px, py, pz);
             float s0, gq[3], c[3];
-            decode_fwd<NEED_N, NEED_TEX, PREC, MASK>(L, dc, px, py, pz, rvalid, i, hi, s0, gq, c, p.h2_mask, sidx);
+            decode_fwd<NEED_N, NEED_TEX, PREC, MASK>(L, dc, px, py, pz, rvalid, i, hi, s0, gq, c, p.h2_mask, sidx, p.h1_mask);
             float nrm;
             const float sdf = s0 + sphere_bias(px, py, pz, cfg.sdf_bias_radius, nrm);
             if (rvalid && hi == 0 && !TT_DBG(cfg.flags, TT_DBG_NO_STORE)) {
@@ -543,7 +551,11 @@ __global__ __launch_bounds__(DECODE_THREADS) void k_decode_rays(DecodeRaysParams
             }
         }
     }
-    tile_stats_flush(st);
+    // (MASK_H1H2: the default mode's instantiation has no register left to carry the lane index across the loop for the flush)
+    if constexpr (MASK == MASK_H1H2)
+        tile_stats_flush_late(st);
+    else
+        tile_stats_flush(st);
 }
 
 // =====================================================================================================
@@ -885,11 +897,11 @@ long long tt_make_geom(const tt_render_cfg* cfg, long long wave_slots, TileGeom*
     return n_blocks * g->n_chunks;
 }
 
-// tt_render_fwd (h2_mask null) / tt_render_fwd_h2mask
+// tt_render_fwd (h2_mask null) / tt_render_fwd_h2mask (h1_mask null) / tt_render_fwd_masks
 static int render_fwd(const float* packed, const tt_mlp_weights* w, const float* rays_o, const float* rays_d,
                       const float* t_starts, const float* t_ends, const tt_render_cfg* cfg, float* opacity, float* depth,
                       float* rgb_fg, float* z_variance, float* normal_acc, float* weights, float* trans, float* sdf,
-                      float* sdf_grad, float* features, uint32_t* h2_mask, void* stream) {
+                      float* sdf_grad, float* features, uint32_t* h2_mask, uint32_t* h1_mask, void* stream) {
     int st = tt_validate_cfg(cfg);
     if (st != TT_OK) return st;
     if (!packed || !w || !rays_o || !rays_d || !t_starts || !t_ends || !opacity || !depth || !rgb_fg || !z_variance ||
@@ -905,14 +917,17 @@ static int render_fwd(const float* packed, const tt_mlp_weights* w, const float*
     p.sdf_grad = sdf_grad;
     p.features = features;
     p.h2_mask = h2_mask;
+    p.h1_mask = h1_mask;
     hipStream_t s = (hipStream_t)stream;
     // one 8-wave workgroup per CU (LDS 93 KB)
     st = tt_plan_queue(cfg, (long long)cus * (DECODE_THREADS / 64), s, &p.geom, &p.n_items, &p.queue, 12);
     if (st != TT_OK) return st;
     const dim3 grid((unsigned)tt_persistent_blocks(p.n_items, cus, DECODE_THREADS / 64));
     tt_dispatch_prec(tt_prec_of_r(cfg->flags), [&](auto P) {
-        if (h2_mask)
-            hipLaunchKernelGGL((k_decode_rays<true, true, decltype(P)::value, true>), grid, dim3(DECODE_THREADS), 0, s, p);
+        if (h2_mask && h1_mask)
+            hipLaunchKernelGGL((k_decode_rays<true, true, decltype(P)::value, MASK_H1H2>), grid, dim3(DECODE_THREADS), 0, s, p);
+        else if (h2_mask)
+            hipLaunchKernelGGL((k_decode_rays<true, true, decltype(P)::value, MASK_H2>), grid, dim3(DECODE_THREADS), 0, s, p);
         else
             hipLaunchKernelGGL((k_decode_rays<true, true, decltype(P)::value>), grid, dim3(DECODE_THREADS), 0, s, p);
     });
@@ -927,7 +942,7 @@ extern "C" int tt_render_fwd(const float* packed, const tt_mlp_weights* w, const
                              float* depth, float* rgb_fg, float* z_variance, float* normal_acc, float* weights,
                              float* trans, float* sdf, float* sdf_grad, float* features, void* stream) {
     return render_fwd(packed, w, rays_o, rays_d, t_starts, t_ends, cfg, opacity, depth, rgb_fg, z_variance, normal_acc,
-                      weights, trans, sdf, sdf_grad, features, nullptr, stream);
+                      weights, trans, sdf, sdf_grad, features, nullptr, nullptr, stream);
 }
 
 extern "C" int tt_render_fwd_h2mask(const float* packed, const tt_mlp_weights* w, const float* rays_o,
@@ -937,7 +952,17 @@ extern "C" int tt_render_fwd_h2mask(const float* packed, const tt_mlp_weights* w
                                     float* sdf_grad, float* features, uint32_t* h2_mask, void* stream) {
     if (!h2_mask) return TT_ERR_BAD_ARG;
     return render_fwd(packed, w, rays_o, rays_d, t_starts, t_ends, cfg, opacity, depth, rgb_fg, z_variance, normal_acc,
-                      weights, trans, sdf, sdf_grad, features, h2_mask, stream);
+                      weights, trans, sdf, sdf_grad, features, h2_mask, nullptr, stream);
+}
+
+extern "C" int tt_render_fwd_masks(const float* packed, const tt_mlp_weights* w, const float* rays_o,
+                                   const float* rays_d, const float* t_starts, const float* t_ends,
+                                   const tt_render_cfg* cfg, float* opacity, float* depth, float* rgb_fg,
+                                   float* z_variance, float* normal_acc, float* weights, float* trans, float* sdf,
+                                   float* sdf_grad, float* features, uint32_t* h2_mask, uint32_t* h1_mask, void* stream) {
+    if (!h2_mask || !h1_mask) return TT_ERR_BAD_ARG;
+    return render_fwd(packed, w, rays_o, rays_d, t_starts, t_ends, cfg, opacity, depth, rgb_fg, z_variance, normal_acc,
+                      weights, trans, sdf, sdf_grad, features, h2_mask, h1_mask, stream);
 }
 
 // Decode only (no march): sdf [+ sdf_grad] [+ features] at the mid-points of the given intervals.  Used by the
@@ -961,6 +986,7 @@ extern "C" int tt_decode_rays(const float* packed, const tt_mlp_weights* w, cons
     p.sdf_grad = sdf_grad;
     p.features = features;
     p.h2_mask = nullptr;
+    p.h1_mask = nullptr;
     hipStream_t s = (hipStream_t)stream;
     const long long slots = (long long)cus * (DECODE_THREADS / 64);
     // The sdf-only decode (the sampler's proposal pass) is so cheap per tile step that an item's ray set-up, its queue pop and

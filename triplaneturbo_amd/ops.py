@@ -212,6 +212,30 @@ class RenderConfig:
     # backward reads it (tt_render_fwd_h2mask / tt_render_bwd_geo_h2mask); False = the backward recomputes the layer for
     # its signs (tt_render_fwd / tt_render_bwd_geo: the A/B reference of the mask path)
     fwd_mask: bool = True
+    # with fwd_mask: the forward saves the sign mask of the FIRST hidden layer as well (8 more bytes per sample) and the
+    # geometry backward forms v = m1 . (W1 u) from one W1 product (tt_render_fwd_masks / tt_render_bwd_geo_masks); False =
+    # the h2-only pair above (the A/B reference of the one-product form).  No effect without fwd_mask.
+    fwd_mask_h1: bool = True
+
+
+def sign_mask_bits(words: Tensor) -> Tensor:
+    """(n, 2) int32 sign-mask words of tt_render_fwd_h2mask / tt_render_fwd_masks -> (n, 64) bool.  Element e of the hidden
+    vector sits in dword (e >> 2) & 1 at bit (e & 3) + 4 (e >> 3): the kernels' register layout (include/tt_abi.h)."""
+    if words.ndim != 2 or words.shape[1] != 2:
+        raise ValueError(f"sign-mask words: expected (n, 2), got {tuple(words.shape)}")
+    w = words.to(torch.int64) & 0xFFFFFFFF
+    e = torch.arange(64, device=words.device)
+    return ((w[:, (e >> 2) & 1] >> ((e & 3) + 4 * (e >> 3))[None, :]) & 1).bool()
+
+
+def sign_mask_words(bits: Tensor) -> Tensor:
+    """Inverse of sign_mask_bits: (n, 64) bool -> (n, 2) int32 words."""
+    if bits.ndim != 2 or bits.shape[1] != 64:
+        raise ValueError(f"sign-mask bits: expected (n, 64), got {tuple(bits.shape)}")
+    e = torch.arange(64, device=bits.device)
+    contrib = bits.to(torch.int64) << ((e & 3) + 4 * (e >> 3))[None, :]
+    w = torch.stack([contrib[:, ((e >> 2) & 1) == d].sum(dim=1) for d in (0, 1)], dim=1)
+    return torch.where(w >= 1 << 31, w - (1 << 32), w).to(torch.int32)
 
 
 def planes_pack(space_cache: Tensor) -> Tensor:
@@ -469,11 +493,15 @@ def _ray_outputs(n_rays: int, device, S: Optional[int] = None) -> dict:
 
 def render_forward_raw(packed: Tensor, sdf_w: Sequence[Tensor], feat_w: Sequence[Tensor], rays_o: Tensor,
                        rays_d: Tensor, t_starts: Tensor, t_ends: Tensor, rays_per_view: int, rc: RenderConfig,
-                       per_sample: bool = True, image_w: int = 0, h2_mask: Union[bool, Tensor] = False):
+                       per_sample: bool = True, image_w: int = 0, h2_mask: Union[bool, Tensor] = False,
+                       h1_mask: Union[bool, Tensor] = False):
     """One tt_render_fwd call (decode kernel + march kernel).  rays_* (n_rays,3); t_* (n_rays,S); image_w = width
     of each view's ray image (enables 8x4 pixel tiles).  Returns a dict of raw kernel outputs.  h2_mask=True (or the
     int32 buffer to write): the tt_render_fwd_h2mask form, which also returns "h2_mask" (n_rays*S, 2) int32, the saved
-    state of tt_render_bwd_geo_h2mask."""
+    state of tt_render_bwd_geo_h2mask.  h1_mask=True (or the buffer; needs h2_mask): the tt_render_fwd_masks form, which
+    returns "h1_mask" in the same shape and layout too, the saved state of tt_render_bwd_geo_masks."""
+    if h1_mask is not False and h2_mask is False:
+        raise ValueError("h1_mask needs h2_mask (tt_render_fwd_masks writes both)")
     packed, rays_o, rays_d, t_starts, t_ends = _ray_args(packed, rays_o, rays_d, t_starts, t_ends)
     n_rays, S = t_starts.shape
     cfg = _make_cfg(packed, n_rays, rays_per_view, S, rc, per_sample, image_w)
@@ -489,6 +517,15 @@ def render_forward_raw(packed: Tensor, sdf_w: Sequence[Tensor], feat_w: Sequence
         out["h2_mask"] = _chk(h2_mask, "h2_mask", (n_rays * S, 2), torch.int32)
         if out["h2_mask"].data_ptr() != h2_mask.data_ptr():
             raise ValueError("h2_mask must be contiguous (the kernel writes it in place)")
+    if h1_mask is not False:
+        if h1_mask is True:
+            h1_mask = torch.empty((n_rays * S, 2), device=packed.device, dtype=torch.int32)
+        out["h1_mask"] = _chk(h1_mask, "h1_mask", (n_rays * S, 2), torch.int32)
+        if out["h1_mask"].data_ptr() != h1_mask.data_ptr():
+            raise ValueError("h1_mask must be contiguous (the kernel writes it in place)")
+        _launch("tt_render_fwd_masks", packed, wst, rays_o, rays_d, t_starts, t_ends, cfg, *out.values(),
+                label="tt_render_fwd")
+    elif h2_mask is not False:
         _launch("tt_render_fwd_h2mask", packed, wst, rays_o, rays_d, t_starts, t_ends, cfg, *out.values(),
                 label="tt_render_fwd")
     else:
@@ -633,6 +670,12 @@ def _grads_struct(tensors: Sequence[Tensor]):
     return _lib.MlpWeights(*[_ptr(t) for t in tensors])  # same layout as tt_mlp_grads (6 pointers)
 
 
+def _both_masks(rc: RenderConfig) -> bool:
+    """The differentiable render saves the h1 sign mask next to the h2 one: the fp32-MFMA kernel has no use for it (its
+    geometry backward stays on the h2-only path), so that mode does not pay for the word."""
+    return bool(rc.fwd_mask and rc.fwd_mask_h1 and rc.prec != "f32")
+
+
 class _TriplaneRenderFn(torch.autograd.Function):
     """Differentiable fused render on packed planes.  forward = tt_render_fwd; backward = tt_render_bwd_geo +
     tt_render_bwd_tex.  Differentiable inputs: the packed planes (see pack_planes) and the six MLP weights (sample
@@ -648,7 +691,8 @@ class _TriplaneRenderFn(torch.autograd.Function):
         ctx.set_materialize_grads(False)  # unused outputs (e.g. `features`, `weights`) reach backward as None, not as
         #                                    100 MB of zeros the kernels would have to read
         raw = render_forward_raw(packed, (w1, w2, w3), (v1, v2, v3), rays_o, rays_d, t_starts, t_ends, rays_per_view,
-                                 rc, per_sample=True, image_w=image_w, h2_mask=need_grad and rc.fwd_mask)
+                                 rc, per_sample=True, image_w=image_w, h2_mask=need_grad and rc.fwd_mask,
+                                 h1_mask=need_grad and _both_masks(rc))
         ctx.rays_per_view = rays_per_view
         ctx.rc = rc
         ctx.image_w = image_w
@@ -656,7 +700,8 @@ class _TriplaneRenderFn(torch.autograd.Function):
         if need_grad:
             ctx.save_for_backward(packed, w1, w2, w3, v1, v2, v3, rays_o, rays_d, t_starts, t_ends, raw["opacity"],
                                   raw["depth"], raw["trans"], raw["weights"], raw["features"], raw["sdf"],
-                                  raw["sdf_grad"], *([raw["h2_mask"]] if rc.fwd_mask else []))
+                                  raw["sdf_grad"], *([raw["h2_mask"]] if rc.fwd_mask else []),
+                                  *([raw["h1_mask"]] if _both_masks(rc) else []))
         ctx.mark_non_differentiable(raw["trans"])
         return (raw["opacity"], raw["depth"], raw["rgb_fg"], raw["z_variance"], raw["normal_acc"], raw["weights"],
                 raw["sdf"], raw["sdf_grad"], raw["features"], raw["trans"])
@@ -666,7 +711,7 @@ class _TriplaneRenderFn(torch.autograd.Function):
     def backward(ctx, g_op, g_depth, g_rgb, g_zvar, g_nacc, g_weights, g_sdf, g_sdf_grad, g_features, _g_trans):
         (packed, w1, w2, w3, v1, v2, v3, rays_o, rays_d, t_starts, t_ends, opacity, depth, trans, weights,
          features, sdf, sdf_grad) = ctx.saved_tensors[:18]
-        h2_mask = ctx.saved_tensors[18:]  # (the forward's h2 sign mask) or nothing: rc.fwd_mask
+        masks = ctx.saved_tensors[18:]  # the forward's h2 sign mask [and h1 sign mask], or nothing: rc.fwd_mask[_h1]
         n_rays, S = t_starts.shape
         cfg = _make_cfg(packed, n_rays, ctx.rays_per_view, S, ctx.rc, True, ctx.image_w, stats_row=1)
         cfg_tex = _make_cfg(packed, n_rays, ctx.rays_per_view, S, ctx.rc, True, ctx.image_w, stats_row=2)
@@ -682,9 +727,9 @@ class _TriplaneRenderFn(torch.autograd.Function):
         g_k_rays = None
         if ctx.needs_input_grad[14]:  # d loss / d inv_std, one partial per ray (summed below in a fixed order)
             g_k_rays = torch.empty((n_rays,), device=packed.device, dtype=torch.float32)
-        _launch("tt_render_bwd_geo_h2mask" if h2_mask else "tt_render_bwd_geo", packed, wst, rays_o, rays_d, t_starts,
+        _launch(("tt_render_bwd_geo", "tt_render_bwd_geo_h2mask", "tt_render_bwd_geo_masks")[len(masks)], packed, wst, rays_o, rays_d, t_starts,
                 t_ends, cfg, opacity, depth, trans, sdf, sdf_grad, features, g_op, g_depth, g_rgb, g_zvar, g_nacc,
-                g_weights, g_sdf, g_sdf_grad, g_k_rays, workspace, grad_packed, gst, *h2_mask, label="tt_render_bwd_geo")
+                g_weights, g_sdf, g_sdf_grad, g_k_rays, workspace, grad_packed, gst, *masks, label="tt_render_bwd_geo")
         _launch("tt_render_bwd_tex", packed, wst, rays_o, rays_d, t_starts, t_ends, cfg_tex, weights, features, g_rgb,
                 g_features, grad_packed, gst, label="tt_render_bwd_tex")
         g_packed = None
