@@ -71,6 +71,8 @@
  *                           leaves to external tools.
  *   tt_simplify_*           mesh simplification for export: vertex clustering with quadric-error placement.  The
  *                           reference exports the raw marching-cubes mesh; this step has no counterpart there.
+ *   tt_decimate_*           mesh decimation for export: manifold-preserving parallel quadric edge collapse.  No
+ *                           counterpart in the reference either.
  *   tt_bake_*               Mesh.v_tng (threestudio/models/mesh.py:162-205) and the tangent-space normal map (map_Bump)
  *                           the exporter bakes for a simplified mesh from the field's analytic normals.
  *   tt_dist_*               closest point on a triangle mesh with a backward pass, and a surface sampler: what
@@ -924,6 +926,93 @@ int tt_simplify_emit_count(const int64_t* sorted_face_keys, const int64_t* face_
                            void* stream);
 int tt_simplify_emit(const float* cluster_pos, const int32_t* t_pos_idx, const int32_t* rank, int32_t V, int32_t T,
                      int32_t C, void* workspace, float* v_out, int32_t* t_out, int32_t* vertex_map, void* stream);
+
+/* ---- mesh decimation (tt_decimate.hip): manifold-preserving, round-based parallel quadric edge collapse ----
+ * Garland & Heckbert 1997 with the collapses of one round chosen so that their closed neighbourhoods are pairwise
+ * disjoint: they can then be applied together and every validity check made for one of them still holds.  The
+ * reference has no such step.  A mesh is v_pos (V,3) fp32 and t_pos_idx (T,3) int32 with every index in [0, V) (the
+ * host checks it; every kernel skips an index outside).  target_faces >= 4.
+ *   state       v_pos (V,3) fp32, the live faces tri (T,3) int32, one symmetric 4x4 quadric per vertex as 10 doubles
+ *               (a00 a01 a02 a11 a12 a22 b0 b1 b2 c: error(x) = x^T A x + 2 b^T x + c), root (V) int32 = the current
+ *               representative of every input vertex, remap (V) int32 = the identity between rounds.  Vertices are
+ *               never renumbered during the rounds.
+ *   quadrics    once, from the INPUT mesh, in fp64 (tt_decimate_quadrics, one thread per vertex): for the faces of the
+ *               vertex in ascending face order (the vertex -> face CSR: vf_ptr (V+1), vf_col = face corners 3f + k
+ *               ascending inside a row), n = (p1 - p0) x (p2 - p0), l = |n|; l == 0 contributes nothing; else
+ *               n^ = n / l, area = l / 2, d = -n^ . p0; A += area n^ n^T, b += area d n^, c += area d d.
+ *   topology    of a round (host): the unique edges (a, b), a <= b, in lexicographic order with the number of face
+ *               edges that use each (edges (E,2), counts (E) int32), the vertex -> neighbour CSR with ascending rows
+ *               (nbr_ptr (V+1), nbr_col (2E)) and the vertex -> face CSR of the live faces.
+ *   locking     tt_decimate_lock, one thread per edge: locked (V) uint8 = 1 for both endpoints of an edge with
+ *               counts != 2 (boundary, non-manifold) or a == b, else 0.  A locked vertex never moves or merges.
+ *   cost        tt_decimate_edges, one thread per edge, Qe = Qa + Qb, fp64: det and the cofactors of A;
+ *               |det| > 1e-9 (trace A / 3)^3: x = -A^-1 b; else x = the cheapest of v_a, v_b, (v_a + v_b) / 2, ties in
+ *               that order.  cost = max(error(x), 0) at the fp64 x, rounded to fp32; x is rounded to fp32.
+ *   validity    neither endpoint locked, a != b; deg a + deg b - 4 >= 3 (deg = row length of the neighbour CSR);
+ *               |N(a) n N(b)| == 2 by a merge of the two rows (the link condition) and both common neighbours have
+ *               deg >= 4; every face of star(a) u star(b) that does not hold both endpoints, with its corner a or b
+ *               moved to the fp32 x, has n_new != 0 and n_old . n_new > 0.2 |n_old| |n_new| (fp64).
+ *               cost_bits (E) = the bit pattern of the fp32 cost (unsigned order = cost order), 0xffffffff for an
+ *               invalid edge; xopt (E,3) fp32, zero for an invalid edge.
+ *   threshold   (host, on the device) tau = the cost_bits at rank floor(TT_DECIMATE_QUANTILE n_valid) of the valid
+ *               edges' ascending cost_bits, as one int64 in DEVICE memory; the candidates are the valid edges with
+ *               cost_bits <= tau.
+ *   priorities  key = (uint64) hash32(a, b, round) << 32 | edge index, with (all uint32, wrapping)
+ *                   h = (a * 0x9E3779B1) ^ ((b + 0x7F4A7C15) * 0x85EBCA77) ^ ((round + 1) * 0xC2B2AE3D);
+ *                   h ^= h >> 16; h *= 0x7FEB352D; h ^= h >> 15; h *= 0x846CA68B; h ^= h >> 16.
+ *   selection   TT_DECIMATE_SELECT_PASSES passes of tt_decimate_mark, tt_decimate_select over state (E) uint8 (0 no
+ *               candidate, 1 candidate, 2 selected, 3 blocked), taken (V) uint8 (host: zero before pass 0) and owner
+ *               (V) uint64 (host: all ones before every pass).  The closed neighbourhood of an edge is {a, b} u N(a)
+ *               u N(b).  mark: pass 0 writes every state from cost_bits and tau; a candidate whose neighbourhood
+ *               holds a taken vertex becomes blocked; every other candidate does a 64-bit atomicMin of its key into
+ *               owner[w] for every w of its neighbourhood.  select: a candidate that owns every such w becomes selected
+ *               and sets taken[w] for all of them.  Selected edges have pairwise disjoint closed neighbourhoods; the
+ *               candidate with the smallest key is always selected in pass 0.
+ *   budget      (host) need = ceil((T - target_faces) / 2); of more than `need` selected edges the `need` smallest by
+ *               (cost_bits, edge index) are kept, listed in ascending edge index.
+ *   apply       tt_decimate_apply for the K kept edges: v_pos[a] = xopt, Q[a] += Q[b], remap[b] = a; every face is
+ *               remapped, one with two equal corners is dropped, the survivors are written to t_out (room for T rows)
+ *               in their order (the two-counter compaction of tt_compact.h); root[v] = remap[root[v]]; remap returns
+ *               to the identity.  out_totals[1] (2 int32, DEVICE memory, read back) = the number of faces written.
+ *   rounds      stop when T <= target_faces, when a round has no valid edge (stalled), or after max_rounds.
+ *   output      tt_decimate_emit_count leaves (V', 0) in out_totals; tt_decimate_emit, with the same workspace and T,
+ *               writes the vertices a live face references in index order (v_out (V',3)), the faces renumbered (t_out
+ *               (T,3)) and vertex_map (V) int32 = the output vertex of each input vertex's root, -1 for a vertex no
+ *               face referenced.
+ * Guarantees: identical inputs give bit-identical outputs (no float atomics, fixed summation orders, the one atomic is
+ * an integer min).  A closed 2-manifold input gives a closed 2-manifold with the same Euler characteristic and number
+ * of components; no collapse flips a face past the 0.2 bound; locked vertices keep their position bit for bit and are
+ * all present; a closed manifold input that does not stall ends with target_faces - 1 <= T' <= target_faces.  NOT
+ * guaranteed: freedom from self-intersection between parts of the surface that are far apart on the mesh, and any
+ * particular accuracy.
+ * Use: bytes = tt_decimate_workspace_bytes(V, T) for the INPUT sizes (one workspace for every call of one run, T only
+ * falls); quadrics once; per round lock, edges, (mark, select) per pass, apply; at the end emit_count, emit.  Every
+ * entry point validates its arguments before any HIP call (TT_ERR_BAD_ARG); V, T <= TT_MESH_MAX_ITEMS, 1 <= E <= 3 T,
+ * 1 <= K <= T. */
+#define TT_DECIMATE_QUANTILE 0.25f
+#define TT_DECIMATE_SELECT_PASSES 2
+#define TT_DECIMATE_MIN_FACES 4
+#define TT_DECIMATE_DEFAULT_ROUNDS 1024
+int64_t tt_decimate_workspace_bytes(int32_t V, int32_t T);
+int tt_decimate_quadrics(const float* v_pos, const int32_t* t_pos_idx, const int32_t* vf_ptr, const int32_t* vf_col,
+                         int32_t V, int32_t T, double* quadrics, void* stream);
+int tt_decimate_lock(const int32_t* edges, const int32_t* counts, int32_t V, int32_t E, uint8_t* locked, void* stream);
+int tt_decimate_edges(const float* v_pos, const double* quadrics, const int32_t* t_pos_idx, const int32_t* edges,
+                      const int32_t* nbr_ptr, const int32_t* nbr_col, const int32_t* vf_ptr, const int32_t* vf_col,
+                      const uint8_t* locked, int32_t V, int32_t T, int32_t E, int32_t* cost_bits, float* xopt,
+                      void* stream);
+int tt_decimate_mark(const int32_t* edges, const int32_t* nbr_ptr, const int32_t* nbr_col, const int32_t* cost_bits,
+                     const int64_t* tau, int32_t V, int32_t T, int32_t E, int32_t round, int32_t pass, uint8_t* state,
+                     const uint8_t* taken, int64_t* owner, void* stream);
+int tt_decimate_select(const int32_t* edges, const int32_t* nbr_ptr, const int32_t* nbr_col, int32_t V, int32_t T,
+                       int32_t E, int32_t round, uint8_t* state, uint8_t* taken, const int64_t* owner, void* stream);
+int tt_decimate_apply(const int32_t* kept_edges, const float* kept_xopt, const int32_t* t_pos_idx, int32_t V, int32_t T,
+                      int32_t K, void* workspace, float* v_pos, double* quadrics, int32_t* remap, int32_t* root,
+                      int32_t* t_out, int32_t* out_totals, void* stream);
+int tt_decimate_emit_count(const int32_t* t_pos_idx, int32_t V, int32_t T, void* workspace, int32_t* out_totals,
+                           void* stream);
+int tt_decimate_emit(const float* v_pos, const int32_t* t_pos_idx, const int32_t* root, int32_t V, int32_t T,
+                     void* workspace, float* v_out, int32_t* t_out, int32_t* vertex_map, void* stream);
 
 /* ---- tangents and normal-map baking (tt_bake.hip): Mesh.v_tng (threestudio/models/mesh.py:162-205) and the
  * exporter's map_Bump ----

@@ -104,6 +104,10 @@ class MultipromptMeshExporter(Exporter):
         self.simplify_grid: Optional[int] = None
         self.simplify_target_faces: Optional[int] = None
         self.simplify_max_error: Optional[float] = None
+        # Mesh.decimate's argument, an attribute for the same reason: with it set the exported mesh is mesh[0] decimated
+        # to at most that many faces (manifold-preserving edge collapse); together with a simplify attribute it is a
+        # ValueError at call time.
+        self.decimate_target_faces: Optional[int] = None
         # the tangent-space normal map of the exported mesh (map_Bump, ops.bake_normal_map) on the obj-mtl path with
         # save_texture, and the number of projection steps it takes towards the iso-surface; attributes for the same
         # reason.  Unset, params are exactly what they are without the bake.
@@ -125,6 +129,9 @@ class MultipromptMeshExporter(Exporter):
         if sum(v is not None for v in simplify.values()) > 1:
             raise ValueError("multiprompt-mesh-exporter: set at most one of simplify_grid, simplify_target_faces and "
                              "simplify_max_error")
+        if self.decimate_target_faces is not None and any(v is not None for v in simplify.values()):
+            raise ValueError("multiprompt-mesh-exporter: decimate_target_faces cannot be combined with a simplify_* "
+                             "attribute")
         isosurface = getattr(self.geometry, "isosurface", None)
         if isosurface is None:
             raise RuntimeError("geometry.isosurface is not set: configure a generative-space-mesh-rasterize-renderer "
@@ -134,6 +141,8 @@ class MultipromptMeshExporter(Exporter):
             mesh = mesh[0]
         if any(v is not None for v in simplify.values()):
             mesh = mesh.simplify(**simplify)
+        if self.decimate_target_faces is not None:
+            mesh = mesh.decimate(self.decimate_target_faces)
         # the texture belongs to mesh[0]: decode it from the first prompt's slice of the space cache
         space_cache = prompt_slice(space_cache, 0)
         if self.cfg.fmt == "obj-mtl":

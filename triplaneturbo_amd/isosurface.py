@@ -374,6 +374,19 @@ class Mesh:
         mesh.extras["simplify"] = {k: info[k] for k in ("grid", "cell", "n_clusters", "vertex_map")}
         return mesh
 
+    def decimate(self, target_faces: int) -> Mesh:
+        """A low-poly copy with this mesh's topology: rounds of parallel quadric edge collapses down to at most
+        target_faces (>= 4) faces (ops.mesh_decimate; include/tt_abi.h "mesh decimation").  A closed 2-manifold stays
+        one, with the same genus and number of components, and no face flips; vertices on a boundary or a non-manifold
+        edge stay where they are.  A new Mesh that inherits extras, with extras["decimate"] = ops.mesh_decimate's info
+        ({target_faces, n_rounds, stalled, n_locked, vertex_map, unchanged}); a mesh that is empty, small enough or
+        admits no collapse comes back with its own tensors.  The result never requires grad."""
+        v_pos, t_pos_idx, info = ops.mesh_decimate(self.v_pos, self.t_pos_idx, target_faces)
+        mesh = Mesh(v_pos, t_pos_idx)
+        mesh.extras = dict(self.extras)
+        mesh.extras["decimate"] = info
+        return mesh
+
     def _compute_vertex_normal(self) -> Tensor:
         i0, i1, i2 = (self.t_pos_idx[:, c].long() for c in range(3))
         v0, v1, v2 = self.v_pos[i0, :], self.v_pos[i1, :], self.v_pos[i2, :]

@@ -1433,6 +1433,129 @@ def mesh_simplify(v_pos: Tensor, t_pos_idx: Tensor, grid: int, lam: float = SIMP
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# mesh decimation (include/tt_abi.h, "mesh decimation"): manifold-preserving parallel quadric edge collapse
+def _decimate_unchanged(v_pos: Tensor, t_pos_idx: Tensor, target_faces: int, stalled: bool = False, n_locked: int = 0,
+                        return_trace: bool = False) -> Tuple[Tensor, Tensor, dict]:
+    V = v_pos.shape[0]
+    info = {"target_faces": target_faces, "n_rounds": 0, "stalled": stalled, "n_locked": n_locked, "unchanged": True,
+            "vertex_map": torch.arange(V, device=v_pos.device, dtype=torch.int32)}
+    if return_trace:
+        info["trace"] = []
+    return v_pos, t_pos_idx, info
+
+
+@torch.no_grad()
+def mesh_decimate(v_pos: Tensor, t_pos_idx: Tensor, target_faces: int, max_rounds: Optional[int] = None,
+                  return_trace: bool = False) -> Tuple[Tensor, Tensor, dict]:
+    """Edge-collapse decimation to at most target_faces faces that keeps a closed 2-manifold a closed 2-manifold of the
+    same genus and flips no face: rounds of quadric edge collapses whose closed neighbourhoods are pairwise disjoint
+    (tt_decimate_*; per round one face-edge sort, two CSR sorts, one sort of the costs and four small read-backs).
+    Vertices on a boundary or a non-manifold edge are locked: they never move or merge.  Returns v_pos' (V',3) fp32,
+    t_pos_idx' (T',3) int32 and info = {target_faces, n_rounds (rounds that collapsed something), stalled (a round
+    found no valid collapse before the target was reached), n_locked (locked vertices of the input), vertex_map (V,)
+    int32: the output vertex each input vertex ended in, -1 for one no face referenced, unchanged}; with return_trace
+    info["trace"] holds one (edges (k,2) int32, xopt (k,3) fp32, cost_bits (k,) int64) per round: the collapses b -> a it
+    applied.  A closed manifold that does not stall ends with target_faces - 1 or target_faces faces.  A mesh that is
+    empty, has no more than target_faces faces or admits no collapse comes back as it is (unchanged = True).
+    Bit-identical from call to call.  Positions are detached; the result never requires grad."""
+    if isinstance(target_faces, bool) or not isinstance(target_faces, int):
+        raise TypeError(f"target_faces must be an int, got {type(target_faces).__name__}")
+    if target_faces < _lib.TT_DECIMATE_MIN_FACES:
+        raise ValueError(f"target_faces must be at least {_lib.TT_DECIMATE_MIN_FACES}, got {target_faces}")
+    if max_rounds is None:
+        max_rounds = _lib.TT_DECIMATE_DEFAULT_ROUNDS
+    elif isinstance(max_rounds, bool) or not isinstance(max_rounds, int) or max_rounds < 0:
+        raise ValueError(f"max_rounds must be a non-negative int, got {max_rounds!r}")
+    if (isinstance(v_pos, Tensor) and isinstance(t_pos_idx, Tensor) and v_pos.shape[1:] == t_pos_idx.shape[1:] == (3,)
+            and t_pos_idx.dtype in (torch.int32, torch.int64) and 0 in (v_pos.shape[0], t_pos_idx.shape[0])):
+        return _decimate_unchanged(v_pos.detach(), t_pos_idx, target_faces, return_trace=return_trace)  # an empty mesh
+    v_pos = _chk(v_pos, "v_pos", (None, 3)).detach()
+    t_pos_idx = _chk_index(t_pos_idx, "t_pos_idx", 3)
+    V, T, dev = v_pos.shape[0], t_pos_idx.shape[0], v_pos.device
+    _chk_size("mesh too large for tt_decimate_*", V=V, T=T)
+    chk = torch.cat([torch.isfinite(v_pos).all().reshape(1).long(), _minmax(t_pos_idx).long()]).tolist()  # one read-back
+    _chk_range("t_pos_idx", chk[1], chk[2], V)
+    if not chk[0]:
+        raise ValueError("v_pos holds a value that is not finite")
+    if T <= target_faces:
+        return _decimate_unchanged(v_pos, t_pos_idx, target_faces, return_trace=return_trace)
+    i32 = dict(device=dev, dtype=torch.int32)
+    u8 = dict(device=dev, dtype=torch.uint8)
+    ws = _workspace("tt_decimate_workspace_bytes", V, T, device=dev)
+    pos = v_pos.clone()
+    bufs = [t_pos_idx.int().contiguous().clone(), torch.empty((T, 3), **i32)]  # the live faces, written back and forth
+    tri, cur = bufs[0], 0
+    vf_ptr, vf_col = _csr(tri.reshape(-1).long(), None, V, 3 * T)
+    quadrics = torch.empty((V, 10), device=dev, dtype=torch.float64)
+    _launch("tt_decimate_quadrics", pos, tri, vf_ptr, vf_col, V, T, quadrics, label="decimate_quadrics")
+    root, remap = torch.arange(V, **i32), torch.arange(V, **i32)
+    locked, taken = torch.empty(V, **u8), torch.empty(V, **u8)
+    owner = torch.empty(V, device=dev, dtype=torch.int64)
+    totals = torch.empty(2, **i32)
+    trace, stalled, n_locked, rnd = [], False, 0, 0
+    while T > target_faces and rnd < max_rounds:
+        fe = sort_face_edges(tri, V)
+        e0, e1 = fe.uniq // fe.base, fe.uniq % fe.base
+        E = int(e0.shape[0])
+        edges = torch.stack([e0, e1], dim=1).int().contiguous()
+        nbr_ptr, nbr_col = _csr(torch.cat([e0, e1]), torch.cat([e1, e0]), V, V)
+        if rnd > 0:
+            vf_ptr, vf_col = _csr(tri.reshape(-1).long(), None, V, 3 * T)
+        _launch("tt_decimate_lock", edges, fe.counts.int().contiguous(), V, E, locked, label="decimate_lock")
+        cost_bits, xopt = torch.empty(E, **i32), torch.empty((E, 3), device=dev, dtype=torch.float32)
+        _launch("tt_decimate_edges", pos, quadrics, tri, edges, nbr_ptr, nbr_col, vf_ptr, vf_col, locked, V, T, E,
+                cost_bits, xopt, label="decimate_edges")
+        # the threshold stays on the device: the cost bits at rank floor(quantile * n_valid) of the valid edges
+        cb = cost_bits.long() & 0xffffffff
+        n_valid = (cb != 0xffffffff).sum()
+        rank = (n_valid.double() * _lib.TT_DECIMATE_QUANTILE).floor().long().clamp(max=E - 1)
+        tau = torch.sort(cb)[0].gather(0, rank.reshape(1)).contiguous()
+        state = torch.empty(E, **u8)
+        taken.zero_()
+        for p in range(_lib.TT_DECIMATE_SELECT_PASSES):
+            owner.fill_(-1)
+            _launch("tt_decimate_mark", edges, nbr_ptr, nbr_col, cost_bits, tau, V, T, E, rnd, p, state, taken, owner,
+                    label="decimate_mark")
+            _launch("tt_decimate_select", edges, nbr_ptr, nbr_col, V, T, E, rnd, state, taken, owner,
+                    label="decimate_select")
+        selected = state == 2
+        n_valid, n_selected, n_lock = torch.stack([n_valid, selected.sum(), locked.sum()]).tolist()  # one read-back
+        if rnd == 0:
+            n_locked = n_lock
+        if n_valid == 0 or n_selected == 0:
+            stalled = True
+            break
+        need = (T - target_faces + 1) // 2
+        kept = selected.nonzero().reshape(-1)  # ascending edge index
+        if n_selected > need:  # the `need` smallest by (cost bits, edge index)
+            kept = torch.sort(kept[torch.sort(cb[kept], stable=True)[1][:need]])[0]
+        K = int(kept.shape[0])
+        k_edges, k_xopt = edges[kept].contiguous(), xopt[kept].contiguous()
+        out = bufs[1 - cur]
+        _launch("tt_decimate_apply", k_edges, k_xopt, tri, V, T, K, ws, pos, quadrics, remap, root, out, totals,
+                label="decimate_apply")
+        T = int(totals[1].item())
+        cur = 1 - cur
+        tri = bufs[cur][:T]
+        rnd += 1
+        if return_trace:
+            trace.append((k_edges, k_xopt, cb[kept]))
+    if rnd == 0:
+        return _decimate_unchanged(v_pos, t_pos_idx, target_faces, stalled, n_locked, return_trace)
+    _launch("tt_decimate_emit_count", tri, V, T, ws, totals, label="decimate_emit_count")
+    n_vert = int(totals[0].item())
+    v_out = torch.empty((n_vert, 3), device=dev, dtype=torch.float32)
+    t_out = torch.empty((T, 3), **i32)
+    vertex_map = torch.empty(V, **i32)
+    _launch("tt_decimate_emit", pos, tri, root, V, T, ws, v_out, t_out, vertex_map, label="decimate_emit")
+    info = {"target_faces": target_faces, "n_rounds": rnd, "stalled": stalled, "n_locked": n_locked,
+            "vertex_map": vertex_map, "unchanged": False}
+    if return_trace:
+        info["trace"] = trace
+    return v_out, t_out, info
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # point-to-mesh distance (include/tt_abi.h, "point-to-mesh distance"): closest point on a triangle mesh, surface samples
 def dist_default_grid(n_faces: int) -> int:
     """The grid a TriangleGrid takes when the caller names none: clamp(ceil(sqrt(T) / 8), 1, TT_DIST_MAX_GRID), about two (cell, triangle) pairs
