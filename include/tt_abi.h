@@ -73,6 +73,8 @@
  *                           reference exports the raw marching-cubes mesh; this step has no counterpart there.
  *   tt_decimate_*           mesh decimation for export: manifold-preserving parallel quadric edge collapse.  No
  *                           counterpart in the reference either.
+ *   tt_remesh_*             isotropic remeshing (split, collapse, flip, relax) of an extracted mesh.  The reference
+ *                           hands the raw extraction to xatlas; no counterpart there.
  *   tt_bake_*               Mesh.v_tng (threestudio/models/mesh.py:162-205) and the tangent-space normal map (map_Bump)
  *                           the exporter bakes for a simplified mesh from the field's analytic normals.
  *   tt_dist_*               closest point on a triangle mesh with a backward pass, and a surface sampler: what
@@ -1013,6 +1015,111 @@ int tt_decimate_emit_count(const int32_t* t_pos_idx, int32_t V, int32_t T, void*
                            void* stream);
 int tt_decimate_emit(const float* v_pos, const int32_t* t_pos_idx, const int32_t* root, int32_t V, int32_t T,
                      void* workspace, float* v_out, int32_t* t_out, int32_t* vertex_map, void* stream);
+
+/* ---- isotropic remeshing (tt_remesh.hip): split, collapse, flip, relax (Botsch & Kobbelt 2004) ----
+ * Brings the edges of a mesh towards one length L and its vertices towards valence 6 on the surface of the INPUT mesh.
+ * The reference has no such step.  A mesh is v_pos (V,3) fp32 and t_pos_idx (T,3) int32 with every index in [0, V)
+ * (the host checks it; every kernel skips an index outside).  edge_length L > 0, iterations >= 0.
+ *   thresholds  h = (float)((4.0 / 3.0) * L), l = (float)(0.8 * L) (the products in double, L a double), hi2 = h * h,
+ *               lo2 = l * l in fp32 (host).  len2(p, q) = (dx dx + dy dy) + dz dz with d = q - p, every operation
+ *               rounded to fp32, no fused multiply-add; the midpoint of p, q is 0.5f * (p + q) per component in fp32.
+ *               Every length comparison below is len2 against hi2 or lo2.
+ *   topology    of a pass or round (host), as decimation's: the unique edges (a, b), a <= b, lexicographic, with their
+ *               counts, the two CSR tables with ascending rows, locked (tt_decimate_lock; recomputed every round);
+ *               for the split face_edge (3T) int32 = the unique edge of face edge 3f + k (corners k, (k+1) % 3); for
+ *               the flip edge_fe (E,2) int32 = the two face edges 3f + k of an edge with counts == 2 in ascending
+ *               order, -1 -1 for any other edge.
+ *   iteration   split, collapse, flip, move; after the last iteration one more split.
+ *   split       passes until no edge has len2 > hi2, at most TT_REMESH_MAX_SPLIT_PASSES (then split_capped).  A pass
+ *               marks every edge with a != b and len2 > hi2, boundary and non-manifold ones included; marked edge e
+ *               gets vertex V + rank(e), rank among the marked edges in ascending edge order, at the midpoint.
+ *               tt_remesh_split_count leaves (marked edges, child faces) in out_totals (read back; the host refuses
+ *               a result beyond TT_MESH_MAX_ITEMS before it emits); tt_remesh_split_emit writes the midpoints to
+ *               v_new (M,3) (the host appends them to v_pos), the marked edges to marked (M,2) and the children to
+ *               t_out (Tn,3) in parent order, then template order.  With m_k the midpoint vertex of edge k of face
+ *               (c0, c1, c2):
+ *                 none marked   (c0, c1, c2)
+ *                 edge k only   a = c_k, b = c_k+1, c = c_k+2:  (a, m_k, c), (m_k, b, c)
+ *                 all but k     a, b, c as above, mb = m_k+1, mc = m_k+2:  (mb, c, mc), then the quad a, b, mb, mc cut
+ *                               by the diagonal a-mb if len2(a, mb) < len2(b, mc), or if they are equal and a < b:
+ *                               (a, b, mb), (a, mb, mc); else by b-mc: (a, b, mc), (b, mb, mc)
+ *                 all three     (c0, m0, m2), (c1, m1, m0), (c2, m2, m1), (m0, m1, m2)
+ *               Orientation is kept, the templates of two faces agree on their shared edge by construction (no
+ *               selection), no existing vertex moves: surface and topology are kept exactly.
+ *   collapse    rounds until a round has no candidate, at most TT_REMESH_MAX_ROUNDS (then rounds_capped).
+ *               tt_remesh_collapse_candidates, one thread per edge: neither endpoint locked (so the edge has two
+ *               faces); len2(a, b) < lo2; decimation's link condition (deg a + deg b - 4 >= 3, exactly two common
+ *               neighbours, both of deg >= 4); with x = the midpoint, len2(w, x) <= hi2 for every w of N(a) u N(b)
+ *               other than a, b; decimation's flip test of star(a) u star(b) at x.  cost_bits = 0 for a candidate,
+ *               0xffffffff else; xopt = x.  Selection is one pass of tt_decimate_mark (tau = 0: every candidate is
+ *               eligible) and tt_decimate_select with the keys hash32(a, b, round) << 32 | edge index; every selected
+ *               edge is applied by tt_decimate_apply (b -> a at x; the quadrics it sums are not read).
+ *   flip        rounds as for collapse.  Edge (a, b), a < b, with the face that runs a -> b, (a, b, c), and the face
+ *               that runs b -> a, (b, a, d), becomes edge (c, d): the first face becomes (a, d, c), the second
+ *               (d, b, c).  tt_remesh_flip_select, one thread per edge.  Candidate: counts == 2 with the two faces in
+ *               opposite directions; a, b unlocked; c != d and d not in N(c); with val = deg and target = 6 (4 for a
+ *               locked vertex), the sum of |val - target| over a, b, c, d strictly falls for val a, val b - 1 and
+ *               val c, val d + 1; len2(c, d) <= hi2; each of (d - a) x (c - a), (b - d) x (c - d) has a positive dot
+ *               product with each of (b - a) x (c - a), (a - b) x (d - b) (fp64).  state (E) uint8: 0 no candidate, 1
+ *               candidate, 2 selected; cd (E,2) = (c, d), faces (E,2) = the two faces.  A candidate does a 64-bit
+ *               atomicMin of its key into owner[] of a, b, c, d (owner (V) uint64, set to all ones by the call) and is
+ *               selected iff it owns the four: selected flips share no vertex, so they share no face, cannot create
+ *               one edge twice and leave each other's checks valid.  tt_remesh_flip_apply rewrites the two faces of
+ *               every selected edge in place.
+ *   move        one Jacobi step.  tt_remesh_relax, one thread per vertex: movable = not locked, in a face and with a
+ *               neighbour; q = p + (g - p) - ((g - p) . n) n in fp64, rounded to fp32, with g the mean of the
+ *               neighbours (ascending) and n the normalised sum of (p1 - p0) x (p2 - p0) over its faces in ascending
+ *               face order (zero when the sum is); q = p for any other vertex.  q is sent to the closest point of the
+ *               INPUT mesh (tt_dist_query on a grid of the input built once per call); tt_remesh_place puts a movable
+ *               vertex at (b0 s0 + b1 s1) + b2 s2 of that face's corners in fp32 and leaves every other one.  The fold
+ *               guard: tt_remesh_fold_flag is one Jacobi step over the faces (positions: old where rev_in is set,
+ *               else new): a face whose old normal is not zero and whose new normal has a non-positive dot product
+ *               with it (fp64) sets rev_out of its three corners and adds one to count; rev_out starts as a copy of
+ *               rev_in.  The host repeats with the two arrays swapped until count == 0 (the reverted set only grows,
+ *               and with every vertex reverted no face fails); tt_remesh_revert puts the old position back.
+ *   output      tt_decimate_emit_count / tt_decimate_emit: the referenced vertices in ascending index, the faces in
+ *               order.  One more tt_dist_query gives every output vertex its closest input face and barycentrics.
+ * Guarantees: identical inputs give bit-identical outputs (no float atomics; the atomics are the integer min of the
+ * selections, the integer add of the guard's count and flag stores).  A closed 2-manifold input stays one with the same
+ * Euler characteristic and number of components; no operation flips a face; locked vertices of the input keep their
+ * position bit for bit; unless split_capped, no edge of the result has len2 > hi2; every vertex the last move left
+ * unreverted lies on the input surface (to the fp32 evaluation of its barycentrics).  NOT guaranteed: a lower bound on
+ * edge length (blocked collapses remain; the share of short edges is what tools report), sharp features, vertices of
+ * the closing split on the surface (they lie on chords), differentiability.
+ * TT_REMESH_MAX_ROUNDS / _SPLIT_PASSES bound a phase; every phase measured so far ended by exhaustion.  Measured maxima
+ * (profiles/mesh_remesh.json, the two 160^3 scenes, 84 k and 473 k faces): 151 collapse rounds (L = 4.6 x the mean edge;
+ * 47 at 1.9 x, 31 at 1.0 x), 10 flip rounds, 1 split pass; the numpy restatement on the meshes of
+ * tests/test_remesh_reference.py (1 000 to 3 000 faces): 25 rounds, 2 passes.  The rounds grow with L / mean edge.
+ * Use: per pass bytes = tt_remesh_workspace_bytes(T, E).  Every entry point validates its arguments before any HIP call
+ * (TT_ERR_BAD_ARG); V, T <= TT_MESH_MAX_ITEMS, 1 <= E <= 3 T, 1 <= M <= E, T <= Tn <= 4 T. */
+#define TT_REMESH_MAX_ROUNDS 1024
+#define TT_REMESH_MAX_SPLIT_PASSES 32
+#define TT_REMESH_DEFAULT_ITERATIONS 5
+int64_t tt_remesh_workspace_bytes(int32_t T, int32_t E);
+int tt_remesh_split_count(const float* v_pos, const int32_t* edges, const int32_t* face_edge, int32_t V, int32_t T,
+                          int32_t E, float hi2, void* workspace, int32_t* out_totals, void* stream);
+int tt_remesh_split_emit(const float* v_pos, const int32_t* t_pos_idx, const int32_t* edges, const int32_t* face_edge,
+                         int32_t V, int32_t T, int32_t E, int32_t M, int32_t Tn, void* workspace, float* v_new,
+                         int32_t* marked, int32_t* t_out, void* stream);
+int tt_remesh_collapse_candidates(const float* v_pos, const int32_t* t_pos_idx, const int32_t* edges,
+                                  const int32_t* nbr_ptr, const int32_t* nbr_col, const int32_t* vf_ptr,
+                                  const int32_t* vf_col, const uint8_t* locked, int32_t V, int32_t T, int32_t E,
+                                  float hi2, float lo2, int32_t* cost_bits, float* xopt, void* stream);
+int tt_remesh_flip_select(const float* v_pos, const int32_t* t_pos_idx, const int32_t* edges, const int32_t* edge_fe,
+                          const int32_t* nbr_ptr, const int32_t* nbr_col, const uint8_t* locked, int32_t V, int32_t T,
+                          int32_t E, float hi2, int32_t round, uint8_t* state, int32_t* cd, int32_t* faces,
+                          int64_t* owner, void* stream);
+int tt_remesh_flip_apply(const int32_t* edges, const int32_t* cd, const int32_t* faces, const uint8_t* state, int32_t V,
+                         int32_t T, int32_t E, int32_t* t_pos_idx, void* stream);
+int tt_remesh_relax(const float* v_pos, const int32_t* t_pos_idx, const int32_t* nbr_ptr, const int32_t* nbr_col,
+                    const int32_t* vf_ptr, const int32_t* vf_col, const uint8_t* locked, int32_t V, int32_t T, int32_t E,
+                    float* q, uint8_t* movable, void* stream);
+int tt_remesh_place(const float* v_old, const int32_t* face, const float* bary, const float* src_pos,
+                    const int32_t* src_tri, const uint8_t* movable, int32_t V, int32_t V0, int32_t T0, float* v_new,
+                    void* stream);
+int tt_remesh_fold_flag(const float* v_old, const float* v_new, const int32_t* t_pos_idx, const uint8_t* rev_in,
+                        int32_t V, int32_t T, uint8_t* rev_out, int32_t* count, void* stream);
+int tt_remesh_revert(const float* v_old, const uint8_t* rev, int32_t V, float* v_new, void* stream);
 
 /* ---- tangents and normal-map baking (tt_bake.hip): Mesh.v_tng (threestudio/models/mesh.py:162-205) and the
  * exporter's map_Bump ----

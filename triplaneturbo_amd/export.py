@@ -108,6 +108,11 @@ class MultipromptMeshExporter(Exporter):
         # to at most that many faces (manifold-preserving edge collapse); together with a simplify attribute it is a
         # ValueError at call time.
         self.decimate_target_faces: Optional[int] = None
+        # Mesh.remesh's arguments, attributes for the same reason: with one of them set the exported mesh is mesh[0]
+        # remeshed isotropically (at that edge length, or towards that many faces); both, or one together with a
+        # simplify attribute or decimate_target_faces, is a ValueError at call time.
+        self.remesh_edge_length: Optional[float] = None
+        self.remesh_target_faces: Optional[int] = None
         # the tangent-space normal map of the exported mesh (map_Bump, ops.bake_normal_map) on the obj-mtl path with
         # save_texture, and the number of projection steps it takes towards the iso-surface; attributes for the same
         # reason.  Unset, params are exactly what they are without the bake.
@@ -132,6 +137,13 @@ class MultipromptMeshExporter(Exporter):
         if self.decimate_target_faces is not None and any(v is not None for v in simplify.values()):
             raise ValueError("multiprompt-mesh-exporter: decimate_target_faces cannot be combined with a simplify_* "
                              "attribute")
+        remesh = {"edge_length": self.remesh_edge_length, "target_faces": self.remesh_target_faces}
+        if all(v is not None for v in remesh.values()):
+            raise ValueError("multiprompt-mesh-exporter: set at most one of remesh_edge_length and remesh_target_faces")
+        if any(v is not None for v in remesh.values()) and (
+                self.decimate_target_faces is not None or any(v is not None for v in simplify.values())):
+            raise ValueError("multiprompt-mesh-exporter: remesh_edge_length / remesh_target_faces cannot be combined "
+                             "with a simplify_* attribute or decimate_target_faces")
         isosurface = getattr(self.geometry, "isosurface", None)
         if isosurface is None:
             raise RuntimeError("geometry.isosurface is not set: configure a generative-space-mesh-rasterize-renderer "
@@ -143,6 +155,8 @@ class MultipromptMeshExporter(Exporter):
             mesh = mesh.simplify(**simplify)
         if self.decimate_target_faces is not None:
             mesh = mesh.decimate(self.decimate_target_faces)
+        if any(v is not None for v in remesh.values()):
+            mesh = mesh.remesh(**remesh)
         # the texture belongs to mesh[0]: decode it from the first prompt's slice of the space cache
         space_cache = prompt_slice(space_cache, 0)
         if self.cfg.fmt == "obj-mtl":

@@ -387,6 +387,43 @@ class Mesh:
         mesh.extras["decimate"] = info
         return mesh
 
+    def remesh(self, edge_length: Optional[float] = None, target_faces: Optional[int] = None,
+               iterations: Optional[int] = None) -> Mesh:
+        """A copy with near-equilateral triangles of one size on this mesh's surface: isotropic remeshing (split the
+        long edges, collapse the short ones, flip towards valence 6, relax tangentially and pull back onto this
+        surface; ops.mesh_remesh; include/tt_abi.h "isotropic remeshing").  Exactly one of `edge_length` (the target
+        edge length L) and `target_faces` must be given; target_faces sets L = sqrt(4 A / (sqrt(3) target_faces)) with
+        A this mesh's area, the edge at which equilateral triangles cover A with that many faces -- the face count of
+        the result FOLLOWS this estimate, it is not exact.  `iterations` defaults to TT_REMESH_DEFAULT_ITERATIONS.  A
+        closed 2-manifold stays one, with the same genus and number of components, no face flips, vertices on a
+        boundary or a non-manifold edge stay where they are, and no edge of the result is longer than 4/3 L (unless
+        extras["remesh"]["split_capped"]).  Short edges whose collapse is blocked remain, sharp features are not
+        preserved, nothing is differentiable.  A new Mesh that inherits extras, with extras["remesh"] =
+        ops.mesh_remesh's info; vertex colours, when this mesh carries them, are interpolated at the closest point of
+        this mesh to every new vertex (source_face / source_bary).  A mesh that is empty or that nothing changes comes
+        back with its own tensors.  The result never requires grad."""
+        if (edge_length is None) == (target_faces is None):
+            raise ValueError("remesh: give exactly one of edge_length and target_faces")
+        if target_faces is not None:
+            if isinstance(target_faces, bool) or not isinstance(target_faces, int) or target_faces < 1:
+                raise ValueError(f"target_faces must be a positive int, got {target_faces!r}")
+            p = self.v_pos.detach()[self.t_pos_idx.long()]
+            area = 0.5 * float(torch.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0], dim=-1).norm(dim=-1).double().sum())
+            if not area > 0.0:
+                raise ValueError("remesh(target_faces=): the mesh has no area; give edge_length")
+            edge_length = ops.remesh_edge_length(area, target_faces)
+        v_pos, t_pos_idx, info = ops.mesh_remesh(self.v_pos, self.t_pos_idx, edge_length, iterations)
+        mesh = Mesh(v_pos, t_pos_idx)
+        mesh.extras = dict(self.extras)
+        mesh.extras["remesh"] = info
+        if self._v_rgb is not None:
+            if info["unchanged"]:
+                mesh._v_rgb = self._v_rgb
+            else:
+                corners = self._v_rgb.detach()[self.t_pos_idx.long()[info["source_face"].long()]]  # (V',3,C)
+                mesh._v_rgb = (info["source_bary"].to(corners.dtype)[:, :, None] * corners).sum(1)
+        return mesh
+
     def _compute_vertex_normal(self) -> Tensor:
         i0, i1, i2 = (self.t_pos_idx[:, c].long() for c in range(3))
         v0, v1, v2 = self.v_pos[i0, :], self.v_pos[i1, :], self.v_pos[i2, :]

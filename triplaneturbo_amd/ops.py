@@ -1556,6 +1556,248 @@ def mesh_decimate(v_pos: Tensor, t_pos_idx: Tensor, target_faces: int, max_round
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# isotropic remeshing (include/tt_abi.h, "isotropic remeshing"): split, collapse, flip, relax on the input's surface
+def remesh_thresholds(edge_length: float) -> Tuple[float, float]:
+    """(hi2, lo2) of the contract: the fp32 squares of (float)(4/3 L) and (float)(4/5 L)."""
+    h, l = np.float32((4.0 / 3.0) * edge_length), np.float32(0.8 * edge_length)
+    return float(np.float32(h * h)), float(np.float32(l * l))
+
+
+def remesh_edge_length(area: float, target_faces: int) -> float:
+    """The edge length at which equilateral triangles cover `area` with target_faces faces: sqrt(4 A / (sqrt 3 N))."""
+    return float(np.sqrt(4.0 * area / (np.sqrt(3.0) * target_faces)))
+
+
+class _RemeshTopology:
+    """The topology of one pass or round of ops.mesh_remesh (host plumbing, as ops.mesh_decimate's): the unique edges
+    with their counts from one face-edge sort; on demand the neighbour CSR and the locked vertices (`nbr`), the
+    vertex -> face CSR (`vf`), the unique edge of every face edge (`face_edge`) and the two face edges of every
+    two-face edge (`edge_fe`)."""
+
+    def __init__(self, tri: Tensor, V: int, nbr: bool = False, vf: bool = False, face_edge: bool = False,
+                 edge_fe: bool = False):
+        with _timed("remesh_topology"):
+            fe = sort_face_edges(tri, V)
+            e0, e1 = fe.uniq // fe.base, fe.uniq % fe.base
+            self.E = int(e0.shape[0])
+            self.edges = torch.stack([e0, e1], dim=1).int().contiguous()
+            self.counts = fe.counts.int().contiguous()
+            if nbr:
+                self.nbr_ptr, self.nbr_col = _csr(torch.cat([e0, e1]), torch.cat([e1, e0]), V, V)
+            if vf:
+                self.vf_ptr, self.vf_col = _csr(tri.reshape(-1).long(), None, V, 3 * tri.shape[0])
+            if face_edge:
+                self.face_edge = torch.empty(fe.perm.shape[0], device=tri.device, dtype=torch.int32)
+                self.face_edge[fe.perm] = fe.inverse.int()
+            if edge_fe:
+                self.edge_fe = torch.full((self.E, 2), -1, device=tri.device, dtype=torch.int32)
+                two = fe.counts == 2
+                first = fe.starts[two]
+                self.edge_fe[two] = torch.stack([fe.perm[first], fe.perm[first + 1]], dim=1).int()
+        if nbr:
+            self.locked = torch.empty(V, device=tri.device, dtype=torch.uint8)
+            _launch("tt_decimate_lock", self.edges, self.counts, V, self.E, self.locked, label="remesh_lock")
+
+
+@torch.no_grad()
+def mesh_remesh(v_pos: Tensor, t_pos_idx: Tensor, edge_length: float, iterations: Optional[int] = None,
+                return_trace: bool = False) -> Tuple[Tensor, Tensor, dict]:
+    """Isotropic remeshing towards edge length `edge_length` on the surface of the input mesh (tt_remesh_*; Botsch and
+    Kobbelt): `iterations` (default TT_REMESH_DEFAULT_ITERATIONS) times split the edges longer than 4/3 L, collapse the
+    edges shorter than 4/5 L to their midpoint, flip edges towards valence 6 and move every vertex tangentially and
+    back onto the input surface (ops.mesh_closest_point on a TriangleGrid of the input); then one more split.
+    Collapses and flips run in rounds of operations with disjoint neighbourhoods, chosen by hashed integer priorities
+    (per round one face-edge sort, the CSR sorts and one read-back).  Vertices on a boundary or a non-manifold edge are
+    locked: they never move or merge.  A closed 2-manifold stays one with the same Euler characteristic and
+    components, no operation flips a face, and unless info["split_capped"] no edge of the result is longer than
+    4/3 L.  NOT guaranteed: a lower bound on edge length (blocked collapses remain), sharp features, and the vertices
+    of the closing split lie on chords of the surface, not on it.  Nothing is differentiable.
+
+    Returns v_pos' (V',3) fp32, t_pos_idx' (T',3) int32 and info = {edge_length, iterations, n_split, n_collapsed,
+    n_flipped, n_reverted (lists: one entry per iteration, n_split one more for the closing split), n_locked (locked
+    vertices of the input), split_capped, rounds_capped (a phase ended at TT_REMESH_MAX_SPLIT_PASSES /
+    TT_REMESH_MAX_ROUNDS), rounds (one dict {collapse, flip} per iteration) and split_passes (one count per split phase):
+    the rounds and passes that changed something, source_face (V',) int32 and source_bary
+    (V',3) fp32: the closest point of the input mesh to every output vertex, unchanged}; with return_trace
+    info["trace"] holds the ordered records ("split", edges (k,2) int32), ("collapse", edges (k,2) int32, xopt (k,3)
+    fp32), ("flip", edges (k,2) int32, cd (k,2) int32) and ("move", positions (V,3) fp32, reverted (V,) uint8).  An
+    empty mesh, or one that no operation changes, comes back as it is (unchanged = True).  Bit-identical from call to
+    call.  Positions are detached; the result never requires grad."""
+    if iterations is None:
+        iterations = _lib.TT_REMESH_DEFAULT_ITERATIONS
+    if isinstance(iterations, bool) or not isinstance(iterations, int):
+        raise TypeError(f"iterations must be an int, got {type(iterations).__name__}")
+    if iterations < 0:
+        raise ValueError(f"iterations must not be negative, got {iterations}")
+    if isinstance(edge_length, bool) or not isinstance(edge_length, (int, float)):
+        raise TypeError(f"edge_length must be a number, got {type(edge_length).__name__}")
+    edge_length = float(edge_length)
+    hi2, lo2 = remesh_thresholds(edge_length) if np.isfinite(edge_length) else (0.0, 0.0)
+    if not (edge_length > 0.0 and 0.0 < lo2 and hi2 < float("inf")):
+        raise ValueError(f"edge_length must be finite and positive (its square in fp32 too), got {edge_length!r}")
+    info = {"edge_length": edge_length, "iterations": iterations, "n_split": [], "n_collapsed": [], "n_flipped": [],
+            "n_reverted": [], "n_locked": 0, "split_capped": False, "rounds_capped": False, "rounds": [],
+            "split_passes": [], "unchanged": True}
+    trace: list = []  # filled with return_trace only
+
+    def record(*rec) -> None:
+        if return_trace:
+            trace.append(rec)
+
+    if return_trace:
+        info["trace"] = trace
+    if (isinstance(v_pos, Tensor) and isinstance(t_pos_idx, Tensor) and v_pos.shape[1:] == t_pos_idx.shape[1:] == (3,)
+            and t_pos_idx.dtype in (torch.int32, torch.int64) and 0 in (v_pos.shape[0], t_pos_idx.shape[0])):
+        n = v_pos.shape[0]  # an empty mesh
+        info["source_face"] = torch.full((n,), -1, device=v_pos.device, dtype=torch.int32)
+        info["source_bary"] = torch.zeros((n, 3), device=v_pos.device, dtype=torch.float32)
+        return v_pos.detach(), t_pos_idx, info
+    v_pos = _chk(v_pos, "v_pos", (None, 3)).detach()
+    t_pos_idx = _chk_index(t_pos_idx, "t_pos_idx", 3)
+    dev = v_pos.device
+    _chk_size("mesh too large for tt_remesh_*", V=v_pos.shape[0], T=t_pos_idx.shape[0])
+    chk = torch.cat([torch.isfinite(v_pos).all().reshape(1).long(), _minmax(t_pos_idx).long()]).tolist()  # one read-back
+    _chk_range("t_pos_idx", chk[1], chk[2], v_pos.shape[0])
+    if not chk[0]:
+        raise ValueError("v_pos holds a value that is not finite")
+    i32 = dict(device=dev, dtype=torch.int32)
+    u8 = dict(device=dev, dtype=torch.uint8)
+    f32 = dict(device=dev, dtype=torch.float32)
+    pos, tri = v_pos.clone(), t_pos_idx.int().contiguous().clone()
+    tg = TriangleGrid(v_pos, tri)  # the input surface: every move is pulled back onto it
+    totals, count = torch.empty(2, **i32), torch.empty(1, **i32)
+    tau = torch.zeros(1, device=dev, dtype=torch.int64)  # tt_decimate_mark's threshold: every candidate is eligible
+    info["n_locked"] = int(_RemeshTopology(tri, pos.shape[0], nbr=True).locked.sum().item())
+
+    def split_phase() -> None:
+        nonlocal pos, tri
+        n = 0
+        for p in range(_lib.TT_REMESH_MAX_SPLIT_PASSES + 1):
+            V, T = pos.shape[0], tri.shape[0]
+            tp = _RemeshTopology(tri, V, face_edge=True)
+            ws = _workspace("tt_remesh_workspace_bytes", T, tp.E, device=dev)
+            _launch("tt_remesh_split_count", pos, tp.edges, tp.face_edge, V, T, tp.E, hi2, ws, totals,
+                    label="remesh_split_count")
+            M, Tn = totals.tolist()  # the pass's read-back
+            if M == 0:
+                break
+            if p == _lib.TT_REMESH_MAX_SPLIT_PASSES:
+                info["split_capped"] = True
+                break
+            _chk_size("mesh too large for tt_remesh_* after a split pass: use a larger edge_length", V=V + M, T=Tn)
+            v_new, marked = torch.empty((M, 3), **f32), torch.empty((M, 2), **i32)
+            t_out = torch.empty((Tn, 3), **i32)
+            _launch("tt_remesh_split_emit", pos, tri, tp.edges, tp.face_edge, V, T, tp.E, M, Tn, ws, v_new, marked,
+                    t_out, label="remesh_split_emit")
+            pos, tri = torch.cat([pos, v_new]), t_out
+            record("split", marked)
+            n += M
+        info["n_split"].append(n)
+        info["split_passes"].append(p)
+
+    def collapse_phase() -> int:
+        nonlocal tri
+        V, n = pos.shape[0], 0
+        taken, owner = torch.empty(V, **u8), torch.empty(V, device=dev, dtype=torch.int64)
+        quadrics = torch.zeros((V, 10), device=dev, dtype=torch.float64)  # tt_decimate_apply sums them; never read here
+        remap, root = torch.arange(V, **i32), torch.arange(V, **i32)
+        for rnd in range(_lib.TT_REMESH_MAX_ROUNDS + 1):
+            T = tri.shape[0]
+            tp = _RemeshTopology(tri, V, nbr=True, vf=True)
+            E = tp.E
+            cost_bits, xopt, state = torch.empty(E, **i32), torch.empty((E, 3), **f32), torch.empty(E, **u8)
+            _launch("tt_remesh_collapse_candidates", pos, tri, tp.edges, tp.nbr_ptr, tp.nbr_col, tp.vf_ptr, tp.vf_col,
+                    tp.locked, V, T, E, hi2, lo2, cost_bits, xopt, label="remesh_collapse_candidates")
+            taken.zero_()
+            owner.fill_(-1)
+            _launch("tt_decimate_mark", tp.edges, tp.nbr_ptr, tp.nbr_col, cost_bits, tau, V, T, E, rnd, 0, state, taken,
+                    owner, label="remesh_collapse_mark")
+            _launch("tt_decimate_select", tp.edges, tp.nbr_ptr, tp.nbr_col, V, T, E, rnd, state, taken, owner,
+                    label="remesh_collapse_select")
+            kept = (state == 2).nonzero().reshape(-1)  # ascending edge index; the round's read-back
+            K = int(kept.shape[0])
+            if K == 0:
+                return rnd
+            if rnd == _lib.TT_REMESH_MAX_ROUNDS:
+                info["rounds_capped"] = True
+                return rnd
+            k_edges, k_xopt = tp.edges[kept].contiguous(), xopt[kept].contiguous()
+            ws = _workspace("tt_decimate_workspace_bytes", V, T, device=dev)
+            out = torch.empty((T, 3), **i32)
+            _launch("tt_decimate_apply", k_edges, k_xopt, tri, V, T, K, ws, pos, quadrics, remap, root, out, totals,
+                    label="remesh_collapse_apply")
+            tri = out[:int(totals[1].item())]
+            record("collapse", k_edges, k_xopt)
+            info["n_collapsed"][-1] += K
+        raise AssertionError("unreachable")
+
+    def flip_phase() -> int:
+        V, T = pos.shape[0], tri.shape[0]
+        owner = torch.empty(V, device=dev, dtype=torch.int64)
+        for rnd in range(_lib.TT_REMESH_MAX_ROUNDS + 1):
+            tp = _RemeshTopology(tri, V, nbr=True, edge_fe=True)
+            E = tp.E
+            state, cd, faces = torch.empty(E, **u8), torch.empty((E, 2), **i32), torch.empty((E, 2), **i32)
+            _launch("tt_remesh_flip_select", pos, tri, tp.edges, tp.edge_fe, tp.nbr_ptr, tp.nbr_col, tp.locked, V, T, E,
+                    hi2, rnd, state, cd, faces, owner, label="remesh_flip_select")
+            kept = (state == 2).nonzero().reshape(-1)  # the round's read-back
+            K = int(kept.shape[0])
+            if K == 0:
+                return rnd
+            if rnd == _lib.TT_REMESH_MAX_ROUNDS:
+                info["rounds_capped"] = True
+                return rnd
+            _launch("tt_remesh_flip_apply", tp.edges, cd, faces, state, V, T, E, tri, label="remesh_flip_apply")
+            record("flip", tp.edges[kept].contiguous(), cd[kept].contiguous())
+            info["n_flipped"][-1] += K
+        raise AssertionError("unreachable")
+
+    def move_phase() -> None:
+        nonlocal pos
+        V, T = pos.shape[0], tri.shape[0]
+        tp = _RemeshTopology(tri, V, nbr=True, vf=True)
+        q, movable, new = torch.empty((V, 3), **f32), torch.empty(V, **u8), torch.empty((V, 3), **f32)
+        _launch("tt_remesh_relax", pos, tri, tp.nbr_ptr, tp.nbr_col, tp.vf_ptr, tp.vf_col, tp.locked, V, T, tp.E, q,
+                movable, label="remesh_relax")
+        _, face, bary = mesh_closest_point(q, tg)
+        _launch("tt_remesh_place", pos, face, bary, tg.v_pos, tg.t_pos_idx, movable, V, tg.v_pos.shape[0], tg.n_faces,
+                new, label="remesh_place")
+        rev, cur = [torch.zeros(V, **u8), torch.empty(V, **u8)], 0
+        while True:  # the reverted set only grows: at most V steps, in practice one or two
+            _launch("tt_remesh_fold_flag", pos, new, tri, rev[cur], V, T, rev[1 - cur], count, label="remesh_fold_flag")
+            if int(count.item()) == 0:
+                break
+            cur = 1 - cur
+        _launch("tt_remesh_revert", pos, rev[cur], V, new, label="remesh_revert")
+        info["n_reverted"].append(int(rev[cur].sum().item()))
+        pos = new
+        if return_trace:  # a copy: the next collapse round writes into pos
+            record("move", new.clone(), rev[cur])
+
+    for _ in range(iterations):
+        split_phase()
+        info["n_collapsed"].append(0)
+        info["n_flipped"].append(0)
+        info["rounds"].append({"collapse": collapse_phase(), "flip": flip_phase()})
+        move_phase()
+    split_phase()
+    changed = sum(info["n_split"]) + sum(info["n_collapsed"]) + sum(info["n_flipped"]) > 0
+    if not changed and bool(torch.equal(pos, v_pos)):
+        v_out, t_out = v_pos, t_pos_idx
+    else:
+        V, T = pos.shape[0], tri.shape[0]
+        ws = _workspace("tt_decimate_workspace_bytes", V, T, device=dev)
+        _launch("tt_decimate_emit_count", tri, V, T, ws, totals, label="remesh_emit_count")
+        v_out = torch.empty((int(totals[0].item()), 3), **f32)
+        t_out = torch.empty((T, 3), **i32)
+        _launch("tt_decimate_emit", pos, tri, torch.arange(V, **i32), V, T, ws, v_out, t_out, torch.empty(V, **i32),
+                label="remesh_emit")
+        info["unchanged"] = False
+    _, info["source_face"], info["source_bary"] = mesh_closest_point(v_out, tg)
+    return v_out, t_out, info
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # point-to-mesh distance (include/tt_abi.h, "point-to-mesh distance"): closest point on a triangle mesh, surface samples
 def dist_default_grid(n_faces: int) -> int:
     """The grid a TriangleGrid takes when the caller names none: clamp(ceil(sqrt(T) / 8), 1, TT_DIST_MAX_GRID), about two (cell, triangle) pairs
