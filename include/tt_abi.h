@@ -66,6 +66,8 @@
  *   tt_uv_* / tt_tex_fill   the mesh exporter's xatlas UV unwrap (threestudio/models/mesh.py:207-249) and cv2.inpaint
  *                           texture padding (multiprompt_mesh_exporter.py:96-107): axis-projection charts, shelf
  *                           packing, an overlap guard, nearest-texel fill.
+ *   tt_uv_lscm_*            the opt-in conformal flattening of those charts (least-squares conformal maps, an fp64
+ *                           conjugate-gradient solve per chart); xatlas's own charts are not reproduced.
  *   tt_tex_fwd / _bwd       nvdiffrast's 2-D `texture` without mipmaps (CUDA-only, un-vendored): sampling map_Kd at
  *                           interpolated UVs, the step the reference's export render (evaluation/mesh_visualize.py)
  *                           leaves to external tools.
@@ -858,6 +860,79 @@ int tt_uv_overlap(const float* v_tex, const int32_t* t_tex_idx, int32_t Vt, int3
 int64_t tt_tex_fill_workspace_bytes(int32_t H, int32_t W);
 int tt_tex_fill(const float* img, const uint8_t* mask, int32_t H, int32_t W, int32_t C, void* workspace, float* out,
                 void* stream);
+
+/* ---- conformal UV charts (tt_uv_lscm.hip; tt_uv_lscm_index in tt_uv.hip): least-squares conformal maps (Levy et al.
+ * 2002, "Least squares conformal maps for automatic texture atlas generation") of the charts above ----
+ * The opt-in second flattening of the atlas (ops.uv_atlas(method="lscm")): labels, charts, packing, the overlap guard
+ * and the fill are the ones above; only the map of a chart's vertices into its box changes.  A chart is the set of
+ * faces with one id in chart (T) int32; every solver number is fp64.
+ *   unknowns    one UV vertex per distinct (chart, vertex) pair, tt_uv_emit's numbering: tt_uv_lscm_index writes
+ *               t_tex_idx (T,3) from the workspace tt_uv_emit_count has just left (Vt = its out_totals[0]).
+ *   tables      the solver works on the UV vertices in CHART ORDER: sorted by chart, then by UV-vertex id (a stable
+ *               sort, the caller's), position i.  `tables` is ONE int32 array of tt_uv_lscm_table_ints(T, Vt, C, NT)
+ *               ints: fc [3T] position of corner 3f + k | ccol [3T] the corners of every position, each row ascending
+ *               | vmesh [Vt] mesh vertex of position i | vchart [Vt] its chart | vperm [Vt] its UV-vertex id | cptr
+ *               [Vt+1] rows of ccol | vptr [C+1] positions of chart c | tptr [C+1] tiles of chart c | tchart [NT] chart
+ *               of tile t | tbegin [NT] its first position.  A chart of n vertices has ceil(n / TT_UV_LSCM_TILE) tiles,
+ *               in order.  Every entry is clamped into range before it is used as an index.
+ *   energy      per face f with n = (p1 - p0) x (p2 - p0), |n|^2 as in "labels" above: local frame x along p1 - p0, y =
+ *               n x x, so p0 = (0,0), p1 = (x1,0), p2 = (x2,y2), x1 = |p1 - p0|, x2 = (p2 - p0).(p1 - p0) / x1, y2 = |n|
+ *               / x1 > 0, A_f = |n| / 2, all in double from the fp32 positions.  With W_k = (y_{k+1} - y_{k+2}, x_{k+2}
+ *               - x_{k+1}), grad u = (1 / 2 A_f) sum_k u_k W_k, and E = sum_f A_f |grad v - J grad u|^2, J = rotation
+ *               by +90 degrees in that frame: the minimiser keeps orientation.  A face with |n|^2 = 0 has no term.
+ *   pins        p0 = the chart's UV vertex farthest from the middle 0.5 (min + max) of the chart's 3-D box, squared
+ *               distance (dx^2 + dy^2) + dz^2 in double, no fused operations; on a tie the smallest UV-vertex id.  p1 =
+ *               the one farthest from p0, same rule.  Pinned at (0, 0) and (|p1 - p0|, 0).  A chart whose vertices all
+ *               coincide has no pins: it fails.
+ *   solve       the normal equations M^T M x = -M^T M x_pin of E on the free entries, conjugate gradients with the
+ *               Jacobi preconditioner, x_0 = 0, all charts in lock step with their own alpha, beta and residual
+ *               (alpha = r.z / p.Ap, or 0 when p.Ap <= 0; beta likewise).  An entry whose diagonal is 0 (only zero-area
+ *               faces use the vertex) stays 0.  After each iteration a chart with |r|^2 <= tol^2 |b|^2 is converged
+ *               and changes no more; without an iteration nothing is converged.  tt_uv_lscm_iterate runs n_iters
+ *               iterations (at most TT_UV_LSCM_MAX_BATCH) and leaves the number of charts still iterating in
+ *               out_totals[0] (DEVICE): the caller reads it back every TT_UV_LSCM_CHECK_EVERY iterations, never per
+ *               iteration.  M is applied matrix-free: a face pass writes the three corner terms, a vertex gather sums
+ *               them in ascending corner order.  Per-chart sums: a wave per tile (4 positions per lane ascending, then
+ *               a fixed shuffle tree), then a wave per chart over its tiles, the same way.  No float atomics.
+ *   normalise   k = sqrt(sum A_f / sum UV area) over the chart's faces with A_f > 0; the chart fails unless both
+ *               sums and k^2 are positive and finite.
+ *   orient      theta = atan2(2 s_uv, s_uu - s_vv) / 2 from the sums of squares of the chart's UV vertices about their
+ *               mean (atan2(0, 0) = 0: no rotation on a tie); final (u, v) = k R(-theta) (u, v), rounded to fp32.
+ *               rotation = -theta, scale = k.  The chart's box is the min / max of the fp32 values.
+ *   accept      a chart keeps its map iff it converged, did not fail above, and every face with A_f > 0 has UV area
+ *               > 0 and k^2 UV area / A_f in [tau, 1 / tau] (double; tau the (double) of the float): the projection's
+ *               own worst case.  Every other chart falls back: fallback = 1, box = its chart_box row of tt_uv_charts
+ *               (zeros when chart_box is NULL), rotation 0, scale 1.
+ *   emit        tt_uv_lscm_emit: tt_uv_emit's fp32 formula on (u, v) = the final coordinates, or, for a fallback chart,
+ *               the projection of its label: with every chart fallen back, v_tex is bit-identical to tt_uv_emit's.
+ *   outputs     tt_uv_lscm_finish: uv (Vt,2) fp64 the raw solution (before normalise / orient; the partial iterate of a
+ *               chart that did not converge), uv_final (Vt,2) fp32 (0 for fallback charts), box_out (C,4), fallback (C)
+ *               uint8, pins (C,2) int32 UV-vertex ids, iterations (C) int32, residual (C) |r| / |b| (0 when b = 0, 1
+ *               before the first iteration), rotation, scale (C) fp64.
+ * Determinism: integer atomics (boxes, pins, flags) and fixed-order sums only: bit-identical from launch to launch.
+ * Use: tt_uv_emit_count; tt_uv_lscm_index; the caller's tables; tt_uv_lscm_setup; tt_uv_lscm_iterate until 0 charts
+ * iterate or the caller's limit; tt_uv_lscm_finish; tt_uv_pack on box_out; tt_uv_lscm_emit.  One workspace of
+ * tt_uv_lscm_workspace_bytes(T, Vt, C, NT) for setup .. finish.  C <= Vt, C <= NT <= Vt, Vt <= 3T. */
+#define TT_UV_LSCM_TILE 256
+#define TT_UV_LSCM_CHECK_EVERY 32
+#define TT_UV_LSCM_MAX_BATCH 4096
+#define TT_UV_LSCM_DEFAULT_TOL 1e-8
+#define TT_UV_LSCM_DEFAULT_MAX_ITERS 20000
+int64_t tt_uv_lscm_workspace_bytes(int32_t T, int32_t Vt, int32_t C, int32_t NT);
+int64_t tt_uv_lscm_table_ints(int32_t T, int32_t Vt, int32_t C, int32_t NT);
+int tt_uv_lscm_index(int32_t V, int32_t T, int32_t N, void* workspace, int32_t* t_tex_idx, void* stream);
+int tt_uv_lscm_setup(const float* v_pos, const int32_t* tables, int32_t V, int32_t T, int32_t Vt, int32_t C, int32_t NT,
+                     void* workspace, void* stream);
+int tt_uv_lscm_iterate(const int32_t* tables, int32_t T, int32_t Vt, int32_t C, int32_t NT, int32_t n_iters, double tol,
+                       void* workspace, int32_t* out_totals, void* stream);
+int tt_uv_lscm_finish(const int32_t* tables, const float* chart_box, int32_t T, int32_t Vt, int32_t C, int32_t NT,
+                      float tau, void* workspace, double* uv, float* uv_final, float* box_out, uint8_t* fallback,
+                      int32_t* pins, int32_t* iterations, double* residual, double* rotation, double* scale,
+                      void* stream);
+int tt_uv_lscm_emit(const float* v_pos, const int32_t* t_pos_idx, const int32_t* labels, const int32_t* chart,
+                    const int32_t* t_tex_idx, const float* uv_final, const uint8_t* fallback, const float* chart_box,
+                    const int32_t* offsets, int32_t C, float scale, int32_t V, int32_t T, int32_t Vt, int32_t N,
+                    int32_t padding, float* v_tex, void* stream);
 
 /* ---- mesh simplification (tt_simplify.hip): vertex clustering with quadric-error placement ----
  * Lindstrom 2000 ("Out-of-core simplification of large polygonal models") with the quadrics of Garland & Heckbert

@@ -24,7 +24,7 @@ LIB_PATH = os.path.join(_HERE, "libtt_hip.so")
 # environment variables (profiling ablations and tuning sweeps, tools/).  The product library above never calls getenv.
 _DEFAULT_LIB_PATH = LIB_PATH
 TUNING_LIB_PATH = os.path.join(_HERE, "libtt_hip_tuning.so")
-SOURCES = ["tt_forward.hip", "tt_march.hip", "tt_backward.hip", "tt_backward_tex.hip", "tt_points.hip", "tt_composite.hip", "tt_grad2.hip", "tt_sampler.hip", "tt_hashgrid.hip", "tt_isosurface.hip", "tt_tets.hip", "tt_raster.hip", "tt_texture.hip", "tt_mesh.hip", "tt_uv.hip", "tt_simplify.hip", "tt_decimate.hip", "tt_remesh.hip", "tt_bake.hip", "tt_dist.hip", "tt_wind.hip", "tt_ray.hip", "tt_host.cpp"]
+SOURCES = ["tt_forward.hip", "tt_march.hip", "tt_backward.hip", "tt_backward_tex.hip", "tt_points.hip", "tt_composite.hip", "tt_grad2.hip", "tt_sampler.hip", "tt_hashgrid.hip", "tt_isosurface.hip", "tt_tets.hip", "tt_raster.hip", "tt_texture.hip", "tt_mesh.hip", "tt_uv.hip", "tt_uv_lscm.hip", "tt_simplify.hip", "tt_decimate.hip", "tt_remesh.hip", "tt_bake.hip", "tt_dist.hip", "tt_wind.hip", "tt_ray.hip", "tt_host.cpp"]
 # per-translation-unit flags: the texture backward is faster under hipcc's max-ILP scheduling strategy (3.11 -> 3.02 ms;
 # the other kernels are not); the geometry backward is faster with its transient MFMA results in VGPRs rather than AGPRs
 # (-amdgpu-mfma-vgpr-form: 471 -> 248 v_accvgpr_read, 3.045 -> 2.995 ms; texture backward slower, forward neutral) and

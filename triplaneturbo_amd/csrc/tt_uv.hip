@@ -548,6 +548,21 @@ extern "C" int tt_uv_emit(const float* v_pos, const int32_t* t_pos_idx, const in
     return tt_check_launch();
 }
 
+// t_tex_idx alone, from the workspace tt_uv_emit_count left: what the conformal flattening (tt_uv_lscm.hip) starts from
+__global__ __launch_bounds__(UV_BLOCK) void k_uv_index(int T, UvWs w, int* __restrict__ t_tex_idx) {
+    const int q = blockIdx.x * UV_BLOCK + threadIdx.x;
+    if (q < 3 * T) t_tex_idx[q] = w.uvid[w.rep[q]];
+}
+
+extern "C" int tt_uv_lscm_index(int32_t V, int32_t T, int32_t N, void* workspace, int32_t* t_tex_idx, void* stream) {
+    if (!uv_sizes_ok(V, T, N) || !workspace || (T > 0 && !t_tex_idx)) return TT_ERR_BAD_ARG;
+    if (T == 0) return 0;
+    const UvWs w = uv_ws(workspace, V, T, N);
+    hipLaunchKernelGGL(k_uv_index, dim3(tt_grid(3ll * T)), dim3(UV_BLOCK), 0, (hipStream_t)stream, (int)T, w,
+                       (int*)t_tex_idx);
+    return tt_check_launch();
+}
+
 extern "C" int tt_uv_overlap(const float* v_tex, const int32_t* t_tex_idx, int32_t Vt, int32_t V, int32_t T,
                              int32_t N, void* workspace, uint8_t* flags, int32_t* out_totals, void* stream) {
     if (!uv_sizes_ok(V, T, N) || Vt < 0 || (int64_t)Vt > 3 * (int64_t)T || !workspace || !out_totals)

@@ -116,6 +116,9 @@ class MultipromptMeshExporter(Exporter):
         # the tangent-space normal map of the exported mesh (map_Bump, ops.bake_normal_map) on the obj-mtl path with
         # save_texture, and the number of projection steps it takes towards the iso-surface; attributes for the same
         # reason.  Unset, params are exactly what they are without the bake.
+        # the flattening of the atlas' charts (Mesh.unwrap_uv's `method`: "axis", or "lscm" for conformal charts); an
+        # attribute for the same reason.  None means "axis": unset, the export is what it is without the attribute.
+        self.uv_method: Optional[str] = None
         self.bake_normal_map: bool = False
         self.bake_project_steps: int = 2
         self.bake_info: Optional[Dict[str, Any]] = None  # ops.bake_normal_map's info of the last bake
@@ -172,7 +175,8 @@ class MultipromptMeshExporter(Exporter):
                 "map_Pr": None, "map_format": self.cfg.texture_format}
 
     def _unwrap(self, mesh) -> None:
-        mesh.unwrap_uv(self.cfg.xatlas_chart_options, self.cfg.xatlas_pack_options, texture_size=self.cfg.texture_size)
+        mesh.unwrap_uv(self.cfg.xatlas_chart_options, self.cfg.xatlas_pack_options, texture_size=self.cfg.texture_size,
+                       method=self.uv_method)
 
     def _bake_max_step(self, mesh) -> float:
         """The longest projection step: the cell of a simplified mesh, else one cell of the isosurface grid."""

@@ -138,11 +138,13 @@ class Mesh:
         return self._v_tng_tex
 
     def _unwrap_uv(self, xatlas_chart_options: Optional[dict] = None, xatlas_pack_options: Optional[dict] = None,
-                   texture_size: Optional[int] = None) -> Tuple[Tensor, Tensor]:
+                   texture_size: Optional[int] = None, method: Optional[str] = "axis") -> Tuple[Tensor, Tensor]:
         """mesh.py:207-242 on the HIP axis-projection atlas (ops.uv_atlas, include/tt_abi.h "UV atlas and texture
         fill").  Of xatlas's options only PackOptions.padding (texels around every chart, default 2 as the exporter's
         inpaint radius) and PackOptions.resolution (the atlas size; else texture_size, else 1024) mean something here;
-        any other option raises NotImplementedError naming it."""
+        any other option raises NotImplementedError naming it.  `method`: "axis" (None means the same), or "lscm" for
+        conformal maps of the same charts (include/tt_abi.h, "conformal UV charts")."""
+        method = ops.uv_method(method)
         chart_opts, pack_opts = dict(xatlas_chart_options or {}), dict(xatlas_pack_options or {})
         for k in chart_opts:
             raise NotImplementedError(f"xatlas chart option {k!r}: the atlas is axis-projection charts, not xatlas")
@@ -151,14 +153,15 @@ class Mesh:
                 raise NotImplementedError(f"xatlas pack option {k!r}: only 'padding' and 'resolution' are supported")
         N = int(pack_opts.get("resolution") or texture_size or 1024)
         v_tex, t_tex_idx, info = ops.uv_atlas(self.v_pos.detach(), self.t_pos_idx, self.topology, texture_size=N,
-                                              padding=int(pack_opts.get("padding", 2)))
+                                              padding=int(pack_opts.get("padding", 2)), method=method)
         self.uv_info = info
         return v_tex, t_tex_idx
 
     def unwrap_uv(self, xatlas_chart_options: Optional[dict] = None, xatlas_pack_options: Optional[dict] = None,
-                  texture_size: Optional[int] = None) -> None:
-        """mesh.py:244-249; `texture_size` (the exporter's) sizes the atlas unless the pack options name a resolution."""
-        self._v_tex, self._t_tex_idx = self._unwrap_uv(xatlas_chart_options, xatlas_pack_options, texture_size)
+                  texture_size: Optional[int] = None, method: Optional[str] = "axis") -> None:
+        """mesh.py:244-249; `texture_size` (the exporter's) sizes the atlas unless the pack options name a resolution;
+        `method` as in _unwrap_uv."""
+        self._v_tex, self._t_tex_idx = self._unwrap_uv(xatlas_chart_options, xatlas_pack_options, texture_size, method)
         self._v_tng = self._v_tng_tex = None  # tangents belong to the UVs they were built from
 
     @property

@@ -1259,12 +1259,136 @@ def mesh_remove_small_components(v_pos: Tensor, t_pos_idx: Tensor, threshold, to
 # UV atlas and texture fill (include/tt_abi.h, "UV atlas and texture fill"): the exporter's xatlas / cv2.inpaint
 UV_DEFAULT_ROUNDS, UV_DEFAULT_TAU = _lib.TT_UV_DEFAULT_ROUNDS, _lib.TT_UV_DEFAULT_TAU
 UV_MAX_OVERLAP_ROUNDS = _lib.TT_UV_MAX_OVERLAP_ROUNDS
+UV_METHODS = ("axis", "lscm")
+UV_LSCM_DEFAULT_TOL, UV_LSCM_DEFAULT_MAX_ITERS = _lib.TT_UV_LSCM_DEFAULT_TOL, _lib.TT_UV_LSCM_DEFAULT_MAX_ITERS
+
+
+def uv_method(method: Optional[str]) -> str:
+    """The canonical name of an atlas flattening: None means "axis"; anything but UV_METHODS is a ValueError."""
+    name = "axis" if method is None else method
+    if name not in UV_METHODS:
+        raise ValueError(f"unknown UV method {method!r}: one of {UV_METHODS}")
+    return name
+
+
+def _lscm_tables(tri: Tensor, chart: Tensor, t_tex_idx: Tensor, Vt: int, C: int) -> Tuple[Tensor, int]:
+    """The int32 `tables` of tt_uv_lscm_* (include/tt_abi.h, "conformal UV charts": the UV vertices in chart order, the
+    corner CSR on them, the charts' vertex ranges and their tiles) and the tile count: two stable torch sorts and one
+    read-back (plumbing)."""
+    dev, T, tile = tri.device, tri.shape[0], _lib.TT_UV_LSCM_TILE
+    i64 = dict(device=dev, dtype=torch.int64)
+    tt = t_tex_idx.reshape(-1).long()
+    # chart and mesh vertex of every UV vertex (all corners of one (chart, vertex) pair write the same value)
+    vchart_u, vmesh_u = torch.empty(Vt, **i64), torch.empty(Vt, **i64)
+    vchart_u[tt] = chart.long().repeat_interleave(3)
+    vmesh_u[tt] = tri.reshape(-1).long()
+    vchart, vperm = torch.sort(vchart_u, stable=True)
+    spos = torch.empty(Vt, **i64)
+    spos[vperm] = torch.arange(Vt, **i64)
+    fc = spos[tt]
+    cptr, ccol = _csr(fc, None, Vt, 3 * T)
+    n = torch.bincount(vchart, minlength=C)
+    vptr, tptr = torch.zeros(C + 1, **i64), torch.zeros(C + 1, **i64)
+    vptr[1:] = torch.cumsum(n, 0)
+    n_tile = (n + (tile - 1)) // tile
+    tptr[1:] = torch.cumsum(n_tile, 0)
+    NT = int(tptr[-1].item())
+    tchart = torch.repeat_interleave(torch.arange(C, **i64), n_tile)
+    tbegin = vptr[tchart] + tile * (torch.arange(NT, **i64) - tptr[tchart])
+    tables = torch.cat([fc, ccol.long(), vmesh_u[vperm], vchart, vperm, cptr.long(), vptr, tptr, tchart, tbegin])
+    return tables.int().contiguous(), NT
+
+
+def _lscm_flatten(v_pos: Tensor, tri: Tensor, chart: Tensor, t_tex_idx: Tensor, Vt: int, C: int,
+                  chart_box: Optional[Tensor], tau: float, tol: float, max_iters: int) -> dict:
+    """tt_uv_lscm_setup / _iterate / _finish on dense chart ids 0..C-1 and their UV vertices (t_tex_idx, Vt): the
+    conformal map of every chart and which charts keep it.  The solver's state is read back once every
+    TT_UV_LSCM_CHECK_EVERY iterations (4 bytes: the charts still iterating)."""
+    dev, V, T = v_pos.device, v_pos.shape[0], tri.shape[0]
+    tables, NT = _lscm_tables(tri, chart, t_tex_idx, Vt, C)
+    if tables.numel() != int(_lib.load().tt_uv_lscm_table_ints(T, Vt, C, NT)):
+        raise RuntimeError("uv lscm: the tables do not have the layout of include/tt_abi.h")
+    ws = _workspace("tt_uv_lscm_workspace_bytes", T, Vt, C, NT, device=dev)
+    totals = torch.empty(4, device=dev, dtype=torch.int32)
+    with _timed("uv_lscm_solve"):
+        _launch("tt_uv_lscm_setup", v_pos, tables, V, T, Vt, C, NT, ws)
+        it = 0
+        while it < max_iters:
+            n = min(_lib.TT_UV_LSCM_CHECK_EVERY, max_iters - it)
+            _launch("tt_uv_lscm_iterate", tables, T, Vt, C, NT, n, float(tol), ws, totals)
+            it += n
+            if int(totals[0].item()) == 0:
+                break
+        f64 = dict(device=dev, dtype=torch.float64)
+        out = {"uv": torch.empty((Vt, 2), **f64), "uv_final": torch.empty((Vt, 2), device=dev),
+               "box": torch.empty((C, 4), device=dev), "fallback": torch.empty(C, device=dev, dtype=torch.uint8),
+               "pins": torch.empty((C, 2), device=dev, dtype=torch.int32),
+               "chart_iterations": torch.empty(C, device=dev, dtype=torch.int32), "residual": torch.empty(C, **f64),
+               "rotation": torch.empty(C, **f64), "scale": torch.empty(C, **f64)}
+        _launch("tt_uv_lscm_finish", tables, chart_box, T, Vt, C, NT, float(tau), ws, out["uv"], out["uv_final"],
+                out["box"], out["fallback"], out["pins"], out["chart_iterations"], out["residual"], out["rotation"],
+                out["scale"])
+    out["fallback"] = out["fallback"].bool()
+    out["iterations"] = it
+    return out
+
+
+def _chk_lscm_args(tau: float, tol: float, max_iters: int) -> Tuple[float, float, int]:
+    if not (0.0 < float(tau) <= _lib.TT_UV_MAX_TAU):
+        raise ValueError(f"tau must lie in (0, {_lib.TT_UV_MAX_TAU}], got {tau}")
+    if not (0.0 <= float(tol) < 1.0):
+        raise ValueError(f"lscm tolerance must lie in [0, 1), got {tol}")
+    if isinstance(max_iters, bool) or int(max_iters) != max_iters or max_iters < 0:
+        raise ValueError(f"lscm max_iters must be an integer >= 0, got {max_iters}")
+    return float(tau), float(tol), int(max_iters)
+
+
+@torch.no_grad()
+def uv_flatten_lscm(v_pos: Tensor, t_pos_idx: Tensor, chart: Tensor, tol: float = UV_LSCM_DEFAULT_TOL,
+                    max_iters: int = UV_LSCM_DEFAULT_MAX_ITERS, tau: float = UV_DEFAULT_TAU
+                    ) -> Tuple[Tensor, Tensor, dict]:
+    """The least-squares conformal map of every chart of a face -> chart assignment (`chart` (T,) int32: a chart is the
+    set of faces with one id), the solver of uv_atlas(method="lscm") on its own (include/tt_abi.h, "conformal UV
+    charts").  Returns uv (Vt,2) fp64, the raw solution with the chart's two pins at (0,0) and (|p1 - p0|, 0); t_tex_idx
+    (T,3) int32, one UV vertex per distinct (chart, vertex) pair in order of its first corner; and info, whose (C,)
+    entries follow the sorted chart ids info["chart_ids"]: fallback (bool: the chart did not converge within max_iters
+    to |r| <= tol |b|, is degenerate, flips a face or stretches one beyond [tau, 1/tau] in area), pins (C,2),
+    iterations, chart_iterations, residual, rotation, scale, uv_final (Vt,2) fp32 (scaled to the 3-D area, principal
+    axis along u; zeros for fallback charts) and box (C,4).  Nothing raises for a chart that fails.  Bit-identical from
+    call to call."""
+    tau, tol, max_iters = _chk_lscm_args(tau, tol, max_iters)
+    v_pos = _chk(v_pos.detach(), "v_pos", (None, 3))
+    V = v_pos.shape[0]
+    t_pos_idx = _chk_index(t_pos_idx, "t_pos_idx", 3)
+    T = t_pos_idx.shape[0]
+    _chk_size("mesh too large for tt_uv_lscm_*", V=V, T=T)
+    chart = _chk(chart, "chart", (T,), dtype=torch.int32)
+    dev = v_pos.device
+    i32 = dict(device=dev, dtype=torch.int32)
+    if T == 0:
+        return (torch.zeros((0, 2), device=dev, dtype=torch.float64), torch.zeros((0, 3), **i32),
+                {"charts": 0, "iterations": 0})
+    _chk_range("t_pos_idx", *_minmax(t_pos_idx).tolist(), V)  # one read-back
+    tri = t_pos_idx.int().contiguous()
+    ids, dense = torch.unique(chart, return_inverse=True)
+    dense, C = dense.int().contiguous(), int(ids.shape[0])
+    ws = _workspace("tt_uv_workspace_bytes", V, T, 1, device=dev)
+    totals = torch.empty(4, **i32)
+    _launch("tt_uv_emit_count", tri, dense, V, T, 1, ws, totals)
+    Vt = int(totals[0].item())
+    t_tex_idx = torch.empty((T, 3), **i32)
+    _launch("tt_uv_lscm_index", V, T, 1, ws, t_tex_idx)
+    info = _lscm_flatten(v_pos, tri, dense, t_tex_idx, Vt, C, None, tau, tol, max_iters)
+    info.update(charts=C, chart_ids=ids)
+    return info["uv"], t_tex_idx, info
 
 
 @torch.no_grad()
 def uv_atlas(v_pos: Tensor, t_pos_idx: Tensor, topology: Optional[MeshTopology] = None, texture_size: int = 1024,
              padding: int = 2, rounds: int = UV_DEFAULT_ROUNDS, tau: float = UV_DEFAULT_TAU,
-             max_overlap_rounds: int = UV_MAX_OVERLAP_ROUNDS) -> Tuple[Tensor, Tensor, dict]:
+             max_overlap_rounds: int = UV_MAX_OVERLAP_ROUNDS, method: Optional[str] = "axis",
+             lscm_tol: float = UV_LSCM_DEFAULT_TOL, lscm_max_iters: int = UV_LSCM_DEFAULT_MAX_ITERS
+             ) -> Tuple[Tensor, Tensor, dict]:
     """Axis-projection UV atlas of a mesh for a texture_size^2 texture with `padding` texels around every chart:
     v_tex (Vt,2) fp32 in [0,1], t_tex_idx (T,3) int32 (face f of t_pos_idx), and info = {charts, scale (texels per
     world unit), fill_ratio (covered texel centres / N^2), overlap_rounds, labels, chart, chart_box, offsets,
@@ -1272,7 +1396,18 @@ def uv_atlas(v_pos: Tensor, t_pos_idx: Tensor, topology: Optional[MeshTopology] 
     one read-back of the chart boxes), UVs (tt_uv_emit_count / tt_uv_emit), then the overlap guard (tt_uv_overlap):
     faces on a texel centre that two UV triangles cover become singleton charts and the atlas is redone; after
     max_overlap_rounds such rounds every face of a chart that still overlaps becomes a singleton.  Bit-identical from
-    call to call."""
+    call to call.
+
+    method="lscm" flattens the same charts by a least-squares conformal map instead (include/tt_abi.h, "conformal UV
+    charts"; _lscm_flatten, re-solved in every overlap round): each chart is scaled to its 3-D area and turned with its
+    principal axis along u before packing; a chart that does not converge within lscm_max_iters to lscm_tol, flips a
+    face or changes a face's area by more than [tau, 1/tau] keeps its axis projection.  info["lscm"] then holds, for
+    the last round: uv (Vt,2) fp64 (the raw solution), uv_final, iterations, chart_iterations, residual (C,), pins
+    (C,2), fallback (C,) bool, rotation, scale (C,), and chart_round0, the charts before the overlap guard."""
+    method = uv_method(method)
+    lscm = method == "lscm"
+    if lscm:
+        tau, lscm_tol, lscm_max_iters = _chk_lscm_args(tau, lscm_tol, lscm_max_iters)
     v_pos = _chk(v_pos.detach(), "v_pos", (None, 3))
     V = v_pos.shape[0]
     topo = topology if topology is not None else mesh_topology(t_pos_idx, V)
@@ -1299,7 +1434,16 @@ def uv_atlas(v_pos: Tensor, t_pos_idx: Tensor, topology: Optional[MeshTopology] 
         _launch("tt_uv_charts", v_pos, tri, pairs, labels, singleton, V, T, P, N, ws, chart, box, totals,
                 label="uv_charts")
         C = int(totals[0].item())
-        box_h = box[:C].cpu()
+        if lscm:  # the conformal maps come before the packing: their boxes are what is packed
+            _launch("tt_uv_emit_count", tri, chart, V, T, N, ws, totals)
+            Vt = int(totals[0].item())
+            t_tex_idx = torch.empty((T, 3), **i32)
+            _launch("tt_uv_lscm_index", V, T, N, ws, t_tex_idx)
+            sol = _lscm_flatten(v_pos, tri, chart, t_tex_idx, Vt, C, box, tau, lscm_tol, lscm_max_iters)
+            if r == 0:
+                sol_chart0 = chart.clone()
+        pbox = sol["box"] if lscm else box  # (C,4) / (T,4): rows 0..C-1 are the charts' boxes
+        box_h = pbox[:C].cpu()
         off_h = torch.empty((C, 2), dtype=torch.int32)
         scale_h = torch.zeros(1, dtype=torch.float32)
         st = _lib.load().tt_uv_pack(_ptr(box_h), C, N, pad, _ptr(off_h), _ptr(scale_h))  # on the host: no stream
@@ -1310,11 +1454,17 @@ def uv_atlas(v_pos: Tensor, t_pos_idx: Tensor, topology: Optional[MeshTopology] 
         offsets = off_h.to(dev)
         scale = float(scale_h[0])
         with _timed("uv_emit"):
-            _launch("tt_uv_emit_count", tri, chart, V, T, N, ws, totals)
-            Vt = int(totals[0].item())
-            v_tex = torch.empty((Vt, 2), device=dev, dtype=torch.float32)
-            t_tex_idx = torch.empty((T, 3), **i32)
-            _launch("tt_uv_emit", v_pos, tri, labels, chart, box, offsets, C, scale, V, T, N, pad, ws, v_tex, t_tex_idx)
+            if lscm:
+                v_tex = torch.empty((Vt, 2), device=dev, dtype=torch.float32)
+                _launch("tt_uv_lscm_emit", v_pos, tri, labels, chart, t_tex_idx, sol["uv_final"],
+                        sol["fallback"].to(torch.uint8), pbox, offsets, C, scale, V, T, Vt, N, pad, v_tex)
+            else:
+                _launch("tt_uv_emit_count", tri, chart, V, T, N, ws, totals)
+                Vt = int(totals[0].item())
+                v_tex = torch.empty((Vt, 2), device=dev, dtype=torch.float32)
+                t_tex_idx = torch.empty((T, 3), **i32)
+                _launch("tt_uv_emit", v_pos, tri, labels, chart, box, offsets, C, scale, V, T, N, pad, ws, v_tex,
+                        t_tex_idx)
         _launch("tt_uv_overlap", v_tex, t_tex_idx, Vt, V, T, N, ws, flags, totals, label="uv_overlap")
         n_flagged, n_covered = (int(x) for x in totals[:2].cpu())
         if n_flagged == 0:
@@ -1328,6 +1478,8 @@ def uv_atlas(v_pos: Tensor, t_pos_idx: Tensor, topology: Optional[MeshTopology] 
         r += 1  # a flagged face is never a singleton: every round adds singletons, so the loop ends
     info.update(charts=C, scale=scale, fill_ratio=n_covered / float(N * N), overlap_rounds=r, labels=labels,
                 chart=chart, chart_box=box_h, offsets=off_h, singleton=singleton)
+    if lscm:
+        info["lscm"] = dict(sol, chart_round0=sol_chart0)
     return v_tex, t_tex_idx, info
 
 
