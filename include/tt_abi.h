@@ -492,6 +492,10 @@ int tt_composite_bwd(const float* opacity, const float* depth, const float* rgb_
  * padding_mode 0 = zeros, 1 = border (the reference passes it as a bool); align_corners 0 / 1; dtype TT_DTYPE_*
  * (half computes in fp32).  Reflection padding and the 3-D variant are TT_ERR_UNSUPPORTED / not exported (the
  * reference never calls them).  grad_input is zero-filled inside (like the reference).
+ * A point with a non-finite grid coordinate (NaN or +-inf on either axis) is inert, as in the reference, whose
+ * within_bounds_2d skips its taps: its rows of grad_grad_output and grad_grid are exactly 0 and it adds 0 to
+ * grad_input (the same contract as tt_texture_* for non-finite UVs).  The sizes are the caller's to get right:
+ * nothing here can check a pointer against n, c, h, w or n_points_per_batch (grid_sample_gradfix.grad2_2d does).
  * tt_grid_sample_2d_grad2 is the fp32 entry point. */
 #define TT_DTYPE_F32 0
 #define TT_DTYPE_F16 1

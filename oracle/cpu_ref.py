@@ -202,8 +202,10 @@ def bilinear_corners(grid: Tensor, H: int, W: int, padding_mode: str = "zeros", 
         ix = ((gx + 1) * W - 1) / 2
         iy = ((gy + 1) * H - 1) / 2
     if padding_mode == "border":
-        ix = ix.clamp(0, W - 1)
-        iy = iy.clamp(0, H - 1)
+        # (clip_coordinates_set_grad: the gradient is 0 for ip <= 0 and ip >= size-1; torch.clamp's own backward lets
+        # it through AT the two bounds, so the clipped branch is cut off the graph.  Same values.)
+        ix = torch.where((ix > 0) & (ix < W - 1), ix, ix.detach().clamp(0, W - 1))
+        iy = torch.where((iy > 0) & (iy < H - 1), iy, iy.detach().clamp(0, H - 1))
     elif padding_mode != "zeros":
         raise ValueError(padding_mode)
     ix_nw = torch.floor(ix)

@@ -123,14 +123,27 @@ __global__ __launch_bounds__(256) void k_grid_sample_2d_grad2(Grad2Params<T> p) 
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
          idx += (long long)gridDim.x * blockDim.x) {
         const long long n = idx / p.M, m = idx - n * p.M;
-        const Axis<A> ax = axis_setup<A>(ld<A>(p.grid + idx * 2 + 0), p.W, p.border, p.align);
-        const Axis<A> ay = axis_setup<A>(ld<A>(p.grid + idx * 2 + 1), p.H, p.border, p.align);
+        // a non-finite coordinate (inf - floor(inf) = NaN, and NaN * 0 = NaN: the 0/1 flags do not silence it) makes
+        // its point inert like the reference's within_bounds_2d does: the taps are set up at 0 and every coefficient
+        // is selected to 0, so the point's rows are 0 and it adds 0 to grad_input.  Finite points: same bits as before.
+        const A gxn = ld<A>(p.grid + idx * 2 + 0), gyn = ld<A>(p.grid + idx * 2 + 1);
+        // "both finite" as ONE compare (tt_mask.h): the halved magnitudes cannot overflow, NaN fails the compare
+        const bool live = fabs(gxn) * (A)0.5 + fabs(gyn) * (A)0.5 < (A)INFINITY;
+        const Axis<A> ax = axis_setup<A>(live ? gxn : (A)0, p.W, p.border, p.align);
+        const Axis<A> ay = axis_setup<A>(live ? gyn : (A)0, p.H, p.border, p.align);
         const A tx = ld<A>(p.g2_grid + idx * 2 + 0), ty = ld<A>(p.g2_grid + idx * 2 + 1);
         // corners k = (x tap, y tap): 00 nw, 10 ne, 01 sw, 11 se
-        const A w[4] = {ax.w0 * ay.w0, ax.w1 * ay.w0, ax.w0 * ay.w1, ax.w1 * ay.w1};
-        const A a[4] = {ax.d0 * ay.w0, ax.d1 * ay.w0, ax.d0 * ay.w1, ax.d1 * ay.w1};
-        const A b[4] = {ax.w0 * ay.d0, ax.w1 * ay.d0, ax.w0 * ay.d1, ax.w1 * ay.d1};
-        const A c[4] = {ax.d0 * ay.d0, ax.d1 * ay.d0, ax.d0 * ay.d1, ax.d1 * ay.d1};
+        A w[4] = {ax.w0 * ay.w0, ax.w1 * ay.w0, ax.w0 * ay.w1, ax.w1 * ay.w1};
+        A a[4] = {ax.d0 * ay.w0, ax.d1 * ay.w0, ax.d0 * ay.w1, ax.d1 * ay.w1};
+        A b[4] = {ax.w0 * ay.d0, ax.w1 * ay.d0, ax.w0 * ay.d1, ax.w1 * ay.d1};
+        A c[4] = {ax.d0 * ay.d0, ax.d1 * ay.d0, ax.d0 * ay.d1, ax.d1 * ay.d1};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            w[k] = live ? w[k] : (A)0;
+            a[k] = live ? a[k] : (A)0;
+            b[k] = live ? b[k] : (A)0;
+            c[k] = live ? c[k] : (A)0;
+        }
         const size_t off[4] = {(size_t)ay.i0 * p.W + ax.i0, (size_t)ay.i0 * p.W + ax.i1, (size_t)ay.i1 * p.W + ax.i0,
                                (size_t)ay.i1 * p.W + ax.i1};
         A t[4];  // coefficient of v_k in grad_grad_output = coefficient of go in grad_input[k]

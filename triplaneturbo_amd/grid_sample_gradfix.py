@@ -22,16 +22,19 @@ _DTYPES = {torch.float32: _lib.TT_DTYPE_F32, torch.float16: _lib.TT_DTYPE_F16, t
 
 def grad2_2d(grad2_grad_input, grad2_grad_grid, grad_output, input, grid, padding_mode, align_corners):
     """gridsample_cuda.cpp:26-37 signature; returns [grad_grad_output, grad_input, grad_grid].  half / float / double,
-    padding_mode 0 (zeros) or 1 (border) -- the reference passes it as a bool --, either align_corners."""
+    padding_mode 0 (zeros) or 1 (border) -- the reference passes it as a bool --, either align_corners.
+    input (N,C,H,W), grid (N,Ho,Wo,2), grad_output (N,C,Ho,Wo), one dtype: anything else is a TypeError / ValueError
+    before any launch (the kernel indexes by these sizes and checks nothing).  A point with a non-finite grid
+    coordinate is inert: zero rows in grad_grad_output and grad_grid, no contribution to grad_input."""
     dt = input.dtype
     if dt not in _DTYPES:
         raise TypeError(f"grad2_2d: unsupported dtype {dt}")
-    input = _chk(input, "input", dtype=dt)
-    grid = _chk(grid, "grid", dtype=dt)
-    grad_output = _chk(grad_output, "grad_output", dtype=dt)
+    input = _chk(input, "input", (None, None, None, None), dtype=dt)
+    N, C, H, W = input.shape
+    grid = _chk(grid, "grid", (N, None, None, 2), dtype=dt)
+    grad_output = _chk(grad_output, "grad_output", (N, C, grid.shape[1], grid.shape[2]), dtype=dt)
     g2i = _chk(grad2_grad_input, "grad2_grad_input", input.shape, dtype=dt)
     g2g = _chk(grad2_grad_grid, "grad2_grad_grid", grid.shape, dtype=dt)
-    N, C, H, W = input.shape
     M = grid.shape[1] * grid.shape[2]
     ggo = torch.empty_like(grad_output)
     gi = torch.empty_like(input)
