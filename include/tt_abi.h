@@ -947,9 +947,10 @@ int tt_uv_lscm_emit(const float* v_pos, const int32_t* t_pos_idx, const int32_t*
  *   box         in fp32: lo_a = min over the vertices of v_a; ext = the largest of the three extents max v_a - lo_a;
  *               h = ext / (float)G; inv_h = (float)G / ext (two IEEE divisions).  ext == 0, V == 0 or T == 0: the host
  *               returns the mesh as it is and calls nothing here.
- *   cell        of EVERY vertex, referenced or not: c_a = min(G-1, max(0, (int)floorf((v_a - lo_a) * inv_h))), the
- *               subtraction and the product each rounded to fp32 (this form has no sum behind its product, so nothing
- *               contracts into an FMA and a float32 restatement gets bit-identical keys); key = (c_x G + c_y) G + c_z.
+ *   cell        of EVERY vertex, referenced or not: c_a = min(G-1, max(0, floorf((v_a - lo_a) * inv_h))), the
+ *               subtraction and the product each rounded to fp32 (tri_cell of csrc/tt_trigrid.h; it has no sum behind
+ *               its product, so nothing contracts into an FMA and a float32 restatement gets bit-identical keys);
+ *               key = (c_x G + c_y) G + c_z.
  *               tt_simplify_keys writes keys (V) int64.
  *   clusters    the distinct keys, ranked by ascending key; C of them.  The host sorts the keys (stable, so a cluster's
  *               vertices are in ascending vertex index); tt_simplify_ranks, from the sorted keys and the permutation,
@@ -1276,8 +1277,10 @@ int tt_bake_encode(const float* rast, const float* v_nrm, const int32_t* t_pos_i
  *               search.
  *   grid        G^3 cells over the mesh's bounding cube, 1 <= G <= TT_DIST_MAX_GRID: lo_a = min v_a, ext = the largest
  *               of the three extents, h = ext / (float)G, inv_h = (float)G / ext (ext == 0: h = inv_h = 0, everything
- *               is in cell 0).  cell(x) = min(G-1, max(0, (int)floorf((x - lo_a) * inv_h))), difference and product
- *               each rounded to fp32; key = (c_x G + c_y) G + c_z, so consecutive cells along z are consecutive rows.
+ *               is in cell 0).  cell(x) = min(G-1, max(0, floorf((x - lo_a) * inv_h))), difference and product each
+ *               rounded to fp32, the clamp taken before the conversion to int: ONE device function, tri_cell of
+ *               csrc/tt_trigrid.h, which every stage below shares along with the cube, the record and the view of
+ *               the tables; key = (c_x G + c_y) G + c_z, so consecutive cells along z are consecutive rows.
  *               tt_dist_build_count packs every triangle into a 48-byte record (three float4: a, b, c, w unused),
  *               counts per cell the triangles whose axis-aligned box overlaps it (cells of the box's two corners,
  *               integer atomics) and scans (tt_scan.h): cell_ptr (G^3 + 1) int32; M = the number of (cell, triangle)
@@ -1367,11 +1370,11 @@ int tt_dist_sample_emit(const float* v_pos, const int32_t* t_pos_idx, const int6
  *   tree        a dense octree over the bounding cube (lo_a = min v_a, ext = the largest extent, as the distance grid)
  *               with L levels below the root, 0 <= L <= TT_WIND_MAX_LEVELS; G = 2^L leaf cells per axis, inv_h = G / ext
  *               (0 where ext == 0).  A face belongs to the leaf cell of its centroid ((a + b) + c) * (1/3 in fp32), every
- *               operation rounded to fp32, cell(x) as for the distance grid.  The Morton key of cell (c_x, c_y, c_z) puts
- *               bit b of c_x, c_y, c_z at bits 3b+2, 3b+1, 3b.  tt_wind_face_keys writes the records in face order and
- *               keys (T) int64; the host sorts (key, face) (one stable sort) and gathers the records into that order:
- *               sorted_records, and leaf_ptr (8^L + 1) int32, the CSR of the leaves.  The faces under node (l, m) are
- *               then the range leaf_ptr[m 8^(L-l)] .. leaf_ptr[(m+1) 8^(L-l)] of the sorted list.
+ *               operation rounded to fp32, cell(x) the distance grid's own function (tri_cell).  The Morton key of cell
+ *               (c_x, c_y, c_z) puts bit b of c_x, c_y, c_z at bits 3b+2, 3b+1, 3b.  tt_wind_face_keys writes the
+ *               records in face order and keys (T) int64; the host sorts (key, face) (one stable sort) and gathers the
+ *               records into that order: sorted_records, and leaf_ptr (8^L + 1) int32, the CSR of the leaves.  The
+ *               faces under node (l, m) are then the range leaf_ptr[m 8^(L-l)] .. leaf_ptr[(m+1) 8^(L-l)] of the sorted list.
  *   node table  level l holds its 8^l nodes in Morton order from node (8^l - 1) / 7 on; tt_wind_node_count(L) =
  *               (8^(L+1) - 1) / 7 nodes of 8 floats: N_x, N_y, N_z, r, c_x, c_y, c_z, A.  N = sum 1/2 (b-a) x (c-a), the
  *               sum of the area vectors; A = sum of the areas |1/2 (b-a) x (c-a)|; c the area-weighted centroid
@@ -1417,7 +1420,8 @@ int tt_wind_fast(const float* points, const int64_t* order, int32_t N, const flo
  * The query behind ops.mesh_ray_cast / mesh_ray_occluded / ray_mesh_depth, Mesh.ray_cast and the ambient-occlusion map
  * of a simplified export (ops.bake_ambient_occlusion, map_Ka).  The reference has no such step.  The mesh is the
  * TriangleGrid of "point-to-mesh distance" above, unchanged: records (T,3,4), cell_ptr (G^3 + 1), cell_tri (M), lo, ext,
- * h, inv_h, G.  A ray is a row o of origins (N,3) and a row d of dirs (N,3), fp32; d has any length, t is in units of d;
+ * h, inv_h, G (the kernels take it as the TriGridView of csrc/tt_trigrid.h).  A ray is a row o of origins (N,3) and a
+ * row d of dirs (N,3), fp32; d has any length, t is in units of d;
  * t_max is one fp32 per call, >= 0, +inf allowed.  Hits have 0 <= t <= t_max.
  *   pair        ONE device function (ray_pair) with one call site (ray_walk), shared by the three kernels: the
  *               watertight test of Woop, Benthin and Wald (JCGT 2013) in fp32.  kz = argmax |d| (the lowest index at
@@ -1450,12 +1454,12 @@ int tt_wind_fast(const float* points, const int64_t* order, int32_t N, const flo
  *               first slice has s = -inf, the last e = +inf (inf - inf opens likewise).  s > t_hi ends the walk.
  *               [t0, t1] = [s, e] cut by the span; if it is not empty, on each lateral axis b the ray's coordinates
  *               o_b + t0 d_b and o_b + t1 d_b (o_b itself where d_b == 0), their minimum lowered and their maximum
- *               raised by tol, go through the grid's own cell() -- the monotone function the triangles were binned
- *               with (here with its clamp taken before the conversion, so that an infinity lands on a cell) -- and
- *               give the cell range.  Every triangle of every cell of that rectangle is tested against the ray; a hit
- *               is accepted whatever cell it falls in; (t, face) is minimised.  After a slice the walk stops when the
- *               best t is STRICTLY below s: equality goes on.  tt_ray_any and tt_ray_ao leave at the first accepted
- *               pair instead.  G = 1 is brute force through the same code.
+ *               raised by tol, go through the grid's own cell() -- tri_cell of csrc/tt_trigrid.h, the monotone function
+ *               the triangles were binned with (its clamp is taken before the conversion, so that an infinity lands on
+ *               a cell) -- and give the cell range.  Every triangle of every cell of that rectangle is tested against
+ *               the ray; a hit is accepted whatever cell it falls in; (t, face) is minimised.  After a slice the walk
+ *               stops when the best t is STRICTLY below s: equality goes on.  tt_ray_any and tt_ray_ao leave at the
+ *               first accepted pair instead.  G = 1 is brute force through the same code.
  *   why it is   Let the pair accept triangle f at the fp32 value t.  P = the point of f nearest to R(t) = o + t d (in
  *   conservative exact arithmetic).  The pair's t is within 2^-20 (L + |o|) / |d| of the exact parameter (measured 2.4e-7 of
  *               that scale, tests/ray_reference.py), so |R(t) - P| <= eps = 2^-19 S.  P lies in f's box, so by the

@@ -23,11 +23,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import triplaneturbo_amd as tt  # noqa: E402
-from triplaneturbo_amd import ops  # noqa: E402
+from triplaneturbo_amd import _lib, ops  # noqa: E402
 from triplaneturbo_amd.isosurface import DiffMarchingCubeHelper, Mesh, isosurface  # noqa: E402
 import winding_reference as W  # noqa: E402
 from time_export import timed  # noqa: E402
 from time_mesh_distance import make_points  # noqa: E402
+
+if os.environ.get("TT_LIB_VARIANT"):  # dev A/B of an experiment build (tools/build_variants.py)
+    _lib.use_variant(os.environ["TT_LIB_VARIANT"])
 
 BAR = 1.7e-5  # tests/test_gpu_winding.py
 BRUTE_POINTS = 2000

@@ -10,18 +10,14 @@
 //   k_dist_sample_count -> tt_exclusive_scan<long long> -> k_dist_sample_emit   one thread per sample
 // The answer of a query is the lexicographic minimum of (d2, face) over ALL triangles; dist_closest is the only place a
 // pair is evaluated and k_dist_query holds its only call, so neither the grid, the order inside a cell nor the launch
-// can change a bit of it.
+// can change a bit of it.  The cube, its cell rule, the record, the `order` lookup, the grid's device view and the
+// argument checks are tt_trigrid.h, shared with tt_ray.hip, tt_wind.hip and tt_simplify.hip.
 #include <math.h>
 
-#include "tt_host.h"
 #include "tt_scan.h"
+#include "tt_trigrid.h"
 
 #define DIST_BLOCK TT_ITEM_BLOCK
-
-struct DistGrid {
-    float lo[3], ext, h, inv_h;
-    int G;
-};
 
 struct DistWs {
     int *xs, *cursor;
@@ -159,20 +155,15 @@ __device__ __forceinline__ DistHit dist_closest(const float p[3], const float a[
 // ---------------------------------------------------------------------------------------------------------------
 // grid build
 // ---------------------------------------------------------------------------------------------------------------
-// subtract, then multiply, each rounded on its own; monotone in x, which is all the search's bound needs
-__device__ __forceinline__ int dist_cell(float x, float lo, float inv_h, int G) {
-    const int c = (int)floorf(__fmul_rn(__fsub_rn(x, lo), inv_h));
-    return min(G - 1, max(0, c));
-}
-
-__device__ __forceinline__ void dist_tri_cells(const float4 r0, const float4 r1, const float4 r2, const DistGrid& g,
+// the cells of a triangle's box: tri_cell (tt_trigrid.h) of its two corners; monotone, which is all the search's bound needs
+__device__ __forceinline__ void dist_tri_cells(const float4 r0, const float4 r1, const float4 r2, const TriCube& g,
                                                int c0[3], int c1[3]) {
     const float mn[3] = {fminf(r0.x, fminf(r1.x, r2.x)), fminf(r0.y, fminf(r1.y, r2.y)), fminf(r0.z, fminf(r1.z, r2.z))};
     const float mx[3] = {fmaxf(r0.x, fmaxf(r1.x, r2.x)), fmaxf(r0.y, fmaxf(r1.y, r2.y)), fmaxf(r0.z, fmaxf(r1.z, r2.z))};
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        c0[a] = dist_cell(mn[a], g.lo[a], g.inv_h, g.G);
-        c1[a] = max(c0[a], dist_cell(mx[a], g.lo[a], g.inv_h, g.G));
+        c0[a] = tri_cell(mn[a], g.lo[a], g.inv_h, g.G);
+        c1[a] = max(c0[a], tri_cell(mx[a], g.lo[a], g.inv_h, g.G));
     }
 }
 
@@ -185,18 +176,15 @@ __global__ __launch_bounds__(DIST_BLOCK) void k_dist_zero(int* __restrict__ a, l
 }
 
 __global__ __launch_bounds__(DIST_BLOCK) void k_dist_build(const float* __restrict__ v_pos, const int* __restrict__ tri,
-                                                           int V, int T, DistGrid g, float4* __restrict__ rec,
+                                                           int V, int T, TriCube g, float4* __restrict__ rec,
                                                            int* __restrict__ cell_cnt,
                                                            unsigned long long* __restrict__ total) {
     const int f = blockIdx.x * DIST_BLOCK + threadIdx.x;
     if (f >= T) return;
     float4 r[3];
+    tri_record(v_pos, tri, V, f, r);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const unsigned i = min((unsigned)tri[(size_t)f * 3 + k], (unsigned)(V - 1));  // the host checked the range
-        r[k] = make_float4(v_pos[(size_t)i * 3], v_pos[(size_t)i * 3 + 1], v_pos[(size_t)i * 3 + 2], 0.f);
-        rec[(size_t)f * 3 + k] = r[k];
-    }
+    for (int k = 0; k < 3; ++k) rec[(size_t)f * 3 + k] = r[k];
     int c0[3], c1[3];
     dist_tri_cells(r[0], r[1], r[2], g, c0, c1);
     for (int z = c0[0]; z <= c1[0]; ++z)
@@ -206,7 +194,7 @@ __global__ __launch_bounds__(DIST_BLOCK) void k_dist_build(const float* __restri
                          (unsigned long long)(c1[2] - c0[2] + 1));
 }
 
-__global__ __launch_bounds__(DIST_BLOCK) void k_dist_fill(const float4* __restrict__ rec, int T, DistGrid g,
+__global__ __launch_bounds__(DIST_BLOCK) void k_dist_fill(const float4* __restrict__ rec, int T, TriCube g,
                                                           const int* __restrict__ cell_ptr, int* __restrict__ cursor,
                                                           int M, int* __restrict__ cell_tri) {
     const int f = blockIdx.x * DIST_BLOCK + threadIdx.x;
@@ -225,31 +213,15 @@ __global__ __launch_bounds__(DIST_BLOCK) void k_dist_fill(const float4* __restri
 // ---------------------------------------------------------------------------------------------------------------
 // query
 // ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool dist_finite3(const float p[3]) {
-    return fabsf(p[0]) <= 3.4028235e38f && fabsf(p[1]) <= 3.4028235e38f && fabsf(p[2]) <= 3.4028235e38f;  // NaN: false
-}
-
-// p clamped to the cube, its cell, |p - q|^2
-__device__ __forceinline__ float dist_point_cell(const float p[3], const DistGrid& g, int c[3]) {
-    float pq2 = 0.f;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float q = fminf(fmaxf(p[a], g.lo[a]), g.lo[a] + g.ext);
-        c[a] = dist_cell(q, g.lo[a], g.inv_h, g.G);
-        pq2 += (p[a] - q) * (p[a] - q);
-    }
-    return pq2;
-}
-
-__global__ __launch_bounds__(DIST_BLOCK) void k_dist_keys(const float* __restrict__ points, int N, DistGrid g,
+__global__ __launch_bounds__(DIST_BLOCK) void k_dist_keys(const float* __restrict__ points, int N, TriCube g,
                                                           long long* __restrict__ keys) {
     const int i = blockIdx.x * DIST_BLOCK + threadIdx.x;
     if (i >= N) return;
     const float p[3] = {points[(size_t)i * 3], points[(size_t)i * 3 + 1], points[(size_t)i * 3 + 2]};
     int c[3] = {0, 0, 0};
-    const bool ok = dist_finite3(p);
-    if (ok) dist_point_cell(p, g, c);
-    keys[i] = ok ? (long long)((c[0] * g.G + c[1]) * g.G + c[2]) : -1ll;
+    const bool ok = tri_finite3(p[0], p[1], p[2]);
+    if (ok) tri_point_cell(p, g, c);
+    keys[i] = ok ? (long long)tri_key(c, g.G) : -1ll;
 }
 
 struct DistBest {
@@ -259,30 +231,25 @@ struct DistBest {
 
 __global__ __launch_bounds__(DIST_BLOCK) void k_dist_query(const float* __restrict__ points,
                                                            const long long* __restrict__ order, int N,
-                                                           const float4* __restrict__ rec,
-                                                           const int* __restrict__ cell_ptr,
-                                                           const int* __restrict__ cell_tri, int T, int M, DistGrid g,
-                                                           float* __restrict__ out_d2, int* __restrict__ out_face,
-                                                           float* __restrict__ out_bary) {
+                                                           TriGridView grid, float* __restrict__ out_d2,
+                                                           int* __restrict__ out_face, float* __restrict__ out_bary) {
     const int t = blockIdx.x * DIST_BLOCK + threadIdx.x;
     if (t >= N) return;
-    long long i = t;
-    if (order) {
-        i = order[t];
-        if ((unsigned long long)i >= (unsigned long long)N) return;
-    }
+    const long long i = tri_row(order, t, N);
+    if (i < 0) return;
+    const TriCube& g = grid.cube;
     const float p[3] = {points[(size_t)i * 3], points[(size_t)i * 3 + 1], points[(size_t)i * 3 + 2]};
-    if (!dist_finite3(p)) {  // before the search: no loop depends on such a point
-        out_d2[i] = __int_as_float(0x7fc00000);
+    if (!tri_finite3(p[0], p[1], p[2])) {  // before the search: no loop depends on such a point
+        out_d2[i] = tri_nan();
         out_face[i] = -1;
         out_bary[(size_t)i * 3] = out_bary[(size_t)i * 3 + 1] = out_bary[(size_t)i * 3 + 2] = 0.f;
         return;
     }
     int c[3];
-    const float pq2 = dist_point_cell(p, g, c);
+    const float pq2 = tri_point_cell(p, g, c);
     const int G = g.G;
     const int rmax = max(max(max(c[0], G - 1 - c[0]), max(c[1], G - 1 - c[1])), max(c[2], G - 1 - c[2]));
-    DistBest best{__int_as_float(0x7f800000), 0.f, 0.f, 0x7fffffff};
+    DistBest best{tri_inf(), 0.f, 0.f, 0x7fffffff};
     for (int r = 0; r <= rmax; ++r) {
         const int z0 = max(c[0] - r, 0), z1 = min(c[0] + r, G - 1);
         const int y0 = max(c[1] - r, 0), y1 = min(c[1] + r, G - 1);
@@ -299,11 +266,13 @@ __global__ __launch_bounds__(DIST_BLOCK) void k_dist_query(const float* __restri
 #pragma nounroll
                 for (int sp = 0; sp < 2; ++sp) {  // one loop, so dist_closest has one call site and one instruction stream
                     if (s0[sp] < 0 || s1[sp] > G - 1 || s0[sp] > s1[sp]) continue;
-                    const int kb = max(cell_ptr[row + s0[sp]], 0), ke = min(cell_ptr[row + s1[sp] + 1], M);
+                    int kb, ke;
+                    tri_rows(grid, row + s0[sp], row + s1[sp], kb, ke);
                     for (int k = kb; k < ke; ++k) {
-                        const int f = cell_tri[k];
-                        if ((unsigned)f >= (unsigned)T) continue;
-                        const float4 r0 = rec[(size_t)f * 3], r1 = rec[(size_t)f * 3 + 1], r2 = rec[(size_t)f * 3 + 2];
+                        const int f = grid.cell_tri[k];
+                        if (!tri_face_ok(grid, f)) continue;
+                        const float4 r0 = grid.rec[(size_t)f * 3], r1 = grid.rec[(size_t)f * 3 + 1],
+                                     r2 = grid.rec[(size_t)f * 3 + 2];
                         const float ta[3] = {r0.x, r0.y, r0.z}, tb[3] = {r1.x, r1.y, r1.z}, tc[3] = {r2.x, r2.y, r2.z};
                         const DistHit hit = dist_closest(p, ta, tb, tc);
                         if (hit.d2 < best.d2 || (hit.d2 == best.d2 && f < best.f)) {
@@ -377,23 +346,13 @@ __global__ __launch_bounds__(DIST_BLOCK) void k_dist_bwd(const float* __restrict
 // ---------------------------------------------------------------------------------------------------------------
 #define DIST_SAMPLE_MAX_K 131072  // a face beyond this has more samples than TT_DIST_MAX_SAMPLES by itself
 
-__device__ __forceinline__ void dist_face_corners(const float* __restrict__ v_pos, const int* __restrict__ tri, int V,
-                                                  int f, float p[3][3]) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const unsigned i = min((unsigned)tri[(size_t)f * 3 + k], (unsigned)(V - 1));
-#pragma unroll
-        for (int a = 0; a < 3; ++a) p[k][a] = v_pos[(size_t)i * 3 + a];
-    }
-}
-
 // k_f = max(1, ceil(L_f / spacing)), L_f the fp32 longest edge: every product and sum rounded on its own
-__device__ __forceinline__ int dist_face_k(const float p[3][3], float spacing) {
+__device__ __forceinline__ int dist_face_k(const float4 p[3], float spacing) {
     float l2 = 0.f;
 #pragma unroll
     for (int e = 0; e < 3; ++e) {
         const int j = (e + 1) % 3;
-        const float x = __fsub_rn(p[j][0], p[e][0]), y = __fsub_rn(p[j][1], p[e][1]), z = __fsub_rn(p[j][2], p[e][2]);
+        const float x = __fsub_rn(p[j].x, p[e].x), y = __fsub_rn(p[j].y, p[e].y), z = __fsub_rn(p[j].z, p[e].z);
         l2 = fmaxf(l2, __fadd_rn(__fadd_rn(__fmul_rn(x, x), __fmul_rn(y, y)), __fmul_rn(z, z)));
     }
     const float k = ceilf(__fdiv_rn(__fsqrt_rn(l2), spacing));
@@ -405,8 +364,8 @@ __global__ __launch_bounds__(DIST_BLOCK) void k_dist_sample_count(const float* _
                                                                   float spacing, long long* __restrict__ cnt) {
     const int f = blockIdx.x * DIST_BLOCK + threadIdx.x;
     if (f >= T) return;
-    float p[3][3];
-    dist_face_corners(v_pos, tri, V, f, p);
+    float4 p[3];
+    tri_record(v_pos, tri, V, f, p);
     const long long k = dist_face_k(p, spacing);
     cnt[f] = (k + 1) * (k + 2) / 2;
 }
@@ -425,8 +384,8 @@ __global__ __launch_bounds__(DIST_BLOCK) void k_dist_sample_emit(const float* __
         if (offs[mid] <= (long long)s) lo = mid; else hi = mid - 1;
     }
     const int f = lo;
-    float p[3][3];
-    dist_face_corners(v_pos, tri, V, f, p);
+    float4 p[3];
+    tri_record(v_pos, tri, V, f, p);
     const int k = dist_face_k(p, spacing);
     const long long m = min(max((long long)s - offs[f], 0ll), ((long long)k + 1) * (k + 2) / 2 - 1);
     // row i starts at i (k + 1) - i (i - 1) / 2 and holds j = 0 .. k - i
@@ -437,39 +396,31 @@ __global__ __launch_bounds__(DIST_BLOCK) void k_dist_sample_emit(const float* __
     for (int it = 0; it < 2 && i > 0 && (long long)i * (k + 1) - (long long)i * (i - 1) / 2 > m; ++it) --i;
     const int j = (int)(m - ((long long)i * (k + 1) - (long long)i * (i - 1) / 2));
     const float fi = (float)i / (float)k, fj = (float)j / (float)k;
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-        out[(size_t)s * 3 + a] = p[0][a] + fi * (p[1][a] - p[0][a]) + fj * (p[2][a] - p[0][a]);
+    out[(size_t)s * 3] = p[0].x + fi * (p[1].x - p[0].x) + fj * (p[2].x - p[0].x);
+    out[(size_t)s * 3 + 1] = p[0].y + fi * (p[1].y - p[0].y) + fj * (p[2].y - p[0].y);
+    out[(size_t)s * 3 + 2] = p[0].z + fi * (p[1].z - p[0].z) + fj * (p[2].z - p[0].z);
     out_face[s] = f;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------------------------
-static bool dist_finite(double x) { return x >= -1e300 && x <= 1e300; }
-static bool dist_mesh_ok(int32_t V, int32_t T) {
-    return V >= 1 && T >= 1 && V <= TT_MESH_MAX_ITEMS && T <= TT_MESH_MAX_ITEMS;
-}
-// ext = 0 (a mesh without extent) is a grid whose every point and triangle lands in cell 0: h = inv_h = 0
-static bool dist_grid_ok(int32_t G, float lo_x, float lo_y, float lo_z, float ext, float h, float inv_h) {
-    return G >= 1 && G <= TT_DIST_MAX_GRID && dist_finite(lo_x) && dist_finite(lo_y) && dist_finite(lo_z) &&
-           dist_finite(ext) && dist_finite(h) && dist_finite(inv_h) && ext >= 0.f && h >= 0.f && inv_h >= 0.f;
-}
-static long long dist_cells(int32_t G) { return (long long)G * G * G; }
+static long long dist_grid_size(int32_t G) { return (long long)G * G * G; }
 
 extern "C" int64_t tt_dist_workspace_bytes(int32_t grid) {
     if (grid < 1 || grid > TT_DIST_MAX_GRID) return TT_ERR_BAD_ARG;
-    return dist_layout(nullptr, dist_cells(grid)).bytes;
+    return dist_layout(nullptr, dist_grid_size(grid)).bytes;
 }
 
 extern "C" int tt_dist_build_count(const float* v_pos, const int32_t* t_pos_idx, int32_t V, int32_t T, int32_t grid,
                                    float lo_x, float lo_y, float lo_z, float ext, float inv_h, void* workspace,
                                    float* records, int32_t* cell_ptr, int64_t* out_total, void* stream) {
-    if (!dist_mesh_ok(V, T) || !dist_grid_ok(grid, lo_x, lo_y, lo_z, ext, 0.f, inv_h)) return TT_ERR_BAD_ARG;
+    TriCube g;
+    if (!tri_mesh_ok(V, T) || !tri_cube(grid, TT_DIST_MAX_GRID, lo_x, lo_y, lo_z, ext, 0.f, inv_h, &g))
+        return TT_ERR_BAD_ARG;
     if (!v_pos || !t_pos_idx || !workspace || !records || !cell_ptr || !out_total) return TT_ERR_BAD_ARG;
-    const long long cells = dist_cells(grid);
+    const long long cells = dist_grid_size(grid);
     const DistWs w = dist_layout(workspace, cells).w;
-    const DistGrid g{{lo_x, lo_y, lo_z}, ext, 0.f, inv_h, (int)grid};
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_dist_zero, dim3(tt_grid(cells + 1)), dim3(DIST_BLOCK), 0, s, (int*)cell_ptr, cells + 1,
                        w.cursor, cells, (unsigned long long*)out_total);
@@ -482,11 +433,11 @@ extern "C" int tt_dist_build_count(const float* v_pos, const int32_t* t_pos_idx,
 extern "C" int tt_dist_build_fill(const float* records, int32_t T, int32_t grid, float lo_x, float lo_y, float lo_z,
                                   float ext, float inv_h, void* workspace, const int32_t* cell_ptr, int32_t M,
                                   int32_t* cell_tri, void* stream) {
-    if (T < 1 || T > TT_MESH_MAX_ITEMS || M < 1 || !dist_grid_ok(grid, lo_x, lo_y, lo_z, ext, 0.f, inv_h))
+    TriCube g;
+    if (!tri_count_ok(T) || M < 1 || !tri_cube(grid, TT_DIST_MAX_GRID, lo_x, lo_y, lo_z, ext, 0.f, inv_h, &g))
         return TT_ERR_BAD_ARG;
     if (!records || !workspace || !cell_ptr || !cell_tri) return TT_ERR_BAD_ARG;
-    const DistWs w = dist_layout(workspace, dist_cells(grid)).w;
-    const DistGrid g{{lo_x, lo_y, lo_z}, ext, 0.f, inv_h, (int)grid};
+    const DistWs w = dist_layout(workspace, dist_grid_size(grid)).w;
     hipLaunchKernelGGL(k_dist_fill, dim3(tt_grid(T)), dim3(DIST_BLOCK), 0, (hipStream_t)stream,
                        (const float4*)records, (int)T, g, (const int*)cell_ptr, w.cursor, (int)M, (int*)cell_tri);
     return tt_check_launch();
@@ -494,10 +445,11 @@ extern "C" int tt_dist_build_fill(const float* records, int32_t T, int32_t grid,
 
 extern "C" int tt_dist_keys(const float* points, int32_t N, int32_t grid, float lo_x, float lo_y, float lo_z, float ext,
                             float inv_h, int64_t* keys, void* stream) {
-    if (N < 0 || N > TT_MESH_MAX_ITEMS || !dist_grid_ok(grid, lo_x, lo_y, lo_z, ext, 0.f, inv_h)) return TT_ERR_BAD_ARG;
+    TriCube g;
+    if (!tri_items_ok(N) || !tri_cube(grid, TT_DIST_MAX_GRID, lo_x, lo_y, lo_z, ext, 0.f, inv_h, &g))
+        return TT_ERR_BAD_ARG;
     if (N == 0) return TT_OK;
     if (!points || !keys) return TT_ERR_BAD_ARG;
-    const DistGrid g{{lo_x, lo_y, lo_z}, ext, 0.f, inv_h, (int)grid};
     hipLaunchKernelGGL(k_dist_keys, dim3(tt_grid(N)), dim3(DIST_BLOCK), 0, (hipStream_t)stream, points, (int)N, g,
                        (long long*)keys);
     return tt_check_launch();
@@ -507,22 +459,20 @@ extern "C" int tt_dist_query(const float* points, const int64_t* order, int32_t 
                              const int32_t* cell_ptr, const int32_t* cell_tri, int32_t T, int32_t M, int32_t grid,
                              float lo_x, float lo_y, float lo_z, float ext, float h, float inv_h, float* d2,
                              int32_t* face, float* bary, void* stream) {
-    if (N < 0 || N > TT_MESH_MAX_ITEMS || T < 1 || T > TT_MESH_MAX_ITEMS || M < 1 ||
-        !dist_grid_ok(grid, lo_x, lo_y, lo_z, ext, h, inv_h))
+    TriGridView g;
+    if (!tri_view(N, records, cell_ptr, cell_tri, T, M, grid, lo_x, lo_y, lo_z, ext, h, inv_h, &g))
         return TT_ERR_BAD_ARG;
     if (N == 0) return TT_OK;
-    if (!points || !records || !cell_ptr || !cell_tri || !d2 || !face || !bary) return TT_ERR_BAD_ARG;
-    const DistGrid g{{lo_x, lo_y, lo_z}, ext, h, inv_h, (int)grid};
+    if (!points || !d2 || !face || !bary) return TT_ERR_BAD_ARG;
     hipLaunchKernelGGL(k_dist_query, dim3(tt_grid(N)), dim3(DIST_BLOCK), 0, (hipStream_t)stream, points,
-                       (const long long*)order, (int)N, (const float4*)records, (const int*)cell_ptr,
-                       (const int*)cell_tri, (int)T, (int)M, g, d2, (int*)face, bary);
+                       (const long long*)order, (int)N, g, d2, (int*)face, bary);
     return tt_check_launch();
 }
 
 extern "C" int tt_dist_bwd(const float* points, const float* v_pos, const int32_t* t_pos_idx, const int32_t* face,
                            const float* bary, const float* g_d2, int32_t N, int32_t V, int32_t T, float* grad_points,
                            float* grad_v_pos, void* stream) {
-    if (N < 0 || N > TT_MESH_MAX_ITEMS || !dist_mesh_ok(V, T)) return TT_ERR_BAD_ARG;
+    if (!tri_items_ok(N) || !tri_mesh_ok(V, T)) return TT_ERR_BAD_ARG;
     if (N == 0) return TT_OK;
     if (!points || !v_pos || !t_pos_idx || !face || !bary || !g_d2 || (!grad_points && !grad_v_pos))
         return TT_ERR_BAD_ARG;
@@ -533,7 +483,7 @@ extern "C" int tt_dist_bwd(const float* points, const float* v_pos, const int32_
 }
 
 extern "C" int64_t tt_dist_sample_workspace_bytes(int32_t T) {
-    if (T < 1 || T > TT_MESH_MAX_ITEMS) return TT_ERR_BAD_ARG;
+    if (!tri_count_ok(T)) return TT_ERR_BAD_ARG;
     TtCarver c{nullptr};
     c.take<long long>(tt_xscan_blocks(T) + 1);
     return c.bytes();
@@ -541,7 +491,7 @@ extern "C" int64_t tt_dist_sample_workspace_bytes(int32_t T) {
 
 extern "C" int tt_dist_sample_count(const float* v_pos, const int32_t* t_pos_idx, int32_t V, int32_t T, float spacing,
                                     void* workspace, int64_t* offsets, void* stream) {
-    if (!dist_mesh_ok(V, T) || !dist_finite(spacing) || !(spacing > 0.f)) return TT_ERR_BAD_ARG;
+    if (!tri_mesh_ok(V, T) || !tri_finite(spacing) || !(spacing > 0.f)) return TT_ERR_BAD_ARG;
     if (!v_pos || !t_pos_idx || !workspace || !offsets) return TT_ERR_BAD_ARG;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_dist_sample_count, dim3(tt_grid(T)), dim3(DIST_BLOCK), 0, s, v_pos, (const int*)t_pos_idx,
@@ -553,7 +503,7 @@ extern "C" int tt_dist_sample_count(const float* v_pos, const int32_t* t_pos_idx
 
 extern "C" int tt_dist_sample_emit(const float* v_pos, const int32_t* t_pos_idx, const int64_t* offsets, int32_t V,
                                    int32_t T, float spacing, int32_t S, float* points, int32_t* face, void* stream) {
-    if (!dist_mesh_ok(V, T) || !dist_finite(spacing) || !(spacing > 0.f) || S < 1 || S > TT_DIST_MAX_SAMPLES)
+    if (!tri_mesh_ok(V, T) || !tri_finite(spacing) || !(spacing > 0.f) || S < 1 || S > TT_DIST_MAX_SAMPLES)
         return TT_ERR_BAD_ARG;
     if (!v_pos || !t_pos_idx || !offsets || !points || !face) return TT_ERR_BAD_ARG;
     hipLaunchKernelGGL(k_dist_sample_emit, dim3(tt_grid(S)), dim3(DIST_BLOCK), 0, (hipStream_t)stream, v_pos,

@@ -10,10 +10,12 @@
 // not antisymmetric, and the two triangles of an edge must see the same magnitude.  __fmul_rn / __fsub_rn do not see to
 // that: they are plain operators in a header compiled with contraction allowed, which the compiler fuses after
 // inlining, and differently in each kernel.  So contraction is switched off for this whole file and the operations whose
-// order the contract names go through ray_mul / ray_sub / ray_add below, compiled under that setting.
+// order the contract names go through ray_mul / ray_sub / ray_add below, compiled under that setting.  The grid itself
+// (the cube, its cell rule, the view of the tables, the `order` lookup, the argument checks) is tt_trigrid.h, the one
+// the triangles were binned with; nothing there depends on this file's contraction setting.
 #include <math.h>
 
-#include "tt_host.h"
+#include "tt_trigrid.h"
 
 #pragma clang fp contract(off)
 __device__ __forceinline__ float ray_mul(float x, float y) { return x * y; }
@@ -25,18 +27,8 @@ __device__ __forceinline__ float ray_add(float x, float y) { return x + y; }
 #define RAY_FLT_MIN 1.17549435e-38f
 #define RAY_FLT_MAX 3.4028235e38f
 
-struct RayGrid {  // the TriangleGrid of tt_dist.hip
-    float lo[3], ext, h, inv_h;
-    int G;
-};
-
-__device__ __forceinline__ float ray_inf() { return __int_as_float(0x7f800000); }
-__device__ __forceinline__ float ray_nan() { return __int_as_float(0x7fc00000); }
 // component k of (x, y, z) by selects: a register array indexed at run time would live in scratch
 __device__ __forceinline__ float ray_sel(float x, float y, float z, int k) { return k == 0 ? x : (k == 1 ? y : z); }
-__device__ __forceinline__ bool ray_finite3(float x, float y, float z) {
-    return fabsf(x) <= RAY_FLT_MAX && fabsf(y) <= RAY_FLT_MAX && fabsf(z) <= RAY_FLT_MAX;  // NaN: false
-}
 // argmax |d|, the lowest index at equal magnitude
 __device__ __forceinline__ int ray_major(float dx, float dy, float dz) {
     int k = 0;
@@ -50,7 +42,7 @@ __device__ __forceinline__ int ray_major(float dx, float dy, float dz) {
 }
 // a ray the kernels serve: finite, and a direction whose largest component is a normal fp32 number (1 / d is finite)
 __device__ __forceinline__ bool ray_usable(float ox, float oy, float oz, float dx, float dy, float dz) {
-    return ray_finite3(ox, oy, oz) && ray_finite3(dx, dy, dz) &&
+    return tri_finite3(ox, oy, oz) && tri_finite3(dx, dy, dz) &&
            fmaxf(fabsf(dx), fmaxf(fabsf(dy), fabsf(dz))) >= RAY_FLT_MIN;
 }
 
@@ -129,12 +121,8 @@ __device__ __forceinline__ bool ray_pair(const RayFrame& fr, float ox, float oy,
 // ---------------------------------------------------------------------------------------------------------------
 // the walk: slices of cells along the dominant axis
 // ---------------------------------------------------------------------------------------------------------------
-// The grid's cell(): the value of dist_cell (tt_dist.hip) for every x it is defined for, with the clamp taken before
-// the conversion so that +-inf and NaN (an overflowing ray) land on a cell too.  Monotone in x.
-__device__ __forceinline__ int ray_cell(float x, float lo, float inv_h, int G) {
-    const float c = floorf(ray_mul(ray_sub(x, lo), inv_h));
-    return (int)fminf(fmaxf(c, 0.f), (float)(G - 1));  // fmaxf(NaN, 0) = 0
-}
+// The grid's cell() is tri_cell (tt_trigrid.h), the function the triangles were binned with: monotone in x, and defined
+// for +-inf and NaN (an overflowing ray), which land on a cell too.
 // x - (2^-16 |x| + pad) and x + (...).  inf - inf is NaN here and stays: every use is an fmaxf / fminf, which drops it,
 // or a compare, which is false -- both read it as "open", -inf below and +inf above (and no select on a NaN test joined
 // with another condition is formed: tools/mask_hazard_lint.py)
@@ -149,10 +137,9 @@ struct RayBest {
 // ANY: return at the first accepted pair.  Else best = the lexicographic minimum of (t, f).  Returns "some pair hit".
 template <bool ANY>
 __device__ __forceinline__ bool ray_walk(float ox, float oy, float oz, float dx, float dy, float dz, float t_max,
-                                         const float4* __restrict__ rec, const int* __restrict__ cell_ptr,
-                                         const int* __restrict__ cell_tri, int T, int M, const RayGrid& g,
-                                         RayBest& best) {
+                                         const TriGridView& grid, RayBest& best) {
     const RayFrame fr = ray_frame(dx, dy, dz);
+    const TriCube& g = grid.cube;
     const int G = g.G;
     const float o[3] = {ox, oy, oz}, d[3] = {dx, dy, dz};
     // tol = 2^-16 (ext + max |o - centre| + max |centre|)
@@ -193,28 +180,29 @@ __device__ __forceinline__ bool ray_walk(float ox, float oy, float oz, float dx,
         const float q0 = la + (float)k * g.h, q1 = la + (float)(k + 1) * g.h;
         const float tq0 = __fdiv_rn(q0 - oa, da), tq1 = __fdiv_rn(q1 - oa, da);
         float s = ray_below(up ? tq0 : tq1, tol_t), e = ray_above(up ? tq1 : tq0, tol_t);
-        if (j == 0) s = -ray_inf();
-        if (j == G - 1) e = ray_inf();
+        if (j == 0) s = -tri_inf();
+        if (j == G - 1) e = tri_inf();
         if (s > t_hi) break;  // s does not decrease with j: every later slice is empty as well
         const float t0 = fmaxf(s, t_lo), t1 = fminf(e, t_hi);
         if (t0 <= t1) {
             const float xu0 = du == 0.f ? ou : ou + t0 * du, xu1 = du == 0.f ? ou : ou + t1 * du;
             const float xv0 = dv == 0.f ? ov : ov + t0 * dv, xv1 = dv == 0.f ? ov : ov + t1 * dv;
-            const int u0 = ray_cell(fminf(xu0, xu1) - tol, lu, g.inv_h, G);
-            const int u1 = max(u0, ray_cell(fmaxf(xu0, xu1) + tol, lu, g.inv_h, G));
-            const int v0 = ray_cell(fminf(xv0, xv1) - tol, lv, g.inv_h, G);
-            const int v1 = max(v0, ray_cell(fmaxf(xv0, xv1) + tol, lv, g.inv_h, G));
+            const int u0 = tri_cell(fminf(xu0, xu1) - tol, lu, g.inv_h, G);
+            const int u1 = max(u0, tri_cell(fmaxf(xu0, xu1) + tol, lu, g.inv_h, G));
+            const int v0 = tri_cell(fminf(xv0, xv1) - tol, lv, g.inv_h, G);
+            const int v1 = max(v0, tri_cell(fmaxf(xv0, xv1) + tol, lv, g.inv_h, G));
             for (int iu = u0; iu <= u1; ++iu) {
                 for (int iv = v0; iv <= v1; iv = row ? v1 + 1 : iv + 1) {
                     const int c_first = k * sa + iu * su + iv * sv;  // all three coordinates are in [0, G)
                     const int c_last = row ? c_first + (v1 - v0) : c_first;
-                    const int pb = max(cell_ptr[c_first], 0), pe = min(cell_ptr[c_last + 1], M);
+                    int pb, pe;
+                    tri_rows(grid, c_first, c_last, pb, pe);
                     for (int p = pb; p < pe; ++p) {
-                        const int f = cell_tri[p];
-                        if ((unsigned)f >= (unsigned)T) continue;
+                        const int f = grid.cell_tri[p];
+                        if (!tri_face_ok(grid, f)) continue;
                         RayHit hit;
-                        if (!ray_pair(fr, ox, oy, oz, rec[(size_t)f * 3], rec[(size_t)f * 3 + 1],
-                                      rec[(size_t)f * 3 + 2], t_max, hit))
+                        if (!ray_pair(fr, ox, oy, oz, grid.rec[(size_t)f * 3], grid.rec[(size_t)f * 3 + 1],
+                                      grid.rec[(size_t)f * 3 + 2], t_max, hit))
                             continue;
                         if (ANY) return true;
                         any = true;
@@ -244,25 +232,19 @@ __device__ __forceinline__ bool ray_walk(float ox, float oy, float oz, float dx,
 __global__ __launch_bounds__(RAY_BLOCK) void k_ray_cast(const float* __restrict__ origins,
                                                         const float* __restrict__ dirs,
                                                         const long long* __restrict__ order, int N, float t_max,
-                                                        const float4* __restrict__ rec,
-                                                        const int* __restrict__ cell_ptr,
-                                                        const int* __restrict__ cell_tri, int T, int M, RayGrid g,
-                                                        float* __restrict__ out_t, int* __restrict__ out_face,
-                                                        float* __restrict__ out_bary) {
+                                                        TriGridView grid, float* __restrict__ out_t,
+                                                        int* __restrict__ out_face, float* __restrict__ out_bary) {
     const int th = blockIdx.x * RAY_BLOCK + threadIdx.x;
     if (th >= N) return;
-    long long i = th;
-    if (order) {
-        i = order[th];
-        if ((unsigned long long)i >= (unsigned long long)N) return;
-    }
+    const long long i = tri_row(order, th, N);
+    if (i < 0) return;
     const float ox = origins[(size_t)i * 3], oy = origins[(size_t)i * 3 + 1], oz = origins[(size_t)i * 3 + 2];
     const float dx = dirs[(size_t)i * 3], dy = dirs[(size_t)i * 3 + 1], dz = dirs[(size_t)i * 3 + 2];
-    RayBest best{ray_inf(), 0.f, 0.f, 0.f, 0x7fffffff};
+    RayBest best{tri_inf(), 0.f, 0.f, 0.f, 0x7fffffff};
     if (!ray_usable(ox, oy, oz, dx, dy, dz)) {  // before the walk: no loop depends on such a row
-        best.t = ray_nan();
+        best.t = tri_nan();
     } else {
-        ray_walk<false>(ox, oy, oz, dx, dy, dz, t_max, rec, cell_ptr, cell_tri, T, M, g, best);
+        ray_walk<false>(ox, oy, oz, dx, dy, dz, t_max, grid, best);
     }
     out_t[i] = best.t;
     out_face[i] = best.f == 0x7fffffff ? -1 : best.f;
@@ -274,23 +256,17 @@ __global__ __launch_bounds__(RAY_BLOCK) void k_ray_cast(const float* __restrict_
 __global__ __launch_bounds__(RAY_BLOCK) void k_ray_any(const float* __restrict__ origins,
                                                        const float* __restrict__ dirs,
                                                        const long long* __restrict__ order, int N, float t_max,
-                                                       const float4* __restrict__ rec,
-                                                       const int* __restrict__ cell_ptr,
-                                                       const int* __restrict__ cell_tri, int T, int M, RayGrid g,
-                                                       unsigned char* __restrict__ out_hit) {
+                                                       TriGridView grid, unsigned char* __restrict__ out_hit) {
     const int th = blockIdx.x * RAY_BLOCK + threadIdx.x;
     if (th >= N) return;
-    long long i = th;
-    if (order) {
-        i = order[th];
-        if ((unsigned long long)i >= (unsigned long long)N) return;
-    }
+    const long long i = tri_row(order, th, N);
+    if (i < 0) return;
     const float ox = origins[(size_t)i * 3], oy = origins[(size_t)i * 3 + 1], oz = origins[(size_t)i * 3 + 2];
     const float dx = dirs[(size_t)i * 3], dy = dirs[(size_t)i * 3 + 1], dz = dirs[(size_t)i * 3 + 2];
-    RayBest best{ray_inf(), 0.f, 0.f, 0.f, 0x7fffffff};
+    RayBest best{tri_inf(), 0.f, 0.f, 0.f, 0x7fffffff};
     bool hit = false;
     if (ray_usable(ox, oy, oz, dx, dy, dz))
-        hit = ray_walk<true>(ox, oy, oz, dx, dy, dz, t_max, rec, cell_ptr, cell_tri, T, M, g, best);
+        hit = ray_walk<true>(ox, oy, oz, dx, dy, dz, t_max, grid, best);
     out_hit[i] = hit ? 1 : 0;
 }
 
@@ -327,10 +303,7 @@ __global__ __launch_bounds__(RAY_BLOCK) void k_ray_ao_init(const float* __restri
 __global__ __launch_bounds__(RAY_BLOCK) void k_ray_ao(const float* __restrict__ points,
                                                       const float* __restrict__ normals,
                                                       const float* __restrict__ dirs_local, int N, int K, float bias,
-                                                      float max_distance, const float4* __restrict__ rec,
-                                                      const int* __restrict__ cell_ptr,
-                                                      const int* __restrict__ cell_tri, int T, int M, RayGrid g,
-                                                      int* __restrict__ hits) {
+                                                      float max_distance, TriGridView grid, int* __restrict__ hits) {
     const long long r = (long long)blockIdx.x * RAY_BLOCK + threadIdx.x;  // ray r = (point r / K, direction r % K)
     if (r >= (long long)N * K) return;
     const long long i = r / K;
@@ -350,34 +323,26 @@ __global__ __launch_bounds__(RAY_BLOCK) void k_ray_ao(const float* __restrict__ 
     const float dz = ray_add(ray_add(ray_mul(x, tz), ray_mul(y, bz)), ray_mul(z, n[2]));
     const float ox = ray_add(p[0], ray_mul(bias, n[0])), oy = ray_add(p[1], ray_mul(bias, n[1])),
                 oz = ray_add(p[2], ray_mul(bias, n[2]));
-    RayBest best{ray_inf(), 0.f, 0.f, 0.f, 0x7fffffff};
+    RayBest best{tri_inf(), 0.f, 0.f, 0.f, 0x7fffffff};
     if (!ray_usable(ox, oy, oz, dx, dy, dz)) return;  // such a ray hits nothing
-    if (ray_walk<true>(ox, oy, oz, dx, dy, dz, max_distance, rec, cell_ptr, cell_tri, T, M, g, best))
+    if (ray_walk<true>(ox, oy, oz, dx, dy, dz, max_distance, grid, best))
         atomicAdd(hits + i, 1);  // an integer count: the order of arrival cannot show
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------------------------
-static bool ray_finite(double x) { return x >= -1e300 && x <= 1e300; }
-static bool ray_grid_ok(int32_t N, int32_t T, int32_t M, int32_t G, float lo_x, float lo_y, float lo_z, float ext, float h,
-                        float inv_h) {
-    return N >= 0 && N <= TT_MESH_MAX_ITEMS && T >= 1 && T <= TT_MESH_MAX_ITEMS && M >= 1 && G >= 1 &&
-           G <= TT_DIST_MAX_GRID && ray_finite(lo_x) && ray_finite(lo_y) && ray_finite(lo_z) && ray_finite(ext) &&
-           ray_finite(h) && ray_finite(inv_h) && ext >= 0.f && h >= 0.f && inv_h >= 0.f;
-}
-
 extern "C" int tt_ray_cast(const float* origins, const float* dirs, const int64_t* order, int32_t N, float t_max,
                            const float* records, const int32_t* cell_ptr, const int32_t* cell_tri, int32_t T, int32_t M,
                            int32_t grid, float lo_x, float lo_y, float lo_z, float ext, float h, float inv_h, float* t,
                            int32_t* face, float* bary, void* stream) {
-    if (!ray_grid_ok(N, T, M, grid, lo_x, lo_y, lo_z, ext, h, inv_h) || !(t_max >= 0.f)) return TT_ERR_BAD_ARG;
+    TriGridView g;
+    if (!tri_view(N, records, cell_ptr, cell_tri, T, M, grid, lo_x, lo_y, lo_z, ext, h, inv_h, &g) || !(t_max >= 0.f))
+        return TT_ERR_BAD_ARG;
     if (N == 0) return TT_OK;
-    if (!origins || !dirs || !records || !cell_ptr || !cell_tri || !t || !face || !bary) return TT_ERR_BAD_ARG;
-    const RayGrid g{{lo_x, lo_y, lo_z}, ext, h, inv_h, (int)grid};
+    if (!origins || !dirs || !t || !face || !bary) return TT_ERR_BAD_ARG;
     hipLaunchKernelGGL(k_ray_cast, dim3(tt_grid(N)), dim3(RAY_BLOCK), 0, (hipStream_t)stream, origins, dirs,
-                       (const long long*)order, (int)N, t_max, (const float4*)records, (const int*)cell_ptr,
-                       (const int*)cell_tri, (int)T, (int)M, g, t, (int*)face, bary);
+                       (const long long*)order, (int)N, t_max, g, t, (int*)face, bary);
     return tt_check_launch();
 }
 
@@ -385,13 +350,13 @@ extern "C" int tt_ray_any(const float* origins, const float* dirs, const int64_t
                           const float* records, const int32_t* cell_ptr, const int32_t* cell_tri, int32_t T, int32_t M,
                           int32_t grid, float lo_x, float lo_y, float lo_z, float ext, float h, float inv_h,
                           uint8_t* hit, void* stream) {
-    if (!ray_grid_ok(N, T, M, grid, lo_x, lo_y, lo_z, ext, h, inv_h) || !(t_max >= 0.f)) return TT_ERR_BAD_ARG;
+    TriGridView g;
+    if (!tri_view(N, records, cell_ptr, cell_tri, T, M, grid, lo_x, lo_y, lo_z, ext, h, inv_h, &g) || !(t_max >= 0.f))
+        return TT_ERR_BAD_ARG;
     if (N == 0) return TT_OK;
-    if (!origins || !dirs || !records || !cell_ptr || !cell_tri || !hit) return TT_ERR_BAD_ARG;
-    const RayGrid g{{lo_x, lo_y, lo_z}, ext, h, inv_h, (int)grid};
+    if (!origins || !dirs || !hit) return TT_ERR_BAD_ARG;
     hipLaunchKernelGGL(k_ray_any, dim3(tt_grid(N)), dim3(RAY_BLOCK), 0, (hipStream_t)stream, origins, dirs,
-                       (const long long*)order, (int)N, t_max, (const float4*)records, (const int*)cell_ptr,
-                       (const int*)cell_tri, (int)T, (int)M, g, (unsigned char*)hit);
+                       (const long long*)order, (int)N, t_max, g, (unsigned char*)hit);
     return tt_check_launch();
 }
 
@@ -399,16 +364,15 @@ extern "C" int tt_ray_ao(const float* points, const float* normals, const float*
                          float bias, float max_distance, const float* records, const int32_t* cell_ptr,
                          const int32_t* cell_tri, int32_t T, int32_t M, int32_t grid, float lo_x, float lo_y,
                          float lo_z, float ext, float h, float inv_h, int32_t* hits, void* stream) {
-    if (!ray_grid_ok(N, T, M, grid, lo_x, lo_y, lo_z, ext, h, inv_h) || K < 1 || K > TT_RAY_MAX_DIRS ||
-        !ray_finite(bias) || !(max_distance >= 0.f))
+    TriGridView g;
+    if (!tri_view(N, records, cell_ptr, cell_tri, T, M, grid, lo_x, lo_y, lo_z, ext, h, inv_h, &g) || K < 1 ||
+        K > TT_RAY_MAX_DIRS || !tri_finite(bias) || !(max_distance >= 0.f))
         return TT_ERR_BAD_ARG;
     if (N == 0) return TT_OK;
-    if (!points || !normals || !dirs_local || !records || !cell_ptr || !cell_tri || !hits) return TT_ERR_BAD_ARG;
-    const RayGrid g{{lo_x, lo_y, lo_z}, ext, h, inv_h, (int)grid};
+    if (!points || !normals || !dirs_local || !hits) return TT_ERR_BAD_ARG;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_ray_ao_init, dim3(tt_grid(N)), dim3(RAY_BLOCK), 0, s, points, normals, (int)N, (int*)hits);
     hipLaunchKernelGGL(k_ray_ao, dim3(tt_grid((long long)N * K)), dim3(RAY_BLOCK), 0, s, points, normals, dirs_local,
-                       (int)N, (int)K, bias, max_distance, (const float4*)records, (const int*)cell_ptr,
-                       (const int*)cell_tri, (int)T, (int)M, g, (int*)hits);
+                       (int)N, (int)K, bias, max_distance, g, (int*)hits);
     return tt_check_launch();
 }

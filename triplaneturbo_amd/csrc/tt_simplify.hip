@@ -16,6 +16,7 @@
 //   k_simp_emit     vertices, faces, vertex_map
 // No float atomics; identical inputs give bit-identical outputs.
 #include "tt_compact.h"
+#include "tt_trigrid.h"
 
 #define SIMP_BLOCK TT_ITEM_BLOCK
 #define SIMP_WAVES (SIMP_BLOCK / 64)
@@ -57,12 +58,7 @@ struct SimpBox {
 // ---------------------------------------------------------------------------------------------------------------
 // cells and clusters
 // ---------------------------------------------------------------------------------------------------------------
-// subtract, then multiply, each rounded on its own (nothing here may contract into an FMA: tt_abi.h)
-__device__ __forceinline__ int simp_cell(float v, float lo, float inv_h, int G) {
-    const int c = (int)floorf(__fmul_rn(__fsub_rn(v, lo), inv_h));
-    return min(G - 1, max(0, c));
-}
-
+// a vertex's cell is tri_cell (tt_trigrid.h); nothing here may contract into an FMA (tt_abi.h)
 __device__ __forceinline__ void simp_centre(int key, const SimpBox& b, float ctr[3]) {
     const int c[3] = {key / (b.G * b.G), (key / b.G) % b.G, key % b.G};
 #pragma unroll
@@ -75,8 +71,8 @@ __global__ __launch_bounds__(SIMP_BLOCK) void k_simp_keys(const float* __restric
     if (i >= V) return;
     int c[3];
 #pragma unroll
-    for (int a = 0; a < 3; ++a) c[a] = simp_cell(v_pos[(size_t)i * 3 + a], b.lo[a], b.inv_h, b.G);
-    keys[i] = (long long)((c[0] * b.G + c[1]) * b.G + c[2]);
+    for (int a = 0; a < 3; ++a) c[a] = tri_cell(v_pos[(size_t)i * 3 + a], b.lo[a], b.inv_h, b.G);
+    keys[i] = (long long)tri_key(c, b.G);
 }
 
 __device__ __forceinline__ int simp_start(const long long* __restrict__ skeys, int i) {
@@ -316,11 +312,7 @@ __global__ __launch_bounds__(SIMP_BLOCK) void k_simp_emit(const float* __restric
 // ---------------------------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------------------------
-static bool simp_sizes_ok(int32_t V, int32_t T) {
-    return V >= 1 && T >= 1 && V <= TT_MESH_MAX_ITEMS && T <= TT_MESH_MAX_ITEMS;
-}
 static bool simp_grid_ok(int32_t G) { return G >= TT_SIMPLIFY_MIN_GRID && G <= TT_SIMPLIFY_MAX_GRID; }
-static bool simp_finite(double x) { return x >= -1e300 && x <= 1e300; }
 // C clusters of V vertices; more than TT_SIMPLIFY_MAX_CLUSTERS do not fit the face key
 static int simp_clusters_status(int32_t V, int32_t C) {
     if (C < 1 || C > V) return TT_ERR_BAD_ARG;
@@ -328,14 +320,14 @@ static int simp_clusters_status(int32_t V, int32_t C) {
 }
 
 extern "C" int64_t tt_simplify_workspace_bytes(int32_t V, int32_t T) {
-    if (!simp_sizes_ok(V, T)) return TT_ERR_BAD_ARG;
+    if (!tri_mesh_ok(V, T)) return TT_ERR_BAD_ARG;
     return simp_layout(nullptr, V, T).bytes;
 }
 
 extern "C" int tt_simplify_keys(const float* v_pos, int32_t V, int32_t grid, float lo_x, float lo_y, float lo_z,
                                 float inv_h, int64_t* keys, void* stream) {
-    if (V < 1 || V > TT_MESH_MAX_ITEMS || !simp_grid_ok(grid) || !v_pos || !keys) return TT_ERR_BAD_ARG;
-    if (!simp_finite(lo_x) || !simp_finite(lo_y) || !simp_finite(lo_z) || !simp_finite(inv_h) || !(inv_h > 0.f))
+    if (!tri_count_ok(V) || !simp_grid_ok(grid) || !v_pos || !keys) return TT_ERR_BAD_ARG;
+    if (!tri_finite(lo_x) || !tri_finite(lo_y) || !tri_finite(lo_z) || !tri_finite(inv_h) || !(inv_h > 0.f))
         return TT_ERR_BAD_ARG;
     const SimpBox b{{lo_x, lo_y, lo_z}, 0.f, inv_h, (int)grid};
     hipLaunchKernelGGL(k_simp_keys, dim3(tt_grid(V)), dim3(SIMP_BLOCK), 0, (hipStream_t)stream, v_pos, (int)V, b,
@@ -345,7 +337,7 @@ extern "C" int tt_simplify_keys(const float* v_pos, int32_t V, int32_t grid, flo
 
 extern "C" int tt_simplify_ranks(const int64_t* sorted_keys, const int64_t* perm, int32_t V, int32_t T, int32_t grid,
                                  void* workspace, int32_t* rank, int32_t* out_totals, void* stream) {
-    if (!simp_sizes_ok(V, T) || !simp_grid_ok(grid)) return TT_ERR_BAD_ARG;
+    if (!tri_mesh_ok(V, T) || !simp_grid_ok(grid)) return TT_ERR_BAD_ARG;
     if (!sorted_keys || !perm || !workspace || !rank || !out_totals) return TT_ERR_BAD_ARG;
     const SimpWs w = simp_layout(workspace, V, T).w;
     hipStream_t s = (hipStream_t)stream;
@@ -359,7 +351,7 @@ extern "C" int tt_simplify_ranks(const int64_t* sorted_keys, const int64_t* perm
 
 extern "C" int tt_simplify_pairs(const int32_t* t_pos_idx, const int32_t* rank, int32_t V, int32_t T, int32_t C,
                                  void* workspace, int64_t* pair_keys, void* stream) {
-    if (!simp_sizes_ok(V, T) || !t_pos_idx || !rank || !workspace || !pair_keys) return TT_ERR_BAD_ARG;
+    if (!tri_mesh_ok(V, T) || !t_pos_idx || !rank || !workspace || !pair_keys) return TT_ERR_BAD_ARG;
     if (const int st = simp_clusters_status(V, C)) return st;
     const SimpWs w = simp_layout(workspace, V, T).w;
     hipStream_t s = (hipStream_t)stream;
@@ -373,11 +365,11 @@ extern "C" int tt_simplify_solve(const float* v_pos, const int32_t* t_pos_idx, c
                                  const int64_t* perm, int32_t V, int32_t T, int32_t C, int32_t grid, float lo_x,
                                  float lo_y, float lo_z, float h, double lam, void* workspace, float* cluster_pos,
                                  void* stream) {
-    if (!simp_sizes_ok(V, T) || !simp_grid_ok(grid)) return TT_ERR_BAD_ARG;
+    if (!tri_mesh_ok(V, T) || !simp_grid_ok(grid)) return TT_ERR_BAD_ARG;
     if (!v_pos || !t_pos_idx || !sorted_pair_keys || !perm || !workspace || !cluster_pos) return TT_ERR_BAD_ARG;
-    if (!simp_finite(lo_x) || !simp_finite(lo_y) || !simp_finite(lo_z) || !simp_finite(h) || !(h > 0.f))
+    if (!tri_finite(lo_x) || !tri_finite(lo_y) || !tri_finite(lo_z) || !tri_finite(h) || !(h > 0.f))
         return TT_ERR_BAD_ARG;
-    if (!simp_finite(lam) || !(lam >= 0.0)) return TT_ERR_BAD_ARG;
+    if (!tri_finite(lam) || !(lam >= 0.0)) return TT_ERR_BAD_ARG;
     if (const int st = simp_clusters_status(V, C)) return st;
     const SimpWs w = simp_layout(workspace, V, T).w;
     const SimpBox b{{lo_x, lo_y, lo_z}, h, 0.f, (int)grid};
@@ -389,7 +381,7 @@ extern "C" int tt_simplify_solve(const float* v_pos, const int32_t* t_pos_idx, c
 
 extern "C" int tt_simplify_faces(const int32_t* t_pos_idx, const int32_t* rank, int32_t V, int32_t T, int32_t C,
                                  int64_t* face_keys, void* stream) {
-    if (!simp_sizes_ok(V, T) || !t_pos_idx || !rank || !face_keys) return TT_ERR_BAD_ARG;
+    if (!tri_mesh_ok(V, T) || !t_pos_idx || !rank || !face_keys) return TT_ERR_BAD_ARG;
     if (const int st = simp_clusters_status(V, C)) return st;
     hipLaunchKernelGGL(k_simp_faces, dim3(tt_grid(T)), dim3(SIMP_BLOCK), 0, (hipStream_t)stream,
                        (const int*)t_pos_idx, (const int*)rank, (int)V, (int)T, (int)C, (long long*)face_keys);
@@ -399,7 +391,7 @@ extern "C" int tt_simplify_faces(const int32_t* t_pos_idx, const int32_t* rank, 
 extern "C" int tt_simplify_emit_count(const int64_t* sorted_face_keys, const int64_t* face_perm,
                                       const int32_t* t_pos_idx, const int32_t* rank, int32_t V, int32_t T, int32_t C,
                                       void* workspace, int32_t* out_totals, void* stream) {
-    if (!simp_sizes_ok(V, T)) return TT_ERR_BAD_ARG;
+    if (!tri_mesh_ok(V, T)) return TT_ERR_BAD_ARG;
     if (!sorted_face_keys || !face_perm || !t_pos_idx || !rank || !workspace || !out_totals) return TT_ERR_BAD_ARG;
     if (const int st = simp_clusters_status(V, C)) return st;
     const SimpWs w = simp_layout(workspace, V, T).w;
@@ -415,7 +407,7 @@ extern "C" int tt_simplify_emit_count(const int64_t* sorted_face_keys, const int
 extern "C" int tt_simplify_emit(const float* cluster_pos, const int32_t* t_pos_idx, const int32_t* rank, int32_t V,
                                 int32_t T, int32_t C, void* workspace, float* v_out, int32_t* t_out,
                                 int32_t* vertex_map, void* stream) {
-    if (!simp_sizes_ok(V, T)) return TT_ERR_BAD_ARG;
+    if (!tri_mesh_ok(V, T)) return TT_ERR_BAD_ARG;
     if (!cluster_pos || !t_pos_idx || !rank || !workspace || !v_out || !t_out || !vertex_map) return TT_ERR_BAD_ARG;
     if (const int st = simp_clusters_status(V, C)) return st;
     const SimpWs w = simp_layout(workspace, V, T).w;

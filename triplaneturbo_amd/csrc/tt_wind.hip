@@ -1,7 +1,8 @@
 // tt_wind.hip -- generalized winding number of a triangle mesh: the exact sum and a Barnes-Hut (dipole) tree.
 // The contract (the pair, the exact answer, the tree, the stackless walk) is written in include/tt_abi.h, "winding number".
-//   k_wind_face_keys   48-byte record of every triangle (the layout of k_dist_build) and the Morton key of its centroid's
-//                      leaf cell; the host sorts (key, face) (stable) and gathers the records into that order
+//   k_wind_face_keys   48-byte record of every triangle (tri_record of tt_trigrid.h) and the Morton key of its centroid's
+//                      leaf cell (tri_cell of the cube with G = 2^L); the host sorts (key, face) (stable) and gathers
+//                      the records into that order
 //   k_wind_leaves      one thread per leaf: N, c, r over the leaf's faces in sorted order
 //   k_wind_up          one thread per node of a level, one launch per level: the eight children in child order
 //   k_wind_point_keys  Morton key of every point's leaf cell (the host's optional cell-order sort)
@@ -11,16 +12,11 @@
 // Sums run in a fixed order in double and there is no float atomic: every table and every answer is deterministic.
 #include <math.h>
 
-#include "tt_host.h"
 #include "tt_mask.h"
+#include "tt_trigrid.h"
 
 #define WIND_BLOCK TT_ITEM_BLOCK
 #define WIND_TILE WIND_BLOCK  // records per LDS tile of k_wind_exact: one per thread, 12 KB
-
-struct WindBox {
-    float lo[3], ext, inv_h;
-    int L;
-};
 
 __device__ __forceinline__ float wind_dot(const float x[3], const float y[3]) {
     return x[0] * y[0] + x[1] * y[1] + x[2] * y[2];
@@ -61,19 +57,10 @@ __device__ __forceinline__ float wind_pair(const float p[3], const float4 ra, co
     return w == w ? w : 0.f;
 }
 
-__device__ __forceinline__ bool wind_finite3(const float p[3]) {
-    return fabsf(p[0]) <= 3.4028235e38f && fabsf(p[1]) <= 3.4028235e38f && fabsf(p[2]) <= 3.4028235e38f;  // NaN: false
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // cells and keys
 // ---------------------------------------------------------------------------------------------------------------
-// the cell rule of the distance grid with G = 2^L: subtract, then multiply, each rounded on its own
-__device__ __forceinline__ int wind_cell(float x, float lo, float inv_h, int G) {
-    const int c = (int)floorf(__fmul_rn(__fsub_rn(x, lo), inv_h));
-    return min(G - 1, max(0, c));
-}
-
+// a leaf cell is tri_cell (tt_trigrid.h) of the cube with G = 2^L
 // bit b of (x, y, z) goes to bits 3b+2, 3b+1, 3b: child k = 4 x_bit + 2 y_bit + z_bit of its parent
 __device__ __forceinline__ unsigned wind_morton(const int c[3], int L) {
     unsigned key = 0;
@@ -83,40 +70,34 @@ __device__ __forceinline__ unsigned wind_morton(const int c[3], int L) {
 }
 
 __global__ __launch_bounds__(WIND_BLOCK) void k_wind_face_keys(const float* __restrict__ v_pos,
-                                                               const int* __restrict__ tri, int V, int T, WindBox g,
-                                                               float4* __restrict__ rec, long long* __restrict__ keys) {
+                                                               const int* __restrict__ tri, int V, int T, TriCube g,
+                                                               int L, float4* __restrict__ rec,
+                                                               long long* __restrict__ keys) {
     const int f = blockIdx.x * WIND_BLOCK + threadIdx.x;
     if (f >= T) return;
     float4 r[3];
+    tri_record(v_pos, tri, V, f, r);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const unsigned i = min((unsigned)tri[(size_t)f * 3 + k], (unsigned)(V - 1));  // the host checked the range
-        r[k] = make_float4(v_pos[(size_t)i * 3], v_pos[(size_t)i * 3 + 1], v_pos[(size_t)i * 3 + 2], 0.f);
-        rec[(size_t)f * 3 + k] = r[k];
-    }
+    for (int k = 0; k < 3; ++k) rec[(size_t)f * 3 + k] = r[k];
     const float third = 0.33333334f;
     const float cen[3] = {__fmul_rn(__fadd_rn(__fadd_rn(r[0].x, r[1].x), r[2].x), third),
                           __fmul_rn(__fadd_rn(__fadd_rn(r[0].y, r[1].y), r[2].y), third),
                           __fmul_rn(__fadd_rn(__fadd_rn(r[0].z, r[1].z), r[2].z), third)};
     int c[3];
 #pragma unroll
-    for (int a = 0; a < 3; ++a) c[a] = wind_cell(cen[a], g.lo[a], g.inv_h, 1 << g.L);
-    keys[f] = (long long)wind_morton(c, g.L);
+    for (int a = 0; a < 3; ++a) c[a] = tri_cell(cen[a], g.lo[a], g.inv_h, g.G);
+    keys[f] = (long long)wind_morton(c, L);
 }
 
-__global__ __launch_bounds__(WIND_BLOCK) void k_wind_point_keys(const float* __restrict__ points, int N, WindBox g,
-                                                                long long* __restrict__ keys) {
+__global__ __launch_bounds__(WIND_BLOCK) void k_wind_point_keys(const float* __restrict__ points, int N, TriCube g,
+                                                                int L, long long* __restrict__ keys) {
     const int i = blockIdx.x * WIND_BLOCK + threadIdx.x;
     if (i >= N) return;
     const float p[3] = {points[(size_t)i * 3], points[(size_t)i * 3 + 1], points[(size_t)i * 3 + 2]};
     int c[3] = {0, 0, 0};
-    const bool ok = wind_finite3(p);
-    if (ok) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-            c[a] = wind_cell(fminf(fmaxf(p[a], g.lo[a]), g.lo[a] + g.ext), g.lo[a], g.inv_h, 1 << g.L);
-    }
-    keys[i] = ok ? (long long)wind_morton(c, g.L) : -1ll;
+    const bool ok = tri_finite3(p[0], p[1], p[2]);
+    if (ok) tri_point_cell(p, g, c);
+    keys[i] = ok ? (long long)wind_morton(c, L) : -1ll;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -220,7 +201,7 @@ __global__ __launch_bounds__(WIND_BLOCK) void k_wind_exact(const float* __restri
         for (int a = 0; a < 3; ++a) p[a] = points[(size_t)i * 3 + a];
     }
     // a point that is not finite stages its share of every tile and takes no part in the pair loop
-    const bool live = i < N && wind_finite3(p);
+    const bool live = i < N && tri_finite3(p[0], p[1], p[2]);
     double acc = 0.0;
     for (int base = 0; base < T; base += WIND_TILE) {
         const int n = min(WIND_TILE, T - base);
@@ -235,7 +216,7 @@ __global__ __launch_bounds__(WIND_BLOCK) void k_wind_exact(const float* __restri
         }
         __syncthreads();
     }
-    if (i < N) out[i] = live ? (float)(acc * WIND_INV_4PI) : __int_as_float(0x7fc00000);
+    if (i < N) out[i] = live ? (float)(acc * WIND_INV_4PI) : tri_nan();
 }
 
 __global__ __launch_bounds__(WIND_BLOCK) void k_wind_fast(const float* __restrict__ points,
@@ -246,14 +227,11 @@ __global__ __launch_bounds__(WIND_BLOCK) void k_wind_fast(const float* __restric
                                                           float* __restrict__ out) {
     const int t = blockIdx.x * WIND_BLOCK + threadIdx.x;
     if (t >= N) return;
-    long long i = t;
-    if (order) {
-        i = order[t];
-        if ((unsigned long long)i >= (unsigned long long)N) return;
-    }
+    const long long i = tri_row(order, t, N);
+    if (i < 0) return;
     const float p[3] = {points[(size_t)i * 3], points[(size_t)i * 3 + 1], points[(size_t)i * 3 + 2]};
-    if (!wind_finite3(p)) {  // before the walk: no loop depends on such a point
-        out[i] = __int_as_float(0x7fc00000);
+    if (!tri_finite3(p[0], p[1], p[2])) {  // before the walk: no loop depends on such a point
+        out[i] = tri_nan();
         return;
     }
     double acc = 0.0;
@@ -298,13 +276,11 @@ __global__ __launch_bounds__(WIND_BLOCK) void k_wind_fast(const float* __restric
 // ---------------------------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------------------------
-static bool wind_finite(double x) { return x >= -1e300 && x <= 1e300; }
 static bool wind_levels_ok(int32_t L) { return L >= 0 && L <= TT_WIND_MAX_LEVELS; }
-static bool wind_box_ok(int32_t L, float lo_x, float lo_y, float lo_z, float ext, float inv_h) {
-    return wind_levels_ok(L) && wind_finite(lo_x) && wind_finite(lo_y) && wind_finite(lo_z) && wind_finite(ext) &&
-           wind_finite(inv_h) && ext >= 0.f && inv_h >= 0.f;
+// the cube of a tree of L levels: G = 2^L leaf cells per axis
+static bool wind_cube(int32_t L, float lo_x, float lo_y, float lo_z, float ext, float inv_h, TriCube* out) {
+    return wind_levels_ok(L) && tri_cube(1 << L, 1 << TT_WIND_MAX_LEVELS, lo_x, lo_y, lo_z, ext, 0.f, inv_h, out);
 }
-static bool wind_count_ok(int32_t n) { return n >= 1 && n <= TT_MESH_MAX_ITEMS; }
 
 extern "C" int64_t tt_wind_node_count(int32_t levels) {
     if (!wind_levels_ok(levels)) return TT_ERR_BAD_ARG;
@@ -314,18 +290,18 @@ extern "C" int64_t tt_wind_node_count(int32_t levels) {
 extern "C" int tt_wind_face_keys(const float* v_pos, const int32_t* t_pos_idx, int32_t V, int32_t T, int32_t levels,
                                  float lo_x, float lo_y, float lo_z, float ext, float inv_h, float* records,
                                  int64_t* keys, void* stream) {
-    if (!wind_count_ok(V) || !wind_count_ok(T) || !wind_box_ok(levels, lo_x, lo_y, lo_z, ext, inv_h))
+    TriCube g;
+    if (!tri_mesh_ok(V, T) || !wind_cube(levels, lo_x, lo_y, lo_z, ext, inv_h, &g))
         return TT_ERR_BAD_ARG;
     if (!v_pos || !t_pos_idx || !records || !keys) return TT_ERR_BAD_ARG;
-    const WindBox g{{lo_x, lo_y, lo_z}, ext, inv_h, (int)levels};
     hipLaunchKernelGGL(k_wind_face_keys, dim3(tt_grid(T)), dim3(WIND_BLOCK), 0, (hipStream_t)stream, v_pos,
-                       (const int*)t_pos_idx, (int)V, (int)T, g, (float4*)records, (long long*)keys);
+                       (const int*)t_pos_idx, (int)V, (int)T, g, (int)levels, (float4*)records, (long long*)keys);
     return tt_check_launch();
 }
 
 extern "C" int tt_wind_build(const float* sorted_records, const int32_t* leaf_ptr, int32_t T, int32_t levels,
                              float* nodes, void* stream) {
-    if (!wind_count_ok(T) || !wind_levels_ok(levels)) return TT_ERR_BAD_ARG;
+    if (!tri_count_ok(T) || !wind_levels_ok(levels)) return TT_ERR_BAD_ARG;
     if (!sorted_records || !leaf_ptr || !nodes) return TT_ERR_BAD_ARG;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_wind_leaves, dim3(tt_grid(1ll << (3 * levels))), dim3(WIND_BLOCK), 0, s,
@@ -337,18 +313,18 @@ extern "C" int tt_wind_build(const float* sorted_records, const int32_t* leaf_pt
 
 extern "C" int tt_wind_point_keys(const float* points, int32_t N, int32_t levels, float lo_x, float lo_y, float lo_z,
                                   float ext, float inv_h, int64_t* keys, void* stream) {
-    if (N < 0 || N > TT_MESH_MAX_ITEMS || !wind_box_ok(levels, lo_x, lo_y, lo_z, ext, inv_h)) return TT_ERR_BAD_ARG;
+    TriCube g;
+    if (!tri_items_ok(N) || !wind_cube(levels, lo_x, lo_y, lo_z, ext, inv_h, &g)) return TT_ERR_BAD_ARG;
     if (N == 0) return TT_OK;
     if (!points || !keys) return TT_ERR_BAD_ARG;
-    const WindBox g{{lo_x, lo_y, lo_z}, ext, inv_h, (int)levels};
     hipLaunchKernelGGL(k_wind_point_keys, dim3(tt_grid(N)), dim3(WIND_BLOCK), 0, (hipStream_t)stream, points, (int)N, g,
-                       (long long*)keys);
+                       (int)levels, (long long*)keys);
     return tt_check_launch();
 }
 
 extern "C" int tt_wind_exact(const float* points, int32_t N, const float* records, int32_t T, float* out,
                              void* stream) {
-    if (N < 0 || N > TT_MESH_MAX_ITEMS || !wind_count_ok(T)) return TT_ERR_BAD_ARG;
+    if (!tri_items_ok(N) || !tri_count_ok(T)) return TT_ERR_BAD_ARG;
     if (N == 0) return TT_OK;
     if (!points || !records || !out) return TT_ERR_BAD_ARG;
     hipLaunchKernelGGL(k_wind_exact, dim3(tt_grid(N)), dim3(WIND_BLOCK), 0, (hipStream_t)stream, points, (int)N,
@@ -359,7 +335,7 @@ extern "C" int tt_wind_exact(const float* points, int32_t N, const float* record
 extern "C" int tt_wind_fast(const float* points, const int64_t* order, int32_t N, const float* sorted_records,
                             const int32_t* leaf_ptr, const float* nodes, int32_t T, int32_t levels, float beta,
                             float* out, void* stream) {
-    if (N < 0 || N > TT_MESH_MAX_ITEMS || !wind_count_ok(T) || !wind_levels_ok(levels) || !(beta > 0.f))
+    if (!tri_items_ok(N) || !tri_count_ok(T) || !wind_levels_ok(levels) || !(beta > 0.f))
         return TT_ERR_BAD_ARG;
     if (N == 0) return TT_OK;
     if (!points || !sorted_records || !leaf_ptr || !nodes || !out) return TT_ERR_BAD_ARG;

@@ -142,6 +142,20 @@ def _chk_range(name: str, lo: int, hi: int, n: int) -> None:
         raise ValueError(f"{name} holds an index outside [0, {n})")
 
 
+def _mesh_box(v_pos: Tensor, t_pos_idx: Tensor) -> Tuple[np.ndarray, np.ndarray, np.float32]:
+    """The bounding box of a mesh in fp32, (lo (3,), hi (3,), ext = the largest of the three extents hi - lo), from ONE
+    read-back that also carries the index range (every value exact in double).  ValueError for an index outside
+    [0, V) or a position that is not finite (an extent that overflows fp32 included)."""
+    box = torch.cat([v_pos.amin(0).double(), v_pos.amax(0).double(), _minmax(t_pos_idx).double()]).cpu()
+    _chk_range("t_pos_idx", int(box[6]), int(box[7]), v_pos.shape[0])
+    lo, hi = box[:3].float().numpy(), box[3:6].float().numpy()
+    with np.errstate(over="ignore", invalid="ignore"):
+        ext = (hi - lo).max()  # IEEE fp32, as on the device
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all() and np.isfinite(ext)):
+        raise ValueError("v_pos holds a value that is not finite")
+    return lo, hi, ext
+
+
 def _chk_size(what: str, **counts: int) -> None:
     if max(counts.values()) > _lib.TT_MESH_MAX_ITEMS:
         sizes = ", ".join(f"{k}={v}" for k, v in counts.items())
@@ -1537,14 +1551,7 @@ def mesh_simplify(v_pos: Tensor, t_pos_idx: Tensor, grid: int, lam: float = SIMP
     t_pos_idx = _chk_index(t_pos_idx, "t_pos_idx", 3)
     V, T, dev = v_pos.shape[0], t_pos_idx.shape[0], v_pos.device
     _chk_size("mesh too large for tt_simplify_*", V=V, T=T)
-    # the box in fp32: minima, maxima and their difference on the device, the two divisions in IEEE fp32 on the host
-    lo_t = v_pos.amin(0)
-    box = torch.cat([lo_t.double(), (v_pos.amax(0) - lo_t).amax().reshape(1).double(),
-                     _minmax(t_pos_idx).double()]).cpu()  # one read-back; every value exact in double
-    lo, ext = box[:3].float().numpy(), box[3].float().numpy()
-    _chk_range("t_pos_idx", int(box[4]), int(box[5]), V)
-    if not bool(torch.isfinite(box[:4]).all()):
-        raise ValueError("v_pos holds a value that is not finite")
+    lo, _, ext = _mesh_box(v_pos, t_pos_idx)  # the box in fp32; the two divisions below in IEEE fp32 on the host
     if ext == 0:
         return _simplify_unchanged(v_pos, t_pos_idx, grid, 0.0)
     h, inv_h = ext / np.float32(grid), np.float32(grid) / ext
@@ -1986,13 +1993,7 @@ class TriangleGrid:
         V, T, dev = self.v_pos.shape[0], self.t_pos_idx.shape[0], self.v_pos.device
         G = dist_default_grid(T) if grid is None else grid
         _chk_size("grid too large for tt_dist_*", cells=G ** 3 + 1)
-        lo_t = self.v_pos.amin(0)
-        box = torch.cat([lo_t.double(), (self.v_pos.amax(0) - lo_t).amax().reshape(1).double(),
-                         _minmax(self.t_pos_idx).double()]).cpu()  # one read-back; every value exact in double
-        _chk_range("t_pos_idx", int(box[4]), int(box[5]), V)
-        if not bool(torch.isfinite(box[:4]).all()):
-            raise ValueError("v_pos holds a value that is not finite")
-        lo, ext = box[:3].float().numpy(), box[3].float().numpy()
+        lo, hi, ext = self._box = _mesh_box(self.v_pos, self.t_pos_idx)
         h, inv_h = ext / np.float32(G), (np.float32(G) / ext if ext > 0 else np.float32(0))
         if not np.isfinite(inv_h) or (ext > 0 and not h > 0):
             raise ValueError(f"the mesh's extent {float(ext)} is too small for grid {G} in fp32")
@@ -2001,17 +2002,47 @@ class TriangleGrid:
         self.records = torch.empty((T, 3, 4), device=dev, dtype=torch.float32)
         self.cell_ptr = torch.empty(G ** 3 + 1, device=dev, dtype=torch.int32)
         total = torch.empty(1, device=dev, dtype=torch.int64)
-        _launch("tt_dist_build_count", self.v_pos, self.t_pos_idx, V, T, G, *self.lo, self.ext, self.inv_h, ws,
-                self.records, self.cell_ptr, total, label="dist_build_count")
+        _launch("tt_dist_build_count", self.v_pos, self.t_pos_idx, V, T, *_box_args(self), ws, self.records,
+                self.cell_ptr, total, label="dist_build_count")
         self.M = int(total.item())
         _chk_size(f"grid {G} gives too many (cell, triangle) pairs for tt_dist_*: use a coarser grid", M=self.M)
         self.cell_tri = torch.empty(self.M, device=dev, dtype=torch.int32)
-        _launch("tt_dist_build_fill", self.records, T, G, *self.lo, self.ext, self.inv_h, ws, self.cell_ptr, self.M,
-                self.cell_tri, label="dist_build_fill")
+        _launch("tt_dist_build_fill", self.records, T, *_box_args(self), ws, self.cell_ptr, self.M, self.cell_tri,
+                label="dist_build_fill")
 
     @property
     def n_faces(self) -> int:
         return self.t_pos_idx.shape[0]
+
+
+def _box_args(tg: TriangleGrid) -> tuple:  # the cube as tt_dist_build_* and tt_dist_keys take it
+    return (tg.G, *tg.lo, tg.ext, tg.inv_h)
+
+
+def _grid_args(tg: TriangleGrid) -> tuple:  # the built grid as tt_dist_query and tt_ray_* take it
+    return (tg.records, tg.cell_ptr, tg.cell_tri, tg.n_faces, tg.M, tg.G, *tg.lo, tg.ext, tg.h, tg.inv_h)
+
+
+def _chk_built(given, cls, name: str):
+    if not isinstance(given, cls):
+        raise TypeError(f"{name} must be a {cls.__name__}, got {type(given).__name__}")
+    return given
+
+
+def _given_or_built(given, cls, name: str, v_pos: Tensor, t_pos_idx: Tensor):
+    """`given` (a TriangleGrid / WindingTree the caller built for this mesh) or, for None, a new cls(v_pos, t_pos_idx)."""
+    if given is None:
+        return cls(v_pos, t_pos_idx)
+    if _chk_built(given, cls, name).v_pos.shape != v_pos.shape:
+        raise ValueError(f"{name} was built for {given.v_pos.shape[0]} vertices, v_pos has {v_pos.shape[0]}")
+    return given
+
+
+def _cell_order(points: Tensor, tg: TriangleGrid) -> Tensor:
+    """The `order` of tt_dist_query / tt_ray_cast: `points` (N,3), N >= 1, by cell key (tt_dist_keys, one stable sort)."""
+    keys = torch.empty(points.shape[0], device=points.device, dtype=torch.int64)
+    _launch("tt_dist_keys", points, points.shape[0], *_box_args(tg), keys, label="dist_keys")
+    return torch.sort(keys, stable=True)[1]
 
 
 @torch.no_grad()
@@ -2022,8 +2053,7 @@ def mesh_closest_point(points: Tensor, tg: TriangleGrid, cell_order: bool = Fals
     bit independent of the grid, the order of the points and the launch.  A row with a coordinate that is not finite
     gives (NaN, -1, 0).  cell_order=True serves the points in the order of their cell key (tt_dist_keys, one stable
     torch.sort) and writes the rows back in the caller's order: the same answer, a different memory access pattern."""
-    if not isinstance(tg, TriangleGrid):
-        raise TypeError(f"tg must be a TriangleGrid, got {type(tg).__name__}")
+    _chk_built(tg, TriangleGrid, "tg")
     points = _chk(points, "points", (None, 3)).detach()
     N, dev = points.shape[0], points.device
     _chk_size("too many points for tt_dist_query", N=N)
@@ -2032,13 +2062,8 @@ def mesh_closest_point(points: Tensor, tg: TriangleGrid, cell_order: bool = Fals
     bary = torch.empty((N, 3), device=dev, dtype=torch.float32)
     if N == 0:
         return d2, face, bary
-    order = None
-    if cell_order:
-        keys = torch.empty(N, device=dev, dtype=torch.int64)
-        _launch("tt_dist_keys", points, N, tg.G, *tg.lo, tg.ext, tg.inv_h, keys, label="dist_keys")
-        order = torch.sort(keys, stable=True)[1]
-    _launch("tt_dist_query", points, order, N, tg.records, tg.cell_ptr, tg.cell_tri, tg.n_faces, tg.M, tg.G, *tg.lo,
-            tg.ext, tg.h, tg.inv_h, d2, face, bary, label="dist_query")
+    order = _cell_order(points, tg) if cell_order else None
+    _launch("tt_dist_query", points, order, N, *_grid_args(tg), d2, face, bary, label="dist_query")
     return d2, face, bary
 
 
@@ -2075,12 +2100,7 @@ def point_mesh_distance2(points: Tensor, v_pos: Tensor, t_pos_idx: Tensor, tg: O
     from the detached positions.  A point that is not finite gives NaN and no gradient."""
     points = _chk(points, "points", (None, 3))
     v_pos = _chk(v_pos, "v_pos", (None, 3))
-    if tg is None:
-        tg = TriangleGrid(v_pos, t_pos_idx)
-    elif not isinstance(tg, TriangleGrid):
-        raise TypeError(f"tg must be a TriangleGrid, got {type(tg).__name__}")
-    elif tg.v_pos.shape != v_pos.shape:
-        raise ValueError(f"tg was built for {tg.v_pos.shape[0]} vertices, v_pos has {v_pos.shape[0]}")
+    tg = _given_or_built(tg, TriangleGrid, "tg", v_pos, t_pos_idx)
     return _PointMeshDistance2Fn.apply(points, v_pos, tg)
 
 
@@ -2161,13 +2181,7 @@ class WindingTree:
         self.v_pos, self.t_pos_idx = _chk_mesh(v_pos, t_pos_idx, "tt_wind_*")
         V, T, dev = self.v_pos.shape[0], self.t_pos_idx.shape[0], self.v_pos.device
         L = wind_default_levels(T) if levels is None else levels
-        lo_t = self.v_pos.amin(0)
-        box = torch.cat([lo_t.double(), (self.v_pos.amax(0) - lo_t).amax().reshape(1).double(),
-                         _minmax(self.t_pos_idx).double()]).cpu()  # one read-back; every value exact in double
-        _chk_range("t_pos_idx", int(box[4]), int(box[5]), V)
-        if not bool(torch.isfinite(box[:4]).all()):
-            raise ValueError("v_pos holds a value that is not finite")
-        lo, ext = box[:3].float().numpy(), box[3].float().numpy()
+        lo, _, ext = _mesh_box(self.v_pos, self.t_pos_idx)
         inv_h = np.float32(1 << L) / ext if ext > 0 else np.float32(0)
         if not np.isfinite(inv_h):
             raise ValueError(f"the mesh's extent {float(ext)} is too small for {L} levels in fp32")
@@ -2289,12 +2303,7 @@ def mesh_signed_distance(points: Tensor, v_pos: Tensor, t_pos_idx: Tensor, tg: O
     beta = _chk_beta(beta)
     points = _chk(points, "points", (None, 3))
     v_pos = _chk(v_pos, "v_pos", (None, 3))
-    if tree is None:
-        tree = WindingTree(v_pos, t_pos_idx)
-    elif not isinstance(tree, WindingTree):
-        raise TypeError(f"tree must be a WindingTree, got {type(tree).__name__}")
-    elif tree.v_pos.shape != v_pos.shape:
-        raise ValueError(f"tree was built for {tree.v_pos.shape[0]} vertices, v_pos has {v_pos.shape[0]}")
+    tree = _given_or_built(tree, WindingTree, "tree", v_pos, t_pos_idx)
     d2 = point_mesh_distance2(points, v_pos, t_pos_idx, tg)
     inside = mesh_winding_number(points, tree, beta=beta) > 0.5
     sign = torch.where(inside, -torch.ones_like(d2), torch.ones_like(d2)).detach()
@@ -2314,22 +2323,11 @@ def _chk_t_max(t_max, name: str = "t_max") -> float:
 
 
 def _chk_rays(origins: Tensor, dirs: Tensor, tg, what: str) -> Tuple[Tensor, Tensor]:
-    if not isinstance(tg, TriangleGrid):
-        raise TypeError(f"tg must be a TriangleGrid, got {type(tg).__name__}")
+    _chk_built(tg, TriangleGrid, "tg")
     origins = _chk(origins, "origins", (None, 3)).detach()
     dirs = _chk(dirs, "dirs", (origins.shape[0], 3)).detach()
     _chk_size(f"too many rays for {what}", N=origins.shape[0])
     return origins, dirs
-
-
-def _ray_order(origins: Tensor, tg: "TriangleGrid") -> Tensor:
-    keys = torch.empty(origins.shape[0], device=origins.device, dtype=torch.int64)
-    _launch("tt_dist_keys", origins, origins.shape[0], tg.G, *tg.lo, tg.ext, tg.inv_h, keys, label="dist_keys")
-    return torch.sort(keys, stable=True)[1]
-
-
-def _grid_args(tg: "TriangleGrid") -> tuple:
-    return (tg.records, tg.cell_ptr, tg.cell_tri, tg.n_faces, tg.M, tg.G, *tg.lo, tg.ext, tg.h, tg.inv_h)
 
 
 @torch.no_grad()
@@ -2349,7 +2347,7 @@ def mesh_ray_cast(origins: Tensor, dirs: Tensor, tg: TriangleGrid, t_max: float 
     bary = torch.empty((N, 3), device=dev, dtype=torch.float32)
     if N == 0:
         return t, face, bary
-    order = _ray_order(origins, tg) if cell_order else None
+    order = _cell_order(origins, tg) if cell_order else None
     _launch("tt_ray_cast", origins, dirs, order, N, t_max, *_grid_args(tg), t, face, bary, label="ray_cast")
     return t, face, bary
 
@@ -2376,12 +2374,7 @@ def ray_mesh_depth(origins: Tensor, dirs: Tensor, v_pos: Tensor, t_pos_idx: Tens
     origins = _chk(origins, "origins", (None, 3))
     dirs = _chk(dirs, "dirs", (origins.shape[0], 3))
     v_pos = _chk(v_pos, "v_pos", (None, 3))
-    if tg is None:
-        tg = TriangleGrid(v_pos, t_pos_idx)
-    elif not isinstance(tg, TriangleGrid):
-        raise TypeError(f"tg must be a TriangleGrid, got {type(tg).__name__}")
-    elif tg.v_pos.shape != v_pos.shape:
-        raise ValueError(f"tg was built for {tg.v_pos.shape[0]} vertices, v_pos has {v_pos.shape[0]}")
+    tg = _given_or_built(tg, TriangleGrid, "tg", v_pos, t_pos_idx)
     t, face, _ = mesh_ray_cast(origins, dirs, tg, t_max)
     hit = face >= 0
     idx = tg.t_pos_idx[face.clamp(min=0).long()].long()
@@ -2410,10 +2403,9 @@ def ao_directions(K: int) -> Tensor:
 
 
 def _tg_diagonal(tg: TriangleGrid) -> float:
-    """The bounding-box diagonal of the mesh in `tg`; one read-back, kept on the grid."""
-    if getattr(tg, "_diagonal", None) is None:
-        tg._diagonal = float((tg.v_pos.amax(0) - tg.v_pos.amin(0)).double().norm())
-    return tg._diagonal
+    """The bounding-box diagonal of the mesh in `tg` from the box its constructor read: fp32 extents, normed in double."""
+    lo, hi, _ = tg._box
+    return float(np.sqrt(np.sum((hi - lo).astype(np.float64) ** 2)))
 
 
 @torch.no_grad()
@@ -2422,8 +2414,7 @@ def mesh_ao_hits(points: Tensor, normals: Tensor, tg: TriangleGrid, n_rays: int 
     """hits (N,) int32 of tt_ray_ao: how many of the n_rays rays of ao_directions about normals[i], started at
     points[i] + bias n^, hit the mesh in `tg` within max_distance; -1 for a point or normal that is not finite or a zero
     normal.  Defaults as mesh_ambient_occlusion."""
-    if not isinstance(tg, TriangleGrid):
-        raise TypeError(f"tg must be a TriangleGrid, got {type(tg).__name__}")
+    _chk_built(tg, TriangleGrid, "tg")
     points = _chk(points, "points", (None, 3)).detach()
     normals = _chk(normals, "normals", (points.shape[0], 3)).detach()
     N, dev = points.shape[0], points.device
