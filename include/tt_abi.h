@@ -1508,6 +1508,67 @@ int tt_ray_ao(const float* points, const float* normals, const float* dirs_local
               int32_t M, int32_t grid, float lo_x, float lo_y, float lo_z, float ext, float h, float inv_h,
               int32_t* hits, void* stream);
 
+/* ---- mesh to SDF grid (tt_dist.hip): the signed distance of a triangle mesh on a regular grid, clamped to a band ----
+ * The field of a mesh, for ops.marching_cubes (ops.mesh_sdf_grid, Mesh.sdf_grid, Mesh.solidify): level (R,R,R) fp32 in
+ * the layout tt_mc_* reads, level[(i R + j) R + k] at the corner with position (x, y, z)_a = fl(lo_a + fl(idx_a * h)),
+ * idx = (i, j, k) -- the product and the sum each rounded to fp32, never fused: the values torch computes for
+ * lo + idx.float() * h.  New symbols only: TT_ABI_VERSION is unchanged.
+ *   value       tau = fl(band * h) (the host's), (d2, face) = tt_dist_query's answer at the corner, BIT FOR BIT, d =
+ *               sqrt(d2) correctly rounded.  A corner with d < tau is a BAND corner: level = sgn d, face = its face.
+ *               Every other corner: level = sgn tau, face = -1.
+ *   sign        a corner with d < sign_tau (>= tau, the host's) is a SIGN corner: sgn = -1 where its winding number w >
+ *               0.5, else +1 (NaN: +1), the rule of ops.mesh_signed_distance.  Any other corner takes the sign of the
+ *               nearest sign corner BELOW it along the last axis in its (i, j) row, and + when there is none.  With
+ *               sign_tau = tau the sign corners are the band corners.  ops.mesh_sdf_grid passes sign_tau = max(band,
+ *               1 + 2^-10) h: along a row the distance to a closed surface changes by at most h per corner, so the first
+ *               corner behind a crossing has d <= h and is a sign corner itself -- a band narrower than a cell would
+ *               otherwise carry the outside sign through the interior whenever the crossing's inner corner is not in
+ *               the band.  For band >= 1 + 2^-10 the two sets coincide.
+ *   scatter     tt_sdfgrid_scatter finds the CANDIDATES, the corners within reach of some triangle.  Work item =
+ *               (triangle, one i-plane x 4 rows of its box): the triangle's bounding box in corner indices, grown by
+ *               reach = sign_tau / h + 1/100 + 2^-18 m / h cells (double), m the largest |coordinate| of the triangle
+ *               and of the grid's corners, and clipped to the grid.  tt_exclusive_scan of the item counts (int64, the
+ *               total stays on the device), a grid-stride loop over items, a binary search for the item's triangle: a
+ *               thread loops over at most 4 R corners however large the triangle.  A corner whose squared distance to
+ *               the triangle's BOX exceeds 1.001 (reach h)^2 is skipped; else dist_closest, the query's device
+ *               function, gives the pair's d2, and d2 <= (reach h)^2 goes to atomicMin (uint64) on (bits of d2) << 32 |
+ *               face -- d2 >= 0 orders as its bits do.  Integer atomics only: the candidate set does not depend on the
+ *               launch or on the order of the triangles.  A triangle with a vertex that is not finite reaches no
+ *               corner (the query never lets it win either).  Every index is clamped to [0, R) before it addresses a
+ *               key.
+ *   why two     The scatter's d2 is the query's up to the LAST BIT only: dist_closest is inlined into both kernels,
+ *   passes      under the same contraction setting, and the compiler fuses products and sums differently in the two
+ *               (measured on a 32^3 sphere at R = 33: 30 % of the band corners differ in the last bit of sqrt(d2), 1 %
+ *               in the face of a tie; a barrier that hides the loop invariants from the optimiser changed neither).
+ *               So the scatter's keys only select: the slack above exceeds that bit by three orders of magnitude, every
+ *               sign corner is a candidate, and the host runs tt_dist_query on the candidates -- near points, which
+ *               the ring search is built for -- and tt_wind_fast next to it.  Their answers are what the grid holds.
+ *   compaction  tt_compact.h over the keys that are not empty: out_count (2) int32, both the number of candidates,
+ *               DEVICE memory, read back once.  tt_sdfgrid_corners writes them in ascending corner id: corner (n_cand)
+ *               int32, points (n_cand,3) fp32.
+ *   finish      tt_sdfgrid_finish takes d2 (n_cand), nearest (n_cand) int32 (tt_dist_query's) and winding (n_cand) of the
+ *               candidates: k_sdf_keys replaces their keys by the query's (nearest = -1: empty) and writes sgn into
+ *               level; then k_sdf_finish, one wave per (i, j) row over 64 corners of the last axis at a time (ballots
+ *               of sign / inside, the highest set bit below a lane, a carry between chunks), writes level and face of
+ *               every corner.  A candidate beyond sign_tau is an ordinary far corner.
+ * Use: ws = tt_sdfgrid_workspace_bytes(R, T) = 12 R^3 bytes (keys, compaction offsets) + 8 T (item offsets) + block
+ * sums; scatter, read out_count, corners, tt_dist_query and tt_wind_fast on points, finish -- all with the same
+ * workspace.  2 <= R <= TT_SDFGRID_MAX_RES, 0 < tau <= sign_tau <= (TT_SDFGRID_MAX_BAND + 1) h, h > 0, 1 <= T <=
+ * TT_MESH_MAX_ITEMS, 0 <= n_cand <= R^3; every entry point validates before any HIP call (TT_ERR_BAD_ARG).  No float
+ * atomics, no scratch, no spin wait.  Not differentiable.
+ * Out of scope: a gradient, adaptive or sparse grids, dual contouring of sharp features, a ShapeLoss on the grid. */
+#define TT_SDFGRID_MAX_RES 512
+#define TT_SDFGRID_MAX_BAND 16
+int64_t tt_sdfgrid_workspace_bytes(int32_t resolution, int32_t T);
+int tt_sdfgrid_scatter(const float* records, int32_t T, int32_t resolution, float lo_x, float lo_y, float lo_z, float h,
+                       float tau, float sign_tau, void* workspace, int32_t* out_count, void* stream);
+int tt_sdfgrid_corners(int32_t resolution, int32_t T, float lo_x, float lo_y, float lo_z, float h, float tau,
+                       float sign_tau, const void* workspace, int32_t n_cand, int32_t* corner, float* points,
+                       void* stream);
+int tt_sdfgrid_finish(int32_t resolution, int32_t T, float tau, float sign_tau, void* workspace, const int32_t* corner,
+                      const float* d2, const int32_t* nearest, const float* winding, int32_t n_cand, float* level,
+                      int32_t* face, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

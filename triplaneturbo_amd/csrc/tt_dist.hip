@@ -511,3 +511,291 @@ extern "C" int tt_dist_sample_emit(const float* v_pos, const int32_t* t_pos_idx,
                        (int*)face);
     return tt_check_launch();
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// mesh to SDF grid (include/tt_abi.h, "mesh to SDF grid"): the fourth consumer of the triangle record, the other way
+// round -- triangles scatter to the grid corners near them.
+//   k_sdf_count    work items of every triangle -> tt_exclusive_scan<long long> -> offsets, the total stays on the device
+//   k_sdf_scatter  one thread per item (triangle, one i-plane x SDF_ROWS rows of its grown box): dist_closest at every
+//                  corner that can be within reach, 64-bit integer atomicMin of (bits of d2) << 32 | face
+//   k_sdf_flags    the corners some triangle reached (the CANDIDATES) -> tt_compact.h; k_sdf_emit: their ids, positions
+//   k_sdf_keys     the query's (d2, face) and the sign of every candidate, handed back by the host, into keys / level
+//   k_sdf_finish   one wave per (i, j) row: level and face of every corner, the far sign carried along the row
+// The scatter's own d2 is NOT the query's bit for bit, although both call dist_closest under this file's contraction
+// setting: inlined into two kernels the function is scheduled and fused twice, and on 30 % of the band corners of a
+// 32^3 sphere the two d2 differ in the last bit (measured; an optimisation barrier on the twelve inputs did not change
+// that).  So the scatter only FINDS the corners near the surface, with a margin far above that last bit, and the host
+// runs k_dist_query itself on them -- near points, which the ring search is built for.  What is written to level and
+// face is the query's answer by construction.
+// ---------------------------------------------------------------------------------------------------------------
+#include "tt_compact.h"
+
+#define SDF_ROWS 4               // rows (second axis) of one work item
+#define SDF_EMPTY (~0ull)        // a key no triangle reached: its d2 half is a NaN, which fails both band tests
+#define SDF_SCATTER_BLOCKS 4096  // grid-stride blocks of k_sdf_scatter (the item count never leaves the device)
+
+struct SdfGrid {
+    float lo[3], h, tau, sign_tau;
+    double reach, mag;  // sign_tau / h + 1/100 cells; max |lo_a| + R h, the largest coordinate of a corner
+    int R;
+};
+struct SdfWs {
+    unsigned long long* keys;
+    long long *offs, *xs;
+    int* tot;
+    TtCompact2 cmp;
+};
+struct SdfLayout {
+    SdfWs w;
+    long long bytes;
+};
+static SdfLayout sdf_layout(void* base, long long R, long long T) {
+    TtCarver c{(char*)base};
+    SdfLayout l;
+    const long long n = R * R * R;
+    l.w.keys = c.take<unsigned long long>(n);
+    l.w.offs = c.take<long long>(T + 1);
+    l.w.xs = c.take<long long>(tt_xscan_blocks(T) + 1);
+    l.w.tot = c.take<int>(2);
+    l.w.cmp = tt_compact2_carve(c, n, l.w.tot);
+    l.bytes = c.bytes();
+    return l;
+}
+
+// corner i of an axis: fl(lo + fl(i * h)), the product and the sum each rounded, whatever the file's setting
+__device__ __forceinline__ float sdf_corner(float lo, int i, float h) {
+#pragma clang fp contract(off)
+    const float s = (float)i * h;
+    return lo + s;
+}
+
+// The corners [c0, c1] per axis a triangle can reach (empty: c0 > c1 on some axis) and the squared distance `lim` up
+// to which a corner is a candidate.  The reach is sign_tau plus a slack: 1/100 cell, and 2^-18 of the largest
+// coordinate in play (d2 is a difference of vectors that long, each rounded to 2^-24 of it a few times over; a corner
+// carries two such roundings).  A record that is not finite reaches nothing.
+__device__ __forceinline__ bool sdf_box(const float4 r0, const float4 r1, const float4 r2, const SdfGrid& g, int c0[3],
+                                        int c1[3], float mn[3], float mx[3], float* lim) {
+    if (!tri_finite3(r0.x, r0.y, r0.z) || !tri_finite3(r1.x, r1.y, r1.z) || !tri_finite3(r2.x, r2.y, r2.z)) return false;
+    mn[0] = fminf(r0.x, fminf(r1.x, r2.x)), mn[1] = fminf(r0.y, fminf(r1.y, r2.y)), mn[2] = fminf(r0.z, fminf(r1.z, r2.z));
+    mx[0] = fmaxf(r0.x, fmaxf(r1.x, r2.x)), mx[1] = fmaxf(r0.y, fmaxf(r1.y, r2.y)), mx[2] = fmaxf(r0.z, fmaxf(r1.z, r2.z));
+    double mag = g.mag;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) mag = fmax(mag, fmax(fabs((double)mn[a]), fabs((double)mx[a])));
+    const double reach = g.reach + mag / (double)g.h * (1.0 / 262144.0);
+    const double r = reach * (double)g.h;
+    *lim = (float)(r * r);
+    bool any = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double lo = ceil(((double)mn[a] - (double)g.lo[a]) / (double)g.h - reach);
+        const double hi = floor(((double)mx[a] - (double)g.lo[a]) / (double)g.h + reach);
+        c0[a] = (int)fmin(fmax(lo, 0.0), (double)g.R);  // R: past the last corner, an empty range
+        c1[a] = (int)fmin(fmax(hi, -1.0), (double)(g.R - 1));
+        any = any && c0[a] <= c1[a];
+    }
+    return any;
+}
+__device__ __forceinline__ long long sdf_items(const int c0[3], const int c1[3]) {
+    return (long long)(c1[0] - c0[0] + 1) * ((c1[1] - c0[1]) / SDF_ROWS + 1);
+}
+
+__global__ __launch_bounds__(DIST_BLOCK) void k_sdf_init(unsigned long long* __restrict__ keys, long long n) {
+    const long long i = (long long)blockIdx.x * DIST_BLOCK + threadIdx.x;
+    if (i < n) keys[i] = SDF_EMPTY;
+}
+
+__global__ __launch_bounds__(DIST_BLOCK) void k_sdf_count(const float4* __restrict__ rec, int T, SdfGrid g,
+                                                          long long* __restrict__ cnt) {
+    const int f = blockIdx.x * DIST_BLOCK + threadIdx.x;
+    if (f >= T) return;
+    int c0[3], c1[3];
+    float mn[3], mx[3], lim;
+    const bool any = sdf_box(rec[(size_t)f * 3], rec[(size_t)f * 3 + 1], rec[(size_t)f * 3 + 2], g, c0, c1, mn, mx, &lim);
+    cnt[f] = any ? sdf_items(c0, c1) : 0ll;
+}
+
+__global__ __launch_bounds__(DIST_BLOCK) void k_sdf_scatter(const float4* __restrict__ rec, int T, SdfGrid g,
+                                                            const long long* __restrict__ offs,
+                                                            unsigned long long* __restrict__ keys) {
+    const long long total = offs[T];
+    const int R = g.R;
+    for (long long item = (long long)blockIdx.x * DIST_BLOCK + threadIdx.x; item < total;
+         item += (long long)gridDim.x * DIST_BLOCK) {
+        int lo = 0, hi = T - 1;  // the face: the last f with offs[f] <= item
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (offs[mid] <= item) lo = mid; else hi = mid - 1;
+        }
+        const int f = lo;
+        const float4 r0 = rec[(size_t)f * 3], r1 = rec[(size_t)f * 3 + 1], r2 = rec[(size_t)f * 3 + 2];
+        int c0[3], c1[3];
+        float mn[3], mx[3], lim;
+        if (!sdf_box(r0, r1, r2, g, c0, c1, mn, mx, &lim)) continue;
+        const float box_lim = lim * 1.001f;  // the squared distance to the triangle's BOX, with its own rounding
+        const long long local = item - offs[f];
+        const int nrb = (c1[1] - c0[1]) / SDF_ROWS + 1;
+        const int i = c0[0] + (int)(local / nrb), jb = c0[1] + (int)(local % nrb) * SDF_ROWS;
+        if (local < 0 || i > c1[0]) continue;
+        const float ta[3] = {r0.x, r0.y, r0.z}, tb[3] = {r1.x, r1.y, r1.z}, tc[3] = {r2.x, r2.y, r2.z};
+        float p[3];
+        p[0] = sdf_corner(g.lo[0], i, g.h);
+        const float bx = fmaxf(fmaxf(mn[0] - p[0], p[0] - mx[0]), 0.f);
+        const int je = min(jb + SDF_ROWS - 1, c1[1]);
+        for (int j = jb; j <= je; ++j) {
+            p[1] = sdf_corner(g.lo[1], j, g.h);
+            const float by = fmaxf(fmaxf(mn[1] - p[1], p[1] - mx[1]), 0.f);
+            const float bxy = bx * bx + by * by;
+            if (bxy > box_lim) continue;
+            const size_t row = ((size_t)i * R + j) * R;
+            for (int k = c0[2]; k <= c1[2]; ++k) {
+                p[2] = sdf_corner(g.lo[2], k, g.h);
+                const float bz = fmaxf(fmaxf(mn[2] - p[2], p[2] - mx[2]), 0.f);
+                if (bxy + bz * bz > box_lim) continue;
+                const DistHit hit = dist_closest(p, ta, tb, tc);
+                if (!(hit.d2 <= lim)) continue;
+                const unsigned long long key = ((unsigned long long)__float_as_uint(hit.d2) << 32) | (unsigned)f;
+                unsigned long long* slot = keys + row + k;  // i, j, k in [0, R): sdf_box clamps every range
+                if (key < __atomic_load_n(slot, __ATOMIC_RELAXED)) atomicMin(slot, key);
+            }
+        }
+    }
+}
+
+// the correctly rounded root, as torch's sqrt is (HIP's __fsqrt_rn is the hardware's approximation)
+__device__ __forceinline__ float sdf_key_d(unsigned long long key) { return sqrtf(__uint_as_float((unsigned)(key >> 32))); }
+
+// both streams of the compaction: the candidates
+__global__ __launch_bounds__(TT_COMPACT_BLOCK) void k_sdf_flags(const unsigned long long* __restrict__ keys, TtCompact2 c) {
+    const int i = blockIdx.x * TT_COMPACT_BLOCK + threadIdx.x;
+    const unsigned cand = i < c.n ? (unsigned)(keys[i] != SDF_EMPTY) : 0u;
+    tt_compact2_first_level<1>(c, cand, cand);
+}
+
+__global__ __launch_bounds__(DIST_BLOCK) void k_sdf_emit(const unsigned long long* __restrict__ keys, SdfGrid g,
+                                                         TtCompact2 c, int n_cand, int* __restrict__ corner,
+                                                         float* __restrict__ points) {
+    const int i = blockIdx.x * DIST_BLOCK + threadIdx.x;
+    if (i >= c.n || keys[i] == SDF_EMPTY) return;
+    const int at = tt_compact2_hi(c, i);
+    if (at < 0 || at >= n_cand) return;
+    corner[at] = i;
+    const int k = i % g.R, j = (i / g.R) % g.R, z = i / (g.R * g.R);
+    points[(size_t)at * 3] = sdf_corner(g.lo[0], z, g.h);
+    points[(size_t)at * 3 + 1] = sdf_corner(g.lo[1], j, g.h);
+    points[(size_t)at * 3 + 2] = sdf_corner(g.lo[2], k, g.h);
+}
+
+// the query's answer replaces the scatter's key; the sign goes to level (-1 where w > 0.5, the rule of
+// ops.mesh_signed_distance).  A face of -1 (a point the query refused) leaves the corner empty.
+__global__ __launch_bounds__(DIST_BLOCK) void k_sdf_keys(const int* __restrict__ corner, const float* __restrict__ d2,
+                                                         const int* __restrict__ face, const float* __restrict__ w,
+                                                         int n_cand, int n, unsigned long long* __restrict__ keys,
+                                                         float* __restrict__ level) {
+    const int s = blockIdx.x * DIST_BLOCK + threadIdx.x;
+    if (s >= n_cand) return;
+    const int i = corner[s];
+    if ((unsigned)i >= (unsigned)n) return;
+    const int f = face[s];
+    keys[i] = f >= 0 ? ((unsigned long long)__float_as_uint(d2[s]) << 32) | (unsigned)f : SDF_EMPTY;
+    level[i] = w[s] > 0.5f ? -1.f : 1.f;
+}
+
+// One wave per (i, j) row, 64 corners of the last axis at a time: a sign corner carries its own sign (in `level`, from
+// k_sdf_keys); any other corner takes the sign of the nearest sign corner below it in the row, + when there is none.
+__global__ __launch_bounds__(DIST_BLOCK) void k_sdf_finish(const unsigned long long* __restrict__ keys, int R, float tau,
+                                                           float sign_tau, float* __restrict__ level,
+                                                           int* __restrict__ face) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * (DIST_BLOCK / 64) + (threadIdx.x >> 6);
+    if (row >= (long long)R * R) return;  // wave-uniform
+    unsigned carry = 0;  // 1: the last sign corner so far was inside
+    for (int kb = 0; kb < R; kb += 64) {
+        const int k = kb + lane;
+        const size_t at = (size_t)row * R + min(k, R - 1);
+        const unsigned long long key = k < R ? keys[at] : SDF_EMPTY;
+        const float d = sdf_key_d(key);
+        const bool band = d < tau, sign = d < sign_tau;
+        const bool neg = sign && level[at] < 0.f;
+        const unsigned long long sm = __ballot(sign), nm = __ballot(neg);
+        const unsigned long long below = sm & ((1ull << lane) - 1ull);
+        unsigned inside = carry;
+        if (below) inside = (unsigned)((nm >> (63 - __clzll((long long)below))) & 1ull);
+        if (sign) inside = neg ? 1u : 0u;
+        if (k < R) {
+            level[at] = (inside ? -1.f : 1.f) * (band ? d : tau);
+            face[at] = band ? (int)(unsigned)(key & 0xffffffffull) : -1;
+        }
+        if (sm) carry = (unsigned)((nm >> (63 - __clzll((long long)sm))) & 1ull);
+    }
+}
+
+// (R, lo, h, tau, sign_tau) as a grid; false for an argument out of range or not finite
+static bool sdf_grid(int32_t R, float lo_x, float lo_y, float lo_z, float h, float tau, float sign_tau, SdfGrid* out) {
+    if (!(R >= 2 && R <= TT_SDFGRID_MAX_RES && tri_finite(lo_x) && tri_finite(lo_y) && tri_finite(lo_z) &&
+          tri_finite(h) && h > 0.f && tri_finite(tau) && tau > 0.f && tri_finite(sign_tau) && sign_tau >= tau))
+        return false;
+    const double cells = (double)sign_tau / (double)h;
+    if (!(cells <= TT_SDFGRID_MAX_BAND + 1.0)) return false;
+    const double mag = fmax(fmax(fabs((double)lo_x), fabs((double)lo_y)), fabs((double)lo_z)) + (double)R * (double)h;
+    *out = SdfGrid{{lo_x, lo_y, lo_z}, h, tau, sign_tau, cells + 0.01, mag, (int)R};
+    return true;
+}
+
+extern "C" int64_t tt_sdfgrid_workspace_bytes(int32_t resolution, int32_t T) {
+    if (resolution < 2 || resolution > TT_SDFGRID_MAX_RES || !tri_count_ok(T)) return TT_ERR_BAD_ARG;
+    return sdf_layout(nullptr, resolution, T).bytes;
+}
+
+extern "C" int tt_sdfgrid_scatter(const float* records, int32_t T, int32_t resolution, float lo_x, float lo_y,
+                                  float lo_z, float h, float tau, float sign_tau, void* workspace, int32_t* out_count,
+                                  void* stream) {
+    SdfGrid g;
+    if (!tri_count_ok(T) || !sdf_grid(resolution, lo_x, lo_y, lo_z, h, tau, sign_tau, &g)) return TT_ERR_BAD_ARG;
+    if (!records || !workspace || !out_count) return TT_ERR_BAD_ARG;
+    const SdfWs w = sdf_layout(workspace, resolution, T).w;
+    const long long n = (long long)resolution * resolution * resolution;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_sdf_init, dim3(tt_grid(n)), dim3(DIST_BLOCK), 0, s, w.keys, n);
+    hipLaunchKernelGGL(k_sdf_count, dim3(tt_grid(T)), dim3(DIST_BLOCK), 0, s, (const float4*)records, (int)T, g, w.offs);
+    tt_exclusive_scan<long long>(w.offs, T, w.offs, w.xs, w.offs + T, s);
+    hipLaunchKernelGGL(k_sdf_scatter, dim3(SDF_SCATTER_BLOCKS), dim3(DIST_BLOCK), 0, s, (const float4*)records, (int)T,
+                       g, (const long long*)w.offs, w.keys);
+    hipLaunchKernelGGL(k_sdf_flags, dim3((unsigned)w.cmp.nblk), dim3(TT_COMPACT_BLOCK), 0, s,
+                       (const unsigned long long*)w.keys, w.cmp);
+    tt_compact2_scan_blocks(w.cmp, (int*)out_count, s);
+    return tt_check_launch();
+}
+
+extern "C" int tt_sdfgrid_corners(int32_t resolution, int32_t T, float lo_x, float lo_y, float lo_z, float h, float tau,
+                                  float sign_tau, const void* workspace, int32_t n_cand, int32_t* corner,
+                                  float* points, void* stream) {
+    SdfGrid g;
+    const long long n = (long long)resolution * resolution * resolution;
+    if (!tri_count_ok(T) || !sdf_grid(resolution, lo_x, lo_y, lo_z, h, tau, sign_tau, &g) || n_cand < 0 || n_cand > n)
+        return TT_ERR_BAD_ARG;
+    if (n_cand == 0) return TT_OK;
+    if (!workspace || !corner || !points) return TT_ERR_BAD_ARG;
+    const SdfWs w = sdf_layout((void*)workspace, resolution, T).w;
+    hipLaunchKernelGGL(k_sdf_emit, dim3(tt_grid(n)), dim3(DIST_BLOCK), 0, (hipStream_t)stream,
+                       (const unsigned long long*)w.keys, g, w.cmp, (int)n_cand, (int*)corner, points);
+    return tt_check_launch();
+}
+
+extern "C" int tt_sdfgrid_finish(int32_t resolution, int32_t T, float tau, float sign_tau, void* workspace,
+                                 const int32_t* corner, const float* d2, const int32_t* nearest, const float* winding,
+                                 int32_t n_cand, float* level, int32_t* face, void* stream) {
+    const long long n = (long long)resolution * resolution * resolution;
+    if (resolution < 2 || resolution > TT_SDFGRID_MAX_RES || !tri_count_ok(T) || !tri_finite(tau) || !(tau > 0.f) ||
+        !tri_finite(sign_tau) || !(sign_tau >= tau) || n_cand < 0 || n_cand > n)
+        return TT_ERR_BAD_ARG;
+    if (!workspace || !level || !face || (n_cand > 0 && (!corner || !d2 || !nearest || !winding))) return TT_ERR_BAD_ARG;
+    const SdfWs w = sdf_layout(workspace, resolution, T).w;
+    hipStream_t s = (hipStream_t)stream;
+    if (n_cand > 0)
+        hipLaunchKernelGGL(k_sdf_keys, dim3(tt_grid(n_cand)), dim3(DIST_BLOCK), 0, s, (const int*)corner, d2,
+                           (const int*)nearest, winding, (int)n_cand, (int)n, w.keys, level);
+    const long long rows = (long long)resolution * resolution;
+    hipLaunchKernelGGL(k_sdf_finish, dim3((unsigned)((rows + DIST_BLOCK / 64 - 1) / (DIST_BLOCK / 64))), dim3(DIST_BLOCK),
+                       0, s, (const unsigned long long*)w.keys, (int)resolution, tau, sign_tau, level, (int*)face);
+    return tt_check_launch();
+}

@@ -113,6 +113,12 @@ class MultipromptMeshExporter(Exporter):
         # simplify attribute or decimate_target_faces, is a ValueError at call time.
         self.remesh_edge_length: Optional[float] = None
         self.remesh_target_faces: Optional[int] = None
+        # Mesh.solidify's arguments, attributes for the same reason: with solidify_resolution set mesh[0] goes through
+        # the field first (a watertight surface without interior walls, thickened or eroded by solidify_offset) and
+        # simplify / decimate / remesh, when set, work on that.  Unset, the export is what it is without the attribute;
+        # solidify_offset alone is a ValueError at call time.
+        self.solidify_resolution: Optional[int] = None
+        self.solidify_offset: float = 0.0
         # the tangent-space normal map of the exported mesh (map_Bump, ops.bake_normal_map) on the obj-mtl path with
         # save_texture, and the number of projection steps it takes towards the iso-surface; attributes for the same
         # reason.  Unset, params are exactly what they are without the bake.
@@ -147,6 +153,8 @@ class MultipromptMeshExporter(Exporter):
                 self.decimate_target_faces is not None or any(v is not None for v in simplify.values())):
             raise ValueError("multiprompt-mesh-exporter: remesh_edge_length / remesh_target_faces cannot be combined "
                              "with a simplify_* attribute or decimate_target_faces")
+        if self.solidify_resolution is None and self.solidify_offset != 0:
+            raise ValueError("multiprompt-mesh-exporter: solidify_offset needs solidify_resolution")
         isosurface = getattr(self.geometry, "isosurface", None)
         if isosurface is None:
             raise RuntimeError("geometry.isosurface is not set: configure a generative-space-mesh-rasterize-renderer "
@@ -154,6 +162,8 @@ class MultipromptMeshExporter(Exporter):
         mesh = isosurface(space_cache)
         if type(mesh) == list:
             mesh = mesh[0]
+        if self.solidify_resolution is not None:
+            mesh = mesh.solidify(self.solidify_resolution, offset=self.solidify_offset)
         if any(v is not None for v in simplify.values()):
             mesh = mesh.simplify(**simplify)
         if self.decimate_target_faces is not None:

@@ -2311,6 +2311,112 @@ def mesh_signed_distance(points: Tensor, v_pos: Tensor, t_pos_idx: Tensor, tg: O
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# mesh to SDF grid (include/tt_abi.h, "mesh to SDF grid"): the clamped signed distance on a regular grid
+SDFGRID_SIGN_BAND = 1.0 + 2.0 ** -10  # cells: corners nearer than this carry their own sign even in a narrower band
+
+
+def _chk_sdf_grid_args(resolution, band, default_bounds: bool) -> Tuple[int, float]:
+    """(R, band) of ops.mesh_sdf_grid, checked before any tensor is looked at."""
+    if isinstance(resolution, bool) or not isinstance(resolution, int):
+        raise TypeError(f"resolution must be an int, got {type(resolution).__name__}")
+    if not 2 <= resolution <= _lib.TT_SDFGRID_MAX_RES:
+        raise ValueError(f"resolution must be in [2, {_lib.TT_SDFGRID_MAX_RES}], got {resolution}")
+    if isinstance(band, bool) or not isinstance(band, (int, float)) or not 0 < band <= _lib.TT_SDFGRID_MAX_BAND:
+        raise ValueError(f"band must be in (0, {_lib.TT_SDFGRID_MAX_BAND}] grid cells, got {band!r}")
+    need = 2 * (int(np.ceil(band)) + 1) + 2
+    if default_bounds and resolution < need:
+        raise ValueError(f"resolution {resolution} leaves no room for band {band} around the mesh: "
+                         f"bounds=None needs resolution >= 2 * (ceil(band) + 1) + 2 = {need}")
+    return resolution, float(band)
+
+
+def sdf_grid_bounds(box_lo, box_hi, resolution: int, band: float) -> Tuple[np.ndarray, np.float32]:
+    """(lo (3,) fp32, h fp32) of the default grid of ops.mesh_sdf_grid: the cube about the centre of the box (box_lo,
+    box_hi) in which the box's largest extent spans R - 1 - 2 m cells, m = ceil(band) + 1, so that at least m cells
+    lie between the box and every face of the grid (h carries a relative 2^-20 on top against its own rounding)."""
+    lo, hi = np.asarray(box_lo, np.float64), np.asarray(box_hi, np.float64)
+    m = int(np.ceil(band)) + 1
+    ext = float((hi - lo).max())
+    if not ext > 0.0:
+        raise ValueError("the mesh has no extent: give bounds=(lo, side)")
+    h = ext * (1.0 + 2.0 ** -20) / (resolution - 1 - 2 * m)
+    return ((lo + hi) * 0.5 - h * (resolution - 1) * 0.5).astype(np.float32), np.float32(h)
+
+
+@torch.no_grad()
+def mesh_sdf_grid(v_pos: Tensor, t_pos_idx: Tensor, resolution: int, band: float = 3.0, bounds=None,
+                  tg: Optional[TriangleGrid] = None, tree: Optional[WindingTree] = None, beta: float = 2.0
+                  ) -> Tuple[Tensor, dict]:
+    """The signed distance of the mesh on a regular grid, clamped to a band: level (R,R,R) fp32 in the layout
+    ops.marching_cubes reads, negative inside, and info = {lo (3,) fp32 tensor, h, tau (Python floats holding fp32
+    values), face (R,R,R) int32, band_corners, sign_corners, candidates}.  NOT differentiable.  (tt_sdfgrid_*; include/tt_abi.h,
+    "mesh to SDF grid".)
+
+    Corner (i,j,k) is the fp32 point lo + (i,j,k) * h, a product then a sum, each rounded: torch's values for
+    lo + idx.float() * h.  bounds=(lo, side): the cube from lo (three numbers) with h = side / (R - 1) in fp32.
+    bounds=None: the cube about the mesh's bounding box with at least ceil(band) + 1 cells between the box and every
+    grid face (sdf_grid_bounds), which needs R >= 2 * (ceil(band) + 1) + 2.
+
+    With tau = band * h in fp32, a corner with d = sqrt(d2) < tau is a band corner: d2 and info["face"] are
+    ops.mesh_closest_point's there, bit for bit: a scatter kernel (triangles to the corners of their grown boxes,
+    integer atomics) finds the corners near the surface, and the closest-point query itself runs on those alone --
+    the same device function inlined into the scatter differs from the query in the last bit.  level =
+    sgn * d with sgn = -1 where ops.mesh_winding_number(..., beta) > 0.5, else +1 -- the rule of
+    ops.mesh_signed_distance.  Every other corner has level = +-tau and face = -1.  Its sign is that of the nearest
+    SIGN corner below it along the last axis in its (i,j) row, + when there is none; the sign corners are the corners
+    with d < max(band, 1 + 2^-10) * h, which evaluate their own winding number.  For band >= 1 + 2^-10 they are the
+    band corners; a narrower band alone could not tell the inside of a closed mesh, because the first corner behind a
+    crossing (d <= h) need not be in it.  For a closed input level == mesh.signed_distance(corners).clamp(-tau, tau)
+    at every corner.  An open input is closed along w = 1/2 where sign corners see it, and rows keep the sign they
+    last saw.  The result does not depend on the order of the triangles or the launch (integer atomics only).
+
+    `tg`, `tree`: a TriangleGrid / WindingTree of the same mesh to reuse.  R <= TT_SDFGRID_MAX_RES, 0 < band <=
+    TT_SDFGRID_MAX_BAND; a vertex that is not finite is a ValueError (as for TriangleGrid).  Read-backs: the box (when
+    a grid is built here), the number of candidates, the two counts of info (band_corners, sign_corners; `candidates`
+    is what the scatter selected)."""
+    R, band = _chk_sdf_grid_args(resolution, band, bounds is None)
+    beta = _chk_beta(beta)
+    if bounds is not None:
+        try:
+            b_lo, side = bounds
+            b_lo = np.asarray([float(x) for x in b_lo], np.float32)
+            side = np.float32(float(side))
+        except (TypeError, ValueError):
+            raise ValueError(f"bounds must be (lo, side) with three numbers and a number, got {bounds!r}") from None
+        if b_lo.shape != (3,) or not np.isfinite(b_lo).all() or not (np.isfinite(side) and side > 0):
+            raise ValueError(f"bounds must be (lo, side) with finite lo (3) and side > 0, got {bounds!r}")
+    v_pos = _chk(v_pos, "v_pos", (None, 3)).detach()
+    tg = _given_or_built(tg, TriangleGrid, "tg", v_pos, t_pos_idx)
+    tree = _given_or_built(tree, WindingTree, "tree", v_pos, t_pos_idx)
+    dev, T = v_pos.device, tg.n_faces
+    if bounds is None:
+        lo, h = sdf_grid_bounds(tg._box[0], tg._box[1], R, band)
+    else:
+        lo, h = b_lo, side / np.float32(R - 1)
+    tau, sign_tau = np.float32(band) * h, np.float32(max(band, SDFGRID_SIGN_BAND)) * h
+    if not (np.isfinite(h) and h > 0 and tau > 0 and np.isfinite(sign_tau)):
+        raise ValueError(f"the grid step {float(h)} is not usable in fp32")
+    geo = (*(float(x) for x in lo), float(h), float(tau), float(sign_tau))
+    ws = _workspace("tt_sdfgrid_workspace_bytes", R, T, device=dev)
+    counts = torch.empty(2, device=dev, dtype=torch.int32)
+    _launch("tt_sdfgrid_scatter", tg.records, T, R, *geo, ws, counts, label="sdfgrid_scatter")
+    n_cand = int(counts[1].item())
+    corner = torch.empty(n_cand, device=dev, dtype=torch.int32)
+    points = torch.empty((n_cand, 3), device=dev, dtype=torch.float32)
+    _launch("tt_sdfgrid_corners", R, T, *geo, ws, n_cand, corner, points, label="sdfgrid_corners")
+    d2, nearest, _ = mesh_closest_point(points, tg)
+    w = mesh_winding_number(points, tree, beta=beta)
+    level = torch.empty((R, R, R), device=dev, dtype=torch.float32)
+    face = torch.empty((R, R, R), device=dev, dtype=torch.int32)
+    _launch("tt_sdfgrid_finish", R, T, float(tau), float(sign_tau), ws, corner, d2, nearest, w, n_cand, level, face,
+            label="sdfgrid_finish")
+    d = d2.sqrt()
+    n_band, n_sign = (int(x) for x in torch.stack([(d < float(tau)).sum(), (d < float(sign_tau)).sum()]).cpu())
+    return level, {"lo": torch.from_numpy(lo.copy()).to(dev), "h": float(h), "tau": float(tau), "face": face,
+                   "band_corners": n_band, "sign_corners": n_sign, "candidates": n_cand}
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # ray casting (include/tt_abi.h, "ray casting"): closest hit, any hit, depth with a gradient, ambient occlusion
 def _chk_t_max(t_max, name: str = "t_max") -> float:
     try:
