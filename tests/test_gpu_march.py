@@ -1,11 +1,23 @@
 """The ray march alone (tt_march_fwd / tt_march_bwd, the nerfacc boundary: NeuS alpha -> render_weight_from_alpha ->
 accumulate_along_rays x5) against the oracle on given per-sample sdf / sdf_grad / features.  S covers every kernel
 variant: all passes of a ray held in registers (S <= 64, <= 128, <= 256) and the streaming form (S > 256), with
-ragged last passes.  Backward = autograd of the oracle in fp64 (tolerance: as close as the fp32 oracle, x4)."""
+ragged last passes.  Backward = autograd of the oracle in fp64 (tolerance: as close as the fp32 oracle, x4).
+
+The noise inputs of the first test make every ray opaque within a few dozen samples, so what the later passes compute
+-- and the two values that link the passes, the forward's running transmittance and the backward's reverse-scan carry --
+lies below its bars.  The `late` family (tests/march_reference.py) is there for that hand-over: one ray per crossing
+index, transparent up to a surface that sits on a pass seam (samples b-2 .. b+1 of every multiple b of 64, the second
+and the last two samples), so that every pass of every kernel form starts on a live ray and carries weight and gradient
+mass; tests/test_march_reference_host.py checks that on the CPU.  The `edges` family adds hand-built rays at the kinks:
+cos exactly 0 / -1 / +1, zero-length intervals, sdf == 0, a saturated sample, features +-100.  Both are compared element
+by element -- forward, backward rows and the per-ray d loss / d inv_std -- with bars measured per ray from the oracle's
+four fp32 evaluations; the forms are tied to each other bit for bit by the prefix property, and the optional upstream
+gradients and the g_sdf / g_sdf_grad pass-through are compared with their explicit forms."""
 import pytest
 import torch
 import torch.nn.functional as F
 
+import march_reference as M
 from oracle import cpu_ref as O
 
 pytestmark = pytest.mark.gpu
@@ -98,3 +110,107 @@ def test_march_equals_the_fused_forward():
     again = ops.march_forward_raw(rd, ts, te, full["sdf"], full["sdf_grad"], full["features"], rc)
     for k in again:
         assert torch.equal(again[k], full[k]), k
+
+
+# ------------------------------------------------------------------ the pass hand-over: late surfaces, element-wise bars
+G_NAMES = ("g_opacity", "g_depth", "g_rgb_fg", "g_z_variance", "g_normal_acc", "g_weights")
+
+
+def _subset(c, rays=None, S=None):
+    """The inputs and upstream gradients of case `c` for some of its rays and its first S samples (device tensors)."""
+    rays = torch.arange(c.n_rays) if rays is None else rays
+    S = c.S if S is None else S
+    per_sample = lambda t: t.reshape(c.n_rays, c.S, -1)[rays, :S].reshape(len(rays) * S, -1).contiguous().cuda()  # noqa: E731
+    x = c.x32
+    dev = [x[0][rays].contiguous().cuda(), x[1][rays, :S].contiguous().cuda(), x[2][rays, :S].contiguous().cuda(),
+           per_sample(x[3]), per_sample(x[4]), per_sample(x[5])]
+    ups = {"g_" + k: (per_sample(v) if k == "weights" else v[rays].contiguous().cuda()) for k, v in c.ups.items()}
+    return dev, ups
+
+
+def hip_march(c, rays=None, S=None, backward=True, **override):
+    """tt_march_fwd (+ tt_march_bwd with the case's upstream gradients; override: g_* = None / a tensor) on case `c`."""
+    from triplaneturbo_amd import ops
+    rc = ops.RenderConfig(inv_std=c.inv_std, cos_anneal_ratio=M.RATIO, use_volsdf=c.use_volsdf)
+    dev, ups = _subset(c, rays, S)
+    out = dict(ops.march_forward_raw(*dev, rc))
+    if backward:
+        gk = torch.zeros(dev[1].shape[0], device="cuda")
+        ups.update(override)
+        out["ws"] = ops.march_backward_raw(dev[0], dev[1], dev[2], out, dev[3], dev[4], dev[5], rc, g_inv_std_rays=gk, **ups)
+        out["gk"] = gk
+    torch.cuda.synchronize()
+    return {k: v.cpu() for k, v in out.items()}
+
+
+def check_case(c):
+    """Every element of the forward, the backward rows and g_inv_std_rays within its allowance: all rays in one launch
+    (the ray count of a family is what it is: 5, 9, 13, 17 rays leave a block of the grid ragged), then one ray alone."""
+    got = hip_march(c)
+    for key in M.FWD_KEYS + ("ws", "gk"):
+        c.check(key, got[key])
+    if c.use_volsdf and c.inv_std > 80.0:
+        assert not got["gk"].any() and not c.ref64["gk"].any()  # above the clamp: exactly 0
+    one = torch.tensor([c.n_rays // 2])
+    alone = hip_march(c, rays=one)
+    for key in M.FWD_KEYS + ("ws", "gk"):
+        c.check(key, alone[key], rays=one, tag="hip, 1 ray")
+        rows = one if key in M.RAY_KEYS + ("gk",) else torch.arange(c.S) + int(one) * c.S
+        assert torch.equal(alone[key].reshape(len(rows), -1), got[key].reshape(-1, alone[key].numel() // len(rows))[rows]), key
+
+
+@pytest.mark.parametrize("S", M.S_LIST)
+def test_march_late_surfaces_meet_the_elementwise_allowance(S):
+    check_case(M.case("late", S))
+
+
+@pytest.mark.parametrize("S", M.EDGE_S)
+def test_march_edge_rays_meet_the_allowance_and_saturate_exactly(S):
+    c = M.case("edges", S)
+    check_case(c)
+    got = hip_march(c)
+    ray = M.EDGE_RAYS.index("saturated")
+    after = slice(c.sat + 1, None)
+    T, w = got["trans"].reshape(c.n_rays, S)[ray], got["weights"].reshape(c.n_rays, S)[ray]
+    assert T[c.sat] > 0.99 and w[c.sat] == T[c.sat]  # alpha clipped to exactly 1 on a live ray
+    assert (T[after] == 0).all() and (w[after] == 0).all()
+    assert (got["ws"].reshape(c.n_rays, S, 4)[ray, after] == 0).all()
+
+
+def test_march_prefix_of_a_ray_is_bit_identical_in_every_form():
+    """The forward's data moves only from lower lanes and earlier passes, so the first S' samples of a ray march to the
+    same weights and transmittances whatever follows them -- whichever kernel form S' selects.  This ties the three
+    register forms and the streaming form to each other at every seam."""
+    c = M.case("late", 300)
+    full = hip_march(c, backward=False)
+    for Sp in M.PREFIX_S:
+        part = hip_march(c, S=Sp, backward=False)
+        for key in ("weights", "trans"):
+            want = full[key].reshape(c.n_rays, c.S)[:, :Sp]
+            got = part[key].reshape(c.n_rays, Sp)
+            diff = (got != want).nonzero()
+            assert diff.numel() == 0, (key, Sp, M.form_of(Sp), "first differing (ray, sample)", diff[0].tolist(),
+                                       float(got[tuple(diff[0])]), float(want[tuple(diff[0])]))
+
+
+@pytest.mark.parametrize("S", [129, 300])
+def test_march_optional_upstream_gradients_and_pass_through(S):
+    """Each upstream gradient given as None equals the run with a zero tensor bit for bit, and g_sdf / g_sdf_grad pass
+    through the march boundary as one fp32 add on top of the rows computed without them."""
+    c = M.case("late", S)
+    _, ups = _subset(c)
+    g = torch.Generator().manual_seed(11)
+    extra = {"g_sdf": torch.randn(c.n_rays * S, 1, generator=g).cuda(),
+             "g_sdf_grad": torch.randn(c.n_rays * S, 3, generator=g).cuda()}
+    base = hip_march(c, **extra)
+    for name in G_NAMES + ("g_sdf", "g_sdf_grad"):
+        like = ups.get(name, extra.get(name))
+        none = hip_march(c, **{**extra, name: None})
+        zero = hip_march(c, **{**extra, name: torch.zeros_like(like)})
+        for key in ("ws", "gk"):
+            assert torch.equal(none[key], zero[key]), (name, key)
+        assert not torch.equal(none["ws"], base["ws"]), name  # the gradient does reach the rows
+    without = hip_march(c)
+    assert torch.equal(without["ws"], hip_march(c, g_sdf=None, g_sdf_grad=None)["ws"])
+    assert torch.equal(base["ws"], without["ws"] + torch.cat([extra["g_sdf"], extra["g_sdf_grad"]], dim=1).cpu())
+    assert torch.equal(base["gk"], without["gk"])

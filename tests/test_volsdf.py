@@ -13,6 +13,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import march_reference as M
 from oracle import cpu_ref as O
 from parity import PRECISIONS, check_grads
 
@@ -177,6 +178,19 @@ def test_hip_volsdf_march_forward_backward_and_inv_std_gradient(S, inv_std):
     else:
         assert abs(gk_sum - g64[2].item()) <= max(1e-4, 3 * abs(g32[2].item() - g64[2].item()) / abs(g64[2].item())) * abs(
             g64[2].item())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("S,inv_std", [(S, None) for S in M.S_LIST] + [M.VOLSDF_ABOVE_CLAMP])
+def test_hip_volsdf_march_late_surfaces_meet_the_elementwise_allowance(S, inv_std):
+    """The `late` family of tests/march_reference.py (a live ray at the start of every 64-sample pass) under TT_R_VOLSDF:
+    forward, backward rows and the per-ray d loss / d inv_std element by element, against float64, with bars measured per
+    ray from the oracle's four fp32 evaluations; inv_std per S from M.VOLSDF_INV_STD, inside the clamp, plus one case
+    above it (d / d inv_std exactly 0)."""
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    from test_gpu_march import check_case
+    check_case(M.case("late", S, True, inv_std))
 
 
 @pytest.mark.gpu
